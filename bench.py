@@ -8,15 +8,19 @@ YCbCr8 output (the reference benchmark's sink, tests/JpegLibrary.Benchmarks/Deco
 compressed bytes already resident in HBM and the pixels left resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--images M] [--workload 4k_dri4|4k_dri0|1080p_q90|512_444|...]
+                    [--full] [--dump-outputs DIR]
 
 For N > 1 the driver launches it under torch.distributed.run (one rank per GPU); images shard one-per-GPU
 (embarrassingly parallel: no data-path collective), scaling is weak (per-GPU batch fixed).  Started WITHOUT torchrun with
 --gpus N > 1 it launches those ranks itself (a child `python -m torch.distributed.run ... bench.py`, started before this
 process touches a GPU) and relays their line; --multi-inprocess adds the same shard through the library's own in-process
 driver (jpgpu_multi_*: one process, a context per device).
-Prints ONE JSON line on rank 0.  On the default workload that line also carries `configs`: short passes of the other
-BASELINE.json configurations (512_444, 4k_dri0, 1080p_q90, 4k_progressive, het_8192) run AFTER the headline's timed region,
-each with its own stage times, K3 roofline fraction and oracle spot check; they never change `value`.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs DIR is given, and prints that line.  Everything else is measured only under --full: the CPU baseline, the
+ingest-inclusive rates, the planar-sink pass, the D2H rate, the oracle spot check, the single-image latency (het_8192), two
+batches in flight (progressive workloads) and, on the default workload, `configs`: short passes of the other BASELINE.json
+configurations (512_444, 4k_dri0, 1080p_q90, 4k_progressive, het_8192) run AFTER the headline's timed region, each with its
+own stage times, K3 roofline fraction and oracle spot check; none of them changes `value`.
 """
 import argparse
 import ctypes as C
@@ -490,8 +494,15 @@ def spawn_ranks(args):
     touched a GPU (a process that has must not be replaced or re-executed); its one line is relayed."""
     import subprocess
 
+    argv, skip = [], False
+    for a in sys.argv[1:]:  # (--dump-outputs is passed on as an absolute path: the ranks run from the repository root)
+        if not skip and a != "--multi-inprocess" and a != "--dump-outputs" and not a.startswith("--dump-outputs="):
+            argv.append(a)
+        skip = a == "--dump-outputs" and not skip
+    if args.dump_outputs:
+        argv += ["--dump-outputs", args.dump_outputs]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.abspath(__file__)] + [a for a in sys.argv[1:] if a != "--multi-inprocess"]
+           "--master-port", str(free_port()), os.path.abspath(__file__)] + argv
     log(f"[bench] --gpus {args.gpus} without WORLD_SIZE: launching {' '.join(cmd[1:8])} ...")
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -580,6 +591,44 @@ def library_sha256():
     return h.hexdigest()
 
 
+DUMP_IMAGES = 32  # images whose outputs --dump-outputs writes: the first, the last and the rest drawn with a fixed seed
+DUMP_SAMPLES = 1 << 18  # output samples per image, at positions drawn with a fixed seed (32 x 2^18 float32 = 32 MB)
+DUMP_SEED = 20250601
+
+
+def dump_outputs(batch, n_images, out_dir):
+    """--dump-outputs DIR: what the timed path left in HBM after its last step, as a caller of the batch receives it, in float32 /
+    float64 .npy files -- status.npy (every image's status), and for a fixed, seeded sample of the images sample_images.npy (their
+    indices), image_sums.npy (the sum of ALL of each one's output samples) and pixels.npy (each one's samples at fixed, seeded
+    fractions of its flattened output).  Inputs and sample are the same from run to run for the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    status = np.array([batch.result(i).status for i in range(n_images)], np.float64)
+    if n_images <= DUMP_IMAGES:
+        idx = np.arange(n_images)
+    else:
+        idx = np.sort(np.concatenate([[0, n_images - 1], 1 + rng.permutation(n_images - 2)[:DUMP_IMAGES - 2]]))
+    frac = np.sort(rng.random(DUMP_SAMPLES))
+    sums = np.full(len(idx), np.nan)
+    pixels = None
+    for row, i in enumerate(idx):
+        if status[i] != 0:
+            continue
+        o = batch.output(int(i))
+        flat = np.concatenate([p.ravel() for p in o]) if isinstance(o, list) else o.ravel()
+        # (every image of a workload has the same shape: an output smaller than the sample is written whole)
+        vals = flat if flat.size <= DUMP_SAMPLES else flat[(frac * flat.size).astype(np.int64)]
+        if pixels is None:
+            pixels = np.full((len(idx), vals.size), np.nan, np.float32)
+        n = min(vals.size, pixels.shape[1])
+        pixels[row, :n] = vals[:n]
+        sums[row] = flat.sum(dtype=np.float64)
+    np.save(os.path.join(out_dir, "status.npy"), status)
+    np.save(os.path.join(out_dir, "sample_images.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "image_sums.npy"), sums)
+    np.save(os.path.join(out_dir, "pixels.npy"), pixels if pixels is not None else np.full((len(idx), 0), np.nan, np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -589,10 +638,15 @@ def main():
     ap.add_argument("--workload", default="4k_dri4", choices=sorted(WORKLOADS))
     ap.add_argument("--format", default=None, choices=["interleaved_u8", "planar_u8", "rgb_u8", "rgba_u8"],
                     help="output layout (default: interleaved_u8; het_8192: rgba_u8, the reference benchmark's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the ingest-inclusive (upload beside decode) measurement")
-    ap.add_argument("--no-planar-pass", action="store_true", help="skip the short PLANAR_U8 pass behind roofline.read_frac_planar")
-    ap.add_argument("--latency", action="store_true", help="also time one image per call (always on for het_8192)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: CPU baseline, ingest-inclusive "
+                                                         "rates, planar-sink pass, D2H rate, oracle spot check, het_8192's single-image latency, "
+                                                         "two batches in flight (progressive) and the default workload's `configs`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed (per-image "
+                                                                         "status + a fixed, seeded sample of the outputs) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-ingest", action="store_true", help="--full: skip the ingest-inclusive (upload beside decode) measurement")
+    ap.add_argument("--no-planar-pass", action="store_true", help="--full: skip the short PLANAR_U8 pass behind roofline.read_frac_planar")
+    ap.add_argument("--latency", action="store_true", help="also time one image per call (always on for het_8192 under --full)")
     ap.add_argument("--latency-only", action="store_true", help="print the one-image-per-call table (configs.latency of the default line) and exit")
     ap.add_argument("--gen-threads", type=int, default=0)
     ap.add_argument("--dist", action="store_true", help="initialise torch.distributed (RCCL) even for a single rank: runs the barrier / "
@@ -602,7 +656,7 @@ def main():
                          "than ranks -- rank r uses device r mod (devices present), barriers and the MAX-reduce run on the host group; "
                          "everything else (input generation at granted // world threads, crews, the parked CPU baseline, the slowest-rank "
                          "ingest figures, the JSON line) is the code path of the real launch.  Its `value` is NOT a scaling point: the ranks share a device")
-    ap.add_argument("--no-configs", action="store_true", help="default workload: skip the short passes of the other BASELINE.json configurations")
+    ap.add_argument("--no-configs", action="store_true", help="--full, default workload: skip the short passes of the other BASELINE.json configurations")
     ap.add_argument("--config-scale", type=int, default=1, help="tests: the extra configurations at 1/N of their batch sizes")
     ap.add_argument("--multi-inprocess", action="store_true", help="also run the shard through jpgpu_multi_* (one process, a context per device) "
                                                                      "and report it as value_multi_inprocess")
@@ -611,6 +665,10 @@ def main():
     ap.add_argument("--distinct", type=int, default=0, help="experiments only: synthesise this many distinct images and repeat them "
                                                             "to fill the batch (default: every image of the batch is distinct)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)  # (does not return; nothing has touched a GPU yet)
     if args.format is None:
@@ -737,11 +795,13 @@ def main():
     if dist is not None:
         elapsed = sharding.max_over_ranks(dist, elapsed, device=reduce_device)
     value = sharding.aggregate_throughput(n_images * width * height, n_gpus, args.steps, elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batch, n_images, args.dump_outputs)
 
     # ---- single-image latency (the reference benchmark decodes ONE image per call): decode alone with the file resident in
     # HBM; SetInput + Identify + Decode from host memory; and the same with the pixels copied back to the host
     latency = None
-    if rank == 0 and (args.workload == "het_8192" or args.latency):
+    if rank == 0 and ((args.full and args.workload == "het_8192") or args.latency):
         one = jl.Batch(ctx)
         one.upload(files[:1], fmt)
         one.decode().sync()
@@ -777,7 +837,7 @@ def main():
     # Two batches in flight (two contexts = two streams, inputs of both resident) is what a caller who has more than one
     # batch does about it; reported beside `value`, never as `value`
     two_in_flight = None
-    if rank == 0 and args.workload in ("4k_progressive", "het_progressive") and not os.environ.get("JPGPU_PROG_BY_SCAN"):  # (not under the per-scan profiling switch)
+    if args.full and rank == 0 and args.workload in ("4k_progressive", "het_progressive") and not os.environ.get("JPGPU_PROG_BY_SCAN"):  # (not under the per-scan profiling switch)
         try:
             ctx2 = jl.Context(local_rank)
             other = jl.Batch(ctx2).upload(files, fmt)
@@ -805,7 +865,7 @@ def main():
     # every rank at once (the ranks' crews share the host), the slowest rank's time per batch; from pageable memory through
     # the staging ring, and from page-locked memory by DMA (zero-copy)
     ingest_res = {}
-    if not args.no_ingest:
+    if args.full and not args.no_ingest:
         rounds = max(4, min(args.steps, 8))
         for key in ("pageable", "pinned"):
             per_batch_s, st, err = float("inf"), None, None
@@ -843,7 +903,7 @@ def main():
     # of `value`).  One GPU: all five on this rank.  N > 1: config 4 (8192 x 1080p Q90 over 8 GPUs = 1024 per rank) on every
     # rank, sharded and reduced like the headline.  Bounded: a configuration that would start beyond the time budget is skipped.
     configs = None
-    if args.workload == "4k_dri4" and args.format == "interleaved_u8" and not args.no_configs and not (args.images and args.images < 64):
+    if args.full and args.workload == "4k_dri4" and args.format == "interleaved_u8" and not args.no_configs and not (args.images and args.images < 64):
         configs = {}
         t_cfg = time.perf_counter()
         names = ["512_444", "4k_dri0", "1080p_q90", "4k_progressive", "het_8192"] if world == 1 else ["1080p_q90"]
@@ -972,7 +1032,7 @@ def main():
                                                     "staging ring; pinned: the files lie in page-locked memory and are DMA'd from there")
         # north_star's literal bar -- the IDCT stage's share of the HBM READ bandwidth -- is defined on the planar sink
         # (192 B per block): a short pass of the same batch with PLANAR_U8 output, K3 timed by HIP events
-        if args.format == "interleaved_u8" and not args.no_planar_pass:
+        if args.full and args.format == "interleaved_u8" and not args.no_planar_pass:
             try:
                 pb = jl.Batch(ctx).upload(files, jl.FMT_PLANAR_U8)
                 for _ in range(2):
@@ -991,24 +1051,25 @@ def main():
             except Exception as e:  # pragma: no cover
                 out["roofline"]["read_frac_planar"] = None
                 out["roofline"]["planar_pass_error"] = str(e)[:120]
-        # D2H of the pixels: reported, never part of `value`; a bounded sample of the images, pageable host memory
-        try:
-            n_d2h = min(n_images, 16)
-            t_d = time.perf_counter()
-            nbytes = 0
-            for i in range(n_d2h):
-                o = batch.output(i)
-                nbytes += sum(p.nbytes for p in o) if isinstance(o, list) else o.nbytes
-            t_d = time.perf_counter() - t_d
-            out["host"]["d2h_GBps"] = round(nbytes / t_d / 1e9, 2)
-            out["host"]["d2h_sample"] = f"{n_d2h} images, {nbytes / 1e6:.0f} MB"
-        except Exception as e:  # pragma: no cover
-            out["host"]["d2h_GBps"] = None
-            out["host"]["d2h_error"] = str(e)[:80]
-        # spot check after timing: a few images bit-exact against the oracle (checker only)
-        if os.environ.get("JPGPU_BENCH_EXPERIMENT"):  # kernel-timing experiments with deliberately broken outputs
+        # D2H of the pixels (--full): reported, never part of `value`; a bounded sample of the images, pageable host memory
+        if args.full:
+            try:
+                n_d2h = min(n_images, 16)
+                t_d = time.perf_counter()
+                nbytes = 0
+                for i in range(n_d2h):
+                    o = batch.output(i)
+                    nbytes += sum(p.nbytes for p in o) if isinstance(o, list) else o.nbytes
+                t_d = time.perf_counter() - t_d
+                out["host"]["d2h_GBps"] = round(nbytes / t_d / 1e9, 2)
+                out["host"]["d2h_sample"] = f"{n_d2h} images, {nbytes / 1e6:.0f} MB"
+            except Exception as e:  # pragma: no cover
+                out["host"]["d2h_GBps"] = None
+                out["host"]["d2h_error"] = str(e)[:80]
+        # spot check after timing (--full): a few images bit-exact against the oracle (checker only)
+        if args.full and os.environ.get("JPGPU_BENCH_EXPERIMENT"):  # kernel-timing experiments with deliberately broken outputs
             out["parity_spot_check"] = "oracle unavailable"
-        else:
+        elif args.full:
             out["parity_spot_check"] = spot_check(jl, batch, files, fmt, sorted(set([0, n_images // 2, n_images - 1])))
         if configs is not None:
             out["configs"] = configs
@@ -1020,7 +1081,7 @@ def main():
             except Exception as e:  # pragma: no cover
                 out["multi_inprocess"] = {"value": None, "error": str(e)[:200]}
         # rank 0 alone, the other ranks parked in the host-side barrier below (blocked in a socket read, not spinning)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             big = width * height > 32e6  # 67-Mpixel frames: two decodes per thread, no more threads than CPUs granted (0.5 GB of buffers each)
             out["cpu_baseline"] = cpu_baseline(files, width, height, cpu, rgba=(args.format == "rgba_u8"), per_thread=2 if big else 8,
                                                thread_cap=granted if big else 0)

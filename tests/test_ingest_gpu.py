@@ -260,7 +260,7 @@ def test_bench_runs_its_rccl_path_under_torchrun_with_one_rank():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(root, "bench.py"), "--gpus", "1", "--dist", "--workload", "1080p_q90", "--images", "8", "--steps", "2", "--warmup", "1"]
+           os.path.join(root, "bench.py"), "--gpus", "1", "--dist", "--workload", "1080p_q90", "--images", "8", "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -285,7 +285,8 @@ def test_bench_rehearses_a_two_rank_launch_on_one_device():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--workload", "1080p_q90", "--images", "8", "--steps", "2", "--warmup", "1"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--workload", "1080p_q90", "--images", "8", "--steps", "2", "--warmup", "1",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -311,7 +312,7 @@ def test_bench_line_carries_every_baseline_config_and_the_in_process_driver():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--images", "64", "--steps", "2", "--warmup", "1", "--config-scale", "64",
-                        "--no-ingest", "--multi-inprocess"], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
+                        "--no-ingest", "--multi-inprocess", "--full"], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["value"] > 0 and out["parity_spot_check"] == "bit-exact vs oracle"

@@ -8,7 +8,7 @@ for flags in -DJPGPU_K2_TICKET_AHEAD none -DJPGPU_K2_TICKET_AHEAD none; do
   bash tools/trace/ab_build.sh "$flags" python3 - <<'PY'
 import json, subprocess, sys
 for w, extra in (("4k_dri4", ["--steps", "20", "--warmup", "3"]), ("1080p_q90", ["--steps", "20", "--warmup", "3"]), ("4k_dri0", ["--steps", "8", "--warmup", "2"]), ("het_8192", ["--steps", "5", "--warmup", "2"])):
-    out = subprocess.run([sys.executable, "bench.py", "--workload", w, "--no-cpu-baseline", "--no-ingest", "--no-configs", "--no-planar-pass"] + extra,
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--workload", w, "--no-cpu-baseline", "--no-ingest", "--no-configs", "--no-planar-pass"] + extra,
                          capture_output=True, text=True)
     try:
         d = json.loads(out.stdout.strip().splitlines()[-1])

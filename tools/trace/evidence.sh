@@ -10,9 +10,9 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 run() {  # name, bench args...
   local name=$1; shift
-  python3 $R/bench.py "$@" --no-cpu-baseline --no-ingest > $OUT/bench_$name.json 2> $OUT/bench_$name.err
+  python3 $R/bench.py --full "$@" --no-cpu-baseline --no-ingest > $OUT/bench_$name.json 2> $OUT/bench_$name.err
   rm -rf /tmp/ev_$name
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ev_$name -- python3 $R/bench.py "$@" --steps 5 --warmup 2 --no-cpu-baseline --no-ingest > $OUT/prof_$name.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ev_$name -- python3 $R/bench.py --full "$@" --steps 5 --warmup 2 --no-cpu-baseline --no-ingest > $OUT/prof_$name.log 2>&1
   f=$(find /tmp/ev_$name -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $OUT/kernel_stats_$name.csv
   echo "== $name"; cut -c1-400 $OUT/bench_$name.json; [ -n "$f" ] && head -8 $f | cut -c1-160

@@ -6,18 +6,21 @@
 #                                                             RESTED box (K3 drifts from 9.25 to 9.8-10 ms on a box that has
 #                                                             been under load for minutes), after idct_traffic.json is in place
 # Outputs under gpurun_out/ (pmc_$TAG/, all_$TAG/, ${TAG}_headline/); copy into profiles/ as ${TAG}_* (TAG from the environment).
+# The bench.py --full lines go to $BENCH_OUT (default: bench_out/$TAG in the tree).
 set -u
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${TAG:-r03a}
 cd $R
+BENCH_OUT=${BENCH_OUT:-$PWD/bench_out/$TAG}
+mkdir -p "$BENCH_OUT"
 if [ "${1:-}" = "headline" ]; then
   mkdir -p gpurun_out/${TAG}_headline
   ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/ks && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-ingest --no-configs > /tmp/ks.log 2>&1; cp $(find /tmp/ks -name "*kernel_stats.csv" | head -1) $R/gpurun_out/${TAG}_headline/kernel_stats_1024img.csv )
-  python3 bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_headline/bench.json 2>/dev/null
-  cut -c1-200 gpurun_out/${TAG}_headline/bench.json
+  python3 bench.py --full --steps 20 --warmup 5 > "$BENCH_OUT/bench.json" 2>/dev/null
+  cut -c1-200 "$BENCH_OUT/bench.json"
   # the reference's own benchmark input (DecoderBenchmark.cs): line + kernel statistics
-  python3 bench.py --workload het_8192 --steps 5 --warmup 2 > gpurun_out/${TAG}_headline/bench_het_8192.json 2>/dev/null
-  cut -c1-200 gpurun_out/${TAG}_headline/bench_het_8192.json
+  python3 bench.py --full --workload het_8192 --steps 5 --warmup 2 > "$BENCH_OUT/bench_het_8192.json" 2>/dev/null
+  cut -c1-200 "$BENCH_OUT/bench_het_8192.json"
   ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/kh && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kh -- python3 $R/bench.py --workload het_8192 --steps 5 --warmup 2 --no-cpu-baseline --no-ingest > /tmp/kh.log 2>&1; cp $(find /tmp/kh -name "*kernel_stats.csv" | head -1) $R/gpurun_out/${TAG}_headline/kernel_stats_het_8192.csv )
   # random corpora through every GPU path against the checker (decode incl. failing writers / partial flushes / per-scan sessions,
   # optimizer, encoder): ONE summary, 3 seeds x 1500 files per corpus switch (tools/trace/round_stress.sh)
@@ -37,7 +40,7 @@ python3 tools/trace/multi_slots.py 256 3 $R/gpurun_out/all_$TAG/multi_slots.json
 bash tools/trace/encoder_pmc.sh ${TAG}enc --images 64 > /dev/null 2>&1; cp gpurun_out/pmc_${TAG}enc/summary.txt gpurun_out/all_$TAG/encoder_pmc_summary_64img.txt
 timeout 600 bash tools/trace/progressive_pmc.sh 64 $R/gpurun_out/all_$TAG/progressive_pmc_64.txt > /dev/null 2>&1
 # round 5: config 5 on real content, the reference's encoder benchmark, one canvas's kernel timeline, the config-3 A/B
-python3 bench.py --workload het_progressive --steps 3 --warmup 1 --no-ingest > gpurun_out/all_$TAG/bench_het_progressive.json 2>/dev/null
+python3 bench.py --full --workload het_progressive --steps 3 --warmup 1 --no-ingest > "$BENCH_OUT/bench_het_progressive.json" 2>/dev/null
 bash tools/trace/progressive_by_scan.sh 256 $R/gpurun_out/all_$TAG/progressive_by_scan_256_het.txt het_progressive > /dev/null 2>&1
 for a in "420" "444"; do python3 tools/bench_encode.py --workload het_8192 --subsampling $a > gpurun_out/all_$TAG/bench_encode_het_8192_$a.json 2>/dev/null; done
 python3 tools/bench_encode.py --workload het_8192 --subsampling 420 --optimize-coding > gpurun_out/all_$TAG/bench_encode_het_8192_420_optimize.json 2>/dev/null
