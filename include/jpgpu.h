@@ -236,6 +236,24 @@ typedef struct jpgpu_ingest_stats {
     int32_t n_linearised;   /* multi-segment files the host had to gather as a whole (full marker walks) */
 } jpgpu_ingest_stats;
 int jpgpu_batch_ingest_stats(const jpgpu_batch *b, jpgpu_ingest_stats *stats);
+/* How the last upload planned the entropy stage of its sequential scans (read only; for tests and tools).  K2 = scans with
+ * restart intervals: workgroups of the plain list, and runs of adjacent scans with the same tables and geometry POOLED into
+ * chunks of 64 intervals (at most 8 pools).  K2S = scans without restart intervals: the final pass's plain list and its pools
+ * (at most 8), and the distinct table sets among those scans. */
+typedef struct jpgpu_plan_stats {
+    int32_t k2_plain_work;      /* entries (workgroups) of K2's plain list */
+    int32_t k2_pools;           /* pooled runs of K2 */
+    int32_t k2_pooled_chunks;   /* chunks of 64 restart intervals over all K2 pools */
+    int32_t huffman_waves;      /* waves per K2 workgroup (what the batch's largest table set leaves room for) */
+    int32_t k2s_scans;          /* scans decoded by K2S */
+    int32_t k2s_plain_work;     /* entries of the K2S final pass's plain list */
+    int32_t k2s_pools;          /* pooled runs of the K2S final pass */
+    int32_t k2s_table_sets;     /* distinct table sets among the K2S scans */
+    int32_t k2s_subs_per_lane;  /* subsequences a lane of the K2S final pass takes */
+} jpgpu_plan_stats;
+/* sizeof(jpgpu_plan_stats) as THIS library writes it. */
+size_t jpgpu_sizeof_plan_stats(void);
+int jpgpu_batch_plan_stats(const jpgpu_batch *b, jpgpu_plan_stats *stats);
 
 /* Coefficient hand-off for multi-scan (progressive, SOF2) images -- BASELINE config 5's "coefficient accumulate then single
  * IDCT pass": the caller's progressive entropy decoder accumulates the coefficient store, the GPU runs what
@@ -279,7 +297,11 @@ void *jpgpu_batch_coefficients_device(const jpgpu_batch *b, uint64_t *total_bloc
 /* Copies one image's output / coefficient blocks (int16[blocks][64], zig-zag order, MCU scan order) to the host.  (A progressive
  * frame whose Dispose() is taken literally -- component slots that do not cover every component once, the partial flush of a
  * failed file -- is transformed IN its store: behind the output stage its "coefficients" are samples; the pass runs once per
- * entropy stage, a second jpgpu_batch_run_idct / jpgpu_progressive_dispose flushes the same samples again.) */
+ * entropy stage, a second jpgpu_batch_run_idct / jpgpu_progressive_dispose flushes the same samples again.)
+ * A multi-scan baseline image whose plan did not hold -- a middle scan leaves one byte unread in front of its terminating
+ * marker, and the file is planned again and decoded on its own -- has its output and result from that re-plan after every
+ * stage call; its coefficients are refused with JPGPU_ERR_NOT_SUPPORTED (the batch's store holds what the first plan's scans
+ * made of the file). */
 int jpgpu_batch_download_output(jpgpu_batch *b, int i, void *dst, size_t cap);
 int jpgpu_batch_download_coefficients(jpgpu_batch *b, int i, int16_t *dst, size_t cap_blocks);
 /* Overwrites one image's coefficient blocks from the host (IDCT-stage parity tests; config-5 style accumulate-then-IDCT). */

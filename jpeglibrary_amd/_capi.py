@@ -67,6 +67,12 @@ class IngestStats(C.Structure):
                 ("n_pinned_dma", C.c_int32), ("n_linearised", C.c_int32)]
 
 
+class PlanStats(C.Structure):
+    _fields_ = [("k2_plain_work", C.c_int32), ("k2_pools", C.c_int32), ("k2_pooled_chunks", C.c_int32), ("huffman_waves", C.c_int32),
+                ("k2s_scans", C.c_int32), ("k2s_plain_work", C.c_int32), ("k2s_pools", C.c_int32), ("k2s_table_sets", C.c_int32),
+                ("k2s_subs_per_lane", C.c_int32)]
+
+
 class Segment(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t)]
 
@@ -105,6 +111,8 @@ SYMBOLS = [
     ("jpgpu_multi_batch", _P, [_P, C.c_int]),
     ("jpgpu_multi_context", _P, [_P, C.c_int]),
     ("jpgpu_batch_ingest_stats", C.c_int, [_P, C.POINTER(IngestStats)]),
+    ("jpgpu_sizeof_plan_stats", C.c_size_t, []),
+    ("jpgpu_batch_plan_stats", C.c_int, [_P, C.POINTER(PlanStats)]),
     ("jpgpu_batch_progressive_fallbacks", C.c_int, [_P]),
     ("jpgpu_status_string", C.c_char_p, [C.c_int]),
     ("jpgpu_detail_string", C.c_char_p, [C.c_int]),
@@ -240,6 +248,9 @@ def _load():
     if lib.jpgpu_version() < 101 or lib.jpgpu_sizeof_image_result() != C.sizeof(ImageResult):
         raise ImportError(f"{LIB_PATH} (version {lib.jpgpu_version()}, jpgpu_image_result of {lib.jpgpu_sizeof_image_result()} bytes) does not "
                           f"match this binding (101, {C.sizeof(ImageResult)} bytes): rebuild it")
+    if lib.jpgpu_sizeof_plan_stats() != C.sizeof(PlanStats):
+        raise ImportError(f"{LIB_PATH} (jpgpu_plan_stats of {lib.jpgpu_sizeof_plan_stats()} bytes) does not match this binding "
+                          f"({C.sizeof(PlanStats)} bytes): rebuild it")
     return lib
 
 

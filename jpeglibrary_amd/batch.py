@@ -130,6 +130,12 @@ class Batch:
         self._check(_lib.jpgpu_batch_ingest_stats(self._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in _capi.IngestStats._fields_}
 
+    def plan_stats(self):
+        """How the last upload() planned the entropy stage: K2's plain list and pools, K2S's final-pass list, pools and table sets."""
+        st = _capi.PlanStats()
+        self._check(_lib.jpgpu_batch_plan_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in _capi.PlanStats._fields_}
+
     def progressive_fallbacks(self):
         """Times the single-launch progressive path timed out and the step was re-issued level by level."""
         return _lib.jpgpu_batch_progressive_fallbacks(self._h)

@@ -465,6 +465,12 @@ int jpgpu_batch_ingest_stats(const jpgpu_batch *b, jpgpu_ingest_stats *stats) {
     stats->n_linearised = s.n_linearised;
     return JPGPU_OK;
 }
+size_t jpgpu_sizeof_plan_stats(void) { return sizeof(jpgpu_plan_stats); }
+int jpgpu_batch_plan_stats(const jpgpu_batch *b, jpgpu_plan_stats *stats) {
+    if (!b || !stats) return JPGPU_ERR_ARGUMENT;
+    b->impl.plan_stats(stats);
+    return JPGPU_OK;
+}
 int jpgpu_batch_totals(const jpgpu_batch *b, uint64_t *compressed_bytes, uint64_t *blocks, uint64_t *pixels, uint64_t *output_bytes) {
     if (!b) return JPGPU_ERR_ARGUMENT;
     b->impl.totals(compressed_bytes, blocks, pixels, output_bytes);

@@ -101,6 +101,7 @@ class WorkCrew;
 class DeviceBatch {
   public:
     const IngestStats &ingest_stats() const { return ingest_; }
+    void plan_stats(jpgpu_plan_stats *st) const;  // jpgpu_batch_plan_stats: the entropy stage's work lists and pools
     explicit DeviceBatch(jpgpu_ctx *ctx) : ctx_(ctx) {}
     ~DeviceBatch();
 
@@ -276,6 +277,7 @@ class DeviceBatch {
     int k1_fallbacks_ = 0;
     bool sub_same_valid_ = false;  // d_sub_same_ holds the twins of this upload's subsequences (subseq_same_kernel)
     int n_sub_work_ = 0, n_sub_gather_ = 0, n_sub_scans_ = 0, n_sub_final_work_ = 0, sub_final_spl_ = 2;
+    int n_sr_sets_ = 0;  // distinct table sets among the DRI = 0 scans (the K2S round kernel's lookups)
     DevBuffer d_sub_final_work_;
     std::vector<SubseqPool> sub_pools_;  // pooled runs of the final pass: entries of d_sub_final_work_ behind the first n_sub_final_work_
     uint32_t total_subs_ = 0, max_subs_per_scan_ = 0;

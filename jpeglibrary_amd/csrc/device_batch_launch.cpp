@@ -19,6 +19,7 @@ namespace jpgpu {
 
 int DeviceBatch::run_marker_index() {
     status_valid_ = false;
+    redo_.clear();  // (every stage that rewrites coefficients or samples: a re-planned image's output is this plan's again behind it)
     if (k1_onepass_) {
         // one pass with a decoupled look-back (k1_markers.hip: groups of four chunks, handed out scan-interleaved, classified once);
         // a group that runs out of patience counts its predecessors itself and says so in *h_k1_giveup_ (a count for the tests)
@@ -42,6 +43,7 @@ int DeviceBatch::run_marker_index() {
 }
 int DeviceBatch::run_huffman() {
     status_valid_ = false;
+    redo_.clear();
     dispose_done_ = false;  // (the stores hold coefficients again)
     hipError_t e = launch_huffman(ctx_->stream, (const uint8_t *)d_unstuffed_.ptr, (const DevScan *)d_scans_.ptr, (const HuffWork *)d_huff_work_.ptr,
                                   n_huff_work_, (const uint32_t *)d_ends_u_.ptr, (DevScanStatus *)d_status_.ptr,
@@ -242,6 +244,7 @@ int DeviceBatch::run_dispose_passes(hipStream_t stream) {
 }
 
 int DeviceBatch::run_idct() {
+    redo_.clear();  // (K3 writes this plan's samples over what a re-plan copied in: result() / download_output() plan again)
     if (k2s_unchecked_) k2s_idct_behind_ = true;
     const YccRgbFactors kf = ycc_rgb_factors();
     int rc0 = clear_partial_outputs();
@@ -350,7 +353,7 @@ int DeviceBatch::decode() {
         }
     }
     hipEvent_t *ev = &ev_pool_[ev_used_];
-    redo_.clear();  // (a re-planned image's output is this batch's own plan's again behind this decode)
+    redo_.clear();  // (a re-planned image's output is this batch's own plan's again behind this decode; so behind every stage)
     in_decode_request_ = true;
     const bool serial = !overlap_ok_ || (decodes_since_query_ % kSerialEvery) == 0;
     decodes_since_query_++;

@@ -517,6 +517,7 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
         if (k == sr_set_scan.size()) sr_set_scan.push_back(j);
         h_scans_[j].sr_set = k;
     }
+    n_sr_sets_ = (int)sr_set_scan.size();
     n_chunk_work_ = (int)chunk_work.size();
     std::stable_sort(k1_order.begin(), k1_order.end(), [](const ChunkWork &a, const ChunkWork &b) { return a.chunk < b.chunk; });
     n_k1_groups_ = (int)k1_order.size();

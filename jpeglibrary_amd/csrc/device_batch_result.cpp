@@ -303,6 +303,18 @@ int DeviceBatch::download_coefficients(int i, int16_t *dst, size_t cap_blocks) {
     if (!img || !dst) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_download_coefficients: bad argument");
     if (img->status != JPGPU_OK) return fail(img->status, img->error);
     if (cap_blocks < img->total_blocks) return fail(JPGPU_ERR_ARGUMENT, "Destination buffer is too small.");
+    if (img->jobs.size() > 1 && !entropy_only_) {
+        // (several scans: did the plan hold?  An image planned again -- redo_swallowed -- was decoded by a batch of its own, and the
+        // store holds what THIS plan's scans made of the file, scans the reference never decodes among them: refused)
+        if (redo_.find(i) == redo_.end()) {
+            jpgpu_image_result tmp;
+            const int rr = result(i, &tmp);
+            if (rr != JPGPU_OK) return rr;
+        }
+        if (redo_.find(i) != redo_.end())
+            return fail(JPGPU_ERR_NOT_SUPPORTED, "The image's scans were planned again (a middle scan leaves one byte unread in front of its "
+                                                 "terminating marker): its coefficients are not in the batch's store.");
+    }
     int rc = (replay_possible_ && !replay_done_) ? fetch_status() : sync();
     if (rc != JPGPU_OK) return rc;
     hipError_t e = hipMemcpy(dst, (const int16_t *)d_coefs_.ptr + img->coef_offset * 64, img->total_blocks * 128, hipMemcpyDeviceToHost);
@@ -319,6 +331,19 @@ int DeviceBatch::upload_coefficients(int i, const int16_t *src, size_t nblocks) 
     if (rc != JPGPU_OK) return rc;
     hipError_t e = hipMemcpy((int16_t *)d_coefs_.ptr + img->coef_offset * 64, src, nblocks * 128, hipMemcpyHostToDevice);
     return e == hipSuccess ? JPGPU_OK : hip_fail(e, "hipMemcpy(coefficients)");
+}
+
+void DeviceBatch::plan_stats(jpgpu_plan_stats *st) const {
+    memset(st, 0, sizeof *st);
+    st->k2_plain_work = n_huff_work_;
+    st->k2_pools = (int32_t)k2_pools_.size();
+    for (const SubseqPool &p : k2_pools_) st->k2_pooled_chunks += p.count;
+    st->huffman_waves = huffman_waves(k2_tab_bytes_);
+    st->k2s_scans = n_sub_scans_;
+    st->k2s_plain_work = n_sub_final_work_;
+    st->k2s_pools = (int32_t)sub_pools_.size();
+    st->k2s_table_sets = n_sr_sets_;
+    st->k2s_subs_per_lane = sub_final_spl_;
 }
 
 void DeviceBatch::totals(uint64_t *compressed, uint64_t *blocks, uint64_t *pixels, uint64_t *out_bytes) const {

@@ -31,3 +31,33 @@ def load_reference_buffer(name, width, height, ncomp) -> np.ndarray:
     buf = np.zeros((height, width, 4), dtype=np.uint16)
     buf[..., :ncomp] = (high[..., :ncomp] << 8) | (high[..., :ncomp] ^ low[..., :ncomp])
     return buf
+
+
+def middle_scan_swallow_files():
+    """Multi-scan baseline files (three single-component scans, 96 x 72 4:4:4, with and without restart intervals) with 1-3 bytes
+    of fill in front of the second SOS, the third SOS or EOI; a DHT of its own in front of the third scan behind one byte; and
+    one byte in front of both middle scans.  One whole byte behind a MIDDLE scan makes the reference's reader resume one byte
+    into the marker behind it (JpegHuffmanBaselineScanDecoder.cs:167-176), so which scans exist depends on the decode: the
+    batch plans such a file again (DeviceBatch::redo_swallowed).  Returns (files, tags); tag = (dri, fill bytes, where)."""
+    from tools import jpegsynth
+
+    files, tags = [], []
+    for dri in (0, 4):
+        good = bytes(jpegsynth.encode(96, 72, "444", 80, dri, seed=31 + dri, noninterleaved=True))
+        sos = [i for i in range(len(good) - 1) if good[i] == 0xFF and good[i + 1] == 0xDA]
+        eoi = len(good) - 2
+        assert len(sos) == 3
+        for k in (1, 2, 3):
+            for where, at in (("second_sos", sos[1]), ("third_sos", sos[2]), ("eoi", eoi)):
+                files.append(good[:at] + bytes([0x5A] * k) + good[at:])
+                tags.append((dri, k, where))
+        # a DHT of its own in front of the third scan: the swallowed marker is then the DHT's, the third SOS is found, and the scan
+        # decodes with the tables in force before (the same ones here)
+        dht = good[good.index(b"\xff\xc4"):]
+        dht = dht[:2 + int.from_bytes(dht[2:4], "big")]
+        files.append(good[:sos[2]] + b"\x5a" + dht + good[sos[2]:])
+        tags.append((dri, 1, "dht_before_third_sos"))
+        # both middle scans at once: the re-plan is re-planned
+        files.append(good[:sos[1]] + b"\x5a" + good[sos[1]:sos[2]] + b"\x5a" + good[sos[2]:])
+        tags.append((dri, 1, "second_and_third_sos"))
+    return files, tags

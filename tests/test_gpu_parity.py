@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import jpeglibrary_amd as jl
-from golden_util import load_reference_buffer, read_jpeg
+from golden_util import load_reference_buffer, middle_scan_swallow_files, read_jpeg
 from oracle import pyoracle as po
 from tools import jpegsynth
 
@@ -1401,25 +1401,7 @@ def test_a_middle_scan_that_leaves_one_byte_unread_is_planned_again():
     the checker, for each of the three scans of a multi-scan baseline frame, with and without restart intervals, beside files that do
     not need it; and whatever is asked for first (result or pixels)."""
     names = {0: "OK", 1: "InvalidDataException", 2: "InvalidOperationException", 3: "NotSupportedException", 4: "ArgumentException"}
-    files, tags = [], []
-    for dri in (0, 4):
-        good = bytes(jpegsynth.encode(96, 72, "444", 80, dri, seed=31 + dri, noninterleaved=True))
-        sos = [i for i in range(len(good) - 1) if good[i] == 0xFF and good[i + 1] == 0xDA]
-        eoi = len(good) - 2
-        assert len(sos) == 3
-        for k in (1, 2, 3):
-            for where, at in (("second_sos", sos[1]), ("third_sos", sos[2]), ("eoi", eoi)):
-                files.append(good[:at] + bytes([0x5A] * k) + good[at:])
-                tags.append((dri, k, where))
-        # a DHT of its own in front of the third scan: the swallowed marker is then the DHT's, the third SOS is found, and the scan
-        # decodes with the tables in force before (the same ones here)
-        dht = good[good.index(b"\xff\xc4"):]
-        dht = dht[:2 + int.from_bytes(dht[2:4], "big")]
-        files.append(good[:sos[2]] + b"\x5a" + dht + good[sos[2]:])
-        tags.append((dri, 1, "dht_before_third_sos"))
-        # both middle scans at once: the re-plan is re-planned
-        files.append(good[:sos[1]] + b"\x5a" + good[sos[1]:sos[2]] + b"\x5a" + good[sos[2]:])
-        tags.append((dri, 1, "second_and_third_sos"))
+    files, tags = middle_scan_swallow_files()
     refs = []
     for f in files:
         px, _, err = po.decode_8bit_partial(f)
