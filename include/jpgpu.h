@@ -254,6 +254,11 @@ typedef struct jpgpu_plan_stats {
 /* sizeof(jpgpu_plan_stats) as THIS library writes it. */
 size_t jpgpu_sizeof_plan_stats(void);
 int jpgpu_batch_plan_stats(const jpgpu_batch *b, jpgpu_plan_stats *stats);
+/* How the last upload planned K3 (read only; for tests and tools): work entries (workgroups) per output layout class -- generic,
+ * YCbCr 1x1 / 2x1 / 2x2, gray, store holding samples.  Scans ordered behind other scans of their image are not counted.
+ * n must be JPGPU_IDCT_LAYOUT_CLASSES. */
+#define JPGPU_IDCT_LAYOUT_CLASSES 6
+int jpgpu_batch_idct_work(const jpgpu_batch *b, int32_t *counts, int n);
 
 /* Coefficient hand-off for multi-scan (progressive, SOF2) images -- BASELINE config 5's "coefficient accumulate then single
  * IDCT pass": the caller's progressive entropy decoder accumulates the coefficient store, the GPU runs what

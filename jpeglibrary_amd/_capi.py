@@ -113,6 +113,7 @@ SYMBOLS = [
     ("jpgpu_batch_ingest_stats", C.c_int, [_P, C.POINTER(IngestStats)]),
     ("jpgpu_sizeof_plan_stats", C.c_size_t, []),
     ("jpgpu_batch_plan_stats", C.c_int, [_P, C.POINTER(PlanStats)]),
+    ("jpgpu_batch_idct_work", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
     ("jpgpu_batch_progressive_fallbacks", C.c_int, [_P]),
     ("jpgpu_status_string", C.c_char_p, [C.c_int]),
     ("jpgpu_detail_string", C.c_char_p, [C.c_int]),

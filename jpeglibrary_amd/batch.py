@@ -15,6 +15,7 @@ from .errors import raise_for_status
 _lib = _capi.lib
 FMT_INTERLEAVED_U8, FMT_PLANAR_U8, FMT_PLANAR_I16 = _capi.FMT_INTERLEAVED_U8, _capi.FMT_PLANAR_U8, _capi.FMT_PLANAR_I16
 FMT_RGB_U8, FMT_RGBA_U8, FMT_EXTENDED_U16 = _capi.FMT_RGB_U8, _capi.FMT_RGBA_U8, _capi.FMT_EXTENDED_U16
+IDCT_LAYOUT_CLASSES = 6  # JPGPU_IDCT_LAYOUT_CLASSES: generic, YCbCr 1x1 / 2x1 / 2x2, gray, store holding samples
 
 
 class _BorrowedContext:
@@ -131,10 +132,13 @@ class Batch:
         return {k: getattr(st, k) for k, _ in _capi.IngestStats._fields_}
 
     def plan_stats(self):
-        """How the last upload() planned the entropy stage: K2's plain list and pools, K2S's final-pass list, pools and table sets."""
+        """How the last upload() planned the entropy stage (K2's plain list and pools, K2S's final-pass list, pools and table
+        sets) and K3: idct_work = work entries per output layout class (generic, YCbCr 1x1, 2x1, 2x2, gray, store of samples)."""
         st = _capi.PlanStats()
         self._check(_lib.jpgpu_batch_plan_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in _capi.PlanStats._fields_}
+        work = (C.c_int32 * IDCT_LAYOUT_CLASSES)()
+        self._check(_lib.jpgpu_batch_idct_work(self._h, work, IDCT_LAYOUT_CLASSES))
+        return dict({k: getattr(st, k) for k, _ in _capi.PlanStats._fields_}, idct_work=list(work))
 
     def progressive_fallbacks(self):
         """Times the single-launch progressive path timed out and the step was re-issued level by level."""

@@ -471,6 +471,12 @@ int jpgpu_batch_plan_stats(const jpgpu_batch *b, jpgpu_plan_stats *stats) {
     b->impl.plan_stats(stats);
     return JPGPU_OK;
 }
+static_assert(JPGPU_IDCT_LAYOUT_CLASSES == kNumIdctLayoutClasses, "jpgpu_batch_idct_work: one count per K3 layout class");
+int jpgpu_batch_idct_work(const jpgpu_batch *b, int32_t *counts, int n) {
+    if (!b || !counts || n != JPGPU_IDCT_LAYOUT_CLASSES) return JPGPU_ERR_ARGUMENT;
+    b->impl.idct_work(counts);
+    return JPGPU_OK;
+}
 int jpgpu_batch_totals(const jpgpu_batch *b, uint64_t *compressed_bytes, uint64_t *blocks, uint64_t *pixels, uint64_t *output_bytes) {
     if (!b) return JPGPU_ERR_ARGUMENT;
     b->impl.totals(compressed_bytes, blocks, pixels, output_bytes);

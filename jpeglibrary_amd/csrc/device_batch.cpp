@@ -185,6 +185,10 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
     } else {
         if (fh.num_components > 4)  // jpgpu_plane_info describes four planes; a fifth component would land on plane 0
             throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "The planar output formats describe at most 4 components.", kDetailUnsupportedFrame);
+        // the test writer spreads P bits over 16 (JpegExtendingOutputWriter.cs:83-110): at P = 0 its ExpandBits loop never
+        // ends, above 16 the shifts leave the 32-bit range -- there is no behaviour to follow, the image fails by itself
+        if (format_ == JPGPU_FMT_EXTENDED_U16 && (fh.precision < 1 || fh.precision > 16))
+            throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "EXTENDED_U16 is defined for precisions 1..16 only.", kDetailUnsupportedFrame);
         // EXTENDED_U16 is produced from int16 planes (K3's PLANAR_I16 output in a scratch buffer, see run_idct)
         const uint64_t sample_bytes = (format_ == JPGPU_FMT_PLANAR_I16 || format_ == JPGPU_FMT_EXTENDED_U16) ? 2 : 1;
         uint64_t off = 0;

@@ -102,6 +102,7 @@ class DeviceBatch {
   public:
     const IngestStats &ingest_stats() const { return ingest_; }
     void plan_stats(jpgpu_plan_stats *st) const;  // jpgpu_batch_plan_stats: the entropy stage's work lists and pools
+    void idct_work(int32_t counts[kNumIdctLayoutClasses]) const;  // jpgpu_batch_idct_work: K3 work entries per layout class
     explicit DeviceBatch(jpgpu_ctx *ctx) : ctx_(ctx) {}
     ~DeviceBatch();
 

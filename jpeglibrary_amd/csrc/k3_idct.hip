@@ -159,7 +159,9 @@ __device__ __forceinline__ void block_idct(const float (&f)[64], int32_t level_s
 #pragma unroll
         for (int c2 = 0; c2 < 4; c2++) {
             const float2v v = b[r][c2] * 0.1250f;                  // MultiplyInplace(C_0_125)
-            const int32_t x = (int32_t)__builtin_rintf(v.x);       // MathF.Round: half to even (v_rndne_f32)
+            // MathF.Round: half to even (v_rndne_f32).  Outside int32 the conversion saturates (v_cvt_i32_f32), where the x64
+            // reference gives INT_MIN: a fence, pinned by tests/test_idct_stage_gpu.py
+            const int32_t x = (int32_t)__builtin_rintf(v.x);
             const int32_t y = (int32_t)__builtin_rintf(v.y);
             const uint32_t pk = ((uint32_t)x & 0xFFFFu) | ((uint32_t)y << 16);
             // (short)(Round + levelShift): 16-bit wrap-around add on both halves (v_pk_add_u16)
@@ -276,7 +278,9 @@ __global__ __launch_bounds__(256) void extend_u16_kernel(const uint8_t *__restri
     uint16_t *out = reinterpret_cast<uint16_t *>(out_base + g.out_off);
     for (uint64_t px = (uint64_t)blockIdx.x * 256 + threadIdx.x; px < (uint64_t)g.width * g.height; px += (uint64_t)gridDim.x * 256) {
     const uint32_t y = (uint32_t)(px / g.width), x = (uint32_t)(px - (uint64_t)y * g.width);
-    const uint32_t p = g.precision, mx = (1u << p) - 1u;
+    // (the host refuses precisions outside 1..16 for this format, DeviceBatch::plan_image_geometry; the clamp keeps the shifts
+    // below 32 and the ExpandBits loop finite whatever reaches the kernel)
+    const uint32_t p = g.precision < 1u ? 1u : (g.precision > 16u ? 16u : g.precision), mx = (1u << p) - 1u;
     uint16_t v4[4] = {0, 0, 0, 0};
 #pragma unroll  // (compile-time component index: the descriptor's arrays stay in registers, no scratch)
     for (uint32_t c = 0; c < 4u; c++) {

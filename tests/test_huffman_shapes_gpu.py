@@ -14,23 +14,10 @@ import numpy as np
 import pytest
 
 import jpeglibrary_amd as jl
+from golden_util import BitWriter as _Bits, block_symbols as _symbols, canonical_codes as _canonical
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
-
-
-def _canonical(lengths):
-    """{symbol: length} -> ({symbol: (code, length)}, BITS[16], HUFFVAL) the way Annex C assigns codes"""
-    order = sorted(lengths.items(), key=lambda kv: (kv[1], kv[0]))
-    bits, codes, code, prev = [0] * 16, {}, 0, order[0][1]
-    for sym, ln in order:
-        code <<= ln - prev
-        prev = ln
-        codes[sym] = (code, ln)
-        assert code < (1 << ln) - (1 if ln == 16 else 0), "code space exhausted"
-        code += 1
-        bits[ln - 1] += 1
-    return codes, bits, [s for s, _ in order]
 
 
 def _shape(freq, shape, is_dc):
@@ -43,50 +30,6 @@ def _shape(freq, shape, is_dc):
         by_cat = sorted(syms, key=lambda s: -s)
         return {s: min(16, i + 1 + (1 if i == len(by_cat) - 1 else 0)) if i < 15 else 16 for i, s in enumerate(by_cat)}
     raise ValueError(shape)
-
-
-class _Bits:
-    def __init__(self):
-        self.out, self.acc, self.n = bytearray(), 0, 0
-
-    def put(self, code, ln):
-        self.acc = (self.acc << ln) | (code & ((1 << ln) - 1))
-        self.n += ln
-        while self.n >= 8:
-            b = (self.acc >> (self.n - 8)) & 0xFF
-            self.out.append(b)
-            if b == 0xFF:
-                self.out.append(0)
-            self.n -= 8
-        self.acc &= (1 << self.n) - 1
-
-    def flush(self):
-        if self.n:
-            self.put((1 << (8 - self.n)) - 1, 8 - self.n)
-
-
-def _symbols(block, pred):
-    """(DC category, DC bits), [(AC symbol, magnitude bits, size)] of one zig-zag block"""
-    def mag(v):
-        s = int(abs(v)).bit_length()
-        return s, (v if v >= 0 else v + (1 << s) - 1) & ((1 << s) - 1)
-
-    d = int(block[0]) - pred
-    out, run = [], 0
-    for k in range(1, 64):
-        v = int(block[k])
-        if v == 0:
-            run += 1
-            continue
-        while run > 15:
-            out.append((0xF0, 0, 0))
-            run -= 16
-        s, m = mag(v)
-        out.append(((run << 4) | s, m, s))
-        run = 0
-    if run:
-        out.append((0x00, 0, 0))
-    return mag(d), out
 
 
 def _recode(pixels, luma, quality, dri, dc_shape, ac_shape):
