@@ -340,6 +340,30 @@ int jpgpu_batch_subseq_fallbacks(const jpgpu_batch *b);
  * relies on workgroups being dispatched in list order) and the step was re-issued scan level by scan level.  Valid after
  * jpgpu_batch_result. */
 int jpgpu_batch_progressive_fallbacks(const jpgpu_batch *b);
+/* How the last upload planned the scans of its progressive (SOF2) frames, and which launches the last decode / run_entropy
+ * took for them (read only; for tests and tools).  A scan waits for the earlier scans of its frame that touch the same
+ * coefficients: `levels` counts the launch groups that ordering gives, `max_deps` the most DIRECT producers any scan has
+ * (more than three: the batch is not pipelined).  Chains: 0 = DC scans, 1 + min(3, c) = AC scans of frame component c. */
+#define JPGPU_PROGRESSIVE_CHAINS 5
+#define JPGPU_PROG_LAUNCH_NONE 0             /* no progressive scan was launched (yet) */
+#define JPGPU_PROG_LAUNCH_PIPELINED_GATED 1  /* one launch, every workgroup resident, followers watch their producers */
+#define JPGPU_PROG_LAUNCH_PIPELINED_FORCED 2 /* the same launch without the residency gate (JPGPU_PROG_FORCE_PIPELINE) */
+#define JPGPU_PROG_LAUNCH_CHAINS 3           /* one stream per chain, one launch per scan ordinal of the chain */
+#define JPGPU_PROG_LAUNCH_BY_LEVEL 4         /* one launch (pair) per dependency level */
+typedef struct jpgpu_progressive_plan {
+    int32_t scans;          /* progressive scans planned, over all frames */
+    int32_t levels;         /* launch groups (dependency levels; scans in file order where the plan is scan by scan) */
+    int32_t max_deps;       /* largest number of direct producers of one scan */
+    int32_t pipelined;      /* the plan allows the single pipelined launch (0 after a fallback as well) */
+    int32_t chains_ok;      /* the plan allows the chain launches */
+    int32_t pipe_waves;     /* entries of the pipelined launch's list: one per wave */
+    int32_t wave_tails;     /* scans that run behind their only producer in that producer's wave */
+    int32_t lane_work;      /* work entries of the lane-per-interval kernel (scans of many restart intervals, empty bands) */
+    int32_t chain_scans[JPGPU_PROGRESSIVE_CHAINS]; /* scans per chain */
+    int32_t launch_form;    /* JPGPU_PROG_LAUNCH_* of the last decode / run_entropy */
+} jpgpu_progressive_plan;
+size_t jpgpu_sizeof_progressive_plan(void);
+int jpgpu_batch_progressive_plan(const jpgpu_batch *b, jpgpu_progressive_plan *plan);
 /* Total entropy-segment bytes / blocks / pixels of the successfully parsed images. */
 int jpgpu_batch_totals(const jpgpu_batch *b, uint64_t *compressed_bytes, uint64_t *blocks, uint64_t *pixels,
                        uint64_t *output_bytes);

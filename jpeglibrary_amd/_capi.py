@@ -73,6 +73,16 @@ class PlanStats(C.Structure):
                 ("k2s_subs_per_lane", C.c_int32)]
 
 
+class ProgressivePlan(C.Structure):
+    _fields_ = [("scans", C.c_int32), ("levels", C.c_int32), ("max_deps", C.c_int32), ("pipelined", C.c_int32), ("chains_ok", C.c_int32),
+                ("pipe_waves", C.c_int32), ("wave_tails", C.c_int32), ("lane_work", C.c_int32), ("chain_scans", C.c_int32 * 5),
+                ("launch_form", C.c_int32)]
+
+
+# jpgpu_progressive_plan.launch_form (JPGPU_PROG_LAUNCH_*)
+PROG_LAUNCH_NAMES = ("none", "pipelined_gated", "pipelined_forced", "chains", "by_level")
+
+
 class Segment(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t)]
 
@@ -115,6 +125,8 @@ SYMBOLS = [
     ("jpgpu_batch_plan_stats", C.c_int, [_P, C.POINTER(PlanStats)]),
     ("jpgpu_batch_idct_work", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
     ("jpgpu_batch_progressive_fallbacks", C.c_int, [_P]),
+    ("jpgpu_sizeof_progressive_plan", C.c_size_t, []),
+    ("jpgpu_batch_progressive_plan", C.c_int, [_P, C.POINTER(ProgressivePlan)]),
     ("jpgpu_status_string", C.c_char_p, [C.c_int]),
     ("jpgpu_detail_string", C.c_char_p, [C.c_int]),
     ("jpgpu_batch_create", C.c_int, [_P, C.POINTER(_P)]),
@@ -252,6 +264,9 @@ def _load():
     if lib.jpgpu_sizeof_plan_stats() != C.sizeof(PlanStats):
         raise ImportError(f"{LIB_PATH} (jpgpu_plan_stats of {lib.jpgpu_sizeof_plan_stats()} bytes) does not match this binding "
                           f"({C.sizeof(PlanStats)} bytes): rebuild it")
+    if lib.jpgpu_sizeof_progressive_plan() != C.sizeof(ProgressivePlan):
+        raise ImportError(f"{LIB_PATH} (jpgpu_progressive_plan of {lib.jpgpu_sizeof_progressive_plan()} bytes) does not match this "
+                          f"binding ({C.sizeof(ProgressivePlan)} bytes): rebuild it")
     return lib
 
 

@@ -144,6 +144,16 @@ class Batch:
         """Times the single-launch progressive path timed out and the step was re-issued level by level."""
         return _lib.jpgpu_batch_progressive_fallbacks(self._h)
 
+    def progressive_plan(self):
+        """How the last upload() planned the scans of its progressive frames (scans, levels, max_deps, pipelined, chains_ok,
+        pipe_waves, wave_tails, lane_work, chain_scans[5]) and launch_form: what the last decode() / run_entropy() launched for
+        them -- "pipelined_gated", "pipelined_forced", "chains", "by_level" or "none"."""
+        st = _capi.ProgressivePlan()
+        self._check(_lib.jpgpu_batch_progressive_plan(self._h, C.byref(st)))
+        d = {k: getattr(st, k) for k, _ in _capi.ProgressivePlan._fields_}
+        return dict(d, pipelined=bool(st.pipelined), chains_ok=bool(st.chains_ok), chain_scans=list(st.chain_scans),
+                    launch_form=_capi.PROG_LAUNCH_NAMES[st.launch_form])
+
     def subseq_rounds(self):
         """Synchronisation rounds the DRI = 0 subsequence decoder needed in the last decode (0 = not used)."""
         return _lib.jpgpu_batch_subseq_rounds(self._h)

@@ -471,6 +471,13 @@ int jpgpu_batch_plan_stats(const jpgpu_batch *b, jpgpu_plan_stats *stats) {
     b->impl.plan_stats(stats);
     return JPGPU_OK;
 }
+static_assert(JPGPU_PROGRESSIVE_CHAINS == jpgpu_ctx::kProgChains, "jpgpu_progressive_plan: one count per chain stream");
+size_t jpgpu_sizeof_progressive_plan(void) { return sizeof(jpgpu_progressive_plan); }
+int jpgpu_batch_progressive_plan(const jpgpu_batch *b, jpgpu_progressive_plan *plan) {
+    if (!b || !plan) return JPGPU_ERR_ARGUMENT;
+    b->impl.progressive_plan(plan);
+    return JPGPU_OK;
+}
 static_assert(JPGPU_IDCT_LAYOUT_CLASSES == kNumIdctLayoutClasses, "jpgpu_batch_idct_work: one count per K3 layout class");
 int jpgpu_batch_idct_work(const jpgpu_batch *b, int32_t *counts, int n) {
     if (!b || !counts || n != JPGPU_IDCT_LAYOUT_CLASSES) return JPGPU_ERR_ARGUMENT;

@@ -102,6 +102,7 @@ class DeviceBatch {
   public:
     const IngestStats &ingest_stats() const { return ingest_; }
     void plan_stats(jpgpu_plan_stats *st) const;  // jpgpu_batch_plan_stats: the entropy stage's work lists and pools
+    void progressive_plan(jpgpu_progressive_plan *p) const;  // jpgpu_batch_progressive_plan
     void idct_work(int32_t counts[kNumIdctLayoutClasses]) const;  // jpgpu_batch_idct_work: K3 work entries per layout class
     explicit DeviceBatch(jpgpu_ctx *ctx) : ctx_(ctx) {}
     ~DeviceBatch();
@@ -306,6 +307,10 @@ class DeviceBatch {
     bool prog_chains_ok_ = false;
     bool prog_pipelined_ = false;  // all progressive scans are single streams with <= 3 direct dependencies: one launch
     uint32_t prog_spin_budget_ = 1u << 22;  // polls a follower scan may spend in the pipelined launch (JPGPU_PROG_SPIN_BUDGET)
+    // what jpgpu_batch_progressive_plan reports beside the lists above: scans planned, the most direct producers of one scan,
+    // scans that share their producer's wave, scans per chain; and the launches run_progressive() last took (JPGPU_PROG_LAUNCH_*)
+    int prog_scans_ = 0, prog_max_deps_ = 0, prog_wave_tails_ = 0, prog_launch_form_ = 0;
+    int prog_chain_scans_[jpgpu_ctx::kProgChains] = {};
     int prog_fallbacks_ = 0;                // times the pipelined launch timed out and the step was re-issued level by level
     std::vector<std::pair<uint64_t, uint64_t>> prog_clear_;  // (first block, blocks) of every progressive frame's store
     // RGB / RGBA output for layouts without a fused conversion: INTERLEAVED_U8 samples in a scratch image first

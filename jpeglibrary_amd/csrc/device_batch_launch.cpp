@@ -154,6 +154,7 @@ int DeviceBatch::run_progressive() {
         // workgroups keeps n / 1024 waves per SIMD busy, and a lone wave issues an instruction every ~5 cycles at best), and
         // the step takes as long as its longest chain instead of the sum over dependency levels.
         jpgpu_ctx *cx = ctx_;
+        prog_launch_form_ = JPGPU_PROG_LAUNCH_CHAINS;
         for (int x = 0; x < jpgpu_ctx::kProgChains; x++) {
             if (!cx->prog_stream[x]) {
                 hipError_t e = hipStreamCreateWithFlags(&cx->prog_stream[x], hipStreamNonBlocking);
@@ -190,6 +191,7 @@ int DeviceBatch::run_progressive() {
         hipError_t e0 = hipMemsetAsync(d_prog_sync_.ptr, 0, 256, ctx_->stream);
         if (e0 != hipSuccess) return hip_fail(e0, "hipMemsetAsync(progressive sync)");
         const int n = n_waves;
+        prog_launch_form_ = launch_mode == 1 ? JPGPU_PROG_LAUNCH_PIPELINED_GATED : JPGPU_PROG_LAUNCH_PIPELINED_FORCED;
         hipError_t e = launch_progressive_streams(ctx_->stream, (const uint8_t *)d_unstuffed_.ptr, (const DevScan *)d_scans_.ptr,
                                                   (const HuffWork *)d_prog_work_.ptr + prog_pipe_begin_, n,
                                                   (const uint32_t *)d_ends_u_.ptr, (DevScanStatus *)d_status_.ptr,
@@ -197,6 +199,7 @@ int DeviceBatch::run_progressive() {
         if (e != hipSuccess) return hip_fail(e, "progressive_stream_kernel");
         return JPGPU_OK;
     }
+    prog_launch_form_ = JPGPU_PROG_LAUNCH_BY_LEVEL;
     for (size_t k = 0; k + 1 < prog_begin_.size(); k++) {
         if (dbg_max && (int)k >= atoi(dbg_max)) break;
         hipError_t e = launch_progressive(ctx_->stream, (const uint8_t *)d_unstuffed_.ptr, (const DevScan *)d_scans_.ptr,

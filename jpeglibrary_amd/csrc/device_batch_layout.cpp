@@ -115,6 +115,8 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
     std::vector<std::vector<HuffWork>> prog_work_by_ordinal, prog_streams_by_ordinal;
     std::vector<std::vector<HuffWork>> prog_chain_work[jpgpu_ctx::kProgChains];  // [chain][ordinal in the frame's chain]
     prog_chains_ok_ = true;
+    prog_scans_ = prog_max_deps_ = prog_wave_tails_ = prog_launch_form_ = 0;
+    for (int &n : prog_chain_scans_) n = 0;
     // a scan with fewer restart intervals than this gets one WAVE per interval (progressive_stream_kernel)
     const uint32_t stream_max_intervals = getenv("JPGPU_PROG_STREAM_MAX_INTERVALS") ? (uint32_t)atoi(getenv("JPGPU_PROG_STREAM_MAX_INTERVALS")) : 16u;
     prog_clear_.clear();
@@ -326,6 +328,8 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
                 const bool by_scan = by_scan_env || prog_by_scan_;
                 if (job.disabled || img.replay_skip) continue;  // (replay of a failed file: the reference never got to this scan; K1 still indexes it)
                 const int ordinal = by_scan ? j - img.jobs[0] - 1 : job.ordinal;
+                prog_scans_++;
+                prog_max_deps_ = std::max(prog_max_deps_, (int)job.n_deps);
                 if (by_scan) prog_pipelined_ = false;
                 if ((size_t)ordinal >= prog_work_by_ordinal.size()) {
                     prog_work_by_ordinal.resize((size_t)ordinal + 1);
@@ -353,6 +357,7 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
                         in_chain += ((o.scan_components != 1 || o.ss == 0) ? 0 : 1 + std::min(3, o.comp[0].component_index)) == chain;
                     }
                     if (prog_chain_work[chain].size() <= (size_t)in_chain) prog_chain_work[chain].resize((size_t)in_chain + 1);
+                    prog_chain_scans_[chain]++;
                     for (uint32_t i = 0; i < s.n_intervals; i++) prog_chain_work[chain][(size_t)in_chain].push_back({(uint32_t)j, i});
                 } else {
                     prog_chains_ok_ = false;  // a scan of many restart intervals (lane kernel): level by level
@@ -618,6 +623,7 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
                 h_scans_[(size_t)(j0 + a)].wave_next = (uint8_t)(k - a);
                 has_next[(size_t)a] = 1;
                 is_tail[(size_t)(j0 + k)] = 1;
+                prog_wave_tails_++;
                 wave_bytes[(size_t)k] = together;
             }
         }

@@ -346,6 +346,20 @@ void DeviceBatch::plan_stats(jpgpu_plan_stats *st) const {
     st->k2s_subs_per_lane = sub_final_spl_;
 }
 
+void DeviceBatch::progressive_plan(jpgpu_progressive_plan *p) const {
+    memset(p, 0, sizeof *p);
+    p->scans = prog_scans_;
+    p->levels = prog_begin_.empty() ? 0 : (int32_t)prog_begin_.size() - 1;
+    p->max_deps = prog_max_deps_;
+    p->pipelined = prog_scans_ > 0 && prog_pipelined_;
+    p->chains_ok = prog_scans_ > 0 && prog_chains_ok_;
+    p->pipe_waves = prog_pipe_count_;
+    p->wave_tails = prog_wave_tails_;
+    p->lane_work = prog_begin_.empty() ? 0 : prog_begin_.back();
+    for (int x = 0; x < jpgpu_ctx::kProgChains; x++) p->chain_scans[x] = prog_chain_scans_[x];
+    p->launch_form = prog_launch_form_;
+}
+
 void DeviceBatch::idct_work(int32_t counts[kNumIdctLayoutClasses]) const {
     for (int c = 0; c < kNumIdctLayoutClasses; c++) counts[c] = idct_class_begin_[c + 1] - idct_class_begin_[c];
 }
