@@ -79,7 +79,14 @@ typedef enum jpgpu_format {
      * (ushort)sample clamped to 2^P - 1 (a negative sample becomes the maximum), the P bits spread over 16
      * (FastExpandBits / ExpandBits :86-111), sub-sampled components replicated like WriteBlockSlow, clipped to W x H;
      * channels >= the frame's component count stay zero.  What the golden PNG pairs of the reference hold. */
-    JPGPU_FMT_EXTENDED_U16 = 5
+    JPGPU_FMT_EXTENDED_U16 = 5,
+    /* INTERLEAVED_U8's geometry with the sample-to-byte step chosen by the frame's precision P the way
+     * apps/JpegDecode/DecodeAction.cs:41-54 chooses its writer: P == 8 the bytes of INTERLEAVED_U8; 9 <= P <= 16
+     * (byte)Clamp(sample >> (P - 8), 0, 255), an arithmetic shift (JpegBufferOutputWriterGreaterThan8Bit.cs:57,64-67);
+     * 1 <= P <= 7 Clamp(sample, 0, 2^P - 1) (signed) spread over 8 bits by ExpandBits
+     * (JpegBufferOutputWriterLessThan8Bit.cs:59-60, 67-93).  Any other P: the image fails by itself with
+     * JPGPU_ERR_NOT_SUPPORTED / JPGPU_DETAIL_UNSUPPORTED_FRAME. */
+    JPGPU_FMT_INTERLEAVED_U8_SCALED = 6
 } jpgpu_format;
 
 typedef struct jpgpu_ctx jpgpu_ctx;
@@ -491,6 +498,12 @@ int jpgpu_decoder_set_output_writer(jpgpu_decoder *d, jpgpu_write_block_fn fn, v
  * the interleaved buffer is produced directly on the GPU (INTERLEAVED_U8) and copied into `out`. */
 int jpgpu_decoder_set_output_buffer8(jpgpu_decoder *d, int width, int height, int component_count, uint8_t *out,
                                      size_t cap);
+/* SetOutputWriter with the reference's other two stock sinks (apps/JpegDecode/JpegBufferOutputWriterLessThan8Bit.cs,
+ * JpegBufferOutputWriterGreaterThan8Bit.cs; the writer's own `precision`, 1..16, picks the conversion, 8 is the 8-bit sink's):
+ * produced directly on the GPU (INTERLEAVED_U8_SCALED) when width, height, component count and precision equal the frame's,
+ * else the writer is replayed on the host with its own precision. */
+int jpgpu_decoder_set_output_buffer8_scaled(jpgpu_decoder *d, int width, int height, int precision, int component_count, uint8_t *out,
+                                            size_t cap);
 int jpgpu_decoder_decode(jpgpu_decoder *d);                                      /* Decode :509-550 */
 /* The TIFF-style surface (JPEG-in-TIFF keeps tables, frame header and strips apart; SURVEY 5 "checkpoint / resume" row): the
  * caller sets the pieces itself instead of letting Decode()'s marker loop find them, then hands over one scan's entropy data. */
@@ -505,7 +518,7 @@ int jpgpu_decoder_clear_huffman_table(jpgpu_decoder *d);                        
 int jpgpu_decoder_clear_quantization_table(jpgpu_decoder *d);                    /* ClearQuantizationTable :784-787 */
 /* ProcessScan(ref JpegReader, JpegScanHeader) :624-632: JpegScanDecoder.Create(StartOfFrame, this, GetFrameHeader()) -- the restart
  * interval is latched at this moment -- one ProcessScan over `entropy` (reader.RemainingBytes), Dispose.  The output
- * goes to the writer set with jpgpu_decoder_set_output_writer / _set_output_buffer8; *bytes_consumed = the reader's advance. */
+ * goes to the writer set with jpgpu_decoder_set_output_writer / _set_output_buffer8 / _set_output_buffer8_scaled; *bytes_consumed = the reader's advance. */
 int jpgpu_decoder_process_scan(jpgpu_decoder *d, const jpgpu_scan *scan, const uint8_t *entropy, size_t len, size_t *bytes_consumed);
 void jpgpu_decoder_reset(jpgpu_decoder *d);                                      /* Reset :930 */
 void jpgpu_decoder_reset_input(jpgpu_decoder *d);                                /* ResetInput :941 */

@@ -5,11 +5,11 @@ There is no CPU fallback: creating a context without a GPU raises NoDeviceError.
 """
 from . import _capi  # noqa: F401  (loads libjpgpu.so, fails loudly when absent)
 from . import sharding  # noqa: F401
-from .batch import FMT_EXTENDED_U16, FMT_INTERLEAVED_U8, FMT_PLANAR_I16, FMT_PLANAR_U8, FMT_RGB_U8, FMT_RGBA_U8, Batch, decode_batch
+from .batch import FMT_EXTENDED_U16, FMT_INTERLEAVED_U8, FMT_INTERLEAVED_U8_SCALED, FMT_PLANAR_I16, FMT_PLANAR_U8, FMT_RGB_U8, FMT_RGBA_U8, Batch, decode_batch
 from .context import Context, default_context, device_count
 from .encoder import EncodeBatch, encode_batch
 from .optimizer import JpegOptimizer, OptimizeBatch, build_optimal_huffman_table, optimize_batch
-from .decoder import (JpegBlockOutputWriter, JpegBufferOutputWriter8Bit, JpegDecoder, JpegExtendingOutputWriter, JpegFrameComponentSpecificationParameters,
+from .decoder import (JpegBlockOutputWriter, JpegBufferOutputWriter8Bit, JpegBufferOutputWriterGreaterThan8Bit, JpegBufferOutputWriterLessThan8Bit, JpegDecoder, JpegExtendingOutputWriter, JpegFrameComponentSpecificationParameters,
                       JpegFrameHeader, JpegGpuProgressiveScanDecoder, JpegHuffmanDecodingTable, JpegScanComponentSpecificationParameters, JpegScanHeader)
 from .jpeg_encoder import (JpegBufferInputReader, JpegEncoder, JpegHuffmanEncodingTable, JpegQuantizationTable, JpegStandardHuffmanEncodingTable,
                            JpegStandardQuantizationTable)
@@ -22,6 +22,7 @@ __all__ = [
     "JpegStandardHuffmanEncodingTable", "JpegBufferInputReader", "EncodeBatch", "encode_batch", "JpegOptimizer", "OptimizeBatch", "optimize_batch", "build_optimal_huffman_table", "Context", "default_context", "device_count", "JpegDecoder", "JpegBlockOutputWriter",
     "JpegBufferOutputWriter8Bit", "JpegExtendingOutputWriter", "JpegFrameHeader", "JpegFrameComponentSpecificationParameters", "JpegScanHeader",
     "JpegScanComponentSpecificationParameters", "JpegHuffmanDecodingTable", "JpegGpuProgressiveScanDecoder", "FMT_INTERLEAVED_U8", "FMT_PLANAR_U8", "FMT_PLANAR_I16", "FMT_RGB_U8", "FMT_RGBA_U8", "FMT_EXTENDED_U16",
+    "FMT_INTERLEAVED_U8_SCALED", "JpegBufferOutputWriterGreaterThan8Bit", "JpegBufferOutputWriterLessThan8Bit",
     "JpegError", "InvalidDataException", "InvalidOperationException", "NotSupportedException", "ArgumentException",
     "DeviceError", "NoDeviceError",
 ]

@@ -15,6 +15,7 @@ from .errors import raise_for_status
 _lib = _capi.lib
 FMT_INTERLEAVED_U8, FMT_PLANAR_U8, FMT_PLANAR_I16 = _capi.FMT_INTERLEAVED_U8, _capi.FMT_PLANAR_U8, _capi.FMT_PLANAR_I16
 FMT_RGB_U8, FMT_RGBA_U8, FMT_EXTENDED_U16 = _capi.FMT_RGB_U8, _capi.FMT_RGBA_U8, _capi.FMT_EXTENDED_U16
+FMT_INTERLEAVED_U8_SCALED = _capi.FMT_INTERLEAVED_U8_SCALED
 IDCT_LAYOUT_CLASSES = 6  # JPGPU_IDCT_LAYOUT_CLASSES: generic, YCbCr 1x1 / 2x1 / 2x2, gray, store holding samples
 
 
@@ -186,13 +187,13 @@ class Batch:
         return p, total.value
 
     def output(self, i):
-        """Downloads image i. INTERLEAVED_U8 -> uint8[H,W,C]; RGB_U8 / RGBA_U8 -> uint8[H,W,3|4]; EXTENDED_U16 -> uint16[H,W,4];
+        """Downloads image i. INTERLEAVED_U8 / INTERLEAVED_U8_SCALED -> uint8[H,W,C]; RGB_U8 / RGBA_U8 -> uint8[H,W,3|4]; EXTENDED_U16 -> uint16[H,W,4];
         PLANAR_* -> list of per-component 2-D arrays (padded)."""
         info = self.image_info(i)
         raise_for_status(info.status, _lib.jpgpu_last_error(self.ctx._h))
         raw = np.empty(info.out_bytes, dtype=np.uint8)
         self._check(_lib.jpgpu_batch_download_output(self._h, i, raw.ctypes.data, raw.size))
-        if self.format == FMT_INTERLEAVED_U8:
+        if self.format in (FMT_INTERLEAVED_U8, FMT_INTERLEAVED_U8_SCALED):
             return raw.reshape(info.height, info.width, info.num_components)
         if self.format in (FMT_RGB_U8, FMT_RGBA_U8):
             return raw.reshape(info.height, info.width, 4 if self.format == FMT_RGBA_U8 else 3)

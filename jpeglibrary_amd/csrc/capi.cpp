@@ -567,6 +567,49 @@ struct HostSink8 {
     }
 };
 
+// ref: apps/JpegDecode/JpegBufferOutputWriterLessThan8Bit.cs:35-93 / JpegBufferOutputWriterGreaterThan8Bit.cs:34-67 -- host restatement
+// with the WRITER's precision (1..16; DecodeAction.cs:41-54 picks the class by it), used when the caller's sink differs from the
+// frame in geometry or precision (then the GPU's INTERLEAVED_U8_SCALED layout cannot be used directly).
+struct HostSinkScaled {
+    HostSink8 g;
+    int precision;
+    static uint32_t expand_bits(uint32_t bits, int bit_count) {  // ExpandBits :75-93, FastExpandBits :67-73
+        int current = bit_count;
+        while (current < 8) {
+            bits = (bits << bit_count) | bits;
+            current += bit_count;
+        }
+        if (current > 8) {
+            bits >>= bit_count;
+            current -= bit_count;
+            const int remaining = 8 - current;
+            bits = (bits << remaining) | (bits & ((1u << remaining) - 1u));
+        }
+        return bits;
+    }
+    static void write(void *user, const int16_t *block, int component_index, int x, int y) {
+        const HostSinkScaled *s = static_cast<const HostSinkScaled *>(user);
+        const HostSink8 &g = s->g;
+        if (x > g.width || y > g.height) return;
+        const int ww = std::min(g.width - x, 8), wh = std::min(g.height - y, 8);
+        const int p = s->precision, max = (1 << p) - 1;
+        uint8_t *dst = g.out + ((size_t)y * g.width + x) * g.component_count + component_index;
+        for (int dy = 0; dy < wh; dy++) {
+            uint8_t *row = dst + (size_t)dy * g.width * g.component_count;
+            for (int dx = 0; dx < ww; dx++) {
+                const int v = block[dx];
+                if (p >= 8) {
+                    const int t = v >> (p - 8);
+                    row[(size_t)dx * g.component_count] = (uint8_t)(t < 0 ? 0 : (t > 255 ? 255 : t));
+                } else {
+                    row[(size_t)dx * g.component_count] = (uint8_t)expand_bits((uint32_t)(v < 0 ? 0 : (v > max ? max : v)), p);
+                }
+            }
+            block += 8;
+        }
+    }
+};
+
 // JpegBlockAllocator.Flush (JpegBlockAllocator.cs:120-190) from PLANAR_I16 planes: component, block row, block column, only the
 // component's own block grid, sub-sampled components expanded like WriteBlockSlow.
 void flush_planes_to_writer(const BaselineGeometry &g, const ImagePlan &img, const uint8_t *planes, jpgpu_write_block_fn fn, void *user) {
@@ -591,11 +634,11 @@ struct ScanOutcome {
     size_t reader_advance;  // what ProcessScan advances the outer reader by
 };
 
-// Runs one scan job on the GPU and delivers its output.  `direct8` non-null: INTERLEAVED_U8 straight into that
-// buffer (geometry must equal the frame's); else PLANAR_I16 + replay through (fn, user).
-ScanOutcome run_scan_on_gpu(DeviceBatch &batch, const ScanJob &job, uint8_t *direct8, size_t direct8_bytes, jpgpu_write_block_fn fn,
-                            void *user, std::string *err) {
-    const int format = direct8 ? JPGPU_FMT_INTERLEAVED_U8 : JPGPU_FMT_PLANAR_I16;
+// Runs one scan job on the GPU and delivers its output.  `direct8` non-null: `direct_format` (INTERLEAVED_U8 or
+// INTERLEAVED_U8_SCALED) straight into that buffer (geometry must equal the frame's); else PLANAR_I16 + replay through (fn, user).
+ScanOutcome run_scan_on_gpu(DeviceBatch &batch, const ScanJob &job, uint8_t *direct8, size_t direct8_bytes, int direct_format,
+                            jpgpu_write_block_fn fn, void *user, std::string *err) {
+    const int format = direct8 ? direct_format : JPGPU_FMT_PLANAR_I16;
     int rc = batch.upload_single_job(job, format, direct8, direct8_bytes);
     if (rc == JPGPU_OK) rc = batch.decode();
     if (rc == JPGPU_OK) rc = batch.sync();
@@ -727,7 +770,19 @@ struct jpgpu_decoder {
     void *user = nullptr;
     HostSink8 sink8 = {0, 0, 0, nullptr};
     size_t sink8_cap = 0;
+    HostSinkScaled scaled = {{0, 0, 0, nullptr}, 0};  // kBuffer8 with precision != 0: the LessThan8Bit / GreaterThan8Bit writers (sink8 holds the same geometry)
     std::unique_ptr<DeviceBatch> batch;
+
+    // the buffer writer's host form
+    jpgpu_write_block_fn sink_fn() const { return scaled.precision ? HostSinkScaled::write : HostSink8::write; }
+    void *sink_user() { return scaled.precision ? (void *)&scaled : (void *)&sink8; }
+    // The device format that IS the buffer writer for this frame, -1 = none (a callback writer, or a sink whose width, height,
+    // component count -- or, for the two precision-scaled writers, precision -- is not the frame's: host replay).
+    int direct_format(const FrameHeader &fh) const {
+        if (writer != kBuffer8 || sink8.width != fh.samples_per_line || sink8.height != fh.lines || sink8.component_count != fh.num_components) return -1;
+        if (scaled.precision == 0) return JPGPU_FMT_INTERLEAVED_U8;
+        return scaled.precision == fh.precision ? (int)JPGPU_FMT_INTERLEAVED_U8_SCALED : -1;
+    }
 };
 
 namespace {
@@ -760,14 +815,14 @@ class GpuScanHandler final : public ScanHandler {
         if (!d_->batch) d_->batch.reset(new DeviceBatch(d_->ctx));
         const FrameHeader &fh = geo_.frame;
         ScanOutcome oc;
-        const bool direct = d_->writer == jpgpu_decoder::kBuffer8 && d_->sink8.width == fh.samples_per_line && d_->sink8.height == fh.lines &&
-                            d_->sink8.component_count == fh.num_components;
-        if (direct) {
-            oc = run_scan_on_gpu(*d_->batch, job, d_->sink8.out, (size_t)fh.samples_per_line * fh.lines * fh.num_components, nullptr, nullptr, &d_->last_error);
+        const int direct_format = d_->direct_format(fh);
+        if (direct_format >= 0) {
+            oc = run_scan_on_gpu(*d_->batch, job, d_->sink8.out, (size_t)fh.samples_per_line * fh.lines * fh.num_components, direct_format, nullptr, nullptr,
+                                 &d_->last_error);
         } else if (d_->writer == jpgpu_decoder::kBuffer8) {
-            oc = run_scan_on_gpu(*d_->batch, job, nullptr, 0, HostSink8::write, &d_->sink8, &d_->last_error);
+            oc = run_scan_on_gpu(*d_->batch, job, nullptr, 0, 0, d_->sink_fn(), d_->sink_user(), &d_->last_error);
         } else {
-            oc = run_scan_on_gpu(*d_->batch, job, nullptr, 0, d_->fn, d_->user, &d_->last_error);
+            oc = run_scan_on_gpu(*d_->batch, job, nullptr, 0, 0, d_->fn, d_->user, &d_->last_error);
         }
         if (oc.result.status != JPGPU_OK) throw_for_result(oc.result);
         reader.try_advance((int)oc.reader_advance);
@@ -791,9 +846,9 @@ class GpuScanHandler final : public ScanHandler {
         if (!d_->batch) d_->batch.reset(new DeviceBatch(d_->ctx));
         DeviceBatch &batch = *d_->batch;
         const FrameHeader &fh = frame.geo().frame;
-        const bool direct = d_->writer == jpgpu_decoder::kBuffer8 && d_->sink8.width == fh.samples_per_line && d_->sink8.height == fh.lines &&
-                            d_->sink8.component_count == fh.num_components;
-        int rc = batch.upload_progressive_frame(frame, dec.input(), dec.input_len(), sof_, direct ? JPGPU_FMT_INTERLEAVED_U8 : JPGPU_FMT_PLANAR_I16);
+        const int direct_format = d_->direct_format(fh);
+        const bool direct = direct_format >= 0;
+        int rc = batch.upload_progressive_frame(frame, dec.input(), dec.input_len(), sof_, direct ? direct_format : (int)JPGPU_FMT_PLANAR_I16);
         if (rc == JPGPU_OK && direct) {
             // the sink's buffer keeps whatever the caller had outside the decoded area
         }
@@ -814,8 +869,8 @@ class GpuScanHandler final : public ScanHandler {
             } else {
                 std::vector<uint8_t> planes(img.out_bytes);
                 if (batch.download_output(0, planes.data(), planes.size()) != JPGPU_OK) throw DecodeError(JPGPU_ERR_DEVICE, "output download failed");
-                jpgpu_write_block_fn fn = d_->writer == jpgpu_decoder::kBuffer8 ? HostSink8::write : d_->fn;
-                void *user = d_->writer == jpgpu_decoder::kBuffer8 ? (void *)&d_->sink8 : d_->user;
+                jpgpu_write_block_fn fn = d_->writer == jpgpu_decoder::kBuffer8 ? d_->sink_fn() : d_->fn;
+                void *user = d_->writer == jpgpu_decoder::kBuffer8 ? d_->sink_user() : d_->user;
                 flush_planes_to_writer(frame.geo(), img, planes.data(), fn, user);
             }
         }
@@ -956,6 +1011,22 @@ int jpgpu_decoder_set_output_buffer8(jpgpu_decoder *d, int width, int height, in
         d->writer = jpgpu_decoder::kBuffer8;
         d->sink8 = {width, height, component_count, out};
         d->sink8_cap = cap;
+        d->scaled.precision = 0;
+        return JPGPU_OK;
+    });
+}
+int jpgpu_decoder_set_output_buffer8_scaled(jpgpu_decoder *d, int width, int height, int precision, int component_count, uint8_t *out, size_t cap) {
+    return guarded(d, [&] {
+        if (!out) throw DecodeError(JPGPU_ERR_ARGUMENT, "Value cannot be null. (Parameter 'output')");
+        if (width < 0 || height < 0 || component_count <= 0 || cap < (size_t)width * height * component_count)
+            throw DecodeError(JPGPU_ERR_ARGUMENT, "Destination buffer is too small.");  // ref: JpegBufferOutputWriterLessThan8Bit.cs:19-22
+        // (the reference's two constructors accept what their WriteBlock cannot serve: ExpandBits(v, 0) never returns, a shift by more
+        // than 8 leaves no sample bits)
+        if (precision < 1 || precision > 16) throw DecodeError(JPGPU_ERR_ARGUMENT, "Specified argument was out of the range of valid values. (Parameter 'precision')");
+        d->writer = jpgpu_decoder::kBuffer8;
+        d->sink8 = {width, height, component_count, out};
+        d->sink8_cap = cap;
+        d->scaled = {d->sink8, precision};
         return JPGPU_OK;
     });
 }
@@ -978,6 +1049,7 @@ void jpgpu_decoder_reset_tables(jpgpu_decoder *d) {
 void jpgpu_decoder_reset_output_writer(jpgpu_decoder *d) {
     if (d) {
         d->writer = jpgpu_decoder::kNone;
+        d->scaled.precision = 0;
         d->fn = nullptr;
         d->user = nullptr;
     }
@@ -1174,7 +1246,7 @@ int jpgpu_progressive_output_size(jpgpu_progressive *p, int format, size_t *byte
         const FrameHeader &fh = p->frame.geo().frame;
         const BaselineGeometry &g = p->frame.geo();
         size_t n = 0;
-        if (format == JPGPU_FMT_INTERLEAVED_U8) n = (size_t)fh.samples_per_line * fh.lines * fh.num_components;
+        if (fmt_is_sample_bytes(format)) n = (size_t)fh.samples_per_line * fh.lines * fh.num_components;
         else if (format == JPGPU_FMT_RGB_U8) n = (size_t)fh.samples_per_line * fh.lines * 3;
         else if (format == JPGPU_FMT_RGBA_U8) n = (size_t)fh.samples_per_line * fh.lines * 4;
         else if (format == JPGPU_FMT_EXTENDED_U16) n = (size_t)fh.samples_per_line * fh.lines * 8;

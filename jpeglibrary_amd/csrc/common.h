@@ -39,9 +39,12 @@ struct DevScanComponent {
     uint8_t dc_slot, ac_slot; // index into DevScan::huff_pool (LDS slot)
 };
 
-enum OutputFormat : int32_t { kFmtInterleavedU8 = 0, kFmtPlanarU8 = 1, kFmtPlanarI16 = 2, kFmtRgbU8 = 3, kFmtRgbaU8 = 4, kFmtExtendedU16 = 5 };
-constexpr int kNumOutputFormats = 6;
-constexpr bool fmt_is_interleaved(int f) { return f == kFmtInterleavedU8 || f == kFmtRgbU8 || f == kFmtRgbaU8; }
+enum OutputFormat : int32_t { kFmtInterleavedU8 = 0, kFmtPlanarU8 = 1, kFmtPlanarI16 = 2, kFmtRgbU8 = 3, kFmtRgbaU8 = 4, kFmtExtendedU16 = 5, kFmtInterleavedU8Scaled = 6 };
+constexpr int kNumOutputFormats = 7;
+// the two formats that hold one byte per sample of every component, out[(y*W+x)*C + c]: the same geometry, layout classes, clearing
+// and canvas rules; they differ in how a sample becomes its byte only (K3)
+constexpr bool fmt_is_sample_bytes(int f) { return f == kFmtInterleavedU8 || f == kFmtInterleavedU8Scaled; }
+constexpr bool fmt_is_interleaved(int f) { return fmt_is_sample_bytes(f) || f == kFmtRgbU8 || f == kFmtRgbaU8; }
 constexpr int fmt_bytes_per_pixel_rgb(int f) { return f == kFmtRgbaU8 ? 4 : 3; }
 
 // Fixed-point factors of JpegYCbCrToRgbConverter.Init (ref: apps/JpegDecode/JpegYCbCrToRgbConverter.cs:66-118):

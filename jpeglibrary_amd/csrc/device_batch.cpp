@@ -173,7 +173,11 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
     img.restart_interval = geo.restart_interval;
     img.mcus_per_line = (uint32_t)geo.mcus_per_line;
     img.mcus_per_column = (uint32_t)geo.mcus_per_column;
-    if (format_ == JPGPU_FMT_INTERLEAVED_U8) {
+    if (fmt_is_sample_bytes(format_)) {
+        // the two stock writers it follows (JpegBufferOutputWriterLessThan8Bit / GreaterThan8Bit): at P = 0 ExpandBits never ends,
+        // above 16 there is no 16-bit sample to shift -- no behaviour to follow, the image fails by itself
+        if (format_ == JPGPU_FMT_INTERLEAVED_U8_SCALED && (fh.precision < 1 || fh.precision > 16))
+            throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "INTERLEAVED_U8_SCALED is defined for precisions 1..16 only.", kDetailUnsupportedFrame);
         img.out_bytes = (uint64_t)img.width * img.height * img.num_components;
     } else if (format_ == JPGPU_FMT_RGB_U8 || format_ == JPGPU_FMT_RGBA_U8) {
         if (fh.num_components != 1 && fh.num_components != 3)  // apps/JpegDecode/DecodeAction.cs:29-33

@@ -398,7 +398,7 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
                 // a tile whose pixel rows are whole 128-byte lines: neighbouring tiles (other workgroups, other XCDs, other
                 // L2s) never write two halves of one line
                 uint32_t row_bytes = 8u * s.max_h;
-                if (format_ == JPGPU_FMT_INTERLEAVED_U8) row_bytes *= s.frame_components;
+                if (fmt_is_sample_bytes(format_)) row_bytes *= s.frame_components;
                 else if (format_ == JPGPU_FMT_RGB_U8) row_bytes *= 3;
                 else if (format_ == JPGPU_FMT_RGBA_U8) row_bytes *= 4;
                 else if (format_ == JPGPU_FMT_PLANAR_I16 || format_ == JPGPU_FMT_EXTENDED_U16) row_bytes *= 2;
@@ -457,7 +457,7 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
                 for (uint32_t first = 0; first < s.total_mcus; first += run)
                     idct_work_by_class[cls].push_back({(uint32_t)j, first, std::min(run, s.total_mcus - first), mcus_per_wg});
                 // the caller's canvas under a whole-pixel layout: the MCU a failing scan stops in is written block by block
-                if (keep_canvas_ && job.kind == kScanSequential && format_ == JPGPU_FMT_INTERLEAVED_U8 &&
+                if (keep_canvas_ && job.kind == kScanSequential && fmt_is_sample_bytes(format_) &&
                     cls >= 1 && cls <= 3)  // (kLayYccH1V1 / H2V1 / H2V2, k3_idct.hip)
                     idct_partial.push_back({(uint32_t)j, kIdctPartialMcu, 1, ((uint32_t)kIdctBlocksPerWg / s.blocks_per_mcu)});
             }

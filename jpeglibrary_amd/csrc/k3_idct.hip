@@ -85,6 +85,7 @@ __device__ __forceinline__ void block_dequant(const uint8_t *c_lds, uint32_t swz
 
 typedef float float2v __attribute__((ext_vector_type(2)));
 typedef short short2v __attribute__((ext_vector_type(2)));
+typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
 
 // The 8-point butterfly of IDCT8x4_LeftPart/RightPart (ref: FastFloatingPointDCT.cs:79-127) on T = float or a pair of
 // floats (two independent columns at once: v_pk_add_f32 / v_pk_mul_f32, each component one IEEE operation, never fused).
@@ -180,6 +181,53 @@ __device__ __forceinline__ uint32_t clamp2_u8(uint32_t pk) {
 // four clamped samples (two packed pairs) -> four bytes
 __device__ __forceinline__ uint32_t pack4_u8(uint32_t pk01, uint32_t pk23) {
     return __builtin_amdgcn_perm(clamp2_u8(pk23), clamp2_u8(pk01), 0x06040200u);  // bytes 0,2 of pk01 then 0,2 of pk23
+}
+// INTERLEAVED_U8_SCALED: the sample-to-byte step of the reference's other two stock writers, chosen by the frame's precision P
+// the way apps/JpegDecode/DecodeAction.cs:41-54 chooses the writer.  Wave-uniform: the terms live in scalar registers, derived from DevScan::precision.
+//   P >= 8  (byte)Clamp(sample >> (P - 8), 0, 255), an arithmetic shift (JpegBufferOutputWriterGreaterThan8Bit.cs:57,64-67); P = 8 is
+//           the 8-bit writer
+//   P <  8  v = Clamp(sample, 0, 2^P - 1), signed, then ExpandBits(v, P) (JpegBufferOutputWriterLessThan8Bit.cs:59-60, 67-93): its
+//           loop ORs copies of v at multiples of P until at least 8 bits are filled, drops the last copy when that went past 8,
+//           and FastExpandBits fills the rem = 8 % P bits left with the LOW bits of what it holds:
+//             r = v * M,  M = 1 + 2^P + ... (8 / P terms);   byte = (r << rem) | (r & (2^rem - 1))
+//           Nothing exceeds 255 on the way, so the two halves of a packed pair never carry into each other.
+struct ScaleTo8 {
+    uint32_t shift2, max2, mul2, rem2, mask2;  // the same 16-bit value in both halves
+    bool expand;                               // P < 8
+};
+__device__ __forceinline__ ScaleTo8 scale_to_8(uint32_t precision) {
+    // (the host refuses precisions outside 1..16 for this format, DeviceBatch::plan_image_geometry; the clamp keeps the shifts defined)
+    const uint32_t p = precision < 1u ? 1u : (precision > 16u ? 16u : precision);
+    ScaleTo8 k;
+    k.expand = p < 8u;
+    const uint32_t pe = k.expand ? p : 1u;  // (1..7: the terms below are only used then)
+    const uint32_t m = (uint32_t)(0x010101110955FFull >> (8u * (pe - 1u))) & 0xFFu;  // M of P = 1..7: 255, 0x55, 9, 0x11, 1, 1, 1
+    const uint32_t rem = 8u % pe;
+    k.shift2 = (k.expand ? 0u : p - 8u) * 0x00010001u;
+    k.max2 = ((1u << pe) - 1u) * 0x00010001u;
+    k.mul2 = m * 0x00010001u;
+    k.rem2 = rem * 0x00010001u;
+    k.mask2 = ((1u << rem) - 1u) * 0x00010001u;
+    return k;
+}
+// P >= 8, two int16 samples -> two bytes in the low half: v_pk_ashrrev_i16, then the 8-bit writer's signed clamp of both halves
+// and the packing in one instruction (v_sat_pk_u8_i16: {sat_u8(S.i16[1]), sat_u8(S.i16[0])}; no builtin names it).  With the
+// v_perm_b32 that joins two such results, four samples take as many instructions as INTERLEAVED_U8's four clamps and one v_perm.
+__device__ __forceinline__ uint32_t shift_sat2_u8(uint32_t pk, const ScaleTo8 &k) {
+    const uint32_t t = __builtin_bit_cast(uint32_t, __builtin_bit_cast(short2v, pk) >> __builtin_bit_cast(short2v, k.shift2));
+    uint32_t r;
+    asm("v_sat_pk_u8_i16 %0, %1" : "=v"(r) : "v"(t));
+    return r;  // (bytes 0 and 1; the upper half is not used)
+}
+// P < 8, two int16 samples -> two bytes, each in the low byte of its half: v_pk_max_i16, v_pk_min_i16, v_pk_mul_lo_u16,
+// v_pk_lshlrev_b16, v_and_or
+__device__ __forceinline__ uint32_t expand2_u8(uint32_t pk, const ScaleTo8 &k) {
+    short2v v = __builtin_bit_cast(short2v, pk);
+    v = __builtin_elementwise_max(v, short2v{0, 0});
+    v = __builtin_elementwise_min(v, __builtin_bit_cast(short2v, k.max2));
+    const ushort2v r = __builtin_bit_cast(ushort2v, v) * __builtin_bit_cast(ushort2v, k.mul2);
+    const ushort2v hi = r << __builtin_bit_cast(ushort2v, k.rem2);
+    return __builtin_bit_cast(uint32_t, hi) | (__builtin_bit_cast(uint32_t, r) & k.mask2);
 }
 // byte gather from the 8 bytes {lo (indices 0-3), hi (indices 4-7)}: one v_perm_b32
 __device__ __forceinline__ uint32_t pick4(uint32_t lo, uint32_t hi, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
@@ -472,6 +520,7 @@ __device__ __forceinline__ void idct_output_body(
     const int16_t *__restrict__ coefs, const DevScan *__restrict__ scans, const IdctWork *__restrict__ work,
     const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf) {
     constexpr int CONV = FMT == kFmtRgbU8 ? 3 : (FMT == kFmtRgbaU8 ? 4 : 0);  // fused YCbCr -> RGB(A), fast layouts and gray only
+    constexpr bool kSampleBytes = fmt_is_sample_bytes(FMT);  // INTERLEAVED_U8 / _SCALED: one path, two sample-to-byte steps
     __shared__ __attribute__((aligned(16))) uint8_t sh_all[kIdctThreads * 128 + kIdctThreads * 64 + kMaxScanComponents * 128];
     uint8_t *sh = sh_all;
     uint8_t *sh_px = sh_all + kIdctThreads * 128;
@@ -580,7 +629,7 @@ __device__ __forceinline__ void idct_output_body(
         // loop -- and in the three variants with the most state in their output assembly spills five of them to scratch for
         // the length of the transform.  There they are derived again in every tile (sixteen instructions) from a copy of the
         // lane id the compiler cannot see through.
-        constexpr bool kPerTile = (FMT == kFmtRgbU8 && (LAY == kLayYccH2V1 || LAY == kLayYccH2V2)) || (FMT == kFmtInterleavedU8 && LAY == kLayGeneric);
+        constexpr bool kPerTile = (FMT == kFmtRgbU8 && (LAY == kLayYccH2V1 || LAY == kLayYccH2V2)) || (kSampleBytes && LAY == kLayGeneric);
         uint32_t t_ = tid;
         if (kPerTile) asm volatile("" : "+v"(t_));
         if (have_block) block_dequant(sh + t_ * 128, (t_ >> 1) & 7, sh_q[ci_early], f);
@@ -648,10 +697,27 @@ __device__ __forceinline__ void idct_output_body(
     } else {
     // u8 formats: clamp (signed, like JpegBufferOutputWriter8Bit.ClampTo8Bit) and pack 8 samples per row
     uint2 rows[8];
+    if constexpr (FMT == kFmtInterleavedU8Scaled) {
+        const ScaleTo8 k8 = scale_to_8(s.precision);  // (wave-uniform: scalar registers)
+        if (k8.expand) {
+#pragma unroll
+            for (int r = 0; r < 8; r++) {  // bytes 0, 2 of one pair, then 0, 2 of the next
+                rows[r].x = __builtin_amdgcn_perm(expand2_u8(px[r * 4 + 1], k8), expand2_u8(px[r * 4 + 0], k8), 0x06040200u);
+                rows[r].y = __builtin_amdgcn_perm(expand2_u8(px[r * 4 + 3], k8), expand2_u8(px[r * 4 + 2], k8), 0x06040200u);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 8; r++) {  // bytes 0, 1 of one pair, then 0, 1 of the next
+                rows[r].x = __builtin_amdgcn_perm(shift_sat2_u8(px[r * 4 + 1], k8), shift_sat2_u8(px[r * 4 + 0], k8), 0x05040100u);
+                rows[r].y = __builtin_amdgcn_perm(shift_sat2_u8(px[r * 4 + 3], k8), shift_sat2_u8(px[r * 4 + 2], k8), 0x05040100u);
+            }
+        }
+    } else {
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         rows[r].x = pack4_u8(px[r * 4 + 0], px[r * 4 + 1]);
         rows[r].y = pack4_u8(px[r * 4 + 2], px[r * 4 + 3]);
+    }
     }
 
     if (CONV != 0 && LAY == kLayGray) {
@@ -667,11 +733,11 @@ __device__ __forceinline__ void idct_output_body(
                 store_rgb_pixels<8, (CONV == 4 ? 4 : 3)>(out + s.out_off + ((size_t)(y0 + r) * s.width + x0) * (CONV == 4 ? 4 : 3), px);
             }
         }
-    } else if (FMT == kFmtPlanarU8 || (FMT == kFmtInterleavedU8 && LAY == kLayGray)) {
+    } else if (FMT == kFmtPlanarU8 || (kSampleBytes && LAY == kLayGray)) {
         // planar u8 (planes padded to whole MCUs), or a single-component interleaved image (same addressing,
         // pitch = W, clipped at the bottom; the host only picks kLayGray when W is a multiple of 8)
         if (writes) {
-            const bool gray = (FMT == kFmtInterleavedU8);
+            const bool gray = kSampleBytes;
             uint8_t *plane = out + s.out_off + (gray ? 0 : s.plane_off[ci]);
             const uint32_t pitch = gray ? s.width : s.plane_pitch[ci];
             const uint32_t x0 = (mcu_x * comp.h + s.blk_x[b]) * 8, y0 = (mcu_y * comp.v + s.blk_y[b]) * 8;
@@ -788,6 +854,7 @@ hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *
         if (c == kIdctClassStoreHoldsSamples) {  // the generic Dispose() pass has run: the store goes to the writer as it is
             if (format == kFmtPlanarI16) hipLaunchKernelGGL((flush_output_kernel<kFmtPlanarI16>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf);
             else if (format == kFmtPlanarU8) hipLaunchKernelGGL((flush_output_kernel<kFmtPlanarU8>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf);
+            else if (format == kFmtInterleavedU8Scaled) hipLaunchKernelGGL((flush_output_kernel<kFmtInterleavedU8Scaled>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf);
             else hipLaunchKernelGGL((flush_output_kernel<kFmtInterleavedU8>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool,
                                     (format == kFmtRgbU8 || format == kFmtRgbaU8) ? generic_out : out, kf);
         } else if (format == kFmtPlanarI16) {
@@ -810,6 +877,14 @@ hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *
             case kLayYccH2V2: launch_idct_one<kFmtRgbaU8, kLayYccH2V2>(stream, coefs, scans, w, n, status, quant_pool, out, kf); break;
             case kLayGray: launch_idct_one<kFmtRgbaU8, kLayGray>(stream, coefs, scans, w, n, status, quant_pool, out, kf); break;
             default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, status, quant_pool, generic_out); break;
+            }
+        } else if (format == kFmtInterleavedU8Scaled) {
+            switch (c) {
+            case kLayYccH1V1: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH1V1>(stream, coefs, scans, w, n, status, quant_pool, out); break;
+            case kLayYccH2V1: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH2V1>(stream, coefs, scans, w, n, status, quant_pool, out); break;
+            case kLayYccH2V2: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH2V2>(stream, coefs, scans, w, n, status, quant_pool, out); break;
+            case kLayGray: launch_idct_one<kFmtInterleavedU8Scaled, kLayGray>(stream, coefs, scans, w, n, status, quant_pool, out); break;
+            default: launch_idct_one<kFmtInterleavedU8Scaled, kLayGeneric>(stream, coefs, scans, w, n, status, quant_pool, out); break;
             }
         } else {
             switch (c) {
@@ -842,7 +917,7 @@ hipError_t launch_dispose_pass(hipStream_t stream, int16_t *coefs, const Dispose
     return hipGetLastError();
 }
 
-// Layout class of a scan for the INTERLEAVED_U8 format (0 = generic bytewise path).
+// Layout class of a scan for the INTERLEAVED_U8 / INTERLEAVED_U8_SCALED formats (0 = generic bytewise path).
 int idct_layout_class(const DevScan &s) {
     const uint32_t W = s.width;
     if (s.frame_components == 1 && s.scan_components == 1 && s.comp[0].h == 1 && s.comp[0].v == 1 && (W % 8) == 0 && (s.out_off % 8) == 0)

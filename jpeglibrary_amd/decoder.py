@@ -10,7 +10,8 @@ Names, argument meaning and error behaviour follow the reference so that tests r
     decoder.Decode()
 
 ref: src/JpegLibrary/JpegDecoder.cs, src/JpegLibrary/JpegBlockOutputWriter.cs,
-     apps/JpegDecode/JpegBufferOutputWriter8Bit.cs, tests/JpegLibrary.Tests/Utils/JpegExtendingOutputWriter.cs
+     apps/JpegDecode/JpegBufferOutputWriter8Bit.cs, JpegBufferOutputWriterLessThan8Bit.cs, JpegBufferOutputWriterGreaterThan8Bit.cs,
+     tests/JpegLibrary.Tests/Utils/JpegExtendingOutputWriter.cs
 All block arithmetic (Huffman decode, dequantise, IDCT, level shift) runs in the HIP kernels; this module only
 marshals calls.  There is no CPU fallback.
 """
@@ -57,6 +58,87 @@ class JpegBufferOutputWriter8Bit(JpegBlockOutputWriter):
         out = self.output.reshape(-1)[:w * h * cc].reshape(h, w, cc)
         blk = np.asarray(blockRef, dtype=np.int16).reshape(8, 8)[:wh, :ww]
         out[y:y + wh, x:x + ww, componentIndex] = np.clip(blk, 0, 255).astype(np.uint8)
+
+
+class _JpegBufferOutputWriterScaled(JpegBlockOutputWriter):
+    """What the two precision-scaled buffer writers share: the constructor's buffer check and WriteBlock's walk."""
+
+    def __init__(self, width, height, precision, componentCount, output):  # noqa: N803
+        output = np.asarray(output)
+        if output.dtype != np.uint8 or not output.flags["C_CONTIGUOUS"]:
+            raise ArgumentException("output must be a contiguous uint8 array")
+        if output.size < width * height * componentCount:
+            raise ArgumentException("Destination buffer is too small.")
+        self._check_precision(precision)
+        self.width, self.height, self.precision, self.componentCount, self.output = width, height, precision, componentCount, output
+
+    def _to_byte(self, sample):
+        raise NotImplementedError
+
+    def WriteBlock(self, blockRef, componentIndex, x, y):  # noqa: N802,N803
+        componentCount, width, height = self.componentCount, self.width, self.height  # noqa: N806
+        if x > width or y > height:
+            return
+        writeWidth, writeHeight = min(width - x, 8), min(height - y, 8)  # noqa: N806
+        destination = self.output.reshape(-1)
+        block = np.asarray(blockRef, dtype=np.int16).reshape(-1)
+        base = y * width * componentCount + x * componentCount + componentIndex
+        for destY in range(writeHeight):  # noqa: N806
+            row = base + destY * width * componentCount
+            for destX in range(writeWidth):  # noqa: N806
+                destination[row + destX * componentCount] = self._to_byte(int(block[destY * 8 + destX]))
+
+
+class JpegBufferOutputWriterGreaterThan8Bit(_JpegBufferOutputWriterScaled):
+    """ref: apps/JpegDecode/JpegBufferOutputWriterGreaterThan8Bit.cs -- interleaved u8 buffer of a frame of more than 8 bits:
+    (byte)Math.Clamp(sample >> (precision - 8), 0, 255), an arithmetic shift, so a negative sample becomes 0 (:57, :64-67).
+
+    When its geometry AND precision equal the frame's, JpegDecoder produces this layout directly on the GPU
+    (JPGPU_FMT_INTERLEAVED_U8_SCALED) instead of replaying WriteBlock calls.
+    """
+
+    @staticmethod
+    def _check_precision(precision):
+        if precision < 8:  # :22-25
+            raise ArgumentException("Specified argument was out of the range of valid values. (Parameter 'precision')")
+
+    def _to_byte(self, sample):
+        return min(max(sample >> (self.precision - 8), 0), 255)
+
+
+class JpegBufferOutputWriterLessThan8Bit(_JpegBufferOutputWriterScaled):
+    """ref: apps/JpegDecode/JpegBufferOutputWriterLessThan8Bit.cs -- interleaved u8 buffer of a frame of fewer than 8 bits:
+    Math.Clamp(sample, 0, 2^precision - 1) (signed), the bits spread over 8 by ExpandBits (:59-60, :67-93).
+
+    The reference's constructor refuses precision > 8 only; this one refuses precision < 1 as well: at precision 0 the
+    reference would never return from ExpandBits (its loop adds bitCount = 0 to the bit count until it reaches 8), and a
+    negative one shifts by a negative count.  Produced directly on the GPU under the same condition as the class above.
+    """
+
+    @staticmethod
+    def _check_precision(precision):
+        if precision > 8 or precision < 1:  # :23-26
+            raise ArgumentException("Specified argument was out of the range of valid values. (Parameter 'precision')")
+
+    @staticmethod
+    def _fast_expand_bits(bits, bitCount):  # noqa: N803  (:67-73)
+        remainingBits = 8 - bitCount  # noqa: N806
+        return (bits << remainingBits) | (bits & ((1 << remainingBits) - 1))
+
+    @classmethod
+    def _expand_bits(cls, bits, bitCount):  # noqa: N803  (:75-93)
+        currentBitCount = bitCount  # noqa: N806
+        while currentBitCount < 8:
+            bits = (bits << bitCount) | bits
+            currentBitCount += bitCount  # noqa: N806
+        if currentBitCount > 8:
+            bits = bits >> bitCount
+            currentBitCount -= bitCount  # noqa: N806
+            bits = cls._fast_expand_bits(bits, currentBitCount)
+        return bits
+
+    def _to_byte(self, sample):
+        return self._expand_bits(min(max(sample, 0), (1 << self.precision) - 1), self.precision) & 0xFF
 
 
 class JpegExtendingOutputWriter(JpegBlockOutputWriter):
@@ -390,6 +472,12 @@ class JpegDecoder:
         if type(outputWriter) is JpegBufferOutputWriter8Bit:
             w = outputWriter
             self._check(_lib.jpgpu_decoder_set_output_buffer8(self._h, w.width, w.height, w.componentCount, w.output.ctypes.data, w.output.size))
+            self._cb = None
+            return
+        if type(outputWriter) in (JpegBufferOutputWriterGreaterThan8Bit, JpegBufferOutputWriterLessThan8Bit) and 1 <= outputWriter.precision <= 16:
+            w = outputWriter
+            self._check(_lib.jpgpu_decoder_set_output_buffer8_scaled(self._h, w.width, w.height, w.precision, w.componentCount, w.output.ctypes.data,
+                                                                     w.output.size))
             self._cb = None
             return
 
