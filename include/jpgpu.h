@@ -305,6 +305,11 @@ int jpgpu_batch_result(jpgpu_batch *b, int i, jpgpu_image_result *res);
  * the batch owns the buffer, and zero is what a freshly allocated managed array holds.  (jpgpu_decode_scan, which
  * decodes over the caller's own samples, leaves them alone.) */
 void *jpgpu_batch_output_device(const jpgpu_batch *b, uint64_t *total_bytes);
+/* The coefficient pointer holds dense int16[blocks][64] at every image's coef_offset.  Scans the Huffman stage handed to the IDCT stage in
+ * another form are expanded into a dense copy first: the call then waits for the batch's device work, allocates (on first use) a second
+ * buffer of the coefficient store's size and copies the store into it, and the pointer is that copy's, good until the next entropy stage or
+ * upload.  NULL if that wait, allocation or copy fails (jpgpu_last_error says why).  *total_blocks counts the buffer's blocks, padding
+ * between images included.  (The handle is const for compatibility; the call may change the batch's buffers as described.) */
 void *jpgpu_batch_coefficients_device(const jpgpu_batch *b, uint64_t *total_blocks);
 /* Copies one image's output / coefficient blocks (int16[blocks][64], zig-zag order, MCU scan order) to the host.  (A progressive
  * frame whose Dispose() is taken literally -- component slots that do not cover every component once, the partial flush of a

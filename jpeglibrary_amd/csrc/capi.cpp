@@ -431,7 +431,9 @@ int jpgpu_batch_image_info(const jpgpu_batch *b, int i, jpgpu_image_info *info) 
 
 int jpgpu_batch_result(jpgpu_batch *b, int i, jpgpu_image_result *res) { JPGPU_GUARD(b, b->impl.result(i, res)); }
 void *jpgpu_batch_output_device(const jpgpu_batch *b, uint64_t *total_bytes) { return b ? b->impl.output_device(total_bytes) : nullptr; }
-void *jpgpu_batch_coefficients_device(const jpgpu_batch *b, uint64_t *total_blocks) { return b ? b->impl.coefs_device(total_blocks) : nullptr; }
+void *jpgpu_batch_coefficients_device(const jpgpu_batch *b, uint64_t *total_blocks) {
+    return b ? const_cast<jpgpu_batch *>(b)->impl.coefs_device(total_blocks) : nullptr;  // (may expand split scans into the dense copy first)
+}
 int jpgpu_batch_download_output(jpgpu_batch *b, int i, void *dst, size_t cap) { JPGPU_GUARD(b, b->impl.download_output(i, dst, cap)); }
 int jpgpu_batch_download_coefficients(jpgpu_batch *b, int i, int16_t *dst, size_t cap_blocks) {
     JPGPU_GUARD(b, b->impl.download_coefficients(i, dst, cap_blocks));

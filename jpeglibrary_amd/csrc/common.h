@@ -80,6 +80,8 @@ struct alignas(16) DevScan {
     uint16_t huff_pool[kMaxHuffSlots];   // pool indices of the tables this scan stages (0xFFFF = unused)
     uint16_t quant_pool[kMaxScanComponents];
     uint64_t reserved0;  // bit 0 (kScanStoreHoldsSamples): the frame's store holds samples by the time K3 runs (generic Dispose() pass)
+                         // bit 1 (kScanSplitHandoff): K2 hands this scan's coefficients to K3 as half-line planes (below); then bits
+                         // 8..63 = the scan's first flag word, in uint64 units from the start of the coefficient buffer
     uint32_t chunk_off;  // first entry of this scan in the chunk-summary array (K1)
     uint32_t n_chunks;   // 4 KiB chunks covering the entropy segment (from its 16-byte aligned base)
     uint32_t sub_off;    // DRI = 0 scans: first slot of this scan in the subsequence state arrays (K2S)
@@ -114,6 +116,29 @@ constexpr uint32_t kNoDep = 0xFFFFFFFFu;
 constexpr uint32_t kFailBlockBase = 0xFFFFFFFFu;
 constexpr uint32_t kIdctPartialMcu = 0xFFFFFFFFu;  // IdctWork::first_mcu: "the MCU the scan failed in" (the caller's canvas under a fast layout)
 constexpr uint64_t kScanStoreHoldsSamples = 1;
+// The half-line planes of a sequential scan with restart intervals (K2 -> K3).  The scan's region of the coefficient buffer, padded to an
+// even count of whole intervals, is a LO plane and a HI plane of 64-byte slots: coefficients 0..31 and 32..63 of a block.  Block b of MCU m
+// (inside its interval) of restart interval i has slot split_slot(): one 128-byte line holds the same block of intervals 2p and 2p + 1, the
+// two lanes of a K2 wave that are flushed side by side.  One flag word per (chunk of 64 intervals, m, b), bit i & 63: "the block has a
+// non-zero coefficient in 32..63".  The hi slot of an unflagged block holds nothing and is never read.
+constexpr uint64_t kScanSplitHandoff = 2;
+constexpr int kSplitFlagShift = 8;
+constexpr uint64_t kSplitMaxBytesPerBlock = 8;  // the planner splits a scan whose entropy data is no more than this per block (JPGPU_DENSE_HANDOFF unset)
+constexpr uint64_t kSplitZeroWords = 16;  // 128 zero bytes in front of every split scan's flag words (K3's source for the hi half of an unflagged block)
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define JPGPU_HD __host__ __device__
+#else
+#define JPGPU_HD
+#endif
+JPGPU_HD inline uint64_t split_plane_lines(uint32_t n_intervals, uint32_t dri, uint32_t bpm) { return (uint64_t)((n_intervals + 1) / 2) * dri * bpm; }
+JPGPU_HD inline uint64_t split_region_blocks(uint32_t n_intervals, uint32_t dri, uint32_t bpm) { return 2 * split_plane_lines(n_intervals, dri, bpm); }
+JPGPU_HD inline uint64_t split_flag_words(uint32_t n_intervals, uint32_t dri, uint32_t bpm) { return (uint64_t)((n_intervals + 63) / 64) * dri * bpm; }
+JPGPU_HD inline uint64_t split_slot(uint32_t i, uint32_t m, uint32_t b, uint32_t dri, uint32_t bpm) {
+    return ((((uint64_t)(i >> 1) * dri + m) * bpm + b) << 1) | (i & 1u);
+}
+JPGPU_HD inline uint64_t split_flag_word(uint32_t i, uint32_t m, uint32_t b, uint32_t dri, uint32_t bpm) {
+    return ((uint64_t)(i >> 6) * dri + m) * bpm + b;
+}
 // The reference's Dispose() taken literally for one progressive frame (dispose_pass_kernel): component c of the frame is
 // transformed n[c] times in place, with the quantisation tables of the decoder's component slots that point at it, in slot order.
 struct alignas(16) DisposeJob {

@@ -151,10 +151,7 @@ class DeviceBatch {
         if (total) *total = out_bytes_;
         return d_out_.ptr;
     }
-    void *coefs_device(uint64_t *total_blocks) const {
-        if (total_blocks) *total_blocks = total_blocks_;
-        return d_coefs_.ptr;
-    }
+    void *coefs_device(uint64_t *total_blocks);  // dense int16[blocks][64], whatever form K2 handed the scans over in
     int download_output(int i, void *dst, size_t cap);
     int download_coefficients(int i, int16_t *dst, size_t cap_blocks);
     int upload_coefficients(int i, const int16_t *src, size_t nblocks);
@@ -240,6 +237,18 @@ class DeviceBatch {
     int n_huff_work_ = 0, n_idct_work_ = 0;
     int idct_class_begin_[kNumIdctLayoutClasses + 1] = {};
     std::vector<int> idct_later_begin_;  // d_idct_work_ behind the classes: [k], [k + 1]) = the k-th ordered launch (run_idct)
+    // Sequential scans with restart intervals are handed from K2 to K3 as half-line planes (common.h: kScanSplitHandoff; the planner
+    // decides per scan, JPGPU_DENSE_HANDOFF=1 keeps every scan dense).  Everything else that reads coefficients wants dense blocks:
+    // dense_coefs() expands the split scans into d_dense_ (same offsets; lazily, once per entropy stage).  A caller that uploads
+    // coefficients makes the dense copy the batch's store and every scan dense until the next upload of files.
+    std::vector<uint32_t> split_scans_;
+    uint32_t split_max_blocks_ = 0;
+    uint64_t coef_store_blocks_ = 0;  // the coefficient buffer's blocks: total_blocks_ + the padding of split scans
+    int idct_split_begin_class_[kNumIdctLayoutClasses] = {};  // d_idct_work_: where the split scans' entries of each class begin
+    bool dense_valid_ = false, dense_override_ = false;
+    DevBuffer d_dense_, d_split_ids_;
+    int dense_coefs(const int16_t **ptr);
+    int make_store_dense();
     uint64_t total_blocks_ = 0, out_bytes_ = 0, planes_bytes_ = 0, input_bytes_ = 0, compressed_bytes_ = 0, total_pixels_ = 0;
     DevBuffer d_planes_;  // EXTENDED_U16: K3's PLANAR_I16 output, converted by extend_u16_kernel
     DevBuffer d_extend_desc_;

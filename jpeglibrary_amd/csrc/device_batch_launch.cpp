@@ -45,6 +45,7 @@ int DeviceBatch::run_huffman() {
     status_valid_ = false;
     redo_.clear();
     dispose_done_ = false;  // (the stores hold coefficients again)
+    dense_valid_ = false;   // (... and the dense copy of the split scans is the last decode's)
     hipError_t e = launch_huffman(ctx_->stream, (const uint8_t *)d_unstuffed_.ptr, (const DevScan *)d_scans_.ptr, (const HuffWork *)d_huff_work_.ptr,
                                   n_huff_work_, (const uint32_t *)d_ends_u_.ptr, (DevScanStatus *)d_status_.ptr,
                                   (const DevHuffTable *)d_huff_pool_.ptr, (int16_t *)d_coefs_.ptr, n_huff_slots_, (const uint8_t *)d_lut_pool_.ptr, k2_tab_bytes_);
@@ -257,7 +258,7 @@ int DeviceBatch::run_idct() {
     hipError_t e = launch_idct(ctx_->stream, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const IdctWork *)d_idct_work_.ptr,
                                idct_class_begin_, (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr,
                                extended ? (uint8_t *)d_planes_.ptr : (uint8_t *)d_out_.ptr, extended ? (int)JPGPU_FMT_PLANAR_I16 : format_, kf,
-                               (uint8_t *)d_rgb_scratch_.ptr);
+                               (uint8_t *)d_rgb_scratch_.ptr, split_scans_.empty() || dense_override_ ? nullptr : idct_split_begin_class_);
     if (e != hipSuccess) return hip_fail(e, "idct_output_kernel");
     // scans ordered behind earlier scans of their image (and the failing MCU of a caller's canvas): one bytewise launch per level
     for (size_t lv = 0; lv + 1 < idct_later_begin_.size(); lv++) {

@@ -140,6 +140,15 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
     dispose_max_blocks_ = 0;
     std::vector<IdctWork> idct_work;
     std::vector<IdctWork> idct_work_by_class[kNumIdctLayoutClasses];
+    std::vector<IdctWork> idct_split_by_class[kNumIdctLayoutClasses];  // scans handed over as half-line planes: the split form of K3
+    split_scans_.clear();
+    split_max_blocks_ = 0;
+    dense_valid_ = dense_override_ = false;
+    // JPGPU_DENSE_HANDOFF: 1 = every scan dense, 0 = split wherever K3 has the form, unset = ... and the content promises a gain (below)
+    const char *split_env = getenv("JPGPU_DENSE_HANDOFF");
+    const bool split_wanted = !(split_env && atoi(split_env) != 0) && !entropy_only_ && !keep_canvas_;
+    const bool split_always = split_env != nullptr;
+    uint64_t real_blocks = 0, flag_words = 0;
     std::vector<std::vector<IdctWork>> idct_later_levels;  // scans ordered behind earlier scans of their image: one launch per level
     std::vector<IdctWork> idct_partial;                     // "the MCU the scan failed in", bytewise (the caller's canvas)
     std::vector<int> scan_level(jobs_.size(), 0);
@@ -369,6 +378,7 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
             const uint64_t nblocks = (uint64_t)s.mcus_per_line * s.mcus_per_column * s.blocks_per_mcu;
             if (job.kind == kScanFrameOnly && !img.replay_skip) prog_clear_.push_back({coef_off, nblocks});
             coef_off += nblocks;
+            real_blocks += nblocks;
             img.total_blocks += nblocks;
             compressed_bytes_ += s.data_len;
             // scans without restart intervals are decoded by the self-synchronising subsequence decoder (K2S)
@@ -390,6 +400,24 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
                 }
             } else {
                 for (uint32_t first = 0; first < s.n_intervals && !img.replay_skip; first += huff_intervals_per_wg) huff_work.push_back({(uint32_t)j, first});
+                // Half-line planes for the scans K2's interval decoder writes, where the image is this one scan: its region is the
+                // image's, and the padding (an even count of whole intervals) goes behind it.  (The scans of a multi-scan image lie back
+                // to back in one dense run of the image's blocks, which is what the coefficient readers hand out: they stay dense.)
+                const int k3_class = fmt_is_interleaved(format_) ? idct_layout_class(s) : 0;
+                if (split_wanted && job.kind == kScanSequential && s.dri != 0 && img.jobs.size() == 1 && !img.replay_skip && s.total_mcus > 0 &&
+                    s.blocks_per_mcu != 0 && idct_split_supported(format_, k3_class) &&
+                    // The planes pay where few blocks reach into coefficients 32..63; all that is known of that in front of the decode is
+                    // how many bytes of entropy data a block has.  Q75 content has 5.4 (3 % of the blocks flagged; the step 4.9 % faster),
+                    // Q85 8.7, Q90 12.3 (66 % flagged: K2 gains 0.12 ms, K3 loses 0.19: 1.8 % slower) -- RESULTS.md, first section.
+                    (split_always || (uint64_t)s.data_len <= nblocks * kSplitMaxBytesPerBlock)) {
+                    // (in front of every scan's flag words, one whole line: the zero bytes K3 fetches for unflagged blocks)
+                    flag_words = (flag_words + kSplitZeroWords - 1) / kSplitZeroWords * kSplitZeroWords + kSplitZeroWords;
+                    s.reserved0 |= kScanSplitHandoff | (flag_words << kSplitFlagShift);  // (the buffer-relative base is added below)
+                    flag_words += split_flag_words(s.n_intervals, s.dri, s.blocks_per_mcu);
+                    coef_off += split_region_blocks(s.n_intervals, s.dri, s.blocks_per_mcu) - nblocks;
+                    split_scans_.push_back((uint32_t)j);
+                    split_max_blocks_ = std::max<uint32_t>(split_max_blocks_, (uint32_t)nblocks);
+                }
             }
             if (img.replay_skip) continue;  // (its samples are in the output buffer already)
             if (s.blocks_per_mcu == 0) continue;  // cannot happen for a resolved scan (sampling factors are checked); no blocks, no work
@@ -454,8 +482,9 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
                     if (!listed) rgb_convert_.push_back({(uint32_t)ii, img.out_offset, (uint64_t)img.width * img.height, img.num_components});
                 }
             } else {
+                std::vector<IdctWork> &list = (s.reserved0 & kScanSplitHandoff) ? idct_split_by_class[cls] : idct_work_by_class[cls];
                 for (uint32_t first = 0; first < s.total_mcus; first += run)
-                    idct_work_by_class[cls].push_back({(uint32_t)j, first, std::min(run, s.total_mcus - first), mcus_per_wg});
+                    list.push_back({(uint32_t)j, first, std::min(run, s.total_mcus - first), mcus_per_wg});
                 // the caller's canvas under a whole-pixel layout: the MCU a failing scan stops in is written block by block
                 if (keep_canvas_ && job.kind == kScanSequential && fmt_is_sample_bytes(format_) &&
                     cls >= 1 && cls <= 3)  // (kLayYccH1V1 / H2V1 / H2V2, k3_idct.hip)
@@ -469,7 +498,10 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
         dj.n_blocks = fs.total_mcus * (uint32_t)fs.blocks_per_mcu;
         dispose_max_blocks_ = std::max(dispose_max_blocks_, dj.n_blocks);
     }
-    total_blocks_ = coef_off;
+    total_blocks_ = real_blocks;
+    coef_store_blocks_ = coef_off;
+    // the flag words of the split scans lie behind the blocks and the tile of slack, in the same buffer
+    for (uint32_t j : split_scans_) h_scans_[j].reserved0 += ((coef_store_blocks_ + (uint64_t)kIdctBlocksPerWg) * 16) << kSplitFlagShift;
     out_bytes_ = out_off;
     planes_bytes_ = planes_off;
     total_ends_ = ends_off;
@@ -673,6 +705,10 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
         std::vector<IdctWork> &w = idct_work_by_class[c];
         xcd_interleave(w, xcds);
         idct_work.insert(idct_work.end(), w.begin(), w.end());
+        idct_split_begin_class_[c] = (int)idct_work.size();
+        std::vector<IdctWork> &ws = idct_split_by_class[c];
+        xcd_interleave(ws, xcds);
+        idct_work.insert(idct_work.end(), ws.begin(), ws.end());
         idct_class_begin_[c + 1] = (int)idct_work.size();
     }
     n_idct_work_ = (int)idct_work.size();
@@ -696,7 +732,7 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
         // and cannot share a CU (K2 takes 159 KB of its 160 KB LDS), so the halves time-slice instead of overlapping:
         // 16.39-16.52 ms overlapped vs 16.16-16.37 ms serial per 1024 x 4K (gpurun r02e, both issue orders below)
         const char *ev = getenv("JPGPU_OVERLAP");
-        const bool wanted = ev && atoi(ev) != 0 && dispose_jobs_.empty();  // (the generic Dispose() pass is issued by run_idct alone)
+        const bool wanted = ev && atoi(ev) != 0 && dispose_jobs_.empty() && split_scans_.empty();  // (the generic Dispose() pass is issued by run_idct alone)
         uint32_t split_image = 0;
         uint64_t acc = 0;
         for (size_t ii = 0; ii < images_.size() && acc * 2 < total_blocks_; ii++) {
@@ -776,7 +812,9 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
         {&d_ends_, nullptr, 0, (size_t)total_ends_ * sizeof(uint32_t) + 256},
         {&d_ends_u_, nullptr, 0, (size_t)total_ends_ * sizeof(uint32_t) + 256},
         {&d_unstuffed_, nullptr, 0, (size_t)input_bytes_},
-        {&d_coefs_, nullptr, 0, entropy_only_ ? 256 : (size_t)total_blocks_ * 128 + (size_t)kIdctBlocksPerWg * 128 + 256},  // + one tile of slack (IDCT DMA reads whole tiles)
+        {&d_split_ids_, split_scans_.data(), split_scans_.size() * sizeof(uint32_t), 16},
+        // + one tile of slack (IDCT DMA reads whole tiles) + the split scans' flag words
+        {&d_coefs_, nullptr, 0, entropy_only_ ? 256 : (size_t)coef_store_blocks_ * 128 + (size_t)kIdctBlocksPerWg * 128 + (size_t)flag_words * 8 + 256},
         {&d_out_, nullptr, 0, entropy_only_ ? 256 : (size_t)out_bytes_ + 256},
         {&d_rgb_scratch_, nullptr, 0, rgb_convert_.empty() ? 0 : (size_t)out_bytes_ + 256},
         {&d_planes_, nullptr, 0, format_ == JPGPU_FMT_EXTENDED_U16 && !entropy_only_ ? (size_t)planes_bytes_ + 256 : 0},
@@ -789,6 +827,10 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
             e = hipMemcpyAsync(u.buf->ptr, u.src, u.bytes, hipMemcpyHostToDevice, up);
             if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(descriptors)");
         }
+    }
+    if (!split_scans_.empty()) {  // the flag region starts from zero: the zero bytes in front of every scan's words stay so (K2 writes flag words only)
+        e = hipMemsetAsync((uint8_t *)d_coefs_.ptr + ((size_t)coef_store_blocks_ + (size_t)kIdctBlocksPerWg) * 128, 0, (size_t)flag_words * 8, up);
+        if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(hand-off flags)");
     }
     e = hipMemsetAsync(d_k2_tickets_.ptr, 0, kK2MaxPools * sizeof(uint32_t), up);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(K2 tickets)");

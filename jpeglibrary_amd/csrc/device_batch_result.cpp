@@ -317,8 +317,54 @@ int DeviceBatch::download_coefficients(int i, int16_t *dst, size_t cap_blocks) {
     }
     int rc = (replay_possible_ && !replay_done_) ? fetch_status() : sync();
     if (rc != JPGPU_OK) return rc;
-    hipError_t e = hipMemcpy(dst, (const int16_t *)d_coefs_.ptr + img->coef_offset * 64, img->total_blocks * 128, hipMemcpyDeviceToHost);
+    const int16_t *coefs = nullptr;
+    if ((rc = dense_coefs(&coefs)) != JPGPU_OK) return rc;
+    hipError_t e = hipMemcpy(dst, coefs + img->coef_offset * 64, img->total_blocks * 128, hipMemcpyDeviceToHost);
     return e == hipSuccess ? JPGPU_OK : hip_fail(e, "hipMemcpy(coefficients)");
+}
+
+// The batch's coefficients as dense blocks.  Without split scans (or once a caller has uploaded coefficients) that is the store itself;
+// otherwise a copy of it with the split scans expanded, made once per entropy stage.  The device work of the batch has been waited for.
+int DeviceBatch::dense_coefs(const int16_t **ptr) {
+    *ptr = (const int16_t *)d_coefs_.ptr;
+    if (split_scans_.empty() || dense_override_ || !d_coefs_.ptr) return JPGPU_OK;
+    if (!dense_valid_) {
+        const size_t bytes = (size_t)coef_store_blocks_ * 128;
+        hipError_t e = d_dense_.reserve(bytes + (size_t)kIdctBlocksPerWg * 128 + 256);  // (it may become the store: same slack)
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc(dense coefficients)");
+        e = hipMemcpyAsync(d_dense_.ptr, d_coefs_.ptr, bytes, hipMemcpyDeviceToDevice, ctx_->stream);  // the dense scans as they are
+        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(dense coefficients)");
+        e = launch_expand_handoff(ctx_->stream, (const int16_t *)d_coefs_.ptr, (int16_t *)d_dense_.ptr, (const DevScan *)d_scans_.ptr,
+                                  (const uint32_t *)d_split_ids_.ptr, (int)split_scans_.size(), split_max_blocks_);
+        if (e != hipSuccess) return hip_fail(e, "expand_handoff_kernel");
+        e = hipStreamSynchronize(ctx_->stream);
+        if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(dense coefficients)");
+        dense_valid_ = true;
+    }
+    *ptr = (const int16_t *)d_dense_.ptr;
+    return JPGPU_OK;
+}
+
+// A caller is about to overwrite coefficients: from here to the next upload of files the store is dense throughout -- the dense copy
+// takes the store's place, every scan's descriptor says dense, K2 and K3 follow the descriptors.
+int DeviceBatch::make_store_dense() {
+    if (split_scans_.empty() || dense_override_) return JPGPU_OK;
+    const int16_t *coefs = nullptr;
+    const int rc = dense_coefs(&coefs);
+    if (rc != JPGPU_OK) return rc;
+    std::swap(d_coefs_, d_dense_);
+    for (uint32_t j : split_scans_) h_scans_[j].reserved0 &= kScanStoreHoldsSamples;
+    hipError_t e = hipMemcpy(d_scans_.ptr, h_scans_.data(), h_scans_.size() * sizeof(DevScan), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy(scan descriptors)");
+    dense_override_ = true;
+    return JPGPU_OK;
+}
+
+void *DeviceBatch::coefs_device(uint64_t *total_blocks) {
+    if (total_blocks) *total_blocks = coef_store_blocks_;
+    const int16_t *coefs = (const int16_t *)d_coefs_.ptr;
+    if (!split_scans_.empty() && !dense_override_ && (sync() != JPGPU_OK || dense_coefs(&coefs) != JPGPU_OK)) return nullptr;
+    return (void *)coefs;
 }
 
 int DeviceBatch::upload_coefficients(int i, const int16_t *src, size_t nblocks) {
@@ -329,6 +375,7 @@ int DeviceBatch::upload_coefficients(int i, const int16_t *src, size_t nblocks) 
     dispose_done_ = false;
     int rc = sync();
     if (rc != JPGPU_OK) return rc;
+    if ((rc = make_store_dense()) != JPGPU_OK) return rc;
     hipError_t e = hipMemcpy((int16_t *)d_coefs_.ptr + img->coef_offset * 64, src, nblocks * 128, hipMemcpyHostToDevice);
     return e == hipSuccess ? JPGPU_OK : hip_fail(e, "hipMemcpy(coefficients)");
 }

@@ -147,6 +147,13 @@ __device__ __forceinline__ void k2_wave(const uint8_t *__restrict__ udata, const
 
     // flush addressing: lane (blk, chunk) of pass `it` stores 16 bytes of the block staged by lane blk
     const uint64_t coef_off = s.coef_off;
+    // ... or, for a scan handed over as half-line planes (common.h: kScanSplitHandoff; wave-uniform), 16 bytes of a 64-byte slot
+    const bool split = (s.reserved0 & kScanSplitHandoff) != 0;
+    uint8_t *split_lo = reinterpret_cast<uint8_t *>(coefs + coef_off * 64);
+    const uint64_t split_hi_off = split_plane_lines(n_intervals, dri_eff, bpm) * 128;
+    uint64_t *split_flags = reinterpret_cast<uint64_t *>(coefs) + (s.reserved0 >> kSplitFlagShift) + (uint64_t)(wave_first >> 6) * dri_eff * bpm;
+    uint32_t split_step = 0;  // mcu * bpm + b
+    uint64_t my_flags = 0;
 
     for (uint32_t mcu = 0; mcu < wave_mcus; mcu++) {
         for (uint32_t b = 0; b < bpm; b++) {
@@ -192,22 +199,61 @@ __device__ __forceinline__ void k2_wave(const uint8_t *__restrict__ udata, const
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (!split) {
 #pragma unroll
-            for (int it = 0; it < 8; it++) {
-                const uint32_t blk = it * 8 + (lane >> 3);
-                const uint32_t chunk = lane & 7;
-                uint4 *src = reinterpret_cast<uint4 *>(stage + blk * 128 + ((chunk ^ ((blk >> 1) & 7)) * 16));
-                const uint4 v = *src;
-                const uint4 z = {0, 0, 0, 0};
-                *src = z;
-                const uint32_t owner = wave_first + blk;
-                if (owner < n_ends) {
-                    const uint32_t owner_mcus = (owner == n_intervals - 1) ? total_mcus - owner * dri_eff : dri_eff;
-                    if (mcu < owner_mcus) {
-                        const uint64_t block_index = coef_off + ((uint64_t)owner * dri_eff + mcu) * bpm + b;
-                        *reinterpret_cast<uint4 *>(coefs + block_index * 64 + chunk * 8) = v;
+                for (int it = 0; it < 8; it++) {
+                    const uint32_t blk = it * 8 + (lane >> 3);
+                    const uint32_t chunk = lane & 7;
+                    uint4 *src = reinterpret_cast<uint4 *>(stage + blk * 128 + ((chunk ^ ((blk >> 1) & 7)) * 16));
+                    const uint4 v = *src;
+                    const uint4 z = {0, 0, 0, 0};
+                    *src = z;
+                    const uint32_t owner = wave_first + blk;
+                    if (owner < n_ends) {
+                        const uint32_t owner_mcus = (owner == n_intervals - 1) ? total_mcus - owner * dri_eff : dri_eff;
+                        if (mcu < owner_mcus) {
+                            const uint64_t block_index = coef_off + ((uint64_t)owner * dri_eff + mcu) * bpm + b;
+                            *reinterpret_cast<uint4 *>(coefs + block_index * 64 + chunk * 8) = v;
+                        }
                     }
                 }
+            } else {
+                // half-line planes: lanes 8j .. 8j + 7 of a pass hold blocks 2p, 2p + 1 = restart intervals 2p, 2p + 1: one whole line of the
+                // lo plane, and -- when either block has a non-zero coefficient in 32..63 -- the same line of the hi plane
+                uint64_t step_flags = 0;
+#pragma unroll
+                for (int it = 0; it < 4; it++) {
+                    const uint32_t blk = it * 16 + (lane >> 2);
+                    const uint32_t chunk = lane & 3;
+                    const uint32_t swz = (blk >> 1) & 7;
+                    uint4 *src_lo = reinterpret_cast<uint4 *>(stage + blk * 128 + ((chunk ^ swz) * 16));
+                    uint4 *src_hi = reinterpret_cast<uint4 *>(stage + blk * 128 + (((chunk + 4) ^ swz) * 16));
+                    const uint4 v = *src_lo, w = *src_hi;
+                    const uint4 z = {0, 0, 0, 0};
+                    *src_lo = z;
+                    *src_hi = z;
+                    const uint64_t nz = __ballot((w.x | w.y | w.z | w.w) != 0);  // four lanes per block, eight per line
+                    // a line is written where its even interval has this MCU (the odd one is its equal or the scan's short last one)
+                    const uint32_t even = wave_first + (blk & ~1u);
+                    const bool have = even < n_ends && mcu < ((even == n_intervals - 1) ? total_mcus - even * dri_eff : dri_eff);
+                    const uint64_t off = split_slot(wave_first + blk, mcu, b, dri_eff, bpm) * 64 + chunk * 16;
+                    if (have) *reinterpret_cast<uint4 *>(split_lo + off) = v;
+                    if (have && ((nz >> (lane & ~7u)) & 0xFFu) != 0) *reinterpret_cast<uint4 *>(split_lo + split_hi_off + off) = w;
+                    // the sixteen blocks' flags: a nibble of the ballot each -> a bit each
+                    uint64_t x = nz | (nz >> 1);
+                    x = (x | (x >> 2)) & 0x1111111111111111ull;
+                    x = (x | (x >> 3)) & 0x0303030303030303ull;
+                    x = (x | (x >> 6)) & 0x000F000F000F000Full;
+                    x = (x | (x >> 12)) & 0x000000FF000000FFull;
+                    x = (x | (x >> 24)) & 0xFFFFull;
+                    step_flags |= x << (16 * it);
+                }
+                // the step's flag word stays in the lane whose index is the step's; 64 of them (or the chunk's last ones) go out in one store
+                if (lane == (split_step & 63u)) my_flags = step_flags;
+                if ((split_step & 63u) == 63u || split_step + 1 == wave_mcus * bpm) {
+                    if (lane <= (split_step & 63u)) split_flags[(split_step & ~63u) + lane] = my_flags;
+                }
+                split_step++;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();

@@ -28,6 +28,13 @@ __device__ constexpr uint8_t kNat[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24,
 
 // The 8-point butterfly of IDCT8x4_LeftPart/RightPart (ref: FastFloatingPointDCT.cs:79-127), one column.
 // Operation order and parenthesisation are normative.
+// ceil(65536 / n), n = 1 .. kMaxBlocksPerMcu (the split form's block -> MCU arithmetic)
+// The split form divides by multiplying (idct_output_body: sp_rb, sp_rd, sp_rw); the ranges those reciprocals are exact for rest on these:
+// a tile is at most 256 blocks (block and MCU numbers inside it < 256, its lines < 128) of at most 16 per MCU.
+static_assert(kIdctBlocksPerWg == 256, "the split form's reciprocals are exact for tiles of up to 256 blocks");
+static_assert(kMaxBlocksPerMcu == 16, "kRecip16 and the 16-bit reciprocals of the split form cover 1..16 blocks per MCU");
+__device__ constexpr uint32_t kRecip16[kMaxBlocksPerMcu + 1] = {0, 65536, 32768, 21846, 16384, 13108, 10923, 9363, 8192, 7282, 6554, 5958, 5462, 5042, 4682, 4370, 4096};
+
 #define JPGPU_IDCT8(y0, y1, y2, y3, y4, y5, y6, y7)                     \
     {                                                                   \
         float mz0 = y1 + y7;                                            \
@@ -515,7 +522,9 @@ typedef const __attribute__((address_space(1))) void jpgpu_gbl_void;
 
 // PRE: the store already holds SAMPLES (the generic Dispose() pass of a progressive frame whose component slots do not map one
 // to one onto its components, dispose_pass_kernel below): no dequantisation, no transform -- the block goes to the writer as it lies
-template <int FMT, int LAY, bool PRE>
+// SPLIT: the scans of this launch were handed over as half-line planes (dma_tile below); a kernel name of its own, because the sixteen
+// dense variants have no register to spare for a branch
+template <int FMT, int LAY, bool PRE, bool SPLIT = false>
 __device__ __forceinline__ void idct_output_body(
     const int16_t *__restrict__ coefs, const DevScan *__restrict__ scans, const IdctWork *__restrict__ work,
     const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf) {
@@ -581,10 +590,122 @@ __device__ __forceinline__ void idct_output_body(
     // (slot ^ swizzle(block)); the swizzle term ((block >> 1) & 7) does not depend on k, so every lane's source is
     // one fixed offset plus k * 4096.  Always a full tile: the coefficient buffer has a tile of slack behind it.
     const uint32_t tile_blocks = mcus_per_tile * bpm;
-    auto dma_tile = [&](uint32_t tile_first) {
+    // A scan handed over as half-line planes (common.h: kScanSplitHandoff).  The LDS side is the same; a lane's source is a 64-byte slot
+    // -- lo plane for pieces 0..3, hi plane for pieces 4..7 of a flagged block; the hi pieces of an unflagged block are zeros, fetched
+    // from the scan's zero line or written by the lane (dma_tile).  The flag bytes of a tile are fetched two tiles ahead, behind the
+    // transform, and arrive under the wait the DMA has anyway (fetched as the byte that holds the block's bit, kept as one bit per block).
+    constexpr bool split = SPLIT && !PRE;
+    if (split && (s.reserved0 & kScanSplitHandoff) == 0) return;  // (the host lists split scans apart: never taken)
+    const uint32_t sp_dri = split ? s.dri : 1u;
+    // Reciprocals for the block -> (MCU, interval) arithmetic.  (Wave-uniform, but a division leaves its result in a vector register: moved
+    // to scalar ones, none is held across the transform.  The first from a table: a division of such small numbers is done in float, with
+    // a fused multiply-add the parity claim's ISA test would count.)
+    const uint32_t sp_rb = kRecip16[bpm <= (uint32_t)kMaxBlocksPerMcu ? bpm : 0];  // blk / bpm == blk * sp_rb >> 16 for blk < 256, bpm <= 16
+    const uint32_t sp_rd = __builtin_amdgcn_readfirstlane(sp_dri <= 256u ? ((1u << 20) + sp_dri - 1) / sp_dri : 0u);  // x / dri == x * sp_rd >> 20 for x < dri + 256 <= 512
+    // Tiles of whole PAIRS of intervals (the headline: 40 MCUs = five pairs of DRI = 4) are one contiguous run of slots in either plane: the
+    // DMA then takes them in slot order -- a base plus constants, as the dense form does -- and the lane finds ITS block in the staging
+    // instead (sp_own_block).  Other tiles gather block by block (sp_locate).
+    const uint32_t sp_w = sp_dri * bpm;  // blocks of one interval
+    const bool sp_fast = split && mcus_per_tile % (2 * sp_dri) == 0 && first_mcu % (2 * sp_dri) == 0;
+    const uint32_t sp_rw = __builtin_amdgcn_readfirstlane((65536u + sp_w - 1) / sp_w);  // x / sp_w == x * sp_rw >> 16 for x < 128, sp_w <= 128
+    const uint8_t *sp_hi = coef_bytes + split_plane_lines(s.n_intervals, sp_dri, bpm) * 128;
+    const uint8_t *sp_flags = reinterpret_cast<const uint8_t *>(reinterpret_cast<const uint64_t *>(coefs) + (s.reserved0 >> kSplitFlagShift));
+    // block k * 32 + (t >> 3) of the tile at tile_first: its line in either plane, its restart interval, its flag word.  No branches: the
+    // eight flag loads of a tile are to be issued back to back, and so are its sixteen DMAs
+    auto sp_locate = [&](uint32_t tile_first, uint32_t t, int k, uint32_t &line, uint32_t &iv, uint32_t &word) {
+        const uint32_t i0 = __builtin_amdgcn_readfirstlane(tile_first / sp_dri), m0 = tile_first - i0 * sp_dri;  // (wave-uniform)
+        const uint32_t blk = (uint32_t)k * 32 + (t >> 3);
+        uint32_t q = (blk * sp_rb) >> 16;
+        const uint32_t bb = blk - q * bpm;
+        const uint32_t last = s.total_mcus - 1 - tile_first;  // lanes behind the scan's last MCU fetch that MCU's blocks: never past the region
+        q = q < last ? q : last;
+        const uint32_t mm = m0 + q;
+        const uint32_t by_mul = (mm * sp_rd) >> 20, by_cmp = mm >= sp_dri ? 1u : 0u;
+        const uint32_t qi = sp_dri > 256u ? by_cmp : by_mul;
+        const uint32_t m = mm - qi * sp_dri;
+        iv = i0 + qi;
+        line = ((iv >> 1) * sp_dri + m) * bpm + bb;
+        word = ((iv >> 6) * sp_dri + m) * bpm + bb;
+    };
+    // tiles of whole pairs: every DMA instruction takes 16 lines = 32 slots, the even intervals' slots into staging blocks k * 32 + 0..15 and
+    // the odd intervals' into k * 32 + 16..31 -- the blocks of one interval, which neighbouring lanes dequantise, then lie side by side as
+    // they do in the dense form, and the staging's swizzle keeps their reads apart.  Staging block k * 32 + (t >> 3): its interval, flag word
+    auto sp_locate_fast = [&](uint32_t i0, uint32_t t, int k, uint32_t &iv, uint32_t &word) {  // i0: the tile's first interval (even)
+        const uint32_t ll = (uint32_t)k * 16 + ((t >> 3) & 15u);                  // line of the tile
+        const uint32_t pp = (ll * sp_rw) >> 16;
+        iv = i0 + 2 * pp + ((t >> 7) & 1u);
+        iv = iv < s.n_intervals ? iv : s.n_intervals - 1;  // (slots behind the scan's last interval: any flag will do, inside the scan's words)
+        word = (iv >> 6) * sp_w + (ll - pp * sp_w);
+    };
+    // ... and where the lane's own block (MCU t / bpm of the tile, block t % bpm) lies in that staging
+    auto sp_own_block = [&](uint32_t t) {
+        const uint32_t ml = (t * sp_rb) >> 16, bb = t - ml * bpm;
+        const uint32_t ir = (ml * sp_rd) >> 20, m = ml - ir * sp_dri;  // (2 * dri <= MCUs per tile: the reciprocal holds)
+        const uint32_t ll = ((ir >> 1) * sp_dri + m) * bpm + bb;
+        return ((ll >> 4) << 5) | ((ir & 1u) << 4) | (ll & 15u);
+    };
+    // (the first interval of a tile of whole pairs, without a division per tile: sp_i0 is that of the tile in the staging)
+    const uint32_t sp_ipt = __builtin_amdgcn_readfirstlane(mcus_per_tile / sp_dri);
+    uint32_t sp_i0 = __builtin_amdgcn_readfirstlane(first_mcu / sp_dri);
+    // (every lane loads, the lanes of lo pieces too: a byte its neighbours load anyway, and no branch around the loads)
+    auto sp_load_flags = [&](uint32_t tile_first, uint32_t tile_i0, uint32_t (&fb)[8], uint32_t &bit_at) {
+        uint32_t t_ = tid;
+        asm volatile("" : "+v"(t_));
+        bit_at = 0;  // three bits per k: where in its byte the block's bit is
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            uint32_t line, iv, word;
+            if (sp_fast) sp_locate_fast(tile_i0, t_, k, iv, word);
+            else sp_locate(tile_first, t_, k, line, iv, word);
+            fb[k] = sp_flags[word * 8 + ((iv >> 3) & 7u)];  // (a scan's flag words are fewer than 2^29)
+            bit_at |= (iv & 7u) << (3 * k);
+        }
+    };
+    // -> bit k: block k * 32 + (tid >> 3) of the tile is flagged (one register from here to the tile's DMA)
+    auto sp_pack_flags = [&](uint32_t (&fb)[8], uint32_t bit_at) {
+        uint32_t bits = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            asm volatile("" : "+v"(fb[k]));  // (stays behind the wait in front of it)
+            bits |= ((fb[k] >> ((bit_at >> (3 * k)) & 7u)) & 1u) << k;
+        }
+        return bits;
+    };
+    auto dma_tile = [&](uint32_t tile_first, uint32_t tile_i0, uint32_t hi_bits) {
         // (recomputed per tile, three instructions, rather than kept in a register across the transform)
         uint32_t t_ = tid;
         asm volatile("" : "+v"(t_));
+        if (split && sp_fast) {
+            // every lane fetches: an unflagged block's hi pieces come from the 128 zero bytes in front of the scan's flag words (a line that
+            // never leaves the L1), so the sixteen DMAs go out without a branch between them and nothing is written to the staging by hand
+            const uint32_t piece = (t_ & 7) ^ ((t_ >> 4) & 7);
+            const uint32_t slot = ((t_ >> 3) & 15u) * 2 + (t_ >> 7);  // of the instruction's 32
+            const uint8_t *src = (piece < 4 ? coef_bytes : sp_hi) + (uint64_t)(tile_i0 >> 1) * sp_w * 128 + (slot * 64 + (piece & 3u) * 16);
+            const uint8_t *zeros = sp_flags - 128 + (piece & 3u) * 16;
+            const uint32_t fetch_bits = piece < 4 ? 0xFFu : hi_bits;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const uint8_t *from = ((fetch_bits >> k) & 1u) ? src + (uint32_t)(k * 2048) : zeros;
+                if (k < 6 || (uint32_t)k * 32 + slot < tile_blocks)  // slots behind the tile's last block are not fetched
+                    __builtin_amdgcn_global_load_lds((jpgpu_gbl_void *)from, (jpgpu_lds_void *)(sh + ((uint32_t)k * kIdctThreads + wave * 64) * 16), 16, 0, 0);
+            }
+            return;
+        }
+        if (split) {
+            const uint32_t piece = (t_ & 7) ^ ((t_ >> 4) & 7);
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                uint32_t line, iv, word;
+                sp_locate(tile_first, t_, k, line, iv, word);
+                const bool wanted = k < 6 || (uint32_t)k * 32 + (t_ >> 3) < tile_blocks;  // blocks behind the tile's last MCU are not fetched
+                const bool fetch = wanted && (piece < 4 || ((hi_bits >> k) & 1u) != 0);
+                const uint8_t *src = (piece < 4 ? coef_bytes : sp_hi) + ((uint64_t)line * 128 + (iv & 1u) * 64 + (piece & 3u) * 16);
+                if (fetch)
+                    __builtin_amdgcn_global_load_lds((jpgpu_gbl_void *)src, (jpgpu_lds_void *)(sh + ((uint32_t)k * kIdctThreads + wave * 64) * 16), 16, 0, 0);
+                if (wanted && !fetch) *reinterpret_cast<uint4 *>(sh + ((uint32_t)k * kIdctThreads + t_) * 16) = uint4{0, 0, 0, 0};
+            }
+            return;
+        }
         const uint32_t dma_lane_off = (t_ >> 3) * 128 + (((t_ & 7) ^ ((t_ >> 4) & 7)) * 16);
         const uint8_t *src = coef_bytes + (uint64_t)tile_first * bpm * 128;  // wave-uniform
 #pragma unroll
@@ -594,7 +715,20 @@ __device__ __forceinline__ void idct_output_body(
                                                  (jpgpu_lds_void *)(sh + ((uint32_t)k * kIdctThreads + wave * 64) * 16), 16, 0, 0);
     };
 
-    dma_tile(first_mcu);
+    uint32_t hi_next = 0;  // split scans: the flag bits of the tile behind the one in the staging
+    if (split) {
+        uint32_t fb[8], at;
+        sp_load_flags(first_mcu, sp_i0, fb, at);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        hi_next = sp_pack_flags(fb, at);
+    }
+    dma_tile(first_mcu, sp_i0, hi_next);
+    if (split && first_mcu + mcus_per_tile < range_end) {
+        uint32_t fb[8], at;
+        sp_load_flags(first_mcu + mcus_per_tile, sp_i0 + sp_ipt, fb, at);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        hi_next = sp_pack_flags(fb, at);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -629,17 +763,24 @@ __device__ __forceinline__ void idct_output_body(
         // loop -- and in the three variants with the most state in their output assembly spills five of them to scratch for
         // the length of the transform.  There they are derived again in every tile (sixteen instructions) from a copy of the
         // lane id the compiler cannot see through.
-        constexpr bool kPerTile = (FMT == kFmtRgbU8 && (LAY == kLayYccH2V1 || LAY == kLayYccH2V2)) || (kSampleBytes && LAY == kLayGeneric);
+        constexpr bool kPerTile = split || (FMT == kFmtRgbU8 && (LAY == kLayYccH2V1 || LAY == kLayYccH2V2)) || (kSampleBytes && LAY == kLayGeneric);
         uint32_t t_ = tid;
         if (kPerTile) asm volatile("" : "+v"(t_));
+        if (split && sp_fast) t_ = sp_own_block(t_);  // (the staging is in slot order)
         if (have_block) block_dequant(sh + t_ * 128, (t_ >> 1) & 7, sh_q[ci_early], f);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every lane holds its coefficients: the staging can be refilled
-    if (have_next) dma_tile(next_first);  // in flight during the whole transform below
+    if (have_next) dma_tile(next_first, sp_i0 + sp_ipt, hi_next);  // in flight during the whole transform below
+    hi_next = 0;  // (dead from here to the flag bytes behind the transform)
 
     // phase B2: IDCT entirely in registers
     if (!PRE && have_block) block_idct(f, (int32_t)s.level_shift, px);
+    // split scans: the flag bytes of the tile after the next one, fetched behind the transform (f[] is dead) and waited for where the DMA is
+    uint32_t sp_fb[8], sp_at = 0;
+    const bool sp_ahead = split && next_first + mcus_per_tile < range_end;
+    if (sp_ahead) sp_load_flags(next_first + mcus_per_tile, sp_i0 + 2 * sp_ipt, sp_fb, sp_at);
+    sp_i0 += sp_ipt;
     // (a frame has fewer than 2^32 blocks: 32-bit arithmetic; computed behind the transform, nothing more alive across it)
     const bool reached = mcu < decoded && mcu * bpm + b < fail_block;
     if ((s.shadow_mask & 0xFu) == 0) {
@@ -681,13 +822,15 @@ __device__ __forceinline__ void idct_output_body(
     const uint32_t mcu_y = mcu_late / s.mcus_per_line, mcu_x = mcu_late - mcu_y * s.mcus_per_line;
     const uint32_t ci = s.blk_comp[b_late < kMaxBlocksPerMcu ? b_late : 0];  // (again: one byte from the L1-resident descriptor)
     const DevScanComponent comp = s.comp[ci];
+    // (the split form indexes the block's place with the late copy: an address derived from `b` would be held across the whole tile loop)
+    const uint32_t b_out = split ? b_late : b;
 
     if (FMT == kFmtPlanarI16) {
         // "O1": unclamped int16 at component-native resolution, planes padded to whole MCUs
         if (writes) {
             int16_t *plane = reinterpret_cast<int16_t *>(out + s.out_off + s.plane_off[ci]);
             const uint32_t pitch = s.plane_pitch[ci];
-            const uint32_t x0 = (mcu_x * comp.h + s.blk_x[b]) * 8, y0 = (mcu_y * comp.v + s.blk_y[b]) * 8;
+            const uint32_t x0 = (mcu_x * comp.h + s.blk_x[b_out]) * 8, y0 = (mcu_y * comp.v + s.blk_y[b_out]) * 8;
 #pragma unroll
             for (int r = 0; r < 8; r++) {
                 const uint4 v = {px[r * 4 + 0], px[r * 4 + 1], px[r * 4 + 2], px[r * 4 + 3]};
@@ -723,7 +866,7 @@ __device__ __forceinline__ void idct_output_body(
     if (CONV != 0 && LAY == kLayGray) {
         // a single-component image as R = G = B = Y (Cb = Cr = 128 contribute nothing, DecodeAction.cs:57-65)
         if (writes) {
-            const uint32_t x0 = (mcu_x * comp.h + s.blk_x[b]) * 8, y0 = (mcu_y * comp.v + s.blk_y[b]) * 8;
+            const uint32_t x0 = (mcu_x * comp.h + s.blk_x[b_out]) * 8, y0 = (mcu_y * comp.v + s.blk_y[b_out]) * 8;
 #pragma unroll
             for (int r = 0; r < 8; r++) {
                 if (y0 + r >= s.height) continue;
@@ -740,7 +883,7 @@ __device__ __forceinline__ void idct_output_body(
             const bool gray = kSampleBytes;
             uint8_t *plane = out + s.out_off + (gray ? 0 : s.plane_off[ci]);
             const uint32_t pitch = gray ? s.width : s.plane_pitch[ci];
-            const uint32_t x0 = (mcu_x * comp.h + s.blk_x[b]) * 8, y0 = (mcu_y * comp.v + s.blk_y[b]) * 8;
+            const uint32_t x0 = (mcu_x * comp.h + s.blk_x[b_out]) * 8, y0 = (mcu_y * comp.v + s.blk_y[b_out]) * 8;
 #pragma unroll
             for (int r = 0; r < 8; r++)
                 if (!gray || y0 + r < s.height) *reinterpret_cast<uint2 *>(plane + (size_t)(y0 + r) * pitch + x0) = rows[r];
@@ -755,6 +898,7 @@ __device__ __forceinline__ void idct_output_body(
     // issued (vmcnt retires in order: waiting later would also wait for those stores to drain), then one barrier
     // publishes both the sample tile and the refilled staging.
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+    if (sp_ahead) hi_next = sp_pack_flags(sp_fb, sp_at);
     __builtin_amdgcn_s_barrier();
     synced = true;
 
@@ -764,6 +908,7 @@ __device__ __forceinline__ void idct_output_body(
 
     if (!synced) {  // planar / gray paths: publish the refilled staging
         asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+        if (sp_ahead) hi_next = sp_pack_flags(sp_fb, sp_at);
         __builtin_amdgcn_s_barrier();
     }
   }  // tile loop
@@ -782,11 +927,50 @@ hipError_t launch_extend_u16(hipStream_t stream, const uint8_t *planes, uint8_t 
 }
 
 
+// A scan handed over as half-line planes, written out as the dense int16[blocks][64] every reader outside K3 expects (coefficient
+// download, the device pointer, a caller about to overwrite coefficients): lo slot + hi slot of a flagged block, zeros for the hi half of
+// an unflagged one.  Same offsets in both buffers; eight lanes per block.
+__global__ __launch_bounds__(256) void expand_handoff_kernel(const int16_t *__restrict__ coefs, int16_t *__restrict__ dense,
+                                                             const DevScan *__restrict__ scans, const uint32_t *__restrict__ scan_ids) {
+    const DevScan &s = scans[scan_ids[blockIdx.y]];
+    const uint32_t bpm = s.blocks_per_mcu, dri = s.dri;
+    const uint32_t n_blocks = s.total_mcus * bpm;
+    const uint8_t *lo = reinterpret_cast<const uint8_t *>(coefs + s.coef_off * 64);
+    const uint8_t *hi = lo + split_plane_lines(s.n_intervals, dri, bpm) * 128;
+    const uint64_t *flags = reinterpret_cast<const uint64_t *>(coefs) + (s.reserved0 >> kSplitFlagShift);
+    const uint32_t piece = threadIdx.x & 7;
+    for (uint32_t g = blockIdx.x * 32 + (threadIdx.x >> 3); g < n_blocks; g += gridDim.x * 32) {
+        const uint32_t mcu = g / bpm, b = g - mcu * bpm;
+        const uint32_t i = mcu / dri, m = mcu - i * dri;
+        const uint64_t off = split_slot(i, m, b, dri, bpm) * 64 + (piece & 3) * 16;
+        uint4 v = {0, 0, 0, 0};
+        if (piece < 4) v = *reinterpret_cast<const uint4 *>(lo + off);
+        else if ((flags[split_flag_word(i, m, b, dri, bpm)] >> (i & 63u)) & 1u) v = *reinterpret_cast<const uint4 *>(hi + off);
+        *reinterpret_cast<uint4 *>(dense + (s.coef_off + g) * 64 + piece * 8) = v;
+    }
+}
+hipError_t launch_expand_handoff(hipStream_t stream, const int16_t *coefs, int16_t *dense, const DevScan *scans, const uint32_t *scan_ids, int n_scans,
+                                 uint32_t max_blocks) {
+    if (n_scans <= 0 || max_blocks == 0) return hipSuccess;
+    const uint32_t bx = (uint32_t)std::min<uint64_t>(((uint64_t)max_blocks + 31) / 32, 2048);
+    for (int base = 0; base < n_scans; base += 65535) {  // grid.y limit
+        const int n = n_scans - base < 65535 ? n_scans - base : 65535;
+        hipLaunchKernelGGL(expand_handoff_kernel, dim3(bx, (uint32_t)n), dim3(256), 0, stream, coefs, dense, scans, scan_ids + base);
+    }
+    return hipGetLastError();
+}
+
 template <int FMT, int LAY>
 __global__ __launch_bounds__(kIdctThreads, (FMT == kFmtPlanarI16 ? 2 : 3)) void idct_output_kernel(
     const int16_t *__restrict__ coefs, const DevScan *__restrict__ scans, const IdctWork *__restrict__ work,
     const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf) {
     idct_output_body<FMT, LAY, false>(coefs, scans, work, status, quant_pool, out, kf);
+}
+template <int FMT, int LAY>
+__global__ __launch_bounds__(kIdctThreads, (FMT == kFmtPlanarI16 ? 2 : 3)) void idct_split_kernel(
+    const int16_t *__restrict__ coefs, const DevScan *__restrict__ scans, const IdctWork *__restrict__ work,
+    const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf) {
+    idct_output_body<FMT, LAY, false, true>(coefs, scans, work, status, quant_pool, out, kf);
 }
 template <int FMT>
 __global__ __launch_bounds__(kIdctThreads, 2) void flush_output_kernel(
@@ -836,20 +1020,29 @@ __global__ __launch_bounds__(64) void dispose_pass_kernel(int16_t *__restrict__ 
 }
 
 template <int FMT, int LAY>
-static void launch_idct_one(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work, int n_work,
+static void launch_idct_one(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work, int n_work, int n_dense,
                             const DevScanStatus *status, const DevQuantTable *quant_pool, uint8_t *out,
                             YccRgbFactors kf = YccRgbFactors{0, 0, 0, 0}) {
-    hipLaunchKernelGGL((idct_output_kernel<FMT, LAY>), dim3(n_work), dim3(kIdctThreads), 0, stream, coefs, scans, work, status,
-                       quant_pool, out, kf);
+    // the first n_dense entries: scans with dense coefficient blocks; the rest: scans handed over as half-line planes
+    if (n_dense > 0)
+        hipLaunchKernelGGL((idct_output_kernel<FMT, LAY>), dim3(n_dense), dim3(kIdctThreads), 0, stream, coefs, scans, work, status,
+                           quant_pool, out, kf);
+    if constexpr (idct_split_supported(FMT, LAY))  // (the planner lists no split scan under another format and class)
+      if (n_work > n_dense)
+        hipLaunchKernelGGL((idct_split_kernel<FMT, LAY>), dim3(n_work - n_dense), dim3(kIdctThreads), 0, stream, coefs, scans, work + n_dense, status,
+                           quant_pool, out, kf);
 }
 
-// work is sorted by layout class; class_begin[c]..class_begin[c+1] are the workgroups of class c.
+// work is sorted by layout class; class_begin[c]..class_begin[c+1] are the workgroups of class c, and from split_begin[c] on (where
+// given) those of scans handed over as half-line planes.
 hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
                        const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status,
-                       const DevQuantTable *quant_pool, uint8_t *out, int format, const YccRgbFactors &kf, uint8_t *generic_out) {
+                       const DevQuantTable *quant_pool, uint8_t *out, int format, const YccRgbFactors &kf, uint8_t *generic_out,
+                       const int *split_begin) {
     for (int c = 0; c < kNumIdctLayoutClasses; c++) {
         const int n = class_begin[c + 1] - class_begin[c];
         if (n <= 0) continue;
+        const int nd = split_begin ? split_begin[c] - class_begin[c] : n;
         const IdctWork *w = work + class_begin[c];
         if (c == kIdctClassStoreHoldsSamples) {  // the generic Dispose() pass has run: the store goes to the writer as it is
             if (format == kFmtPlanarI16) hipLaunchKernelGGL((flush_output_kernel<kFmtPlanarI16>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf);
@@ -858,41 +1051,41 @@ hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *
             else hipLaunchKernelGGL((flush_output_kernel<kFmtInterleavedU8>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool,
                                     (format == kFmtRgbU8 || format == kFmtRgbaU8) ? generic_out : out, kf);
         } else if (format == kFmtPlanarI16) {
-            launch_idct_one<kFmtPlanarI16, kLayGeneric>(stream, coefs, scans, w, n, status, quant_pool, out);
+            launch_idct_one<kFmtPlanarI16, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, out);
         } else if (format == kFmtPlanarU8) {
-            launch_idct_one<kFmtPlanarU8, kLayGeneric>(stream, coefs, scans, w, n, status, quant_pool, out);
+            launch_idct_one<kFmtPlanarU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, out);
         } else if (format == kFmtRgbU8) {
             switch (c) {
-            case kLayYccH1V1: launch_idct_one<kFmtRgbU8, kLayYccH1V1>(stream, coefs, scans, w, n, status, quant_pool, out, kf); break;
-            case kLayYccH2V1: launch_idct_one<kFmtRgbU8, kLayYccH2V1>(stream, coefs, scans, w, n, status, quant_pool, out, kf); break;
-            case kLayYccH2V2: launch_idct_one<kFmtRgbU8, kLayYccH2V2>(stream, coefs, scans, w, n, status, quant_pool, out, kf); break;
-            case kLayGray: launch_idct_one<kFmtRgbU8, kLayGray>(stream, coefs, scans, w, n, status, quant_pool, out, kf); break;
+            case kLayYccH1V1: launch_idct_one<kFmtRgbU8, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
+            case kLayYccH2V1: launch_idct_one<kFmtRgbU8, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
+            case kLayYccH2V2: launch_idct_one<kFmtRgbU8, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
+            case kLayGray: launch_idct_one<kFmtRgbU8, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
             // no fused path: the samples go to `generic_out` as INTERLEAVED_U8 and are converted by launch_ycc_to_rgb
-            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, status, quant_pool, generic_out); break;
+            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
             }
         } else if (format == kFmtRgbaU8) {
             switch (c) {
-            case kLayYccH1V1: launch_idct_one<kFmtRgbaU8, kLayYccH1V1>(stream, coefs, scans, w, n, status, quant_pool, out, kf); break;
-            case kLayYccH2V1: launch_idct_one<kFmtRgbaU8, kLayYccH2V1>(stream, coefs, scans, w, n, status, quant_pool, out, kf); break;
-            case kLayYccH2V2: launch_idct_one<kFmtRgbaU8, kLayYccH2V2>(stream, coefs, scans, w, n, status, quant_pool, out, kf); break;
-            case kLayGray: launch_idct_one<kFmtRgbaU8, kLayGray>(stream, coefs, scans, w, n, status, quant_pool, out, kf); break;
-            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, status, quant_pool, generic_out); break;
+            case kLayYccH1V1: launch_idct_one<kFmtRgbaU8, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
+            case kLayYccH2V1: launch_idct_one<kFmtRgbaU8, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
+            case kLayYccH2V2: launch_idct_one<kFmtRgbaU8, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
+            case kLayGray: launch_idct_one<kFmtRgbaU8, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
+            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
             }
         } else if (format == kFmtInterleavedU8Scaled) {
             switch (c) {
-            case kLayYccH1V1: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH1V1>(stream, coefs, scans, w, n, status, quant_pool, out); break;
-            case kLayYccH2V1: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH2V1>(stream, coefs, scans, w, n, status, quant_pool, out); break;
-            case kLayYccH2V2: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH2V2>(stream, coefs, scans, w, n, status, quant_pool, out); break;
-            case kLayGray: launch_idct_one<kFmtInterleavedU8Scaled, kLayGray>(stream, coefs, scans, w, n, status, quant_pool, out); break;
-            default: launch_idct_one<kFmtInterleavedU8Scaled, kLayGeneric>(stream, coefs, scans, w, n, status, quant_pool, out); break;
+            case kLayYccH1V1: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
+            case kLayYccH2V1: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
+            case kLayYccH2V2: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
+            case kLayGray: launch_idct_one<kFmtInterleavedU8Scaled, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
+            default: launch_idct_one<kFmtInterleavedU8Scaled, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
             }
         } else {
             switch (c) {
-            case kLayYccH1V1: launch_idct_one<kFmtInterleavedU8, kLayYccH1V1>(stream, coefs, scans, w, n, status, quant_pool, out); break;
-            case kLayYccH2V1: launch_idct_one<kFmtInterleavedU8, kLayYccH2V1>(stream, coefs, scans, w, n, status, quant_pool, out); break;
-            case kLayYccH2V2: launch_idct_one<kFmtInterleavedU8, kLayYccH2V2>(stream, coefs, scans, w, n, status, quant_pool, out); break;
-            case kLayGray: launch_idct_one<kFmtInterleavedU8, kLayGray>(stream, coefs, scans, w, n, status, quant_pool, out); break;
-            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, status, quant_pool, out); break;
+            case kLayYccH1V1: launch_idct_one<kFmtInterleavedU8, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
+            case kLayYccH2V1: launch_idct_one<kFmtInterleavedU8, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
+            case kLayYccH2V2: launch_idct_one<kFmtInterleavedU8, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
+            case kLayGray: launch_idct_one<kFmtInterleavedU8, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
+            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
             }
         }
         const hipError_t e = hipGetLastError();

@@ -70,12 +70,28 @@ constexpr int kNumIdctLayoutClasses = 6;
 constexpr int kIdctClassStoreHoldsSamples = 5;  // frames whose generic Dispose() pass has run (any format): flush_output_kernel
 // Output layout class of a scan for INTERLEAVED_U8 (0 = generic bytewise path, else a specialised kernel).
 int idct_layout_class(const DevScan &s);
+// Has K3 a form that reads half-line planes (idct_split_kernel) for this output format and layout class?  Not where the output assembly
+// of the dense form already takes every register the occupancy allows -- the bytewise generic layout of the interleaved formats, RGB_U8
+// from 4:2:2 / 4:2:0, RGBA_U8 from 4:2:0, the scaled sink's gray layout -- the flag bytes held across it would go to scratch: those
+// scans stay dense.
+constexpr bool idct_split_supported(int format, int layout_class) {
+    if (format == kFmtPlanarI16 || format == kFmtPlanarU8 || format == kFmtExtendedU16) return true;
+    if (layout_class == 0 || layout_class >= kIdctClassStoreHoldsSamples) return false;
+    if (format == kFmtRgbU8) return layout_class == 1 || layout_class == 4;
+    if (format == kFmtRgbaU8) return layout_class != 3;
+    if (format == kFmtInterleavedU8Scaled) return layout_class != 4;
+    return true;
+}
 // work is sorted by layout class; class_begin[c]..class_begin[c+1] are the workgroups of class c.
 // RGB / RGBA formats: classes with a fused conversion write `out`; the generic class writes INTERLEAVED_U8 samples into
 // `generic_out` (same offsets), to be converted by launch_ycc_to_rgb.
 hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
                        const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status,
-                       const DevQuantTable *quant_pool, uint8_t *out, int format, const YccRgbFactors &kf, uint8_t *generic_out);
+                       const DevQuantTable *quant_pool, uint8_t *out, int format, const YccRgbFactors &kf, uint8_t *generic_out,
+                       const int *split_begin = nullptr);
+// a scan K2 handed over as half-line planes (common.h: kScanSplitHandoff) -> dense int16[blocks][64] at the same offsets of `dense`
+hipError_t launch_expand_handoff(hipStream_t stream, const int16_t *coefs, int16_t *dense, const DevScan *scans, const uint32_t *scan_ids, int n_scans,
+                                 uint32_t max_blocks);
 // the reference's Dispose() taken literally (frames whose component slots do not map one to one onto their components)
 hipError_t launch_dispose_pass(hipStream_t stream, int16_t *coefs, const DisposeJob *jobs, int n_jobs, uint32_t max_blocks, const DevQuantTable *quant_pool);
 hipError_t launch_ycc_to_rgb(hipStream_t stream, const uint8_t *src, uint8_t *dst, uint64_t n_pixels, int comps, int bpp, const YccRgbFactors &kf);
