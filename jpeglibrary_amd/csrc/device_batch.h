@@ -178,6 +178,28 @@ class DeviceBatch {
     int fail(int status, const std::string &msg);
     int hip_fail(hipError_t e, const char *what);
     int layout_and_upload(const std::vector<const uint8_t *> &file_ptr, const std::vector<size_t> &file_len);
+    // its stages, in the order they run (device_batch_layout.cpp); UploadPlan is what one stage hands the next
+    struct UploadPlan;
+    void reset_upload_state(const UploadPlan &p);
+    void choose_batch_shapes(UploadPlan &p);
+    uint16_t huff_index(UploadPlan &p, const HuffTable &t);
+    uint16_t quant_index(const QuantTable &t);
+    void plan_image(UploadPlan &p, size_t ii, const std::vector<size_t> &file_len);  // per scan job: the five below
+    void fill_scan(UploadPlan &p, size_t ii, int j, size_t file_len);
+    void plan_dispose_job(int j, bool listed);
+    void plan_progressive_scan(UploadPlan &p, const ImagePlan &img, int j);
+    void plan_entropy_work(UploadPlan &p, size_t ii, int j);
+    void plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlapping_scans);
+    void list_rgb_convert(size_t ii);
+    void resolve_offsets(UploadPlan &p);
+    void pool_huffman_runs(UploadPlan &p);
+    void plan_subseq_lists(UploadPlan &p);
+    void assemble_progressive_lists(UploadPlan &p);
+    void plan_output_clears();
+    void assemble_idct_lists(UploadPlan &p);
+    void plan_overlap_halves(UploadPlan &p);
+    void init_status();
+    int upload_plan(const UploadPlan &p, const std::vector<const uint8_t *> &file_ptr, const std::vector<size_t> &file_len);
     void plan_image_geometry(ImagePlan &img, const BaselineGeometry &geo) const;
     // ingest (jpgpu_batch_upload), see device_batch.cpp
     struct FilePlan;
@@ -343,9 +365,9 @@ class DeviceBatch {
     static constexpr int kSerialEvery = 8;
     bool overlap_ok_ = false;
     int decodes_since_query_ = 0;
-    int huff_split_ = 0;
-    int idct_split_begin_[2][kNumIdctLayoutClasses + 1] = {};
-    DevBuffer d_idct_work_split_;
+    int huff_half_ = 0;  // d_huff_work_: where the second half's entries begin
+    int idct_half_begin_[2][kNumIdctLayoutClasses + 1] = {};  // d_idct_work_halves_: the classes of each half
+    DevBuffer d_idct_work_halves_;
 };
 
 }  // namespace jpgpu

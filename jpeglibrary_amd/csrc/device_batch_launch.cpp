@@ -332,7 +332,7 @@ int DeviceBatch::run_idct() {
 //     stream : K1(all)  K2(A) ------ K3(A) ----------------- [join] 
 //     stream2:                 wait  K2(B) ------ K3(B) ------/
 // (16.1 vs 17.2 ms per 1024 x 4K measured with two contexts in round 1, with K3 at 10.5 ms; with round 2's kernels it no
-// longer pays -- see the numbers at `wanted` in layout_and_upload -- so the mode is opt-in: JPGPU_OVERLAP=1.)
+// longer pays -- see the numbers at `wanted` in plan_overlap_halves -- so the mode is opt-in: JPGPU_OVERLAP=1.)
 // Kernels that share the machine have no duration of their own, and bench.py's per-kernel roofline is computed from
 // exactly that: the first decode() after an upload or a jpgpu_batch_stage_ms query, and every 8th after it, is issued
 // serially on one stream with an event between the stages.  jpgpu_batch_stage_ms reports the stage times from those serial
@@ -388,14 +388,14 @@ int DeviceBatch::decode() {
                                   (int16_t *)d_coefs_.ptr, n_huff_slots_, (const uint8_t *)d_lut_pool_.ptr, k2_tab_bytes_);
         };
         auto k3 = [&](hipStream_t st, int half) {
-            return launch_idct(st, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const IdctWork *)d_idct_work_split_.ptr,
-                               idct_split_begin_[half], (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr,
+            return launch_idct(st, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const IdctWork *)d_idct_work_halves_.ptr,
+                               idct_half_begin_[half], (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr,
                                (uint8_t *)d_out_.ptr, format_, kf, (uint8_t *)d_rgb_scratch_.ptr);
         };
-        if ((e = k2(s1, 0, huff_split_)) != hipSuccess) return hip_fail(e, "huffman_decode_kernel");
+        if ((e = k2(s1, 0, huff_half_)) != hipSuccess) return hip_fail(e, "huffman_decode_kernel");
         if ((rc = mark(1, s1)) != JPGPU_OK) return rc;  // K1 and K2(A) are done: the second half may start
         if ((e = hipStreamWaitEvent(s2, ev[1], 0)) != hipSuccess) return hip_fail(e, "hipStreamWaitEvent");
-        if ((e = k2(s2, huff_split_, n_huff_work_ - huff_split_)) != hipSuccess) return hip_fail(e, "huffman_decode_kernel");
+        if ((e = k2(s2, huff_half_, n_huff_work_ - huff_half_)) != hipSuccess) return hip_fail(e, "huffman_decode_kernel");
         if ((e = k3(s1, 0)) != hipSuccess) return hip_fail(e, "idct_output_kernel");
         if ((e = k3(s2, 1)) != hipSuccess) return hip_fail(e, "idct_output_kernel");
         if ((rc = mark(2, s2)) != JPGPU_OK) return rc;
