@@ -566,7 +566,8 @@ int jpgpu_encoder_upload(jpgpu_encoder *e, const uint8_t *const *pixels, const j
 /* SetQuantizationTable(new JpegQuantizationTable(0, identifier, elements)) for image i (JpegEncoder.cs:102-126): the caller's own
  * table instead of the standard one scaled by `quality`.  identifier 0 = the first component's table, 1 = the other components';
  * 64 elements in zig-zag order, element precision 0, so 1..255 each (the segment stores bytes; 0 would divide by zero in
- * ZigZagAndQuantizeBlock).  Between jpgpu_encoder_upload and jpgpu_encoder_encode. */
+ * ZigZagAndQuantizeBlock).  Between jpgpu_encoder_upload and jpgpu_encoder_encode.  Behind jpgpu_encoder_upload_described it is
+ * JPGPU_ERR_INVALID_OPERATION for every image: a description carries its tables. */
 int jpgpu_encoder_set_quantization_table(jpgpu_encoder *e, int i, int identifier, const uint16_t *zigzag64);
 /* Encode(): FDCT + quantise, Huffman code lengths, bit emission, byte stuffing -- all on the device */
 int jpgpu_encoder_encode(jpgpu_encoder *e);
@@ -584,6 +585,75 @@ int jpgpu_encoder_download(jpgpu_encoder *e, int i, void *dst, size_t cap);     
 void *jpgpu_encoder_output_device(const jpgpu_encoder *e, int i, size_t *bytes);                  /* stream i, resident in HBM */
 /* quantised zig-zag blocks in encoding order (what ZigZagAndQuantizeBlock produced, JpegEncoder.cs:812-826) */
 int jpgpu_encoder_download_coefficients(jpgpu_encoder *e, int i, int16_t *dst, size_t cap_blocks);
+
+/* ---- (4b) described images: every component arrangement JpegEncoder.AddComponent accepts (JpegEncoder.cs:175-240).
+ * A jpgpu_encode_description is the encoder's state after the caller's Set* / AddComponent sequence, list by list:
+ *   components      AddComponent order.  A component reads sample number (position in this list) of every input pixel
+ *                   (component.Index, JpegBufferInputReader.cs:47), whatever its component_index says.
+ *   quant_tables    SetQuantizationTable order: the stream's DQT, written whole (WriteQuantizationTables :305-330) and independent
+ *                   of what the components captured (a table replaced after AddComponent reaches the DQT, not the component).
+ *   huffman_tables  SetHuffmanTable order: the stream's DHT.  given = 1: a JpegHuffmanEncodingTable(JpegHuffmanCanonicalCode[])
+ *                   as the caller built it -- TryWrite (JpegHuffmanEncodingTable.cs:50-86) decides the DHT bytes, GetCode
+ *                   (:94-100) the code of all 256 symbols (a symbol the table does not hold gets entry 0's code and length);
+ *                   given = 0: left to be built from the image (JpegHuffmanEncodingTableBuilder).
+ * Any table to be built sends the image down TransformBlocks / BuildHuffmanTables / WritePreparedScanData (:264-274), none down
+ * WriteScanData (:278-280).  A builder no component feeds makes Build throw "No symbol is recorded.": the image's status
+ * (JPGPU_ERR_INVALID_OPERATION), as with jpgpu_encoder_upload.  An arrangement without a component at the maximum sampling factors
+ * in both directions (2 x 1 beside 1 x 2) is refused: JPGPU_ERR_NOT_SUPPORTED as that image's status, see DESIGN.md section 5.
+ * An EncodeAction arrangement (what jpgpu_encoder_upload describes) gives the bytes jpgpu_encoder_upload gives. */
+#define JPGPU_ENC_MAX_COMPONENTS 4
+#define JPGPU_ENC_MAX_TABLES 8
+typedef struct jpgpu_encode_component {
+    uint8_t component_index;  /* the identifier SOF0 and SOS carry */
+    uint8_t h, v;             /* sampling factors: 1, 2 or 4 */
+    uint8_t tq;               /* identifier of the captured quantisation table (written to SOF0) */
+    uint8_t td, ta;           /* DC / AC Huffman table identifiers (looked up in huffman_tables, first match) */
+    uint8_t reserved[2];
+    uint16_t quant[64];       /* the 64 elements AddComponent captured, zig-zag order, 1..255 */
+} jpgpu_encode_component;
+typedef struct jpgpu_encode_quant_table {
+    uint8_t identifier;
+    uint8_t reserved;
+    uint16_t elements[64];    /* zig-zag order, 1..255 */
+} jpgpu_encode_quant_table;
+typedef struct jpgpu_encode_huffman_table {
+    uint8_t table_class;      /* 0 = DC, 1 = AC */
+    uint8_t identifier;       /* identifier & 0xf goes into the Tc/Th byte */
+    uint8_t given;            /* 1: the codes below; 0: built from the image */
+    uint8_t reserved;
+    int32_t num_codes;        /* given: 1..256 entries of the JpegHuffmanCanonicalCode[] */
+    uint16_t code[256];       /* .Code (below 2^length) */
+    uint8_t symbol[256];      /* .Symbol */
+    uint8_t length[256];      /* .CodeLength, 0..16 (0 = an entry TryWrite leaves out; such entries come first) */
+} jpgpu_encode_huffman_table;
+typedef struct jpgpu_encode_description {
+    int32_t width, height;
+    int32_t in_components;       /* samples per input pixel, at least num_components */
+    int32_t input_rgb;           /* 0; 1 (R,G,B) or 2 (R,G,B,A) with exactly three components, as in jpgpu_encode_params */
+    int32_t restart_interval;    /* the extension of jpgpu_encode_params */
+    int32_t most_optimal_coding; /* JpegEncoder.MostOptimalCoding */
+    int32_t num_components, num_quant_tables, num_huffman_tables;
+    int32_t reserved;
+    jpgpu_encode_component components[JPGPU_ENC_MAX_COMPONENTS];
+    jpgpu_encode_quant_table quant_tables[JPGPU_ENC_MAX_TABLES];
+    jpgpu_encode_huffman_table huffman_tables[JPGPU_ENC_MAX_TABLES];
+} jpgpu_encode_description;
+size_t jpgpu_sizeof_encode_component(void);
+size_t jpgpu_sizeof_encode_quant_table(void);
+size_t jpgpu_sizeof_encode_huffman_table(void);
+size_t jpgpu_sizeof_encode_description(void);
+/* jpgpu_encoder_upload for described images.  Argument errors fail the call; a refused arrangement is that image's status alone.
+ * An upload that holds an image the general kernels take counts and emits the bits of ALL its images as two kernels
+ * (jpgpu_encoder_emit_passes: no one-pass call); uploads of EncodeAction arrangements alone run as they always did. */
+int jpgpu_encoder_upload_described(jpgpu_encoder *e, const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n);
+/* status of image i as known so far (after the upload: JPGPU_OK or the refusal; after the encode also "No symbol is recorded.") */
+int jpgpu_encoder_image_status(const jpgpu_encoder *e, int i);
+/* Host only, no context, no device: the status an encode of `desc` would report, with its message in message[message_cap]
+ * (may be NULL), and -- for a description without tables to be built -- the SOI, DQT, (DRI,) SOF0, DHT, SOS bytes Encode()
+ * writes in front of the scan (*len; JPGPU_ERR_ARGUMENT when cap is too small, *len still set).  With tables to be built the
+ * DHT depends on the image: *len = 0.  JPGPU_ERR_INVALID_OPERATION: a table to be built that no component feeds. */
+int jpgpu_encode_description_header(const jpgpu_encode_description *desc, uint8_t *dst, size_t cap, size_t *len, char *message,
+                                    size_t message_cap);
 
 /* ------------------------------------------------------------------------------------------------
  * (5) Optimizer -- replaces JpegOptimizer (ref: JpegOptimizer.cs) for single-scan baseline files:

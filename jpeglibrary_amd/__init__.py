@@ -11,14 +11,14 @@ from .encoder import EncodeBatch, encode_batch
 from .optimizer import JpegOptimizer, OptimizeBatch, build_optimal_huffman_table, optimize_batch
 from .decoder import (JpegBlockOutputWriter, JpegBufferOutputWriter8Bit, JpegBufferOutputWriterGreaterThan8Bit, JpegBufferOutputWriterLessThan8Bit, JpegDecoder, JpegExtendingOutputWriter, JpegFrameComponentSpecificationParameters,
                       JpegFrameHeader, JpegGpuProgressiveScanDecoder, JpegHuffmanDecodingTable, JpegScanComponentSpecificationParameters, JpegScanHeader)
-from .jpeg_encoder import (JpegBufferInputReader, JpegEncoder, JpegHuffmanEncodingTable, JpegQuantizationTable, JpegStandardHuffmanEncodingTable,
+from .jpeg_encoder import (JpegBufferInputReader, JpegEncoder, JpegHuffmanCanonicalCode, JpegHuffmanEncodingTable, JpegHuffmanEncodingTableBuilder, JpegQuantizationTable, JpegStandardHuffmanEncodingTable,
                            JpegStandardQuantizationTable)
 from .multi import MultiDecoder
 from .errors import (ArgumentException, DeviceError, InvalidDataException, InvalidOperationException, JpegError,
                      NoDeviceError, NotSupportedException)
 
 __all__ = [
-    "Batch", "decode_batch", "MultiDecoder", "JpegEncoder", "JpegQuantizationTable", "JpegStandardQuantizationTable", "JpegHuffmanEncodingTable",
+    "Batch", "decode_batch", "MultiDecoder", "JpegEncoder", "JpegQuantizationTable", "JpegStandardQuantizationTable", "JpegHuffmanEncodingTable", "JpegHuffmanCanonicalCode", "JpegHuffmanEncodingTableBuilder",
     "JpegStandardHuffmanEncodingTable", "JpegBufferInputReader", "EncodeBatch", "encode_batch", "JpegOptimizer", "OptimizeBatch", "optimize_batch", "build_optimal_huffman_table", "Context", "default_context", "device_count", "JpegDecoder", "JpegBlockOutputWriter",
     "JpegBufferOutputWriter8Bit", "JpegExtendingOutputWriter", "JpegFrameHeader", "JpegFrameComponentSpecificationParameters", "JpegScanHeader",
     "JpegScanComponentSpecificationParameters", "JpegHuffmanDecodingTable", "JpegGpuProgressiveScanDecoder", "FMT_INTERLEAVED_U8", "FMT_PLANAR_U8", "FMT_PLANAR_I16", "FMT_RGB_U8", "FMT_RGBA_U8", "FMT_EXTENDED_U16",

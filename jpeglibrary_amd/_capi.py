@@ -62,6 +62,31 @@ class EncodeParams(C.Structure):
                 ("quality", C.c_int32), ("input_rgb", C.c_int32), ("optimize_coding", C.c_int32), ("restart_interval", C.c_int32)]
 
 
+ENC_MAX_COMPONENTS, ENC_MAX_TABLES = 4, 8
+
+
+class EncodeComponent(C.Structure):
+    _fields_ = [("component_index", C.c_uint8), ("h", C.c_uint8), ("v", C.c_uint8), ("tq", C.c_uint8), ("td", C.c_uint8), ("ta", C.c_uint8),
+                ("reserved", C.c_uint8 * 2), ("quant", C.c_uint16 * 64)]
+
+
+class EncodeQuantTable(C.Structure):
+    _fields_ = [("identifier", C.c_uint8), ("reserved", C.c_uint8), ("elements", C.c_uint16 * 64)]
+
+
+class EncodeHuffmanTable(C.Structure):
+    _fields_ = [("table_class", C.c_uint8), ("identifier", C.c_uint8), ("given", C.c_uint8), ("reserved", C.c_uint8), ("num_codes", C.c_int32),
+                ("code", C.c_uint16 * 256), ("symbol", C.c_uint8 * 256), ("length", C.c_uint8 * 256)]
+
+
+class EncodeDescription(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("in_components", C.c_int32), ("input_rgb", C.c_int32),
+                ("restart_interval", C.c_int32), ("most_optimal_coding", C.c_int32), ("num_components", C.c_int32),
+                ("num_quant_tables", C.c_int32), ("num_huffman_tables", C.c_int32), ("reserved", C.c_int32),
+                ("components", EncodeComponent * ENC_MAX_COMPONENTS), ("quant_tables", EncodeQuantTable * ENC_MAX_TABLES),
+                ("huffman_tables", EncodeHuffmanTable * ENC_MAX_TABLES)]
+
+
 class IngestStats(C.Structure):
     _fields_ = [("threads", C.c_int32), ("n_header_only", C.c_int32), ("n_full_walk", C.c_int32), ("parse_ms", C.c_float),
                 ("copy_ms", C.c_float), ("full_walk_ms", C.c_float), ("layout_ms", C.c_float), ("total_ms", C.c_float),
@@ -209,6 +234,14 @@ SYMBOLS = [
     ("jpgpu_encoder_download", C.c_int, [_P, C.c_int, C.c_void_p, C.c_size_t]),
     ("jpgpu_encoder_output_device", C.c_void_p, [_P, C.c_int, C.POINTER(C.c_size_t)]),
     ("jpgpu_encoder_download_coefficients", C.c_int, [_P, C.c_int, C.c_void_p, C.c_size_t]),
+    ("jpgpu_sizeof_encode_component", C.c_size_t, []),
+    ("jpgpu_sizeof_encode_quant_table", C.c_size_t, []),
+    ("jpgpu_sizeof_encode_huffman_table", C.c_size_t, []),
+    ("jpgpu_sizeof_encode_description", C.c_size_t, []),
+    ("jpgpu_encoder_upload_described", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(EncodeDescription), C.c_int]),
+    ("jpgpu_encoder_image_status", C.c_int, [_P, C.c_int]),
+    ("jpgpu_encode_description_header", C.c_int, [C.POINTER(EncodeDescription), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p,
+                                                  C.c_size_t]),
     ("jpgpu_optimizer_create", C.c_int, [_P, C.POINTER(_P)]),
     ("jpgpu_optimizer_destroy", None, [_P]),
     ("jpgpu_optimizer_upload", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int]),
@@ -269,6 +302,11 @@ def _load():
     if lib.jpgpu_sizeof_progressive_plan() != C.sizeof(ProgressivePlan):
         raise ImportError(f"{LIB_PATH} (jpgpu_progressive_plan of {lib.jpgpu_sizeof_progressive_plan()} bytes) does not match this "
                           f"binding ({C.sizeof(ProgressivePlan)} bytes): rebuild it")
+    for name, mirror in (("component", EncodeComponent), ("quant_table", EncodeQuantTable), ("huffman_table", EncodeHuffmanTable),
+                         ("description", EncodeDescription)):
+        size = getattr(lib, "jpgpu_sizeof_encode_" + name)()
+        if size != C.sizeof(mirror):
+            raise ImportError(f"{LIB_PATH} (jpgpu_encode_{name} of {size} bytes) does not match this binding ({C.sizeof(mirror)} bytes): rebuild it")
     return lib
 
 

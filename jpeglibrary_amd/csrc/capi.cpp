@@ -1378,6 +1378,41 @@ void *jpgpu_encoder_output_device(const jpgpu_encoder *enc, int i, size_t *bytes
 int jpgpu_encoder_download_coefficients(jpgpu_encoder *enc, int i, int16_t *dst, size_t cap_blocks) {
     JPGPU_GUARD(enc, enc->impl.download_coefficients(i, dst, cap_blocks));
 }
+size_t jpgpu_sizeof_encode_component(void) { return sizeof(jpgpu_encode_component); }
+size_t jpgpu_sizeof_encode_quant_table(void) { return sizeof(jpgpu_encode_quant_table); }
+size_t jpgpu_sizeof_encode_huffman_table(void) { return sizeof(jpgpu_encode_huffman_table); }
+size_t jpgpu_sizeof_encode_description(void) { return sizeof(jpgpu_encode_description); }
+int jpgpu_encoder_upload_described(jpgpu_encoder *enc, const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n) {
+    JPGPU_GUARD(enc, enc->impl.upload_described(pixels, desc, n));
+}
+int jpgpu_encoder_image_status(const jpgpu_encoder *enc, int i) { return enc ? enc->impl.image_status(i) : JPGPU_ERR_ARGUMENT; }
+int jpgpu_encode_description_header(const jpgpu_encode_description *desc, uint8_t *dst, size_t cap, size_t *len, char *message, size_t message_cap) {
+    if (message && message_cap) message[0] = 0;
+    if (len) *len = 0;
+    if (!desc || !len) return JPGPU_ERR_ARGUMENT;
+    try {
+        EncPlan plan;
+        std::string error;
+        int rc = resolve_encode_description(*desc, &plan, &error);
+        if (rc == JPGPU_OK && plan.status != JPGPU_OK) {
+            rc = plan.status;
+            error = plan.message;
+        }
+        if (rc == JPGPU_OK && !plan.any_builder) {
+            *len = plan.header.size();
+            if (!dst || cap < plan.header.size()) {
+                rc = JPGPU_ERR_ARGUMENT;
+                error = "Destination buffer is too small.";
+            } else {
+                memcpy(dst, plan.header.data(), plan.header.size());
+            }
+        }
+        if (message && message_cap) snprintf(message, message_cap, "%s", error.c_str());
+        return rc;
+    } catch (const std::bad_alloc &) {
+        return JPGPU_ERR_OUT_OF_MEMORY;
+    }
+}
 
 }  // extern "C"
 

@@ -129,11 +129,271 @@ void rgb_ycc_factors(int32_t out[8]) {
     out[7] = fix(0.081312411F);
 }
 
+// ------------------------------------------------------------------------------------------------ described images
+
+namespace {
+// JpegHuffmanEncodingTable(JpegHuffmanCanonicalCode[]) (ref: JpegHuffmanEncodingTable.cs:21-37), TryWrite (:50-86), GetCode (:94-100)
+void resolve_given_table(const jpgpu_encode_huffman_table &t, EncPlan::Slot *slot) {
+    const int n = t.num_codes;
+    int code_count = 0;
+    uint8_t symbol_map[256] = {};
+    for (int i = 0; i < n; i++)
+        if (t.length[i] != 0) {
+            symbol_map[t.symbol[i]] = (uint8_t)i;
+            code_count++;
+        }
+    for (int s = 0; s < 256; s++) {  // a symbol the table does not hold: entry 0
+        slot->table.code[s] = t.code[symbol_map[s]];
+        slot->table.len[s] = t.length[symbol_map[s]];
+    }
+    slot->dht.clear();
+    for (int len = 1; len <= 16; len++) {
+        int count = 0;
+        for (int i = n - code_count; i < n; i++) count += t.length[i] == len;
+        slot->dht.push_back((uint8_t)count);
+    }
+    for (int i = n - code_count; i < n; i++) slot->dht.push_back(t.symbol[i]);
+}
+
+void std_slot(int t, EncPlan::Slot *slot) {
+    build_enc_table(kStd[t], &slot->table);
+    slot->dht.assign(kStd[t].lengths, kStd[t].lengths + 16);
+    slot->dht.insert(slot->dht.end(), kStd[t].values, kStd[t].values + kStd[t].count);
+}
+}  // namespace
+
+int resolve_encode_description(const jpgpu_encode_description &d, EncPlan *plan, std::string *error) {
+    auto bad = [&](int status, const char *msg) {
+        if (error) *error = msg;
+        return status;
+    };
+    *plan = EncPlan();
+    plan->layout.assign(1, DevEncLayout());
+    memset(&plan->layout[0], 0, sizeof(DevEncLayout));
+    // ---- what the reference's setters throw on (JpegEncoder.cs:102-240), and what this interface cannot express
+    if (d.width <= 0 || d.height <= 0 || d.width > 65535 || d.height > 65535) return bad(JPGPU_ERR_ARGUMENT, "image dimensions out of range");
+    if (d.num_components < 0 || d.num_components > JPGPU_ENC_MAX_COMPONENTS) return bad(JPGPU_ERR_ARGUMENT, "1 to 4 components can be described.");
+    if (d.num_components == 0) return bad(JPGPU_ERR_INVALID_OPERATION, "No component is specified.");
+    if (d.num_quant_tables < 1 || d.num_quant_tables > JPGPU_ENC_MAX_TABLES) return bad(JPGPU_ERR_ARGUMENT, "1 to 8 quantization tables can be described.");
+    if (d.num_huffman_tables < 1 || d.num_huffman_tables > JPGPU_ENC_MAX_TABLES) return bad(JPGPU_ERR_ARGUMENT, "1 to 8 Huffman tables can be described.");
+    const int nc = d.num_components;
+    for (int c = 0; c < nc; c++) {
+        const jpgpu_encode_component &k = d.components[c];
+        if ((k.h != 1 && k.h != 2 && k.h != 4) || (k.v != 1 && k.v != 2 && k.v != 4)) return bad(JPGPU_ERR_ARGUMENT, "Subsampling factor can only be 1, 2 or 4.");
+        for (int o = 0; o < c; o++)
+            if (d.components[o].component_index == k.component_index) return bad(JPGPU_ERR_ARGUMENT, "The component index is already used by another component.");
+        for (int i = 0; i < 64; i++)
+            if (k.quant[i] == 0 || k.quant[i] > 255) return bad(JPGPU_ERR_ARGUMENT, "Quantization table elements must be in 1..255 (element precision 0).");
+    }
+    for (int t = 0; t < d.num_quant_tables; t++) {
+        for (int o = 0; o < t; o++)
+            if (d.quant_tables[o].identifier == d.quant_tables[t].identifier) return bad(JPGPU_ERR_ARGUMENT, "A quantization table identifier appears twice.");
+        for (int i = 0; i < 64; i++)
+            if (d.quant_tables[t].elements[i] == 0 || d.quant_tables[t].elements[i] > 255)
+                return bad(JPGPU_ERR_ARGUMENT, "Quantization table elements must be in 1..255 (element precision 0).");
+    }
+    for (int t = 0; t < d.num_huffman_tables; t++) {
+        const jpgpu_encode_huffman_table &h = d.huffman_tables[t];
+        if (h.table_class > 1) return bad(JPGPU_ERR_ARGUMENT, "Huffman table class is 0 (DC) or 1 (AC).");
+        for (int o = 0; o < t; o++)  // AddTable (JpegHuffmanEncodingTableCollection.cs:82-88) throws InvalidOperationException
+            if (d.huffman_tables[o].table_class == h.table_class && d.huffman_tables[o].identifier == h.identifier)
+                return bad(JPGPU_ERR_INVALID_OPERATION, "Operation is not valid due to the current state of the object.");
+        if (h.given) {
+            if (h.num_codes < 1 || h.num_codes > 256) return bad(JPGPU_ERR_ARGUMENT, "A given Huffman table holds 1 to 256 codes.");
+            for (int i = 0; i < h.num_codes; i++)
+                if (h.length[i] > 16 || (h.length[i] < 16 && (h.code[i] >> h.length[i]) != 0))
+                    return bad(JPGPU_ERR_ARGUMENT, "A Huffman code is at most 16 bits long and fits its length.");
+        }
+    }
+    auto find_slot = [&](int cls, int id) {
+        for (int t = 0; t < d.num_huffman_tables; t++)
+            if (d.huffman_tables[t].table_class == cls && d.huffman_tables[t].identifier == id) return t;
+        return -1;
+    };
+    int dc_slot[4], ac_slot[4];
+    for (int c = 0; c < nc; c++) {
+        dc_slot[c] = find_slot(0, d.components[c].td);
+        ac_slot[c] = find_slot(1, d.components[c].ta);
+        if (dc_slot[c] < 0 || ac_slot[c] < 0) return bad(JPGPU_ERR_ARGUMENT, "Huffman table is not defined.");
+    }
+    if (d.in_components < nc || d.in_components > 255) return bad(JPGPU_ERR_ARGUMENT, "The input holds fewer samples per pixel than components were added.");
+    if (d.input_rgb < 0 || d.input_rgb > 2) return bad(JPGPU_ERR_ARGUMENT, "input_rgb is 0 (samples), 1 (R,G,B) or 2 (R,G,B,A).");
+    if (d.input_rgb && (nc != 3 || d.in_components != (d.input_rgb == 2 ? 4 : 3))) return bad(JPGPU_ERR_ARGUMENT, "RGB input needs 3 components.");
+    if (d.restart_interval < 0 || d.restart_interval > 65535) return bad(JPGPU_ERR_ARGUMENT, "restart interval out of range (0..65535)");
+
+    plan->width = d.width;
+    plan->height = d.height;
+    plan->in_components = d.in_components;
+    plan->input_rgb = d.input_rgb;
+    plan->restart_interval = d.restart_interval;
+    // ---- tables
+    plan->n_slots = d.num_huffman_tables;
+    plan->slots.assign((size_t)plan->n_slots, EncPlan::Slot());
+    plan->most_optimal = d.most_optimal_coding != 0;
+    bool fed[JPGPU_ENC_MAX_TABLES] = {};
+    for (int c = 0; c < nc; c++) fed[dc_slot[c]] = fed[ac_slot[c]] = true;
+    for (int t = 0; t < plan->n_slots; t++) {
+        const jpgpu_encode_huffman_table &h = d.huffman_tables[t];
+        EncPlan::Slot &s = plan->slots[t];
+        memset(&s.table, 0, sizeof s.table);
+        s.given = h.given != 0;
+        s.tc_th = (uint8_t)((h.table_class << 4) | (h.identifier & 0xf));
+        if (s.given) resolve_given_table(h, &s);
+        else plan->any_builder = true;
+    }
+    // ---- geometry
+    DevEncLayout &L = plan->layout[0];
+    uint32_t max_h = 1, max_v = 1;
+    for (int c = 0; c < nc; c++) {
+        max_h = std::max<uint32_t>(max_h, d.components[c].h);
+        max_v = std::max<uint32_t>(max_v, d.components[c].v);
+    }
+    L.ncomp = (uint32_t)nc;
+    L.max_h = max_h;
+    L.max_v = max_v;
+    L.own_blocks = plan->any_builder ? 1 : 0;
+    const uint32_t hb = ((uint32_t)d.width + 7) / 8, vb = ((uint32_t)d.height + 7) / 8;
+    uint32_t b = 0;
+    bool full_resolution = false;
+    for (int c = 0; c < 4; c++)
+        for (int i = 0; i < 64; i++) L.quant[c][i] = 1;
+    for (int c = 0; c < nc; c++) {
+        const jpgpu_encode_component &k = d.components[c];
+        L.h[c] = k.h;
+        L.v[c] = k.v;
+        L.hs[c] = (uint8_t)(max_h / k.h);
+        L.vs[c] = (uint8_t)(max_v / k.v);
+        L.dc_slot[c] = (uint8_t)dc_slot[c];
+        L.ac_slot[c] = (uint8_t)ac_slot[c];
+        L.first_blk[c] = (uint8_t)b;
+        L.grid_w[c] = (hb + L.hs[c] - 1) / L.hs[c];  // JpegBlockAllocator.cs:61-62
+        L.grid_h[c] = (vb + L.vs[c] - 1) / L.vs[c];
+        for (int i = 0; i < 64; i++) L.quant[c][i] = k.quant[i];
+        for (uint32_t y = 0; y < k.v; y++)
+            for (uint32_t x = 0; x < k.h; x++) {
+                L.blk_comp[b] = (uint8_t)c;
+                L.blk_x[b] = (uint8_t)x;
+                L.blk_y[b] = (uint8_t)y;
+                if (L.hs[c] == 1 && L.vs[c] == 1) L.tail_first = b;
+                L.blk_info[b] = (uint32_t)c | (x << 2) | (y << 4) | ((uint32_t)k.h << 6) | ((uint32_t)k.v << 9) | ((uint32_t)dc_slot[c] << 12) |
+                                ((uint32_t)ac_slot[c] << 15) | ((uint32_t)L.first_blk[c] << 18) | (((uint32_t)L.first_blk[c] + k.h * k.v - 1u) << 24);
+                b++;
+            }
+        full_resolution = full_resolution || (L.hs[c] == 1 && L.vs[c] == 1);
+    }
+    plan->bpm = b;
+    const uint32_t mcus_per_line = ((uint32_t)d.width + 8 * max_h - 1) / (8 * max_h), mcus_per_column = ((uint32_t)d.height + 8 * max_v - 1) / (8 * max_v);
+    if (L.own_blocks) {  // the last block of the last MCU that lies outside its component's grid: what the dummy block ends up as
+        const uint32_t last = mcus_per_line * mcus_per_column - 1, mx = last % mcus_per_line, my = last / mcus_per_line;
+        for (uint32_t k = 0; k < b; k++) {
+            const uint32_t c = L.blk_comp[k];
+            if (mx * L.h[c] + L.blk_x[k] >= L.grid_w[c] || my * L.v[c] + L.blk_y[k] >= L.grid_h[c]) L.dummy_blk = last * b + k;
+        }
+    }
+    // ---- marker segments, from the lists (JpegEncoder.cs:261-280)
+    std::vector<uint8_t> &h = plan->header_pre;
+    put_marker(h, 0xD8);
+    put_marker(h, 0xDB);  // WriteQuantizationTables (:305-330): every table of the list, used or not
+    put_length(h, (uint16_t)(65 * d.num_quant_tables));
+    for (int t = 0; t < d.num_quant_tables; t++) {
+        h.push_back(d.quant_tables[t].identifier);  // JpegQuantizationTable.TryWrite: precision << 4 | identifier
+        for (int i = 0; i < 64; i++) h.push_back((uint8_t)d.quant_tables[t].elements[i]);
+    }
+    if (d.restart_interval) {
+        put_marker(h, 0xDD);
+        put_length(h, 2);
+        h.push_back((uint8_t)(d.restart_interval >> 8));
+        h.push_back((uint8_t)d.restart_interval);
+    }
+    put_marker(h, 0xC0);  // WriteStartOfFrame (:353-381)
+    put_length(h, (uint16_t)(6 + 3 * nc));
+    h.push_back(8);
+    h.push_back((uint8_t)(d.height >> 8));
+    h.push_back((uint8_t)d.height);
+    h.push_back((uint8_t)(d.width >> 8));
+    h.push_back((uint8_t)d.width);
+    h.push_back((uint8_t)nc);
+    for (int c = 0; c < nc; c++) {
+        h.push_back(d.components[c].component_index);
+        h.push_back((uint8_t)((d.components[c].h << 4) | d.components[c].v));
+        h.push_back(d.components[c].tq);
+    }
+    std::vector<uint8_t> &sos = plan->header_post;
+    put_marker(sos, 0xDA);  // WriteStartOfScan (:387-408)
+    put_length(sos, (uint16_t)(1 + 2 * nc + 3));
+    sos.push_back((uint8_t)nc);
+    for (int c = 0; c < nc; c++) {
+        sos.push_back(d.components[c].component_index);
+        sos.push_back((uint8_t)((d.components[c].td << 4) | (d.components[c].ta & 0xf)));
+    }
+    sos.push_back(0);
+    sos.push_back(63);
+    sos.push_back(0);
+    if (!plan->any_builder) {
+        plan->header = plan->header_pre;
+        put_marker(plan->header, 0xC4);  // WriteHuffmanTables (:336-347): every table of the collection, in SetHuffmanTable order
+        size_t total = 0;
+        for (int t = 0; t < plan->n_slots; t++) total += 1 + plan->slots[t].dht.size();
+        put_length(plan->header, (uint16_t)total);
+        for (int t = 0; t < plan->n_slots; t++) {
+            plan->header.push_back(plan->slots[t].tc_th);
+            plan->header.insert(plan->header.end(), plan->slots[t].dht.begin(), plan->slots[t].dht.end());
+        }
+        plan->header.insert(plan->header.end(), sos.begin(), sos.end());
+    }
+    // ---- what Encode() of this image reports
+    if (!full_resolution) {
+        plan->status = JPGPU_ERR_NOT_SUPPORTED;
+        plan->message = "No component has the maximum sampling factors in both directions: every block then starts from the block encoded before it "
+                        "(one block buffer for the whole scan), which is a serial chain over the image.";
+        return JPGPU_OK;
+    }
+    for (int t = 0; t < plan->n_slots; t++)
+        if (!plan->slots[t].given && !fed[t]) {  // JpegHuffmanEncodingTableBuilder.Build of a builder no component feeds
+            plan->status = JPGPU_ERR_INVALID_OPERATION;
+            plan->message = "No symbol is recorded.";
+        }
+    // ---- an EncodeAction arrangement?  (apps/JpegEncode/EncodeAction.cs:38-63: what jpgpu_encoder_upload describes)
+    bool legacy = (nc == 1 || nc == 3) && d.num_quant_tables == 2 && d.num_huffman_tables == 4 && d.quant_tables[0].identifier == 0 &&
+                  d.quant_tables[1].identifier == 1 && d.in_components == (d.input_rgb == 2 ? 4 : nc);
+    for (int c = 0; legacy && c < nc; c++) {
+        const jpgpu_encode_component &k = d.components[c];
+        const int t = c == 0 ? 0 : 1;
+        legacy = k.component_index == c + 1 && k.tq == t && k.td == t && k.ta == t && (c == 0 || (k.h == 1 && k.v == 1)) &&
+                 memcmp(k.quant, d.quant_tables[t].elements, sizeof k.quant) == 0;
+    }
+    for (int t = 0; legacy && t < 4; t++) {  // DC0, AC0, DC1, AC1: the four standard tables, or all four to be built
+        const jpgpu_encode_huffman_table &ht = d.huffman_tables[t];
+        legacy = ht.table_class == (t & 1) && ht.identifier == (t >> 1) && (ht.given != 0) == (d.huffman_tables[0].given != 0);
+        if (legacy && ht.given) {
+            EncPlan::Slot s;
+            std_slot(t, &s);
+            legacy = s.dht == plan->slots[t].dht && memcmp(&s.table, &plan->slots[t].table, sizeof s.table) == 0;
+        }
+    }
+    if (legacy) {
+        plan->legacy = true;
+        plan->legacy_has_quant = true;
+        plan->params.width = d.width;
+        plan->params.height = d.height;
+        plan->params.components = nc;
+        plan->params.luma_h = d.components[0].h;
+        plan->params.luma_v = d.components[0].v;
+        plan->params.quality = 50;
+        plan->params.input_rgb = d.input_rgb;
+        plan->params.optimize_coding = plan->any_builder ? (plan->most_optimal ? 2 : 1) : 0;
+        plan->params.restart_interval = d.restart_interval;
+        for (int t = 0; t < 2; t++)
+            for (int i = 0; i < 64; i++) plan->legacy_quant[t][i] = d.quant_tables[t].elements[i];
+    }
+    return JPGPU_OK;
+}
+
 EncodeBatch::~EncodeBatch() {
     for (hipEvent_t ev : ev_)
         if (ev) (void)hipEventDestroy(ev);
     for (DevBuffer *b : {&d_samples_, &d_pixels_, &d_images_, &d_tables_, &d_work_mcu_, &d_work_blk_, &d_work_stat_, &d_work_chunk_, &d_coefs_, &d_bits_, &d_bit_off_,
-                         &d_raw_bits_, &d_raw_, &d_marks_, &d_chunk_ff_, &d_out_, &d_out_len_, &d_hist_, &d_headers_, &d_chain_, &d_work_order_})
+                         &d_raw_bits_, &d_raw_, &d_marks_, &d_chunk_ff_, &d_out_, &d_out_len_, &d_hist_, &d_headers_, &d_chain_, &d_work_order_, &d_layouts_})
         b->release();
 }
 
@@ -148,6 +408,30 @@ int EncodeBatch::hip_fail(hipError_t e, const char *what) {
 
 int EncodeBatch::upload(const uint8_t *const *pixels, const jpgpu_encode_params *params, int n) {
     if (n < 0 || (n > 0 && (!pixels || !params))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encode_upload: null argument");
+    std::vector<EncPlan> plans((size_t)n);
+    for (int i = 0; i < n; i++) {
+        plans[(size_t)i].legacy = true;
+        plans[(size_t)i].params = params[i];
+    }
+    upload_described_ = false;
+    return upload_plans(pixels, plans);
+}
+
+int EncodeBatch::upload_described(const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n) {
+    if (n < 0 || (n > 0 && (!pixels || !desc))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_described: null argument");
+    std::vector<EncPlan> plans((size_t)n);
+    for (int i = 0; i < n; i++) {
+        std::string error;
+        const int rc = resolve_encode_description(desc[i], &plans[(size_t)i], &error);
+        if (rc != JPGPU_OK) return fail(rc, error);
+    }
+    upload_described_ = true;
+    return upload_plans(pixels, plans);
+}
+
+// Both uploads: an EncodeAction arrangement (plan.legacy) is laid out as it always was, a described one beside it.
+int EncodeBatch::upload_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans) {
+    const int n = (int)plans.size();
     hipError_t e = hipSetDevice(ctx_->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     images_.assign((size_t)n, DevEncImage());
@@ -157,13 +441,71 @@ int EncodeBatch::upload(const uint8_t *const *pixels, const jpgpu_encode_params 
     optimized_.clear();
     most_optimal_.assign((size_t)n, 0);
     status_.assign((size_t)n, JPGPU_OK);
+    messages_.assign((size_t)n, "No symbol is recorded.");
+    general_.clear();
+    general_plans_.clear();
+    layouts_.clear();
+    any_general_builder_ = false;
     encoded_ = false;
     any_restart_ = false;
     emit_hint_ = 0;
     std::vector<EncWork> work_mcu, work_blk, work_stat;  // per 128 MCUs | per 256 units (blocks or restart intervals) | per 256 blocks
     uint64_t px_off = 0, coef_off = 0, smp_off = 0;
     for (int i = 0; i < n; i++) {
-        const jpgpu_encode_params &p = params[i];
+        if (!plans[(size_t)i].legacy) {
+            // ---- a described arrangement: the general kernels (DevEncLayout); a refused one holds no work at all
+            const EncPlan &pl = plans[(size_t)i];
+            DevEncImage &im = images_[i];
+            memset(&im, 0, sizeof im);
+            status_[i] = pl.status;
+            if (pl.status != JPGPU_OK) messages_[i] = pl.message;
+            const bool run = pl.status == JPGPU_OK;
+            const DevEncLayout &pll = pl.layout[0];
+            im.px_off = px_off;
+            im.coef_off = coef_off;
+            general_.push_back(i);
+            general_plans_.push_back(pl);
+            layouts_.push_back(pll);
+            im.layout = (uint32_t)layouts_.size();
+            im.width = (uint32_t)pl.width;
+            im.height = (uint32_t)pl.height;
+            im.in_components = (uint32_t)pl.in_components;
+            im.components = pll.ncomp;
+            im.luma_h = pll.max_h;
+            im.luma_v = pll.max_v;
+            im.input_rgb = pl.input_rgb ? 1 : 0;
+            im.restart_interval = (uint32_t)pl.restart_interval;
+            rgb_ycc_factors(im.r2y);
+            if (run) {
+                im.mcus_per_line = (im.width + 8 * im.luma_h - 1) / (8 * im.luma_h);
+                im.mcus_per_column = (im.height + 8 * im.luma_v - 1) / (8 * im.luma_v);
+                im.bpm = pl.bpm;
+                im.total_blocks = im.mcus_per_line * im.mcus_per_column * im.bpm;
+                any_restart_ = any_restart_ || im.restart_interval != 0;
+                im.n_units = im.restart_interval ? (im.mcus_per_line * im.mcus_per_column + im.restart_interval - 1) / im.restart_interval : im.total_blocks;
+                px_off = align_up64(px_off + (uint64_t)im.width * im.height * im.in_components, 256);
+                coef_off += im.total_blocks;
+                const uint32_t total_mcus = im.mcus_per_line * im.mcus_per_column;
+                for (uint32_t f = 0; f < total_mcus; f += kEncMcusPerWg) work_mcu.push_back({(uint32_t)i, f});
+                im.work_first = (uint32_t)work_blk.size();
+                for (uint32_t f = 0; f < im.n_units; f += 256) work_blk.push_back({(uint32_t)i, f});
+                if (pl.any_builder) {
+                    any_general_builder_ = true;
+                    for (uint32_t f = 0; f < im.total_blocks; f += 256) work_stat.push_back({(uint32_t)i, f});
+                }
+                headers_[i] = pl.header;
+                headers_pre_[i] = pl.header_pre;
+                headers_post_[i] = pl.header_post;
+                im.header_len = (uint32_t)pl.header.size();
+                // tables to be built: the DHT is written once the statistics are in; reserve the largest it can be
+                if (pl.any_builder) im.header_len = (uint32_t)(pl.header_pre.size() + 4 + (size_t)pl.n_slots * (1 + 16 + 256) + pl.header_post.size());
+            } else {
+                im.work_first = (uint32_t)work_blk.size();
+                im.width = im.height = im.restart_interval = 0;  // (no pixels are uploaded for it)
+            }
+            continue;  // (the layout's table slots are placed once the number of EncodeAction images with built tables is known)
+        }
+        const jpgpu_encode_params &p = plans[(size_t)i].params;
         // argument checks of the reference's setters (JpegEncoder.cs:175-184, EncodeAction.cs:19-22)
         if (p.quality <= 0 || p.quality > 100) return fail(JPGPU_ERR_ARGUMENT, "Specified argument was out of the range of valid values. (Parameter 'quality')");
         if ((p.luma_h != 1 && p.luma_h != 2 && p.luma_h != 4) || (p.luma_v != 1 && p.luma_v != 2 && p.luma_v != 4))
@@ -268,6 +610,13 @@ int EncodeBatch::upload(const uint8_t *const *pixels, const jpgpu_encode_params 
         im.header_len = (uint32_t)h.size();
         // optimizeCoding: the DHT is written once the statistics are in; reserve the largest it can be (4 x 256 symbols)
         if (im.table_base != 0) im.header_len = (uint32_t)(headers_pre_[i].size() + 4 + 4 * (1 + 16 + 256) + headers_post_[i].size());
+        if (plans[(size_t)i].legacy_has_quant)  // the described form of SetQuantizationTable(0 / 1): as set_quantization_table patches them in
+            for (int t = 0; t < 2; t++)
+                for (int k = 0; k < 64; k++) {
+                    const size_t at = 2 + 2 + 2 + (size_t)t * 65 + 1 + (size_t)k;
+                    im.quant[t][k] = plans[(size_t)i].legacy_quant[t][k];
+                    headers_[i][at] = headers_pre_[i][at] = (uint8_t)im.quant[t][k];
+                }
     }
     total_blocks_ = coef_off;
     n_work_mcu_ = (int)work_mcu.size();
@@ -279,9 +628,15 @@ int EncodeBatch::upload(const uint8_t *const *pixels, const jpgpu_encode_params 
     for (size_t k = 0; k < work_order.size(); k++) work_order[k] = (uint32_t)k;
     std::stable_sort(work_order.begin(), work_order.end(), [&](uint32_t a, uint32_t b) { return work_blk[a].first < work_blk[b].first; });
 
-    std::vector<EncHuffTable> tables(4 + 4 * optimized_.size());
+    std::vector<EncHuffTable> tables(4 + 4 * optimized_.size() + 8 * general_.size());
     memset(tables.data(), 0, tables.size() * sizeof(EncHuffTable));
     for (int t = 0; t < 4; t++) build_enc_table(kStd[t], &tables[t]);
+    for (size_t g = 0; g < general_.size(); g++) {  // a described image: eight slots, the given tables known now
+        layouts_[g].table_base = (uint32_t)(4 + 4 * optimized_.size() + 8 * g);
+        layouts_[g].hist_index = (uint32_t)((size_t)n * 4 * 256 + g * 8 * 256);
+        for (int t = 0; t < general_plans_[g].n_slots; t++)
+            if (general_plans_[g].slots[t].given) tables[layouts_[g].table_base + (size_t)t] = general_plans_[g].slots[t].table;
+    }
 
     struct Up {
         DevBuffer *buf;
@@ -290,7 +645,8 @@ int EncodeBatch::upload(const uint8_t *const *pixels, const jpgpu_encode_params 
     };
     const Up ups[] = {
         {&d_tables_, tables.data(), tables.size() * sizeof(EncHuffTable), 0},
-        {&d_hist_, nullptr, 0, (size_t)n * 4 * 256 * sizeof(uint32_t) + 256},
+        {&d_hist_, nullptr, 0, ((size_t)n * 4 + general_.size() * 8) * 256 * sizeof(uint32_t) + 256},
+        {&d_layouts_, layouts_.data(), layouts_.size() * sizeof(DevEncLayout), 256},
         {&d_work_mcu_, work_mcu.data(), work_mcu.size() * sizeof(EncWork), 0},
         {&d_work_blk_, work_blk.data(), work_blk.size() * sizeof(EncWork), 0},
         {&d_work_order_, work_order.data(), work_order.size() * sizeof(uint32_t), 16},
@@ -314,6 +670,7 @@ int EncodeBatch::upload(const uint8_t *const *pixels, const jpgpu_encode_params 
     }
     for (int i = 0; i < n; i++) {
         const DevEncImage &im = images_[i];
+        if (im.width == 0) continue;  // (a refused arrangement)
         e = hipMemcpyAsync((uint8_t *)d_pixels_.ptr + im.px_off, pixels[i], (size_t)im.width * im.height * im.in_components, hipMemcpyHostToDevice,
                            ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(pixels)");
@@ -324,6 +681,8 @@ int EncodeBatch::upload(const uint8_t *const *pixels, const jpgpu_encode_params 
 
 int EncodeBatch::set_quantization_table(int i, int identifier, const uint16_t *zigzag64) {
     if (i < 0 || i >= (int)images_.size() || !zigzag64) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_set_quantization_table: bad argument");
+    if (upload_described_)  // (a description carries its tables: captured ones per component, the DQT's as a list of its own)
+        return fail(JPGPU_ERR_INVALID_OPERATION, "jpgpu_encoder_set_quantization_table belongs to jpgpu_encoder_upload: a described image carries its tables.");
     if (identifier != 0 && identifier != 1) return fail(JPGPU_ERR_NOT_SUPPORTED, "Quantization table identifiers 0 and 1 are supported.");
     for (int k = 0; k < 64; k++)
         if (zigzag64[k] == 0 || zigzag64[k] > 255) return fail(JPGPU_ERR_ARGUMENT, "Quantization table elements must be in 1..255 (element precision 0).");
@@ -353,24 +712,37 @@ int EncodeBatch::encode() {
     uint32_t fused_shapes = 0;
     bool any_other = false;
     const bool no_fused = !enc_fused_enabled();
+    const DevEncLayout *layouts = layouts_.empty() ? nullptr : (const DevEncLayout *)d_layouts_.ptr;  // described images in the upload
+    const bool any_plain = layouts_.size() < images_.size();
     for (const DevEncImage &im : images_) {
+        if (im.layout != 0) continue;  // (enc_general_fdct_kernel)
         max_record = std::max(max_record, enc_sample_bytes_per_mcu(im.luma_h, im.luma_v, im.components));
         const int shape = no_fused ? 0 : enc_image_fused_shape(im);
         if (shape != 0) fused_shapes |= 1u << shape;
         else any_other = true;
     }
+    if (n_work_blk_ == 0) {  // nothing but refused arrangements: no kernel counts anything, the streams are empty
+        e = hipMemsetAsync(d_raw_bits_.ptr, 0, (size_t)n * sizeof(uint64_t), ctx_->stream);
+        if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(bit counts)");
+    }
     (void)hipEventRecord(ev_[0], ctx_->stream);
     e = launch_fdct_quant(ctx_->stream, (const uint8_t *)d_pixels_.ptr, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_mcu_.ptr, n_work_mcu_,
                           (uint8_t *)d_samples_.ptr, (int16_t *)d_coefs_.ptr, max_record, fused_shapes, any_other);
     if (e != hipSuccess) return hip_fail(e, "fdct_quant_kernel");
-    if (!optimized_.empty()) {
+    if (layouts) {
+        e = launch_fdct_quant_general(ctx_->stream, (const uint8_t *)d_pixels_.ptr, (const DevEncImage *)d_images_.ptr, layouts,
+                                          (const EncWork *)d_work_mcu_.ptr, n_work_mcu_, (int16_t *)d_coefs_.ptr);
+        if (e != hipSuccess) return hip_fail(e, "enc_general_fdct_kernel");
+    }
+    if (!optimized_.empty() || any_general_builder_) {
         // optimizeCoding: BuildHuffmanTables (:491-550) -- statistics on the device, JpegHuffmanEncodingTableBuilder.Build on the host
-        e = hipMemsetAsync(d_hist_.ptr, 0, (size_t)n * 4 * 256 * sizeof(uint32_t), ctx_->stream);
+        const size_t n_hist = ((size_t)n * 4 + general_.size() * 8) * 256;
+        e = hipMemsetAsync(d_hist_.ptr, 0, n_hist * sizeof(uint32_t), ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(statistics)");
         e = launch_block_stats(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_stat_.ptr, n_work_stat_,
-                               (const int16_t *)d_coefs_.ptr, (uint32_t *)d_hist_.ptr);
+                               (const int16_t *)d_coefs_.ptr, (uint32_t *)d_hist_.ptr, any_general_builder_ ? layouts : nullptr, !optimized_.empty());
         if (e != hipSuccess) return hip_fail(e, "block_stats_kernel");
-        std::vector<uint32_t> hist((size_t)n * 4 * 256);
+        std::vector<uint32_t> hist(n_hist);
         e = hipMemcpyAsync(hist.data(), d_hist_.ptr, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx_->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpy(statistics)");
@@ -411,8 +783,61 @@ int EncodeBatch::encode() {
             h.insert(h.end(), headers_post_[i].begin(), headers_post_[i].end());
             images_[i].header_len = (uint32_t)h.size();
         }
-        e = hipMemcpyAsync((EncHuffTable *)d_tables_.ptr + 4, built.data(), built.size() * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
+        e = built.empty() ? hipSuccess
+                          : hipMemcpyAsync((EncHuffTable *)d_tables_.ptr + 4, built.data(), built.size() * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(built tables)");
+        // described images: every builder of the collection from the counters of its slot (the components that share a table have
+        // added theirs up there); the given tables keep their bytes; DHT in SetHuffmanTable order
+        std::vector<EncHuffTable> slots(any_general_builder_ ? 8 * general_.size() : 0);
+        for (size_t g = 0; g < general_.size(); g++) {
+            const int i = general_[g];
+            const EncPlan &pl = general_plans_[g];
+            if (!pl.any_builder || pl.status != JPGPU_OK) continue;
+            std::vector<uint8_t> &h = headers_[i];
+            h = headers_pre_[i];
+            std::vector<uint8_t> body;
+            for (int t = 0; t < pl.n_slots; t++) {
+                EncHuffTable &et = slots[8 * g + (size_t)t];
+                body.push_back(pl.slots[t].tc_th);
+                if (pl.slots[t].given) {
+                    et = pl.slots[t].table;
+                    body.insert(body.end(), pl.slots[t].dht.begin(), pl.slots[t].dht.end());
+                    continue;
+                }
+                std::vector<OptimalCode> codes;
+                if (!build_optimal_table(&hist[layouts_[g].hist_index + (size_t)t * 256], &codes, pl.most_optimal != 0)) {
+                    status_[i] = JPGPU_ERR_INVALID_OPERATION;  // (resolve_encode_description has seen every such case: not reached)
+                    messages_[i] = "No symbol is recorded.";
+                    break;
+                }
+                for (int sym = 0; sym < 256; sym++) {
+                    et.code[sym] = codes[0].code;
+                    et.len[sym] = codes[0].length;
+                }
+                for (const OptimalCode &c : codes) {
+                    et.code[c.symbol] = c.code;
+                    et.len[c.symbol] = c.length;
+                }
+                for (int l = 1; l <= 16; l++) {
+                    int count = 0;
+                    for (const OptimalCode &c : codes) count += c.length == l;
+                    body.push_back((uint8_t)count);
+                }
+                for (const OptimalCode &c : codes) body.push_back(c.symbol);
+            }
+            put_marker(h, 0xC4);
+            put_length(h, (uint16_t)body.size());
+            h.insert(h.end(), body.begin(), body.end());
+            h.insert(h.end(), headers_post_[i].begin(), headers_post_[i].end());
+            images_[i].header_len = (uint32_t)h.size();
+            e = hipMemcpyAsync((EncHuffTable *)d_tables_.ptr + layouts_[g].table_base, &slots[8 * g], 8 * sizeof(EncHuffTable), hipMemcpyHostToDevice,
+                               ctx_->stream);
+            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(built tables)");
+        }
+        if (any_general_builder_) {  // (`slots` leaves scope; the EncodeAction images' upload is as it always was)
+            e = hipStreamSynchronize(ctx_->stream);
+            if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(built tables)");
+        }
     }
     (void)hipEventRecord(ev_[1], ctx_->stream);
     std::vector<uint64_t> raw_bits((size_t)n);
@@ -421,7 +846,7 @@ int EncodeBatch::encode() {
     // The chains are per image: a batch of ONE image is one chain, as long as the image has workgroups, and runs at the speed the
     // look-back travels (one 8192 x 8192 canvas: 0.13 ms against the two kernels' 0.107); from two images on the one pass wins.
     bool fused_emit = false;
-    bool try_fused = enc_fused_emit_enabled() && !any_restart_ && emit_hint_ != 0xFFFFFFFFu && n >= 2;
+    bool try_fused = enc_fused_emit_enabled() && !any_restart_ && emit_hint_ != 0xFFFFFFFFu && n >= 2 && layouts_.empty();  // (bits_emit_kernel: EncodeAction arrangements)
     uint64_t slot = 0;
     const size_t chain_bytes = 256 + enc_chain_bytes(n_work_blk_);  // control words | one record per workgroup
     if (try_fused) {
@@ -469,7 +894,7 @@ int EncodeBatch::encode() {
     uint32_t *wg_bits = reinterpret_cast<uint32_t *>((uint8_t *)d_bit_off_.ptr + (((size_t)n_work_blk_ * sizeof(uint64_t) + 255) & ~(size_t)255));
     e = launch_block_bits(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_blk_.ptr, n_work_blk_,
                           (const EncHuffTable *)d_tables_.ptr, (const int16_t *)d_coefs_.ptr, (uint32_t *)d_bits_.ptr, n, wg_bits, (uint64_t *)d_bit_off_.ptr,
-                          (uint64_t *)d_raw_bits_.ptr);
+                          (uint64_t *)d_raw_bits_.ptr, layouts, any_plain);
     if (e != hipSuccess) return hip_fail(e, "block_bits_kernel");
     (void)hipEventRecord(ev_[2], ctx_->stream);
     // the sizes of the raw and finished streams depend on the data: one host round trip
@@ -537,7 +962,7 @@ int EncodeBatch::encode() {
     if (!fused_emit) {
         e = launch_emit(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_blk_.ptr, n_work_blk_, (const EncHuffTable *)d_tables_.ptr,
                         (const int16_t *)d_coefs_.ptr, (const uint32_t *)d_bits_.ptr, (const uint64_t *)d_bit_off_.ptr, (const uint64_t *)d_raw_bits_.ptr,
-                        (uint8_t *)d_raw_.ptr, (uint32_t *)d_marks_.ptr, (uint32_t)std::min<uint64_t>((emit_words + 1023) & ~1023ull, kEmitLdsWordsMax));
+                        (uint8_t *)d_raw_.ptr, (uint32_t *)d_marks_.ptr, (uint32_t)std::min<uint64_t>((emit_words + 1023) & ~1023ull, kEmitLdsWordsMax), layouts, any_plain);
         if (e != hipSuccess) return hip_fail(e, "emit_kernel");
     }
     (void)hipEventRecord(ev_[4], ctx_->stream);
@@ -568,7 +993,7 @@ int EncodeBatch::stage_ms(float ms[5]) {
 int EncodeBatch::encoded_size(int i, size_t *bytes) const {
     if (i < 0 || i >= (int)images_.size() || !bytes || !encoded_) return JPGPU_ERR_ARGUMENT;
     if (status_[i] != JPGPU_OK) {
-        ctx_->last_error = "No symbol is recorded.";
+        ctx_->last_error = messages_[i];
         return status_[i];
     }
     *bytes = (size_t)out_len_[i];
@@ -578,7 +1003,7 @@ int EncodeBatch::encoded_size(int i, size_t *bytes) const {
 int EncodeBatch::download(int i, void *dst, size_t cap) {
     if (i < 0 || i >= (int)images_.size() || !dst) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encode_download: bad argument");
     if (!encoded_) return fail(JPGPU_ERR_INVALID_OPERATION, "Nothing has been encoded yet.");
-    if (status_[i] != JPGPU_OK) return fail(status_[i], "No symbol is recorded.");
+    if (status_[i] != JPGPU_OK) return fail(status_[i], messages_[i]);
     if (cap < out_len_[i]) return fail(JPGPU_ERR_ARGUMENT, "Destination buffer is too small.");
     hipError_t e = hipMemcpy(dst, (const uint8_t *)d_out_.ptr + images_[i].out_off, (size_t)out_len_[i], hipMemcpyDeviceToHost);
     return e == hipSuccess ? JPGPU_OK : hip_fail(e, "hipMemcpy(encoded stream)");
@@ -591,7 +1016,15 @@ int EncodeBatch::download_coefficients(int i, int16_t *dst, size_t cap_blocks) {
     const DevEncImage &im = images_[i];
     hipError_t e = hipMemcpy(dst, (const int16_t *)d_coefs_.ptr + im.coef_off * 64, (size_t)im.total_blocks * 128, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy(coefficients)");
-    if (im.table_base != 0) {
+    if (im.layout != 0 && layouts_[im.layout - 1].own_blocks != 0) {
+        // a described arrangement on the TransformBlocks path: blocks outside their component's grid are the allocator's dummy block
+        const DevEncLayout &L = layouts_[im.layout - 1];
+        for (uint32_t blk = 0; blk < im.total_blocks; blk++) {
+            const uint32_t mcu = blk / im.bpm, b = blk - mcu * im.bpm, c = L.blk_comp[b];
+            const uint32_t bx = (mcu % im.mcus_per_line) * L.h[c] + L.blk_x[b], by = (mcu / im.mcus_per_line) * L.v[c] + L.blk_y[b];
+            if ((bx >= L.grid_w[c] || by >= L.grid_h[c]) && blk != L.dummy_blk) memcpy(dst + (size_t)blk * 64, dst + (size_t)L.dummy_blk * 64, 128);
+        }
+    } else if (im.table_base != 0) {
         // optimizeCoding: the blocks as BuildHuffmanTables / WritePreparedScanData see them -- luma blocks outside the
         // component's own grid alias the allocator's dummy block (enc_source_block in encode_kernels.hip)
         const uint32_t ny = im.luma_h * im.luma_v, last = (im.mcus_per_line * im.mcus_per_column - 1) * im.bpm + ny - 1;

@@ -11,11 +11,40 @@ namespace jpgpu {
 
 void rgb_ycc_factors(int32_t out[8]);
 
+// A jpgpu_encode_description resolved on the host (no device needed): the reference's checks, the marker segments, the by-symbol
+// Huffman tables and the block map of the general kernels -- or the jpgpu_encode_params of the EncodeAction arrangement it is.
+struct EncPlan {
+    int status = JPGPU_OK;  // JPGPU_OK, or what Encode() of this image reports (the refused arrangement, an empty builder)
+    std::string message;
+    bool legacy = false;    // an EncodeAction arrangement: today's entry point takes it
+    jpgpu_encode_params params = {};
+    bool legacy_has_quant = false;  // SetQuantizationTable with the caller's tables 0 and 1 (legacy_quant)
+    uint16_t legacy_quant[2][64] = {};
+    int width = 0, height = 0, in_components = 0, input_rgb = 0, restart_interval = 0;  // of a described arrangement
+    bool any_builder = false;
+    int most_optimal = 0;
+    int n_slots = 0;
+    struct Slot {
+        bool given = false;
+        uint8_t tc_th = 0;         // the DHT's Tc/Th byte
+        EncHuffTable table;        // given: GetCode for all 256 symbols
+        std::vector<uint8_t> dht;  // given: 16 counts + symbols, as TryWrite writes them
+    };
+    std::vector<Slot> slots;    // n_slots of them (none for an EncodeAction arrangement handed over as its parameters)
+    std::vector<uint8_t> header_pre, header_post;  // SOI, DQT, (DRI,) SOF0 | SOS
+    std::vector<uint8_t> header;                   // without builders: SOI .. SOS
+    std::vector<DevEncLayout> layout;  // one (none for an EncodeAction arrangement handed over as its parameters)
+    uint32_t bpm = 0;
+};
+// returns JPGPU_OK (plan->status may still refuse the image) or the argument error of the call, with its message in *error
+int resolve_encode_description(const jpgpu_encode_description &d, EncPlan *plan, std::string *error);
+
 class EncodeBatch {
   public:
     explicit EncodeBatch(jpgpu_ctx *ctx) : ctx_(ctx) {}
     ~EncodeBatch();
     int upload(const uint8_t *const *pixels, const jpgpu_encode_params *params, int n);  // SetInputReader x n (+ H2D)
+    int upload_described(const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n);
     int set_quantization_table(int i, int identifier, const uint16_t *zigzag64);           // SetQuantizationTable of image i
     int encode();                                                                        // JpegEncoder.Encode() x n
     // device time of the last encode() by stage (HIP events on the context's stream): E1 pixels -> quantised blocks, E2 bit counts
@@ -35,6 +64,7 @@ class EncodeBatch {
 
   private:
     int fail(int status, const std::string &msg);
+    int upload_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans);
     int hip_fail(hipError_t e, const char *what);
     jpgpu_ctx *ctx_;
     std::vector<DevEncImage> images_;
@@ -44,6 +74,13 @@ class EncodeBatch {
     std::vector<int> optimized_;                       // images with optimizeCoding
     std::vector<uint8_t> most_optimal_;                // ... and MostOptimalCoding (package merge)
     std::vector<int> status_;                          // per image: JPGPU_OK or the reference's failure ("No symbol is recorded.")
+    std::vector<std::string> messages_;                // ... and its message
+    std::vector<int> general_;                         // described images that are no EncodeAction arrangement (DevEncImage.layout = k + 1)
+    std::vector<EncPlan> general_plans_;               // ... their resolved descriptions
+    std::vector<DevEncLayout> layouts_;
+    DevBuffer d_layouts_;
+    bool any_general_builder_ = false;
+    bool upload_described_ = false;                    // the last upload was jpgpu_encoder_upload_described
     DevBuffer d_hist_;
     std::vector<uint64_t> out_len_;
     bool encoded_ = false;

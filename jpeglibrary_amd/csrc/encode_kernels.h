@@ -29,11 +29,31 @@ struct alignas(16) DevEncImage {
     uint32_t restart_interval;  // MCUs per restart interval, 0 = none (see jpgpu_encode_params)
     uint32_t n_units;     // lanes of block_bits / emit for this image: its blocks, or its restart intervals
     uint32_t hdr_off;     // the image's SOI..SOS bytes in the batch's header buffer (place_headers_kernel puts them at out_off)
-    uint32_t reserved0;
+    uint32_t layout;      // 0: an EncodeAction arrangement (the fields above say it all); k: a described arrangement, DevEncLayout k - 1
     int32_t r2y[8];       // Fix() factors of the RGB -> YCbCr tables (host: rgb_ycc_factors)
     uint16_t quant[2][64];  // zig-zag quantisation tables: luma, chroma
 };
 static_assert(sizeof(DevEncImage) % 16 == 0, "DevEncImage must be a multiple of 16 bytes");
+
+// A described arrangement (jpgpu_encode_description): what the general kernels need beside the DevEncImage.  Every block of an
+// MCU maps to its component through blk_comp; the component picks the quantisation table, the two Huffman slots (of the image's
+// eight, table_base + slot) and the DC predictor (the previous block of the same component).
+struct alignas(16) DevEncLayout {
+    uint32_t ncomp, max_h, max_v;
+    uint32_t own_blocks;   // 1: TransformBlocks / allocator semantics (a table is built from the image), 0: WriteScanData
+    uint32_t tail_first;   // the last block of an MCU that belongs to a full-resolution component (hs == vs == 1)
+    uint32_t dummy_blk;    // own_blocks: the block (of the image) that holds what the allocator's dummy block ends up with
+    uint32_t table_base;   // first of the image's 8 Huffman slots in the table array
+    uint32_t hist_index;   // the image's 8 x 256 counters in the statistics buffer
+    uint8_t blk_comp[64], blk_x[64], blk_y[64];  // block of the MCU -> component, position inside the component's h x v
+    uint8_t h[4], v[4], hs[4], vs[4], dc_slot[4], ac_slot[4], first_blk[4], reserved[4];
+    uint32_t grid_w[4], grid_h[4];  // the component's own block grid (JpegBlockAllocator.cs:61-62)
+    // everything the entropy kernels need of a block of the MCU in ONE dword (enc_blk_*): component | x << 2 | y << 4 | h << 6 |
+    // v << 9 | DC slot << 12 | AC slot << 15 | the component's first block << 18 | its last block << 24
+    uint32_t blk_info[64];
+    uint16_t quant[4][64];          // captured quantisation tables by component, zig-zag
+};
+static_assert(sizeof(DevEncLayout) % 16 == 0, "DevEncLayout must be a multiple of 16 bytes");
 
 // JpegHuffmanEncodingTable.GetCode by symbol (ref: JpegHuffmanEncodingTable.cs:94-100); len 0 = no code
 struct EncHuffTable {
@@ -56,14 +76,20 @@ hipError_t launch_fdct_quant(hipStream_t stream, const uint8_t *pixels, const De
                              uint32_t fused_shapes, bool any_other);
 int enc_image_fused_shape(const DevEncImage &im);
 size_t enc_sample_bytes_per_mcu(uint32_t luma_h, uint32_t luma_v, uint32_t components);
+// the described arrangements (DevEncImage.layout != 0): pixels -> quantised blocks in one kernel, one lane per MCU; then the
+// general forms of block_stats / block_bits / emit (launch_*: `layouts` != nullptr runs them beside the EncodeAction forms,
+// each form leaving the other's images alone)
+hipError_t launch_fdct_quant_general(hipStream_t stream, const uint8_t *pixels, const DevEncImage *images, const DevEncLayout *layouts,
+                                     const EncWork *work, int n_work, int16_t *coefs);
 hipError_t launch_block_bits(hipStream_t stream, const DevEncImage *images, const EncWork *work, int n_work, const EncHuffTable *tables,
-                             const int16_t *coefs, uint32_t *bits, int n_images, uint32_t *wg_bits, uint64_t *wg_base, uint64_t *raw_bits);
+                             const int16_t *coefs, uint32_t *bits, int n_images, uint32_t *wg_bits, uint64_t *wg_base, uint64_t *raw_bits,
+                             const DevEncLayout *layouts = nullptr, bool any_plain = true);
 // optimizeCoding: GatherBlockStatistics for every block (ref: JpegEncoder.cs:552-597) -> hist[image][4][256]
 hipError_t launch_block_stats(hipStream_t stream, const DevEncImage *images, const EncWork *work, int n_work, const int16_t *coefs,
-                              uint32_t *hist);
+                              uint32_t *hist, const DevEncLayout *layouts = nullptr, bool any_plain = true);
 hipError_t launch_emit(hipStream_t stream, const DevEncImage *images, const EncWork *work, int n_work, const EncHuffTable *tables,
                        const int16_t *coefs, const uint32_t *bits, const uint64_t *wg_base, const uint64_t *raw_bits, uint8_t *raw,
-                       uint32_t *marks, uint32_t lds_words);
+                       uint32_t *marks, uint32_t lds_words, const DevEncLayout *layouts = nullptr, bool any_plain = true);
 // E2 + E3 as one pass over the blocks (round 5; images without restart intervals): see bits_emit_kernel
 size_t enc_chain_bytes(int n_work);
 hipError_t launch_bits_emit(hipStream_t stream, const DevEncImage *images, const EncWork *work, int n_work, const EncHuffTable *tables,

@@ -85,7 +85,7 @@ __device__ __forceinline__ void block_fdct(float (&f)[64]) {
 // 1 x 1 -> instance 1, 2, 3; from R,G,B,A pixels -> 4, 5, 6); every other shape (0) goes through E1a + E1b.
 __host__ __device__ inline int enc_fused_shape(const DevEncImage &im) {
     // (four-byte pixels: R, G, B, A with the alpha ignored -- ConvertRgba32ToYCbCr8, instances 4, 5, 6)
-    if (im.components != 3 || !(im.in_components == 3 || (im.in_components == 4 && im.input_rgb != 0))) return 0;
+    if (im.layout != 0 || im.components != 3 || !(im.in_components == 3 || (im.in_components == 4 && im.input_rgb != 0))) return 0;
     const int wide = im.in_components == 4 ? 3 : 0;
     if (im.luma_h == 2 && im.luma_v == 2) return 1 + wide;
     if (im.luma_h == 2 && im.luma_v == 1) return 2 + wide;
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(8 * kEncMcusPerWg) void enc_gather_kernel(const uin
     extern __shared__ __attribute__((aligned(16))) uint8_t sh_records[];
     const EncWork wk = work[blockIdx.x];
     const DevEncImage &im = images[wk.image];
-    if (skip_fused && enc_fused_ok(im)) return;  // (uniform: fdct_fused_kernel takes the image)
+    if ((skip_fused && enc_fused_ok(im)) || im.layout != 0) return;  // (uniform: fdct_fused_kernel / enc_general_fdct_kernel takes the image)
     const uint32_t m = threadIdx.x % kEncMcusPerWg, k = threadIdx.x / kEncMcusPerWg;
     const uint32_t mcus_per_line = im.mcus_per_line;
     const uint32_t n_mcus = mcus_per_line * im.mcus_per_column;
@@ -392,7 +392,7 @@ __global__ __launch_bounds__(kEncMcusPerWg, JPGPU_E1B_WAVES) void fdct_quant_ker
     __shared__ __attribute__((aligned(16))) uint8_t sh_blk[kEncMcusPerWg * 128];
     const EncWork wk = work[blockIdx.x];
     const DevEncImage &im = images[wk.image];
-    if (skip_fused && enc_fused_ok(im)) return;
+    if ((skip_fused && enc_fused_ok(im)) || im.layout != 0) return;
     const uint32_t lane = threadIdx.x;
     if (lane < 64) {
         sh_q[0][lane] = quant_pair(im.quant[0][lane]);
@@ -473,6 +473,101 @@ __global__ __launch_bounds__(kEncMcusPerWg, JPGPU_E1B_WAVES) void fdct_quant_ker
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // read before the next block's rows overwrite it
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ E1 general
+//
+// E1 for a described arrangement (DevEncLayout): one lane per MCU walks the MCU's blocks in encode order, reads every block's
+// samples straight from the pixels (a box of hs x vs pixels per sample, zero outside the image: JpegBufferInputReader.cs:33-39),
+// and runs ShiftDataLevel + TransformFDCT + ZigZagAndQuantizeBlock on it.  Nothing is assumed about which component comes first.
+//   WriteScanData (own_blocks == 0): block (x, y) of a component sits at pixel ((colMcu maxH + x) 8, (rowMcu maxV + y) 8)
+//     (JpegEncoder.cs:701-720) and a sub-sampled block is ADDED to the one block buffer of the scan, which holds the previous
+//     block's quantised coefficients (:720, :756-799).  A full-resolution block overwrites the buffer, so the chain into an MCU
+//     starts at the previous MCU's last full-resolution block (tail_first): the lane recomputes that tail first -- no lane
+//     waits for another, and a workgroup boundary is no different from any other MCU boundary.  MCU 0 starts from zeros.
+//   TransformBlocks (own_blocks == 1): block (x, y) sits at pixel ((colMcu h + x) 8 hs, (rowMcu v + y) 8 vs) (:457-468) in a
+//     zeroed allocator block of its own; blocks outside the component's grid all are the allocator's ONE dummy block, which
+//     a sub-sampled read adds to and a full-resolution read overwrites.  What the dummy holds at the end is decided inside the
+//     last MCU (its full-resolution component leaves the grid there whenever any component does anywhere): the carry below
+//     follows the out-of-grid blocks of the lane's own MCU, and the host names the last of them in the last MCU (dummy_blk).
+__device__ __forceinline__ int32_t enc_general_sample(const EncSrc &s, uint32_t c, uint32_t x, uint32_t y) {
+    if (x >= s.width || y >= s.height) return 0;
+    const uint8_t *p = s.px + ((size_t)y * s.width + x) * s.comps;
+    if (!s.rgb) return p[c];
+    return enc_convert(s, c, p[0], p[1], p[2]);
+}
+
+__global__ __launch_bounds__(kEncMcusPerWg) void enc_general_fdct_kernel(const uint8_t *__restrict__ pixels, const DevEncImage *__restrict__ images,
+                                                                         const DevEncLayout *__restrict__ layouts, const EncWork *__restrict__ work,
+                                                                         int16_t *__restrict__ coefs) {
+    __shared__ QuantPair sh_q[4][64];
+    const EncWork wk = work[blockIdx.x];
+    const DevEncImage &im = images[wk.image];
+    if (im.layout == 0) return;  // (uniform: an EncodeAction arrangement)
+    const DevEncLayout &L = layouts[im.layout - 1u];
+    for (uint32_t i = threadIdx.x; i < 256u; i += kEncMcusPerWg) sh_q[i >> 6][i & 63u] = quant_pair(L.quant[i >> 6][i & 63u]);
+    __syncthreads();
+    const uint32_t mcus_per_line = im.mcus_per_line, n_mcus = mcus_per_line * im.mcus_per_column, bpm = im.bpm;
+    const uint32_t mcu = wk.first + threadIdx.x;
+    if (mcu >= n_mcus) return;
+    EncSrc src;
+    src.px = pixels + im.px_off;
+    src.width = im.width;
+    src.height = im.height;
+    src.comps = im.in_components;
+    src.rgb = im.input_rgb != 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) src.k[i] = im.r2y[i];
+    const bool own = L.own_blocks != 0;
+    // the block buffer (WriteScanData) / the dummy block (TransformBlocks) as the lane's blocks find it, packed zig-zag int16
+    uint4 carry[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) carry[r] = uint4{0, 0, 0, 0};
+    const uint32_t c0 = L.blk_comp[0];
+    const bool need_tail = !own && mcu > 0 && (L.hs[c0] != 1 || L.vs[c0] != 1);
+#pragma unroll 1
+    for (uint32_t t = need_tail ? L.tail_first : bpm; t < 2u * bpm; t++) {
+        const bool mine = t >= bpm;  // (not the previous MCU's tail)
+        const uint32_t m = mine ? mcu : mcu - 1u, b = mine ? t - bpm : t;
+        const uint32_t c = L.blk_comp[b], hs = L.hs[c], vs = L.vs[c];
+        const uint32_t mx = m % mcus_per_line, my = m / mcus_per_line;
+        uint32_t x0, y0;
+        bool in_grid = true;
+        if (own) {
+            const uint32_t bx = mx * L.h[c] + L.blk_x[b], by = my * L.v[c] + L.blk_y[b];
+            x0 = bx * 8u * hs;
+            y0 = by * 8u * vs;
+            in_grid = bx < L.grid_w[c] && by < L.grid_h[c];
+        } else {
+            x0 = (mx * L.max_h + L.blk_x[b]) * 8u;
+            y0 = (my * L.max_v + L.blk_y[b]) * 8u;
+        }
+        const bool sub = hs != 1u || vs != 1u;
+        const bool add = sub && (own ? !in_grid : true);  // the read adds to what the buffer holds
+        const uint32_t total = (31 - __builtin_clz(hs)) + (31 - __builtin_clz(vs));
+        const int32_t half = total == 0 ? 0 : 1 << (total - 1);
+        int32_t smp[64];
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            int32_t base[8];
+            unpack8_i16(carry[r], base);
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                int32_t sum = 0;
+                for (uint32_t dy = 0; dy < vs; dy++)
+                    for (uint32_t dx = 0; dx < hs; dx++) sum += enc_general_sample(src, c, x0 + (uint32_t)i * hs + dx, y0 + (uint32_t)r * vs + dy);
+                // CopySubsampleBlock adds shorts (:796), then (short)((sum + delta) >> totalShift) (:783)
+                smp[r * 8 + i] = (int32_t)(int16_t)(((int32_t)(int16_t)((add ? base[i] : 0) + sum) + half) >> total);
+            }
+        }
+        int16_t *out = coefs + (im.coef_off + (uint64_t)m * bpm + b) * 64;
+        const bool keep = own ? !in_grid : true;  // ZigZagAndQuantizeBlock writes into the buffer the next read starts from
+        fdct_quantize_rows(smp, sh_q[c], [&](int r, const int32_t (&row)[8]) {
+            const uint4 pk = pack8_i16(row);
+            if (mine) *reinterpret_cast<uint4 *>(out + r * 8) = pk;
+            if (keep) carry[r] = pk;
+        });
     }
 }
 
@@ -879,6 +974,44 @@ __device__ __forceinline__ int32_t enc_dc_predictor(const DevEncImage &im, const
     return img_coefs[(size_t)enc_source_block(im, (mcu - 1) * im.bpm + pb) * 64];
 }
 
+// The same for a described arrangement: blocks outside their component's own grid alias the allocator's dummy block, whose final
+// content enc_general_fdct_kernel leaves in block dummy_blk (JpegBlockAllocator.cs:108-111)
+__device__ __forceinline__ uint32_t enc_general_source_block(const DevEncImage &im, const DevEncLayout &L, uint32_t mcu, uint32_t b) {
+    const uint32_t blk = mcu * im.bpm + b;
+    if (L.own_blocks == 0) return blk;
+    const uint32_t info = L.blk_info[b], c = info & 3u;
+    const uint32_t bx = (mcu % im.mcus_per_line) * ((info >> 6) & 7u) + ((info >> 2) & 3u);
+    const uint32_t by = (mcu / im.mcus_per_line) * ((info >> 9) & 7u) + ((info >> 4) & 3u);
+    return (bx < L.grid_w[c] && by < L.grid_h[c]) ? blk : L.dummy_blk;
+}
+
+// Where a block of the scan comes from and what it is coded with: source block, DC predictor, the two table slots.
+// G = false: the EncodeAction arrangement (luma blocks first, then 1 x 1 blocks on tables 1); G = true: a described one.
+struct EncBlockRef {
+    int32_t pred;
+    uint32_t src, dc, ac;
+};
+template <bool G>
+__device__ __forceinline__ EncBlockRef enc_block_ref(const DevEncImage &im, const DevEncLayout *L, const int16_t *img_coefs, uint32_t mcu, uint32_t b) {
+    EncBlockRef r;
+    if constexpr (!G) {
+        uint32_t comp;
+        r.pred = enc_dc_predictor(im, img_coefs, mcu, b, comp);
+        r.src = enc_source_block(im, mcu * im.bpm + b);
+        r.dc = comp == 0 ? 0 : 2;
+        r.ac = comp == 0 ? 1 : 3;
+    } else {
+        const uint32_t info = L->blk_info[b], first = (info >> 18) & 63u, last = (info >> 24) & 63u;
+        r.dc = (info >> 12) & 7u;
+        r.ac = (info >> 15) & 7u;
+        r.src = enc_general_source_block(im, *L, mcu, b);
+        if (b > first) r.pred = img_coefs[(size_t)enc_general_source_block(im, *L, mcu, b - 1) * 64];
+        else if (mcu == 0 || (im.restart_interval != 0 && mcu % im.restart_interval == 0)) r.pred = 0;
+        else r.pred = img_coefs[(size_t)enc_general_source_block(im, *L, mcu - 1, last) * 64];
+    }
+    return r;
+}
+
 // Walks the symbols of one block in EncodeBlock order (:828-870) and hands (code, length) pairs to `put`.
 template <typename Put>
 __device__ __forceinline__ void enc_block_symbols(const uint4 (&cv)[8], int32_t dc_pred, const EncHuffTable &dc, const EncHuffTable &ac, Put put) {
@@ -931,23 +1064,28 @@ __device__ __forceinline__ void enc_block_symbols(const uint4 (&cv)[8], int32_t 
 
 // The four Huffman encoding tables of an image (DC0, AC0, DC1, AC1: 3 KB) staged in LDS: every symbol of every lane looks two of
 // their entries up.
+template <uint32_t N = 4>
 __device__ __forceinline__ void enc_stage_tables(const EncHuffTable *__restrict__ tables, uint32_t table_base, EncHuffTable *sh_tab) {
     const uint32_t *src = reinterpret_cast<const uint32_t *>(tables + table_base);
     uint32_t *dst = reinterpret_cast<uint32_t *>(sh_tab);
-    for (uint32_t i = threadIdx.x; i < 4u * (uint32_t)sizeof(EncHuffTable) / 4u; i += blockDim.x) dst[i] = src[i];
+    for (uint32_t i = threadIdx.x; i < N * (uint32_t)sizeof(EncHuffTable) / 4u; i += blockDim.x) dst[i] = src[i];
     __syncthreads();
 }
 
 // E2: bits of every block (EncodeBlock with a counting writer).  bits[] receives the block's offset inside its workgroup
 // of 256 blocks, wg_bits[] the workgroup's total: the image-wide scan (block_offsets_kernel) then runs over one entry per
 // workgroup instead of one per block.
+template <bool G>
 __global__ __launch_bounds__(256) void block_bits_kernel(const DevEncImage *__restrict__ images, const EncWork *__restrict__ work,
                                                          const EncHuffTable *__restrict__ tables, const int16_t *__restrict__ coefs,
-                                                         uint32_t *__restrict__ bits, uint32_t *__restrict__ wg_bits) {
-    __shared__ EncHuffTable sh_tab[4];
+                                                         uint32_t *__restrict__ bits, uint32_t *__restrict__ wg_bits,
+                                                         const DevEncLayout *__restrict__ layouts) {
+    __shared__ EncHuffTable sh_tab[G ? 8 : 4];
     const EncWork wk = work[blockIdx.x];
     const DevEncImage &im = images[wk.image];
-    enc_stage_tables(tables, im.table_base, sh_tab);
+    if ((im.layout != 0) != G) return;  // (uniform: the other form of this kernel takes the image)
+    const DevEncLayout *L = G ? layouts + (im.layout - 1u) : nullptr;
+    enc_stage_tables<G ? 8 : 4>(tables, G ? L->table_base : im.table_base, sh_tab);
     const uint32_t blk = wk.first + threadIdx.x;  // block, or restart interval
     uint32_t n = 0;
     const int16_t *img_coefs = coefs + im.coef_off * 64;
@@ -959,22 +1097,19 @@ __global__ __launch_bounds__(256) void block_bits_kernel(const DevEncImage *__re
             const uint32_t end_mcu = first_mcu + im.restart_interval < total_mcus ? first_mcu + im.restart_interval : total_mcus;
             for (uint32_t mcu = first_mcu; mcu < end_mcu; mcu++)
                 for (uint32_t b = 0; b < im.bpm; b++) {
-                    uint32_t comp;
-                    const int32_t pred = enc_dc_predictor(im, img_coefs, mcu, b, comp);
-                    const uint4 *src = reinterpret_cast<const uint4 *>(img_coefs + (size_t)enc_source_block(im, mcu * im.bpm + b) * 64);
+                    const EncBlockRef ref = enc_block_ref<G>(im, L, img_coefs, mcu, b);
+                    const uint4 *src = reinterpret_cast<const uint4 *>(img_coefs + (size_t)ref.src * 64);
                     const uint4 cv[8] = {src[0], src[1], src[2], src[3], src[4], src[5], src[6], src[7]};
-                    enc_block_symbols(cv, pred, sh_tab[comp == 0 ? 0 : 2], sh_tab[comp == 0 ? 1 : 3],
-                                      [&](uint32_t, uint32_t len) { n += len; });
+                    enc_block_symbols(cv, ref.pred, sh_tab[ref.dc], sh_tab[ref.ac], [&](uint32_t, uint32_t len) { n += len; });
                 }
             n = (n + 7u) & ~7u;
         }
     } else if (blk < im.total_blocks) {
     const uint32_t mcu = blk / im.bpm, b = blk - mcu * im.bpm;
-    uint32_t comp;
-    const int32_t pred = enc_dc_predictor(im, img_coefs, mcu, b, comp);
-    const uint4 *src = reinterpret_cast<const uint4 *>(img_coefs + (size_t)enc_source_block(im, blk) * 64);
+    const EncBlockRef ref = enc_block_ref<G>(im, L, img_coefs, mcu, b);
+    const uint4 *src = reinterpret_cast<const uint4 *>(img_coefs + (size_t)ref.src * 64);
     const uint4 cv[8] = {src[0], src[1], src[2], src[3], src[4], src[5], src[6], src[7]};
-    enc_block_symbols(cv, pred, sh_tab[comp == 0 ? 0 : 2], sh_tab[comp == 0 ? 1 : 3], [&](uint32_t, uint32_t len) { n += len; });
+    enc_block_symbols(cv, ref.pred, sh_tab[ref.dc], sh_tab[ref.ac], [&](uint32_t, uint32_t len) { n += len; });
     }
     // exclusive scan of n over the workgroup
     __shared__ uint32_t sh_wave[4];
@@ -1002,23 +1137,28 @@ __global__ __launch_bounds__(256) void block_bits_kernel(const DevEncImage *__re
 // at compile time (enc_block_symbols' walk with a counting `put`) -- where a loop of 63 two-byte loads per lane walked it before
 // (1.9 ms per 8192 x 8192 canvas against E1's 0.09: the whole cost of optimizeCoding), and every WAVE counts into a histogram of
 // its own (most symbols of most blocks are the same handful: 256 lanes on one LDS word).
+template <bool G>
 __global__ __launch_bounds__(256) void block_stats_kernel(const DevEncImage *__restrict__ images, const EncWork *__restrict__ work,
-                                                          const int16_t *__restrict__ coefs, uint32_t *__restrict__ hist) {
-    __shared__ uint32_t lh[4][4 * 256];  // [wave][table][symbol]
+                                                          const int16_t *__restrict__ coefs, uint32_t *__restrict__ hist,
+                                                          const DevEncLayout *__restrict__ layouts) {
+    constexpr uint32_t kTables = G ? 8 : 4;  // a described image: up to eight tables (statistics of a given one are not read)
+    __shared__ uint32_t lh[4][kTables * 256];  // [wave][table][symbol]
     const EncWork wk = work[blockIdx.x];
     const DevEncImage &im = images[wk.image];
-    for (uint32_t i = threadIdx.x; i < 4u * 4u * 256u; i += 256u) (&lh[0][0])[i] = 0;
+    if ((im.layout != 0) != G) return;  // (uniform: the other form of this kernel takes the image)
+    const DevEncLayout *L = G ? layouts + (im.layout - 1u) : nullptr;
+    for (uint32_t i = threadIdx.x; i < 4u * kTables * 256u; i += 256u) (&lh[0][0])[i] = 0;
     __syncthreads();
     const uint32_t blk = wk.first + threadIdx.x;
-    if (im.table_base != 0 && blk < im.total_blocks) {
+    if ((G ? L->own_blocks != 0 : im.table_base != 0) && blk < im.total_blocks) {
         const int16_t *img_coefs = coefs + im.coef_off * 64;
         const uint32_t mcu = blk / im.bpm, b = blk - mcu * im.bpm;
-        uint32_t comp;
-        const int32_t pred = enc_dc_predictor(im, img_coefs, mcu, b, comp);
-        const uint4 *src = reinterpret_cast<const uint4 *>(img_coefs + (size_t)enc_source_block(im, blk) * 64);
+        const EncBlockRef ref = enc_block_ref<G>(im, L, img_coefs, mcu, b);
+        const int32_t pred = ref.pred;
+        const uint4 *src = reinterpret_cast<const uint4 *>(img_coefs + (size_t)ref.src * 64);
         const uint4 cv[8] = {src[0], src[1], src[2], src[3], src[4], src[5], src[6], src[7]};
         uint32_t *mine = lh[threadIdx.x >> 6];
-        uint32_t *hdc = mine + (comp == 0 ? 0 : 2) * 256, *hac = mine + (comp == 0 ? 1 : 3) * 256;
+        uint32_t *hdc = mine + ref.dc * 256, *hac = mine + ref.ac * 256;
         const uint32_t w[32] = {cv[0].x, cv[0].y, cv[0].z, cv[0].w, cv[1].x, cv[1].y, cv[1].z, cv[1].w, cv[2].x, cv[2].y, cv[2].z,
                                 cv[2].w, cv[3].x, cv[3].y, cv[3].z, cv[3].w, cv[4].x, cv[4].y, cv[4].z, cv[4].w, cv[5].x, cv[5].y,
                                 cv[5].z, cv[5].w, cv[6].x, cv[6].y, cv[6].z, cv[6].w, cv[7].x, cv[7].y, cv[7].z, cv[7].w};
@@ -1053,8 +1193,8 @@ __global__ __launch_bounds__(256) void block_stats_kernel(const DevEncImage *__r
         if (run > 0) atomicAdd(&hac[0], 1u);
     }
     __syncthreads();
-    uint32_t *gh = hist + (size_t)wk.image * 4 * 256;
-    for (uint32_t i = threadIdx.x; i < 4u * 256u; i += 256u) {
+    uint32_t *gh = hist + (G ? (size_t)L->hist_index : (size_t)wk.image * 4 * 256);
+    for (uint32_t i = threadIdx.x; i < kTables * 256u; i += 256u) {
         const uint32_t v = lh[0][i] + lh[1][i] + lh[2][i] + lh[3][i];
         if (v != 0) atomicAdd(&gh[i], v);
     }
@@ -1099,16 +1239,19 @@ __global__ __launch_bounds__(1024) void block_offsets_kernel(const DevEncImage *
 // LDS): the host has the images' bit totals by now and asks for twice the batch's largest AVERAGE stretch, between 8 and
 // 32 KB -- with the 32 KB it used to hold always, four workgroups fitted a CU and the kernel ran at 4 waves per SIMD:
 // 2.74 ms per 256 x 4K at Q75, 2.04 ms with 16 KB, 1.94 with the 8 KB the rule picks there (the walk alone, block_bits_kernel: 1.6).
+template <bool G>
 __global__ __launch_bounds__(256) void emit_kernel(const DevEncImage *__restrict__ images, const EncWork *__restrict__ work,
                                                    const EncHuffTable *__restrict__ tables, const int16_t *__restrict__ coefs,
                                                    const uint32_t *__restrict__ bits, const uint64_t *__restrict__ wg_base,
                                                    const uint64_t *__restrict__ raw_bits, uint8_t *__restrict__ raw,
-                                                   uint32_t *__restrict__ marks, uint32_t lds_words) {
+                                                   uint32_t *__restrict__ marks, uint32_t lds_words, const DevEncLayout *__restrict__ layouts) {
     extern __shared__ uint32_t sh_words[];
-    __shared__ EncHuffTable sh_tab[4];
+    __shared__ EncHuffTable sh_tab[G ? 8 : 4];
     const EncWork wk = work[blockIdx.x];
     const DevEncImage &im = images[wk.image];
-    enc_stage_tables(tables, im.table_base, sh_tab);
+    if ((im.layout != 0) != G) return;  // (uniform: the other form of this kernel takes the image)
+    const DevEncLayout *L = G ? layouts + (im.layout - 1u) : nullptr;
+    enc_stage_tables<G ? 8 : 4>(tables, G ? L->table_base : im.table_base, sh_tab);
     const uint32_t blk = wk.first + threadIdx.x;  // block, or restart interval
     const bool active = blk < im.n_units;
     const int16_t *img_coefs = coefs + im.coef_off * 64;
@@ -1157,11 +1300,10 @@ __global__ __launch_bounds__(256) void emit_kernel(const DevEncImage *__restrict
         };
         for (uint32_t mcu = first_mcu; mcu < end_mcu; mcu++)
             for (uint32_t b = 0; b < im.bpm; b++) {
-                uint32_t comp;
-                const int32_t pred = enc_dc_predictor(im, img_coefs, mcu, b, comp);
-                const uint4 *src = reinterpret_cast<const uint4 *>(img_coefs + (size_t)enc_source_block(im, mcu * im.bpm + b) * 64);
+                const EncBlockRef ref = enc_block_ref<G>(im, L, img_coefs, mcu, b);
+                const uint4 *src = reinterpret_cast<const uint4 *>(img_coefs + (size_t)ref.src * 64);
                 const uint4 cv[8] = {src[0], src[1], src[2], src[3], src[4], src[5], src[6], src[7]};
-                enc_block_symbols(cv, pred, sh_tab[comp == 0 ? 0 : 2], sh_tab[comp == 0 ? 1 : 3], put_counted);
+                enc_block_symbols(cv, ref.pred, sh_tab[ref.dc], sh_tab[ref.ac], put_counted);
             }
         const uint32_t rem = (8u - (nbits & 7u)) & 7u;
         if (rem) put((1u << rem) - 1u, rem);
@@ -1172,11 +1314,10 @@ __global__ __launch_bounds__(256) void emit_kernel(const DevEncImage *__restrict
         }
     } else if (active) {
         const uint32_t mcu = blk / im.bpm, b = blk - mcu * im.bpm;
-        uint32_t comp;
-        const int32_t pred = enc_dc_predictor(im, img_coefs, mcu, b, comp);
-        const uint4 *src = reinterpret_cast<const uint4 *>(img_coefs + (size_t)enc_source_block(im, blk) * 64);
+        const EncBlockRef ref = enc_block_ref<G>(im, L, img_coefs, mcu, b);
+        const uint4 *src = reinterpret_cast<const uint4 *>(img_coefs + (size_t)ref.src * 64);
         const uint4 cv[8] = {src[0], src[1], src[2], src[3], src[4], src[5], src[6], src[7]};
-        enc_block_symbols(cv, pred, sh_tab[comp == 0 ? 0 : 2], sh_tab[comp == 0 ? 1 : 3], put);
+        enc_block_symbols(cv, ref.pred, sh_tab[ref.dc], sh_tab[ref.ac], put);
         if (blk == im.total_blocks - 1) {
             // ExitBitMode (ref: JpegWriter.cs:123-147): pad the last byte with one-bits
             const uint32_t rem = (uint32_t)((8u - (raw_bits[wk.image] & 7u)) & 7u);
@@ -1540,26 +1681,39 @@ hipError_t launch_fdct_quant(hipStream_t stream, const uint8_t *pixels, const De
     }
     return hipGetLastError();
 }
-hipError_t launch_block_bits(hipStream_t stream, const DevEncImage *images, const EncWork *work, int n_work, const EncHuffTable *tables,
-                             const int16_t *coefs, uint32_t *bits, int n_images, uint32_t *wg_bits, uint64_t *wg_base, uint64_t *raw_bits) {
+hipError_t launch_fdct_quant_general(hipStream_t stream, const uint8_t *pixels, const DevEncImage *images, const DevEncLayout *layouts,
+                                     const EncWork *work, int n_work, int16_t *coefs) {
     if (n_work <= 0) return hipSuccess;
-    hipLaunchKernelGGL(block_bits_kernel, dim3(n_work), dim3(256), 0, stream, images, work, tables, coefs, bits, wg_bits);
+    hipLaunchKernelGGL(enc_general_fdct_kernel, dim3(n_work), dim3(kEncMcusPerWg), 0, stream, pixels, images, layouts, work, coefs);
+    return hipGetLastError();
+}
+hipError_t launch_block_bits(hipStream_t stream, const DevEncImage *images, const EncWork *work, int n_work, const EncHuffTable *tables,
+                             const int16_t *coefs, uint32_t *bits, int n_images, uint32_t *wg_bits, uint64_t *wg_base, uint64_t *raw_bits,
+                             const DevEncLayout *layouts, bool any_plain) {
+    if (n_work <= 0) return hipSuccess;
+    if (any_plain) hipLaunchKernelGGL(block_bits_kernel<false>, dim3(n_work), dim3(256), 0, stream, images, work, tables, coefs, bits, wg_bits, layouts);
+    if (layouts) hipLaunchKernelGGL(block_bits_kernel<true>, dim3(n_work), dim3(256), 0, stream, images, work, tables, coefs, bits, wg_bits, layouts);
     hipLaunchKernelGGL(block_offsets_kernel, dim3(n_images), dim3(1024), 0, stream, images, wg_bits, wg_base, raw_bits);
     return hipGetLastError();
 }
 hipError_t launch_block_stats(hipStream_t stream, const DevEncImage *images, const EncWork *work, int n_work, const int16_t *coefs,
-                              uint32_t *hist) {
+                              uint32_t *hist, const DevEncLayout *layouts, bool any_plain) {
     if (n_work <= 0) return hipSuccess;
-    hipLaunchKernelGGL(block_stats_kernel, dim3(n_work), dim3(256), 0, stream, images, work, coefs, hist);
+    if (any_plain) hipLaunchKernelGGL(block_stats_kernel<false>, dim3(n_work), dim3(256), 0, stream, images, work, coefs, hist, layouts);
+    if (layouts) hipLaunchKernelGGL(block_stats_kernel<true>, dim3(n_work), dim3(256), 0, stream, images, work, coefs, hist, layouts);
     return hipGetLastError();
 }
 hipError_t launch_emit(hipStream_t stream, const DevEncImage *images, const EncWork *work, int n_work, const EncHuffTable *tables,
                        const int16_t *coefs, const uint32_t *bits, const uint64_t *wg_base, const uint64_t *raw_bits, uint8_t *raw,
-                       uint32_t *marks, uint32_t lds_words) {
+                       uint32_t *marks, uint32_t lds_words, const DevEncLayout *layouts, bool any_plain) {
     if (n_work <= 0) return hipSuccess;
     if (lds_words != 0) lds_words = std::min(std::max(lds_words, kEmitLdsWordsMin), kEmitLdsWordsMax);  // 0: no workgroup's stretch would fit
-    hipLaunchKernelGGL(emit_kernel, dim3(n_work), dim3(256), (size_t)lds_words * 4, stream, images, work, tables, coefs, bits, wg_base, raw_bits, raw,
-                       marks, lds_words);
+    if (any_plain)
+        hipLaunchKernelGGL(emit_kernel<false>, dim3(n_work), dim3(256), (size_t)lds_words * 4, stream, images, work, tables, coefs, bits, wg_base, raw_bits,
+                           raw, marks, lds_words, layouts);
+    if (layouts)
+        hipLaunchKernelGGL(emit_kernel<true>, dim3(n_work), dim3(256), (size_t)lds_words * 4, stream, images, work, tables, coefs, bits, wg_base, raw_bits,
+                           raw, marks, lds_words, layouts);
     return hipGetLastError();
 }
 // E2 + E3 in one pass (restart-free batches): chain = n_work x 16 bytes and ctl = 2 words, both zeroed by the caller; ctl[1] != 0

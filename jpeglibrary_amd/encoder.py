@@ -16,6 +16,50 @@ from .errors import raise_for_status
 _lib = _capi.lib
 
 
+def describe(width, height, components, quant_tables, huffman_tables, in_components=None, input_rgb=0, restart_interval=0,
+             most_optimal_coding=False):
+    """A jpgpu_encode_description: the encoder's state after the caller's Set* / AddComponent sequence (include/jpgpu.h, 4b).
+    components: (component_index, h, v, tq, td, ta, captured 64 zig-zag elements) in AddComponent order;
+    quant_tables: (identifier, 64 zig-zag elements) in SetQuantizationTable order;
+    huffman_tables: (table_class, identifier, codes) in SetHuffmanTable order, codes = None (built from the image) or the
+    JpegHuffmanCanonicalCode[] as (symbol, code, length) triples."""
+    if len(components) > _capi.ENC_MAX_COMPONENTS:
+        raise ValueError("at most four components can be described")
+    if len(quant_tables) > _capi.ENC_MAX_TABLES or len(huffman_tables) > _capi.ENC_MAX_TABLES:
+        raise ValueError("at most eight tables of a kind can be described")
+    d = _capi.EncodeDescription()
+    d.width, d.height = int(width), int(height)
+    d.in_components = len(components) if in_components is None else int(in_components)
+    d.input_rgb, d.restart_interval, d.most_optimal_coding = int(input_rgb), int(restart_interval), int(bool(most_optimal_coding))
+    d.num_components, d.num_quant_tables, d.num_huffman_tables = len(components), len(quant_tables), len(huffman_tables)
+    for k, (index, h, v, tq, td, ta, quant) in enumerate(components):
+        c = d.components[k]
+        c.component_index, c.h, c.v, c.tq, c.td, c.ta = int(index), int(h), int(v), int(tq), int(td), int(ta)
+        c.quant[:] = [int(q) for q in quant]
+    for k, (identifier, elements) in enumerate(quant_tables):
+        d.quant_tables[k].identifier = int(identifier)
+        d.quant_tables[k].elements[:] = [int(q) for q in elements]
+    for k, (table_class, identifier, codes) in enumerate(huffman_tables):
+        t = d.huffman_tables[k]
+        t.table_class, t.identifier, t.given = int(table_class), int(identifier), 0 if codes is None else 1
+        if codes is not None:
+            if len(codes) > 256:
+                raise ValueError("a Huffman table holds at most 256 codes")
+            t.num_codes = len(codes)
+            for j, (symbol, code, length) in enumerate(codes):
+                t.symbol[j], t.code[j], t.length[j] = int(symbol), int(code), int(length)
+    return d
+
+
+def description_header(desc):
+    """Host only: (status, message, SOI..SOS bytes of the WriteScanData path) for a description, no device needed."""
+    n = C.c_size_t(0)
+    buf = C.create_string_buffer(4096)
+    msg = C.create_string_buffer(512)
+    rc = _lib.jpgpu_encode_description_header(C.byref(desc), buf, len(buf), C.byref(n), msg, len(msg))
+    return rc, msg.value.decode("utf-8", "replace"), buf.raw[:n.value] if rc == 0 else b""
+
+
 class EncodeBatch:
     def __init__(self, ctx: Context = None):
         self.ctx = ctx or default_context()
@@ -55,6 +99,34 @@ class EncodeBatch:
         self._check(_lib.jpgpu_encoder_upload(self._h, ptrs, params, n))
         self._n = n
         return self
+
+    def upload_described(self, images, descriptions):
+        """images: uint8 arrays (H, W, in_components) or (H, W); descriptions: describe(...) per image.  An arrangement the device
+        path refuses is that image's status (image_status / output raise it); the other images of the upload are unaffected."""
+        n = len(images)
+        if len(descriptions) != n:
+            raise ValueError("one description per image")
+        ptrs = (C.c_void_p * n)()
+        descs = (_capi.EncodeDescription * n)(*descriptions)
+        keep = []
+        self._blocks = []
+        for i, im in enumerate(images):
+            a = np.ascontiguousarray(im, dtype=np.uint8)
+            d = descs[i]
+            if a.size != d.width * d.height * d.in_components:
+                raise ValueError("image %d: %d samples for %d x %d x %d" % (i, a.size, d.height, d.width, d.in_components))
+            keep.append(a)
+            ptrs[i] = a.ctypes.data
+            comps = [d.components[k] for k in range(d.num_components)]
+            mh, mv = max([c.h for c in comps] or [1]), max([c.v for c in comps] or [1])
+            self._blocks.append((-(-d.width // (8 * mh))) * (-(-d.height // (8 * mv))) * sum(c.h * c.v for c in comps))
+        self._check(_lib.jpgpu_encoder_upload_described(self._h, ptrs, descs, n))
+        self._n = n
+        return self
+
+    def image_status(self, i):
+        """JPGPU_OK or the status Encode() of image i reports, as known so far."""
+        return _lib.jpgpu_encoder_image_status(self._h, i)
 
     def set_quantization_table(self, i, identifier, zigzag64):
         """SetQuantizationTable for image i: the caller's own table (zig-zag order, 1..255) instead of the scaled standard one."""

@@ -10,10 +10,14 @@ GPU encoder, so that a test can be written like the reference's own callers (app
     encoder.AddComponent(1, 0, 0, 0, 2, 2); encoder.AddComponent(2, 1, 1, 1, 1, 1); encoder.AddComponent(3, 1, 1, 1, 1, 1)
     encoder.SetInputReader(JpegBufferInputReader(width, height, 3, ycbcr)); encoder.SetOutput(writer); encoder.Encode()
 
-Same names, argument meaning and exceptions.  What the device path takes is the EncodeAction family: component 1 with sampling
-(h, v) on tables 0, optionally components 2 and 3 with sampling 1 x 1 on tables 1; quantisation tables of the caller's choice
-(element precision 0); Huffman tables either the four standard ones or all four left to be built from the image; any other
-arrangement the reference's encoder would accept raises NotSupportedException here.  Nothing touches the device before Encode().
+Same names, argument meaning and exceptions.  The device path takes every arrangement AddComponent accepts: one to four
+components with sampling factors 1, 2 or 4 each, any component identifiers, quantisation tables of the caller's choice under any
+identifier (the stream's DQT holds the tables as they are at Encode(), a component quantises with the one it captured), Huffman
+tables given (the standard ones, JpegHuffmanEncodingTable(codes), a JpegHuffmanEncodingTableBuilder's result) or left to be
+built from the image, table by table.  Encode() hands the state to the device as one described image (jpgpu_encode_description);
+an EncodeAction arrangement takes the fused kernels it always took.  NotSupportedException remains for two things: more components
+than the input holds samples per pixel, and an arrangement without a component at the maximum sampling factors in both directions
+(DESIGN.md section 5).  A second Encode() on one object is not mirrored.  Nothing touches the device before Encode().
 """
 import numpy as np
 
@@ -64,15 +68,93 @@ class JpegStandardQuantizationTable:
                                      [min(max((x * scale + 50) // 100, 1), 255) for x in quantizationTable.Elements])
 
 
-class JpegHuffmanEncodingTable:
-    """An encoding table object.  The device path knows the four standard ones (JpegStandardHuffmanEncodingTable) by identity."""
+class JpegHuffmanCanonicalCode:
+    """ref: JpegHuffmanCanonicalCode.cs -- one entry of an encoding table."""
 
-    def __init__(self, standard_slot):
-        self._standard_slot = standard_slot  # 0 DC luminance, 1 AC luminance, 2 DC chrominance, 3 AC chrominance
+    def __init__(self, symbol=0, code=0, codeLength=0):
+        self.Symbol, self.Code, self.CodeLength = int(symbol) & 0xFF, int(code) & 0xFFFF, int(codeLength) & 0xFF
+
+
+class JpegHuffmanEncodingTable:
+    """ref: JpegHuffmanEncodingTable.cs:21-37 -- whatever array of codes the caller hands over.  TryWrite (:50-86) writes its last
+    `code count` entries (those with a length), GetCode (:94-100) answers a symbol the table does not hold with entry 0."""
+
+    def __init__(self, codes):
+        if codes is None:
+            raise ArgumentException("Value cannot be null. (Parameter 'codes')")
+        self._codes = list(codes)
+
+    @property
+    def BytesRequired(self):  # :42
+        return (16 + sum(1 for c in self._codes if c.CodeLength != 0)) & 0xFFFF
+
+    def GetCode(self, symbol):  # :94-100 -> (code, codeLength)
+        index = 0
+        for i, c in enumerate(self._codes):
+            if c.CodeLength != 0 and c.Symbol == symbol:
+                index = i & 0xFF
+        c = self._codes[index]
+        return c.Code, c.CodeLength
+
+
+class JpegHuffmanEncodingTableBuilder:
+    """ref: JpegHuffmanEncodingTableBuilder.cs:14-65 -- counts symbols, Build() gives the table the encoder would have built."""
+
+    def __init__(self):
+        self._frequencies = [0] * 256
+
+    def IncrementCodeCount(self, symbol):  # :30-34
+        self._frequencies[symbol] += 1
+
+    def Reset(self):  # :39-42
+        self._frequencies = [0] * 256
+
+    def Build(self, optimal=False):  # :62-65; InvalidOperationException("No symbol is recorded.") without symbols
+        from .optimizer import build_optimal_huffman_table
+
+        _, values, code, length = build_optimal_huffman_table(self._frequencies, optimal)
+        return JpegHuffmanEncodingTable([JpegHuffmanCanonicalCode(v, code[v], length[v]) for v in values.tolist()])
+
+
+# ref: JpegStandardHuffmanEncodingTable.cs:14-83 (ITU-T T.81 Annex K.3): code counts by length, symbols
+_STD_DC_LUMINANCE = ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12)))
+_STD_DC_CHROMINANCE = ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12)))
+_STD_AC_LUMINANCE = ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125), (
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+    0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+    0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+    0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+    0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+    0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa))
+_STD_AC_CHROMINANCE = ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119), (
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+    0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+    0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+    0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+    0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+    0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+    0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa))
+
+
+def _build_canonical_code(bits, values):
+    """ref: JpegStandardHuffmanEncodingTable.BuildCanonicalCode (:85-131)."""
+    lengths = [n + 1 for n, count in enumerate(bits) for _ in range(count)]
+    codes, code, current = [], 0, lengths[0]
+    for i, (symbol, length) in enumerate(zip(values, lengths)):
+        if i > 0:
+            code += 1
+            if length > current:
+                code <<= length - current
+                current = length
+        codes.append(JpegHuffmanCanonicalCode(symbol, code, length))
+    return JpegHuffmanEncodingTable(codes)
 
 
 class JpegStandardHuffmanEncodingTable:  # ref: JpegStandardHuffmanEncodingTable.cs:142-195
-    _tables = [JpegHuffmanEncodingTable(k) for k in range(4)]
+    _tables = [_build_canonical_code(*t) for t in (_STD_DC_LUMINANCE, _STD_AC_LUMINANCE, _STD_DC_CHROMINANCE, _STD_AC_CHROMINANCE)]
 
     @classmethod
     def GetLuminanceDCTable(cls):
@@ -108,7 +190,7 @@ class JpegEncoder:
         self._input = None
         self._output = None
         self._quant = []        # SetQuantizationTable order (:102-126)
-        self._huffman = {}      # (class, identifier) -> table or None (= to be built), in SetHuffmanTable order
+        self._huffman = {}      # (class, identifier & 0xff) -> table or None (= to be built), in SetHuffmanTable order
         self._components = []   # AddComponent order
         self.restart_interval = 0  # extension (see jpgpu_encode_params): 0 = what the reference writes
 
@@ -135,7 +217,10 @@ class JpegEncoder:
         self._quant.append(table)
 
     def SetHuffmanTable(self, isDcTable, identifier, table=None):  # :137-148; no table = built from the image's statistics
-        self._huffman[(0 if isDcTable else 1, int(identifier))] = table
+        key = (0 if isDcTable else 1, int(identifier) & 0xFF)
+        if key in self._huffman:  # AddTable (JpegHuffmanEncodingTableCollection.cs:82-88)
+            raise InvalidOperationException("Operation is not valid due to the current state of the object.")
+        self._huffman[key] = table
 
     def AddComponent(self, componentIndex, quantizationTableIdentifier, huffmanDcTableIdentifier, huffmanAcTableIdentifier, horizontalSubsampling,
                      verticalSubsampling):  # :175-239
@@ -168,44 +253,23 @@ class JpegEncoder:
             raise InvalidOperationException("No component is specified.")
         comps = self._components
         reader = self._input
-        # what the device path encodes: the EncodeAction arrangement
-        if len(comps) not in (1, 3) or reader.ComponentCount != len(comps):
-            raise NotSupportedException("1 or 3 components are supported.")
-        if [c[0] for c in comps] != [1, 2, 3][:len(comps)]:
-            raise NotSupportedException("Component indices 1, 2, 3 in this order are supported.")
-        first = comps[0]
-        if (first[2], first[3]) != (0, 0) or first[1].Identifier != 0:
-            raise NotSupportedException("The first component uses quantization table 0 and Huffman tables 0.")
-        for c in comps[1:]:
-            if (c[2], c[3], c[4], c[5]) != (1, 1, 1, 1) or c[1].Identifier != 1 or c[1].Elements != comps[1][1].Elements:
-                raise NotSupportedException("The other components use quantization table 1, Huffman tables 1 and sampling 1 x 1.")
-        needed = [(0, 0), (1, 0)] + ([(0, 1), (1, 1)] if len(comps) == 3 else [])
-        tables = [self._huffman[k] for k in needed]
-        if all(t is None for t in tables):
-            mode = 2 if self.MostOptimalCoding else 1
-        elif all(t is not None and t._standard_slot == 2 * k[1] + k[0] for t, k in zip(tables, needed)):
-            mode = 0
-        else:
-            raise NotSupportedException("Huffman tables: either the standard tables or all of them built from the image.")
-        # (a single component with tables to be built: the chrominance builders stay empty and BuildTables throws "No symbol is
-        # recorded." -- the device path reports exactly that when the stream is asked for)
-        for c in comps:  # the stream's DQT holds the CURRENT tables, the components quantise with the ones captured at AddComponent
-            if c[1].Elements != next(t for t in self._quant if t.Identifier == c[1].Identifier).Elements:
-                raise NotSupportedException("A quantization table was replaced after AddComponent captured it.")
-        # every table of the collection is written (WriteQuantizationTables :305-335, WriteHuffmanTables :336-352): the device path
-        # writes exactly tables 0 and 1 of each kind, so that is what the collection must hold
-        if sorted(t.Identifier for t in self._quant) != [0, 1] or sorted(self._huffman) != [(0, 0), (0, 1), (1, 0), (1, 1)]:
-            raise NotSupportedException("Quantization tables 0 and 1 and Huffman tables 0 and 1 (DC and AC) are what the stream carries.")
-        if [t.Identifier for t in self._quant] != [0, 1] or list(self._huffman) != [(0, 0), (1, 0), (0, 1), (1, 1)]:
-            raise NotSupportedException("Tables are written in the order they were set: 0 before 1, DC before AC.")
+        if reader.ComponentCount < len(comps):  # (the reference's reader would run past its pixels)
+            raise NotSupportedException("The input holds fewer samples per pixel than components were added.")
+        if len(comps) > 4 or len(self._quant) > 8 or len(self._huffman) > 8:
+            raise NotSupportedException("Up to four components and eight tables of a kind are supported.")
+        from .encoder import describe
+
+        desc = describe(reader.Width, reader.Height,
+                        [(c[0], c[4], c[5], c[1].Identifier, c[2], c[3], c[1].Elements) for c in comps],
+                        [(t.Identifier, t.Elements) for t in self._quant],  # the tables as they are NOW (WriteQuantizationTables :305-330)
+                        [(k[0], k[1], None if t is None else [(c.Symbol, c.Code, c.CodeLength) for c in t._codes]) for k, t in self._huffman.items()],
+                        in_components=reader.ComponentCount, restart_interval=self.restart_interval, most_optimal_coding=self.MostOptimalCoding)
         pixels = reader.buffer[:reader.Width * reader.Height * reader.ComponentCount].reshape(reader.Height, reader.Width, reader.ComponentCount)
         batch = EncodeBatch(self._ctx)
         try:
-            batch.upload([pixels], (first[4], first[5]), 50, rgb=False, optimize_coding=mode, restart_interval=self.restart_interval)
-            batch.set_quantization_table(0, 0, first[1].Elements)
-            batch.set_quantization_table(0, 1, (comps[1][1] if len(comps) == 3 else next(t for t in self._quant if t.Identifier == 1)).Elements)
+            batch.upload_described([pixels], [desc])
             batch.encode()
-            data = batch.output(0)
+            data = batch.output(0)  # (raises what Encode() of this image reports)
         finally:
             batch.close()
         out = self._output

@@ -4,6 +4,11 @@ restatement on the host cores.  Not the headline benchmark (that is bench.py); p
 
     python tools/bench_encode.py [--images 64] [--steps 5] [--width 3840 --height 2160] [--quality 75]
     python tools/bench_encode.py --workload het_8192 [--subsampling 420|444] [--optimize-coding] [--images 8]
+    python tools/bench_encode.py --arrangement cmyk|420-split [--optimize-coding]
+
+--arrangement = a described image (jpgpu_encode_description) that is no EncodeAction arrangement, so the general kernels take it:
+cmyk = four 1 x 1 components (four samples per pixel); 420-split = 2 x 2 / 1 x 1 / 1 x 1 from RGB pixels like the default run, but
+with three quantisation tables and Huffman tables of its own per component -- the headline shape forced onto the general path.
 
 --workload het_8192 = the reference's OWN encoder benchmark (tests/JpegLibrary.Benchmarks/EncoderBenchmark.cs:21-58, 77-135): the
 8192 x 8192 canvas of HETissueSlide.jpg (drawn 2 x 2 into the top-left quarter, the rest black), decoded to Rgba32 pixels, encoded
@@ -34,6 +39,44 @@ def image(w, h, seed):
     return np.clip(np.rint(img), 0, 255).astype(np.uint8)
 
 
+def described_arrangement(jl, name, w, h, quality, optimize_coding):
+    from jpeglibrary_amd.encoder import describe
+
+    sq, sh = jl.JpegStandardQuantizationTable, jl.JpegStandardHuffmanEncodingTable
+    lum = sq.ScaleByQuality(sq.GetLuminanceTable(0, 0), quality).Elements
+    chrom = sq.ScaleByQuality(sq.GetChrominanceTable(0, 1), quality).Elements
+    codes = lambda t: None if optimize_coding else [(c.Symbol, c.Code, c.CodeLength) for c in t._codes]
+    dc_l, ac_l, dc_c, ac_c = (codes(t) for t in (sh.GetLuminanceDCTable(), sh.GetLuminanceACTable(), sh.GetChrominanceDCTable(), sh.GetChrominanceACTable()))
+    if name == "cmyk":
+        comps = [(k + 1, 1, 1, t, t, t, (lum, chrom)[t]) for k, t in enumerate((0, 1, 1, 0))]
+        return describe(w, h, comps, [(0, lum), (1, chrom)], [(0, 0, dc_l), (1, 0, ac_l), (0, 1, dc_c), (1, 1, ac_c)])
+    comps = [(1, 2, 2, 0, 0, 0, lum), (2, 1, 1, 1, 1, 1, chrom), (3, 1, 1, 2, 2, 2, chrom)]
+    return describe(w, h, comps, [(0, lum), (1, chrom), (2, chrom)], [(0, 0, dc_l), (1, 0, ac_l), (0, 1, dc_c), (1, 1, ac_c), (0, 2, dc_c), (1, 2, ac_c)],
+                    input_rgb=1)
+
+
+def bench_arrangement(jl, args):
+    distinct = min(args.images, 16)
+    with ThreadPoolExecutor(16) as ex:
+        base = list(ex.map(lambda s: image(args.width, args.height, s), range(distinct)))
+    if args.arrangement == "cmyk":  # a fourth sample per pixel
+        base = [np.ascontiguousarray(np.concatenate([im, 255 - im[..., :1]], axis=-1)) for im in base]
+    imgs = [base[i % distinct] for i in range(args.images)]
+    desc = described_arrangement(jl, args.arrangement, args.width, args.height, args.quality, args.optimize_coding)
+    desc.restart_interval = args.dri
+    b = jl.EncodeBatch().upload_described(imgs, [desc] * args.images)
+    b.encode()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        b.encode()
+    dt = (time.perf_counter() - t0) / args.steps
+    px = args.images * args.width * args.height
+    print(json.dumps({"metric": f"Mpixels/s encoded (described arrangement {args.arrangement}, general kernels, {'built' if args.optimize_coding else 'given'} tables)",
+                      "value": round(px / dt / 1e6, 1), "unit": "Mpixels/s", "ms_per_step": round(dt * 1e3, 2), "images": args.images,
+                      "arrangement": args.arrangement, "restart_interval": args.dri, "bytes_per_image": len(b.output(0)),
+                      "stage_ms": {k: round(v, 3) for k, v in b.stage_ms().items()}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=64)
@@ -46,8 +89,12 @@ def main():
     ap.add_argument("--subsampling", default="420", choices=["420", "444"])
     ap.add_argument("--optimize-coding", action="store_true", help="Huffman tables from each image's own statistics (EncodeAction's switch)")
     ap.add_argument("--pixels", default=None, choices=["rgb", "rgba"], help="input pixels (default: rgba for het_8192 like the reference's benchmark, rgb otherwise)")
+    ap.add_argument("--arrangement", default=None, choices=["cmyk", "420-split"], help="a described image the general kernels take (see above)")
     args = ap.parse_args()
     import jpeglibrary_amd as jl
+
+    if args.arrangement:
+        return bench_arrangement(jl, args)
     from oracle import pyoracle as po
 
     luma = (2, 2) if args.subsampling == "420" else (1, 1)
