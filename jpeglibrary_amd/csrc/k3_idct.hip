@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "encode_kernels.h"
 #include "kernels_device.h"
+#include "k3_index_math.h"
 
 namespace jpgpu {
 
@@ -375,15 +376,17 @@ __global__ __launch_bounds__(256) void extend_u16_kernel(const uint8_t *__restri
 
 // Output assembly of the INTERLEAVED_U8 format from the LDS sample tile [8 rows][256 blocks][8 B] (phase C).
 // CONV: 0 = the samples as they are (Y,Cb,Cr), 3 / 4 = converted to R,G,B / R,G,B,A bytes (fast layouts only).
+// The fast layouts take the tile's place from wave-uniform state (k3_index_math.h): pos = its first MCU, mpl / line_recip = the MCUs of a
+// line and their reciprocal, row_recip = that of n_mcu, img_h = the frame's lines, img = the image in the output buffer.  Nothing in their
+// task loop divides.
 template <int LAY, int CONV>
-__device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_px, const DevScan &s, uint32_t tile_first, uint32_t n_mcu,
+__device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_px, const DevScan &s, const K3TilePos &pos, uint32_t mpl,
+                                                             uint32_t line_recip, uint32_t row_recip, uint32_t img_h, uint32_t n_mcu,
                                                              uint32_t tid, bool have_block, const DevScanComponent &comp, uint32_t mcu_x,
-                                                             uint32_t mcu_y, uint32_t b, uint8_t *out, const YccRgbFactors &kf, bool reached,
+                                                             uint32_t mcu_y, uint32_t b, uint8_t *img, const YccRgbFactors &kf, bool reached,
                                                              uint32_t mcu, uint32_t fail_block) {
-    const uint32_t W = s.width, H = s.height, C = s.frame_components;
-    uint8_t *img = out + s.out_off;
-
     if (LAY == kLayGeneric) {
+        const uint32_t W = s.width, H = s.height, C = s.frame_components;
         // any component count / sampling: bytewise stores with WriteBlockSlow's replication
         // (ref: ScanDecoder/JpegHuffmanBaselineScanDecoder.cs:238-268) and the sink's clipping (x < W, y < H)
         if (have_block) {
@@ -433,15 +436,24 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
     constexpr uint32_t rows_per_mcu = 8 * max_v;
     constexpr uint32_t vshift = max_v >> 1;
     constexpr uint32_t kbpm = max_h * max_v + 2;
+    constexpr uint32_t bpp = CONV == 4 ? 4 : 3;
     const uint32_t n_tasks = rows_per_mcu * n_mcu;
+    const uint32_t W = mpl * (8 * max_h);  // (whole MCUs: idct_layout_class)
+    // wave-uniform: the first pixel line of the tile's first MCU line; a lane adds a 32-bit offset (a tile spans few lines, or short ones)
+    const uint32_t y0 = pos.gy0 * rows_per_mcu;
+    uint8_t *line0 = img + (uint64_t)y0 * W * bpp;
     for (uint32_t t = tid; t < n_tasks; t += kIdctThreads) {
-        const uint32_t row = t / n_mcu, m = t - row * n_mcu;
-        const uint32_t gm = tile_first + m;
-        const uint32_t gx = gm % s.mcus_per_line, gy = gm / s.mcus_per_line;
-        const uint32_t y = gy * rows_per_mcu + row;
-        if (y >= H) continue;
-        const uint8_t *yrow = sh_px + (row & 7) * kPxRowStride + (m * kbpm + (row >> 3) * max_h) * 8;
-        const uint8_t *crow = sh_px + (row >> vshift) * kPxRowStride + (m * kbpm + max_h * max_v) * 8;
+        const uint32_t row = k3_task_row(t, row_recip), m = t - k3_mul24(row, n_mcu);
+        const uint32_t x = pos.gx0 + m, wraps = k3_line_wraps(x, mpl, line_recip);
+        uint32_t back = k3_mul24(wraps, mpl);
+        asm("" : "+v"(back));  // (kept a 24-bit product: folded into the subtraction it becomes a full 32-bit multiply-add by -mpl)
+        const uint32_t gx = x - back;
+        const uint32_t yl = wraps * rows_per_mcu + row;  // pixel line below line0
+        if (y0 + yl >= img_h) continue;
+        const uint32_t mb = k3_mul24(m, kbpm);
+        const uint8_t *yrow = sh_px + (row & 7) * kPxRowStride + (mb + (row >> 3) * max_h) * 8;
+        const uint8_t *crow = sh_px + (row >> vshift) * kPxRowStride + (mb + max_h * max_v) * 8;
+        uint8_t *dst_px = line0 + (k3_mul24(yl, W * bpp) + k3_mul24(gx, 8 * max_h * bpp));  // (W * bpp < 2^18; the sum is far below 2^32)
         if (max_h == 2 && CONV != 0) {
             const uint4 yv = *reinterpret_cast<const uint4 *>(yrow);  // 16 luma samples (two adjacent blocks)
             const uint4 cv = *reinterpret_cast<const uint4 *>(crow);  // 8 Cb (x,y) + 8 Cr (z,w)
@@ -452,7 +464,7 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
                 px[2 * j] = rgb_pixel(byte_of(j < 4 ? yv.x : yv.z, j < 4 ? yv.y : yv.w, (2 * j) & 7), t);
                 px[2 * j + 1] = rgb_pixel(byte_of(j < 4 ? yv.x : yv.z, j < 4 ? yv.y : yv.w, (2 * j + 1) & 7), t);
             }
-            store_rgb_pixels<16, (CONV == 4 ? 4 : 3)>(img + ((size_t)y * W + gx * 16) * (CONV == 4 ? 4 : 3), px);
+            store_rgb_pixels<16, bpp>(dst_px, px);
         } else if (CONV != 0) {
             const uint2 yv = *reinterpret_cast<const uint2 *>(yrow);
             const uint2 bv = *reinterpret_cast<const uint2 *>(crow);
@@ -460,7 +472,7 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
             uint32_t px[8];
 #pragma unroll
             for (int j = 0; j < 8; j++) px[j] = rgb_pixel(byte_of(yv.x, yv.y, j), chroma_terms(byte_of(bv.x, bv.y, j), byte_of(rv.x, rv.y, j), kf));
-            store_rgb_pixels<8, (CONV == 4 ? 4 : 3)>(img + ((size_t)y * W + gx * 8) * (CONV == 4 ? 4 : 3), px);
+            store_rgb_pixels<8, bpp>(dst_px, px);
         } else if (max_h == 2) {
             const uint4 yv = *reinterpret_cast<const uint4 *>(yrow);  // 16 luma samples (two adjacent blocks)
             const uint4 cv = *reinterpret_cast<const uint4 *>(crow);  // 8 Cb (x,y) + 8 Cr (z,w)
@@ -479,7 +491,7 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
             o2.y = pick4(yv.w, cc3, JPGPU_SEL(0, 4, 5, 1));
             o2.z = pick4(yv.w, cc3, JPGPU_SEL(4, 5, 2, 6));
             o2.w = pick4(yv.w, cc3, JPGPU_SEL(7, 3, 6, 7));
-            uint4 *dst = reinterpret_cast<uint4 *>(img + ((size_t)y * W + gx * 16) * 3);
+            uint4 *dst = reinterpret_cast<uint4 *>(dst_px);
             dst[0] = o0;
             dst[1] = o1;
             dst[2] = o2;
@@ -502,7 +514,7 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
                 o2.x = pick4(yv.y, mid, JPGPU_SEL(4, 5, 2, 6));
                 o2.y = pick4(yv.y, hi, JPGPU_SEL(5, 3, 6, 7));
             }
-            uint2 *dst = reinterpret_cast<uint2 *>(img + ((size_t)y * W + gx * 8) * 3);
+            uint2 *dst = reinterpret_cast<uint2 *>(dst_px);
             dst[0] = o0;
             dst[1] = o1;
             dst[2] = o2;
@@ -530,10 +542,11 @@ __device__ __forceinline__ void idct_output_body(
     const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf) {
     constexpr int CONV = FMT == kFmtRgbU8 ? 3 : (FMT == kFmtRgbaU8 ? 4 : 0);  // fused YCbCr -> RGB(A), fast layouts and gray only
     constexpr bool kSampleBytes = fmt_is_sample_bytes(FMT);  // INTERLEAVED_U8 / _SCALED: one path, two sample-to-byte steps
-    __shared__ __attribute__((aligned(16))) uint8_t sh_all[kIdctThreads * 128 + kIdctThreads * 64 + kMaxScanComponents * 128];
+    __shared__ __attribute__((aligned(16))) uint8_t sh_all[kIdctThreads * 128 + kIdctThreads * 64 + kMaxScanComponents * 128 + (SPLIT && !PRE ? 64 : 0)];
     uint8_t *sh = sh_all;
     uint8_t *sh_px = sh_all + kIdctThreads * 128;
     uint16_t(*sh_q)[64] = reinterpret_cast<uint16_t(*)[64]>(sh_all + kIdctThreads * 128 + kIdctThreads * 64);
+    uint8_t *sh_flag = sh_all + kIdctThreads * 128 + kIdctThreads * 64 + kMaxScanComponents * 128;  // split scans: two sets of eight flag words
 
     const IdctWork wk = work[blockIdx.x];
     const DevScan &s = scans[wk.scan];
@@ -611,10 +624,10 @@ __device__ __forceinline__ void idct_output_body(
     const uint8_t *sp_hi = coef_bytes + split_plane_lines(s.n_intervals, sp_dri, bpm) * 128;
     const uint8_t *sp_flags = reinterpret_cast<const uint8_t *>(reinterpret_cast<const uint64_t *>(coefs) + (s.reserved0 >> kSplitFlagShift));
     // block k * 32 + (t >> 3) of the tile at tile_first: its line in either plane, its restart interval, its flag word.  No branches: the
-    // eight flag loads of a tile are to be issued back to back, and so are its sixteen DMAs
-    auto sp_locate = [&](uint32_t tile_first, uint32_t t, int k, uint32_t &line, uint32_t &iv, uint32_t &word) {
+    // sixteen DMAs of a tile are to be issued back to back
+    auto sp_locate = [&](uint32_t tile_first, uint32_t t, uint32_t k, uint32_t &line, uint32_t &iv, uint32_t &word) {
         const uint32_t i0 = __builtin_amdgcn_readfirstlane(tile_first / sp_dri), m0 = tile_first - i0 * sp_dri;  // (wave-uniform)
-        const uint32_t blk = (uint32_t)k * 32 + (t >> 3);
+        const uint32_t blk = k * 32 + (t >> 3);
         uint32_t q = (blk * sp_rb) >> 16;
         const uint32_t bb = blk - q * bpm;
         const uint32_t last = s.total_mcus - 1 - tile_first;  // lanes behind the scan's last MCU fetch that MCU's blocks: never past the region
@@ -630,8 +643,8 @@ __device__ __forceinline__ void idct_output_body(
     // tiles of whole pairs: every DMA instruction takes 16 lines = 32 slots, the even intervals' slots into staging blocks k * 32 + 0..15 and
     // the odd intervals' into k * 32 + 16..31 -- the blocks of one interval, which neighbouring lanes dequantise, then lie side by side as
     // they do in the dense form, and the staging's swizzle keeps their reads apart.  Staging block k * 32 + (t >> 3): its interval, flag word
-    auto sp_locate_fast = [&](uint32_t i0, uint32_t t, int k, uint32_t &iv, uint32_t &word) {  // i0: the tile's first interval (even)
-        const uint32_t ll = (uint32_t)k * 16 + ((t >> 3) & 15u);                  // line of the tile
+    auto sp_locate_fast = [&](uint32_t i0, uint32_t t, uint32_t k, uint32_t &iv, uint32_t &word) {  // i0: the tile's first interval (even)
+        const uint32_t ll = k * 16 + ((t >> 3) & 15u);                  // line of the tile
         const uint32_t pp = (ll * sp_rw) >> 16;
         iv = i0 + 2 * pp + ((t >> 7) & 1u);
         iv = iv < s.n_intervals ? iv : s.n_intervals - 1;  // (slots behind the scan's last interval: any flag will do, inside the scan's words)
@@ -647,28 +660,38 @@ __device__ __forceinline__ void idct_output_body(
     // (the first interval of a tile of whole pairs, without a division per tile: sp_i0 is that of the tile in the staging)
     const uint32_t sp_ipt = __builtin_amdgcn_readfirstlane(mcus_per_tile / sp_dri);
     uint32_t sp_i0 = __builtin_amdgcn_readfirstlane(first_mcu / sp_dri);
-    // (every lane loads, the lanes of lo pieces too: a byte its neighbours load anyway, and no branch around the loads)
-    auto sp_load_flags = [&](uint32_t tile_first, uint32_t tile_i0, uint32_t (&fb)[8], uint32_t &bit_at) {
+    // One look-up per staging block: lane j looks up block j of the tile's staging (DMA instruction j >> 5, its slot j & 31), fetched as the
+    // byte that holds the block's bit.  Behind the wait a ballot makes 64 bits per wave: the wave's two DMA instructions' 32 slots each, so
+    // dword k of the eight in LDS is DMA instruction k's.  Written in front of a barrier the tile has anyway, read behind it.
+    auto sp_load_flag = [&](uint32_t tile_first, uint32_t tile_i0, uint32_t &fb, uint32_t &bit_at) {
         uint32_t t_ = tid;
         asm volatile("" : "+v"(t_));
-        bit_at = 0;  // three bits per k: where in its byte the block's bit is
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            uint32_t line, iv, word;
-            if (sp_fast) sp_locate_fast(tile_i0, t_, k, iv, word);
-            else sp_locate(tile_first, t_, k, line, iv, word);
-            fb[k] = sp_flags[word * 8 + ((iv >> 3) & 7u)];  // (a scan's flag words are fewer than 2^29)
-            bit_at |= (iv & 7u) << (3 * k);
-        }
+        const uint32_t k = t_ >> 5, t8 = (t_ & 31u) << 3;
+        uint32_t line, iv, word;
+        if (sp_fast) sp_locate_fast(tile_i0, t8, k, iv, word);
+        else sp_locate(tile_first, t8, k, line, iv, word);
+        fb = sp_flags[word * 8 + ((iv >> 3) & 7u)];  // (a scan's flag words are fewer than 2^29)
+        bit_at = iv & 7u;
+    };
+    // The waits of the tile loop are inline assembly, which hipcc's wait-count pass does not read: it would take the flag byte's load -- issued
+    // under one `if`, consumed under another -- for pending still, and guard the next write of its register with a vmcnt(0) of its own, behind
+    // the task loop: a wait for the tile's own output stores (vmcnt retires in order).  The same wait again as an instruction it does read.
+    auto sp_wait_seen = [&]() {
+        if (split) __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0), expcnt untouched (gfx9 encoding)
+    };
+    auto sp_publish_flags = [&](uint32_t fb, uint32_t bit_at, uint32_t set) {
+        asm volatile("" : "+v"(fb));  // (stays behind the wait in front of it)
+        const uint64_t w = __builtin_amdgcn_ballot_w64(((fb >> bit_at) & 1u) != 0);
+        if ((tid & 63u) == 0) *reinterpret_cast<uint2 *>(sh_flag + set * 32 + wave * 8) = uint2{(uint32_t)w, (uint32_t)(w >> 32)};
     };
     // -> bit k: block k * 32 + (tid >> 3) of the tile is flagged (one register from here to the tile's DMA)
-    auto sp_pack_flags = [&](uint32_t (&fb)[8], uint32_t bit_at) {
+    auto sp_read_flags = [&](uint32_t set) {
+        const uint4 lo = *reinterpret_cast<const uint4 *>(sh_flag + set * 32), hi = *reinterpret_cast<const uint4 *>(sh_flag + set * 32 + 16);
+        const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        const uint32_t at = tid >> 3;
         uint32_t bits = 0;
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            asm volatile("" : "+v"(fb[k]));  // (stays behind the wait in front of it)
-            bits |= ((fb[k] >> ((bit_at >> (3 * k)) & 7u)) & 1u) << k;
-        }
+        for (int k = 0; k < 8; k++) bits |= ((w[k] >> at) & 1u) << k;
         return bits;
     };
     auto dma_tile = [&](uint32_t tile_first, uint32_t tile_i0, uint32_t hi_bits) {
@@ -717,18 +740,38 @@ __device__ __forceinline__ void idct_output_body(
 
     uint32_t hi_next = 0;  // split scans: the flag bits of the tile behind the one in the staging
     if (split) {
-        uint32_t fb[8], at;
-        sp_load_flags(first_mcu, sp_i0, fb, at);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        hi_next = sp_pack_flags(fb, at);
+        // the first two tiles' flags, into the two sets of words (one look-up site for both: once per workgroup, not worth its code twice)
+        const uint32_t n_sets = first_mcu + mcus_per_tile < range_end ? 2u : 1u;
+#pragma nounroll
+        for (uint32_t set = 0; set < n_sets; set++) {
+            uint32_t fb, at;
+            sp_load_flag(first_mcu + set * mcus_per_tile, sp_i0 + set * sp_ipt, fb, at);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            sp_wait_seen();
+            sp_publish_flags(fb, at, set);
+        }
+        __syncthreads();
+        const uint32_t hi_first = sp_read_flags(0);
+        if (n_sets == 2) hi_next = sp_read_flags(1);
+        dma_tile(first_mcu, sp_i0, hi_first);
+    } else {
+        dma_tile(first_mcu, sp_i0, 0);
     }
-    dma_tile(first_mcu, sp_i0, hi_next);
-    if (split && first_mcu + mcus_per_tile < range_end) {
-        uint32_t fb[8], at;
-        sp_load_flags(first_mcu + mcus_per_tile, sp_i0 + sp_ipt, fb, at);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        hi_next = sp_pack_flags(fb, at);
-    }
+    // The place of the tile's first MCU in the image and what the output assembly divides by, wave-uniform (k3_index_math.h): one
+    // division each per workgroup, none in the tile loop
+    const uint32_t mpl = __builtin_amdgcn_readfirstlane(s.mcus_per_line);
+    const uint32_t line_recip = __builtin_amdgcn_readfirstlane(k3_line_recip(mpl));
+    const uint32_t img_h = __builtin_amdgcn_readfirstlane((uint32_t)s.height);
+    uint8_t *const img = out + s.out_off;  // (read here: the waits of the tile loop keep a load inside it from being moved out)
+    K3TilePos pos = k3_tile_pos(first_mcu, mpl);
+    pos.gx0 = __builtin_amdgcn_readfirstlane(pos.gx0);
+    pos.gy0 = __builtin_amdgcn_readfirstlane(pos.gy0);
+    K3TilePos pos_step = k3_tile_pos(mcus_per_tile, mpl);
+    pos_step.gx0 = __builtin_amdgcn_readfirstlane(pos_step.gx0);
+    pos_step.gy0 = __builtin_amdgcn_readfirstlane(pos_step.gy0);
+    // (a run's last tile may be shorter: its reciprocal apart)
+    const uint32_t row_recip_full = __builtin_amdgcn_readfirstlane(k3_row_recip(mcus_per_tile));
+    const uint32_t row_recip_last = __builtin_amdgcn_readfirstlane(k3_row_recip((range_end - first_mcu - 1) % mcus_per_tile + 1));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -777,9 +820,9 @@ __device__ __forceinline__ void idct_output_body(
     // phase B2: IDCT entirely in registers
     if (!PRE && have_block) block_idct(f, (int32_t)s.level_shift, px);
     // split scans: the flag bytes of the tile after the next one, fetched behind the transform (f[] is dead) and waited for where the DMA is
-    uint32_t sp_fb[8], sp_at = 0;
+    uint32_t sp_fb = 0, sp_at = 0;
     const bool sp_ahead = split && next_first + mcus_per_tile < range_end;
-    if (sp_ahead) sp_load_flags(next_first + mcus_per_tile, sp_i0 + 2 * sp_ipt, sp_fb, sp_at);
+    if (sp_ahead) sp_load_flag(next_first + mcus_per_tile, sp_i0 + 2 * sp_ipt, sp_fb, sp_at);
     sp_i0 += sp_ipt;
     // (a frame has fewer than 2^32 blocks: 32-bit arithmetic; computed behind the transform, nothing more alive across it)
     const bool reached = mcu < decoded && mcu * bpm + b < fail_block;
@@ -817,9 +860,12 @@ __device__ __forceinline__ void idct_output_body(
     // the MCU's place in the image is only needed from here on: computed behind the transform (an empty asm the compiler may not
     // move across keeps it from being hoisted in front of it), two registers fewer are alive while the 64 + 32 of the
     // transform are -- what four of the sixteen variants spilled (profiles/r03_kernel_resources.txt)
-    uint32_t mcu_late = mcu, b_late = b;
-    asm volatile("" : "+v"(mcu_late), "+v"(b_late));
-    const uint32_t mcu_y = mcu_late / s.mcus_per_line, mcu_x = mcu_late - mcu_y * s.mcus_per_line;
+    uint32_t ml_late = mcu_local, b_late = b;
+    asm volatile("" : "+v"(ml_late), "+v"(b_late));
+    const uint32_t mcu_wraps = k3_line_wraps(pos.gx0 + ml_late, mpl, line_recip);  // (lines below the tile's first MCU line: no division per lane)
+    uint32_t mcu_back = k3_mul24(mcu_wraps, mpl);
+    asm("" : "+v"(mcu_back));  // (kept a 24-bit product, as in the task loop)
+    const uint32_t mcu_y = pos.gy0 + mcu_wraps, mcu_x = pos.gx0 + ml_late - mcu_back;
     const uint32_t ci = s.blk_comp[b_late < kMaxBlocksPerMcu ? b_late : 0];  // (again: one byte from the L1-resident descriptor)
     const DevScanComponent comp = s.comp[ci];
     // (the split form indexes the block's place with the late copy: an address derived from `b` would be held across the whole tile loop)
@@ -898,19 +944,29 @@ __device__ __forceinline__ void idct_output_body(
     // issued (vmcnt retires in order: waiting later would also wait for those stores to drain), then one barrier
     // publishes both the sample tile and the refilled staging.
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
-    if (sp_ahead) hi_next = sp_pack_flags(sp_fb, sp_at);
+    sp_wait_seen();
+    if (sp_ahead) sp_publish_flags(sp_fb, sp_at, 0);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     synced = true;
 
-    interleaved_output_from_tile<LAY, CONV>(sh_px, s, tile_first, n_mcu, tid, writes, comp, mcu_x, mcu_y, b, out, kf, reached, mcu, fail_block);
+    // (tile_mcus clamps at range_end only, so at most the run's LAST tile is short: two reciprocals cover every n_mcu; a tile walk that
+    // shortens another tile needs its own)
+    interleaved_output_from_tile<LAY, CONV>(sh_px, s, pos, mpl, line_recip, n_mcu == mcus_per_tile ? row_recip_full : row_recip_last, img_h, n_mcu, tid,
+                                            writes, comp, mcu_x, mcu_y, b, img, kf, reached, mcu, fail_block);
     }  // interleaved
     }  // u8 formats
 
     if (!synced) {  // planar / gray paths: publish the refilled staging
         asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
-        if (sp_ahead) hi_next = sp_pack_flags(sp_fb, sp_at);
+        sp_wait_seen();
+        if (sp_ahead) sp_publish_flags(sp_fb, sp_at, 0);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     }
+    // (behind the output assembly, off the path from the barrier to the tile's stores; the words are next written behind the next tile's first barrier)
+    if (sp_ahead) hi_next = sp_read_flags(0);
+    k3_tile_advance(pos, pos_step, mpl);
   }  // tile loop
 }
 
