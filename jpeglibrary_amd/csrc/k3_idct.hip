@@ -15,6 +15,7 @@
 #include "encode_kernels.h"
 #include "kernels_device.h"
 #include "k3_index_math.h"
+#include "k3_store_quads.h"
 
 namespace jpgpu {
 
@@ -374,6 +375,51 @@ __global__ __launch_bounds__(256) void extend_u16_kernel(const uint8_t *__restri
     }
 }
 
+// The quad exchange of k3_store_quads.h: d0, d1, d2 = what the lane writes in stores 0, 1, 2, out of the quad's o0, o1, o2.  A selected move is
+// one v_cndmask_b32_dpp -- the lanes of `keep` (vcc) take the second source, the lane the move is aimed at the first, read from lane `src` of
+// its quad -- which takes inline assembly: from the builtins hipcc makes a v_mov_b32_dpp and a v_cndmask_b32 of it.  Two per output dword.
+// In a tile whose quads do not exchange every mask is all lanes: every lane has its vcc bit set and takes the second source, its own
+// register, so d = o and what the DPP source reads never matters.  (bound_ctrl is what makes that hold beside lanes that are switched off,
+// as such a tile has them inside a quad: without it a lane whose DPP source lane is off would not be written at all.)
+struct QuadKeepMasks {
+    uint64_t ne0, ne1, ne2, ne3;  // every lane but lane j of each quad
+};
+__device__ __forceinline__ QuadKeepMasks quad_keep_masks(bool exchange) {
+    return QuadKeepMasks{exchange ? 0xEEEEEEEEEEEEEEEEull : ~0ull, exchange ? 0xDDDDDDDDDDDDDDDDull : ~0ull, exchange ? 0xBBBBBBBBBBBBBBBBull : ~0ull,
+                         exchange ? 0x7777777777777777ull : ~0ull};
+}
+constexpr bool quad_move_is(uint32_t store, uint32_t lane, uint32_t src_lane, uint32_t src_reg) {
+    return k3_quad_move(store, lane).src_lane == src_lane && k3_quad_move(store, lane).src_reg == src_reg;
+}
+static_assert(quad_move_is(0, 0, 0, 0) && quad_move_is(0, 1, 1, 0) && quad_move_is(0, 2, 0, 1) && quad_move_is(0, 3, 0, 2), "store 0 of the assembly below");
+static_assert(quad_move_is(1, 0, 1, 2) && quad_move_is(1, 1, 1, 1) && quad_move_is(1, 2, 2, 1) && quad_move_is(1, 3, 2, 0), "store 1 of the assembly below");
+static_assert(quad_move_is(2, 0, 3, 0) && quad_move_is(2, 1, 3, 1) && quad_move_is(2, 2, 2, 2) && quad_move_is(2, 3, 3, 2), "store 2 of the assembly below");
+#define JPGPU_QSEL(d, from, keep, src) \
+    "v_cndmask_b32_dpp " d ", " from ", " keep ", vcc quad_perm:[" src "," src "," src "," src "] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define JPGPU_QSEL4(d, from, keep, src) \
+    JPGPU_QSEL("%[" d "x]", "%[" from "x]", "%[" keep "x]", src) JPGPU_QSEL("%[" d "y]", "%[" from "y]", "%[" keep "y]", src) \
+    JPGPU_QSEL("%[" d "z]", "%[" from "z]", "%[" keep "z]", src) JPGPU_QSEL("%[" d "w]", "%[" from "w]", "%[" keep "w]", src)
+__device__ __forceinline__ void quad_exchange(const uint4 &o0, const uint4 &o1, const uint4 &o2, const QuadKeepMasks &k, uint4 &d0, uint4 &d1, uint4 &d2) {
+    // (hipcc's hazard recogniser does not read inline assembly: the wait states a DPP read needs behind a vector write of its source, and
+    // behind a vector write of exec, are spent here.  No move reads through DPP what a move before it wrote.)
+    asm volatile("s_nop 4\n\t"
+        "s_mov_b64 vcc, %[ne2]\n\t"                       // lane 2 <- lane 0's o1
+        JPGPU_QSEL4("d0", "o1", "o0", "0")
+        "s_mov_b64 vcc, %[ne0]\n\t"                       // lane 0 <- lane 1's o2; lane 0 <- lane 3's o0
+        JPGPU_QSEL4("d1", "o2", "o1", "1") JPGPU_QSEL4("d2", "o0", "o2", "3")
+        "s_mov_b64 vcc, %[ne3]\n\t"                       // lane 3 <- lane 0's o2; lane 3 <- lane 2's o0
+        JPGPU_QSEL4("d0", "o2", "d0", "0") JPGPU_QSEL4("d1", "o0", "d1", "2")
+        "s_mov_b64 vcc, %[ne1]\n\t"                       // lane 1 <- lane 3's o1
+        JPGPU_QSEL4("d2", "o1", "d2", "3")
+        : [d0x] "=&v"(d0.x), [d0y] "=&v"(d0.y), [d0z] "=&v"(d0.z), [d0w] "=&v"(d0.w), [d1x] "=&v"(d1.x), [d1y] "=&v"(d1.y), [d1z] "=&v"(d1.z),
+          [d1w] "=&v"(d1.w), [d2x] "=&v"(d2.x), [d2y] "=&v"(d2.y), [d2z] "=&v"(d2.z), [d2w] "=&v"(d2.w)
+        : [o0x] "v"(o0.x), [o0y] "v"(o0.y), [o0z] "v"(o0.z), [o0w] "v"(o0.w), [o1x] "v"(o1.x), [o1y] "v"(o1.y), [o1z] "v"(o1.z), [o1w] "v"(o1.w),
+          [o2x] "v"(o2.x), [o2y] "v"(o2.y), [o2z] "v"(o2.z), [o2w] "v"(o2.w), [ne0] "s"(k.ne0), [ne1] "s"(k.ne1), [ne2] "s"(k.ne2), [ne3] "s"(k.ne3)
+        : "vcc");
+}
+#undef JPGPU_QSEL4
+#undef JPGPU_QSEL
+
 // Output assembly of the INTERLEAVED_U8 format from the LDS sample tile [8 rows][256 blocks][8 B] (phase C).
 // CONV: 0 = the samples as they are (Y,Cb,Cr), 3 / 4 = converted to R,G,B / R,G,B,A bytes (fast layouts only).
 // The fast layouts take the tile's place from wave-uniform state (k3_index_math.h): pos = its first MCU, mpl / line_recip = the MCUs of a
@@ -442,6 +488,15 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
     // wave-uniform: the first pixel line of the tile's first MCU line; a lane adds a 32-bit offset (a tile spans few lines, or short ones)
     const uint32_t y0 = pos.gy0 * rows_per_mcu;
     uint8_t *line0 = img + (uint64_t)y0 * W * bpp;
+    // Sample bytes of two-block-wide MCUs: the four lanes of a quad exchange 16-byte pieces so that every store instruction writes whole
+    // 64-byte blocks (k3_store_quads.h).  Wave-uniform per tile; a tile whose quads are not four MCUs side by side -- a clipped range, tiles
+    // that are not line-aligned, a line that is no multiple of four MCUs -- takes the same loop with its own registers at +0 / +16 / +32.
+    constexpr bool kQuads = CONV == 0 && max_h == 2;
+    const bool exchange = kQuads && k3_quad_eligible(n_mcu, mpl, pos.gx0);
+    const QuadKeepMasks keep = quad_keep_masks(exchange);
+    uint32_t q_off[kK3QuadStores];
+#pragma unroll
+    for (uint32_t st = 0; st < kK3QuadStores; st++) q_off[st] = exchange ? k3_quad_lane_offset(k3_quad_offsets_packed(st), tid) : st * kK3QuadPieceBytes;
     for (uint32_t t = tid; t < n_tasks; t += kIdctThreads) {
         const uint32_t row = k3_task_row(t, row_recip), m = t - k3_mul24(row, n_mcu);
         const uint32_t x = pos.gx0 + m, wraps = k3_line_wraps(x, mpl, line_recip);
@@ -453,7 +508,8 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
         const uint32_t mb = k3_mul24(m, kbpm);
         const uint8_t *yrow = sh_px + (row & 7) * kPxRowStride + (mb + (row >> 3) * max_h) * 8;
         const uint8_t *crow = sh_px + (row >> vshift) * kPxRowStride + (mb + max_h * max_v) * 8;
-        uint8_t *dst_px = line0 + (k3_mul24(yl, W * bpp) + k3_mul24(gx, 8 * max_h * bpp));  // (W * bpp < 2^18; the sum is far below 2^32)
+        const uint32_t at = k3_mul24(yl, W * bpp) + k3_mul24(gx, 8 * max_h * bpp);  // (W * bpp < 2^18; the sum is far below 2^32)
+        uint8_t *dst_px = line0 + at;
         if (max_h == 2 && CONV != 0) {
             const uint4 yv = *reinterpret_cast<const uint4 *>(yrow);  // 16 luma samples (two adjacent blocks)
             const uint4 cv = *reinterpret_cast<const uint4 *>(crow);  // 8 Cb (x,y) + 8 Cr (z,w)
@@ -491,10 +547,18 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
             o2.y = pick4(yv.w, cc3, JPGPU_SEL(0, 4, 5, 1));
             o2.z = pick4(yv.w, cc3, JPGPU_SEL(4, 5, 2, 6));
             o2.w = pick4(yv.w, cc3, JPGPU_SEL(7, 3, 6, 7));
-            uint4 *dst = reinterpret_cast<uint4 *>(dst_px);
-            dst[0] = o0;
-            dst[1] = o1;
-            dst[2] = o2;
+            if (kQuads) {
+                uint4 d0, d1, d2;
+                quad_exchange(o0, o1, o2, keep, d0, d1, d2);
+                *reinterpret_cast<uint4 *>(line0 + (at + q_off[0])) = d0;
+                *reinterpret_cast<uint4 *>(line0 + (at + q_off[1])) = d1;
+                *reinterpret_cast<uint4 *>(line0 + (at + q_off[2])) = d2;
+            } else {
+                uint4 *dst = reinterpret_cast<uint4 *>(dst_px);
+                dst[0] = o0;
+                dst[1] = o1;
+                dst[2] = o2;
+            }
         } else {
             const uint2 yv = *reinterpret_cast<const uint2 *>(yrow);
             const uint2 bv = *reinterpret_cast<const uint2 *>(crow);

@@ -30,7 +30,9 @@ __global__ __launch_bounds__(640) void scattered(uint8_t *out, int n_images, int
     }
 }
 
-// reference pattern: every store instruction of a wave covers whole 128-byte lines (what idct_output_kernel does)
+// reference pattern: every store instruction of a wave covers whole 128-byte lines, lane after lane.  (NOT what idct_output_kernel does:
+// its lanes own 48-byte pieces, 48 bytes apart, and only three store instructions together cover whole lines -- K3's real geometry is
+// priced in k3_store_geometry.hip.)
 __global__ __launch_bounds__(256) void coalesced(uint8_t *out, size_t total16) {
     size_t i = (size_t)blockIdx.x * 256 * 8 + threadIdx.x;
     uint4 v = {threadIdx.x, blockIdx.x, 3, 4};
