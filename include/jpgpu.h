@@ -86,7 +86,12 @@ typedef enum jpgpu_format {
      * 1 <= P <= 7 Clamp(sample, 0, 2^P - 1) (signed) spread over 8 bits by ExpandBits
      * (JpegBufferOutputWriterLessThan8Bit.cs:59-60, 67-93).  Any other P: the image fails by itself with
      * JPGPU_ERR_NOT_SUPPORTED / JPGPU_DETAIL_UNSUPPORTED_FRAME. */
-    JPGPU_FMT_INTERLEAVED_U8_SCALED = 6
+    JPGPU_FMT_INTERLEAVED_U8_SCALED = 6,
+    /* RGB_U8's bytes as three tight planes R, G, B of W x H each (pitch = W, no MCU padding): plane c at
+     * out_offset + c * W * H, out_bytes = 3 * W * H -- the uint8[3, H, W] layout tensor code consumes, written by K3 itself.
+     * The same conversion (ConvertYCbCr8ToRgb24 applied to the "O2" samples; 1-component frames with Cb = Cr = 128 give three
+     * equal planes) and the same refusals as RGB_U8.  jpgpu_image_info.plane[0..2] describe the planes. */
+    JPGPU_FMT_RGB_PLANAR_U8 = 7
 } jpgpu_format;
 
 typedef struct jpgpu_ctx jpgpu_ctx;
@@ -172,7 +177,7 @@ typedef struct jpgpu_image_info {
     uint64_t total_blocks;
     uint64_t out_offset, out_bytes;   /* in the batch output buffer */
     uint64_t coef_offset;             /* first block index in the batch coefficient buffer */
-    jpgpu_plane_info plane[4];        /* planar formats only */
+    jpgpu_plane_info plane[4];        /* planar formats only (PLANAR_U8, PLANAR_I16, RGB_PLANAR_U8) */
 } jpgpu_image_info;
 
 typedef struct jpgpu_image_result {

@@ -16,12 +16,22 @@ _lib = _capi.lib
 FMT_INTERLEAVED_U8, FMT_PLANAR_U8, FMT_PLANAR_I16 = _capi.FMT_INTERLEAVED_U8, _capi.FMT_PLANAR_U8, _capi.FMT_PLANAR_I16
 FMT_RGB_U8, FMT_RGBA_U8, FMT_EXTENDED_U16 = _capi.FMT_RGB_U8, _capi.FMT_RGBA_U8, _capi.FMT_EXTENDED_U16
 FMT_INTERLEAVED_U8_SCALED = _capi.FMT_INTERLEAVED_U8_SCALED
+FMT_RGB_PLANAR_U8 = _capi.FMT_RGB_PLANAR_U8
 IDCT_LAYOUT_CLASSES = 6  # JPGPU_IDCT_LAYOUT_CLASSES: generic, YCbCr 1x1 / 2x1 / 2x2, gray, store holding samples
 
 
 class _BorrowedContext:
     def __init__(self, handle):
         self._h = C.c_void_p(handle)
+
+
+class _DeviceView:
+    """What torch.as_tensor wraps without a copy: a span of a batch's output buffer described by __cuda_array_interface__ (version 2).
+    torch holds a reference to this object for as long as any tensor made from it lives, and this object holds the batch."""
+
+    def __init__(self, batch, ptr, shape):
+        self._batch = batch
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "|u1", "data": (ptr, False), "version": 2, "strides": None}
 
 
 class Batch:
@@ -187,8 +197,8 @@ class Batch:
         return p, total.value
 
     def output(self, i):
-        """Downloads image i. INTERLEAVED_U8 / INTERLEAVED_U8_SCALED -> uint8[H,W,C]; RGB_U8 / RGBA_U8 -> uint8[H,W,3|4]; EXTENDED_U16 -> uint16[H,W,4];
-        PLANAR_* -> list of per-component 2-D arrays (padded)."""
+        """Downloads image i. INTERLEAVED_U8 / INTERLEAVED_U8_SCALED -> uint8[H,W,C]; RGB_U8 / RGBA_U8 -> uint8[H,W,3|4]; RGB_PLANAR_U8 -> uint8[3,H,W];
+        EXTENDED_U16 -> uint16[H,W,4]; PLANAR_* -> list of per-component 2-D arrays (padded)."""
         info = self.image_info(i)
         raise_for_status(info.status, _lib.jpgpu_last_error(self.ctx._h))
         raw = np.empty(info.out_bytes, dtype=np.uint8)
@@ -197,6 +207,8 @@ class Batch:
             return raw.reshape(info.height, info.width, info.num_components)
         if self.format in (FMT_RGB_U8, FMT_RGBA_U8):
             return raw.reshape(info.height, info.width, 4 if self.format == FMT_RGBA_U8 else 3)
+        if self.format == FMT_RGB_PLANAR_U8:  # three tight planes R, G, B
+            return raw.reshape(3, info.height, info.width)
         if self.format == FMT_EXTENDED_U16:  # the reference tests' JpegExtendingOutputWriter buffer: ushort x 4 per pixel
             return raw.view(np.uint16).reshape(info.height, info.width, 4)
         dt = np.int16 if self.format == FMT_PLANAR_I16 else np.uint8
@@ -206,6 +218,35 @@ class Batch:
             nbytes = p.pitch * p.height * np.dtype(dt).itemsize
             planes.append(raw[p.offset:p.offset + nbytes].view(dt).reshape(p.height, p.pitch)[:, :p.width])
         return planes
+
+    def _tensor_shape(self, info):
+        if self.format in (FMT_INTERLEAVED_U8, FMT_INTERLEAVED_U8_SCALED):
+            return (info.height, info.width, info.num_components)
+        if self.format in (FMT_RGB_U8, FMT_RGBA_U8):
+            return (info.height, info.width, 4 if self.format == FMT_RGBA_U8 else 3)
+        if self.format == FMT_RGB_PLANAR_U8:
+            return (3, info.height, info.width)
+        raise ValueError("output_tensor: format %d is not one dense uint8 array per image (MCU-padded planes, or uint16 pixels); use output()" % self.format)
+
+    def output_tensor(self, i):
+        """Image i as a torch uint8 tensor on the context's device that ALIASES the batch's output buffer -- no copy, no download:
+        data_ptr() == output_device_ptr()[0] + image_info(i).out_offset.  RGB_PLANAR_U8 -> (3, H, W); INTERLEAVED_U8 / INTERLEAVED_U8_SCALED /
+        RGB_U8 -> (H, W, C); RGBA_U8 -> (H, W, 4).  The MCU-padded PLANAR_* formats and EXTENDED_U16 raise ValueError; an image that failed
+        raises as output() does.  sync() is called first, so the tensor may be used on any torch stream.  The tensor keeps the batch alive.
+        One rule remains: the next upload() on this batch, or an explicit close(), invalidates every tensor made from it."""
+        import torch  # (here: the package imports without torch)
+
+        info = self.image_info(i)
+        raise_for_status(info.status, _lib.jpgpu_last_error(self.ctx._h))
+        shape = self._tensor_shape(info)
+        if not getattr(self, "_owned", True):
+            raise ValueError("output_tensor: a borrowed batch (a MultiDecoder shard) is recycled by its owner; use output()")
+        self.sync()
+        base, total = self.output_device_ptr()
+        if not base or info.out_offset + info.out_bytes > total:
+            raise ValueError("output_tensor: the batch has no output buffer for image %d" % i)
+        view = _DeviceView(self, base + info.out_offset, shape)
+        return torch.as_tensor(view, device=torch.device("cuda", self.ctx.device))
 
     def coefficients(self, i):
         """int16[blocks, 64] zig-zag order, MCU scan order (the buffer between the Huffman and IDCT stages)."""
@@ -252,3 +293,15 @@ def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None):
         outs.append(b.output(i) if b.image_info(i).status == 0 else None)
     b.close()
     return outs, results
+
+
+def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, ctx=None):
+    """One-call helper for torch consumers: returns (tensors, results), tensors[i] = Batch.output_tensor(i) -- uint8[3, H, W] on the
+    context's device by default -- or None for an image that failed.  Nothing is downloaded.  The batch is not closed: its output
+    buffer is the tensors' memory and is freed with the last of them."""
+    b = Batch(ctx).upload(files, fmt).decode().sync()
+    tensors, results = [], []
+    for i in range(len(b)):
+        results.append(b.result(i))
+        tensors.append(b.output_tensor(i) if b.image_info(i).status == 0 and results[-1].status == 0 else None)
+    return tensors, results

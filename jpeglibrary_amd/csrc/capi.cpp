@@ -1249,7 +1249,7 @@ int jpgpu_progressive_output_size(jpgpu_progressive *p, int format, size_t *byte
         const BaselineGeometry &g = p->frame.geo();
         size_t n = 0;
         if (fmt_is_sample_bytes(format)) n = (size_t)fh.samples_per_line * fh.lines * fh.num_components;
-        else if (format == JPGPU_FMT_RGB_U8) n = (size_t)fh.samples_per_line * fh.lines * 3;
+        else if (format == JPGPU_FMT_RGB_U8 || format == JPGPU_FMT_RGB_PLANAR_U8) n = (size_t)fh.samples_per_line * fh.lines * 3;
         else if (format == JPGPU_FMT_RGBA_U8) n = (size_t)fh.samples_per_line * fh.lines * 4;
         else if (format == JPGPU_FMT_EXTENDED_U16) n = (size_t)fh.samples_per_line * fh.lines * 8;
         else if (format == JPGPU_FMT_PLANAR_U8 || format == JPGPU_FMT_PLANAR_I16) {

@@ -39,12 +39,17 @@ struct DevScanComponent {
     uint8_t dc_slot, ac_slot; // index into DevScan::huff_pool (LDS slot)
 };
 
-enum OutputFormat : int32_t { kFmtInterleavedU8 = 0, kFmtPlanarU8 = 1, kFmtPlanarI16 = 2, kFmtRgbU8 = 3, kFmtRgbaU8 = 4, kFmtExtendedU16 = 5, kFmtInterleavedU8Scaled = 6 };
-constexpr int kNumOutputFormats = 7;
+enum OutputFormat : int32_t { kFmtInterleavedU8 = 0, kFmtPlanarU8 = 1, kFmtPlanarI16 = 2, kFmtRgbU8 = 3, kFmtRgbaU8 = 4, kFmtExtendedU16 = 5, kFmtInterleavedU8Scaled = 6, kFmtRgbPlanarU8 = 7 };
+constexpr int kNumOutputFormats = 8;
 // the two formats that hold one byte per sample of every component, out[(y*W+x)*C + c]: the same geometry, layout classes, clearing
 // and canvas rules; they differ in how a sample becomes its byte only (K3)
 constexpr bool fmt_is_sample_bytes(int f) { return f == kFmtInterleavedU8 || f == kFmtInterleavedU8Scaled; }
-constexpr bool fmt_is_interleaved(int f) { return fmt_is_sample_bytes(f) || f == kFmtRgbU8 || f == kFmtRgbaU8; }
+// the formats that hold the callers' converter's pixels (JpegYCbCrToRgbConverter over the INTERLEAVED_U8 samples): the same refusals, scratch
+// image and conversion rules; RGB_PLANAR_U8 holds RGB_U8's bytes as three tight W x H planes
+constexpr bool fmt_is_rgb(int f) { return f == kFmtRgbU8 || f == kFmtRgbaU8 || f == kFmtRgbPlanarU8; }
+// the formats K3 assembles from whole pixels of whole MCUs: they take a layout class (idct_layout_class) -- RGB_PLANAR_U8 too, whose planes
+// are pixel-sized like the interleaved image, not MCU-padded like PLANAR_U8's
+constexpr bool fmt_is_interleaved(int f) { return fmt_is_sample_bytes(f) || fmt_is_rgb(f); }
 constexpr int fmt_bytes_per_pixel_rgb(int f) { return f == kFmtRgbaU8 ? 4 : 3; }
 
 // Fixed-point factors of JpegYCbCrToRgbConverter.Init (ref: apps/JpegDecode/JpegYCbCrToRgbConverter.cs:66-118):

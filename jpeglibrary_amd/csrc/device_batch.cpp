@@ -179,13 +179,15 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
         if (format_ == JPGPU_FMT_INTERLEAVED_U8_SCALED && (fh.precision < 1 || fh.precision > 16))
             throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "INTERLEAVED_U8_SCALED is defined for precisions 1..16 only.", kDetailUnsupportedFrame);
         img.out_bytes = (uint64_t)img.width * img.height * img.num_components;
-    } else if (format_ == JPGPU_FMT_RGB_U8 || format_ == JPGPU_FMT_RGBA_U8) {
+    } else if (fmt_is_rgb(format_)) {
         if (fh.num_components != 1 && fh.num_components != 3)  // apps/JpegDecode/DecodeAction.cs:29-33
             throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "This color space is not supported", kDetailUnsupportedFrame);
         if (fh.precision != 8)
             throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "RGB output is defined for 8-bit precision only (the reference converter assumes 8-bit samples).",
                               kDetailUnsupportedFrame);
         img.out_bytes = (uint64_t)img.width * img.height * (format_ == JPGPU_FMT_RGBA_U8 ? 4 : 3);
+        if (format_ == JPGPU_FMT_RGB_PLANAR_U8)  // three tight planes R, G, B (a 1-component frame too: R = G = B)
+            for (int c = 0; c < 3; c++) img.plane[c] = jpgpu_plane_info{(uint64_t)c * img.width * img.height, img.width, img.height, img.width};
     } else {
         if (fh.num_components > 4)  // jpgpu_plane_info describes four planes; a fifth component would land on plane 0
             throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "The planar output formats describe at most 4 components.", kDetailUnsupportedFrame);

@@ -317,7 +317,7 @@ int DeviceBatch::run_idct() {
     }
     for (const RgbConvert &rc : rgb_convert_) {
         e = launch_ycc_to_rgb(ctx_->stream, (const uint8_t *)d_rgb_scratch_.ptr + rc.out_offset, (uint8_t *)d_out_.ptr + rc.out_offset, rc.pixels,
-                              rc.components, format_ == JPGPU_FMT_RGBA_U8 ? 4 : 3, kf);
+                              rc.components, format_ == JPGPU_FMT_RGBA_U8 ? 4 : (format_ == JPGPU_FMT_RGB_PLANAR_U8 ? 1 : 3), kf);
         if (e != hipSuccess) return hip_fail(e, "ycc_to_rgb_kernel");
     }
     return mark_work();

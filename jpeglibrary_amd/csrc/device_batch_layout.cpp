@@ -501,7 +501,7 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
     const ImagePlan &img = images_[ii];
     const ScanJob &job = jobs_[j];
     DevScan &s = h_scans_[j];
-    const bool rgb_out = format_ == JPGPU_FMT_RGB_U8 || format_ == JPGPU_FMT_RGBA_U8;
+    const bool rgb_out = fmt_is_rgb(format_);
     const uint32_t generic_per_wg = (uint32_t)kIdctBlocksPerWg / s.blocks_per_mcu;
     uint32_t mcus_per_wg = generic_per_wg;
     if (p.sw.tile_align) {
@@ -512,6 +512,7 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
         else if (format_ == JPGPU_FMT_RGB_U8) row_bytes *= 3;
         else if (format_ == JPGPU_FMT_RGBA_U8) row_bytes *= 4;
         else if (format_ == JPGPU_FMT_PLANAR_I16 || format_ == JPGPU_FMT_EXTENDED_U16) row_bytes *= 2;
+        // (RGB_PLANAR_U8 like PLANAR_U8: one byte per pixel in each plane's row)
         for (uint32_t t = mcus_per_wg; t * 4 >= mcus_per_wg * 3 && t > 0; t--)
             if ((t * row_bytes) % 128 == 0) {
                 mcus_per_wg = t;
@@ -757,7 +758,7 @@ void DeviceBatch::plan_output_clears() {
         if (!all && !img.replay_skip) out_clear_.push_back({img.out_offset, img.out_bytes, img.planes_offset, img.planes_bytes});
         // RGB / RGBA = the callers' converter applied to the YCbCr8 buffer (DecodeAction.cs:71-74): an image without any scan
         // leaves that buffer as it was (zero here), and the converter still runs over it
-        if (img.jobs.empty() && !img.replay_skip && (format_ == JPGPU_FMT_RGB_U8 || format_ == JPGPU_FMT_RGBA_U8))
+        if (img.jobs.empty() && !img.replay_skip && fmt_is_rgb(format_))
             rgb_convert_.push_back({(uint32_t)(&img - images_.data()), img.out_offset, (uint64_t)img.width * img.height, img.num_components});
     }
 }

@@ -303,14 +303,36 @@ __device__ __forceinline__ void store_rgb_pixels(uint8_t *dst, const uint32_t (&
     }
 }
 
+// RGB_PLANAR_U8: rgb_pixel's three clamped sums of four pixels, kept apart instead of packed per pixel: one dword of four bytes per plane,
+// gathered with byte permutes (three v_perm_b32 per dword; packing the pixels first and separating them again took sixteen more
+// instructions per four pixels, and the output assembly is bound by what it issues)
+constexpr int kConvPlanar = 1;
+__device__ __forceinline__ uint32_t bytes4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {  // the low bytes of four registers
+    return pick4(pick4(a, b, JPGPU_SEL(0, 4, 0, 4)), pick4(c, d, JPGPU_SEL(0, 4, 0, 4)), JPGPU_SEL(0, 1, 4, 5));
+}
+__device__ __forceinline__ void rgb_planes4(uint32_t y0, uint32_t y1, uint32_t y2, uint32_t y3, const ChromaTerms &t0, const ChromaTerms &t1,
+                                            const ChromaTerms &t2, const ChromaTerms &t3, uint32_t &r, uint32_t &g, uint32_t &b) {
+    r = bytes4(clamp_u8_i32((int32_t)y0 + t0.r), clamp_u8_i32((int32_t)y1 + t1.r), clamp_u8_i32((int32_t)y2 + t2.r), clamp_u8_i32((int32_t)y3 + t3.r));
+    g = bytes4(clamp_u8_i32((int32_t)y0 + t0.g), clamp_u8_i32((int32_t)y1 + t1.g), clamp_u8_i32((int32_t)y2 + t2.g), clamp_u8_i32((int32_t)y3 + t3.g));
+    b = bytes4(clamp_u8_i32((int32_t)y0 + t0.b), clamp_u8_i32((int32_t)y1 + t1.b), clamp_u8_i32((int32_t)y2 + t2.b), clamp_u8_i32((int32_t)y3 + t3.b));
+}
+
 // Stand-alone conversion of an interleaved u8 image (C = 3: Y,Cb,Cr; C = 1: Y with Cb = Cr = 128 like
 // apps/JpegDecode/DecodeAction.cs:57-65) for the layouts the writer kernel has no fused path for.
+// bpp = 3 / 4: interleaved R,G,B(,A) pixels; bpp = 1: RGB_PLANAR_U8, three planes of n_pixels bytes each (a wave writes 64 consecutive
+// bytes of each plane).
 __global__ __launch_bounds__(256) void ycc_to_rgb_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, uint64_t n_pixels, int comps,
                                                          int bpp, YccRgbFactors k) {
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n_pixels; i += (uint64_t)gridDim.x * 256) {
         const uint32_t y = src[i * comps];
         const uint32_t cb = comps == 3 ? src[i * 3 + 1] : 128u, cr = comps == 3 ? src[i * 3 + 2] : 128u;
         const uint32_t px = rgb_pixel(y, chroma_terms(cb, cr, k));
+        if (bpp == 1) {
+            dst[i] = (uint8_t)px;
+            dst[n_pixels + i] = (uint8_t)(px >> 8);
+            dst[2 * n_pixels + i] = (uint8_t)(px >> 16);
+            continue;
+        }
         uint8_t *d = dst + i * bpp;
         d[0] = (uint8_t)px;
         d[1] = (uint8_t)(px >> 8);
@@ -421,7 +443,8 @@ __device__ __forceinline__ void quad_exchange(const uint4 &o0, const uint4 &o1, 
 #undef JPGPU_QSEL
 
 // Output assembly of the INTERLEAVED_U8 format from the LDS sample tile [8 rows][256 blocks][8 B] (phase C).
-// CONV: 0 = the samples as they are (Y,Cb,Cr), 3 / 4 = converted to R,G,B / R,G,B,A bytes (fast layouts only).
+// CONV: 0 = the samples as they are (Y,Cb,Cr), 3 / 4 = converted to R,G,B / R,G,B,A bytes (fast layouts only), kConvPlanar = converted and
+// written as three planes of one byte per pixel (RGB_PLANAR_U8; fast layouts, and kLayGray as a layout of one-block MCUs without chroma).
 // The fast layouts take the tile's place from wave-uniform state (k3_index_math.h): pos = its first MCU, mpl / line_recip = the MCUs of a
 // line and their reciprocal, row_recip = that of n_mcu, img_h = the frame's lines, img = the image in the output buffer.  Nothing in their
 // task loop divides.
@@ -477,17 +500,21 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
     } else {
     // YCbCr fast paths: one task = one pixel row of one MCU (8*max_h pixels); consecutive lanes take consecutive MCUs of
     // the same row, so a wave writes one contiguous run of the output row per store instruction group.
-    constexpr uint32_t max_h = (LAY == kLayYccH1V1) ? 1 : 2;
+    constexpr bool gray = LAY == kLayGray;  // (CONV == kConvPlanar only: the other sinks write a gray block from its own lane)
+    constexpr uint32_t max_h = (LAY == kLayYccH1V1 || (gray && CONV == kConvPlanar)) ? 1 : 2;
     constexpr uint32_t max_v = (LAY == kLayYccH2V2) ? 2 : 1;
     constexpr uint32_t rows_per_mcu = 8 * max_v;
     constexpr uint32_t vshift = max_v >> 1;
-    constexpr uint32_t kbpm = max_h * max_v + 2;
-    constexpr uint32_t bpp = CONV == 4 ? 4 : 3;
+    constexpr uint32_t kbpm = (gray && CONV == kConvPlanar) ? 1 : max_h * max_v + 2;
+    constexpr uint32_t bpp = CONV == 4 ? 4 : (CONV == kConvPlanar ? 1 : 3);  // bytes from a pixel to the next of its row
     const uint32_t n_tasks = rows_per_mcu * n_mcu;
     const uint32_t W = mpl * (8 * max_h);  // (whole MCUs: idct_layout_class)
     // wave-uniform: the first pixel line of the tile's first MCU line; a lane adds a 32-bit offset (a tile spans few lines, or short ones)
     const uint32_t y0 = pos.gy0 * rows_per_mcu;
     uint8_t *line0 = img + (uint64_t)y0 * W * bpp;
+    // RGB_PLANAR_U8: the same line in the G and B planes.  A plane is W * H bytes, which can pass 2^32: wave-uniform 64-bit bases like line0,
+    // and the lane's 32-bit offset `at` serves all three.  (W is a multiple of the store width and so is every plane: idct_layout_class.)
+    uint8_t *line1 = line0 + (uint64_t)W * img_h, *line2 = line1 + (uint64_t)W * img_h;
     // Sample bytes of two-block-wide MCUs: the four lanes of a quad exchange 16-byte pieces so that every store instruction writes whole
     // 64-byte blocks (k3_store_quads.h).  Wave-uniform per tile; a tile whose quads are not four MCUs side by side -- a clipped range, tiles
     // that are not line-aligned, a line that is no multiple of four MCUs -- takes the same loop with its own registers at +0 / +16 / +32.
@@ -510,7 +537,42 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
         const uint8_t *crow = sh_px + (row >> vshift) * kPxRowStride + (mb + max_h * max_v) * 8;
         const uint32_t at = k3_mul24(yl, W * bpp) + k3_mul24(gx, 8 * max_h * bpp);  // (W * bpp < 2^18; the sum is far below 2^32)
         uint8_t *dst_px = line0 + at;
-        if (max_h == 2 && CONV != 0) {
+        if (CONV == kConvPlanar) {
+            // three stores per task, one per plane: consecutive lanes write consecutive 8 / 16 bytes of one plane row
+            if (gray) {
+                const uint2 yv = *reinterpret_cast<const uint2 *>(yrow);  // R = G = B = Y (Cb = Cr = 128 contribute nothing, DecodeAction.cs:57-65)
+                *reinterpret_cast<uint2 *>(line0 + at) = yv;
+                *reinterpret_cast<uint2 *>(line1 + at) = yv;
+                *reinterpret_cast<uint2 *>(line2 + at) = yv;
+            } else if (max_h == 2) {
+                const uint4 yv = *reinterpret_cast<const uint4 *>(yrow);  // 16 luma samples (two adjacent blocks)
+                const uint4 cv = *reinterpret_cast<const uint4 *>(crow);  // 8 Cb (x,y) + 8 Cr (z,w)
+                uint32_t r[4], g[4], bl[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {  // four pixels under two chroma sample pairs
+                    const uint32_t y4 = q == 0 ? yv.x : (q == 1 ? yv.y : (q == 2 ? yv.z : yv.w));
+                    const ChromaTerms t0 = chroma_terms(byte_of(cv.x, cv.y, 2 * q), byte_of(cv.z, cv.w, 2 * q), kf);
+                    const ChromaTerms t1 = chroma_terms(byte_of(cv.x, cv.y, 2 * q + 1), byte_of(cv.z, cv.w, 2 * q + 1), kf);
+                    rgb_planes4(y4 & 0xFFu, (y4 >> 8) & 0xFFu, (y4 >> 16) & 0xFFu, y4 >> 24, t0, t0, t1, t1, r[q], g[q], bl[q]);
+                }
+                *reinterpret_cast<uint4 *>(line0 + at) = uint4{r[0], r[1], r[2], r[3]};
+                *reinterpret_cast<uint4 *>(line1 + at) = uint4{g[0], g[1], g[2], g[3]};
+                *reinterpret_cast<uint4 *>(line2 + at) = uint4{bl[0], bl[1], bl[2], bl[3]};
+            } else {
+                const uint2 yv = *reinterpret_cast<const uint2 *>(yrow);
+                const uint2 bv = *reinterpret_cast<const uint2 *>(crow);
+                const uint2 rv = *reinterpret_cast<const uint2 *>(crow + 8);
+                ChromaTerms t[8];
+#pragma unroll
+                for (int j = 0; j < 8; j++) t[j] = chroma_terms(byte_of(bv.x, bv.y, j), byte_of(rv.x, rv.y, j), kf);
+                uint2 r, g, bl;
+                rgb_planes4(byte_of(yv.x, yv.y, 0), byte_of(yv.x, yv.y, 1), byte_of(yv.x, yv.y, 2), byte_of(yv.x, yv.y, 3), t[0], t[1], t[2], t[3], r.x, g.x, bl.x);
+                rgb_planes4(byte_of(yv.x, yv.y, 4), byte_of(yv.x, yv.y, 5), byte_of(yv.x, yv.y, 6), byte_of(yv.x, yv.y, 7), t[4], t[5], t[6], t[7], r.y, g.y, bl.y);
+                *reinterpret_cast<uint2 *>(line0 + at) = r;
+                *reinterpret_cast<uint2 *>(line1 + at) = g;
+                *reinterpret_cast<uint2 *>(line2 + at) = bl;
+            }
+        } else if (max_h == 2 && CONV != 0) {
             const uint4 yv = *reinterpret_cast<const uint4 *>(yrow);  // 16 luma samples (two adjacent blocks)
             const uint4 cv = *reinterpret_cast<const uint4 *>(crow);  // 8 Cb (x,y) + 8 Cr (z,w)
             uint32_t px[16];
@@ -604,7 +666,7 @@ template <int FMT, int LAY, bool PRE, bool SPLIT = false>
 __device__ __forceinline__ void idct_output_body(
     const int16_t *__restrict__ coefs, const DevScan *__restrict__ scans, const IdctWork *__restrict__ work,
     const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf) {
-    constexpr int CONV = FMT == kFmtRgbU8 ? 3 : (FMT == kFmtRgbaU8 ? 4 : 0);  // fused YCbCr -> RGB(A), fast layouts and gray only
+    constexpr int CONV = FMT == kFmtRgbU8 ? 3 : (FMT == kFmtRgbaU8 ? 4 : (FMT == kFmtRgbPlanarU8 ? kConvPlanar : 0));  // fused YCbCr -> RGB(A), fast layouts and gray only
     constexpr bool kSampleBytes = fmt_is_sample_bytes(FMT);  // INTERLEAVED_U8 / _SCALED: one path, two sample-to-byte steps
     __shared__ __attribute__((aligned(16))) uint8_t sh_all[kIdctThreads * 128 + kIdctThreads * 64 + kMaxScanComponents * 128 + (SPLIT && !PRE ? 64 : 0)];
     uint8_t *sh = sh_all;
@@ -973,7 +1035,7 @@ __device__ __forceinline__ void idct_output_body(
     }
     }
 
-    if (CONV != 0 && LAY == kLayGray) {
+    if (CONV != 0 && CONV != kConvPlanar && LAY == kLayGray) {
         // a single-component image as R = G = B = Y (Cb = Cr = 128 contribute nothing, DecodeAction.cs:57-65)
         if (writes) {
             const uint32_t x0 = (mcu_x * comp.h + s.blk_x[b_out]) * 8, y0 = (mcu_y * comp.v + s.blk_y[b_out]) * 8;
@@ -1169,7 +1231,7 @@ hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *
             else if (format == kFmtPlanarU8) hipLaunchKernelGGL((flush_output_kernel<kFmtPlanarU8>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf);
             else if (format == kFmtInterleavedU8Scaled) hipLaunchKernelGGL((flush_output_kernel<kFmtInterleavedU8Scaled>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf);
             else hipLaunchKernelGGL((flush_output_kernel<kFmtInterleavedU8>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool,
-                                    (format == kFmtRgbU8 || format == kFmtRgbaU8) ? generic_out : out, kf);
+                                    fmt_is_rgb(format) ? generic_out : out, kf);
         } else if (format == kFmtPlanarI16) {
             launch_idct_one<kFmtPlanarI16, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, out);
         } else if (format == kFmtPlanarU8) {
@@ -1189,6 +1251,14 @@ hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *
             case kLayYccH2V1: launch_idct_one<kFmtRgbaU8, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
             case kLayYccH2V2: launch_idct_one<kFmtRgbaU8, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
             case kLayGray: launch_idct_one<kFmtRgbaU8, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
+            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
+            }
+        } else if (format == kFmtRgbPlanarU8) {
+            switch (c) {
+            case kLayYccH1V1: launch_idct_one<kFmtRgbPlanarU8, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
+            case kLayYccH2V1: launch_idct_one<kFmtRgbPlanarU8, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
+            case kLayYccH2V2: launch_idct_one<kFmtRgbPlanarU8, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
+            case kLayGray: launch_idct_one<kFmtRgbPlanarU8, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
             default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
             }
         } else if (format == kFmtInterleavedU8Scaled) {
@@ -1214,7 +1284,7 @@ hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *
     return hipSuccess;
 }
 
-// INTERLEAVED_U8 image (comps = 1 or 3) -> RGB / RGBA, for the layouts without a fused path
+// INTERLEAVED_U8 image (comps = 1 or 3) -> RGB / RGBA (bpp = 3 / 4) or the three planes of RGB_PLANAR_U8 (bpp = 1), for the layouts without a fused path
 hipError_t launch_ycc_to_rgb(hipStream_t stream, const uint8_t *src, uint8_t *dst, uint64_t n_pixels, int comps, int bpp, const YccRgbFactors &kf) {
     if (n_pixels == 0) return hipSuccess;
     const uint64_t want = (n_pixels + 255) / 256;
@@ -1230,7 +1300,10 @@ hipError_t launch_dispose_pass(hipStream_t stream, int16_t *coefs, const Dispose
     return hipGetLastError();
 }
 
-// Layout class of a scan for the INTERLEAVED_U8 / INTERLEAVED_U8_SCALED formats (0 = generic bytewise path).
+// Layout class of a scan for the formats K3 assembles from whole pixels (fmt_is_interleaved; 0 = generic bytewise path).
+// RGB_PLANAR_U8 stores 8 (kLayGray, kLayYccH1V1) or 16 bytes (kLayYccH2V1 / H2V2) per lane and plane, at plane c's base out_off + c * W * H plus
+// y * W + 8 or 16 * (MCU column): with W and out_off multiples of 8 / 16, as the conditions below ask, every plane base and every row start
+// is aligned for that store.
 int idct_layout_class(const DevScan &s) {
     const uint32_t W = s.width;
     if (s.frame_components == 1 && s.scan_components == 1 && s.comp[0].h == 1 && s.comp[0].v == 1 && (W % 8) == 0 && (s.out_off % 8) == 0)

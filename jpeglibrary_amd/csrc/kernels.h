@@ -68,7 +68,7 @@ hipError_t launch_huffman_pool(hipStream_t stream, const uint8_t *data, const De
 hipError_t launch_lut_pool(hipStream_t stream, const DevHuffTable *huff_pool, int n_tables, uint8_t *lut_pool);
 constexpr int kNumIdctLayoutClasses = 6;
 constexpr int kIdctClassStoreHoldsSamples = 5;  // frames whose generic Dispose() pass has run (any format): flush_output_kernel
-// Output layout class of a scan for INTERLEAVED_U8 (0 = generic bytewise path, else a specialised kernel).
+// Output layout class of a scan for the formats K3 assembles from whole pixels (fmt_is_interleaved; 0 = generic bytewise path, else a specialised kernel).
 int idct_layout_class(const DevScan &s);
 // Has K3 a form that reads half-line planes (idct_split_kernel) for this output format and layout class?  Not where the output assembly
 // of the dense form already takes every register the occupancy allows -- the bytewise generic layout of the interleaved formats, RGB_U8
@@ -79,12 +79,13 @@ constexpr bool idct_split_supported(int format, int layout_class) {
     if (layout_class == 0 || layout_class >= kIdctClassStoreHoldsSamples) return false;
     if (format == kFmtRgbU8) return layout_class == 1 || layout_class == 4;
     if (format == kFmtRgbaU8) return layout_class != 3;
+    if (format == kFmtRgbPlanarU8) return true;  // all four fast classes compile at the kernel's launch bounds without spill or scratch (tests/test_planar_rgb_isa_cpu.py)
     if (format == kFmtInterleavedU8Scaled) return layout_class != 4;
     return true;
 }
 // work is sorted by layout class; class_begin[c]..class_begin[c+1] are the workgroups of class c.
 // RGB / RGBA formats: classes with a fused conversion write `out`; the generic class writes INTERLEAVED_U8 samples into
-// `generic_out` (same offsets), to be converted by launch_ycc_to_rgb.
+// `generic_out` (same offsets), to be converted by launch_ycc_to_rgb (bpp = 3 / 4, or 1: the three planes of RGB_PLANAR_U8).
 hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
                        const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status,
                        const DevQuantTable *quant_pool, uint8_t *out, int format, const YccRgbFactors &kf, uint8_t *generic_out,
