@@ -651,6 +651,30 @@ size_t jpgpu_sizeof_encode_description(void);
  * An upload that holds an image the general kernels take counts and emits the bits of ALL its images as two kernels
  * (jpgpu_encoder_emit_passes: no one-pass call); uploads of EncodeAction arrangements alone run as they always did. */
 int jpgpu_encoder_upload_described(jpgpu_encoder *e, const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n);
+/* ---- (4c) pixels that are on the device already: jpgpu_encoder_upload / jpgpu_encoder_upload_described without the copy.
+ * device_pixels[i] is device memory of the context's device that holds image i's pixels; pixel_layouts[i] says how (NULL: all
+ * JPGPU_PIXELS_INTERLEAVED):
+ *   JPGPU_PIXELS_INTERLEAVED  (height, width, in_components) -- what the host entries take (in_components: 4 with input_rgb == 2)
+ *   JPGPU_PIXELS_PLANAR       in_components tight planes of height x width bytes: sample c of pixel (x, y) is byte
+ *                             c * height * width + y * width + x (a torch uint8[C, H, W] tensor, FMT RGB_PLANAR_U8's output)
+ * Rows and planes are tight: no pitch.  Any address will do; images whose address, row length (and plane size) are multiples of
+ * 16 bytes take the widest loads.  An upload is all-host or all-device.  Everything behind the upload
+ * (jpgpu_encoder_set_quantization_table, _encode, _stage_ms, _emit_passes, _download, _download_coefficients, _image_status)
+ * behaves as it does behind a host upload, and the streams are the same bytes.
+ * NOTHING IS COPIED: jpgpu_encoder_encode reads the caller's memory.  It must stay valid and unwritten from this call until
+ * jpgpu_encoder_encode returns (which ends with a synchronisation of the context's stream), for every encode of this upload; and
+ * the work that produced the pixels must be complete -- or ordered before the context's stream -- when this call is made.
+ * JPGPU_ERR_ARGUMENT for the whole call, decided here and before anything is enqueued: a NULL encoder, array or pixel pointer; a
+ * pointer hipPointerGetAttributes does not report as device memory of the context's device (host, pinned host and managed memory
+ * are refused); an image whose width * height * in_components bytes do not lie inside ONE allocation (hipMemGetAddressRange); a
+ * layout other than the two above; input_rgb == 2 with JPGPU_PIXELS_PLANAR (no alpha plane is defined).  A refused upload leaves
+ * the encoder empty. */
+#define JPGPU_PIXELS_INTERLEAVED 0
+#define JPGPU_PIXELS_PLANAR 1
+int jpgpu_encoder_upload_device(jpgpu_encoder *e, const void *const *device_pixels, const jpgpu_encode_params *params,
+                                const int32_t *pixel_layouts, int n);
+int jpgpu_encoder_upload_described_device(jpgpu_encoder *e, const void *const *device_pixels, const jpgpu_encode_description *desc,
+                                          const int32_t *pixel_layouts, int n);
 /* status of image i as known so far (after the upload: JPGPU_OK or the refusal; after the encode also "No symbol is recorded.") */
 int jpgpu_encoder_image_status(const jpgpu_encoder *e, int i);
 /* Host only, no context, no device: the status an encode of `desc` would report, with its message in message[message_cap]

@@ -64,6 +64,7 @@ class EncodeParams(C.Structure):
 
 
 ENC_MAX_COMPONENTS, ENC_MAX_TABLES = 4, 8
+PIXELS_INTERLEAVED, PIXELS_PLANAR = 0, 1
 
 
 class EncodeComponent(C.Structure):
@@ -240,6 +241,8 @@ SYMBOLS = [
     ("jpgpu_sizeof_encode_huffman_table", C.c_size_t, []),
     ("jpgpu_sizeof_encode_description", C.c_size_t, []),
     ("jpgpu_encoder_upload_described", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(EncodeDescription), C.c_int]),
+    ("jpgpu_encoder_upload_device", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(EncodeParams), C.POINTER(C.c_int32), C.c_int]),
+    ("jpgpu_encoder_upload_described_device", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(EncodeDescription), C.POINTER(C.c_int32), C.c_int]),
     ("jpgpu_encoder_image_status", C.c_int, [_P, C.c_int]),
     ("jpgpu_encode_description_header", C.c_int, [C.POINTER(EncodeDescription), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p,
                                                   C.c_size_t]),

@@ -1385,6 +1385,14 @@ size_t jpgpu_sizeof_encode_description(void) { return sizeof(jpgpu_encode_descri
 int jpgpu_encoder_upload_described(jpgpu_encoder *enc, const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n) {
     JPGPU_GUARD(enc, enc->impl.upload_described(pixels, desc, n));
 }
+int jpgpu_encoder_upload_device(jpgpu_encoder *enc, const void *const *device_pixels, const jpgpu_encode_params *params, const int32_t *pixel_layouts,
+                                int n) {
+    JPGPU_GUARD(enc, enc->impl.upload_device(device_pixels, params, pixel_layouts, n));
+}
+int jpgpu_encoder_upload_described_device(jpgpu_encoder *enc, const void *const *device_pixels, const jpgpu_encode_description *desc,
+                                          const int32_t *pixel_layouts, int n) {
+    JPGPU_GUARD(enc, enc->impl.upload_described_device(device_pixels, desc, pixel_layouts, n));
+}
 int jpgpu_encoder_image_status(const jpgpu_encoder *enc, int i) { return enc ? enc->impl.image_status(i) : JPGPU_ERR_ARGUMENT; }
 int jpgpu_encode_description_header(const jpgpu_encode_description *desc, uint8_t *dst, size_t cap, size_t *len, char *message, size_t message_cap) {
     if (message && message_cap) message[0] = 0;

@@ -429,9 +429,82 @@ int EncodeBatch::upload_described(const uint8_t *const *pixels, const jpgpu_enco
     return upload_plans(pixels, plans);
 }
 
+int EncodeBatch::upload_device(const void *const *device_pixels, const jpgpu_encode_params *params, const int32_t *pixel_layouts, int n) {
+    if (n < 0 || (n > 0 && (!device_pixels || !params))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_device: null argument");
+    std::vector<EncPlan> plans((size_t)n);
+    for (int i = 0; i < n; i++) {
+        plans[(size_t)i].legacy = true;
+        plans[(size_t)i].params = params[i];
+    }
+    upload_described_ = false;
+    return upload_plans(reinterpret_cast<const uint8_t *const *>(device_pixels), plans, true, pixel_layouts);
+}
+
+int EncodeBatch::upload_described_device(const void *const *device_pixels, const jpgpu_encode_description *desc, const int32_t *pixel_layouts, int n) {
+    if (n < 0 || (n > 0 && (!device_pixels || !desc))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_described_device: null argument");
+    std::vector<EncPlan> plans((size_t)n);
+    for (int i = 0; i < n; i++) {
+        std::string error;
+        const int rc = resolve_encode_description(desc[i], &plans[(size_t)i], &error);
+        if (rc != JPGPU_OK) return fail(rc, error);
+    }
+    upload_described_ = true;
+    return upload_plans(reinterpret_cast<const uint8_t *const *>(device_pixels), plans, true, pixel_layouts);
+}
+
+// A device upload hands the kernels the caller's addresses: every image must lie, whole, inside ONE allocation of device memory of
+// the context's device -- E1 reads width x height x in_components bytes from it and nothing says so but this check.
+int EncodeBatch::check_device_pixels(const uint8_t *const *pixels) {
+    for (size_t i = 0; i < images_.size(); i++) {
+        const DevEncImage &im = images_[i];
+        if (im.width == 0) continue;  // (a refused arrangement: no kernel reads its pixels)
+        const std::string which = "jpgpu_encoder_upload_device: image " + std::to_string(i);
+        const uint8_t *p = pixels[i];
+        const size_t bytes = (size_t)im.width * im.height * im.in_components;
+        hipPointerAttribute_t attr;
+        memset(&attr, 0, sizeof attr);
+        hipError_t e = hipPointerGetAttributes(&attr, p);
+        if (e != hipSuccess) (void)hipGetLastError();  // (host memory the runtime has never seen: an error of this query, not of the stream)
+        if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx_->device)
+            return fail(JPGPU_ERR_ARGUMENT, which + ": the pixels are not in device memory of the context's device");
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
+        if (e != hipSuccess) (void)hipGetLastError();
+        const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)p;
+        if (e != hipSuccess || at < lo || at - lo > size || bytes > size - (at - lo))
+            return fail(JPGPU_ERR_ARGUMENT, which + ": " + std::to_string(bytes) + " bytes of pixels do not lie inside one device allocation");
+    }
+    return JPGPU_OK;
+}
+
+int EncodeBatch::upload_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans, bool device, const int32_t *pixel_layouts) {
+    const int rc = layout_plans(pixels, plans, device, pixel_layouts);
+    if (rc != JPGPU_OK && device) {  // a refused device upload leaves nothing behind that an encode() could read through
+        images_.clear();
+        status_.clear();
+        n_work_mcu_ = n_work_blk_ = n_work_stat_ = 0;
+        encoded_ = false;
+    }
+    return rc;
+}
+
 // Both uploads: an EncodeAction arrangement (plan.legacy) is laid out as it always was, a described one beside it.
-int EncodeBatch::upload_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans) {
+int EncodeBatch::layout_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans, bool device, const int32_t *pixel_layouts) {
     const int n = (int)plans.size();
+    if (device)
+        for (int i = 0; i < n; i++) {
+            if (!pixels[i]) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_device: null pixel pointer");
+            if (pixel_layouts && pixel_layouts[i] != JPGPU_PIXELS_INTERLEAVED && pixel_layouts[i] != JPGPU_PIXELS_PLANAR)
+                return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_device: a pixel layout is JPGPU_PIXELS_INTERLEAVED (0) or JPGPU_PIXELS_PLANAR (1)");
+        }
+    // where image i's pixels are, and how they are laid out
+    auto place = [&](DevEncImage &im, int i, uint64_t px_off) {
+        im.px_off = device ? (uint64_t)(uintptr_t)pixels[i] : px_off;
+        im.px_planar = (device && pixel_layouts && pixel_layouts[i] == JPGPU_PIXELS_PLANAR) ? 1u : 0u;
+        im.plane_stride = (uint64_t)im.width * im.height;
+    };
+    const char *planar_rgba = "jpgpu_encoder_upload_device: Rgba32 pixels (input_rgb == 2) have no planar layout";
     hipError_t e = hipSetDevice(ctx_->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     images_.assign((size_t)n, DevEncImage());
@@ -461,7 +534,6 @@ int EncodeBatch::upload_plans(const uint8_t *const *pixels, const std::vector<En
             if (pl.status != JPGPU_OK) messages_[i] = pl.message;
             const bool run = pl.status == JPGPU_OK;
             const DevEncLayout &pll = pl.layout[0];
-            im.px_off = px_off;
             im.coef_off = coef_off;
             general_.push_back(i);
             general_plans_.push_back(pl);
@@ -475,6 +547,8 @@ int EncodeBatch::upload_plans(const uint8_t *const *pixels, const std::vector<En
             im.luma_v = pll.max_v;
             im.input_rgb = pl.input_rgb ? 1 : 0;
             im.restart_interval = (uint32_t)pl.restart_interval;
+            place(im, i, px_off);
+            if (im.px_planar && pl.input_rgb == 2) return fail(JPGPU_ERR_ARGUMENT, planar_rgba);
             rgb_ycc_factors(im.r2y);
             if (run) {
                 im.mcus_per_line = (im.width + 8 * im.luma_h - 1) / (8 * im.luma_h);
@@ -517,10 +591,11 @@ int EncodeBatch::upload_plans(const uint8_t *const *pixels, const std::vector<En
         if (p.restart_interval < 0 || p.restart_interval > 65535) return fail(JPGPU_ERR_ARGUMENT, "restart interval out of range (0..65535)");
         DevEncImage &im = images_[i];
         memset(&im, 0, sizeof im);
-        im.px_off = px_off;
         im.coef_off = coef_off;
         im.width = (uint32_t)p.width;
         im.height = (uint32_t)p.height;
+        place(im, i, px_off);
+        if (im.px_planar && p.input_rgb == 2) return fail(JPGPU_ERR_ARGUMENT, planar_rgba);
         im.in_components = p.input_rgb == 2 ? 4u : (uint32_t)p.components;  // (2: Rgba32 pixels, the alpha byte stepped over)
         im.components = (uint32_t)p.components;
         im.luma_h = (uint32_t)p.luma_h;
@@ -618,6 +693,11 @@ int EncodeBatch::upload_plans(const uint8_t *const *pixels, const std::vector<En
                     headers_[i][at] = headers_pre_[i][at] = (uint8_t)im.quant[t][k];
                 }
     }
+    if (device) {  // (every argument check is behind us, nothing has been enqueued)
+        const int rc = check_device_pixels(pixels);
+        if (rc != JPGPU_OK) return rc;
+    }
+    pixels_on_device_ = device;
     total_blocks_ = coef_off;
     n_work_mcu_ = (int)work_mcu.size();
     n_work_blk_ = (int)work_blk.size();
@@ -661,6 +741,7 @@ int EncodeBatch::upload_plans(const uint8_t *const *pixels, const std::vector<En
         {&d_images_, nullptr, 0, (size_t)n * sizeof(DevEncImage) + 256},
     };
     for (const Up &u : ups) {
+        if (device && u.buf == &d_pixels_) continue;  // (a device upload copies nothing: E1 reads the caller's memory)
         e = u.buf->reserve(std::max(u.bytes, u.reserve));
         if (e != hipSuccess) return hip_fail(e, "hipMalloc");
         if (u.bytes) {
@@ -668,7 +749,7 @@ int EncodeBatch::upload_plans(const uint8_t *const *pixels, const std::vector<En
             if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync");
         }
     }
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; i < n && !device; i++) {
         const DevEncImage &im = images_[i];
         if (im.width == 0) continue;  // (a refused arrangement)
         e = hipMemcpyAsync((uint8_t *)d_pixels_.ptr + im.px_off, pixels[i], (size_t)im.width * im.height * im.in_components, hipMemcpyHostToDevice,
@@ -710,7 +791,9 @@ int EncodeBatch::encode() {
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(images)");
     size_t max_record = 0;
     uint32_t fused_shapes = 0;
-    bool any_other = false;
+    bool any_other = false, any_other_planar = false;
+    // (a device upload: DevEncImage.px_off is the caller's address itself)
+    const uint8_t *pixel_base = pixels_on_device_ ? nullptr : (const uint8_t *)d_pixels_.ptr;
     const bool no_fused = !enc_fused_enabled();
     const DevEncLayout *layouts = layouts_.empty() ? nullptr : (const DevEncLayout *)d_layouts_.ptr;  // described images in the upload
     const bool any_plain = layouts_.size() < images_.size();
@@ -719,18 +802,18 @@ int EncodeBatch::encode() {
         max_record = std::max(max_record, enc_sample_bytes_per_mcu(im.luma_h, im.luma_v, im.components));
         const int shape = no_fused ? 0 : enc_image_fused_shape(im);
         if (shape != 0) fused_shapes |= 1u << shape;
-        else any_other = true;
+        else (im.px_planar ? any_other_planar : any_other) = true;
     }
     if (n_work_blk_ == 0) {  // nothing but refused arrangements: no kernel counts anything, the streams are empty
         e = hipMemsetAsync(d_raw_bits_.ptr, 0, (size_t)n * sizeof(uint64_t), ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(bit counts)");
     }
     (void)hipEventRecord(ev_[0], ctx_->stream);
-    e = launch_fdct_quant(ctx_->stream, (const uint8_t *)d_pixels_.ptr, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_mcu_.ptr, n_work_mcu_,
-                          (uint8_t *)d_samples_.ptr, (int16_t *)d_coefs_.ptr, max_record, fused_shapes, any_other);
+    e = launch_fdct_quant(ctx_->stream, pixel_base, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_mcu_.ptr, n_work_mcu_,
+                          (uint8_t *)d_samples_.ptr, (int16_t *)d_coefs_.ptr, max_record, fused_shapes, any_other, any_other_planar);
     if (e != hipSuccess) return hip_fail(e, "fdct_quant_kernel");
     if (layouts) {
-        e = launch_fdct_quant_general(ctx_->stream, (const uint8_t *)d_pixels_.ptr, (const DevEncImage *)d_images_.ptr, layouts,
+        e = launch_fdct_quant_general(ctx_->stream, pixel_base, (const DevEncImage *)d_images_.ptr, layouts,
                                           (const EncWork *)d_work_mcu_.ptr, n_work_mcu_, (int16_t *)d_coefs_.ptr);
         if (e != hipSuccess) return hip_fail(e, "enc_general_fdct_kernel");
     }

@@ -45,6 +45,10 @@ class EncodeBatch {
     ~EncodeBatch();
     int upload(const uint8_t *const *pixels, const jpgpu_encode_params *params, int n);  // SetInputReader x n (+ H2D)
     int upload_described(const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n);
+    // the same from pixels that are in device memory already (jpgpu_encoder_upload_device): nothing is copied, E1 reads the caller's
+    // memory; pixel_layouts[i] = JPGPU_PIXELS_INTERLEAVED / JPGPU_PIXELS_PLANAR (null: all interleaved)
+    int upload_device(const void *const *device_pixels, const jpgpu_encode_params *params, const int32_t *pixel_layouts, int n);
+    int upload_described_device(const void *const *device_pixels, const jpgpu_encode_description *desc, const int32_t *pixel_layouts, int n);
     int set_quantization_table(int i, int identifier, const uint16_t *zigzag64);           // SetQuantizationTable of image i
     int encode();                                                                        // JpegEncoder.Encode() x n
     // device time of the last encode() by stage (HIP events on the context's stream): E1 pixels -> quantised blocks, E2 bit counts
@@ -64,7 +68,10 @@ class EncodeBatch {
 
   private:
     int fail(int status, const std::string &msg);
-    int upload_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans);
+    // device = pixels[] are device addresses laid out as pixel_layouts[] says (null: interleaved); else host memory to copy
+    int upload_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans, bool device = false, const int32_t *pixel_layouts = nullptr);
+    int layout_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans, bool device, const int32_t *pixel_layouts);
+    int check_device_pixels(const uint8_t *const *pixels);
     int hip_fail(hipError_t e, const char *what);
     jpgpu_ctx *ctx_;
     std::vector<DevEncImage> images_;
@@ -81,6 +88,7 @@ class EncodeBatch {
     DevBuffer d_layouts_;
     bool any_general_builder_ = false;
     bool upload_described_ = false;                    // the last upload was jpgpu_encoder_upload_described
+    bool pixels_on_device_ = false;                    // the last upload was a device upload: DevEncImage.px_off is an address, d_pixels_ is not in use
     DevBuffer d_hist_;
     std::vector<uint64_t> out_len_;
     bool encoded_ = false;

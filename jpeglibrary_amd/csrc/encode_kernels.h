@@ -10,7 +10,8 @@ namespace jpgpu {
 // (ref: apps/JpegEncode/EncodeAction.cs:38-63): luma component with sampling (luma_h, luma_v) and table 0, two chroma
 // components 1x1 with table 1 (or a single component).
 struct alignas(16) DevEncImage {
-    uint64_t px_off;    // input pixels, byte offset into the batch's pixel buffer (interleaved, in_components per pixel)
+    uint64_t px_off;    // input pixels: byte offset into the batch's pixel buffer (a host upload), or the caller's device address
+                        // (a device upload: the kernels' `pixels` base is null).  Interleaved, in_components per pixel, unless px_planar
     uint64_t coef_off;  // first block in the coefficient buffer (blocks of 64 int16, zig-zag, MCU order)
     uint64_t raw_off;   // raw (unstuffed) entropy bytes, byte offset into the raw buffer (256-byte aligned)
     uint64_t out_off;   // finished stream, byte offset into the output buffer
@@ -32,6 +33,9 @@ struct alignas(16) DevEncImage {
     uint32_t layout;      // 0: an EncodeAction arrangement (the fields above say it all); k: a described arrangement, DevEncLayout k - 1
     int32_t r2y[8];       // Fix() factors of the RGB -> YCbCr tables (host: rgb_ycc_factors)
     uint16_t quant[2][64];  // zig-zag quantisation tables: luma, chroma
+    uint64_t plane_stride;  // px_planar: bytes from plane to plane (height x width: the planes are tight)
+    uint32_t px_planar;     // 1: in_components planes of height x width bytes (JPGPU_PIXELS_PLANAR); a device upload only
+    uint32_t reserved;
 };
 static_assert(sizeof(DevEncImage) % 16 == 0, "DevEncImage must be a multiple of 16 bytes");
 
@@ -68,12 +72,13 @@ struct EncWork {
     uint32_t first;  // first MCU (kEncMcusPerWg per workgroup) / block (256) / stuffing chunk index
 };
 
-// E1: fdct_fused_kernel<H, V> for the images enc_image_fused_shape() gives a shape (1: 2 x 2, 2: 2 x 1, 3: 1 x 1; fused_shapes:
-// bit s set = the batch holds images of shape s), for the others (shape 0; any_other) E1a (pixel pass into `samples`,
-// enc_sample_stride bytes per MCU) + E1b (FDCT + quantisation)
+// E1: fdct_fused_kernel<H, V, BPP> for the images enc_image_fused_shape() gives a shape (1: 2 x 2, 2: 2 x 1, 3: 1 x 1 from three-byte
+// pixels; 4..6 the same from R,G,B,A pixels; 7..9 the same from three planes; fused_shapes: bit s set = the batch holds images of
+// shape s), for the others (shape 0; any_other) E1a (pixel pass into `samples`, enc_sample_stride bytes per MCU) + E1b (FDCT +
+// quantisation).  `pixels` + DevEncImage.px_off is where an image's pixels are.
 hipError_t launch_fdct_quant(hipStream_t stream, const uint8_t *pixels, const DevEncImage *images, const EncWork *work, int n_work,
                              uint8_t *samples, int16_t *coefs, size_t max_record_bytes,  // (the largest enc_sample_bytes_per_mcu of the batch)
-                             uint32_t fused_shapes, bool any_other);
+                             uint32_t fused_shapes, bool any_other /* interleaved */, bool any_other_planar = false);
 int enc_image_fused_shape(const DevEncImage &im);
 size_t enc_sample_bytes_per_mcu(uint32_t luma_h, uint32_t luma_v, uint32_t components);
 // the described arrangements (DevEncImage.layout != 0): pixels -> quantised blocks in one kernel, one lane per MCU; then the

@@ -82,11 +82,12 @@ __device__ __forceinline__ void block_fdct(float (&f)[64]) {
 }
 
 // The shapes fdct_fused_kernel takes (E1 as one kernel: three components from three-sample pixels, luma 2 x 2, 2 x 1 or
-// 1 x 1 -> instance 1, 2, 3; from R,G,B,A pixels -> 4, 5, 6); every other shape (0) goes through E1a + E1b.
+// 1 x 1 -> instance 1, 2, 3; from R,G,B,A pixels -> 4, 5, 6; from three planes -> 7, 8, 9); every other shape (0) goes through
+// E1a + E1b.
 __host__ __device__ inline int enc_fused_shape(const DevEncImage &im) {
     // (four-byte pixels: R, G, B, A with the alpha ignored -- ConvertRgba32ToYCbCr8, instances 4, 5, 6)
-    if (im.layout != 0 || im.components != 3 || !(im.in_components == 3 || (im.in_components == 4 && im.input_rgb != 0))) return 0;
-    const int wide = im.in_components == 4 ? 3 : 0;
+    if (im.layout != 0 || im.components != 3 || !(im.in_components == 3 || (im.in_components == 4 && im.input_rgb != 0 && im.px_planar == 0))) return 0;
+    const int wide = im.px_planar != 0 ? 6 : (im.in_components == 4 ? 3 : 0);
     if (im.luma_h == 2 && im.luma_v == 2) return 1 + wide;
     if (im.luma_h == 2 && im.luma_v == 1) return 2 + wide;
     if (im.luma_h == 1 && im.luma_v == 1) return 3 + wide;
@@ -97,10 +98,32 @@ __host__ __device__ inline bool enc_fused_ok(const DevEncImage &im) { return enc
 // What the sample reader needs from the image descriptor, held in registers (the descriptor is read once).
 struct EncSrc {
     const uint8_t *px;
+    size_t plane;  // planar: bytes from plane to plane
     uint32_t width, height, comps;
-    bool rgb;
+    bool rgb, planar;
     int32_t k[8];  // Fix() factors of the RGB -> YCbCr tables
 };
+// (planar: enc_gather_kernel passes its instance's constant -- each form takes the images of its layout, and the interleaved form's
+// readers stay the code they were before there was a second layout; enc_general_fdct_kernel passes the image's flag)
+__device__ __forceinline__ EncSrc enc_src(const uint8_t *pixels, const DevEncImage &im, bool planar) {
+    EncSrc src;
+    src.px = pixels + im.px_off;
+    src.plane = (size_t)im.plane_stride;
+    src.width = im.width;
+    src.height = im.height;
+    src.comps = im.in_components;
+    src.rgb = im.input_rgb != 0;
+    src.planar = planar;
+#pragma unroll
+    for (int i = 0; i < 8; i++) src.k[i] = im.r2y[i];
+    return src;
+}
+// Sample c of the input pixel (x, y), which lies inside the image: the one place the per-sample readers learn the pixel layout from
+// (interleaved: comps bytes per pixel; planar: comps tight planes of height x width bytes)
+__device__ __forceinline__ int32_t enc_px(const EncSrc &s, uint32_t c, uint32_t x, uint32_t y) {
+    const size_t at = (size_t)y * s.width + x;
+    return s.planar ? s.px[c * s.plane + at] : s.px[at * s.comps + c];
+}
 
 // apps/JpegEncode/JpegRgbToYCbCrConverter.cs:64-96: the tables are i * Fix(x) (+ rounding / offset terms), so the terms
 // are computed (24-bit multiplies: factors < 2^17, samples < 2^8)
@@ -115,9 +138,8 @@ __device__ __forceinline__ int32_t enc_convert(const EncSrc &s, uint32_t c, int3
 // (ref: apps/JpegEncode/JpegBufferInputReader.cs:27-52).
 __device__ __forceinline__ int32_t enc_sample(const EncSrc &s, uint32_t c, uint32_t x, uint32_t y) {
     if (x >= s.width || y >= s.height) return 0;
-    const uint8_t *p = s.px + ((size_t)y * s.width + x) * s.comps;
-    if (s.comps < 3) return p[0];
-    return enc_convert(s, c, p[0], p[1], p[2]);  // (a fourth byte per pixel is alpha: ConvertRgba32ToYCbCr8 steps over it)
+    if (s.comps < 3) return enc_px(s, 0, x, y);
+    return enc_convert(s, c, enc_px(s, 0, x, y), enc_px(s, 1, x, y), enc_px(s, 2, x, y));  // (a fourth byte per pixel is alpha: ConvertRgba32ToYCbCr8 steps over it)
 }
 
 // Component c of P consecutive pixels of one row, all inside the image, the row address dword aligned.
@@ -321,13 +343,14 @@ __device__ __forceinline__ void enc_gather_rows(const EncSrc &src, uint32_t x0, 
 // go out as one contiguous stretch, 16 bytes per lane.  Written where they are produced they are 8- and 16-byte pieces 512
 // bytes apart, eight waves contributing to every line at eight different times: WRITE_SIZE showed 2.5 GB leaving the L2
 // for the 1.06 GB of samples of 64 images (tools/trace/encoder_pmc.sh).  Not STAGE: records too large for 64 KB of LDS.
-template <bool STAGE>
+template <bool STAGE, bool PLANAR>
 __global__ __launch_bounds__(8 * kEncMcusPerWg) void enc_gather_kernel(const uint8_t *__restrict__ pixels, const DevEncImage *__restrict__ images,
                                                                        const EncWork *__restrict__ work, uint8_t *__restrict__ samples, bool skip_fused) {
     extern __shared__ __attribute__((aligned(16))) uint8_t sh_records[];
     const EncWork wk = work[blockIdx.x];
     const DevEncImage &im = images[wk.image];
     if ((skip_fused && enc_fused_ok(im)) || im.layout != 0) return;  // (uniform: fdct_fused_kernel / enc_general_fdct_kernel takes the image)
+    if ((im.px_planar != 0) != PLANAR) return;                        // (... or this kernel's other form)
     const uint32_t m = threadIdx.x % kEncMcusPerWg, k = threadIdx.x / kEncMcusPerWg;
     const uint32_t mcus_per_line = im.mcus_per_line;
     const uint32_t n_mcus = mcus_per_line * im.mcus_per_column;
@@ -338,17 +361,11 @@ __global__ __launch_bounds__(8 * kEncMcusPerWg) void enc_gather_kernel(const uin
     const uint32_t stride = enc_sample_stride(H, V, components);
     uint8_t *global_base = samples + (uint64_t)im.smp_off_256 * 256u;
     if (active) {
-        EncSrc src;
-        src.px = pixels + im.px_off;
-        src.width = im.width;
-        src.height = im.height;
-        src.comps = im.in_components;
-        src.rgb = im.input_rgb != 0;
-#pragma unroll
-        for (int i = 0; i < 8; i++) src.k[i] = im.r2y[i];
+        const EncSrc src = enc_src(pixels, im, PLANAR);
         const uint32_t mx = mcu % mcus_per_line, my = mcu / mcus_per_line;
         const uint32_t x0 = mx * 8 * H;
-        const bool rows_aligned = ((src.width * src.comps) & 3u) == 0;
+        // (interleaved rows that start on a dword: the image's first one does -- a caller's pointer need not -- and so does every next one)
+        const bool rows_aligned = !src.planar && ((((uint32_t)(uintptr_t)src.px) | (src.width * src.comps)) & 3u) == 0;
         int32_t sum1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sum2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         auto rows = [&](auto *out) {
             if (H == 1) enc_gather_rows<1>(src, x0, my * 8 * V, k, V, components, rows_aligned, out, sum1, sum2);
@@ -493,9 +510,8 @@ __global__ __launch_bounds__(kEncMcusPerWg, JPGPU_E1B_WAVES) void fdct_quant_ker
 //     follows the out-of-grid blocks of the lane's own MCU, and the host names the last of them in the last MCU (dummy_blk).
 __device__ __forceinline__ int32_t enc_general_sample(const EncSrc &s, uint32_t c, uint32_t x, uint32_t y) {
     if (x >= s.width || y >= s.height) return 0;
-    const uint8_t *p = s.px + ((size_t)y * s.width + x) * s.comps;
-    if (!s.rgb) return p[c];
-    return enc_convert(s, c, p[0], p[1], p[2]);
+    if (!s.rgb) return enc_px(s, c, x, y);
+    return enc_convert(s, c, enc_px(s, 0, x, y), enc_px(s, 1, x, y), enc_px(s, 2, x, y));
 }
 
 __global__ __launch_bounds__(kEncMcusPerWg) void enc_general_fdct_kernel(const uint8_t *__restrict__ pixels, const DevEncImage *__restrict__ images,
@@ -511,14 +527,7 @@ __global__ __launch_bounds__(kEncMcusPerWg) void enc_general_fdct_kernel(const u
     const uint32_t mcus_per_line = im.mcus_per_line, n_mcus = mcus_per_line * im.mcus_per_column, bpm = im.bpm;
     const uint32_t mcu = wk.first + threadIdx.x;
     if (mcu >= n_mcus) return;
-    EncSrc src;
-    src.px = pixels + im.px_off;
-    src.width = im.width;
-    src.height = im.height;
-    src.comps = im.in_components;
-    src.rgb = im.input_rgb != 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) src.k[i] = im.r2y[i];
+    const EncSrc src = enc_src(pixels, im, im.px_planar != 0);
     const bool own = L.own_blocks != 0;
     // the block buffer (WriteScanData) / the dummy block (TransformBlocks) as the lane's blocks find it, packed zig-zag int16
     uint4 carry[8];
@@ -659,12 +668,21 @@ struct EfConvert {
     float y[3], b[3], r[3], oy, oc;  // luma: R G B; Cb: R G B; Cr: R G B (the negative ones first in the chain)
 };
 
+// BPP of fdct_fused_kernel: bytes per input pixel (3 or 4), or kEfPlanar = three planes of one byte per pixel.  Either way a
+// lane holds the 8 H pixels of its row in ef_words dwords: interleaved as they lie in memory, planar as 8 H bytes of each plane
+// one after the other.
+constexpr int kEfPlanar = 1;
+__host__ __device__ constexpr int ef_words(int H, int BPP) { return 2 * (BPP == kEfPlanar ? 3 : BPP) * H; }
+
 // One pixel row of an MCU (8 H pixels in w): luma row through pass 1 into the transpose buffer (block tblk, and tblk + 1 for
 // the right half when H = 2), chroma sums into the sums buffer -- pairs summed in the lane when H = 2, the row below (above)
 // added from the neighbour lane when V = 2.  EDGE: pixels outside the image (`inside`: one bit per pixel).
-template <int H, int V, int BPP, bool EDGE>
-__device__ __forceinline__ void ef_row(uint8_t *sh, const uint32_t (&w)[2 * BPP * H], uint32_t inside, const EfConvert &cv, uint32_t mloc, uint32_t gk,
-                                       uint32_t tblk, uint32_t gdy, uint32_t ry) {
+// PAIR (H = 1 only): the luma row is not transformed here but handed back in hold[].x (half = 0) or hold[].y (half = 1): the
+// caller runs pass 1 on the rows of two gather rounds as one packed butterfly.
+template <int H, int V, int BPP, bool EDGE, bool PAIR>
+__device__ __forceinline__ void ef_row(uint8_t *sh, const uint32_t (&w)[ef_words(H, BPP)], uint32_t inside, const EfConvert &cv, uint32_t mloc, uint32_t gk,
+                                       uint32_t tblk, uint32_t gdy, uint32_t ry, EncF2 (&hold)[8], uint32_t half) {
+    static_assert(!PAIR || H == 1, "a lane of an H = 2 instance has its pair in its own row");
     float sb[8], sr[8];
     EncF2 v[8];  // H = 2: left block in .x, right block in .y; H = 1: .x
 #pragma unroll
@@ -672,7 +690,7 @@ __device__ __forceinline__ void ef_row(uint8_t *sh, const uint32_t (&w)[2 * BPP 
         EncF2 c[3];
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
-            const int b0 = BPP * i + ch, b1 = BPP * (i + 1) + ch;
+            const int b0 = BPP == kEfPlanar ? ch * 8 * H + i : BPP * i + ch, b1 = BPP == kEfPlanar ? b0 + 1 : b0 + BPP;
             c[ch] = EncF2{(float)((w[b0 >> 2] >> (8 * (b0 & 3))) & 0xFFu), (float)((w[b1 >> 2] >> (8 * (b1 & 3))) & 0xFFu)};
         }
         const EncF2 yv = ef_floor(__builtin_elementwise_fma(EncF2{cv.y[0], cv.y[0]}, c[0],
@@ -732,6 +750,14 @@ __device__ __forceinline__ void ef_row(uint8_t *sh, const uint32_t (&w)[2 * BPP 
         *reinterpret_cast<uint4 *>(sh + kEfSums + ((mloc * 2u + 1u) * 8u + gk) * 16u) =
             uint4{pack2(sr[0], sr[1]), pack2(sr[2], sr[3]), pack2(sr[4], sr[5]), pack2(sr[6], sr[7])};
     }
+    if constexpr (PAIR) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            if (half) hold[i].y = v[i].x;
+            else hold[i].x = v[i].x;
+        }
+        return;
+    }
     // pass 1 of the lane's luma row (H = 2: left and right block side by side)
     float *t = reinterpret_cast<float *>(sh + kEfT) + tblk * kEfS + (ry & 7u) * 8u;
     if (H == 2) {
@@ -753,7 +779,11 @@ __device__ __forceinline__ void ef_row(uint8_t *sh, const uint32_t (&w)[2 * BPP 
 
 // H x V = the luma sampling factors: 2 x 2 (4:2:0), 2 x 1 (4:2:2), 1 x 1 (4:4:4); enc_fused_shape() names the instance.
 // BPP = bytes per input pixel: 3, or 4 = R, G, B and an alpha byte nobody reads (the reference's EncoderBenchmark hands Rgba32
-// pixels to ConvertRgba32ToYCbCr8, tests/JpegLibrary.Benchmarks/ColorConverters/JpegRgbToYCbCrConverter.cs:95-124).
+// pixels to ConvertRgba32ToYCbCr8, tests/JpegLibrary.Benchmarks/ColorConverters/JpegRgbToYCbCrConverter.cs:95-124), or
+// kEfPlanar = three tight planes (a device upload with JPGPU_PIXELS_PLANAR): the fetch is one wide load per plane instead of BPP
+// of one interleaved row, ef_row picks its bytes from other places, and everything behind the conversion is the same.
+// The pixels are the library's own copy (256-byte aligned) or the caller's memory at whatever address it has: every wide or
+// dword access below is taken only when the image's address, its row pitch and (planar) its plane pitch allow it.
 template <int H, int V, int BPP>
 __global__ __launch_bounds__(64) void fdct_fused_kernel(const uint8_t *__restrict__ pixels, const DevEncImage *__restrict__ images,
                                                         const EncWork *__restrict__ work, int16_t *__restrict__ coefs) {
@@ -762,13 +792,16 @@ __global__ __launch_bounds__(64) void fdct_fused_kernel(const uint8_t *__restric
     constexpr uint32_t kRounds = kEfMcus / kPerRound;
     constexpr uint32_t kNY = H * V, kBpm = kNY + 2;      // luma blocks / blocks per MCU
     constexpr uint32_t kRoundsPerPass = 16 / (kPerRound * kNY);  // gather rounds that fill the transpose buffer's 16 blocks
-    constexpr uint32_t kMcuW = 8 * H, kMcuH = 8 * V, kWords = 2 * BPP * H;
+    constexpr bool kPlanar = BPP == kEfPlanar;
+    constexpr uint32_t kMcuW = 8 * H, kMcuH = 8 * V, kWords = ef_words(H, BPP);
+    constexpr uint32_t kPixel = kPlanar ? 1 : BPP;   // bytes from pixel to pixel in a row
+    constexpr uint32_t kLoads = kPlanar ? 3 : BPP;   // wide loads of a lane's 8 H pixels (8 H bytes each)
     constexpr int kShift = (H == 2 ? 1 : 0) + (V == 2 ? 1 : 0);  // pixels per chroma sample = 1 << kShift
     __shared__ __attribute__((aligned(16))) uint8_t sh[kEfLdsBytes];
     constexpr uint32_t kPerItem = kEncMcusPerWg / kEfMcus;
     const EncWork wk = work[blockIdx.x / kPerItem];
     const DevEncImage &im = images[wk.image];
-    if (enc_fused_shape(im) != (H == 2 ? (V == 2 ? 1 : 2) : 3) + (BPP == 4 ? 3 : 0)) return;  // (another instance, or E1a + E1b, takes the image)
+    if (enc_fused_shape(im) != (H == 2 ? (V == 2 ? 1 : 2) : 3) + (kPlanar ? 6 : (BPP == 4 ? 3 : 0))) return;  // (another instance, or E1a + E1b, takes the image)
     const uint32_t mcus_per_line = im.mcus_per_line;
     const uint32_t n_mcus = mcus_per_line * im.mcus_per_column;
     const uint32_t base = wk.first + (blockIdx.x % kPerItem) * kEfMcus;
@@ -801,8 +834,13 @@ __global__ __launch_bounds__(64) void fdct_fused_kernel(const uint8_t *__restric
         cv.r[0] = 0.0f, cv.r[1] = 0.0f, cv.r[2] = 1.0f;
         cv.oy = -128.0f, cv.oc = 0.0f;
     }
-    const uint32_t row_bytes = width * (uint32_t)BPP;
-    const bool rows4 = (row_bytes & 3u) == 0;
+    const uint32_t row_bytes = width * kPixel;
+    // bytes from one wide load of a lane to its next: the next 8 H bytes of the row, or the same pixels of the next plane
+    const size_t load_step = kPlanar ? (size_t)im.plane_stride : (size_t)(8 * H);
+    // every row of every plane starts at base + a multiple of the row pitch (+ a multiple of the plane pitch): the low bits of the
+    // three together are what a row's address can be trusted to be a multiple of
+    const uint32_t align_bits = (uint32_t)(uintptr_t)px | row_bytes | (kPlanar ? (uint32_t)load_step : 0u);
+    const bool rows4 = (align_bits & 3u) == 0;
 
     // ---- luma: rounds of gather + pass 1; pass 2 and out whenever the transpose buffer holds 16 blocks
     // gather: lane = (MCU of the round, pixel row inside the MCU); chroma row, row of the pair.  (Eight neighbouring lanes put
@@ -811,27 +849,37 @@ __global__ __launch_bounds__(64) void fdct_fused_kernel(const uint8_t *__restric
     // The usual case -- pixel rows of an MCU that start on 16 (8 for H = 1) bytes -- fetches the pixels of round g + 1 while
     // round g goes through pass 2: loads from an address clamped into the image, so that they can be issued before anybody
     // knows whether the round touches the image's edge (then they are dropped and the edge variant reads byte by byte).
-    const bool ahead = (row_bytes & (H == 2 ? 15u : 7u)) == 0 && width >= kMcuW && height >= 1;
+    const bool ahead = (align_bits & (H == 2 ? 15u : 7u)) == 0 && width >= kMcuW && height >= 1;
     uint32_t w[kWords];
 #pragma unroll
     for (uint32_t j = 0; j < kWords; j++) w[j] = 0;
+    // The planar 4:4:4 instance: a lane's row is one block wide, and its rows of two consecutive gather rounds (the same row of MCU m and of
+    // MCU m + kPerRound, blocks kPerRound apart in the transpose buffer) go through pass 1 together, .x and .y of one packed butterfly --
+    // the same IEEE operations on each half, one instruction for both.  (The interleaved H = 1 instances keep their scalar butterfly per
+    // round: host uploads run the code they ran.)
+    constexpr bool kPair = kPlanar && H == 1;
+    static_assert(!kPair || (kRoundsPerPass % 2 == 0 && kNY == 1), "pass 2 must come behind an odd round");
+    EncF2 hold[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) hold[i] = EncF2{0.0f, 0.0f};
     auto fetch = [&](uint32_t g) {
         const uint32_t mloc = g * kPerRound + gm;
         const uint32_t mcu = base + mloc < n_mcus ? base + mloc : n_mcus - 1;
         uint32_t x0 = (mcu % mcus_per_line) * kMcuW, y = (mcu / mcus_per_line) * kMcuH + ry;
         x0 = x0 + kMcuW <= width ? x0 : width - kMcuW;
         y = y < height ? y : height - 1;
-        const uint8_t *rowp = px + ((size_t)y * width + x0) * BPP;
+        // (clamped: x0 + 8 H <= width and y < height, so the 8 H bytes at every step lie inside the image, or inside their plane)
+        const uint8_t *rowp = px + ((size_t)y * width + x0) * kPixel;
         if constexpr (H == 2) {
 #pragma unroll
-            for (int j = 0; j < BPP; j++) {
-                const uint4 t = reinterpret_cast<const uint4 *>(rowp)[j];
+            for (uint32_t j = 0; j < kLoads; j++) {
+                const uint4 t = *reinterpret_cast<const uint4 *>(rowp + j * load_step);
                 w[4 * j] = t.x, w[4 * j + 1] = t.y, w[4 * j + 2] = t.z, w[4 * j + 3] = t.w;
             }
         } else {
 #pragma unroll
-            for (int j = 0; j < BPP; j++) {
-                const uint2 t = reinterpret_cast<const uint2 *>(rowp)[j];
+            for (uint32_t j = 0; j < kLoads; j++) {
+                const uint2 t = *reinterpret_cast<const uint2 *>(rowp + j * load_step);
                 w[2 * j] = t.x, w[2 * j + 1] = t.y;
             }
         }
@@ -846,15 +894,20 @@ __global__ __launch_bounds__(64) void fdct_fused_kernel(const uint8_t *__restric
             const uint32_t tblk = (g % kRoundsPerPass) * (kPerRound * kNY) + gm * kNY + (V == 2 ? (ry >> 3) * H : 0u);
             const bool whole = x0 + kMcuW <= width && y < height;
             if (ahead && __builtin_amdgcn_ballot_w64(!whole) == 0) {
-                ef_row<H, V, BPP, false>(sh, w, 0xFFFFu, cv, mloc, gk, tblk, gdy, ry);
+                ef_row<H, V, BPP, false, kPair>(sh, w, 0xFFFFu, cv, mloc, gk, tblk, gdy, ry, hold, g & 1u);
             } else {
                 // the edge of the image (outside it the reader leaves zeros, JpegBufferInputReader.cs:27-52), or rows that do
                 // not start where the wide loads want them
-                const uint8_t *rowp = px + ((size_t)y * width + x0) * BPP;
+                const uint8_t *rowp = px + ((size_t)y * width + x0) * kPixel;
                 uint32_t we[kWords];
                 uint32_t inside = 0xFFFFu;  // the row's pixels that lie inside the image
                 if (whole && rows4) {
-                    __builtin_memcpy(we, __builtin_assume_aligned(rowp, 4), kWords * 4);
+                    if constexpr (kPlanar) {
+#pragma unroll
+                        for (uint32_t c = 0; c < 3; c++) __builtin_memcpy(we + c * 2 * H, __builtin_assume_aligned(rowp + c * load_step, 4), 8 * H);
+                    } else {
+                        __builtin_memcpy(we, __builtin_assume_aligned(rowp, 4), kWords * 4);
+                    }
                 } else {
 #pragma unroll
                     for (uint32_t j = 0; j < kWords; j++) we[j] = 0;
@@ -862,15 +915,37 @@ __global__ __launch_bounds__(64) void fdct_fused_kernel(const uint8_t *__restric
                     if (y < height) {
                         const uint32_t np = x0 >= width ? 0u : (width - x0 < kMcuW ? width - x0 : kMcuW), nb = np * (uint32_t)BPP;
                         inside = (1u << np) - 1u;
-                        for (uint32_t j = 0; j < nb; j++) {
-                            const uint32_t bv = (uint32_t)rowp[j] << (8u * (j & 3u));
+                        if constexpr (kPlanar) {
 #pragma unroll
-                            for (uint32_t q = 0; q < kWords; q++)
-                                if ((j >> 2) == q) we[q] |= bv;
+                            for (uint32_t c = 0; c < 3; c++)
+                                for (uint32_t j = 0; j < np; j++) {
+                                    const uint32_t bv = (uint32_t)rowp[c * load_step + j] << (8u * (j & 3u));
+#pragma unroll
+                                    for (uint32_t q = 0; q < 2 * H; q++)
+                                        if ((j >> 2) == q) we[c * 2 * H + q] |= bv;
+                                }
+                        } else {
+                            for (uint32_t j = 0; j < nb; j++) {
+                                const uint32_t bv = (uint32_t)rowp[j] << (8u * (j & 3u));
+#pragma unroll
+                                for (uint32_t q = 0; q < kWords; q++)
+                                    if ((j >> 2) == q) we[q] |= bv;
+                            }
                         }
                     }
                 }
-                ef_row<H, V, BPP, true>(sh, we, inside, cv, mloc, gk, tblk, gdy, ry);
+                ef_row<H, V, BPP, true, kPair>(sh, we, inside, cv, mloc, gk, tblk, gdy, ry, hold, g & 1u);
+            }
+            if constexpr (kPair) {
+                if (g & 1u) {  // pass 1 of this round's row (.y, block tblk) and the round before's (.x, block tblk - kPerRound)
+                    fdct8(hold[0], hold[1], hold[2], hold[3], hold[4], hold[5], hold[6], hold[7]);
+                    float *t = reinterpret_cast<float *>(sh + kEfT) + (tblk - kPerRound) * kEfS + (ry & 7u) * 8u;
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+                        t[i] = hold[i].x;
+                        t[kPerRound * kEfS + i] = hold[i].y;
+                    }
+                }
             }
             if (ahead && g + 1 < kRounds) fetch(g + 1);
         }
@@ -1662,7 +1737,7 @@ size_t enc_sample_bytes_per_mcu(uint32_t luma_h, uint32_t luma_v, uint32_t compo
 int enc_image_fused_shape(const DevEncImage &im) { return enc_fused_shape(im); }
 
 hipError_t launch_fdct_quant(hipStream_t stream, const uint8_t *pixels, const DevEncImage *images, const EncWork *work, int n_work,
-                             uint8_t *samples, int16_t *coefs, size_t max_record_bytes, uint32_t fused_shapes, bool any_other) {
+                             uint8_t *samples, int16_t *coefs, size_t max_record_bytes, uint32_t fused_shapes, bool any_other, bool any_other_planar) {
     if (n_work <= 0) return hipSuccess;
     const dim3 grid(n_work * (kEncMcusPerWg / kEfMcus));
     if (fused_shapes & 2u) hipLaunchKernelGGL((fdct_fused_kernel<2, 2, 3>), grid, dim3(64), 0, stream, pixels, images, work, coefs);
@@ -1671,12 +1746,20 @@ hipError_t launch_fdct_quant(hipStream_t stream, const uint8_t *pixels, const De
     if (fused_shapes & 16u) hipLaunchKernelGGL((fdct_fused_kernel<2, 2, 4>), grid, dim3(64), 0, stream, pixels, images, work, coefs);
     if (fused_shapes & 32u) hipLaunchKernelGGL((fdct_fused_kernel<2, 1, 4>), grid, dim3(64), 0, stream, pixels, images, work, coefs);
     if (fused_shapes & 64u) hipLaunchKernelGGL((fdct_fused_kernel<1, 1, 4>), grid, dim3(64), 0, stream, pixels, images, work, coefs);
-    if (any_other) {
+    if (fused_shapes & 128u) hipLaunchKernelGGL((fdct_fused_kernel<2, 2, kEfPlanar>), grid, dim3(64), 0, stream, pixels, images, work, coefs);
+    if (fused_shapes & 256u) hipLaunchKernelGGL((fdct_fused_kernel<2, 1, kEfPlanar>), grid, dim3(64), 0, stream, pixels, images, work, coefs);
+    if (fused_shapes & 512u) hipLaunchKernelGGL((fdct_fused_kernel<1, 1, kEfPlanar>), grid, dim3(64), 0, stream, pixels, images, work, coefs);
+    if (any_other || any_other_planar) {
         const bool skip = fused_shapes != 0;
         const size_t lds = max_record_bytes * (size_t)kEncMcusPerWg;
-        if (lds <= 64 * 1024)
-            hipLaunchKernelGGL(enc_gather_kernel<true>, dim3(n_work), dim3(8 * kEncMcusPerWg), lds, stream, pixels, images, work, samples, skip);
-        else hipLaunchKernelGGL(enc_gather_kernel<false>, dim3(n_work), dim3(8 * kEncMcusPerWg), 0, stream, pixels, images, work, samples, skip);
+        const dim3 gather(8 * kEncMcusPerWg);
+        if (lds <= 64 * 1024) {
+            if (any_other) hipLaunchKernelGGL((enc_gather_kernel<true, false>), dim3(n_work), gather, lds, stream, pixels, images, work, samples, skip);
+            if (any_other_planar) hipLaunchKernelGGL((enc_gather_kernel<true, true>), dim3(n_work), gather, lds, stream, pixels, images, work, samples, skip);
+        } else {
+            if (any_other) hipLaunchKernelGGL((enc_gather_kernel<false, false>), dim3(n_work), gather, 0, stream, pixels, images, work, samples, skip);
+            if (any_other_planar) hipLaunchKernelGGL((enc_gather_kernel<false, true>), dim3(n_work), gather, 0, stream, pixels, images, work, samples, skip);
+        }
         hipLaunchKernelGGL(fdct_quant_kernel, dim3(n_work), dim3(kEncMcusPerWg), 0, stream, samples, images, work, coefs, skip);
     }
     return hipGetLastError();

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
+from .batch import _DeviceView
 from .context import Context, default_context
 from .errors import raise_for_status
 
@@ -60,6 +61,45 @@ def description_header(desc):
     return rc, msg.value.decode("utf-8", "replace"), buf.raw[:n.value] if rc == 0 else b""
 
 
+def _blocks_of(w, h, luma, components):
+    return (-(-w // (8 * luma[0]))) * (-(-h // (8 * luma[1]))) * (luma[0] * luma[1] + (2 if components == 3 else 0))
+
+
+def _tensor_pixels(tensors, layout, device, shape_ok):
+    """The checks of upload_tensors / upload_described_tensors, before any library call: [(data_ptr, width, height, channels)] and the
+    C ABI's pixel layout.  shape_ok(i, width, height, channels) says whether image i may have that size and that many samples per pixel."""
+    import torch  # (here: the package imports without torch)
+
+    layout = "chw" if layout is None else layout
+    if layout not in ("chw", "hwc"):
+        raise ValueError("layout is 'chw' (planes, the default) or 'hwc' (interleaved pixels), not %r" % (layout,))
+    out = []
+    for i, t in enumerate(tensors):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("image %d: a torch tensor is expected, not %s (numpy arrays go to upload())" % (i, type(t).__name__))
+        if t.dtype != torch.uint8:
+            raise ValueError("image %d: a uint8 tensor is expected, not %s" % (i, t.dtype))
+        if layout == "chw":
+            if t.dim() != 3:
+                raise ValueError("image %d: layout 'chw' takes (C, H, W) tensors, not %s" % (i, tuple(t.shape)))
+            c, h, w = t.shape
+        else:
+            if t.dim() not in (2, 3):
+                raise ValueError("image %d: layout 'hwc' takes (H, W, C) or (H, W) tensors, not %s" % (i, tuple(t.shape)))
+            h, w = t.shape[:2]
+            c = t.shape[2] if t.dim() == 3 else 1
+        if not shape_ok(i, w, h, c):
+            raise ValueError("image %d: %d x %d pixels, %d samples per pixel in a %s tensor of layout '%s'" % (i, w, h, c, tuple(t.shape), layout))
+        if h < 1 or w < 1:
+            raise ValueError("image %d: an empty tensor %s" % (i, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("image %d: the tensor is not contiguous (strides %s): call .contiguous() -- nothing is copied here" % (i, tuple(t.stride())))
+        if not t.is_cuda or t.device.index != device:
+            raise ValueError("image %d: the tensor is on %s, not on the context's device cuda:%d" % (i, t.device, device))
+        out.append((t.data_ptr(), int(w), int(h), int(c)))
+    return out, (_capi.PIXELS_PLANAR if layout == "chw" else _capi.PIXELS_INTERLEAVED)
+
+
 class EncodeBatch:
     def __init__(self, ctx: Context = None):
         self.ctx = ctx or default_context()
@@ -67,6 +107,7 @@ class EncodeBatch:
         raise_for_status(_lib.jpgpu_encoder_create(self.ctx._h, C.byref(self._h)), b"jpgpu_encoder_create failed")
         self._n = 0
         self._blocks = []
+        self._keep = None
 
     def _check(self, rc):
         raise_for_status(rc, _lib.jpgpu_last_error(self.ctx._h))
@@ -96,9 +137,68 @@ class EncodeBatch:
             params[i] = _capi.EncodeParams(w, h, c, luma[0], luma[1], quality, mode, int(optimize_coding), int(restart_interval))
             mcus = (-(-w // (8 * luma[0]))) * (-(-h // (8 * luma[1])))
             self._blocks.append(mcus * (luma[0] * luma[1] + (2 if c == 3 else 0)))
+        self._keep = None
         self._check(_lib.jpgpu_encoder_upload(self._h, ptrs, params, n))
         self._n = n
         return self
+
+    def _device_upload(self, entry, tensors, pixels, pixel_layout, records):
+        import torch
+
+        n = len(pixels)
+        ptrs = (C.c_void_p * n)(*[p[0] for p in pixels])
+        layouts = (C.c_int32 * n)(*([pixel_layout] * n))
+        # the library reads the tensors on its own stream: what torch has queued on its current one must have happened
+        torch.cuda.current_stream(self.ctx.device).synchronize()
+        self._n = 0
+        self._keep = list(tensors)  # the encoder reads this memory in encode(): held until the next upload or close()
+        self._check(entry(self._h, ptrs, records, layouts, n))
+        self._n = n
+        return self
+
+    def upload_tensors(self, tensors, luma=(2, 2), quality=75, rgb=False, optimize_coding=False, restart_interval=0, layout=None):
+        """upload() for pixels that are on the device already: torch uint8 tensors on the context's device, read where they are --
+        no download, no permute, no copy (jpgpu_encoder_upload_device).  layout='chw' (the default: what decode_to_tensors returns) takes
+        (3, H, W) or (1, H, W); layout='hwc' takes (H, W, 3), (H, W), (H, W, 1) and, with rgb=True, (H, W, 4) = Rgba32.  The other arguments
+        are upload()'s.  ValueError, before the library is called, for a tensor that is not uint8, has another rank or channel count, is
+        not contiguous (call .contiguous(): nothing is copied silently) or is not on the context's device.
+        torch's current stream on that device is synchronised first, so whatever produced the tensors has finished; the batch keeps
+        references to the tensors until the next upload or close(), and they must not be written before encode() has returned."""
+        tensors = list(tensors)
+        hwc = (layout or "chw") == "hwc"
+        pixels, pixel_layout = _tensor_pixels(tensors, layout, self.ctx.device, lambda i, w, h, c: c in (1, 3) or (c == 4 and hwc and rgb))
+        params = (_capi.EncodeParams * len(pixels))()
+        self._blocks = []
+        for i, (_, w, h, c) in enumerate(pixels):
+            mode = 1 if rgb else 0
+            if c == 4:
+                c, mode = 3, 2
+            params[i] = _capi.EncodeParams(w, h, c, luma[0], luma[1], quality, mode, int(optimize_coding), int(restart_interval))
+            self._blocks.append(_blocks_of(w, h, luma, c))
+        return self._device_upload(_lib.jpgpu_encoder_upload_device, tensors, pixels, pixel_layout, params)
+
+    def upload_described_tensors(self, tensors, descriptions, layout=None):
+        """upload_described() for torch uint8 tensors on the context's device (jpgpu_encoder_upload_described_device): layout='chw'
+        (the default) takes (in_components, H, W), e.g. CMYK as (4, H, W); layout='hwc' takes (H, W, in_components), or (H, W) for one.
+        Checks, synchronisation and lifetime as in upload_tensors."""
+        tensors = list(tensors)
+        if len(descriptions) != len(tensors):
+            raise ValueError("one description per image")
+        descs = (_capi.EncodeDescription * len(tensors))(*descriptions)
+        chw = (layout or "chw") == "chw"
+
+        def as_described(i, w, h, c):
+            d = descs[i]
+            return (w, h, c) == (d.width, d.height, d.in_components) and not (chw and d.input_rgb == 2)
+
+        pixels, pixel_layout = _tensor_pixels(tensors, layout, self.ctx.device, as_described)
+        self._blocks = []
+        for i in range(len(pixels)):
+            d = descs[i]
+            comps = [d.components[k] for k in range(d.num_components)]
+            mh, mv = max([c.h for c in comps] or [1]), max([c.v for c in comps] or [1])
+            self._blocks.append((-(-d.width // (8 * mh))) * (-(-d.height // (8 * mv))) * sum(c.h * c.v for c in comps))
+        return self._device_upload(_lib.jpgpu_encoder_upload_described_device, tensors, pixels, pixel_layout, descs)
 
     def upload_described(self, images, descriptions):
         """images: uint8 arrays (H, W, in_components) or (H, W); descriptions: describe(...) per image.  An arrangement the device
@@ -120,6 +220,7 @@ class EncodeBatch:
             comps = [d.components[k] for k in range(d.num_components)]
             mh, mv = max([c.h for c in comps] or [1]), max([c.v for c in comps] or [1])
             self._blocks.append((-(-d.width // (8 * mh))) * (-(-d.height // (8 * mv))) * sum(c.h * c.v for c in comps))
+        self._keep = None
         self._check(_lib.jpgpu_encoder_upload_described(self._h, ptrs, descs, n))
         self._n = n
         return self
@@ -160,6 +261,20 @@ class EncodeBatch:
         self._check(_lib.jpgpu_encoder_download(self._h, i, out.ctypes.data, out.size))
         return out.tobytes()
 
+    def output_tensor(self, i):
+        """Stream i of the last encode() as a 1-D torch uint8 tensor on the context's device that ALIASES the encoder's output buffer
+        (jpgpu_encoder_output_device) -- no download.  An image whose encode failed raises as output() does.  encode() has synchronised
+        the context's stream, so the tensor may be used on any torch stream.  The tensor keeps the batch alive.  One rule remains: the
+        next upload or encode() on this batch, or an explicit close(), invalidates every tensor made from it."""
+        import torch  # (here: the package imports without torch)
+
+        size = C.c_size_t()
+        self._check(_lib.jpgpu_encoder_encoded_size(self._h, i, C.byref(size)))
+        ptr = _lib.jpgpu_encoder_output_device(self._h, i, C.byref(size))
+        if not ptr:
+            raise ValueError("output_tensor: no encode() has produced stream %d" % i)
+        return torch.as_tensor(_DeviceView(self, ptr, (size.value,)), device=torch.device("cuda", self.ctx.device))
+
     def coefficients(self, i):
         out = np.empty((self._blocks[i], 64), np.int16)
         self._check(_lib.jpgpu_encoder_download_coefficients(self._h, i, out.ctypes.data, out.shape[0]))
@@ -169,6 +284,7 @@ class EncodeBatch:
         if self._h:
             _lib.jpgpu_encoder_destroy(self._h)
             self._h = C.c_void_p()
+        self._keep = None
 
     def __del__(self):
         try:
@@ -180,6 +296,15 @@ class EncodeBatch:
 def encode_batch(images, luma=(2, 2), quality=75, rgb=False, ctx=None, optimize_coding=False, restart_interval=0):
     """One-call helper: list of JPEG byte strings."""
     b = EncodeBatch(ctx).upload(images, luma, quality, rgb, optimize_coding, restart_interval).encode()
+    outs = [b.output(i) for i in range(len(b))]
+    b.close()
+    return outs
+
+
+def encode_tensors(tensors, luma=(2, 2), quality=75, rgb=True, ctx=None, optimize_coding=False, restart_interval=0, layout=None):
+    """One-call helper for torch producers: uint8 tensors on the context's device (layout 'chw' by default: decode_to_tensors' output,
+    R,G,B planes) -> list of JPEG byte strings.  The pixels are never downloaded; see EncodeBatch.upload_tensors."""
+    b = EncodeBatch(ctx).upload_tensors(tensors, luma, quality, rgb, optimize_coding, restart_interval, layout).encode()
     outs = [b.output(i) for i in range(len(b))]
     b.close()
     return outs

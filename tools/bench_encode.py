@@ -5,6 +5,12 @@ restatement on the host cores.  Not the headline benchmark (that is bench.py); p
     python tools/bench_encode.py [--images 64] [--steps 5] [--width 3840 --height 2160] [--quality 75]
     python tools/bench_encode.py --workload het_8192 [--subsampling 420|444] [--optimize-coding] [--images 8]
     python tools/bench_encode.py --arrangement cmyk|420-split [--optimize-coding]
+    python tools/bench_encode.py --input device|device_planar [--images 64]
+
+--input host (the default) is the run described below.  --input device / device_planar: ONE process encodes the same images three ways --
+numpy arrays through upload() (host), torch (H, W, 3) tensors through upload_tensors(layout='hwc') (device) and torch (3, H, W) tensors
+through upload_tensors(layout='chw') (device_planar) -- with the UPLOAD INSIDE the timed step (for the device inputs it copies nothing),
+and reports ms_per_step and stage_ms of each; `value` is the named input's rate.
 
 --arrangement = a described image (jpgpu_encode_description) that is no EncodeAction arrangement, so the general kernels take it:
 cmyk = four 1 x 1 components (four samples per pixel); 420-split = 2 x 2 / 1 x 1 / 1 x 1 from RGB pixels like the default run, but
@@ -77,6 +83,41 @@ def bench_arrangement(jl, args):
                       "stage_ms": {k: round(v, 3) for k, v in b.stage_ms().items()}}))
 
 
+def bench_inputs(jl, po, args, base, imgs, luma):
+    """host, device and device_planar over the same images in one process: upload + encode per step"""
+    import torch
+
+    dev = torch.device("cuda", jl.default_context().device)
+    hwc = [torch.from_numpy(im).to(dev) for im in base]
+    chw = [t.permute(2, 0, 1).contiguous() for t in hwc]
+    torch.cuda.synchronize(dev)
+    kw = dict(restart_interval=args.dri, optimize_coding=args.optimize_coding)
+    forms = {"host": lambda b: b.upload(imgs, luma, args.quality, rgb=True, **kw),
+             "device": lambda b: b.upload_tensors([hwc[i % len(hwc)] for i in range(args.images)], luma, args.quality, rgb=True, layout="hwc", **kw),
+             "device_planar": lambda b: b.upload_tensors([chw[i % len(chw)] for i in range(args.images)], luma, args.quality, rgb=True, layout="chw", **kw)}
+    ref = po.encode_8bit(po.rgb_to_ycbcr8(imgs[0]), luma[0], luma[1], args.quality, restart_interval=args.dri, optimize_coding=args.optimize_coding)
+    px = args.images * args.width * args.height
+    inputs = {}
+    for name, upload in forms.items():
+        b = jl.EncodeBatch()
+        upload(b).encode()
+        upload(b).encode()  # (the second encode of a batch sizes its one-pass buffer from the first)
+        fdct, t0 = [], time.perf_counter()
+        for _ in range(args.steps):
+            upload(b).encode()
+            fdct.append(b.stage_ms()["fdct_quant"])
+        dt = (time.perf_counter() - t0) / args.steps
+        inputs[name] = {"ms_per_step": round(dt * 1e3, 2), "mpixels_per_s": round(px / dt / 1e6, 1), "stage_ms": {k: round(v, 3) for k, v in b.stage_ms().items()},
+                        "fdct_quant_ms_median": round(float(np.median(fdct)), 3), "fdct_quant_ms_min": round(float(min(fdct)), 3),
+                        "byte_exact_vs_oracle": b.output(0) == ref}
+        b.close()
+    f = {k: v["fdct_quant_ms_median"] for k, v in inputs.items()}
+    print(json.dumps({"metric": f"Mpixels/s encoded, upload inside the step (RGB 4:{args.subsampling[1]}:{args.subsampling[2]} baseline, input {args.input})",
+                      "value": inputs[args.input]["mpixels_per_s"], "unit": "Mpixels/s", "ms_per_step": inputs[args.input]["ms_per_step"], "images": args.images,
+                      "steps": args.steps, "width": args.width, "height": args.height, "input": args.input, "inputs": inputs,
+                      "fdct_quant_ratio": {"device_over_host": round(f["device"] / f["host"], 4), "planar_over_interleaved": round(f["device_planar"] / f["device"], 4)}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=64)
@@ -90,6 +131,8 @@ def main():
     ap.add_argument("--optimize-coding", action="store_true", help="Huffman tables from each image's own statistics (EncodeAction's switch)")
     ap.add_argument("--pixels", default=None, choices=["rgb", "rgba"], help="input pixels (default: rgba for het_8192 like the reference's benchmark, rgb otherwise)")
     ap.add_argument("--arrangement", default=None, choices=["cmyk", "420-split"], help="a described image the general kernels take (see above)")
+    ap.add_argument("--input", default="host", choices=["host", "device", "device_planar"],
+                    help="where the pixels are: numpy arrays (host), or torch tensors on the device, (H, W, 3) / (3, H, W); see above")
     args = ap.parse_args()
     import jpeglibrary_amd as jl
 
@@ -120,6 +163,10 @@ def main():
     bpp = 4 if pixels == "rgba" else 3
     to_ycc = po.rgba_to_ycbcr8 if pixels == "rgba" else po.rgb_to_ycbcr8
     imgs = [base[i % distinct] for i in range(args.images)]
+    if args.input != "host":
+        if bpp != 3:
+            ap.error("--input device / device_planar compare three-byte pixels: --pixels rgb")
+        return bench_inputs(jl, po, args, base, imgs, luma)
     b = jl.EncodeBatch().upload(imgs, luma, args.quality, rgb=True, restart_interval=args.dri, optimize_coding=args.optimize_coding)
     b.encode()
     t0 = time.perf_counter()
