@@ -104,16 +104,6 @@ void scale_by_quality(const uint16_t *src, int quality, uint16_t *dst) {
         dst[i] = (uint16_t)std::min(std::max(x, 1), 255);
     }
 }
-
-void put_marker(std::vector<uint8_t> &o, uint8_t m) {  // JpegWriter.WriteMarker (JpegWriter.cs:289-303)
-    o.push_back(0xFF);
-    o.push_back(m);
-}
-void put_length(std::vector<uint8_t> &o, uint16_t len) {  // JpegWriter.WriteLength (:309-321): length + 2
-    const uint16_t v = (uint16_t)(len + 2);
-    o.push_back((uint8_t)(v >> 8));
-    o.push_back((uint8_t)v);
-}
 }  // namespace
 
 // Fix() factors of apps/JpegEncode/JpegRgbToYCbCrConverter.cs:38-56 (float32 arithmetic like the reference's Fix, :59-62)
@@ -127,6 +117,85 @@ void rgb_ycc_factors(int32_t out[8]) {
     out[5] = fix(0.5F);
     out[6] = fix(0.418687589F);
     out[7] = fix(0.081312411F);
+}
+
+// ------------------------------------------------------------------------------------------------ marker segments
+
+// EncodeBatch::set_quantization_table patches the DQT this writes, in place, at 2 + 2 + 2 + identifier * 65 + 1: nothing but SOI in
+// front of the segment, ONE segment, and per table one identifier byte + 64 one-byte elements in list order.  Keep that true.
+void write_marker_segments(const EncSegmentQuant *quant, int n_quant, const EncSegmentComponent *comp, int n_comp, int width, int height,
+                           int restart_interval, std::vector<uint8_t> *pre, std::vector<uint8_t> *post) {
+    std::vector<uint8_t> &h = *pre;
+    h.clear();
+    put_marker(h, 0xD8);
+    put_marker(h, 0xDB);  // WriteQuantizationTables (:305-330): ONE segment, every table of the list in SetQuantizationTable order, used or not
+    put_length(h, (uint16_t)(65 * n_quant));
+    for (int t = 0; t < n_quant; t++) {
+        h.push_back(quant[t].identifier);  // JpegQuantizationTable.TryWrite: precision 0 << 4 | identifier
+        for (int i = 0; i < 64; i++) h.push_back((uint8_t)quant[t].elements[i]);
+    }
+    if (restart_interval) {  // DRI in front of SOF0: the reference's decoder latches it there even without Identify()
+        put_marker(h, 0xDD);
+        put_length(h, 2);
+        h.push_back((uint8_t)(restart_interval >> 8));
+        h.push_back((uint8_t)restart_interval);
+    }
+    put_marker(h, 0xC0);  // WriteStartOfFrame (:353-381)
+    put_length(h, (uint16_t)(6 + 3 * n_comp));
+    h.push_back(8);
+    h.push_back((uint8_t)(height >> 8));
+    h.push_back((uint8_t)height);
+    h.push_back((uint8_t)(width >> 8));
+    h.push_back((uint8_t)width);
+    h.push_back((uint8_t)n_comp);
+    for (int c = 0; c < n_comp; c++) {
+        h.push_back(comp[c].id);
+        h.push_back((uint8_t)((comp[c].h << 4) | comp[c].v));
+        h.push_back(comp[c].tq);
+    }
+    std::vector<uint8_t> &sos = *post;
+    sos.clear();
+    put_marker(sos, 0xDA);  // WriteStartOfScan (:387-408)
+    put_length(sos, (uint16_t)(1 + 2 * n_comp + 3));
+    sos.push_back((uint8_t)n_comp);
+    for (int c = 0; c < n_comp; c++) {
+        sos.push_back(comp[c].id);
+        sos.push_back((uint8_t)((comp[c].td << 4) | (comp[c].ta & 0xf)));
+    }
+    sos.push_back(0);
+    sos.push_back(63);
+    sos.push_back(0);
+}
+
+// WriteHuffmanTables (:336-347) between the two: ONE segment, every table of the collection in SetHuffmanTable order
+void assemble_header(const std::vector<uint8_t> &pre, const std::vector<uint8_t> &dht_body, const std::vector<uint8_t> &post,
+                     std::vector<uint8_t> *header) {
+    std::vector<uint8_t> &h = *header;
+    h = pre;
+    put_marker(h, 0xC4);
+    put_length(h, (uint16_t)dht_body.size());
+    h.insert(h.end(), dht_body.begin(), dht_body.end());
+    h.insert(h.end(), post.begin(), post.end());
+}
+
+// ------------------------------------------------------------------------------------------------ stuffing stage layout
+
+StuffPlan plan_stuffing_layout(DevEncImage *images, const uint64_t *raw_bits, int n, bool place_raw) {
+    StuffPlan sp;
+    for (int i = 0; i < n; i++) {
+        DevEncImage &im = images[i];
+        const uint64_t raw_len = (raw_bits[i] + 7) / 8;
+        if (place_raw) im.raw_off = sp.raw_bytes;
+        im.out_off = sp.out_bytes;
+        im.chunk_off = sp.chunks;
+        const uint32_t chunks = std::max<uint32_t>(1u, (uint32_t)((raw_len + kEncStuffChunk - 1) / kEncStuffChunk));
+        for (uint32_t c = 0; c < chunks; c++) sp.work_chunk.push_back({(uint32_t)i, c});
+        sp.chunks += chunks;
+        sp.raw_bytes = align_up64(sp.raw_bytes + raw_len + 64, 256);
+        // every byte may need stuffing; two marker bytes per restart interval
+        sp.out_bytes = align_up64(sp.out_bytes + im.header_len + 2 * raw_len + 2 + 64 + (im.restart_interval ? 2 * (uint64_t)im.n_units : 0), 256);
+    }
+    return sp;
 }
 
 // ------------------------------------------------------------------------------------------------ described images
@@ -155,22 +224,20 @@ void resolve_given_table(const jpgpu_encode_huffman_table &t, EncPlan::Slot *slo
     for (int i = n - code_count; i < n; i++) slot->dht.push_back(t.symbol[i]);
 }
 
-void std_slot(int t, EncPlan::Slot *slot) {
-    build_enc_table(kStd[t], &slot->table);
-    slot->dht.assign(kStd[t].lengths, kStd[t].lengths + 16);
-    slot->dht.insert(slot->dht.end(), kStd[t].values, kStd[t].values + kStd[t].count);
+// the four standard tables in SetHuffmanTable order (DC0, AC0, DC1, AC1): table t's Tc/Th byte, and its 16 counts + symbols
+uint8_t std_tc_th(int t) { return (uint8_t)(((t & 1) << 4) | (t >> 1)); }
+void append_std_dht(int t, std::vector<uint8_t> *dht) {
+    dht->insert(dht->end(), kStd[t].lengths, kStd[t].lengths + 16);
+    dht->insert(dht->end(), kStd[t].values, kStd[t].values + kStd[t].count);
 }
-}  // namespace
 
-int resolve_encode_description(const jpgpu_encode_description &d, EncPlan *plan, std::string *error) {
-    auto bad = [&](int status, const char *msg) {
-        if (error) *error = msg;
+// ---- what the reference's setters throw on (JpegEncoder.cs:102-240), and what this interface cannot express; the slots
+// (d.huffman_tables[]) of every component's DC and AC table on the way
+int check_description(const jpgpu_encode_description &d, int dc_slot[4], int ac_slot[4], const char **msg) {
+    auto bad = [&](int status, const char *m) {
+        *msg = m;
         return status;
     };
-    *plan = EncPlan();
-    plan->layout.assign(1, DevEncLayout());
-    memset(&plan->layout[0], 0, sizeof(DevEncLayout));
-    // ---- what the reference's setters throw on (JpegEncoder.cs:102-240), and what this interface cannot express
     if (d.width <= 0 || d.height <= 0 || d.width > 65535 || d.height > 65535) return bad(JPGPU_ERR_ARGUMENT, "image dimensions out of range");
     if (d.num_components < 0 || d.num_components > JPGPU_ENC_MAX_COMPONENTS) return bad(JPGPU_ERR_ARGUMENT, "1 to 4 components can be described.");
     if (d.num_components == 0) return bad(JPGPU_ERR_INVALID_OPERATION, "No component is specified.");
@@ -210,7 +277,6 @@ int resolve_encode_description(const jpgpu_encode_description &d, EncPlan *plan,
             if (d.huffman_tables[t].table_class == cls && d.huffman_tables[t].identifier == id) return t;
         return -1;
     };
-    int dc_slot[4], ac_slot[4];
     for (int c = 0; c < nc; c++) {
         dc_slot[c] = find_slot(0, d.components[c].td);
         ac_slot[c] = find_slot(1, d.components[c].ta);
@@ -220,18 +286,14 @@ int resolve_encode_description(const jpgpu_encode_description &d, EncPlan *plan,
     if (d.input_rgb < 0 || d.input_rgb > 2) return bad(JPGPU_ERR_ARGUMENT, "input_rgb is 0 (samples), 1 (R,G,B) or 2 (R,G,B,A).");
     if (d.input_rgb && (nc != 3 || d.in_components != (d.input_rgb == 2 ? 4 : 3))) return bad(JPGPU_ERR_ARGUMENT, "RGB input needs 3 components.");
     if (d.restart_interval < 0 || d.restart_interval > 65535) return bad(JPGPU_ERR_ARGUMENT, "restart interval out of range (0..65535)");
+    return JPGPU_OK;
+}
 
-    plan->width = d.width;
-    plan->height = d.height;
-    plan->in_components = d.in_components;
-    plan->input_rgb = d.input_rgb;
-    plan->restart_interval = d.restart_interval;
-    // ---- tables
+// ---- tables: a given one in its by-symbol and its DHT form, a builder as a slot to be filled from the image's statistics
+void resolve_table_slots(const jpgpu_encode_description &d, EncPlan *plan) {
     plan->n_slots = d.num_huffman_tables;
     plan->slots.assign((size_t)plan->n_slots, EncPlan::Slot());
     plan->most_optimal = d.most_optimal_coding != 0;
-    bool fed[JPGPU_ENC_MAX_TABLES] = {};
-    for (int c = 0; c < nc; c++) fed[dc_slot[c]] = fed[ac_slot[c]] = true;
     for (int t = 0; t < plan->n_slots; t++) {
         const jpgpu_encode_huffman_table &h = d.huffman_tables[t];
         EncPlan::Slot &s = plan->slots[t];
@@ -241,7 +303,11 @@ int resolve_encode_description(const jpgpu_encode_description &d, EncPlan *plan,
         if (s.given) resolve_given_table(h, &s);
         else plan->any_builder = true;
     }
-    // ---- geometry
+}
+
+// ---- geometry: the general kernels' block map (DevEncLayout).  Returns whether a component has the maximum factors both ways.
+bool resolve_block_map(const jpgpu_encode_description &d, const int dc_slot[4], const int ac_slot[4], EncPlan *plan) {
+    const int nc = d.num_components;
     DevEncLayout &L = plan->layout[0];
     uint32_t max_h = 1, max_v = 1;
     for (int c = 0; c < nc; c++) {
@@ -290,70 +356,31 @@ int resolve_encode_description(const jpgpu_encode_description &d, EncPlan *plan,
             if (mx * L.h[c] + L.blk_x[k] >= L.grid_w[c] || my * L.v[c] + L.blk_y[k] >= L.grid_h[c]) L.dummy_blk = last * b + k;
         }
     }
-    // ---- marker segments, from the lists (JpegEncoder.cs:261-280)
-    std::vector<uint8_t> &h = plan->header_pre;
-    put_marker(h, 0xD8);
-    put_marker(h, 0xDB);  // WriteQuantizationTables (:305-330): every table of the list, used or not
-    put_length(h, (uint16_t)(65 * d.num_quant_tables));
-    for (int t = 0; t < d.num_quant_tables; t++) {
-        h.push_back(d.quant_tables[t].identifier);  // JpegQuantizationTable.TryWrite: precision << 4 | identifier
-        for (int i = 0; i < 64; i++) h.push_back((uint8_t)d.quant_tables[t].elements[i]);
+    return full_resolution;
+}
+
+// ---- marker segments, from the lists (JpegEncoder.cs:261-280); without builders the DHT is known now and so is all of SOI..SOS
+void write_description_segments(const jpgpu_encode_description &d, EncPlan *plan) {
+    EncSegmentQuant quant[JPGPU_ENC_MAX_TABLES];
+    EncSegmentComponent comp[JPGPU_ENC_MAX_COMPONENTS];
+    for (int t = 0; t < d.num_quant_tables; t++) quant[t] = {d.quant_tables[t].identifier, d.quant_tables[t].elements};
+    for (int c = 0; c < d.num_components; c++) {
+        const jpgpu_encode_component &k = d.components[c];
+        comp[c] = {k.component_index, k.h, k.v, k.tq, k.td, k.ta};
     }
-    if (d.restart_interval) {
-        put_marker(h, 0xDD);
-        put_length(h, 2);
-        h.push_back((uint8_t)(d.restart_interval >> 8));
-        h.push_back((uint8_t)d.restart_interval);
+    write_marker_segments(quant, d.num_quant_tables, comp, d.num_components, d.width, d.height, d.restart_interval, &plan->header_pre, &plan->header_post);
+    if (plan->any_builder) return;
+    std::vector<uint8_t> body;
+    for (const EncPlan::Slot &s : plan->slots) {
+        body.push_back(s.tc_th);
+        body.insert(body.end(), s.dht.begin(), s.dht.end());
     }
-    put_marker(h, 0xC0);  // WriteStartOfFrame (:353-381)
-    put_length(h, (uint16_t)(6 + 3 * nc));
-    h.push_back(8);
-    h.push_back((uint8_t)(d.height >> 8));
-    h.push_back((uint8_t)d.height);
-    h.push_back((uint8_t)(d.width >> 8));
-    h.push_back((uint8_t)d.width);
-    h.push_back((uint8_t)nc);
-    for (int c = 0; c < nc; c++) {
-        h.push_back(d.components[c].component_index);
-        h.push_back((uint8_t)((d.components[c].h << 4) | d.components[c].v));
-        h.push_back(d.components[c].tq);
-    }
-    std::vector<uint8_t> &sos = plan->header_post;
-    put_marker(sos, 0xDA);  // WriteStartOfScan (:387-408)
-    put_length(sos, (uint16_t)(1 + 2 * nc + 3));
-    sos.push_back((uint8_t)nc);
-    for (int c = 0; c < nc; c++) {
-        sos.push_back(d.components[c].component_index);
-        sos.push_back((uint8_t)((d.components[c].td << 4) | (d.components[c].ta & 0xf)));
-    }
-    sos.push_back(0);
-    sos.push_back(63);
-    sos.push_back(0);
-    if (!plan->any_builder) {
-        plan->header = plan->header_pre;
-        put_marker(plan->header, 0xC4);  // WriteHuffmanTables (:336-347): every table of the collection, in SetHuffmanTable order
-        size_t total = 0;
-        for (int t = 0; t < plan->n_slots; t++) total += 1 + plan->slots[t].dht.size();
-        put_length(plan->header, (uint16_t)total);
-        for (int t = 0; t < plan->n_slots; t++) {
-            plan->header.push_back(plan->slots[t].tc_th);
-            plan->header.insert(plan->header.end(), plan->slots[t].dht.begin(), plan->slots[t].dht.end());
-        }
-        plan->header.insert(plan->header.end(), sos.begin(), sos.end());
-    }
-    // ---- what Encode() of this image reports
-    if (!full_resolution) {
-        plan->status = JPGPU_ERR_NOT_SUPPORTED;
-        plan->message = "No component has the maximum sampling factors in both directions: every block then starts from the block encoded before it "
-                        "(one block buffer for the whole scan), which is a serial chain over the image.";
-        return JPGPU_OK;
-    }
-    for (int t = 0; t < plan->n_slots; t++)
-        if (!plan->slots[t].given && !fed[t]) {  // JpegHuffmanEncodingTableBuilder.Build of a builder no component feeds
-            plan->status = JPGPU_ERR_INVALID_OPERATION;
-            plan->message = "No symbol is recorded.";
-        }
-    // ---- an EncodeAction arrangement?  (apps/JpegEncode/EncodeAction.cs:38-63: what jpgpu_encoder_upload describes)
+    assemble_header(plan->header_pre, body, plan->header_post, &plan->header);
+}
+
+// ---- an EncodeAction arrangement?  (apps/JpegEncode/EncodeAction.cs:38-63: what jpgpu_encoder_upload describes)
+void classify_encode_action(const jpgpu_encode_description &d, EncPlan *plan) {
+    const int nc = d.num_components;
     bool legacy = (nc == 1 || nc == 3) && d.num_quant_tables == 2 && d.num_huffman_tables == 4 && d.quant_tables[0].identifier == 0 &&
                   d.quant_tables[1].identifier == 1 && d.in_components == (d.input_rgb == 2 ? 4 : nc);
     for (int c = 0; legacy && c < nc; c++) {
@@ -367,25 +394,62 @@ int resolve_encode_description(const jpgpu_encode_description &d, EncPlan *plan,
         legacy = ht.table_class == (t & 1) && ht.identifier == (t >> 1) && (ht.given != 0) == (d.huffman_tables[0].given != 0);
         if (legacy && ht.given) {
             EncPlan::Slot s;
-            std_slot(t, &s);
+            build_enc_table(kStd[t], &s.table);
+            append_std_dht(t, &s.dht);
             legacy = s.dht == plan->slots[t].dht && memcmp(&s.table, &plan->slots[t].table, sizeof s.table) == 0;
         }
     }
-    if (legacy) {
-        plan->legacy = true;
-        plan->legacy_has_quant = true;
-        plan->params.width = d.width;
-        plan->params.height = d.height;
-        plan->params.components = nc;
-        plan->params.luma_h = d.components[0].h;
-        plan->params.luma_v = d.components[0].v;
-        plan->params.quality = 50;
-        plan->params.input_rgb = d.input_rgb;
-        plan->params.optimize_coding = plan->any_builder ? (plan->most_optimal ? 2 : 1) : 0;
-        plan->params.restart_interval = d.restart_interval;
-        for (int t = 0; t < 2; t++)
-            for (int i = 0; i < 64; i++) plan->legacy_quant[t][i] = d.quant_tables[t].elements[i];
+    if (!legacy) return;
+    plan->legacy = true;
+    plan->legacy_has_quant = true;
+    plan->params.width = d.width;
+    plan->params.height = d.height;
+    plan->params.components = nc;
+    plan->params.luma_h = d.components[0].h;
+    plan->params.luma_v = d.components[0].v;
+    plan->params.quality = 50;
+    plan->params.input_rgb = d.input_rgb;
+    plan->params.optimize_coding = plan->any_builder ? (plan->most_optimal ? 2 : 1) : 0;
+    plan->params.restart_interval = d.restart_interval;
+    for (int t = 0; t < 2; t++)
+        for (int i = 0; i < 64; i++) plan->legacy_quant[t][i] = d.quant_tables[t].elements[i];
+}
+}  // namespace
+
+int resolve_encode_description(const jpgpu_encode_description &d, EncPlan *plan, std::string *error) {
+    *plan = EncPlan();
+    plan->layout.assign(1, DevEncLayout());
+    memset(&plan->layout[0], 0, sizeof(DevEncLayout));
+    int dc_slot[4], ac_slot[4];
+    const char *msg = "";
+    const int rc = check_description(d, dc_slot, ac_slot, &msg);
+    if (rc != JPGPU_OK) {
+        if (error) *error = msg;
+        return rc;
     }
+    plan->width = d.width;
+    plan->height = d.height;
+    plan->in_components = d.in_components;
+    plan->input_rgb = d.input_rgb;
+    plan->restart_interval = d.restart_interval;
+    resolve_table_slots(d, plan);
+    const bool full_resolution = resolve_block_map(d, dc_slot, ac_slot, plan);
+    write_description_segments(d, plan);
+    // ---- what Encode() of this image reports
+    if (!full_resolution) {
+        plan->status = JPGPU_ERR_NOT_SUPPORTED;
+        plan->message = "No component has the maximum sampling factors in both directions: every block then starts from the block encoded before it "
+                        "(one block buffer for the whole scan), which is a serial chain over the image.";
+        return JPGPU_OK;
+    }
+    bool fed[JPGPU_ENC_MAX_TABLES] = {};
+    for (int c = 0; c < d.num_components; c++) fed[dc_slot[c]] = fed[ac_slot[c]] = true;
+    for (int t = 0; t < plan->n_slots; t++)
+        if (!plan->slots[t].given && !fed[t]) {  // JpegHuffmanEncodingTableBuilder.Build of a builder no component feeds
+            plan->status = JPGPU_ERR_INVALID_OPERATION;
+            plan->message = "No symbol is recorded.";
+        }
+    classify_encode_action(d, plan);
     return JPGPU_OK;
 }
 
@@ -406,42 +470,36 @@ int EncodeBatch::hip_fail(hipError_t e, const char *what) {
     return e == hipErrorOutOfMemory ? JPGPU_ERR_OUT_OF_MEMORY : JPGPU_ERR_DEVICE;
 }
 
+// ------------------------------------------------------------------------------------------------ upload
+
 int EncodeBatch::upload(const uint8_t *const *pixels, const jpgpu_encode_params *params, int n) {
     if (n < 0 || (n > 0 && (!pixels || !params))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encode_upload: null argument");
-    std::vector<EncPlan> plans((size_t)n);
-    for (int i = 0; i < n; i++) {
-        plans[(size_t)i].legacy = true;
-        plans[(size_t)i].params = params[i];
-    }
-    upload_described_ = false;
-    return upload_plans(pixels, plans);
+    return upload_params(pixels, params, n, false, nullptr);
 }
-
 int EncodeBatch::upload_described(const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n) {
     if (n < 0 || (n > 0 && (!pixels || !desc))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_described: null argument");
-    std::vector<EncPlan> plans((size_t)n);
-    for (int i = 0; i < n; i++) {
-        std::string error;
-        const int rc = resolve_encode_description(desc[i], &plans[(size_t)i], &error);
-        if (rc != JPGPU_OK) return fail(rc, error);
-    }
-    upload_described_ = true;
-    return upload_plans(pixels, plans);
+    return upload_descriptions(pixels, desc, n, false, nullptr);
 }
-
 int EncodeBatch::upload_device(const void *const *device_pixels, const jpgpu_encode_params *params, const int32_t *pixel_layouts, int n) {
     if (n < 0 || (n > 0 && (!device_pixels || !params))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_device: null argument");
+    return upload_params(reinterpret_cast<const uint8_t *const *>(device_pixels), params, n, true, pixel_layouts);
+}
+int EncodeBatch::upload_described_device(const void *const *device_pixels, const jpgpu_encode_description *desc, const int32_t *pixel_layouts, int n) {
+    if (n < 0 || (n > 0 && (!device_pixels || !desc))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_described_device: null argument");
+    return upload_descriptions(reinterpret_cast<const uint8_t *const *>(device_pixels), desc, n, true, pixel_layouts);
+}
+
+int EncodeBatch::upload_params(const uint8_t *const *pixels, const jpgpu_encode_params *params, int n, bool device, const int32_t *pixel_layouts) {
     std::vector<EncPlan> plans((size_t)n);
     for (int i = 0; i < n; i++) {
         plans[(size_t)i].legacy = true;
         plans[(size_t)i].params = params[i];
     }
     upload_described_ = false;
-    return upload_plans(reinterpret_cast<const uint8_t *const *>(device_pixels), plans, true, pixel_layouts);
+    return upload_plans(pixels, plans, device, pixel_layouts);
 }
 
-int EncodeBatch::upload_described_device(const void *const *device_pixels, const jpgpu_encode_description *desc, const int32_t *pixel_layouts, int n) {
-    if (n < 0 || (n > 0 && (!device_pixels || !desc))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_described_device: null argument");
+int EncodeBatch::upload_descriptions(const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n, bool device, const int32_t *pixel_layouts) {
     std::vector<EncPlan> plans((size_t)n);
     for (int i = 0; i < n; i++) {
         std::string error;
@@ -449,7 +507,7 @@ int EncodeBatch::upload_described_device(const void *const *device_pixels, const
         if (rc != JPGPU_OK) return fail(rc, error);
     }
     upload_described_ = true;
-    return upload_plans(reinterpret_cast<const uint8_t *const *>(device_pixels), plans, true, pixel_layouts);
+    return upload_plans(pixels, plans, device, pixel_layouts);
 }
 
 // A device upload hands the kernels the caller's addresses: every image must lie, whole, inside ONE allocation of device memory of
@@ -478,8 +536,23 @@ int EncodeBatch::check_device_pixels(const uint8_t *const *pixels) {
     return JPGPU_OK;
 }
 
+// what layout_plans' stages hand one another
+struct EncodeBatch::UploadPlan {
+    const uint8_t *const *pixels = nullptr;
+    bool device = false;
+    const int32_t *pixel_layouts = nullptr;
+    std::vector<EncWork> work_mcu, work_blk, work_stat;  // per 128 MCUs | per 256 units (blocks or restart intervals) | per 256 blocks
+    std::vector<uint32_t> work_order;                    // bits_emit_kernel's issue order
+    std::vector<EncHuffTable> tables;
+    uint64_t px_off = 0, coef_off = 0, smp_off = 0;
+};
+
 int EncodeBatch::upload_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans, bool device, const int32_t *pixel_layouts) {
-    const int rc = layout_plans(pixels, plans, device, pixel_layouts);
+    UploadPlan up;
+    up.pixels = pixels;
+    up.device = device;
+    up.pixel_layouts = pixel_layouts;
+    const int rc = layout_plans(up, plans);
     if (rc != JPGPU_OK && device) {  // a refused device upload leaves nothing behind that an encode() could read through
         images_.clear();
         status_.clear();
@@ -489,24 +562,43 @@ int EncodeBatch::upload_plans(const uint8_t *const *pixels, const std::vector<En
     return rc;
 }
 
-// Both uploads: an EncodeAction arrangement (plan.legacy) is laid out as it always was, a described one beside it.
-int EncodeBatch::layout_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans, bool device, const int32_t *pixel_layouts) {
+// Both uploads: an EncodeAction arrangement (plan.legacy) is laid out as it always was, a described one beside it.  The first
+// refusal in image order is the call's.
+int EncodeBatch::layout_plans(UploadPlan &up, const std::vector<EncPlan> &plans) {
     const int n = (int)plans.size();
-    if (device)
-        for (int i = 0; i < n; i++) {
-            if (!pixels[i]) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_device: null pixel pointer");
-            if (pixel_layouts && pixel_layouts[i] != JPGPU_PIXELS_INTERLEAVED && pixel_layouts[i] != JPGPU_PIXELS_PLANAR)
-                return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_device: a pixel layout is JPGPU_PIXELS_INTERLEAVED (0) or JPGPU_PIXELS_PLANAR (1)");
-        }
-    // where image i's pixels are, and how they are laid out
-    auto place = [&](DevEncImage &im, int i, uint64_t px_off) {
-        im.px_off = device ? (uint64_t)(uintptr_t)pixels[i] : px_off;
-        im.px_planar = (device && pixel_layouts && pixel_layouts[i] == JPGPU_PIXELS_PLANAR) ? 1u : 0u;
-        im.plane_stride = (uint64_t)im.width * im.height;
-    };
-    const char *planar_rgba = "jpgpu_encoder_upload_device: Rgba32 pixels (input_rgb == 2) have no planar layout";
+    int rc = check_device_arguments(up, n);
+    if (rc != JPGPU_OK) return rc;
     hipError_t e = hipSetDevice(ctx_->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    reset_upload_state(n);
+    for (int i = 0; i < n; i++) {
+        const EncPlan &pl = plans[(size_t)i];
+        rc = pl.legacy ? plan_encode_action_image(up, i, pl) : plan_described_image(up, i, pl);
+        if (rc != JPGPU_OK) return rc;
+    }
+    if (up.device) {  // (every argument check is behind us, nothing has been enqueued)
+        rc = check_device_pixels(up.pixels);
+        if (rc != JPGPU_OK) return rc;
+    }
+    pixels_on_device_ = up.device;
+    total_blocks_ = up.coef_off;
+    n_work_mcu_ = (int)up.work_mcu.size();
+    n_work_blk_ = (int)up.work_blk.size();
+    n_work_stat_ = (int)up.work_stat.size();
+    place_table_slots(up);
+    return reserve_and_upload(up);
+}
+
+int EncodeBatch::check_device_arguments(const UploadPlan &up, int n) {
+    for (int i = 0; i < n && up.device; i++) {
+        if (!up.pixels[i]) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_device: null pixel pointer");
+        if (up.pixel_layouts && up.pixel_layouts[i] != JPGPU_PIXELS_INTERLEAVED && up.pixel_layouts[i] != JPGPU_PIXELS_PLANAR)
+            return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_device: a pixel layout is JPGPU_PIXELS_INTERLEAVED (0) or JPGPU_PIXELS_PLANAR (1)");
+    }
+    return JPGPU_OK;
+}
+
+void EncodeBatch::reset_upload_state(int n) {
     images_.assign((size_t)n, DevEncImage());
     headers_.assign((size_t)n, std::vector<uint8_t>());
     headers_pre_.assign((size_t)n, std::vector<uint8_t>());
@@ -522,226 +614,191 @@ int EncodeBatch::layout_plans(const uint8_t *const *pixels, const std::vector<En
     encoded_ = false;
     any_restart_ = false;
     emit_hint_ = 0;
-    std::vector<EncWork> work_mcu, work_blk, work_stat;  // per 128 MCUs | per 256 units (blocks or restart intervals) | per 256 blocks
-    uint64_t px_off = 0, coef_off = 0, smp_off = 0;
-    for (int i = 0; i < n; i++) {
-        if (!plans[(size_t)i].legacy) {
-            // ---- a described arrangement: the general kernels (DevEncLayout); a refused one holds no work at all
-            const EncPlan &pl = plans[(size_t)i];
-            DevEncImage &im = images_[i];
-            memset(&im, 0, sizeof im);
-            status_[i] = pl.status;
-            if (pl.status != JPGPU_OK) messages_[i] = pl.message;
-            const bool run = pl.status == JPGPU_OK;
-            const DevEncLayout &pll = pl.layout[0];
-            im.coef_off = coef_off;
-            general_.push_back(i);
-            general_plans_.push_back(pl);
-            layouts_.push_back(pll);
-            im.layout = (uint32_t)layouts_.size();
-            im.width = (uint32_t)pl.width;
-            im.height = (uint32_t)pl.height;
-            im.in_components = (uint32_t)pl.in_components;
-            im.components = pll.ncomp;
-            im.luma_h = pll.max_h;
-            im.luma_v = pll.max_v;
-            im.input_rgb = pl.input_rgb ? 1 : 0;
-            im.restart_interval = (uint32_t)pl.restart_interval;
-            place(im, i, px_off);
-            if (im.px_planar && pl.input_rgb == 2) return fail(JPGPU_ERR_ARGUMENT, planar_rgba);
-            rgb_ycc_factors(im.r2y);
-            if (run) {
-                im.mcus_per_line = (im.width + 8 * im.luma_h - 1) / (8 * im.luma_h);
-                im.mcus_per_column = (im.height + 8 * im.luma_v - 1) / (8 * im.luma_v);
-                im.bpm = pl.bpm;
-                im.total_blocks = im.mcus_per_line * im.mcus_per_column * im.bpm;
-                any_restart_ = any_restart_ || im.restart_interval != 0;
-                im.n_units = im.restart_interval ? (im.mcus_per_line * im.mcus_per_column + im.restart_interval - 1) / im.restart_interval : im.total_blocks;
-                px_off = align_up64(px_off + (uint64_t)im.width * im.height * im.in_components, 256);
-                coef_off += im.total_blocks;
-                const uint32_t total_mcus = im.mcus_per_line * im.mcus_per_column;
-                for (uint32_t f = 0; f < total_mcus; f += kEncMcusPerWg) work_mcu.push_back({(uint32_t)i, f});
-                im.work_first = (uint32_t)work_blk.size();
-                for (uint32_t f = 0; f < im.n_units; f += 256) work_blk.push_back({(uint32_t)i, f});
-                if (pl.any_builder) {
-                    any_general_builder_ = true;
-                    for (uint32_t f = 0; f < im.total_blocks; f += 256) work_stat.push_back({(uint32_t)i, f});
-                }
-                headers_[i] = pl.header;
-                headers_pre_[i] = pl.header_pre;
-                headers_post_[i] = pl.header_post;
-                im.header_len = (uint32_t)pl.header.size();
-                // tables to be built: the DHT is written once the statistics are in; reserve the largest it can be
-                if (pl.any_builder) im.header_len = (uint32_t)(pl.header_pre.size() + 4 + (size_t)pl.n_slots * (1 + 16 + 256) + pl.header_post.size());
-            } else {
-                im.work_first = (uint32_t)work_blk.size();
-                im.width = im.height = im.restart_interval = 0;  // (no pixels are uploaded for it)
-            }
-            continue;  // (the layout's table slots are placed once the number of EncodeAction images with built tables is known)
-        }
-        const jpgpu_encode_params &p = plans[(size_t)i].params;
-        // argument checks of the reference's setters (JpegEncoder.cs:175-184, EncodeAction.cs:19-22)
-        if (p.quality <= 0 || p.quality > 100) return fail(JPGPU_ERR_ARGUMENT, "Specified argument was out of the range of valid values. (Parameter 'quality')");
-        if ((p.luma_h != 1 && p.luma_h != 2 && p.luma_h != 4) || (p.luma_v != 1 && p.luma_v != 2 && p.luma_v != 4))
-            return fail(JPGPU_ERR_ARGUMENT, "Subsampling factor can only be 1, 2 or 4.");
-        if (p.width <= 0 || p.height <= 0 || p.width > 65535 || p.height > 65535) return fail(JPGPU_ERR_ARGUMENT, "image dimensions out of range");
-        if (p.components != 1 && p.components != 3) return fail(JPGPU_ERR_NOT_SUPPORTED, "1 or 3 components are supported.");
-        if (p.input_rgb && p.components != 3) return fail(JPGPU_ERR_ARGUMENT, "RGB input needs 3 components.");
-        if (p.input_rgb < 0 || p.input_rgb > 2) return fail(JPGPU_ERR_ARGUMENT, "input_rgb is 0 (samples), 1 (R,G,B) or 2 (R,G,B,A).");
-        if (p.restart_interval < 0 || p.restart_interval > 65535) return fail(JPGPU_ERR_ARGUMENT, "restart interval out of range (0..65535)");
-        DevEncImage &im = images_[i];
-        memset(&im, 0, sizeof im);
-        im.coef_off = coef_off;
-        im.width = (uint32_t)p.width;
-        im.height = (uint32_t)p.height;
-        place(im, i, px_off);
-        if (im.px_planar && p.input_rgb == 2) return fail(JPGPU_ERR_ARGUMENT, planar_rgba);
-        im.in_components = p.input_rgb == 2 ? 4u : (uint32_t)p.components;  // (2: Rgba32 pixels, the alpha byte stepped over)
-        im.components = (uint32_t)p.components;
-        im.luma_h = (uint32_t)p.luma_h;
-        im.luma_v = (uint32_t)p.luma_v;
-        im.mcus_per_line = (im.width + 8 * im.luma_h - 1) / (8 * im.luma_h);
-        im.mcus_per_column = (im.height + 8 * im.luma_v - 1) / (8 * im.luma_v);
-        im.bpm = im.luma_h * im.luma_v + (im.components == 3 ? 2 : 0);
-        im.total_blocks = im.mcus_per_line * im.mcus_per_column * im.bpm;
-        im.input_rgb = p.input_rgb ? 1 : 0;
-        // restart intervals (an extension, see jpgpu_encode_params): block_bits / emit then take one lane per INTERVAL
-        im.restart_interval = (uint32_t)p.restart_interval;
-        any_restart_ = any_restart_ || p.restart_interval != 0;
-        im.n_units = im.restart_interval ? (im.mcus_per_line * im.mcus_per_column + im.restart_interval - 1) / im.restart_interval : im.total_blocks;
-        if (p.optimize_coding) {
-            most_optimal_[i] = p.optimize_coding == 2;  // JpegEncoder.MostOptimalCoding
-            optimized_.push_back(i);
-            im.table_base = 4u * (uint32_t)optimized_.size();  // tables 0..3 are the standard ones
-        }
-        rgb_ycc_factors(im.r2y);
+}
+
+// where image i's pixels are, and how they are laid out (width, height set)
+int EncodeBatch::place_pixels(const UploadPlan &up, int i, int input_rgb) {
+    DevEncImage &im = images_[i];
+    im.px_off = up.device ? (uint64_t)(uintptr_t)up.pixels[i] : up.px_off;
+    im.px_planar = (up.device && up.pixel_layouts && up.pixel_layouts[i] == JPGPU_PIXELS_PLANAR) ? 1u : 0u;
+    im.plane_stride = (uint64_t)im.width * im.height;
+    if (im.px_planar && input_rgb == 2) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_upload_device: Rgba32 pixels (input_rgb == 2) have no planar layout");
+    return JPGPU_OK;
+}
+
+// The geometry of an image that encodes (sampling factors, bpm, restart interval and pixel format set), its place in the pixel and
+// coefficient buffers and its workgroups: per 128 MCUs (E1), per 256 units (E2 / E3) and, with tables to build, per 256 blocks
+void EncodeBatch::plan_image_work(UploadPlan &up, int i, bool statistics) {
+    DevEncImage &im = images_[i];
+    im.mcus_per_line = (im.width + 8 * im.luma_h - 1) / (8 * im.luma_h);
+    im.mcus_per_column = (im.height + 8 * im.luma_v - 1) / (8 * im.luma_v);
+    im.total_blocks = im.mcus_per_line * im.mcus_per_column * im.bpm;
+    // restart intervals (an extension, see jpgpu_encode_params): block_bits / emit then take one lane per INTERVAL
+    any_restart_ = any_restart_ || im.restart_interval != 0;
+    im.n_units = im.restart_interval ? (im.mcus_per_line * im.mcus_per_column + im.restart_interval - 1) / im.restart_interval : im.total_blocks;
+    up.px_off = align_up64(up.px_off + (uint64_t)im.width * im.height * im.in_components, 256);
+    up.coef_off += im.total_blocks;
+    const uint32_t total_mcus = im.mcus_per_line * im.mcus_per_column;
+    for (uint32_t f = 0; f < total_mcus; f += kEncMcusPerWg) up.work_mcu.push_back({(uint32_t)i, f});
+    im.work_first = (uint32_t)up.work_blk.size();
+    for (uint32_t f = 0; f < im.n_units; f += 256) up.work_blk.push_back({(uint32_t)i, f});
+    if (statistics)
+        for (uint32_t f = 0; f < im.total_blocks; f += 256) up.work_stat.push_back({(uint32_t)i, f});
+}
+
+// A described arrangement: the general kernels (DevEncLayout); a refused one holds no work at all.  (The layout's table slots are
+// placed once the number of EncodeAction images with built tables is known: place_table_slots.)
+int EncodeBatch::plan_described_image(UploadPlan &up, int i, const EncPlan &pl) {
+    DevEncImage &im = images_[i];
+    memset(&im, 0, sizeof im);
+    status_[i] = pl.status;
+    if (pl.status != JPGPU_OK) messages_[i] = pl.message;
+    const DevEncLayout &pll = pl.layout[0];
+    im.coef_off = up.coef_off;
+    general_.push_back(i);
+    general_plans_.push_back(pl);
+    layouts_.push_back(pll);
+    im.layout = (uint32_t)layouts_.size();
+    im.width = (uint32_t)pl.width;
+    im.height = (uint32_t)pl.height;
+    im.in_components = (uint32_t)pl.in_components;
+    im.components = pll.ncomp;
+    im.luma_h = pll.max_h;
+    im.luma_v = pll.max_v;
+    im.input_rgb = pl.input_rgb ? 1 : 0;
+    im.restart_interval = (uint32_t)pl.restart_interval;
+    const int rc = place_pixels(up, i, pl.input_rgb);
+    if (rc != JPGPU_OK) return rc;
+    rgb_ycc_factors(im.r2y);
+    if (pl.status != JPGPU_OK) {
+        im.work_first = (uint32_t)up.work_blk.size();
+        im.width = im.height = im.restart_interval = 0;  // (no pixels are uploaded for it)
+        return JPGPU_OK;
+    }
+    im.bpm = pl.bpm;
+    plan_image_work(up, i, pl.any_builder);
+    any_general_builder_ = any_general_builder_ || pl.any_builder;
+    headers_[i] = pl.header;
+    headers_pre_[i] = pl.header_pre;
+    headers_post_[i] = pl.header_post;
+    im.header_len = (uint32_t)pl.header.size();
+    // tables to be built: the DHT is written once the statistics are in; reserve the largest it can be
+    if (pl.any_builder) im.header_len = (uint32_t)(pl.header_pre.size() + 4 + (size_t)pl.n_slots * (1 + 16 + 256) + pl.header_post.size());
+    return JPGPU_OK;
+}
+
+// An EncodeAction arrangement (apps/JpegEncode/EncodeAction.cs:38-63): tables 0 and 1, components 1..3 with the luma factors on the
+// first, the four standard Huffman tables or four built ones
+int EncodeBatch::plan_encode_action_image(UploadPlan &up, int i, const EncPlan &pl) {
+    const jpgpu_encode_params &p = pl.params;
+    // argument checks of the reference's setters (JpegEncoder.cs:175-184, EncodeAction.cs:19-22)
+    if (p.quality <= 0 || p.quality > 100) return fail(JPGPU_ERR_ARGUMENT, "Specified argument was out of the range of valid values. (Parameter 'quality')");
+    if ((p.luma_h != 1 && p.luma_h != 2 && p.luma_h != 4) || (p.luma_v != 1 && p.luma_v != 2 && p.luma_v != 4))
+        return fail(JPGPU_ERR_ARGUMENT, "Subsampling factor can only be 1, 2 or 4.");
+    if (p.width <= 0 || p.height <= 0 || p.width > 65535 || p.height > 65535) return fail(JPGPU_ERR_ARGUMENT, "image dimensions out of range");
+    if (p.components != 1 && p.components != 3) return fail(JPGPU_ERR_NOT_SUPPORTED, "1 or 3 components are supported.");
+    if (p.input_rgb && p.components != 3) return fail(JPGPU_ERR_ARGUMENT, "RGB input needs 3 components.");
+    if (p.input_rgb < 0 || p.input_rgb > 2) return fail(JPGPU_ERR_ARGUMENT, "input_rgb is 0 (samples), 1 (R,G,B) or 2 (R,G,B,A).");
+    if (p.restart_interval < 0 || p.restart_interval > 65535) return fail(JPGPU_ERR_ARGUMENT, "restart interval out of range (0..65535)");
+    DevEncImage &im = images_[i];
+    memset(&im, 0, sizeof im);
+    im.coef_off = up.coef_off;
+    im.width = (uint32_t)p.width;
+    im.height = (uint32_t)p.height;
+    const int rc = place_pixels(up, i, p.input_rgb);
+    if (rc != JPGPU_OK) return rc;
+    im.in_components = p.input_rgb == 2 ? 4u : (uint32_t)p.components;  // (2: Rgba32 pixels, the alpha byte stepped over)
+    im.components = (uint32_t)p.components;
+    im.luma_h = (uint32_t)p.luma_h;
+    im.luma_v = (uint32_t)p.luma_v;
+    im.bpm = im.luma_h * im.luma_v + (im.components == 3 ? 2 : 0);
+    im.input_rgb = p.input_rgb ? 1 : 0;
+    im.restart_interval = (uint32_t)p.restart_interval;
+    if (p.optimize_coding) {
+        most_optimal_[i] = p.optimize_coding == 2;  // JpegEncoder.MostOptimalCoding
+        optimized_.push_back(i);
+        im.table_base = 4u * (uint32_t)optimized_.size();  // tables 0..3 are the standard ones
+    }
+    rgb_ycc_factors(im.r2y);
+    if (pl.legacy_has_quant) {  // the described form of SetQuantizationTable(0 / 1)
+        memcpy(im.quant, pl.legacy_quant, sizeof im.quant);
+    } else {
         scale_by_quality(kStdLum, p.quality, im.quant[0]);
         scale_by_quality(kStdChr, p.quality, im.quant[1]);
-        px_off = align_up64(px_off + (uint64_t)im.width * im.height * im.in_components, 256);
-        coef_off += im.total_blocks;
-        const uint32_t total_mcus = im.mcus_per_line * im.mcus_per_column;
-        if ((smp_off >> 8) > 0xFFFFFFFFull) return fail(JPGPU_ERR_OUT_OF_MEMORY, "sample buffer beyond 1 TiB");
-        im.smp_off_256 = (uint32_t)(smp_off >> 8);
-        // (an image fdct_fused_kernel takes has no gathered samples: 4.2 GB less per 256 x 4K)
-        if (!enc_fused_enabled() || enc_image_fused_shape(im) == 0)
-            smp_off = align_up64(smp_off + (uint64_t)total_mcus * enc_sample_bytes_per_mcu(im.luma_h, im.luma_v, im.components), 256);
-        for (uint32_t f = 0; f < total_mcus; f += kEncMcusPerWg) work_mcu.push_back({(uint32_t)i, f});
-        im.work_first = (uint32_t)work_blk.size();
-        for (uint32_t f = 0; f < im.n_units; f += 256) work_blk.push_back({(uint32_t)i, f});
-        if (p.optimize_coding)
-            for (uint32_t f = 0; f < im.total_blocks; f += 256) work_stat.push_back({(uint32_t)i, f});
-
-        // ---- marker segments, in the order Encode() writes them (JpegEncoder.cs:261-280)
-        std::vector<uint8_t> &h = headers_[i];
-        const int ncomp = (int)im.components;
-        put_marker(h, 0xD8);
-        put_marker(h, 0xDB);  // WriteQuantizationTables (:305-335): ONE segment, tables in SetQuantizationTable order
-        put_length(h, (uint16_t)(2 * 65));
-        for (int t = 0; t < 2; t++) {
-            h.push_back((uint8_t)t);  // precision 0 << 4 | identifier
-            for (int k = 0; k < 64; k++) h.push_back((uint8_t)im.quant[t][k]);
-        }
-        if (im.restart_interval) {  // DRI in front of SOF0: the reference's decoder latches it there even without Identify()
-            put_marker(h, 0xDD);
-            put_length(h, 2);
-            h.push_back((uint8_t)(im.restart_interval >> 8));
-            h.push_back((uint8_t)im.restart_interval);
-        }
-        put_marker(h, 0xC0);  // WriteStartOfFrame (:353-386)
-        put_length(h, (uint16_t)(6 + 3 * ncomp));
-        h.push_back(8);
-        h.push_back((uint8_t)(im.height >> 8));
-        h.push_back((uint8_t)im.height);
-        h.push_back((uint8_t)(im.width >> 8));
-        h.push_back((uint8_t)im.width);
-        h.push_back((uint8_t)ncomp);
-        for (int c = 0; c < ncomp; c++) {
-            h.push_back((uint8_t)(c + 1));
-            h.push_back(c == 0 ? (uint8_t)((im.luma_h << 4) | im.luma_v) : (uint8_t)0x11);
-            h.push_back(c == 0 ? 0 : 1);
-        }
-        headers_pre_[i] = h;
-        put_marker(h, 0xC4);  // WriteHuffmanTables (:336-352): ONE segment, tables in SetHuffmanTable order
-        int total = 0;
-        for (int t = 0; t < 4; t++) total += 1 + 16 + kStd[t].count;
-        put_length(h, (uint16_t)total);
-        for (int t = 0; t < 4; t++) {
-            h.push_back((uint8_t)(((t & 1) << 4) | (t >> 1)));
-            for (int l = 0; l < 16; l++) h.push_back(kStd[t].lengths[l]);
-            for (int k = 0; k < kStd[t].count; k++) h.push_back(kStd[t].values[k]);
-        }
-        const size_t sos_at = h.size();
-        put_marker(h, 0xDA);  // WriteStartOfScan (:387-413)
-        put_length(h, (uint16_t)(1 + 2 * ncomp + 3));
-        h.push_back((uint8_t)ncomp);
-        for (int c = 0; c < ncomp; c++) {
-            h.push_back((uint8_t)(c + 1));
-            h.push_back(c == 0 ? 0x00 : 0x11);
-        }
-        h.push_back(0);
-        h.push_back(63);
-        h.push_back(0);
-        headers_post_[i].assign(h.begin() + (long)sos_at, h.end());
-        im.header_len = (uint32_t)h.size();
-        // optimizeCoding: the DHT is written once the statistics are in; reserve the largest it can be (4 x 256 symbols)
-        if (im.table_base != 0) im.header_len = (uint32_t)(headers_pre_[i].size() + 4 + 4 * (1 + 16 + 256) + headers_post_[i].size());
-        if (plans[(size_t)i].legacy_has_quant)  // the described form of SetQuantizationTable(0 / 1): as set_quantization_table patches them in
-            for (int t = 0; t < 2; t++)
-                for (int k = 0; k < 64; k++) {
-                    const size_t at = 2 + 2 + 2 + (size_t)t * 65 + 1 + (size_t)k;
-                    im.quant[t][k] = plans[(size_t)i].legacy_quant[t][k];
-                    headers_[i][at] = headers_pre_[i][at] = (uint8_t)im.quant[t][k];
-                }
     }
-    if (device) {  // (every argument check is behind us, nothing has been enqueued)
-        const int rc = check_device_pixels(pixels);
-        if (rc != JPGPU_OK) return rc;
+    plan_image_work(up, i, p.optimize_coding != 0);
+    if ((up.smp_off >> 8) > 0xFFFFFFFFull) return fail(JPGPU_ERR_OUT_OF_MEMORY, "sample buffer beyond 1 TiB");
+    im.smp_off_256 = (uint32_t)(up.smp_off >> 8);
+    // (an image fdct_fused_kernel takes has no gathered samples: 4.2 GB less per 256 x 4K)
+    if (!enc_fused_enabled() || enc_image_fused_shape(im) == 0)
+        up.smp_off = align_up64(up.smp_off + (uint64_t)im.mcus_per_line * im.mcus_per_column * enc_sample_bytes_per_mcu(im.luma_h, im.luma_v, im.components), 256);
+
+    // the marker segments Encode() writes, from EncodeAction's fixed lists; the four standard tables until the statistics say otherwise
+    const EncSegmentQuant quant[2] = {{0, im.quant[0]}, {1, im.quant[1]}};
+    EncSegmentComponent comp[3];
+    for (int c = 0; c < (int)im.components; c++) {
+        const uint8_t t = c == 0 ? 0 : 1;
+        comp[c] = {(uint8_t)(c + 1), (uint8_t)(c == 0 ? im.luma_h : 1), (uint8_t)(c == 0 ? im.luma_v : 1), t, t, t};
     }
-    pixels_on_device_ = device;
-    total_blocks_ = coef_off;
-    n_work_mcu_ = (int)work_mcu.size();
-    n_work_blk_ = (int)work_blk.size();
-    n_work_stat_ = (int)work_stat.size();
+    write_marker_segments(quant, 2, comp, (int)im.components, p.width, p.height, p.restart_interval, &headers_pre_[i], &headers_post_[i]);
+    std::vector<uint8_t> body;
+    for (int t = 0; t < 4; t++) {
+        body.push_back(std_tc_th(t));
+        append_std_dht(t, &body);
+    }
+    assemble_header(headers_pre_[i], body, headers_post_[i], &headers_[i]);
+    im.header_len = (uint32_t)headers_[i].size();
+    // optimizeCoding: the DHT is written once the statistics are in; reserve the largest it can be (4 x 256 symbols)
+    if (im.table_base != 0) im.header_len = (uint32_t)(headers_pre_[i].size() + 4 + 4 * (1 + 16 + 256) + headers_post_[i].size());
+    return JPGPU_OK;
+}
 
-    // bits_emit_kernel's issue order: the work list's entries by (place inside the image, image)
-    std::vector<uint32_t> work_order(work_blk.size());
-    for (size_t k = 0; k < work_order.size(); k++) work_order[k] = (uint32_t)k;
-    std::stable_sort(work_order.begin(), work_order.end(), [&](uint32_t a, uint32_t b) { return work_blk[a].first < work_blk[b].first; });
+// bits_emit_kernel's issue order, and the Huffman tables of the upload: the four standard ones, four per EncodeAction image with
+// built tables (filled in by encode()), eight slots per described image with its given tables known now
+void EncodeBatch::place_table_slots(UploadPlan &up) {
+    // the work list's entries by (place inside the image, image)
+    up.work_order.resize(up.work_blk.size());
+    for (size_t k = 0; k < up.work_order.size(); k++) up.work_order[k] = (uint32_t)k;
+    std::stable_sort(up.work_order.begin(), up.work_order.end(), [&](uint32_t a, uint32_t b) { return up.work_blk[a].first < up.work_blk[b].first; });
 
-    std::vector<EncHuffTable> tables(4 + 4 * optimized_.size() + 8 * general_.size());
-    memset(tables.data(), 0, tables.size() * sizeof(EncHuffTable));
-    for (int t = 0; t < 4; t++) build_enc_table(kStd[t], &tables[t]);
-    for (size_t g = 0; g < general_.size(); g++) {  // a described image: eight slots, the given tables known now
+    up.tables.resize(4 + 4 * optimized_.size() + 8 * general_.size());
+    memset(up.tables.data(), 0, up.tables.size() * sizeof(EncHuffTable));
+    for (int t = 0; t < 4; t++) build_enc_table(kStd[t], &up.tables[t]);
+    for (size_t g = 0; g < general_.size(); g++) {
         layouts_[g].table_base = (uint32_t)(4 + 4 * optimized_.size() + 8 * g);
-        layouts_[g].hist_index = (uint32_t)((size_t)n * 4 * 256 + g * 8 * 256);
+        layouts_[g].hist_index = (uint32_t)(images_.size() * 4 * 256 + g * 8 * 256);
         for (int t = 0; t < general_plans_[g].n_slots; t++)
-            if (general_plans_[g].slots[t].given) tables[layouts_[g].table_base + (size_t)t] = general_plans_[g].slots[t].table;
+            if (general_plans_[g].slots[t].given) up.tables[layouts_[g].table_base + (size_t)t] = general_plans_[g].slots[t].table;
     }
+}
 
+int EncodeBatch::reserve_and_upload(const UploadPlan &up) {
+    const size_t n = images_.size();
     struct Up {
         DevBuffer *buf;
         const void *src;
         size_t bytes, reserve;
     };
     const Up ups[] = {
-        {&d_tables_, tables.data(), tables.size() * sizeof(EncHuffTable), 0},
-        {&d_hist_, nullptr, 0, ((size_t)n * 4 + general_.size() * 8) * 256 * sizeof(uint32_t) + 256},
+        {&d_tables_, up.tables.data(), up.tables.size() * sizeof(EncHuffTable), 0},
+        {&d_hist_, nullptr, 0, (n * 4 + general_.size() * 8) * 256 * sizeof(uint32_t) + 256},
         {&d_layouts_, layouts_.data(), layouts_.size() * sizeof(DevEncLayout), 256},
-        {&d_work_mcu_, work_mcu.data(), work_mcu.size() * sizeof(EncWork), 0},
-        {&d_work_blk_, work_blk.data(), work_blk.size() * sizeof(EncWork), 0},
-        {&d_work_order_, work_order.data(), work_order.size() * sizeof(uint32_t), 16},
-        {&d_work_stat_, work_stat.data(), work_stat.size() * sizeof(EncWork), 16},
-        {&d_pixels_, nullptr, 0, (size_t)px_off + 256},
+        {&d_work_mcu_, up.work_mcu.data(), up.work_mcu.size() * sizeof(EncWork), 0},
+        {&d_work_blk_, up.work_blk.data(), up.work_blk.size() * sizeof(EncWork), 0},
+        {&d_work_order_, up.work_order.data(), up.work_order.size() * sizeof(uint32_t), 16},
+        {&d_work_stat_, up.work_stat.data(), up.work_stat.size() * sizeof(EncWork), 16},
+        {&d_pixels_, nullptr, 0, (size_t)up.px_off + 256},
         {&d_coefs_, nullptr, 0, (size_t)total_blocks_ * 128 + 256},
-        {&d_samples_, nullptr, 0, (size_t)smp_off + 256},
+        {&d_samples_, nullptr, 0, (size_t)up.smp_off + 256},
         {&d_bits_, nullptr, 0, (size_t)total_blocks_ * sizeof(uint32_t) + 256},
-        {&d_bit_off_, nullptr, 0, work_blk.size() * (sizeof(uint64_t) + sizeof(uint32_t)) + 512},  // per workgroup: base (u64) | bits (u32)
-        {&d_raw_bits_, nullptr, 0, (size_t)n * sizeof(uint64_t) + 256},
-        {&d_out_len_, nullptr, 0, (size_t)n * sizeof(uint64_t) + 256},
-        {&d_images_, nullptr, 0, (size_t)n * sizeof(DevEncImage) + 256},
+        {&d_bit_off_, nullptr, 0, up.work_blk.size() * (sizeof(uint64_t) + sizeof(uint32_t)) + 512},  // per workgroup: base (u64) | bits (u32)
+        {&d_raw_bits_, nullptr, 0, n * sizeof(uint64_t) + 256},
+        {&d_out_len_, nullptr, 0, n * sizeof(uint64_t) + 256},
+        {&d_images_, nullptr, 0, n * sizeof(DevEncImage) + 256},
     };
+    hipError_t e;
     for (const Up &u : ups) {
-        if (device && u.buf == &d_pixels_) continue;  // (a device upload copies nothing: E1 reads the caller's memory)
+        if (up.device && u.buf == &d_pixels_) continue;  // (a device upload copies nothing: E1 reads the caller's memory)
         e = u.buf->reserve(std::max(u.bytes, u.reserve));
         if (e != hipSuccess) return hip_fail(e, "hipMalloc");
         if (u.bytes) {
@@ -749,10 +806,10 @@ int EncodeBatch::layout_plans(const uint8_t *const *pixels, const std::vector<En
             if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync");
         }
     }
-    for (int i = 0; i < n && !device; i++) {
+    for (size_t i = 0; i < n && !up.device; i++) {
         const DevEncImage &im = images_[i];
         if (im.width == 0) continue;  // (a refused arrangement)
-        e = hipMemcpyAsync((uint8_t *)d_pixels_.ptr + im.px_off, pixels[i], (size_t)im.width * im.height * im.in_components, hipMemcpyHostToDevice,
+        e = hipMemcpyAsync((uint8_t *)d_pixels_.ptr + im.px_off, up.pixels[i], (size_t)im.width * im.height * im.in_components, hipMemcpyHostToDevice,
                            ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(pixels)");
     }
@@ -768,7 +825,7 @@ int EncodeBatch::set_quantization_table(int i, int identifier, const uint16_t *z
     for (int k = 0; k < 64; k++)
         if (zigzag64[k] == 0 || zigzag64[k] > 255) return fail(JPGPU_ERR_ARGUMENT, "Quantization table elements must be in 1..255 (element precision 0).");
     DevEncImage &im = images_[(size_t)i];
-    // the DQT segment upload() wrote: SOI, FF DB, length, then per table one identifier byte + 64 elements
+    // the DQT segment write_marker_segments wrote: SOI, FF DB, length, then per table one identifier byte + 64 elements
     const size_t at = 2 + 2 + 2 + (size_t)identifier * 65 + 1;
     for (int k = 0; k < 64; k++) {
         im.quant[identifier][k] = zigzag64[k];
@@ -779,24 +836,65 @@ int EncodeBatch::set_quantization_table(int i, int identifier, const uint16_t *z
     return JPGPU_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ encode
+
+// what encode()'s stages hand one another
+struct EncodeBatch::EncodeRun {
+    int n = 0;                                // images
+    const DevEncLayout *layouts = nullptr;    // described images in the upload: their layouts on the device
+    bool any_plain = false;                   // EncodeAction arrangements in the upload
+    std::vector<uint64_t> raw_bits;           // per image, once E2 has counted
+    bool fused_emit = false;                  // bits_emit_kernel has counted AND written the raw streams
+    uint64_t emit_words = 0;                  // emit_kernel's LDS buffer, in words
+    StuffPlan stuff;
+};
+
 int EncodeBatch::encode() {
     hipError_t e = hipSetDevice(ctx_->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const int n = (int)images_.size();
-    if (n == 0) return JPGPU_OK;
+    EncodeRun r;
+    r.n = (int)images_.size();
+    if (r.n == 0) return JPGPU_OK;
     for (hipEvent_t &ev : ev_)
         if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return hip_fail(e, "hipEventCreate");
-    // image descriptors (raw / output offsets are filled in once the bit counts are known)
-    e = hipMemcpyAsync(d_images_.ptr, images_.data(), (size_t)n * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
+    r.layouts = layouts_.empty() ? nullptr : (const DevEncLayout *)d_layouts_.ptr;
+    r.any_plain = layouts_.size() < images_.size();
+    r.raw_bits.assign((size_t)r.n, 0);
+    int rc = upload_image_descriptors();
+    if (rc != JPGPU_OK) return rc;
+    (void)hipEventRecord(ev_[0], ctx_->stream);
+    if ((rc = run_fdct(r)) != JPGPU_OK) return rc;
+    if ((!optimized_.empty() || any_general_builder_) && (rc = build_coding_tables(r)) != JPGPU_OK) return rc;
+    (void)hipEventRecord(ev_[1], ctx_->stream);
+    if ((rc = try_one_pass_emit(r)) != JPGPU_OK) return rc;
+    if (!r.fused_emit && (rc = count_bits_two_kernels(r)) != JPGPU_OK) return rc;  // (ev_[2] is recorded behind whichever kernel counted)
+    if ((rc = plan_stuffing(r)) != JPGPU_OK) return rc;
+    if ((rc = place_headers(r)) != JPGPU_OK) return rc;
+    (void)hipEventRecord(ev_[3], ctx_->stream);
+    if ((rc = emit_and_stuff(r)) != JPGPU_OK) return rc;  // (ev_[4] between E3 and E4, ev_[5] behind E4)
+    encoded_ = true;
+    return JPGPU_OK;
+}
+
+// image descriptors (raw / output offsets are filled in once the bit counts are known)
+int EncodeBatch::upload_image_descriptors() {
+    hipError_t e = hipMemcpyAsync(d_images_.ptr, images_.data(), images_.size() * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(images)");
+    if (n_work_blk_ == 0) {  // nothing but refused arrangements: no kernel counts anything, the streams are empty
+        e = hipMemsetAsync(d_raw_bits_.ptr, 0, images_.size() * sizeof(uint64_t), ctx_->stream);
+        if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(bit counts)");
+    }
+    return JPGPU_OK;
+}
+
+// E1: pixels -> quantised blocks
+int EncodeBatch::run_fdct(const EncodeRun &r) {
     size_t max_record = 0;
     uint32_t fused_shapes = 0;
     bool any_other = false, any_other_planar = false;
     // (a device upload: DevEncImage.px_off is the caller's address itself)
     const uint8_t *pixel_base = pixels_on_device_ ? nullptr : (const uint8_t *)d_pixels_.ptr;
     const bool no_fused = !enc_fused_enabled();
-    const DevEncLayout *layouts = layouts_.empty() ? nullptr : (const DevEncLayout *)d_layouts_.ptr;  // described images in the upload
-    const bool any_plain = layouts_.size() < images_.size();
     for (const DevEncImage &im : images_) {
         if (im.layout != 0) continue;  // (enc_general_fdct_kernel)
         max_record = std::max(max_record, enc_sample_bytes_per_mcu(im.luma_h, im.luma_v, im.components));
@@ -804,261 +902,224 @@ int EncodeBatch::encode() {
         if (shape != 0) fused_shapes |= 1u << shape;
         else (im.px_planar ? any_other_planar : any_other) = true;
     }
-    if (n_work_blk_ == 0) {  // nothing but refused arrangements: no kernel counts anything, the streams are empty
-        e = hipMemsetAsync(d_raw_bits_.ptr, 0, (size_t)n * sizeof(uint64_t), ctx_->stream);
-        if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(bit counts)");
-    }
-    (void)hipEventRecord(ev_[0], ctx_->stream);
-    e = launch_fdct_quant(ctx_->stream, pixel_base, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_mcu_.ptr, n_work_mcu_,
-                          (uint8_t *)d_samples_.ptr, (int16_t *)d_coefs_.ptr, max_record, fused_shapes, any_other, any_other_planar);
+    hipError_t e = launch_fdct_quant(ctx_->stream, pixel_base, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_mcu_.ptr, n_work_mcu_,
+                                     (uint8_t *)d_samples_.ptr, (int16_t *)d_coefs_.ptr, max_record, fused_shapes, any_other, any_other_planar);
     if (e != hipSuccess) return hip_fail(e, "fdct_quant_kernel");
-    if (layouts) {
-        e = launch_fdct_quant_general(ctx_->stream, pixel_base, (const DevEncImage *)d_images_.ptr, layouts,
-                                          (const EncWork *)d_work_mcu_.ptr, n_work_mcu_, (int16_t *)d_coefs_.ptr);
+    if (r.layouts) {
+        e = launch_fdct_quant_general(ctx_->stream, pixel_base, (const DevEncImage *)d_images_.ptr, r.layouts, (const EncWork *)d_work_mcu_.ptr, n_work_mcu_,
+                                      (int16_t *)d_coefs_.ptr);
         if (e != hipSuccess) return hip_fail(e, "enc_general_fdct_kernel");
     }
-    if (!optimized_.empty() || any_general_builder_) {
-        // optimizeCoding: BuildHuffmanTables (:491-550) -- statistics on the device, JpegHuffmanEncodingTableBuilder.Build on the host
-        const size_t n_hist = ((size_t)n * 4 + general_.size() * 8) * 256;
-        e = hipMemsetAsync(d_hist_.ptr, 0, n_hist * sizeof(uint32_t), ctx_->stream);
-        if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(statistics)");
-        e = launch_block_stats(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_stat_.ptr, n_work_stat_,
-                               (const int16_t *)d_coefs_.ptr, (uint32_t *)d_hist_.ptr, any_general_builder_ ? layouts : nullptr, !optimized_.empty());
-        if (e != hipSuccess) return hip_fail(e, "block_stats_kernel");
-        std::vector<uint32_t> hist(n_hist);
-        e = hipMemcpyAsync(hist.data(), d_hist_.ptr, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx_->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpy(statistics)");
-        std::vector<EncHuffTable> built(4 * optimized_.size());
-        memset(built.data(), 0, built.size() * sizeof(EncHuffTable));
-        for (size_t k = 0; k < optimized_.size(); k++) {
-            const int i = optimized_[k];
-            std::vector<uint8_t> &h = headers_[i];
-            h = headers_pre_[i];
-            std::vector<uint8_t> body;
-            status_[i] = JPGPU_OK;
-            for (int t = 0; t < 4; t++) {  // every builder of the collection, in SetHuffmanTable order: DC0, AC0, DC1, AC1
-                std::vector<OptimalCode> codes;
-                if (!build_optimal_table(&hist[((size_t)i * 4 + t) * 256], &codes, most_optimal_[i] != 0)) {
-                    status_[i] = JPGPU_ERR_INVALID_OPERATION;  // "No symbol is recorded." (a single-component image: empty chrominance builders)
-                    break;
-                }
-                EncHuffTable &et = built[4 * k + t];
-                for (int sym = 0; sym < 256; sym++) {  // GetCode of a symbol without a code: the table's first code
-                    et.code[sym] = codes[0].code;
-                    et.len[sym] = codes[0].length;
-                }
-                for (const OptimalCode &c : codes) {
-                    et.code[c.symbol] = c.code;
-                    et.len[c.symbol] = c.length;
-                }
-                body.push_back((uint8_t)(((t & 1) << 4) | (t >> 1)));
-                for (int l = 1; l <= 16; l++) {
-                    int count = 0;
-                    for (const OptimalCode &c : codes) count += c.length == l;
-                    body.push_back((uint8_t)count);
-                }
-                for (const OptimalCode &c : codes) body.push_back(c.symbol);
-            }
-            put_marker(h, 0xC4);
-            put_length(h, (uint16_t)body.size());
-            h.insert(h.end(), body.begin(), body.end());
-            h.insert(h.end(), headers_post_[i].begin(), headers_post_[i].end());
-            images_[i].header_len = (uint32_t)h.size();
-        }
-        e = built.empty() ? hipSuccess
-                          : hipMemcpyAsync((EncHuffTable *)d_tables_.ptr + 4, built.data(), built.size() * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(built tables)");
-        // described images: every builder of the collection from the counters of its slot (the components that share a table have
-        // added theirs up there); the given tables keep their bytes; DHT in SetHuffmanTable order
-        std::vector<EncHuffTable> slots(any_general_builder_ ? 8 * general_.size() : 0);
-        for (size_t g = 0; g < general_.size(); g++) {
-            const int i = general_[g];
-            const EncPlan &pl = general_plans_[g];
-            if (!pl.any_builder || pl.status != JPGPU_OK) continue;
-            std::vector<uint8_t> &h = headers_[i];
-            h = headers_pre_[i];
-            std::vector<uint8_t> body;
-            for (int t = 0; t < pl.n_slots; t++) {
-                EncHuffTable &et = slots[8 * g + (size_t)t];
-                body.push_back(pl.slots[t].tc_th);
-                if (pl.slots[t].given) {
-                    et = pl.slots[t].table;
-                    body.insert(body.end(), pl.slots[t].dht.begin(), pl.slots[t].dht.end());
-                    continue;
-                }
-                std::vector<OptimalCode> codes;
-                if (!build_optimal_table(&hist[layouts_[g].hist_index + (size_t)t * 256], &codes, pl.most_optimal != 0)) {
-                    status_[i] = JPGPU_ERR_INVALID_OPERATION;  // (resolve_encode_description has seen every such case: not reached)
-                    messages_[i] = "No symbol is recorded.";
-                    break;
-                }
-                for (int sym = 0; sym < 256; sym++) {
-                    et.code[sym] = codes[0].code;
-                    et.len[sym] = codes[0].length;
-                }
-                for (const OptimalCode &c : codes) {
-                    et.code[c.symbol] = c.code;
-                    et.len[c.symbol] = c.length;
-                }
-                for (int l = 1; l <= 16; l++) {
-                    int count = 0;
-                    for (const OptimalCode &c : codes) count += c.length == l;
-                    body.push_back((uint8_t)count);
-                }
-                for (const OptimalCode &c : codes) body.push_back(c.symbol);
-            }
-            put_marker(h, 0xC4);
-            put_length(h, (uint16_t)body.size());
-            h.insert(h.end(), body.begin(), body.end());
-            h.insert(h.end(), headers_post_[i].begin(), headers_post_[i].end());
-            images_[i].header_len = (uint32_t)h.size();
-            e = hipMemcpyAsync((EncHuffTable *)d_tables_.ptr + layouts_[g].table_base, &slots[8 * g], 8 * sizeof(EncHuffTable), hipMemcpyHostToDevice,
-                               ctx_->stream);
-            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(built tables)");
-        }
-        if (any_general_builder_) {  // (`slots` leaves scope; the EncodeAction images' upload is as it always was)
-            e = hipStreamSynchronize(ctx_->stream);
-            if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(built tables)");
+    return JPGPU_OK;
+}
+
+// One image's tables from its counters, and its SOI..SOS with the DHT they make: every builder of the collection in SetHuffmanTable
+// order -- an EncodeAction image's four (DC0, AC0, DC1, AC1; `described` null), or a described image's slots, of which the given
+// ones keep their bytes.  false: a builder without symbols, the tables behind it not built (what that means is the caller's).
+bool EncodeBatch::build_image_tables(int i, const EncPlan *described, const uint32_t *counters, bool most_optimal, EncHuffTable *tables) {
+    std::vector<uint8_t> body;
+    bool built = true;
+    for (int t = 0; t < (described ? described->n_slots : 4); t++) {
+        const EncPlan::Slot *slot = described ? &described->slots[t] : nullptr;
+        std::vector<OptimalCode> codes;
+        if (slot && slot->given) {
+            tables[t] = slot->table;
+            body.push_back(slot->tc_th);
+            body.insert(body.end(), slot->dht.begin(), slot->dht.end());
+        } else if (build_optimal_table(counters + (size_t)t * 256, &codes, most_optimal)) {
+            body.push_back(slot ? slot->tc_th : std_tc_th(t));
+            optimal_codes_to_table(codes, &tables[t], &body);
+        } else {
+            built = false;
+            break;
         }
     }
-    (void)hipEventRecord(ev_[1], ctx_->stream);
-    std::vector<uint64_t> raw_bits((size_t)n);
-    // E2 + E3 as one pass (bits_emit_kernel): the raw streams are placed BEFORE their sizes are known -- a slot of the worst case
-    // per image (every coefficient a 32-bit field: 256 bytes per block), of which only the stream itself is ever touched
-    // The chains are per image: a batch of ONE image is one chain, as long as the image has workgroups, and runs at the speed the
-    // look-back travels (one 8192 x 8192 canvas: 0.13 ms against the two kernels' 0.107); from two images on the one pass wins.
-    bool fused_emit = false;
-    bool try_fused = enc_fused_emit_enabled() && !any_restart_ && emit_hint_ != 0xFFFFFFFFu && n >= 2 && layouts_.empty();  // (bits_emit_kernel: EncodeAction arrangements)
+    assemble_header(headers_pre_[i], body, headers_post_[i], &headers_[i]);
+    images_[i].header_len = (uint32_t)headers_[i].size();
+    return built;
+}
+
+// optimizeCoding: BuildHuffmanTables (:491-550) -- statistics on the device, JpegHuffmanEncodingTableBuilder.Build on the host
+int EncodeBatch::build_coding_tables(const EncodeRun &r) {
+    const size_t n_hist = ((size_t)r.n * 4 + general_.size() * 8) * 256;
+    hipError_t e = hipMemsetAsync(d_hist_.ptr, 0, n_hist * sizeof(uint32_t), ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(statistics)");
+    e = launch_block_stats(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_stat_.ptr, n_work_stat_, (const int16_t *)d_coefs_.ptr,
+                           (uint32_t *)d_hist_.ptr, any_general_builder_ ? r.layouts : nullptr, !optimized_.empty());
+    if (e != hipSuccess) return hip_fail(e, "block_stats_kernel");
+    std::vector<uint32_t> hist(n_hist);
+    e = hipMemcpyAsync(hist.data(), d_hist_.ptr, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx_->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy(statistics)");
+    std::vector<EncHuffTable> built(4 * optimized_.size());
+    memset(built.data(), 0, built.size() * sizeof(EncHuffTable));
+    for (size_t k = 0; k < optimized_.size(); k++) {
+        const int i = optimized_[k];
+        status_[i] = JPGPU_OK;
+        // "No symbol is recorded." (a single-component image: empty chrominance builders)
+        if (!build_image_tables(i, nullptr, &hist[(size_t)i * 4 * 256], most_optimal_[i] != 0, &built[4 * k])) status_[i] = JPGPU_ERR_INVALID_OPERATION;
+    }
+    e = built.empty() ? hipSuccess
+                      : hipMemcpyAsync((EncHuffTable *)d_tables_.ptr + 4, built.data(), built.size() * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(built tables)");
+    // described images: every builder of the collection from the counters of its slot (the components that share a table have
+    // added theirs up there)
+    std::vector<EncHuffTable> slots(any_general_builder_ ? 8 * general_.size() : 0);
+    for (size_t g = 0; g < general_.size(); g++) {
+        const int i = general_[g];
+        const EncPlan &pl = general_plans_[g];
+        if (!pl.any_builder || pl.status != JPGPU_OK) continue;
+        if (!build_image_tables(i, &pl, &hist[layouts_[g].hist_index], pl.most_optimal != 0, &slots[8 * g])) {
+            status_[i] = JPGPU_ERR_INVALID_OPERATION;  // (resolve_encode_description has seen every such case: not reached)
+            messages_[i] = "No symbol is recorded.";
+        }
+        e = hipMemcpyAsync((EncHuffTable *)d_tables_.ptr + layouts_[g].table_base, &slots[8 * g], 8 * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
+        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(built tables)");
+    }
+    if (any_general_builder_) {  // (`slots` leaves scope; the EncodeAction images' upload is as it always was)
+        e = hipStreamSynchronize(ctx_->stream);
+        if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(built tables)");
+    }
+    return JPGPU_OK;
+}
+
+// E2 + E3 as one pass (bits_emit_kernel): the raw streams are placed BEFORE their sizes are known -- a slot of the worst case
+// per image (every coefficient a 32-bit field: 256 bytes per block), of which only the stream itself is ever touched
+// The chains are per image: a batch of ONE image is one chain, as long as the image has workgroups, and runs at the speed the
+// look-back travels (one 8192 x 8192 canvas: 0.13 ms against the two kernels' 0.107); from two images on the one pass wins.
+int EncodeBatch::try_one_pass_emit(EncodeRun &r) {
+    // (bits_emit_kernel: EncodeAction arrangements)
+    if (!enc_fused_emit_enabled() || any_restart_ || emit_hint_ == 0xFFFFFFFFu || r.n < 2 || !layouts_.empty()) return JPGPU_OK;
     uint64_t slot = 0;
     const size_t chain_bytes = 256 + enc_chain_bytes(n_work_blk_);  // control words | one record per workgroup
-    if (try_fused) {
-        for (DevEncImage &im : images_) {
-            im.raw_off = slot;
-            slot = align_up64(slot + (uint64_t)im.total_blocks * 256 + 64, 256);
-        }
-        // The worst case is ~50 x the streams themselves (51 GB per 1024 x 4K 4:2:0 where the two kernels size ~1 GB from the counts)
-        // and d_raw_ never shrinks: the slots may take a third of what the device has free, no more -- the finished streams, the
-        // chunk counts and the next upload's buffers are reserved behind them, and a batch that used to encode must not fail there
-        // because this one grabbed the rest.  Beyond that the two kernels run.
-        size_t free_b = 0, total_b = 0;
-        e = (size_t)slot + 256 <= d_raw_.cap ? hipSuccess : hipMemGetInfo(&free_b, &total_b);
-        if (e == hipSuccess && (size_t)slot + 256 > d_raw_.cap && (size_t)slot + 256 > free_b / 3) e = hipErrorOutOfMemory;
-        if (e == hipSuccess) e = d_raw_.reserve((size_t)slot + 256);
-        if (e == hipSuccess) e = d_chain_.reserve(chain_bytes + 256);
-        if (e != hipSuccess) {  // no room for the worst-case slots: the two kernels size the raw streams from the counts
-            (void)hipGetLastError();
-            emit_hint_ = 0xFFFFFFFFu;
-            try_fused = false;
-        }
+    for (DevEncImage &im : images_) {
+        im.raw_off = slot;
+        slot = align_up64(slot + (uint64_t)im.total_blocks * 256 + 64, 256);
     }
-    if (try_fused) {
-        one_pass_emits_++;
-        e = hipMemsetAsync(d_chain_.ptr, 0, chain_bytes, ctx_->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_images_.ptr, images_.data(), (size_t)n * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(images)");
-        e = launch_bits_emit(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_blk_.ptr, n_work_blk_, (const EncHuffTable *)d_tables_.ptr,
-                             (const int16_t *)d_coefs_.ptr, (uint8_t *)d_chain_.ptr + 256, (uint32_t *)d_chain_.ptr, (uint8_t *)d_raw_.ptr, (uint64_t *)d_raw_bits_.ptr,
-                             emit_hint_ ? emit_hint_ : 4096u, (const uint32_t *)d_work_order_.ptr);
-        if (e != hipSuccess) return hip_fail(e, "bits_emit_kernel");
-        (void)hipEventRecord(ev_[2], ctx_->stream);
-        uint32_t ctl[2] = {0, 0};
-        e = hipMemcpyAsync(raw_bits.data(), d_raw_bits_.ptr, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ctl, d_chain_.ptr, sizeof ctl, hipMemcpyDeviceToHost, ctx_->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpy(bit counts)");
-        fused_emit = ctl[1] == 0;
-        if (!fused_emit) {  // a stretch beyond the LDS buffer, or a wait that ran out: this upload takes the two kernels from here on
-            emit_hint_ = 0xFFFFFFFFu;
-            fused_emit_fallbacks_++;
-        }
+    // The worst case is ~50 x the streams themselves (51 GB per 1024 x 4K 4:2:0 where the two kernels size ~1 GB from the counts)
+    // and d_raw_ never shrinks: the slots may take a third of what the device has free, no more -- the finished streams, the
+    // chunk counts and the next upload's buffers are reserved behind them, and a batch that used to encode must not fail there
+    // because this one grabbed the rest.  Beyond that the two kernels run.
+    size_t free_b = 0, total_b = 0;
+    hipError_t e = (size_t)slot + 256 <= d_raw_.cap ? hipSuccess : hipMemGetInfo(&free_b, &total_b);
+    if (e == hipSuccess && (size_t)slot + 256 > d_raw_.cap && (size_t)slot + 256 > free_b / 3) e = hipErrorOutOfMemory;
+    if (e == hipSuccess) e = d_raw_.reserve((size_t)slot + 256);
+    if (e == hipSuccess) e = d_chain_.reserve(chain_bytes + 256);
+    if (e != hipSuccess) {  // no room for the worst-case slots: the two kernels size the raw streams from the counts
+        (void)hipGetLastError();
+        emit_hint_ = 0xFFFFFFFFu;
+        return JPGPU_OK;
     }
-    if (!fused_emit) {
+    one_pass_emits_++;
+    e = hipMemsetAsync(d_chain_.ptr, 0, chain_bytes, ctx_->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_images_.ptr, images_.data(), (size_t)r.n * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(images)");
+    e = launch_bits_emit(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_blk_.ptr, n_work_blk_, (const EncHuffTable *)d_tables_.ptr,
+                         (const int16_t *)d_coefs_.ptr, (uint8_t *)d_chain_.ptr + 256, (uint32_t *)d_chain_.ptr, (uint8_t *)d_raw_.ptr, (uint64_t *)d_raw_bits_.ptr,
+                         emit_hint_ ? emit_hint_ : 4096u, (const uint32_t *)d_work_order_.ptr);
+    if (e != hipSuccess) return hip_fail(e, "bits_emit_kernel");
+    (void)hipEventRecord(ev_[2], ctx_->stream);
+    uint32_t ctl[2] = {0, 0};
+    e = hipMemcpyAsync(r.raw_bits.data(), d_raw_bits_.ptr, (size_t)r.n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctl, d_chain_.ptr, sizeof ctl, hipMemcpyDeviceToHost, ctx_->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy(bit counts)");
+    r.fused_emit = ctl[1] == 0;
+    if (!r.fused_emit) {  // a stretch beyond the LDS buffer, or a wait that ran out: this upload takes the two kernels from here on
+        emit_hint_ = 0xFFFFFFFFu;
+        fused_emit_fallbacks_++;
+    }
+    return JPGPU_OK;
+}
+
+// E2 as its own kernel (E3 follows the stuffing stage's layout: emit_and_stuff)
+int EncodeBatch::count_bits_two_kernels(EncodeRun &r) {
     uint32_t *wg_bits = reinterpret_cast<uint32_t *>((uint8_t *)d_bit_off_.ptr + (((size_t)n_work_blk_ * sizeof(uint64_t) + 255) & ~(size_t)255));
-    e = launch_block_bits(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_blk_.ptr, n_work_blk_,
-                          (const EncHuffTable *)d_tables_.ptr, (const int16_t *)d_coefs_.ptr, (uint32_t *)d_bits_.ptr, n, wg_bits, (uint64_t *)d_bit_off_.ptr,
-                          (uint64_t *)d_raw_bits_.ptr, layouts, any_plain);
+    hipError_t e = launch_block_bits(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_blk_.ptr, n_work_blk_,
+                                     (const EncHuffTable *)d_tables_.ptr, (const int16_t *)d_coefs_.ptr, (uint32_t *)d_bits_.ptr, r.n, wg_bits,
+                                     (uint64_t *)d_bit_off_.ptr, (uint64_t *)d_raw_bits_.ptr, r.layouts, r.any_plain);
     if (e != hipSuccess) return hip_fail(e, "block_bits_kernel");
     (void)hipEventRecord(ev_[2], ctx_->stream);
     // the sizes of the raw and finished streams depend on the data: one host round trip
-    e = hipMemcpyAsync(raw_bits.data(), d_raw_bits_.ptr, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
+    e = hipMemcpyAsync(r.raw_bits.data(), d_raw_bits_.ptr, (size_t)r.n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy(bit counts)");
-    }
-    std::vector<EncWork> work_chunk;
-    uint64_t raw_off = 0, out_off = 0;
-    uint32_t chunk_off = 0;
+    return JPGPU_OK;
+}
+
+// where the stuffing stage reads and writes, E3's LDS buffer, and the buffers both need
+int EncodeBatch::plan_stuffing(EncodeRun &r) {
     // E3's LDS buffer: twice the largest average stretch a workgroup (256 blocks or restart intervals) of any image writes,
     // in steps of 4 KB -- the smaller it is the more workgroups share a CU; a workgroup whose stretch does not fit falls back
     // to atomics in HBM (launch_emit clamps to 8-32 KB).  Images whose AVERAGE stretch is beyond 32 KB (restart intervals of
     // several MCUs: every lane then writes a stretch of its own and the atomics do not collide) do not count; a batch of
     // nothing else asks for no LDS at all.
-    uint64_t emit_words = 0;
-    for (int i = 0; i < n; i++) {
-        DevEncImage &im = images_[i];
-        const uint64_t raw_len = (raw_bits[i] + 7) / 8;
-        const uint64_t wgs = ((uint64_t)im.n_units + 255) / 256;
-        const uint64_t avg_words = raw_bits[i] / 32 / std::max<uint64_t>(wgs, 1) + 1;
-        if (avg_words <= kEmitLdsWordsMax) emit_words = std::max<uint64_t>(emit_words, 2 * avg_words);
-        if (!fused_emit) im.raw_off = raw_off;  // (the one-pass form has placed and written the raw streams already)
-        im.out_off = out_off;
-        im.chunk_off = chunk_off;
-        const uint32_t chunks = (uint32_t)((raw_len + kEncStuffChunk - 1) / kEncStuffChunk);
-        for (uint32_t c = 0; c < std::max(chunks, 1u); c++) work_chunk.push_back({(uint32_t)i, c});
-        chunk_off += std::max(chunks, 1u);
-        raw_off = align_up64(raw_off + raw_len + 64, 256);
-        // every byte may need stuffing; two marker bytes per restart interval
-        out_off = align_up64(out_off + im.header_len + 2 * raw_len + 2 + 64 + (im.restart_interval ? 2 * (uint64_t)im.n_units : 0), 256);
+    for (int i = 0; i < r.n; i++) {
+        const uint64_t wgs = ((uint64_t)images_[i].n_units + 255) / 256;
+        const uint64_t avg_words = r.raw_bits[i] / 32 / std::max<uint64_t>(wgs, 1) + 1;
+        if (avg_words <= kEmitLdsWordsMax) r.emit_words = std::max<uint64_t>(r.emit_words, 2 * avg_words);
     }
     // the next encode() of this upload sizes bits_emit_kernel's LDS buffer like emit_kernel's (no stretch would fit: never again)
-    if (emit_hint_ != 0xFFFFFFFFu) emit_hint_ = emit_words == 0 ? 0xFFFFFFFFu : (uint32_t)std::min<uint64_t>((emit_words + 1023) & ~1023ull, kEmitLdsWordsMax);
-    n_work_chunk_ = (int)work_chunk.size();
-    out_cap_ = out_off;
+    if (emit_hint_ != 0xFFFFFFFFu) emit_hint_ = r.emit_words == 0 ? 0xFFFFFFFFu : (uint32_t)std::min<uint64_t>((r.emit_words + 1023) & ~1023ull, kEmitLdsWordsMax);
+    // (the one-pass form has placed and written the raw streams already)
+    r.stuff = plan_stuffing_layout(images_.data(), r.raw_bits.data(), r.n, !r.fused_emit);
+    const size_t raw_bytes = (size_t)r.stuff.raw_bytes;
+    n_work_chunk_ = (int)r.stuff.work_chunk.size();
+    out_cap_ = r.stuff.out_bytes;
     const struct {
         DevBuffer *buf;
         size_t bytes;
-    } grow[] = {{&d_raw_, fused_emit ? 0 : (size_t)raw_off + 256}, {&d_marks_, fused_emit ? 0 : (size_t)raw_off / 8 + 256}, {&d_out_, (size_t)out_off + 256},
-                {&d_chunk_ff_, (size_t)chunk_off * sizeof(uint32_t) + 256}, {&d_work_chunk_, work_chunk.size() * sizeof(EncWork) + 16}};
+    } grow[] = {{&d_raw_, r.fused_emit ? 0 : raw_bytes + 256}, {&d_marks_, r.fused_emit ? 0 : raw_bytes / 8 + 256}, {&d_out_, (size_t)r.stuff.out_bytes + 256},
+                {&d_chunk_ff_, (size_t)r.stuff.chunks * sizeof(uint32_t) + 256}, {&d_work_chunk_, r.stuff.work_chunk.size() * sizeof(EncWork) + 16}};
+    hipError_t e;
     for (const auto &g : grow) {
         e = g.buf->reserve(g.bytes);
         if (e != hipSuccess) return hip_fail(e, "hipMalloc");
     }
-    if (!fused_emit) {  // (emit_kernel ORs into zeroed words; the one-pass form has one writer per word and no restart marks)
-        e = hipMemsetAsync(d_raw_.ptr, 0, (size_t)raw_off + 256, ctx_->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_marks_.ptr, 0, (size_t)raw_off / 8 + 256, ctx_->stream);
+    if (!r.fused_emit) {  // (emit_kernel ORs into zeroed words; the one-pass form has one writer per word and no restart marks)
+        e = hipMemsetAsync(d_raw_.ptr, 0, raw_bytes + 256, ctx_->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_marks_.ptr, 0, raw_bytes / 8 + 256, ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(raw)");
     }
-    // the headers: one upload for the batch, put in front of the streams on the device
+    return JPGPU_OK;
+}
+
+// the headers: one upload for the batch, put in front of the streams on the device
+int EncodeBatch::place_headers(const EncodeRun &r) {
     header_bytes_.clear();
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; i < r.n; i++) {
         images_[i].hdr_off = (uint32_t)header_bytes_.size();
         header_bytes_.insert(header_bytes_.end(), headers_[i].begin(), headers_[i].end());
     }
-    e = d_headers_.reserve(header_bytes_.size() + 16);
+    hipError_t e = d_headers_.reserve(header_bytes_.size() + 16);
     if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    e = hipMemcpyAsync(d_work_chunk_.ptr, work_chunk.data(), work_chunk.size() * sizeof(EncWork), hipMemcpyHostToDevice, ctx_->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_images_.ptr, images_.data(), (size_t)n * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
+    e = hipMemcpyAsync(d_work_chunk_.ptr, r.stuff.work_chunk.data(), r.stuff.work_chunk.size() * sizeof(EncWork), hipMemcpyHostToDevice, ctx_->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_images_.ptr, images_.data(), (size_t)r.n * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_headers_.ptr, header_bytes_.data(), header_bytes_.size(), hipMemcpyHostToDevice, ctx_->stream);
-    if (e == hipSuccess) e = launch_place_headers(ctx_->stream, (const DevEncImage *)d_images_.ptr, n, (const uint8_t *)d_headers_.ptr, (uint8_t *)d_out_.ptr);
+    if (e == hipSuccess) e = launch_place_headers(ctx_->stream, (const DevEncImage *)d_images_.ptr, r.n, (const uint8_t *)d_headers_.ptr, (uint8_t *)d_out_.ptr);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(headers)");
-    (void)hipEventRecord(ev_[3], ctx_->stream);
-    if (!fused_emit) {
+    return JPGPU_OK;
+}
+
+// E3 (unless the one pass has written the raw streams), E4, and the streams' lengths
+int EncodeBatch::emit_and_stuff(const EncodeRun &r) {
+    hipError_t e;
+    if (!r.fused_emit) {
         e = launch_emit(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_blk_.ptr, n_work_blk_, (const EncHuffTable *)d_tables_.ptr,
                         (const int16_t *)d_coefs_.ptr, (const uint32_t *)d_bits_.ptr, (const uint64_t *)d_bit_off_.ptr, (const uint64_t *)d_raw_bits_.ptr,
-                        (uint8_t *)d_raw_.ptr, (uint32_t *)d_marks_.ptr, (uint32_t)std::min<uint64_t>((emit_words + 1023) & ~1023ull, kEmitLdsWordsMax), layouts, any_plain);
+                        (uint8_t *)d_raw_.ptr, (uint32_t *)d_marks_.ptr, (uint32_t)std::min<uint64_t>((r.emit_words + 1023) & ~1023ull, kEmitLdsWordsMax), r.layouts,
+                        r.any_plain);
         if (e != hipSuccess) return hip_fail(e, "emit_kernel");
     }
     (void)hipEventRecord(ev_[4], ctx_->stream);
     e = launch_stuff(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_chunk_.ptr, n_work_chunk_, (const uint64_t *)d_raw_bits_.ptr,
-                     (const uint8_t *)d_raw_.ptr, (const uint32_t *)d_marks_.ptr, (uint32_t *)d_chunk_ff_.ptr, (uint8_t *)d_out_.ptr,
-                     (uint64_t *)d_out_len_.ptr);
+                     (const uint8_t *)d_raw_.ptr, (const uint32_t *)d_marks_.ptr, (uint32_t *)d_chunk_ff_.ptr, (uint8_t *)d_out_.ptr, (uint64_t *)d_out_len_.ptr);
     if (e != hipSuccess) return hip_fail(e, "stuff kernels");
     (void)hipEventRecord(ev_[5], ctx_->stream);
-    out_len_.assign((size_t)n, 0);
-    e = hipMemcpyAsync(out_len_.data(), d_out_len_.ptr, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
+    out_len_.assign((size_t)r.n, 0);
+    e = hipMemcpyAsync(out_len_.data(), d_out_len_.ptr, (size_t)r.n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy(stream lengths)");
-    encoded_ = true;
     return JPGPU_OK;
 }
 

@@ -11,6 +11,46 @@ namespace jpgpu {
 
 void rgb_ycc_factors(int32_t out[8]);
 
+// JpegWriter.WriteMarker (ref: JpegWriter.cs:289-303) and WriteLength (:309-321: the length counts its own two bytes), for the
+// encoder's byte vectors and the optimizer's strings alike
+template <typename Bytes>
+void put_marker(Bytes &o, int m) {
+    o.push_back((typename Bytes::value_type)0xFF);
+    o.push_back((typename Bytes::value_type)m);
+}
+template <typename Bytes>
+void put_length(Bytes &o, uint16_t length) {
+    const uint16_t v = (uint16_t)(length + 2);
+    o.push_back((typename Bytes::value_type)(v >> 8));
+    o.push_back((typename Bytes::value_type)v);
+}
+
+// The marker segments Encode() writes around the Huffman tables (ref: JpegEncoder.cs:261-280), from the lists the caller's Set* and
+// AddComponent calls left: SOI, DQT, (DRI,) SOF0 into *pre, SOS into *post.
+struct EncSegmentQuant {
+    uint8_t identifier;
+    const uint16_t *elements;  // 64, zig-zag, each 1..255 (element precision 0)
+};
+struct EncSegmentComponent {
+    uint8_t id, h, v, tq, td, ta;
+};
+void write_marker_segments(const EncSegmentQuant *quant, int n_quant, const EncSegmentComponent *comp, int n_comp, int width, int height,
+                           int restart_interval, std::vector<uint8_t> *pre, std::vector<uint8_t> *post);
+// ... and the whole of SOI..SOS: pre, the DHT segment of `dht_body` (per table its Tc/Th byte, 16 counts and symbols), post
+void assemble_header(const std::vector<uint8_t> &pre, const std::vector<uint8_t> &dht_body, const std::vector<uint8_t> &post,
+                     std::vector<uint8_t> *header);
+
+// The stuffing stage's (E4, launch_stuff) layout, for the encoder's images and the optimizer's DRI = 0 scans (descriptors in the
+// encoder's image form): from raw_bits[k] and the image's header_len, restart_interval and n_units, where its raw bytes lie
+// (raw_off; left alone unless place_raw: the one-pass emit has placed them already), where its finished stream goes (out_off: the
+// header, then the worst case of the stuffing) and its chunks of kEncStuffChunk raw bytes (chunk_off, at least one per stream).
+struct StuffPlan {
+    std::vector<EncWork> work_chunk;
+    uint64_t raw_bytes = 0, out_bytes = 0;  // what the raw and the output buffer hold, every stream 256-byte aligned
+    uint32_t chunks = 0;
+};
+StuffPlan plan_stuffing_layout(DevEncImage *images, const uint64_t *raw_bits, int n, bool place_raw);
+
 // A jpgpu_encode_description resolved on the host (no device needed): the reference's checks, the marker segments, the by-symbol
 // Huffman tables and the block map of the general kernels -- or the jpgpu_encode_params of the EncodeAction arrangement it is.
 struct EncPlan {
@@ -68,11 +108,34 @@ class EncodeBatch {
 
   private:
     int fail(int status, const std::string &msg);
-    // device = pixels[] are device addresses laid out as pixel_layouts[] says (null: interleaved); else host memory to copy
-    int upload_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans, bool device = false, const int32_t *pixel_layouts = nullptr);
-    int layout_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans, bool device, const int32_t *pixel_layouts);
-    int check_device_pixels(const uint8_t *const *pixels);
     int hip_fail(hipError_t e, const char *what);
+    // device = pixels[] are device addresses laid out as pixel_layouts[] says (null: interleaved); else host memory to copy
+    int upload_params(const uint8_t *const *pixels, const jpgpu_encode_params *params, int n, bool device, const int32_t *pixel_layouts);
+    int upload_descriptions(const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n, bool device, const int32_t *pixel_layouts);
+    int upload_plans(const uint8_t *const *pixels, const std::vector<EncPlan> &plans, bool device, const int32_t *pixel_layouts);
+    // layout_plans is the list of these; what they hand one another is an UploadPlan that lives for the call
+    struct UploadPlan;
+    int layout_plans(UploadPlan &up, const std::vector<EncPlan> &plans);
+    int check_device_arguments(const UploadPlan &up, int n);
+    void reset_upload_state(int n);
+    int plan_described_image(UploadPlan &up, int i, const EncPlan &pl);
+    int plan_encode_action_image(UploadPlan &up, int i, const EncPlan &pl);
+    int place_pixels(const UploadPlan &up, int i, int input_rgb);
+    void plan_image_work(UploadPlan &up, int i, bool statistics);
+    int check_device_pixels(const uint8_t *const *pixels);
+    void place_table_slots(UploadPlan &up);
+    int reserve_and_upload(const UploadPlan &up);
+    // encode() is the list of these; what they hand one another is an EncodeRun that lives for the call
+    struct EncodeRun;
+    int upload_image_descriptors();
+    int run_fdct(const EncodeRun &r);
+    int build_coding_tables(const EncodeRun &r);
+    bool build_image_tables(int i, const EncPlan *described, const uint32_t *counters, bool most_optimal, EncHuffTable *tables);
+    int try_one_pass_emit(EncodeRun &r);
+    int count_bits_two_kernels(EncodeRun &r);
+    int plan_stuffing(EncodeRun &r);
+    int place_headers(const EncodeRun &r);
+    int emit_and_stuff(const EncodeRun &r);
     jpgpu_ctx *ctx_;
     std::vector<DevEncImage> images_;
     std::vector<std::vector<uint8_t>> headers_;        // SOI .. SOS as Encode() writes them (optimizeCoding: rebuilt per encode())

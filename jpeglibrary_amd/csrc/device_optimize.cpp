@@ -13,6 +13,7 @@
 // that changes between the frame header and the scan or after the scan.  Parity of the bytes is unpinned (the reference holds no golden bytes, and
 // .NET's unstable sort decides the order of equal-length symbols in the DHT).
 #include "device_optimize.h"
+#include "device_encode.h"
 
 #include <algorithm>
 #include <cstring>
@@ -323,6 +324,23 @@ bool build_optimal_table(const uint32_t freq[256], std::vector<OptimalCode> *cod
     return true;
 }
 
+void optimal_codes_to_table(const std::vector<OptimalCode> &codes, EncHuffTable *table, std::vector<uint8_t> *dht) {
+    for (int sym = 0; sym < 256; sym++) {
+        table->code[sym] = codes[0].code;
+        table->len[sym] = codes[0].length;
+    }
+    for (const OptimalCode &c : codes) {
+        table->code[c.symbol] = c.code;
+        table->len[c.symbol] = c.length;
+    }
+    for (int l = 1; l <= 16; l++) {
+        int count = 0;
+        for (const OptimalCode &c : codes) count += c.length == l;
+        dht->push_back((uint8_t)count);
+    }
+    for (const OptimalCode &c : codes) dht->push_back(c.symbol);
+}
+
 // ------------------------------------------------------------------------------------------------ batch
 OptimizeBatch::~OptimizeBatch() {
     for (DevBuffer *b : {&d_work_, &d_scan_ids_, &d_hist_, &d_enc_, &d_sizes_, &d_offsets_, &d_base_, &d_totals_, &d_out_, &d_sub_work_,
@@ -341,15 +359,6 @@ int OptimizeBatch::hip_fail(hipError_t e, const char *what) {
 }
 
 namespace {
-void put_marker(std::string &o, int m) {
-    o.push_back((char)0xFF);
-    o.push_back((char)m);
-}
-void put_length(std::string &o, uint16_t length) {  // JpegWriter.WriteLength: length + 2, big endian (:309-321)
-    const uint16_t v = (uint16_t)(length + 2);
-    o.push_back((char)(v >> 8));
-    o.push_back((char)v);
-}
 struct Refuse {
     int status, detail;
     std::string msg;
@@ -734,6 +743,21 @@ int OptimizeBatch::upload(const uint8_t *const *jpeg, const size_t *len, int n, 
     return JPGPU_OK;
 }
 
+// what run()'s stages hand one another
+struct OptimizeBatch::Run {
+    size_t n_jobs = 0;
+    int n_work = 0, n_scans = 0, n_sub_work = 0, n_sub_scans = 0, n_slots = 0;
+    const uint8_t *udata = nullptr, *input = nullptr;
+    const DevScan *scans = nullptr;
+    DevScanStatus *status = nullptr;
+    const DevHuffTable *pool = nullptr;
+    const uint32_t *ends_u = nullptr, *ends_raw = nullptr;
+    const uint32_t *exit_state = nullptr, *first_block = nullptr;  // of the subsequence synchronisation
+    std::vector<uint64_t> totals, base;                            // per interval scan: bytes, place in d_out_
+    std::vector<uint64_t> sub_total_bits, sout_len;                // per subsequence scan: raw bits, stuffed bytes
+    std::vector<DevEncImage> simages;                              // ... and its descriptor for the stuffing stage
+};
+
 int OptimizeBatch::run() {
     ran_ = false;
     if (!ev0_) {
@@ -742,42 +766,65 @@ int OptimizeBatch::run() {
     (void)hipEventRecord(ev0_, ctx_->stream);
     int rc = batch_.run_marker_index();
     if (rc != JPGPU_OK) return rc;
-    const size_t n_jobs = batch_.h_scans_.size();
-    const int n_work = (int)work_.size(), n_scans = (int)scan_ids_.size();
-    const uint8_t *udata = (const uint8_t *)batch_.d_unstuffed_.ptr, *input = (const uint8_t *)batch_.d_input_.ptr;
-    const DevScan *scans = (const DevScan *)batch_.d_scans_.ptr;
-    DevScanStatus *status = (DevScanStatus *)batch_.d_status_.ptr;
-    const DevHuffTable *pool = (const DevHuffTable *)batch_.d_huff_pool_.ptr;
-    const uint32_t *ends_u = (const uint32_t *)batch_.d_ends_u_.ptr, *ends_raw = (const uint32_t *)batch_.d_ends_.ptr;
-    const int n_slots = batch_.n_huff_slots_;
-    // ---- Scan(): IncrementCodeCount for every symbol
-    hipError_t e = hipMemsetAsync(d_hist_.ptr, 0, n_jobs * kMaxHuffSlots * 256 * sizeof(uint32_t), ctx_->stream);
+    Run r;
+    r.n_jobs = batch_.h_scans_.size();
+    r.n_work = (int)work_.size();
+    r.n_scans = (int)scan_ids_.size();
+    r.n_sub_work = (int)sub_work_.size();
+    r.n_sub_scans = (int)sub_scan_ids_.size();
+    r.n_slots = batch_.n_huff_slots_;
+    r.udata = (const uint8_t *)batch_.d_unstuffed_.ptr;
+    r.input = (const uint8_t *)batch_.d_input_.ptr;
+    r.scans = (const DevScan *)batch_.d_scans_.ptr;
+    r.status = (DevScanStatus *)batch_.d_status_.ptr;
+    r.pool = (const DevHuffTable *)batch_.d_huff_pool_.ptr;
+    r.ends_u = (const uint32_t *)batch_.d_ends_u_.ptr;
+    r.ends_raw = (const uint32_t *)batch_.d_ends_.ptr;
+    if ((rc = count_symbols(r)) != JPGPU_OK) return rc;
+    if ((rc = build_tables(r)) != JPGPU_OK) return rc;
+    if ((rc = measure_and_place(r)) != JPGPU_OK) return rc;
+    if ((rc = emit_intervals(r)) != JPGPU_OK) return rc;
+    if (r.n_sub_scans && (rc = emit_subsequences_and_stuff(r)) != JPGPU_OK) return rc;
+    (void)hipEventRecord(ev1_, ctx_->stream);
+    hipError_t e = hipStreamSynchronize(ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    (void)hipEventElapsedTime(&last_ms_, ev0_, ev1_);
+    collect_lengths(r);
+    ran_ = true;
+    return JPGPU_OK;
+}
+
+// ---- Scan(): IncrementCodeCount for every symbol
+int OptimizeBatch::count_symbols(Run &r) {
+    hipError_t e = hipMemsetAsync(d_hist_.ptr, 0, r.n_jobs * kMaxHuffSlots * 256 * sizeof(uint32_t), ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(histograms)");
-    e = launch_transcode(ctx_->stream, 0, udata, input, scans, (const HuffWork *)d_work_.ptr, n_work, ends_u, ends_raw, status, pool,
-                         (uint32_t *)d_hist_.ptr, nullptr, nullptr, nullptr, nullptr, n_slots);
+    e = launch_transcode(ctx_->stream, 0, r.udata, r.input, r.scans, (const HuffWork *)d_work_.ptr, r.n_work, r.ends_u, r.ends_raw, r.status, r.pool,
+                         (uint32_t *)d_hist_.ptr, nullptr, nullptr, nullptr, nullptr, r.n_slots);
     if (e != hipSuccess) return hip_fail(e, "transcode_kernel<count>");
     // scans without restart intervals: the decoder's self-synchronising subsequences, then the same three passes per subsequence
-    const int n_sub_work = (int)sub_work_.size(), n_sub_scans = (int)sub_scan_ids_.size();
-    const uint32_t *exit_state = nullptr, *first_block = nullptr;
-    if (n_sub_scans) {
-        rc = batch_.run_subseq_sync(&exit_state, &first_block);
+    if (r.n_sub_scans) {
+        const int rc = batch_.run_subseq_sync(&r.exit_state, &r.first_block);
         if (rc != JPGPU_OK) return rc;
-        e = launch_subseq_transcode(ctx_->stream, 0, udata, scans, (const HuffWork *)d_sub_work_.ptr, n_sub_work, ends_u, status, pool, exit_state,
-                                    first_block, (uint32_t *)d_hist_.ptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_slots);
+        e = launch_subseq_transcode(ctx_->stream, 0, r.udata, r.scans, (const HuffWork *)d_sub_work_.ptr, r.n_sub_work, r.ends_u, r.status, r.pool, r.exit_state,
+                                    r.first_block, (uint32_t *)d_hist_.ptr, nullptr, nullptr, nullptr, nullptr, nullptr, r.n_slots);
         if (e != hipSuccess) return hip_fail(e, "subseq_transcode_kernel<count>");
     }
-    h_hist_.assign(n_jobs * kMaxHuffSlots * 256, 0);
+    h_hist_.assign(r.n_jobs * kMaxHuffSlots * 256, 0);
     e = hipMemcpyAsync(h_hist_.data(), d_hist_.ptr, h_hist_.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(histograms)");
     e = hipStreamSynchronize(ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-    // ---- BuildTables (:462): one table per (class, identifier) in builder-creation order == the job's slot order
-    std::vector<EncHuffTable> enc(n_jobs * kMaxHuffSlots);
+    return JPGPU_OK;
+}
+
+// ---- BuildTables (:462): one table per (class, identifier) in builder-creation order == the job's slot order
+int OptimizeBatch::build_tables(Run &r) {
+    std::vector<EncHuffTable> enc(r.n_jobs * kMaxHuffSlots);
     memset(enc.data(), 0, enc.size() * sizeof(EncHuffTable));
     for (Plan &p : plans_) {
         if (p.status != JPGPU_OK || p.job < 0) continue;
         const ScanJob &job = batch_.jobs_[p.job];
-        std::string body;
+        std::vector<uint8_t> body;
         for (int t = 0; t < job.n_huff; t++) {
             std::vector<OptimalCode> codes;
             const uint32_t *freq = &h_hist_[((size_t)p.job * kMaxHuffSlots + t) * 256];
@@ -798,146 +845,128 @@ int OptimizeBatch::run() {
                 }
                 continue;
             }
-            EncHuffTable &et = enc[(size_t)p.job * kMaxHuffSlots + t];
-            // GetCode(symbol) = codes[_symbolMap[symbol]], and _symbolMap is 0 for symbols without a code (JpegHuffmanEncodingTable.cs:18-33, 90-96)
-            for (int sym = 0; sym < 256; sym++) {
-                et.code[sym] = codes[0].code;
-                et.len[sym] = codes[0].length;
-            }
-            for (const OptimalCode &c : codes) {
-                et.code[c.symbol] = c.code;
-                et.len[c.symbol] = c.length;
-            }
-            // JpegHuffmanEncodingTableCollection.Write (:172-190) + JpegHuffmanEncodingTable.TryWrite (:37-79)
-            body.push_back((char)(job.huff_copy[t].table_class << 4 | (job.huff_copy[t].identifier & 0xF)));
-            for (int l = 1; l <= 16; l++) {
-                int count = 0;
-                for (const OptimalCode &c : codes) count += c.length == l;
-                body.push_back((char)count);
-            }
-            for (const OptimalCode &c : codes) body.push_back((char)c.symbol);
+            // JpegHuffmanEncodingTableCollection.Write (:172-190): Tc/Th, then the table's own bytes
+            body.push_back((uint8_t)(job.huff_copy[t].table_class << 4 | (job.huff_copy[t].identifier & 0xF)));
+            optimal_codes_to_table(codes, &enc[(size_t)p.job * kMaxHuffSlots + t], &body);
         }
         p.dht.clear();
         put_marker(p.dht, 0xC4);
         put_length(p.dht, (uint16_t)body.size());
-        p.dht += body;
+        p.dht.append(body.begin(), body.end());
     }
-    e = hipMemcpyAsync(d_enc_.ptr, enc.data(), enc.size() * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
+    hipError_t e = hipMemcpyAsync(d_enc_.ptr, enc.data(), enc.size() * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(encoding tables)");
-    // ---- Optimize(): size of every interval, offsets, bytes
-    e = launch_transcode(ctx_->stream, 1, udata, input, scans, (const HuffWork *)d_work_.ptr, n_work, ends_u, ends_raw, status, pool, nullptr,
-                         (const EncHuffTable *)d_enc_.ptr, (uint32_t *)d_sizes_.ptr, nullptr, nullptr, n_slots);
+    return JPGPU_OK;
+}
+
+// ---- Optimize(): size of every interval and subsequence, and where the interval scans' bytes go
+int OptimizeBatch::measure_and_place(Run &r) {
+    hipError_t e = launch_transcode(ctx_->stream, 1, r.udata, r.input, r.scans, (const HuffWork *)d_work_.ptr, r.n_work, r.ends_u, r.ends_raw, r.status, r.pool,
+                                    nullptr, (const EncHuffTable *)d_enc_.ptr, (uint32_t *)d_sizes_.ptr, nullptr, nullptr, r.n_slots);
     if (e != hipSuccess) return hip_fail(e, "transcode_kernel<measure>");
-    e = launch_transcode_offsets(ctx_->stream, scans, (const uint32_t *)d_scan_ids_.ptr, n_scans, (const uint32_t *)d_sizes_.ptr, nullptr,
-                                 nullptr, (uint64_t *)d_totals_.ptr);
+    e = launch_transcode_offsets(ctx_->stream, r.scans, (const uint32_t *)d_scan_ids_.ptr, r.n_scans, (const uint32_t *)d_sizes_.ptr, nullptr, nullptr,
+                                 (uint64_t *)d_totals_.ptr);
     if (e != hipSuccess) return hip_fail(e, "transcode_offsets_kernel");
-    std::vector<uint64_t> totals((size_t)n_scans), base((size_t)n_scans);
-    if (n_scans) {
-        e = hipMemcpyAsync(totals.data(), d_totals_.ptr, totals.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
+    r.totals.assign((size_t)r.n_scans, 0);
+    r.base.assign((size_t)r.n_scans, 0);
+    if (r.n_scans) {
+        e = hipMemcpyAsync(r.totals.data(), d_totals_.ptr, r.totals.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(totals)");
     }
-    std::vector<uint64_t> sub_total_bits((size_t)n_sub_scans);
-    if (n_sub_scans) {
-        e = launch_subseq_transcode(ctx_->stream, 1, udata, scans, (const HuffWork *)d_sub_work_.ptr, n_sub_work, ends_u, status, pool, exit_state,
-                                    first_block, nullptr, (const EncHuffTable *)d_enc_.ptr, (uint32_t *)d_sub_bits_.ptr, nullptr, nullptr, nullptr,
-                                    n_slots);
+    r.sub_total_bits.assign((size_t)r.n_sub_scans, 0);
+    if (r.n_sub_scans) {
+        e = launch_subseq_transcode(ctx_->stream, 1, r.udata, r.scans, (const HuffWork *)d_sub_work_.ptr, r.n_sub_work, r.ends_u, r.status, r.pool, r.exit_state,
+                                    r.first_block, nullptr, (const EncHuffTable *)d_enc_.ptr, (uint32_t *)d_sub_bits_.ptr, nullptr, nullptr, nullptr, r.n_slots);
         if (e != hipSuccess) return hip_fail(e, "subseq_transcode_kernel<measure>");
-        e = launch_subseq_bit_offsets(ctx_->stream, scans, (const uint32_t *)d_sub_scan_ids_.ptr, n_sub_scans, (const uint32_t *)d_sub_bits_.ptr,
+        e = launch_subseq_bit_offsets(ctx_->stream, r.scans, (const uint32_t *)d_sub_scan_ids_.ptr, r.n_sub_scans, (const uint32_t *)d_sub_bits_.ptr,
                                       (uint64_t *)d_sub_bitoff_.ptr, (uint64_t *)d_sub_totals_.ptr);
         if (e != hipSuccess) return hip_fail(e, "subseq_bit_offsets_kernel");
-        e = hipMemcpyAsync(sub_total_bits.data(), d_sub_totals_.ptr, sub_total_bits.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
+        e = hipMemcpyAsync(r.sub_total_bits.data(), d_sub_totals_.ptr, r.sub_total_bits.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(bit totals)");
     }
     e = hipStreamSynchronize(ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     uint64_t out_bytes = 0;
-    for (int k = 0; k < n_scans; k++) {
-        base[k] = out_bytes;
-        out_bytes = (out_bytes + totals[k] + 255) & ~(uint64_t)255;
+    for (int k = 0; k < r.n_scans; k++) {
+        r.base[k] = out_bytes;
+        out_bytes = (out_bytes + r.totals[k] + 255) & ~(uint64_t)255;
     }
     e = d_out_.reserve((size_t)out_bytes + 256);
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(optimizer output)");
-    if (n_scans) {
-        e = hipMemcpyAsync(d_base_.ptr, base.data(), base.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx_->stream);
+    return JPGPU_OK;
+}
+
+// ---- ... the scans with restart intervals: offsets, bytes
+int OptimizeBatch::emit_intervals(Run &r) {
+    hipError_t e;
+    if (r.n_scans) {
+        e = hipMemcpyAsync(d_base_.ptr, r.base.data(), r.base.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(bases)");
     }
-    e = launch_transcode_offsets(ctx_->stream, scans, (const uint32_t *)d_scan_ids_.ptr, n_scans, (const uint32_t *)d_sizes_.ptr,
+    e = launch_transcode_offsets(ctx_->stream, r.scans, (const uint32_t *)d_scan_ids_.ptr, r.n_scans, (const uint32_t *)d_sizes_.ptr,
                                  (const uint64_t *)d_base_.ptr, (uint64_t *)d_offsets_.ptr, nullptr);
     if (e != hipSuccess) return hip_fail(e, "transcode_offsets_kernel");
-    e = launch_transcode(ctx_->stream, 2, udata, input, scans, (const HuffWork *)d_work_.ptr, n_work, ends_u, ends_raw, status, pool, nullptr,
-                         (const EncHuffTable *)d_enc_.ptr, (uint32_t *)d_sizes_.ptr, (const uint64_t *)d_offsets_.ptr, (uint8_t *)d_out_.ptr, n_slots);
+    e = launch_transcode(ctx_->stream, 2, r.udata, r.input, r.scans, (const HuffWork *)d_work_.ptr, r.n_work, r.ends_u, r.ends_raw, r.status, r.pool, nullptr,
+                         (const EncHuffTable *)d_enc_.ptr, (uint32_t *)d_sizes_.ptr, (const uint64_t *)d_offsets_.ptr, (uint8_t *)d_out_.ptr, r.n_slots);
     if (e != hipSuccess) return hip_fail(e, "transcode_kernel<emit>");
-    std::vector<DevEncImage> simages((size_t)n_sub_scans);
-    std::vector<uint64_t> sout_len((size_t)n_sub_scans);
-    if (n_sub_scans) {
-        // raw (unstuffed) bit buffers + the encoder's stuffing stage (E4): descriptors in the encoder's image form
-        std::vector<uint64_t> scan_raw_off(n_jobs, 0);
-        std::vector<EncWork> work_chunk;
-        uint64_t raw_off = 0, out_off = 0;
-        uint32_t chunk_off = 0;
-        memset(simages.data(), 0, simages.size() * sizeof(DevEncImage));
-        for (int k2 = 0; k2 < n_sub_scans; k2++) {
-            const uint64_t raw_len = (sub_total_bits[k2] + 7) / 8;
-            DevEncImage &im = simages[k2];
-            im.raw_off = raw_off;
-            im.out_off = out_off;
-            im.chunk_off = chunk_off;
-            im.header_len = 0;
-            scan_raw_off[sub_scan_ids_[k2]] = raw_off;
-            const uint32_t chunks = std::max<uint32_t>(1u, (uint32_t)((raw_len + kEncStuffChunk - 1) / kEncStuffChunk));
-            for (uint32_t c = 0; c < chunks; c++) work_chunk.push_back({(uint32_t)k2, c});
-            chunk_off += chunks;
-            raw_off = (raw_off + raw_len + 64 + 255) & ~(uint64_t)255;
-            out_off = (out_off + 2 * raw_len + 2 + 64 + 255) & ~(uint64_t)255;  // every byte may need stuffing
-        }
-        const struct {
-            DevBuffer *buf;
-            size_t bytes;
-        } grow[] = {{&d_raw_, (size_t)raw_off + 256}, {&d_sout_, (size_t)out_off + 256}, {&d_chunk_ff_, (size_t)chunk_off * sizeof(uint32_t) + 256},
-                    {&d_swork_chunk_, work_chunk.size() * sizeof(EncWork) + 16}};
-        for (const auto &g : grow) {
-            e = g.buf->reserve(g.bytes);
-            if (e != hipSuccess) return hip_fail(e, "hipMalloc(optimizer raw buffers)");
-        }
-        e = hipMemsetAsync(d_raw_.ptr, 0, (size_t)raw_off + 256, ctx_->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_scan_raw_off_.ptr, scan_raw_off.data(), scan_raw_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx_->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_simages_.ptr, simages.data(), simages.size() * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_swork_chunk_.ptr, work_chunk.data(), work_chunk.size() * sizeof(EncWork), hipMemcpyHostToDevice, ctx_->stream);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(optimizer raw descriptors)");
-        e = launch_subseq_transcode(ctx_->stream, 2, udata, scans, (const HuffWork *)d_sub_work_.ptr, n_sub_work, ends_u, status, pool, exit_state,
-                                    first_block, nullptr, (const EncHuffTable *)d_enc_.ptr, (uint32_t *)d_sub_bits_.ptr,
-                                    (const uint64_t *)d_sub_bitoff_.ptr, (const uint64_t *)d_scan_raw_off_.ptr, (uint8_t *)d_raw_.ptr, n_slots);
-        if (e != hipSuccess) return hip_fail(e, "subseq_transcode_kernel<emit>");
-        e = launch_stuff(ctx_->stream, (const DevEncImage *)d_simages_.ptr, (const EncWork *)d_swork_chunk_.ptr, (int)work_chunk.size(),
-                         (const uint64_t *)d_sub_totals_.ptr, (const uint8_t *)d_raw_.ptr, nullptr /* no restart marks: restart_interval is 0 */,
-                         (uint32_t *)d_chunk_ff_.ptr, (uint8_t *)d_sout_.ptr,
-                         (uint64_t *)d_sout_len_.ptr);
-        if (e != hipSuccess) return hip_fail(e, "stuff kernels");
-        e = hipMemcpyAsync(sout_len.data(), d_sout_len_.ptr, sout_len.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
-        if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(stuffed lengths)");
+    return JPGPU_OK;
+}
+
+// ---- ... the DRI = 0 scans: raw (unstuffed) bit buffers + the encoder's stuffing stage (E4), descriptors in the encoder's image form
+// (header_len, restart_interval and n_units zero: nothing in front of the stream, no restart marks)
+int OptimizeBatch::emit_subsequences_and_stuff(Run &r) {
+    r.simages.assign((size_t)r.n_sub_scans, DevEncImage());
+    memset(r.simages.data(), 0, r.simages.size() * sizeof(DevEncImage));
+    const StuffPlan sp = plan_stuffing_layout(r.simages.data(), r.sub_total_bits.data(), r.n_sub_scans, true);
+    std::vector<uint64_t> scan_raw_off(r.n_jobs, 0);
+    for (int k = 0; k < r.n_sub_scans; k++) scan_raw_off[sub_scan_ids_[k]] = r.simages[k].raw_off;
+    const struct {
+        DevBuffer *buf;
+        size_t bytes;
+    } grow[] = {{&d_raw_, (size_t)sp.raw_bytes + 256}, {&d_sout_, (size_t)sp.out_bytes + 256}, {&d_chunk_ff_, (size_t)sp.chunks * sizeof(uint32_t) + 256},
+                {&d_swork_chunk_, sp.work_chunk.size() * sizeof(EncWork) + 16}};
+    hipError_t e;
+    for (const auto &g : grow) {
+        e = g.buf->reserve(g.bytes);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc(optimizer raw buffers)");
     }
-    (void)hipEventRecord(ev1_, ctx_->stream);
-    e = hipStreamSynchronize(ctx_->stream);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-    (void)hipEventElapsedTime(&last_ms_, ev0_, ev1_);
+    e = hipMemsetAsync(d_raw_.ptr, 0, (size_t)sp.raw_bytes + 256, ctx_->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_scan_raw_off_.ptr, scan_raw_off.data(), scan_raw_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx_->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_simages_.ptr, r.simages.data(), r.simages.size() * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_swork_chunk_.ptr, sp.work_chunk.data(), sp.work_chunk.size() * sizeof(EncWork), hipMemcpyHostToDevice, ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(optimizer raw descriptors)");
+    e = launch_subseq_transcode(ctx_->stream, 2, r.udata, r.scans, (const HuffWork *)d_sub_work_.ptr, r.n_sub_work, r.ends_u, r.status, r.pool, r.exit_state,
+                                r.first_block, nullptr, (const EncHuffTable *)d_enc_.ptr, (uint32_t *)d_sub_bits_.ptr, (const uint64_t *)d_sub_bitoff_.ptr,
+                                (const uint64_t *)d_scan_raw_off_.ptr, (uint8_t *)d_raw_.ptr, r.n_slots);
+    if (e != hipSuccess) return hip_fail(e, "subseq_transcode_kernel<emit>");
+    e = launch_stuff(ctx_->stream, (const DevEncImage *)d_simages_.ptr, (const EncWork *)d_swork_chunk_.ptr, (int)sp.work_chunk.size(),
+                     (const uint64_t *)d_sub_totals_.ptr, (const uint8_t *)d_raw_.ptr, nullptr /* no restart marks: restart_interval is 0 */,
+                     (uint32_t *)d_chunk_ff_.ptr, (uint8_t *)d_sout_.ptr, (uint64_t *)d_sout_len_.ptr);
+    if (e != hipSuccess) return hip_fail(e, "stuff kernels");
+    r.sout_len.assign((size_t)r.n_sub_scans, 0);
+    e = hipMemcpyAsync(r.sout_len.data(), d_sout_len_.ptr, r.sout_len.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(stuffed lengths)");
+    return JPGPU_OK;
+}
+
+// where every file's scan data lies and how long the file is
+void OptimizeBatch::collect_lengths(const Run &r) {
     int k = 0, ks = 0;
     for (Plan &p : plans_) {
         if (p.status != JPGPU_OK || p.job < 0) continue;
         if (p.by_subsequence) {
-            p.entropy_off = simages[ks].out_off;
-            p.entropy_len = sout_len[ks] >= 2 ? sout_len[ks] - 2 : 0;  // the stuffing stage closes with EOI: that belongs to the host pieces here
+            p.entropy_off = r.simages[ks].out_off;
+            p.entropy_len = r.sout_len[ks] >= 2 ? r.sout_len[ks] - 2 : 0;  // the stuffing stage closes with EOI: that belongs to the host pieces here
             ks++;
         } else {
-            p.entropy_off = base[k];
-            p.entropy_len = totals[k];
+            p.entropy_off = r.base[k];
+            p.entropy_len = r.totals[k];
             k++;
         }
         p.out_len = 0;
         for (const Piece &pc : p.pieces)
             p.out_len += pc.kind == Piece::kBytes ? pc.bytes.size() : (pc.kind == Piece::kHuffmanTables ? p.dht.size() : p.entropy_len);
     }
-    ran_ = true;
-    return JPGPU_OK;
 }
 
 int OptimizeBatch::result(int i, jpgpu_image_result *res, size_t *out_len) {

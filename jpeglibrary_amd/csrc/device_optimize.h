@@ -19,6 +19,10 @@ struct OptimalCode {
 // perm[i] = original index of the key the restated Array.Sort(T[], Comparison<T>) leaves at position i (ascending by key)
 void net_sort_permutation(const int32_t *keys, int n, int32_t *perm);
 bool build_optimal_table(const uint32_t freq[256], std::vector<OptimalCode> *codes, bool most_optimal = false);  // Build(optimal)
+// The JpegHuffmanEncodingTable of those codes, both ways it is read: GetCode for all 256 symbols into *table -- a symbol without a
+// code gets the table's first code, _symbolMap being 0 for it (ref: JpegHuffmanEncodingTable.cs:21-37, 94-100) -- and TryWrite's
+// bytes (:50-86: the 16 counts, then the symbols) appended to *dht.  The Tc/Th byte in front of them is the caller's.
+void optimal_codes_to_table(const std::vector<OptimalCode> &codes, EncHuffTable *table, std::vector<uint8_t> *dht);
 
 class OptimizeBatch {
   public:
@@ -65,6 +69,14 @@ class OptimizeBatch {
     };
     int fail(int status, const std::string &msg);
     int hip_fail(hipError_t e, const char *what);
+    // run() is the list of these; what they hand one another is a Run that lives for the call
+    struct Run;
+    int count_symbols(Run &r);
+    int build_tables(Run &r);
+    int measure_and_place(Run &r);
+    int emit_intervals(Run &r);
+    int emit_subsequences_and_stuff(Run &r);
+    void collect_lengths(const Run &r);
     void plan_file(Plan &p, const uint8_t *data, size_t len, bool strip, bool swallow_terminator = false);
     size_t scan_end(const uint8_t *entropy, size_t len);
     const uint8_t *end_key_ = nullptr;
