@@ -434,6 +434,12 @@ void *jpgpu_batch_output_device(const jpgpu_batch *b, uint64_t *total_bytes) { r
 void *jpgpu_batch_coefficients_device(const jpgpu_batch *b, uint64_t *total_blocks) {
     return b ? const_cast<jpgpu_batch *>(b)->impl.coefs_device(total_blocks) : nullptr;  // (may expand split scans into the dense copy first)
 }
+// (tests only, not part of include/jpgpu.h: tests/test_k2_flush_flags_gpu.py)
+int jpgpu_debug_batch_cus(const jpgpu_batch *b) { return b ? b->ctx->num_cus : 0; }  // a pooled launch has one workgroup per CU at the most
+long long jpgpu_debug_batch_split_flags(jpgpu_batch *b, int i, unsigned long long *dst, size_t cap_words) {
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "flag words are 64 bits");
+    return b ? b->impl.debug_split_flags(i, reinterpret_cast<uint64_t *>(dst), cap_words) : -1;
+}
 int jpgpu_batch_download_output(jpgpu_batch *b, int i, void *dst, size_t cap) { JPGPU_GUARD(b, b->impl.download_output(i, dst, cap)); }
 int jpgpu_batch_download_coefficients(jpgpu_batch *b, int i, int16_t *dst, size_t cap_blocks) {
     JPGPU_GUARD(b, b->impl.download_coefficients(i, dst, cap_blocks));

@@ -152,6 +152,7 @@ class DeviceBatch {
         return d_out_.ptr;
     }
     void *coefs_device(uint64_t *total_blocks);  // dense int16[blocks][64], whatever form K2 handed the scans over in
+    long long debug_split_flags(int i, uint64_t *dst, size_t cap_words);  // tests: the flag words K2 left for image i (-1: not split)
     int download_output(int i, void *dst, size_t cap);
     int download_coefficients(int i, int16_t *dst, size_t cap_blocks);
     int upload_coefficients(int i, const int16_t *src, size_t nblocks);

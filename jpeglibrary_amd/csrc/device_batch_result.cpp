@@ -367,6 +367,19 @@ void *DeviceBatch::coefs_device(uint64_t *total_blocks) {
     return (void *)coefs;
 }
 
+// Tests only: the flag words of image i's scan as K2 left them in the store (common.h: one per (chunk of 64 restart intervals, MCU in
+// the interval, block in the MCU)), copied to dst.  Returns their count; -1 where the scan is not handed over as half-line planes.
+long long DeviceBatch::debug_split_flags(int i, uint64_t *dst, size_t cap_words) {
+    const ImagePlan *img = image(i);
+    if (!img || !dst || img->jobs.size() != 1 || !d_coefs_.ptr) return -1;
+    const DevScan &s = h_scans_[(size_t)img->jobs[0]];
+    if ((s.reserved0 & kScanSplitHandoff) == 0) return -1;
+    const uint64_t n = split_flag_words(s.n_intervals, s.dri, s.blocks_per_mcu);
+    if (cap_words < n || sync() != JPGPU_OK) return -1;
+    const hipError_t e = hipMemcpy(dst, (const uint64_t *)d_coefs_.ptr + (s.reserved0 >> kSplitFlagShift), n * 8, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? (long long)n : -1;
+}
+
 int DeviceBatch::upload_coefficients(int i, const int16_t *src, size_t nblocks) {
     const ImagePlan *img = image(i);
     if (!img || !src) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_coefficients: bad argument");

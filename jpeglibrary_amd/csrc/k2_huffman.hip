@@ -220,33 +220,45 @@ __device__ __forceinline__ void k2_wave(const uint8_t *__restrict__ udata, const
             } else {
                 // half-line planes: lanes 8j .. 8j + 7 of a pass hold blocks 2p, 2p + 1 = restart intervals 2p, 2p + 1: one whole line of the
                 // lo plane, and -- when either block has a non-zero coefficient in 32..63 -- the same line of the hi plane
-                uint64_t step_flags = 0;
+                // The step's flag word is bit j = lane j's block: every lane looks at the hi half of the block it staged itself (its own
+                // swizzle, conflict-free like the decode's writes), one ballot per block step.
+#ifndef JPGPU_K2_PRICE_FLUSH
+                uint4 own = *reinterpret_cast<const uint4 *>(my_stage + (64u ^ swz16));
+#pragma unroll
+                for (uint32_t c = 80; c < 128; c += 16) {
+                    const uint4 o = *reinterpret_cast<const uint4 *>(my_stage + (c ^ swz16));
+                    own.x |= o.x, own.y |= o.y, own.z |= o.z, own.w |= o.w;
+                }
+                const uint64_t step_flags = __ballot((own.x | own.y | own.z | own.w) != 0);
+#else
+                const uint64_t step_flags = 0;  // (priced by omission: no hi half is looked at, read or stored; wrong for flagged blocks)
+#endif
 #pragma unroll
                 for (int it = 0; it < 4; it++) {
                     const uint32_t blk = it * 16 + (lane >> 2);
                     const uint32_t chunk = lane & 3;
                     const uint32_t swz = (blk >> 1) & 7;
                     uint4 *src_lo = reinterpret_cast<uint4 *>(stage + blk * 128 + ((chunk ^ swz) * 16));
-                    uint4 *src_hi = reinterpret_cast<uint4 *>(stage + blk * 128 + (((chunk + 4) ^ swz) * 16));
-                    const uint4 v = *src_lo, w = *src_hi;
+                    const uint4 v = *src_lo;
                     const uint4 z = {0, 0, 0, 0};
                     *src_lo = z;
-                    *src_hi = z;
-                    const uint64_t nz = __ballot((w.x | w.y | w.z | w.w) != 0);  // four lanes per block, eight per line
                     // a line is written where its even interval has this MCU (the odd one is its equal or the scan's short last one)
                     const uint32_t even = wave_first + (blk & ~1u);
                     const bool have = even < n_ends && mcu < ((even == n_intervals - 1) ? total_mcus - even * dri_eff : dri_eff);
                     const uint64_t off = split_slot(wave_first + blk, mcu, b, dri_eff, bpm) * 64 + chunk * 16;
                     if (have) *reinterpret_cast<uint4 *>(split_lo + off) = v;
-                    if (have && ((nz >> (lane & ~7u)) & 0xFFu) != 0) *reinterpret_cast<uint4 *>(split_lo + split_hi_off + off) = w;
-                    // the sixteen blocks' flags: a nibble of the ballot each -> a bit each
-                    uint64_t x = nz | (nz >> 1);
-                    x = (x | (x >> 2)) & 0x1111111111111111ull;
-                    x = (x | (x >> 3)) & 0x0303030303030303ull;
-                    x = (x | (x >> 6)) & 0x000F000F000F000Full;
-                    x = (x | (x >> 12)) & 0x000000FF000000FFull;
-                    x = (x | (x >> 24)) & 0xFFFFull;
-                    step_flags |= x << (16 * it);
+                    // The hi side of a pass whose sixteen blocks are all unflagged is skipped (wave-uniform).  The staging is zero on entry,
+                    // a lane writes only its own block, and the hi half of an unflagged block was never written or written with zeros
+                    // (the look-up above has just read it as zeros): leaving its re-zero out still leaves the staging zero on exit,
+                    // which the next block step and -- in a pooled wave -- the next ticket's chunk rely on.
+                    const uint32_t pass_flags = (uint32_t)(step_flags >> (16 * it)) & 0xFFFFu;
+                    if (pass_flags != 0) {
+                        uint4 *src_hi = reinterpret_cast<uint4 *>(stage + blk * 128 + (((chunk + 4) ^ swz) * 16));
+                        const uint4 w = *src_hi;
+                        *src_hi = z;
+                        // the line goes out when either block of the pair is flagged; the unflagged one's slot is zeros from the staging
+                        if (have && ((pass_flags >> ((lane >> 2) & ~1u)) & 3u) != 0) *reinterpret_cast<uint4 *>(split_lo + split_hi_off + off) = w;
+                    }
                 }
                 // the step's flag word stays in the lane whose index is the step's; 64 of them (or the chunk's last ones) go out in one store
                 if (lane == (split_step & 63u)) my_flags = step_flags;
