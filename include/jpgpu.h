@@ -248,6 +248,41 @@ typedef struct jpgpu_ingest_stats {
     int32_t n_linearised;   /* multi-segment files the host had to gather as a whole (full marker walks) */
 } jpgpu_ingest_stats;
 int jpgpu_batch_ingest_stats(const jpgpu_batch *b, jpgpu_ingest_stats *stats);
+/* ---- (1b) files that are in device memory already: jpgpu_batch_upload without the host link.
+ * device_jpeg[i] is device memory of the context's device that holds the len[i] bytes of file i, whole, at any byte address.
+ * THE FILES ARE COPIED (jpgpu_batch_upload's contract, not the encoder's 4c): when the call returns the batch owns a copy of
+ * every file in its input buffer, the caller may overwrite or free its memory, and every later call on the batch
+ * (jpgpu_batch_decode, the stage calls, _result, the _download_ calls, the re-plans and the partial flush of progressive files)
+ * behaves as it does behind a host upload of the same bytes.  No kernel reads the caller's memory after the call, and none
+ * reads outside [device_jpeg[i], device_jpeg[i] + len[i]) during it.
+ * What crosses the host link: of every file its head -- the bytes up to the end of its first SOS header plus
+ * JPGPU_DEVICE_HEAD_PAD, at most 64 KiB; a device-side walk over the marker segments finds that length, and all 64 KiB are
+ * taken where the walk meets anything it does not expect (the host parses what it gets, no result depends on the walk) -- and,
+ * whole, the files that need the full marker walks on the host (jpgpu_ingest_stats.n_full_walk: several scans, progressive,
+ * bytes behind the EOI, truncated data, a first scan that starts behind the head).  The gather, the walk and the verdict run
+ * as a fixed number of launches and copies per upload on the context's upload stream.
+ * Ordering: like every upload it is ordered behind device work this batch has issued and not yet synchronised; the work that
+ * PRODUCED the bytes must be complete -- or ordered before the context's upload stream -- when this call is made.
+ * JPGPU_ERR_ARGUMENT for the whole call, decided here and before anything is enqueued, leaving the batch empty
+ * (jpgpu_batch_size = 0): a NULL batch or array; a NULL file pointer with len[i] != 0; a pointer hipPointerGetAttributes does
+ * not report as device memory of the context's device (host, pinned host and managed memory are refused); a file whose len[i]
+ * bytes do not lie inside ONE allocation (hipMemGetAddressRange); an unknown format.  len[i] == 0 is the empty file: it gets the
+ * host path's per-image status and its pointer is not looked at. */
+#define JPGPU_DEVICE_HEAD_PAD 64
+int jpgpu_batch_upload_device(jpgpu_batch *b, const void *const *device_jpeg, const size_t *len, int n, int format);
+/* What the last jpgpu_batch_upload_device moved (all zero behind any other upload of the batch, and behind a refused one); jpgpu_batch_ingest_stats keeps reporting
+ * the plans and the times (n_pinned_dma = 0).  Compare jpgpu_sizeof_device_ingest_stats() with sizeof at load time. */
+typedef struct jpgpu_device_ingest_stats {
+    int32_t files_gathered;    /* files copied from the caller's device memory into the input buffer */
+    int32_t files_downloaded;  /* files fetched whole to the host for the full marker walks */
+    int32_t walker_giveups;    /* files whose head is min(len, 64 KiB) because the device-side walk gave up */
+    float gather_ms;           /* device time of the gather (events around it on the upload stream) */
+    uint64_t bytes_gathered;
+    uint64_t head_bytes;       /* D2H: the packed heads, each rounded up to 16 bytes (beside 12 bytes per file of lengths and offsets) */
+    uint64_t bytes_downloaded; /* D2H: the files of files_downloaded */
+} jpgpu_device_ingest_stats;
+size_t jpgpu_sizeof_device_ingest_stats(void);
+int jpgpu_batch_device_ingest_stats(const jpgpu_batch *b, jpgpu_device_ingest_stats *stats);
 /* How the last upload planned the entropy stage of its sequential scans (read only; for tests and tools).  K2 = scans with
  * restart intervals: workgroups of the plain list, and runs of adjacent scans with the same tables and geometry POOLED into
  * chunks of 64 intervals (at most 8 pools).  K2S = scans without restart intervals: the final pass's plain list and its pools

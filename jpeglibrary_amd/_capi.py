@@ -95,6 +95,14 @@ class IngestStats(C.Structure):
                 ("n_pinned_dma", C.c_int32), ("n_linearised", C.c_int32)]
 
 
+class DeviceIngestStats(C.Structure):
+    _fields_ = [("files_gathered", C.c_int32), ("files_downloaded", C.c_int32), ("walker_giveups", C.c_int32), ("gather_ms", C.c_float),
+                ("bytes_gathered", C.c_uint64), ("head_bytes", C.c_uint64), ("bytes_downloaded", C.c_uint64)]
+
+
+DEVICE_HEAD_PAD = 64  # JPGPU_DEVICE_HEAD_PAD
+
+
 class PlanStats(C.Structure):
     _fields_ = [("k2_plain_work", C.c_int32), ("k2_pools", C.c_int32), ("k2_pooled_chunks", C.c_int32), ("huffman_waves", C.c_int32),
                 ("k2s_scans", C.c_int32), ("k2s_plain_work", C.c_int32), ("k2s_pools", C.c_int32), ("k2s_table_sets", C.c_int32),
@@ -161,6 +169,9 @@ SYMBOLS = [
     ("jpgpu_batch_destroy", None, [_P]),
     ("jpgpu_batch_upload", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int]),
     ("jpgpu_batch_upload_segments", C.c_int, [_P, C.POINTER(Segment), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_uint]),
+    ("jpgpu_batch_upload_device", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int]),
+    ("jpgpu_sizeof_device_ingest_stats", C.c_size_t, []),
+    ("jpgpu_batch_device_ingest_stats", C.c_int, [_P, C.POINTER(DeviceIngestStats)]),
     ("jpgpu_batch_upload_frames", C.c_int, [_P, C.POINTER(Frame), C.c_void_p, C.c_int, C.c_int]),
     ("jpgpu_batch_decode", C.c_int, [_P]),
     ("jpgpu_batch_run_entropy", C.c_int, [_P]),
@@ -303,6 +314,9 @@ def _load():
     if lib.jpgpu_sizeof_plan_stats() != C.sizeof(PlanStats):
         raise ImportError(f"{LIB_PATH} (jpgpu_plan_stats of {lib.jpgpu_sizeof_plan_stats()} bytes) does not match this binding "
                           f"({C.sizeof(PlanStats)} bytes): rebuild it")
+    if lib.jpgpu_sizeof_device_ingest_stats() != C.sizeof(DeviceIngestStats):
+        raise ImportError(f"{LIB_PATH} (jpgpu_device_ingest_stats of {lib.jpgpu_sizeof_device_ingest_stats()} bytes) does not match this "
+                          f"binding ({C.sizeof(DeviceIngestStats)} bytes): rebuild it")
     if lib.jpgpu_sizeof_progressive_plan() != C.sizeof(ProgressivePlan):
         raise ImportError(f"{LIB_PATH} (jpgpu_progressive_plan of {lib.jpgpu_sizeof_progressive_plan()} bytes) does not match this "
                           f"binding ({C.sizeof(ProgressivePlan)} bytes): rebuild it")

@@ -34,6 +34,49 @@ class _DeviceView:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "|u1", "data": (ptr, False), "version": 2, "strides": None}
 
 
+def _tensor_files(tensors, device):
+    """The checks of Batch.upload_tensors, before any library call (they need neither a context nor a device): [(data_ptr, bytes)] for
+    1-D contiguous uint8 torch tensors on `device` (a CUDA device index, or a torch.device), one per file.  An empty tensor is the
+    empty file (no pointer)."""
+    import torch  # (here: the package imports without torch)
+
+    want = device if isinstance(device, torch.device) else torch.device("cuda", device)
+
+    if isinstance(tensors, (torch.Tensor, bytes, bytearray, memoryview)):
+        raise ValueError("a list of tensors is expected, one per file, not %s" % type(tensors).__name__)
+    out = []
+    for i, t in enumerate(tensors):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("file %d: a torch tensor is expected, not %s (bytes and numpy arrays go to upload())" % (i, type(t).__name__))
+        if t.dtype != torch.uint8:
+            raise ValueError("file %d: a uint8 tensor is expected, not %s" % (i, t.dtype))
+        if t.dim() != 1:
+            raise ValueError("file %d: a 1-D tensor of the file's bytes is expected, not shape %s" % (i, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("file %d: the tensor is not contiguous; call .contiguous() (nothing is copied silently)" % i)
+        if t.device != want:
+            raise ValueError("file %d: the tensor is on %s, not on the context's device %s" % (i, t.device, want))
+        out.append((t.data_ptr() if t.numel() else None, t.numel()))
+    return out
+
+
+def _all_tensors(files):
+    """decode_batch / decode_to_tensors: is `files` a list of device files (torch tensors)?  A list that mixes them with bytes raises."""
+    import sys
+
+    torch = sys.modules.get("torch")  # (a tensor cannot exist without it; the package imports without torch)
+    kinds = {torch is not None and isinstance(f, torch.Tensor) for f in files}
+    if kinds == {True, False}:
+        raise ValueError("files are all bytes-like (host memory) or all torch tensors (device memory), not a mix")
+    return kinds == {True}
+
+
+def _upload_any(batch, files, fmt):
+    """decode_batch / decode_to_tensors: upload() for bytes-like files, upload_tensors() for a list of torch tensors"""
+    files = list(files)
+    return batch.upload_tensors(files, fmt) if _all_tensors(files) else batch.upload(files, fmt)
+
+
 class Batch:
     def __init__(self, ctx: Context = None):
         self.ctx = ctx or default_context()
@@ -82,6 +125,26 @@ class Batch:
         arr = (_capi.Segment * max(1, len(segs)))(*[_capi.Segment(d, n) for d, n in segs])
         cnt = (C.c_int * max(1, len(per)))(*per)
         self._check(_lib.jpgpu_batch_upload_segments(self._h, arr, cnt, len(per), fmt, (_capi.UPLOAD_PINNED_ARENA if arena else 0) | (_capi.UPLOAD_PINNED if pinned else 0)))
+        self.format = fmt
+        return self
+
+    def upload_tensors(self, tensors, fmt=FMT_INTERLEAVED_U8):
+        """upload() for files that are in device memory already (jpgpu_batch_upload_device): 1-D contiguous torch.uint8 tensors on the
+        context's device, one per file -- an EncodeBatch.output_tensor(i), bytes a storage stack delivered into HBM.  The files are copied
+        into the batch on the device; only their headers cross the host link (and, whole, the files that need the full marker walks).
+        ValueError, before the library is called, for anything that is not such a tensor.  torch's current stream on the device is
+        synchronised first, so whatever produced the bytes has finished.  The batch owns a copy when this returns: no reference to the
+        tensors is kept, they may be overwritten or freed."""
+        import torch
+
+        tensors = list(tensors) if isinstance(tensors, (list, tuple)) else tensors
+        files = _tensor_files(tensors, self.ctx.device)
+        n = len(files)
+        ptrs = (C.c_void_p * max(1, n))(*[p for p, _ in files])
+        lens = (C.c_size_t * max(1, n))(*[m for _, m in files])
+        # the library reads the tensors on its own stream: what torch has queued on its current one must have happened
+        torch.cuda.current_stream(self.ctx.device).synchronize()
+        self._check(_lib.jpgpu_batch_upload_device(self._h, ptrs, lens, n, fmt))
         self.format = fmt
         return self
 
@@ -141,6 +204,14 @@ class Batch:
         st = _capi.IngestStats()
         self._check(_lib.jpgpu_batch_ingest_stats(self._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in _capi.IngestStats._fields_}
+
+    def device_ingest_stats(self):
+        """What the last upload_tensors() moved: files_gathered / bytes_gathered (device to device), head_bytes (the headers, D2H),
+        files_downloaded / bytes_downloaded (files fetched whole for the full marker walks), walker_giveups, gather_ms (device time of the
+        gather).  Zero behind any other upload."""
+        st = _capi.DeviceIngestStats()
+        self._check(_lib.jpgpu_batch_device_ingest_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in _capi.DeviceIngestStats._fields_}
 
     def plan_stats(self):
         """How the last upload() planned the entropy stage (K2's plain list and pools, K2S's final-pass list, pools and table
@@ -284,8 +355,8 @@ class Batch:
 
 
 def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None):
-    """One-call helper: returns (outputs, results)."""
-    b = Batch(ctx).upload(files, fmt).decode().sync()
+    """One-call helper: returns (outputs, results).  files: bytes-like objects, or 1-D uint8 torch tensors on the context's device."""
+    b = _upload_any(Batch(ctx), files, fmt).decode().sync()
     outs, results = [], []
     for i in range(len(b)):
         r = b.result(i)
@@ -298,8 +369,9 @@ def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None):
 def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, ctx=None):
     """One-call helper for torch consumers: returns (tensors, results), tensors[i] = Batch.output_tensor(i) -- uint8[3, H, W] on the
     context's device by default -- or None for an image that failed.  Nothing is downloaded.  The batch is not closed: its output
-    buffer is the tensors' memory and is freed with the last of them."""
-    b = Batch(ctx).upload(files, fmt).decode().sync()
+    buffer is the tensors' memory and is freed with the last of them.  files: bytes-like objects, or 1-D uint8 torch tensors on the
+    context's device (Batch.upload_tensors: e.g. EncodeBatch.output_tensor(i) -- the streams never leave the device)."""
+    b = _upload_any(Batch(ctx), files, fmt).decode().sync()
     tensors, results = [], []
     for i in range(len(b)):
         results.append(b.result(i))

@@ -94,6 +94,7 @@ void jpgpu_destroy(jpgpu_ctx *ctx) {
         if (ctx->staging.drained[i]) (void)hipEventDestroy(ctx->staging.drained[i]);
     }
     if (ctx->staging.verdict) (void)hipHostFree(ctx->staging.verdict);
+    if (ctx->staging.heads) (void)hipHostFree(ctx->staging.heads);
     delete ctx;
 }
 
@@ -389,6 +390,15 @@ int jpgpu_batch_upload(jpgpu_batch *b, const uint8_t *const *jpeg, const size_t 
 }
 int jpgpu_batch_upload_segments(jpgpu_batch *b, const jpgpu_segment *segments, const int *segments_per_file, int n, int format, unsigned flags) {
     JPGPU_GUARD(b, b->impl.upload_segments(segments, segments_per_file, n, format, flags));
+}
+int jpgpu_batch_upload_device(jpgpu_batch *b, const void *const *device_jpeg, const size_t *len, int n, int format) {
+    JPGPU_GUARD(b, b->impl.upload_device(device_jpeg, len, n, format));
+}
+size_t jpgpu_sizeof_device_ingest_stats(void) { return sizeof(jpgpu_device_ingest_stats); }
+int jpgpu_batch_device_ingest_stats(const jpgpu_batch *b, jpgpu_device_ingest_stats *stats) {
+    if (!b || !stats) return JPGPU_ERR_ARGUMENT;
+    *stats = b->impl.device_ingest_stats();
+    return JPGPU_OK;
 }
 int jpgpu_batch_upload_frames(jpgpu_batch *b, const jpgpu_frame *frames, const uint16_t *qt, int n, int format) {
     JPGPU_GUARD(b, b->impl.upload_frames(frames, qt, n, format));

@@ -187,6 +187,17 @@ struct GatherPiece {
     uint32_t len;
     uint32_t pad;
 };
+// jpgpu_batch_upload_device (k0_device_files.hip): gather_device_kernel takes the same pieces with dst_off a multiple of 16 and
+// `pad` = zero bytes to write behind the piece (len + pad a multiple of 16), each at most kGatherPieceBytes long
+constexpr uint32_t kGatherPieceBytes = 64u << 10;
+// one file in the input buffer for head_walk_kernel / head_pack_kernel (a file the ingest refuses for its size: {0, 0})
+struct DeviceFile {
+    uint64_t off;
+    uint32_t len;
+    uint32_t pad;
+};
+constexpr uint32_t kDeviceHeadMax = 64u << 10;   // what the host parser sees of a file it cannot read whole, at most
+constexpr uint32_t kHeadGaveUp = 0x80000000u;    // head_len[i]: the walk met something it does not expect
 struct ChunkSum {
     uint32_t rst_cnt;     // RSTn markers whose FF lies in the chunk
     uint32_t keep_cnt;    // bytes the chunk contributes to the unstuffed copy (markers count 2)

@@ -48,11 +48,13 @@ void DevBuffer::release() {
 
 DeviceBatch::~DeviceBatch() {
     if (ctx_) (void)hipSetDevice(ctx_->device);
-    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_rgb_scratch_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_})
+    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_})
         b->release();
     for (hipEvent_t &e : ev_pool_)
         if (e) (void)hipEventDestroy(e);
     if (done_ev_) (void)hipEventDestroy(done_ev_);
+    for (hipEvent_t ev : gather_ev_)
+        if (ev) (void)hipEventDestroy(ev);
     if (h_k1_giveup_) (void)hipHostFree(h_k1_giveup_);
 }
 
@@ -485,6 +487,14 @@ struct DeviceBatch::FileSegs {
     const uint8_t *base = nullptr;
     size_t base_len = 0;
     std::vector<uint8_t> gathered;
+    // jpgpu_batch_upload_device: the file lies in the caller's device memory (no segments) and, once staged, at `slot` of the
+    // input buffer; `base` is its head as the device delivered it, or the whole file fetched back from its slot; the host sees
+    // nothing else of it but the two bytes at its ingest verdict (verdict_at: offset in the file)
+    const uint8_t *dev = nullptr;
+    bool device = false;
+    uint64_t slot = 0;
+    size_t verdict_at = 0;
+    uint32_t verdict = 0;
     static constexpr size_t kHeadBytes = 64u << 10;
     bool whole() const { return base_len == len; }
     void gather(size_t want) {
@@ -500,6 +510,7 @@ struct DeviceBatch::FileSegs {
         base_len = want;
     }
     uint8_t at(size_t off) const {
+        if (device) return off == verdict_at ? (uint8_t)verdict : off == verdict_at + 1 ? (uint8_t)(verdict >> 8) : 0;
         for (int k = 0; k < n; k++) {
             if (off < seg[k].len) return seg[k].data[off];
             off -= seg[k].len;
@@ -541,23 +552,10 @@ int DeviceBatch::upload_segments(const jpgpu_segment *segments, const int *segme
     if (n < 0 || (n > 0 && (!segments || !segments_per_file))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload: null argument");
     if (format < 0 || format >= kNumOutputFormats) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload: unknown format");
     if (flags & ~(JPGPU_UPLOAD_PINNED | JPGPU_UPLOAD_PINNED_ARENA)) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_segments: unknown flag");
-    const bool pinned = (flags & (JPGPU_UPLOAD_PINNED | JPGPU_UPLOAD_PINNED_ARENA)) != 0;
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t0) { return (float)std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
-    const clk::time_point t_begin = clk::now();
-    ingest_ = IngestStats();
-    hipError_t e = hipSetDevice(ctx_->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    int rc = order_upload_behind_work();
+    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    int rc = begin_ingest(n, format);
     if (rc != JPGPU_OK) return rc;
-    format_ = format;
-    images_.assign((size_t)n, ImagePlan());
-    jobs_.clear();
-    job_image_.clear();
-    job_entropy_off_.clear();
-    constexpr size_t kMaxFile = 0x7FFFFFF0u;
     std::vector<FileSegs> files((size_t)n);
-    uint64_t total_bytes = 0;
     {
         const jpgpu_segment *sp = segments;
         for (int i = 0; i < n; i++) {
@@ -574,9 +572,93 @@ int DeviceBatch::upload_segments(const jpgpu_segment *segments, const int *segme
                 f.base = f.seg[0].data;
                 f.base_len = f.len;
             }
-            total_bytes += f.len;
         }
     }
+    return ingest_files(files, flags, t_begin);
+}
+
+// What every upload of whole files starts with: the batch forgets its images and jobs, the upload stream waits for the batch's
+// unsynchronised device work.
+int DeviceBatch::begin_ingest(int n, int format) {
+    ingest_ = IngestStats();
+    device_ingest_ = jpgpu_device_ingest_stats();
+    hipError_t e = hipSetDevice(ctx_->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    int rc = order_upload_behind_work();
+    if (rc != JPGPU_OK) return rc;
+    format_ = format;
+    images_.assign((size_t)n, ImagePlan());
+    jobs_.clear();
+    job_image_.clear();
+    job_entropy_off_.clear();
+    return JPGPU_OK;
+}
+
+// jpgpu_batch_upload for whole files that lie in device memory of the context's device (include/jpgpu.h, 1b).
+int DeviceBatch::upload_device(const void *const *device_jpeg, const size_t *len, int n, int format) {
+    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    auto refuse = [&](const std::string &why) {
+        images_.clear();
+        jobs_.clear();
+        job_image_.clear();
+        job_entropy_off_.clear();
+        whole_files_ = replay_possible_ = false;
+        device_ingest_ = jpgpu_device_ingest_stats();
+        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_device: " + why);
+    };
+    if (n < 0 || (n > 0 && (!device_jpeg || !len))) return refuse("null argument");
+    if (format < 0 || format >= kNumOutputFormats) return refuse("unknown format");
+    hipError_t e = hipSetDevice(ctx_->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    std::vector<FileSegs> files((size_t)n);
+    for (int i = 0; i < n; i++) {
+        FileSegs &f = files[(size_t)i];
+        f.device = true;
+        f.len = len[i];
+        if (f.len == 0) continue;  // the empty file: its pointer is not looked at
+        f.dev = (const uint8_t *)device_jpeg[i];
+        const std::string which = "file " + std::to_string(i);
+        if (!f.dev) return refuse(which + ": null pointer");
+        const int where = check_device_range(ctx_->device, f.dev, f.len);
+        if (where == 1) return refuse(which + " is not in device memory of the context's device");
+        if (where == 2) return refuse(which + ": " + std::to_string(f.len) + " bytes do not lie inside one device allocation");
+    }
+    const int rc = begin_ingest(n, format);
+    if (rc != JPGPU_OK) return rc;
+    return ingest_files(files, 0, t_begin);
+}
+
+int check_device_range(int device, const void *p, size_t bytes) {
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof attr);
+    hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e != hipSuccess) (void)hipGetLastError();  // (host memory the runtime has never seen: an error of this query, not of the stream)
+    if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != device) return 1;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)p;
+    if (e != hipSuccess || at < lo || at - lo > size || bytes > size - (at - lo)) return 2;
+    return 0;
+}
+
+// The ingest proper, for files in host memory (segments) and in device memory alike.  The two sources differ in how a file's
+// head is obtained (host: it is there, or gathered from the segments; device: the files are staged FIRST, the device says how
+// long each head is and delivers them packed), how a whole file is obtained (host: gathered from the segments by the crew
+// thread that needs it; device: the files that need it are fetched back from their slots together, one synchronisation) and
+// how the two bytes at the verdict are read (FileSegs::at).  Everything else is one body.
+int DeviceBatch::ingest_files(std::vector<FileSegs> &files, unsigned flags, std::chrono::steady_clock::time_point t_begin) {
+    const int n = (int)files.size();
+    const bool device = n > 0 && files[0].device;
+    const bool pinned = (flags & (JPGPU_UPLOAD_PINNED | JPGPU_UPLOAD_PINNED_ARENA)) != 0;
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) { return (float)std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+    hipError_t e = hipSuccess;
+    int rc = JPGPU_OK;
+    constexpr size_t kMaxFile = 0x7FFFFFF0u;
+    uint64_t total_bytes = 0;
+    for (const FileSegs &f : files) total_bytes += f.len;
     std::vector<FilePlan> plans((size_t)n);
 
     const int want = ctx_->host_threads > 0 ? ctx_->host_threads : default_host_threads();
@@ -588,7 +670,17 @@ int DeviceBatch::upload_segments(const jpgpu_segment *segments, const int *segme
     // ---- 1. header-only plans (a multi-segment file: over its first 64 KiB, gathered; should its first scan start behind
     //         them, or the plan not be "headers + one sequential scan", the whole file is gathered for the full walks)
     clk::time_point t0 = clk::now();
+    float device_stage_ms = 0;
+    if (device) {
+        // (a device source: step 2 comes first -- the heads are read from the batch's own copy of the files)
+        rc = stage_device_files(files);
+        if (rc != JPGPU_OK) return rc;
+        device_stage_ms = ms_since(t0);
+        t0 = clk::now();
+    }
     std::atomic<int> n_linearised{0};
+    std::vector<int> fetch;            // device files whose head did not do: fetched whole, together, and planned again
+    std::vector<uint8_t> want_whole((size_t)(device ? n : 0), 0);
     crew.run((size_t)n, [&](size_t i, int) {
         FileSegs &f = files[i];
         FilePlan &fp = plans[i];
@@ -602,6 +694,8 @@ int DeviceBatch::upload_segments(const jpgpu_segment *segments, const int *segme
         if (!f.whole()) {
             if (fp.speculative) {
                 fp.jobs[0].entropy_len = f.len - fp.scan_data_pos;
+            } else if (f.device) {
+                want_whole[i] = 1;
             } else {
                 f.gather(f.len);
                 n_linearised.fetch_add(1, std::memory_order_relaxed);
@@ -610,6 +704,18 @@ int DeviceBatch::upload_segments(const jpgpu_segment *segments, const int *segme
         }
         fp.img.file_len = f.len;
     });
+    for (size_t i = 0; i < want_whole.size(); i++)
+        if (want_whole[i]) fetch.push_back((int)i);
+    if (!fetch.empty()) {
+        rc = fetch_device_files(files, fetch);
+        if (rc != JPGPU_OK) return rc;
+        crew.run(fetch.size(), [&](size_t k, int) {
+            FileSegs &f = files[(size_t)fetch[k]];
+            FilePlan &fp = plans[(size_t)fetch[k]];
+            plan_file_headers(f.base, f.base_len, fp);
+            fp.img.file_len = f.len;
+        });
+    }
     ingest_.parse_ms = ms_since(t0);
 
     // ---- 2. the files -> HBM (every file gets its slot, whatever became of its plan: the layout does not wait for plans)
@@ -638,7 +744,9 @@ int DeviceBatch::upload_segments(const jpgpu_segment *segments, const int *segme
         if (contiguous && lo && (uint64_t)(hi - lo) <= 2 * total_bytes + (1u << 20)) arena_span_ = {lo, (size_t)(hi - lo)};
     }
     uint64_t in_off = 256;
-    if (arena_span_.first) {
+    if (device) {
+        for (int i = 0; i < n; i++) plans[i].img.file_offset = files[(size_t)i].slot;  // (stage_device_files has laid them out)
+    } else if (arena_span_.first) {
         for (int i = 0; i < n; i++) {
             const FileSegs &f = files[(size_t)i];
             const uint8_t *first = nullptr;
@@ -653,23 +761,29 @@ int DeviceBatch::upload_segments(const jpgpu_segment *segments, const int *segme
             if (files[(size_t)i].len <= kMaxFile) in_off = align_up(in_off + files[(size_t)i].len, 256);
         }
     }
-    input_bytes_ = in_off + 256;
-    rc = stage_files(crew, files, plans, pinned);
-    if (rc != JPGPU_OK) return rc;
+    if (!device) {
+        input_bytes_ = in_off + 256;
+        rc = stage_files(crew, files, plans, pinned);
+        if (rc != JPGPU_OK) return rc;
+    }
 
     // ---- 3. the device's verdict on the header-only plans
     std::vector<int> spec;
     for (int i = 0; i < n; i++)
         if (plans[i].speculative) spec.push_back(i);
     if (!spec.empty()) {
-        std::vector<uint32_t> first;
-        rc = verify_plans(plans, spec, first);
+        std::vector<uint32_t> first, bytes;
+        rc = verify_plans(plans, spec, first, device ? &bytes : nullptr);
         if (rc != JPGPU_OK) return rc;
         for (size_t k = 0; k < spec.size(); k++) {
             FilePlan &fp = plans[spec[k]];
-            const FileSegs &f = files[(size_t)spec[k]];
+            FileSegs &f = files[(size_t)spec[k]];
             const size_t dlen = f.len - fp.scan_data_pos;
             const uint32_t pos = first[k];
+            if (device) {
+                f.verdict_at = fp.scan_data_pos + pos;
+                f.verdict = bytes[k];
+            }
             // classify16 only calls FF xx a marker when xx exists: pos + 1 < dlen
             if (pos != 0xFFFFFFFFu && (size_t)pos + 1 < dlen && f.at(fp.scan_data_pos + pos) == 0xFF && f.at(fp.scan_data_pos + pos + 1) == kEOI) {
                 fp.seq_ends.assign(1, (size_t)pos);
@@ -684,10 +798,27 @@ int DeviceBatch::upload_segments(const jpgpu_segment *segments, const int *segme
         if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(upload)");
     }
     work_in_flight_ = false;  // the upload stream waited for this batch's earlier device work, and has been drained
-    ingest_.copy_ms = ms_since(t0);
+    ingest_.copy_ms = ms_since(t0) + device_stage_ms;
 
     // ---- 4. the rest: "one byte into the terminator" verdicts of the confirmed plans, full walks of everything else
     t0 = clk::now();
+    if (device) {
+        // a device file the host has only the head of: like a multi-segment file it keeps its header-only plan when the EOI
+        // closes the file, and takes the general path otherwise; the files that do are fetched together
+        fetch.clear();
+        for (int i = 0; i < n; i++) {
+            FilePlan &fp = plans[i];
+            const FileSegs &f = files[(size_t)i];
+            if (f.whole() || f.len > kMaxFile) continue;
+            if (fp.speculative && fp.scan_data_pos + fp.seq_ends[0] + 2 != f.len) {
+                fp.speculative = false;
+                fp.need_full = true;
+            }
+            if (fp.need_full) fetch.push_back(i);
+        }
+        rc = fetch_device_files(files, fetch);
+        if (rc != JPGPU_OK) return rc;
+    }
     crew.run((size_t)n, [&](size_t i, int) {
         FilePlan &fp = plans[i];
         FileSegs &f = files[i];
@@ -910,7 +1041,10 @@ int DeviceBatch::stage_files(WorkCrew &crew, const std::vector<FileSegs> &files,
 
 // Step 3 of the ingest: first marker that is not RSTn behind every planned SOS header (first_marker_kernel); synchronises
 // the upload stream, so the caller's buffers are free once this returns.
-int DeviceBatch::verify_plans(const std::vector<FilePlan> &plans, const std::vector<int> &spec, std::vector<uint32_t> &first) {
+// bytes (a device source): the two bytes at each reported position too, low byte first (verdict_bytes_kernel behind the verdict;
+// the same D2H carries them).
+int DeviceBatch::verify_plans(const std::vector<FilePlan> &plans, const std::vector<int> &spec, std::vector<uint32_t> &first,
+                              std::vector<uint32_t> *bytes) {
     const size_t n = spec.size();
     std::vector<uint32_t> host(3 * n);  // {offset lo, length} pairs, then offset hi
     uint32_t max_len = 0;
@@ -923,32 +1057,163 @@ int DeviceBatch::verify_plans(const std::vector<FilePlan> &plans, const std::vec
         host[2 * n + k] = (uint32_t)(off >> 32);
         max_len = std::max(max_len, dlen);
     }
-    hipError_t e = d_verify_.reserve(4 * n * sizeof(uint32_t) + 256);
+    const size_t n_out = bytes ? 2 * n : n;
+    hipError_t e = d_verify_.reserve((3 * n + n_out) * sizeof(uint32_t) + 256);
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(verify)");
     StagingRing &ring = ctx_->staging;
-    if (ring.verdict_cap < n) {
-        if (ring.verdict) (void)hipHostFree(ring.verdict);
-        ring.verdict = nullptr;
-        ring.verdict_cap = 0;
-        const size_t cap = std::max<size_t>(n, 4096);
-        e = hipHostMalloc((void **)&ring.verdict, cap * sizeof(uint32_t), hipHostMallocDefault);
-        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(verdict)");
-        ring.verdict_cap = cap;
-    }
+    int rc = reserve_verdict(n_out);
+    if (rc != JPGPU_OK) return rc;
     hipStream_t up = ctx_->upload_stream;
     uint32_t *d = (uint32_t *)d_verify_.ptr;
     e = hipMemcpyAsync(d, host.data(), 3 * n * sizeof(uint32_t), hipMemcpyHostToDevice, up);
     if (e == hipSuccess) e = hipMemsetAsync(d + 3 * n, 0xFF, n * sizeof(uint32_t), up);
     if (e == hipSuccess) e = launch_first_marker(up, (const uint8_t *)d_input_.ptr, d, d + 2 * n, (int)n, max_len, d + 3 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(ring.verdict, d + 3 * n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, up);
+    if (e == hipSuccess && bytes) e = launch_verdict_bytes(up, (const uint8_t *)d_input_.ptr, d, d + 2 * n, d + 3 * n, (int)n, d + 4 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(ring.verdict, d + 3 * n, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, up);
     if (e == hipSuccess) e = hipStreamSynchronize(up);
     if (e != hipSuccess) return hip_fail(e, "ingest verification");
     first.assign(ring.verdict, ring.verdict + n);
+    if (bytes) bytes->assign(ring.verdict + n, ring.verdict + 2 * n);
+    return JPGPU_OK;
+}
+
+// the context's page-locked words for small per-file results of the device (the ingest verdicts, the head lengths)
+int DeviceBatch::reserve_verdict(size_t n) {
+    StagingRing &ring = ctx_->staging;
+    if (ring.verdict_cap >= n) return JPGPU_OK;
+    if (ring.verdict) (void)hipHostFree(ring.verdict);
+    ring.verdict = nullptr;
+    ring.verdict_cap = 0;
+    const size_t cap = std::max<size_t>(n, 4096);
+    const hipError_t e = hipHostMalloc((void **)&ring.verdict, cap * sizeof(uint32_t), hipHostMallocDefault);
+    if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(verdict)");
+    ring.verdict_cap = cap;
+    return JPGPU_OK;
+}
+
+// Step 2 of the ingest for a device source, and how its heads are obtained: the caller's device memory -> the input buffer
+// (gather_device_kernel: the slots of upload_segments' layout, every byte of slack written as zero), then the head the host
+// parser needs of every file: head_walk_kernel says how long it is, head_scan_kernel where it goes, head_pack_kernel packs them.
+// Two small H2D (the pieces, the files), four launches, one D2H of the lengths, offsets and total and a synchronisation -- from
+// there on no kernel reads the caller's memory any more --, then one D2H of the packed heads and a second synchronisation (the host
+// has to know the total before it can ask for the bytes), whatever the number of files.
+int DeviceBatch::stage_device_files(std::vector<FileSegs> &files) {
+    constexpr size_t kMaxFile = 0x7FFFFFF0u;
+    const size_t n = files.size();
+    uint64_t in_off = 256;
+    for (FileSegs &f : files) {
+        f.slot = in_off;
+        if (f.len <= kMaxFile) in_off = align_up(in_off + f.len, 256);
+    }
+    input_bytes_ = in_off + 256;
+    hipError_t e = d_input_.reserve((size_t)input_bytes_);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(input)");
+    std::vector<GatherPiece> gp;
+    std::vector<DeviceFile> df(n);
+    gp.push_back({0u, 0u, 0u, 256u});  // the slack in front of the first file ...
+    for (size_t i = 0; i < n; i++) {
+        const FileSegs &f = files[i];
+        df[i] = {0u, 0u, 0u};
+        if (f.len == 0 || f.len > kMaxFile) continue;
+        df[i] = {f.slot, (uint32_t)f.len, 0u};
+        for (size_t at = 0; at < f.len; at += kGatherPieceBytes) {
+            const uint32_t m = (uint32_t)std::min<size_t>(kGatherPieceBytes, f.len - at);
+            const uint32_t pad = at + m == f.len ? (uint32_t)(align_up(f.len, 256) - f.len) : 0u;  // (the last piece: up to the slot's end)
+            gp.push_back({(uint64_t)(uintptr_t)(f.dev + at), f.slot + at, m, pad});
+        }
+        device_ingest_.files_gathered++;
+        device_ingest_.bytes_gathered += f.len;
+    }
+    gp.push_back({0u, in_off, 0u, 256u});  // ... and behind the last
+    // one device buffer: the pieces, the files, then what comes back in one copy: head_off[n + 1] (64-bit; [n] = the total), head_len[n]
+    const size_t files_at = align_up(gp.size() * sizeof(GatherPiece), 256), off_at = align_up(files_at + n * sizeof(DeviceFile), 256);
+    const size_t len_at = off_at + (n + 1) * sizeof(uint64_t), back_words = 2 * (n + 1) + n;
+    e = d_gather_.reserve(len_at + n * sizeof(uint32_t) + 256);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(gather list)");
+    int rc = reserve_verdict(back_words);
+    if (rc != JPGPU_OK) return rc;
+    StagingRing &ring = ctx_->staging;
+    hipStream_t up = ctx_->upload_stream;
+    uint8_t *d_in = (uint8_t *)d_input_.ptr, *d_list = (uint8_t *)d_gather_.ptr;
+    const DeviceFile *d_files = (const DeviceFile *)(d_list + files_at);
+    uint64_t *d_head_off = (uint64_t *)(d_list + off_at);
+    uint32_t *d_head_len = (uint32_t *)(d_list + len_at);
+    e = hipMemcpyAsync(d_list, gp.data(), gp.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, up);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(d_list + files_at, df.data(), n * sizeof(DeviceFile), hipMemcpyHostToDevice, up);
+    for (hipEvent_t &ev : gather_ev_)
+        if (e == hipSuccess && !ev) e = hipEventCreate(&ev);
+    if (e == hipSuccess) e = hipEventRecord(gather_ev_[0], up);
+    if (e == hipSuccess) e = launch_gather_device(up, (const GatherPiece *)d_list, (int)gp.size(), d_in);
+    if (e == hipSuccess) e = hipEventRecord(gather_ev_[1], up);
+    if (e == hipSuccess) e = launch_head_walk(up, d_in, d_files, (int)n, d_head_len);
+    if (e == hipSuccess) e = launch_head_scan(up, d_head_len, (int)n, d_head_off);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(ring.verdict, d_head_off, back_words * sizeof(uint32_t), hipMemcpyDeviceToHost, up);
+    if (e == hipSuccess) e = hipStreamSynchronize(up);  // (`gp` and `df` are local, pageable vectors; the caller's memory is free from here)
+    if (e == hipSuccess) e = hipEventElapsedTime(&device_ingest_.gather_ms, gather_ev_[0], gather_ev_[1]);
+    if (e != hipSuccess) return hip_fail(e, "gather of device files");
+    if (n == 0) return JPGPU_OK;
+    std::vector<uint64_t> head_off(n + 1);
+    memcpy(head_off.data(), ring.verdict, (n + 1) * sizeof(uint64_t));
+    const std::vector<uint32_t> head_len(ring.verdict + 2 * (n + 1), ring.verdict + back_words);
+    const uint64_t total = head_off[n];
+    for (size_t i = 0; i < n; i++)
+        if (head_len[i] & kHeadGaveUp) device_ingest_.walker_giveups++;
+    device_ingest_.head_bytes = total;
+    if (total == 0) return JPGPU_OK;
+    if (ring.heads_cap < total) {
+        if (ring.heads) (void)hipHostFree(ring.heads);
+        ring.heads = nullptr;
+        ring.heads_cap = 0;
+        const size_t cap = std::max<size_t>((size_t)total, 4u << 20);
+        e = hipHostMalloc((void **)&ring.heads, cap, hipHostMallocDefault);
+        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(heads)");
+        ring.heads_cap = cap;
+    }
+    e = d_heads_.reserve((size_t)total + 256);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(heads)");
+    e = launch_head_pack(up, d_in, d_files, (int)n, d_head_len, d_head_off, (uint8_t *)d_heads_.ptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(ring.heads, d_heads_.ptr, (size_t)total, hipMemcpyDeviceToHost, up);
+    if (e == hipSuccess) e = hipStreamSynchronize(up);
+    if (e != hipSuccess) return hip_fail(e, "heads of device files");
+    for (size_t i = 0; i < n; i++) {
+        if (files[i].len > kMaxFile) continue;
+        files[i].base = ring.heads + head_off[i];
+        // (a hint: what the host reads of it is bounded by the file here too)
+        files[i].base_len = std::min<size_t>(head_len[i] & ~kHeadGaveUp, std::min<size_t>(files[i].len, kDeviceHeadMax));
+    }
+    return JPGPU_OK;
+}
+
+// How a whole device file is obtained: from its slot in the input buffer, one D2H per listed file, issued together, one
+// synchronisation.  The ingest calls it at most twice: behind the header-only plans (heads that did not do) and in front of step 4
+// (plans the device did not confirm, or whose EOI does not close the file).
+int DeviceBatch::fetch_device_files(std::vector<FileSegs> &files, const std::vector<int> &which) {
+    if (which.empty()) return JPGPU_OK;
+    hipStream_t up = ctx_->upload_stream;
+    for (int i : which) {
+        FileSegs &f = files[(size_t)i];
+        f.gathered.resize(f.len);
+        const hipError_t e = hipMemcpyAsync(f.gathered.data(), (const uint8_t *)d_input_.ptr + f.slot, f.len, hipMemcpyDeviceToHost, up);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(up);
+            return hip_fail(e, "hipMemcpyAsync(device file to the host)");
+        }
+        device_ingest_.files_downloaded++;
+        device_ingest_.bytes_downloaded += f.len;
+    }
+    const hipError_t e = hipStreamSynchronize(up);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(device files to the host)");
+    for (int i : which) {
+        FileSegs &f = files[(size_t)i];
+        f.base = f.gathered.data();
+        f.base_len = f.len;
+    }
     return JPGPU_OK;
 }
 
 int DeviceBatch::upload_single_job(const ScanJob &job, int format, const void *initial_output, size_t initial_output_bytes) {
     whole_files_ = false;
+    device_ingest_ = jpgpu_device_ingest_stats();
     if (format < 0 || format >= kNumOutputFormats) return fail(JPGPU_ERR_ARGUMENT, "unknown format");
     format_ = format;
     images_.assign(1, ImagePlan());
@@ -979,6 +1244,7 @@ int DeviceBatch::upload_single_job(const ScanJob &job, int format, const void *i
 
 int DeviceBatch::upload_progressive_frame(const ProgressiveFrame &frame, const uint8_t *file, size_t file_len, int sof, int format) {
     whole_files_ = false;
+    device_ingest_ = jpgpu_device_ingest_stats();
     if (format < 0 || format >= kNumOutputFormats) return fail(JPGPU_ERR_ARGUMENT, "unknown format");
     format_ = format;
     images_.assign(1, ImagePlan());
@@ -1006,6 +1272,7 @@ int DeviceBatch::upload_progressive_frame(const ProgressiveFrame &frame, const u
 
 int DeviceBatch::upload_progressive_scan(const ProgressiveFrame &frame, int scan_index, bool first_scan) {
     whole_files_ = false;
+    device_ingest_ = jpgpu_device_ingest_stats();
     if (scan_index < 0 || scan_index >= (int)frame.scans().size()) return fail(JPGPU_ERR_ARGUMENT, "progressive scan index out of range");
     format_ = JPGPU_FMT_INTERLEAVED_U8;  // no samples are produced by a scan; the smallest output layout
     images_.assign(1, ImagePlan());
@@ -1079,6 +1346,7 @@ int DeviceBatch::rerun_failed_progressive_scan(bool first_scan) {
 
 int DeviceBatch::upload_progressive_dispose(const ProgressiveFrame &frame, int format) {
     whole_files_ = false;
+    device_ingest_ = jpgpu_device_ingest_stats();
     if (format < 0 || format >= kNumOutputFormats) return fail(JPGPU_ERR_ARGUMENT, "unknown format");
     format_ = format;
     images_.assign(1, ImagePlan());
@@ -1105,6 +1373,7 @@ int DeviceBatch::upload_progressive_dispose(const ProgressiveFrame &frame, int f
 
 int DeviceBatch::upload_frames(const jpgpu_frame *frames, const uint16_t *qt, int n, int format) {
     whole_files_ = false;
+    device_ingest_ = jpgpu_device_ingest_stats();
     if (n < 0 || (n > 0 && (!frames || !qt))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_frames: null argument");
     if (format < 0 || format >= kNumOutputFormats) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_frames: unknown format");
     format_ = format;

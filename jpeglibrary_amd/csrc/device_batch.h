@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <chrono>
 #include <map>
 #include <string>
 #include <vector>
@@ -16,6 +17,10 @@ namespace jpgpu {
 // capped at 16; JPGPU_HOST_THREADS overrides.  granted_host_cpus() is the same figure without the cap and the override.
 int default_host_threads();
 int granted_host_cpus();
+// Caller memory a kernel is about to read (jpgpu_encoder_upload_device, jpgpu_batch_upload_device): 0 = [p, p + bytes) is device
+// memory of `device` inside one allocation; 1 = hipPointerGetAttributes does not report p as device memory of that device (host,
+// pinned host and managed memory among them); 2 = the bytes do not lie inside one allocation (hipMemGetAddressRange).
+int check_device_range(int device, const void *p, size_t bytes);
 }  // namespace jpgpu
 
 // Pinned staging ring of a context: the caller's (pageable) file bytes are copied into it by the host crew and leave it
@@ -29,6 +34,8 @@ struct StagingRing {
     hipEvent_t drained[kMaxSlots] = {};  // recorded behind the DMA that reads the slot
     uint32_t *verdict = nullptr;      // pinned: per-file results of the ingest verification kernel
     size_t verdict_cap = 0;
+    uint8_t *heads = nullptr;         // pinned: the packed heads of the files of a device upload (jpgpu_batch_upload_device)
+    size_t heads_cap = 0;
 };
 
 struct jpgpu_ctx {
@@ -116,6 +123,10 @@ class DeviceBatch {
     // segments_per_file[i] entries of `segments`.  flags & JPGPU_UPLOAD_PINNED: every segment lies in page-locked memory
     // (jpgpu_host_alloc / jpgpu_host_register) and is DMA'd to HBM from where it lies -- no staging copy, no crew time.
     int upload_segments(const jpgpu_segment *segments, const int *segments_per_file, int n, int format, unsigned flags);
+    // ... and for whole files in device memory of the context's device (jpgpu_batch_upload_device): copied into the input buffer
+    // on the device; the host sees their heads, and whole only the files that need the full marker walks.
+    int upload_device(const void *const *device_jpeg, const size_t *len, int n, int format);
+    const jpgpu_device_ingest_stats &device_ingest_stats() const { return device_ingest_; }
     // One progressive frame collected by the JpegDecoder mirror: its entropy scans + the Dispose() pass.
     int upload_progressive_frame(const ProgressiveFrame &frame, const uint8_t *file, size_t file_len, int sof, int format);
     // The per-scan boundary (jpgpu_progressive_*): ONE entropy scan of the frame (index into frame.scans()) accumulating into
@@ -208,7 +219,12 @@ class DeviceBatch {
     void plan_file_full(const uint8_t *file, size_t len, int index, FilePlan &fp) const;
     void plan_swallowed_terminator(FilePlan &fp, const uint8_t *file, size_t len, bool identify_is_clean) const;
     struct FileSegs;
+    int begin_ingest(int n, int format);
+    int ingest_files(std::vector<FileSegs> &files, unsigned flags, std::chrono::steady_clock::time_point t_begin);
     int stage_files(WorkCrew &crew, const std::vector<FileSegs> &files, const std::vector<FilePlan> &plans, bool pinned);
+    int stage_device_files(std::vector<FileSegs> &files);
+    int fetch_device_files(std::vector<FileSegs> &files, const std::vector<int> &which);
+    int reserve_verdict(size_t n);
     // device work of this batch issued since its last sync(): uploads are ordered behind it (an upload right
     // after an un-synced decode must not overwrite what that decode's kernels still read)
     int mark_work();
@@ -216,10 +232,12 @@ class DeviceBatch {
     std::pair<const uint8_t *, size_t> arena_span_ = {nullptr, 0};  // JPGPU_UPLOAD_PINNED_ARENA: the span the device copy mirrors
     hipEvent_t done_ev_ = nullptr;
     bool work_in_flight_ = false;
-    int verify_plans(const std::vector<FilePlan> &plans, const std::vector<int> &spec, std::vector<uint32_t> &first);
+    int verify_plans(const std::vector<FilePlan> &plans, const std::vector<int> &spec, std::vector<uint32_t> &first, std::vector<uint32_t> *bytes);
     bool whole_files_ = false;     // the last upload was whole files (upload_files / upload_segments): d_input_ holds them as they came
     bool files_resident_ = false;  // layout_and_upload: the files are in d_input_ already (staged by upload_files)
     IngestStats ingest_;
+    jpgpu_device_ingest_stats device_ingest_ = {};
+    hipEvent_t gather_ev_[2] = {};  // around the gather of a device upload (device_ingest_.gather_ms)
     DevBuffer d_verify_;
     int fetch_status();
     int clear_partial_outputs();
@@ -275,7 +293,8 @@ class DeviceBatch {
     uint64_t total_blocks_ = 0, out_bytes_ = 0, planes_bytes_ = 0, input_bytes_ = 0, compressed_bytes_ = 0, total_pixels_ = 0;
     DevBuffer d_planes_;  // EXTENDED_U16: K3's PLANAR_I16 output, converted by extend_u16_kernel
     DevBuffer d_extend_desc_;
-    DevBuffer d_gather_;  // JPGPU_UPLOAD_PINNED: the piece list of gather_pinned_kernel
+    DevBuffer d_gather_;  // JPGPU_UPLOAD_PINNED: the piece list of gather_pinned_kernel; a device upload: its pieces, files and head lengths
+    DevBuffer d_heads_;   // a device upload: the packed heads
     bool in_decode_request_ = false;  // the last entropy stage was issued by decode() (fetch_status's fallback re-issues the same thing)
     uint32_t total_ends_ = 0;
 

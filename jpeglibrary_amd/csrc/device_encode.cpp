@@ -519,19 +519,9 @@ int EncodeBatch::check_device_pixels(const uint8_t *const *pixels) {
         const std::string which = "jpgpu_encoder_upload_device: image " + std::to_string(i);
         const uint8_t *p = pixels[i];
         const size_t bytes = (size_t)im.width * im.height * im.in_components;
-        hipPointerAttribute_t attr;
-        memset(&attr, 0, sizeof attr);
-        hipError_t e = hipPointerGetAttributes(&attr, p);
-        if (e != hipSuccess) (void)hipGetLastError();  // (host memory the runtime has never seen: an error of this query, not of the stream)
-        if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx_->device)
-            return fail(JPGPU_ERR_ARGUMENT, which + ": the pixels are not in device memory of the context's device");
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
-        if (e != hipSuccess) (void)hipGetLastError();
-        const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)p;
-        if (e != hipSuccess || at < lo || at - lo > size || bytes > size - (at - lo))
-            return fail(JPGPU_ERR_ARGUMENT, which + ": " + std::to_string(bytes) + " bytes of pixels do not lie inside one device allocation");
+        const int where = check_device_range(ctx_->device, p, bytes);
+        if (where == 1) return fail(JPGPU_ERR_ARGUMENT, which + ": the pixels are not in device memory of the context's device");
+        if (where == 2) return fail(JPGPU_ERR_ARGUMENT, which + ": " + std::to_string(bytes) + " bytes of pixels do not lie inside one device allocation");
     }
     return JPGPU_OK;
 }

@@ -170,6 +170,17 @@ hipError_t launch_gather_pinned(hipStream_t stream, const GatherPiece *pieces, i
 hipError_t launch_first_marker(hipStream_t stream, const uint8_t *data, const void *segs, const uint32_t *seg_hi, int n_segs,
                                uint32_t max_len, uint32_t *first);
 
+// jpgpu_batch_upload_device (k0_device_files.hip): files from the caller's device memory into the input buffer; the length of the
+// head the host parser needs of each (kHeadGaveUp: the walk gave up) and the heads packed at head_off[i]; the two bytes at each
+// verdict of first_marker_kernel (low byte first, 0 = no such position)
+hipError_t launch_gather_device(hipStream_t stream, const GatherPiece *pieces, int n_pieces, uint8_t *dst);
+hipError_t launch_head_walk(hipStream_t stream, const uint8_t *data, const DeviceFile *files, int n, uint32_t *head_len);
+hipError_t launch_head_scan(hipStream_t stream, const uint32_t *head_len, int n, uint64_t *head_off);  // head_off[n] = the total
+hipError_t launch_head_pack(hipStream_t stream, const uint8_t *data, const DeviceFile *files, int n, const uint32_t *head_len,
+                            const uint64_t *head_off, uint8_t *heads);
+hipError_t launch_verdict_bytes(hipStream_t stream, const uint8_t *data, const void *segs, const uint32_t *seg_hi, const uint32_t *first,
+                                int n, uint32_t *bytes);
+
 // KT: symbol-level Huffman transcode of baseline scans (JpegOptimizer): mode 0 count, 1 measure, 2 emit (kt_transcode.hip)
 struct EncHuffTable;
 hipError_t launch_transcode(hipStream_t stream, int mode, const uint8_t *udata, const uint8_t *input, const DevScan *scans,
