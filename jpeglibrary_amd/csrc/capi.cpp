@@ -450,6 +450,17 @@ long long jpgpu_debug_batch_split_flags(jpgpu_batch *b, int i, unsigned long lon
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "flag words are 64 bits");
     return b ? b->impl.debug_split_flags(i, reinterpret_cast<uint64_t *>(dst), cap_words) : -1;
 }
+// (tests only, not part of include/jpgpu.h: tests/test_marker_index_gpu.py) K1 alone; what it left for one scan job; which form it takes
+static int run_marker_index_alone(DeviceBatch &impl) {
+    const int rc = impl.run_marker_index();
+    return rc != JPGPU_OK ? rc : impl.sync();
+}
+int jpgpu_debug_batch_run_marker_index(jpgpu_batch *b) { JPGPU_GUARD(b, run_marker_index_alone(b->impl)); }
+long long jpgpu_debug_batch_marker_index(jpgpu_batch *b, int i, int k, uint32_t *head, uint32_t *ends, uint32_t *ends_u, size_t cap_ends, uint8_t *udata,
+                                         size_t cap_udata) {
+    return b ? b->impl.debug_marker_index(i, k, head, ends, ends_u, cap_ends, udata, cap_udata) : -1;
+}
+int jpgpu_debug_batch_k1_onepass(const jpgpu_batch *b) { return b ? (b->impl.debug_k1_onepass() ? 1 : 0) : -1; }
 int jpgpu_batch_download_output(jpgpu_batch *b, int i, void *dst, size_t cap) { JPGPU_GUARD(b, b->impl.download_output(i, dst, cap)); }
 int jpgpu_batch_download_coefficients(jpgpu_batch *b, int i, int16_t *dst, size_t cap_blocks) {
     JPGPU_GUARD(b, b->impl.download_coefficients(i, dst, cap_blocks));

@@ -166,7 +166,7 @@ struct alignas(16) DevScanStatus {
     uint32_t first_error;   // (interval << 8) | detail of the lowest failing interval, 0xFFFFFFFF = none
     uint32_t decoded_mcus;  // MCUs decoded (limits the IDCT pass when EOI came early)
     uint32_t end_pos;       // byte offset (from data_off) of the terminating marker / end of data
-    uint32_t pad[3];        // [0] unstuffed length; [1] progressive scans: restart units completed (0xFFFFFFFF = finished); sequential
+    uint32_t pad[3];        // [0] unstuffed length = where the closing entry's FF FF stands in udata; [1] progressive scans: restart units completed (0xFFFFFFFF = finished); sequential
                             // scans: kFailBlockBase - the failing block, 0 = none;
                             // [2] optimizer walk: bits of the stream left unread behind the scan's last block
 };

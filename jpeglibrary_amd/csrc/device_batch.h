@@ -164,6 +164,9 @@ class DeviceBatch {
     }
     void *coefs_device(uint64_t *total_blocks);  // dense int16[blocks][64], whatever form K2 handed the scans over in
     long long debug_split_flags(int i, uint64_t *dst, size_t cap_words);  // tests: the flag words K2 left for image i (-1: not split)
+    // tests: what K1 left for scan job k of image i (tests/test_marker_index_gpu.py); -1: the image failed at upload or has no such job
+    long long debug_marker_index(int i, int k, uint32_t head[10], uint32_t *ends, uint32_t *ends_u, size_t cap_ends, uint8_t *udata, size_t cap_udata);
+    bool debug_k1_onepass() const { return k1_onepass_; }
     int download_output(int i, void *dst, size_t cap);
     int download_coefficients(int i, int16_t *dst, size_t cap_blocks);
     int upload_coefficients(int i, const int16_t *src, size_t nblocks);

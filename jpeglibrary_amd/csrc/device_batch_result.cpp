@@ -380,6 +380,30 @@ long long DeviceBatch::debug_split_flags(int i, uint64_t *dst, size_t cap_words)
     return e == hipSuccess ? (long long)n : -1;
 }
 
+// Tests only: the marker index of scan job k of image i (ImagePlan::jobs[k]) as K1 left it.  head = {data_off & 15, data_len, dri, n_intervals,
+// total_mcus} of the host's DevScan, then the device's DevScanStatus words {n_ends, terminator, decoded_mcus, end_pos, pad[0] (unstuffed
+// length)}; ends[0 .. n_ends), ends_u[0 .. n_ends), udata[0 .. pad[0] + 2).  Returns n_ends; -1 for an image that failed at upload or has
+// no such job; -2 where the status does not fit the scan or the caller's room (head is filled in: the caller reports it).
+long long DeviceBatch::debug_marker_index(int i, int k, uint32_t head[10], uint32_t *ends, uint32_t *ends_u, size_t cap_ends, uint8_t *udata, size_t cap_udata) {
+    const ImagePlan *img = image(i);
+    if (!img || !head || img->status != JPGPU_OK || k < 0 || (size_t)k >= img->jobs.size() || !d_status_.ptr) return -1;
+    const size_t j = (size_t)img->jobs[(size_t)k];
+    const DevScan &s = h_scans_[j];
+    if (s.kind == kScanFrameOnly || sync() != JPGPU_OK) return -1;
+    DevScanStatus st;
+    if (hipMemcpy(&st, (const DevScanStatus *)d_status_.ptr + j, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    const uint32_t h[10] = {(uint32_t)(s.data_off & 15u), s.data_len, s.dri, s.n_intervals, s.total_mcus, st.n_ends, st.terminator, st.decoded_mcus, st.end_pos, st.pad[0]};
+    memcpy(head, h, sizeof h);
+    const uint64_t ubytes = (uint64_t)st.pad[0] + 2;
+    if (st.n_ends > s.n_intervals || st.n_ends > cap_ends || ubytes > cap_udata || s.data_off + ubytes > d_unstuffed_.cap) return -2;
+    if (st.n_ends != 0 && (!ends || !ends_u)) return -2;
+    if (st.n_ends != 0 && (hipMemcpy(ends, (const uint32_t *)d_ends_.ptr + s.ends_off, (size_t)st.n_ends * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                           hipMemcpy(ends_u, (const uint32_t *)d_ends_u_.ptr + s.ends_off, (size_t)st.n_ends * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        return -1;
+    if (!udata || hipMemcpy(udata, (const uint8_t *)d_unstuffed_.ptr + s.data_off, (size_t)ubytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return (long long)st.n_ends;
+}
+
 int DeviceBatch::upload_coefficients(int i, const int16_t *src, size_t nblocks) {
     const ImagePlan *img = image(i);
     if (!img || !src) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_coefficients: bad argument");

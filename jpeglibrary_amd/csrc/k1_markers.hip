@@ -439,7 +439,9 @@ __device__ __forceinline__ void marker_write_chunk(const uint8_t *__restrict__ d
         const uint64_t covered = (uint64_t)found * (s.dri ? s.dri : s.total_mcus);
         st.decoded_mcus = covered < s.total_mcus ? (uint32_t)covered : s.total_mcus;
         st.end_pos = lp;
-        st.pad[0] = ubase + keep_total;
+        // unstuffed length = where the closing entry's FF FF stands in udata: a real closing entry is among the bytes counted
+        // (keep_total has its two), the pseudo entry of data that ran out stands behind them
+        st.pad[0] = ubase + keep_total - ((cap_here || term_here) ? 2u : 0u);
         st.pad[1] = st.pad[2] = 0;
         status[wk.scan] = st;
     }
@@ -656,9 +658,10 @@ __global__ __launch_bounds__(kScanThreads, JPGPU_K1_WAVES) void marker_onepass_k
     __syncthreads();
     uint32_t x_rst = sh_mine[0], x_keep = sh_mine[1], x_term = sh_mine[2];
     if (sh_ok == 0) {
-        // Out of patience (it cannot happen while the groups are handed out by ticket; the bound is there so that nothing can hang,
-        // and the tests set it to zero): the group counts the chunks in front of it ITSELF -- slow, and dependent on nobody -- and
-        // goes on as if it had been told.  (The first form left here and had the host issue the three kernels: the kernels
+        // Out of patience.  The groups are taken by workgroup index, not by ticket: that the groups in front of this one are running
+        // or done is the dispatcher's habit, not a promise, and the bound is what makes a different dispatch order slow rather than
+        // wrong or stuck (the tests set it to zero): the group counts the chunks in front of it ITSELF -- slow, and dependent on
+        // nobody -- and goes on as if it had been told.  (The first form left here and had the host issue the three kernels: the kernels
         // enqueued behind this one ran on a half-written index in the meantime.)
         x_rst = 0, x_keep = 0, x_term = kInf;
         for (uint32_t ch = 0; ch < first_chunk; ch++) {

@@ -4,6 +4,8 @@ Bit-exact everywhere: coefficients (Huffman stage), samples (IDCT stage), and ev
 Mirrors the reference's own decode tests (tests/JpegLibrary.Tests/Decoder/HuffmanSequentialDecodeTests.cs:23-43).
 """
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -438,12 +440,7 @@ def test_dri0_rounds_are_enqueued_ahead_and_checked_when_the_caller_waits(monkey
         assert np.array_equal(b4.output(i), r), i
 
 
-def test_marker_index_in_one_pass_and_its_bounded_wait(monkeypatch):
-    """Round 5: K1 reads and classifies the entropy segments once -- a workgroup per four 4 KiB chunks publishes its summary and finds the
-    running sums of the groups in front of it by looking back (marker_onepass_kernel) -- where round 4 counted, prefixed and wrote in
-    three kernels that read them twice.  Same ends / unstuffed data / statuses (ref: JpegBitReader.cs:95-138, the restart hand-off of
-    JpegHuffmanBaselineScanDecoder.cs:139-163): every case below against the restatement, in one batch and decode after decode.
-    A spin budget of zero makes any wait a give-up: the group then counts its predecessors itself -- same results."""
+def _marker_index_files():
     files = [jpegsynth.encode(1024, 768, "420", 75, 4, seed=31), jpegsynth.encode(640, 368, "444", 90, 1, seed=32), jpegsynth.encode(800, 600, "422", 60, 0, seed=33),
              jpegsynth.encode(333, 211, "444", 60, 8, seed=10, noninterleaved=True), read_jpeg("progress.jpg"), read_jpeg("yellowcat_progressive_restart.jpg"),
              jpegsynth.encode(1920, 1080, "420", 90, 4, seed=34)]
@@ -452,7 +449,42 @@ def test_marker_index_in_one_pass_and_its_bounded_wait(monkeypatch):
     for f in files:
         px, _, err = po.decode_8bit_partial(f)
         refs.append((px, err))
+    return files, refs
+
+
+def _k1_onepass(batch):
+    """(an accessor for tests, not part of the C ABI of include/jpgpu.h) 1: the batch takes the one-pass marker index, 0: the three kernels"""
+    import ctypes as C
+
+    from jpeglibrary_amd import _capi
+
+    fn = C.CDLL(_capi.LIB_PATH).jpgpu_debug_batch_k1_onepass
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
+    return fn(batch._h)
+
+
+def _k1_three_pass_child():
+    files, refs = _marker_index_files()
     b = jl.Batch().upload(files, jl.FMT_INTERLEAVED_U8)
+    assert _k1_onepass(b) == 0, "JPGPU_K1_THREE_PASS=1 did not select the three-kernel form"
+    for _ in range(2):
+        b.decode().sync()
+        for i, (px, err) in enumerate(refs):
+            assert (b.result(i).status != 0) == (err is not None), i
+            assert np.array_equal(b.output(i), px), i
+    b.close()
+    print("K1FORM three_pass files %d" % len(files))
+
+
+def test_marker_index_in_one_pass_and_its_bounded_wait(monkeypatch):
+    """Round 5: K1 reads and classifies the entropy segments once -- a workgroup per four 4 KiB chunks publishes its summary and finds the
+    running sums of the groups in front of it by looking back (marker_onepass_kernel) -- where round 4 counted, prefixed and wrote in
+    three kernels that read them twice.  Same ends / unstuffed data / statuses (ref: JpegBitReader.cs:95-138, the restart hand-off of
+    JpegHuffmanBaselineScanDecoder.cs:139-163): every case below against the restatement, in one batch and decode after decode.
+    A spin budget of zero makes any wait a give-up: the group then counts its predecessors itself -- same results."""
+    files, refs = _marker_index_files()
+    b = jl.Batch().upload(files, jl.FMT_INTERLEAVED_U8)
+    assert _k1_onepass(b) == 1
     for _ in range(3):  # (the descriptors are not cleared between decodes: tags)
         b.decode().sync()
         for i, (px, err) in enumerate(refs):
@@ -473,10 +505,12 @@ def test_marker_index_in_one_pass_and_its_bounded_wait(monkeypatch):
             assert np.array_equal(b.output(i), px), i
     b.close()
     monkeypatch.delenv("JPGPU_K1_SPIN_BUDGET")
-    monkeypatch.setenv("JPGPU_K1_THREE_PASS", "1")
-    outs, res = jl.decode_batch(files)
-    for i, (px, err) in enumerate(refs):
-        assert np.array_equal(outs[i], px), i
+    # the three-kernel form (JPGPU_K1_THREE_PASS is read once per process: a child of its own, which asserts that the one-pass form is off)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, JPGPU_K1_THREE_PASS="1", PYTHONPATH=os.pathsep.join([root, os.path.join(root, "tests")]))
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "k1_three_pass"], env=env, capture_output=True, text=True, timeout=600)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("K1FORM ")]
+    assert r.returncode == 0 and lines == ["K1FORM three_pass files %d" % len(files)], r.stdout[-2000:] + r.stderr[-3000:]
 
 
 def test_marker_index_tile_writer_on_dense_markers_at_every_alignment():
@@ -1897,3 +1931,6 @@ def test_jpeg_encoder_mirror_takes_the_callers_quantization_tables():
         b.set_quantization_table(0, 2, np.ones(64))
     b.close()
 
+
+if __name__ == "__main__":
+    {"k1_three_pass": _k1_three_pass_child}[sys.argv[1]]()
