@@ -91,7 +91,18 @@ typedef enum jpgpu_format {
      * out_offset + c * W * H, out_bytes = 3 * W * H -- the uint8[3, H, W] layout tensor code consumes, written by K3 itself.
      * The same conversion (ConvertYCbCr8ToRgb24 applied to the "O2" samples; 1-component frames with Cb = Cr = 128 give three
      * equal planes) and the same refusals as RGB_U8.  jpgpu_image_info.plane[0..2] describe the planes. */
-    JPGPU_FMT_RGB_PLANAR_U8 = 7
+    JPGPU_FMT_RGB_PLANAR_U8 = 7,
+    /* RGB_PLANAR_U8's planes with a wider sample T = IEEE binary16 / binary32 -- the float16 / float32 [3, H, W] tensor a model or a float
+     * resize starts from, written by K3 itself: plane c at out_offset + c * W * H * sizeof(T), out_bytes = 3 * W * H * sizeof(T);
+     * jpgpu_image_info.plane[c] = {c * W * H * sizeof(T) (bytes), W, H, W (samples)}.  Sample (c, y, x), with u the byte RGB_PLANAR_U8
+     * holds there and the constants of jpgpu_batch_set_output_affine (default: scale 1, bias 0):
+     *     t = (float)u * scale[c]     one float32 multiply, rounded to nearest even
+     *     v = t + bias[c]             one float32 add, rounded to nearest even; never fused with the multiply
+     *     F32: v      F16: v rounded to nearest even to binary16 (subnormals kept, overflow to infinity)
+     * i.e. numpy's (u.astype(float32) * float32(scale[c]) + float32(bias[c])).astype(float16).  The same refusals as RGB_U8, per image.  No
+     * bfloat16, no interleaved (HWC) float form. */
+    JPGPU_FMT_RGB_PLANAR_F16 = 8,
+    JPGPU_FMT_RGB_PLANAR_F32 = 9
 } jpgpu_format;
 
 typedef struct jpgpu_ctx jpgpu_ctx;
@@ -177,7 +188,7 @@ typedef struct jpgpu_image_info {
     uint64_t total_blocks;
     uint64_t out_offset, out_bytes;   /* in the batch output buffer */
     uint64_t coef_offset;             /* first block index in the batch coefficient buffer */
-    jpgpu_plane_info plane[4];        /* planar formats only (PLANAR_U8, PLANAR_I16, RGB_PLANAR_U8) */
+    jpgpu_plane_info plane[4];        /* planar formats only (PLANAR_U8, PLANAR_I16, RGB_PLANAR_U8 / _F16 / _F32) */
 } jpgpu_image_info;
 
 typedef struct jpgpu_image_result {
@@ -306,6 +317,8 @@ int jpgpu_batch_plan_stats(const jpgpu_batch *b, jpgpu_plan_stats *stats);
  * n must be JPGPU_IDCT_LAYOUT_CLASSES. */
 #define JPGPU_IDCT_LAYOUT_CLASSES 6
 int jpgpu_batch_idct_work(const jpgpu_batch *b, int32_t *counts, int n);
+/* ... and how many of them belong to scans the planner hands over to K3 as half-line planes (the split form of the class's kernel). */
+int jpgpu_batch_idct_split_work(const jpgpu_batch *b, int32_t *counts, int n);
 
 /* Coefficient hand-off for multi-scan (progressive, SOF2) images -- BASELINE config 5's "coefficient accumulate then single
  * IDCT pass": the caller's progressive entropy decoder accumulates the coefficient store, the GPU runs what
@@ -332,6 +345,10 @@ int jpgpu_batch_decode(jpgpu_batch *b);
 /* Individual stages, for stage-level parity tests and profiling. */
 int jpgpu_batch_run_entropy(jpgpu_batch *b); /* marker index + Huffman -> coefficient buffer */
 int jpgpu_batch_run_idct(jpgpu_batch *b);    /* coefficient buffer -> output */
+/* RGB_PLANAR_F16 / _F32: the per-channel constants of the output stage (see the formats).  They belong to the batch, not to an upload: they
+ * hold from the next jpgpu_batch_decode / jpgpu_batch_run_idct on, without a new upload, until they are set again.  A NULL pointer or a
+ * constant that is not finite: JPGPU_ERR_ARGUMENT, and the constants in force stay.  The other formats never read them. */
+int jpgpu_batch_set_output_affine(jpgpu_batch *b, const float scale[3], const float bias[3]);
 int jpgpu_batch_sync(jpgpu_batch *b);
 
 int jpgpu_batch_size(const jpgpu_batch *b);

@@ -13,6 +13,7 @@ OK, ERR_INVALID_DATA, ERR_INVALID_OPERATION, ERR_NOT_SUPPORTED, ERR_ARGUMENT, ER
 FMT_INTERLEAVED_U8, FMT_PLANAR_U8, FMT_PLANAR_I16, FMT_RGB_U8, FMT_RGBA_U8, FMT_EXTENDED_U16 = 0, 1, 2, 3, 4, 5
 FMT_INTERLEAVED_U8_SCALED = 6
 FMT_RGB_PLANAR_U8 = 7
+FMT_RGB_PLANAR_F16, FMT_RGB_PLANAR_F32 = 8, 9
 
 DETAIL_NAMES = {0: "NONE", 1: "INVALID_HUFFMAN_CODE", 2: "MARKER_IN_DATA", 3: "STREAM_ENDED", 4: "EXPECT_RESTART",
                 5: "MISSING_TABLE", 6: "UNSUPPORTED_FRAME", 7: "BAD_HEADER", 8: "EARLY_EOI", 9: "UNEXPECTED_END"}
@@ -160,6 +161,7 @@ SYMBOLS = [
     ("jpgpu_sizeof_plan_stats", C.c_size_t, []),
     ("jpgpu_batch_plan_stats", C.c_int, [_P, C.POINTER(PlanStats)]),
     ("jpgpu_batch_idct_work", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
+    ("jpgpu_batch_idct_split_work", C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
     ("jpgpu_batch_progressive_fallbacks", C.c_int, [_P]),
     ("jpgpu_sizeof_progressive_plan", C.c_size_t, []),
     ("jpgpu_batch_progressive_plan", C.c_int, [_P, C.POINTER(ProgressivePlan)]),
@@ -176,6 +178,7 @@ SYMBOLS = [
     ("jpgpu_batch_decode", C.c_int, [_P]),
     ("jpgpu_batch_run_entropy", C.c_int, [_P]),
     ("jpgpu_batch_run_idct", C.c_int, [_P]),
+    ("jpgpu_batch_set_output_affine", C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("jpgpu_batch_sync", C.c_int, [_P]),
     ("jpgpu_batch_size", C.c_int, [_P]),
     ("jpgpu_batch_image_info", C.c_int, [_P, C.c_int, C.POINTER(ImageInfo)]),

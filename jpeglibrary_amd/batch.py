@@ -17,6 +17,27 @@ FMT_INTERLEAVED_U8, FMT_PLANAR_U8, FMT_PLANAR_I16 = _capi.FMT_INTERLEAVED_U8, _c
 FMT_RGB_U8, FMT_RGBA_U8, FMT_EXTENDED_U16 = _capi.FMT_RGB_U8, _capi.FMT_RGBA_U8, _capi.FMT_EXTENDED_U16
 FMT_INTERLEAVED_U8_SCALED = _capi.FMT_INTERLEAVED_U8_SCALED
 FMT_RGB_PLANAR_U8 = _capi.FMT_RGB_PLANAR_U8
+FMT_RGB_PLANAR_F16, FMT_RGB_PLANAR_F32 = _capi.FMT_RGB_PLANAR_F16, _capi.FMT_RGB_PLANAR_F32
+# the sample type of the formats that are one dense array per image: numpy dtype and the typestr of __cuda_array_interface__
+_SAMPLE_DTYPES = {FMT_RGB_PLANAR_F16: np.float16, FMT_RGB_PLANAR_F32: np.float32}
+_RGB_PLANES = (FMT_RGB_PLANAR_U8, FMT_RGB_PLANAR_F16, FMT_RGB_PLANAR_F32)
+
+
+def _typestr(fmt):
+    """__cuda_array_interface__ typestr of a format's samples: "|u1", or "<f2" / "<f4" for RGB_PLANAR_F16 / _F32"""
+    return np.dtype(_SAMPLE_DTYPES.get(fmt, np.uint8)).str
+
+
+def affine_from_mean_std(mean, std):
+    """The constants of Batch.set_output_affine that make RGB_PLANAR_F16 / _F32 hold (u / 255 - mean[c]) / std[c]: mean and std per channel
+    (R, G, B) in 0..1 units, as model code states them.  scale = 1 / (255 * std), bias = -mean / std, computed in float64 and rounded once
+    to float32.  -> (scale, bias), two float32[3] arrays."""
+    mean, std = np.asarray(mean, dtype=np.float64).reshape(-1), np.asarray(std, dtype=np.float64).reshape(-1)
+    if mean.shape != (3,) or std.shape != (3,):
+        raise ValueError("mean and std are three values each, one per channel (R, G, B)")
+    if not (np.all(np.isfinite(mean)) and np.all(np.isfinite(std))) or np.any(std == 0):
+        raise ValueError("mean and std must be finite and std non-zero")
+    return (1.0 / (255.0 * std)).astype(np.float32), (-mean / std).astype(np.float32)
 IDCT_LAYOUT_CLASSES = 6  # JPGPU_IDCT_LAYOUT_CLASSES: generic, YCbCr 1x1 / 2x1 / 2x2, gray, store holding samples
 
 
@@ -29,9 +50,9 @@ class _DeviceView:
     """What torch.as_tensor wraps without a copy: a span of a batch's output buffer described by __cuda_array_interface__ (version 2).
     torch holds a reference to this object for as long as any tensor made from it lives, and this object holds the batch."""
 
-    def __init__(self, batch, ptr, shape):
+    def __init__(self, batch, ptr, shape, typestr="|u1"):
         self._batch = batch
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "|u1", "data": (ptr, False), "version": 2, "strides": None}
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
 
 
 def _tensor_files(tensors, device):
@@ -177,6 +198,16 @@ class Batch:
         self._check(_lib.jpgpu_batch_run_idct(self._h))
         return self
 
+    def set_output_affine(self, scale, bias):
+        """RGB_PLANAR_F16 / _F32: sample = float32(byte) * scale[c] + bias[c] per channel c (R, G, B); the default is scale 1, bias 0.  The
+        constants belong to the batch, not to an upload: they hold from the next decode() / run_idct() on.  ArgumentException for a constant
+        that is not finite (the ones in force stay).  The other formats never read them."""
+        s, b = np.asarray(scale, dtype=np.float32).reshape(-1), np.asarray(bias, dtype=np.float32).reshape(-1)
+        if s.shape != (3,) or b.shape != (3,):
+            raise ValueError("scale and bias are three values each, one per channel (R, G, B)")
+        self._check(_lib.jpgpu_batch_set_output_affine(self._h, (C.c_float * 3)(*s.tolist()), (C.c_float * 3)(*b.tolist())))
+        return self
+
     def sync(self):
         self._check(_lib.jpgpu_batch_sync(self._h))
         return self
@@ -215,12 +246,15 @@ class Batch:
 
     def plan_stats(self):
         """How the last upload() planned the entropy stage (K2's plain list and pools, K2S's final-pass list, pools and table
-        sets) and K3: idct_work = work entries per output layout class (generic, YCbCr 1x1, 2x1, 2x2, gray, store of samples)."""
+        sets) and K3: idct_work = work entries per output layout class (generic, YCbCr 1x1, 2x1, 2x2, gray, store of samples),
+        idct_split_work = those of them that belong to scans handed over as half-line planes."""
         st = _capi.PlanStats()
         self._check(_lib.jpgpu_batch_plan_stats(self._h, C.byref(st)))
         work = (C.c_int32 * IDCT_LAYOUT_CLASSES)()
         self._check(_lib.jpgpu_batch_idct_work(self._h, work, IDCT_LAYOUT_CLASSES))
-        return dict({k: getattr(st, k) for k, _ in _capi.PlanStats._fields_}, idct_work=list(work))
+        split = (C.c_int32 * IDCT_LAYOUT_CLASSES)()
+        self._check(_lib.jpgpu_batch_idct_split_work(self._h, split, IDCT_LAYOUT_CLASSES))
+        return dict({k: getattr(st, k) for k, _ in _capi.PlanStats._fields_}, idct_work=list(work), idct_split_work=list(split))
 
     def progressive_fallbacks(self):
         """Times the single-launch progressive path timed out and the step was re-issued level by level."""
@@ -269,7 +303,7 @@ class Batch:
 
     def output(self, i):
         """Downloads image i. INTERLEAVED_U8 / INTERLEAVED_U8_SCALED -> uint8[H,W,C]; RGB_U8 / RGBA_U8 -> uint8[H,W,3|4]; RGB_PLANAR_U8 -> uint8[3,H,W];
-        EXTENDED_U16 -> uint16[H,W,4]; PLANAR_* -> list of per-component 2-D arrays (padded)."""
+        RGB_PLANAR_F16 / _F32 -> float16 / float32 [3,H,W]; EXTENDED_U16 -> uint16[H,W,4]; PLANAR_* -> list of per-component 2-D arrays (padded)."""
         info = self.image_info(i)
         raise_for_status(info.status, _lib.jpgpu_last_error(self.ctx._h))
         raw = np.empty(info.out_bytes, dtype=np.uint8)
@@ -278,8 +312,8 @@ class Batch:
             return raw.reshape(info.height, info.width, info.num_components)
         if self.format in (FMT_RGB_U8, FMT_RGBA_U8):
             return raw.reshape(info.height, info.width, 4 if self.format == FMT_RGBA_U8 else 3)
-        if self.format == FMT_RGB_PLANAR_U8:  # three tight planes R, G, B
-            return raw.reshape(3, info.height, info.width)
+        if self.format in _RGB_PLANES:  # three tight planes R, G, B
+            return raw.view(_SAMPLE_DTYPES.get(self.format, np.uint8)).reshape(3, info.height, info.width)
         if self.format == FMT_EXTENDED_U16:  # the reference tests' JpegExtendingOutputWriter buffer: ushort x 4 per pixel
             return raw.view(np.uint16).reshape(info.height, info.width, 4)
         dt = np.int16 if self.format == FMT_PLANAR_I16 else np.uint8
@@ -295,13 +329,14 @@ class Batch:
             return (info.height, info.width, info.num_components)
         if self.format in (FMT_RGB_U8, FMT_RGBA_U8):
             return (info.height, info.width, 4 if self.format == FMT_RGBA_U8 else 3)
-        if self.format == FMT_RGB_PLANAR_U8:
+        if self.format in _RGB_PLANES:
             return (3, info.height, info.width)
         raise ValueError("output_tensor: format %d is not one dense uint8 array per image (MCU-padded planes, or uint16 pixels); use output()" % self.format)
 
     def output_tensor(self, i):
         """Image i as a torch uint8 tensor on the context's device that ALIASES the batch's output buffer -- no copy, no download:
-        data_ptr() == output_device_ptr()[0] + image_info(i).out_offset.  RGB_PLANAR_U8 -> (3, H, W); INTERLEAVED_U8 / INTERLEAVED_U8_SCALED /
+        data_ptr() == output_device_ptr()[0] + image_info(i).out_offset.  RGB_PLANAR_U8 -> (3, H, W); RGB_PLANAR_F16 / _F32 -> a torch.float16 /
+        float32 (3, H, W) tensor; INTERLEAVED_U8 / INTERLEAVED_U8_SCALED /
         RGB_U8 -> (H, W, C); RGBA_U8 -> (H, W, 4).  The MCU-padded PLANAR_* formats and EXTENDED_U16 raise ValueError; an image that failed
         raises as output() does.  sync() is called first, so the tensor may be used on any torch stream.  The tensor keeps the batch alive.
         One rule remains: the next upload() on this batch, or an explicit close(), invalidates every tensor made from it."""
@@ -316,7 +351,7 @@ class Batch:
         base, total = self.output_device_ptr()
         if not base or info.out_offset + info.out_bytes > total:
             raise ValueError("output_tensor: the batch has no output buffer for image %d" % i)
-        view = _DeviceView(self, base + info.out_offset, shape)
+        view = _DeviceView(self, base + info.out_offset, shape, _typestr(self.format))
         return torch.as_tensor(view, device=torch.device("cuda", self.ctx.device))
 
     def coefficients(self, i):
@@ -366,12 +401,31 @@ def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None):
     return outs, results
 
 
-def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, ctx=None):
+def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None):
     """One-call helper for torch consumers: returns (tensors, results), tensors[i] = Batch.output_tensor(i) -- uint8[3, H, W] on the
     context's device by default -- or None for an image that failed.  Nothing is downloaded.  The batch is not closed: its output
     buffer is the tensors' memory and is freed with the last of them.  files: bytes-like objects, or 1-D uint8 torch tensors on the
-    context's device (Batch.upload_tensors: e.g. EncodeBatch.output_tensor(i) -- the streams never leave the device)."""
-    b = _upload_any(Batch(ctx), files, fmt).decode().sync()
+    context's device (Batch.upload_tensors: e.g. EncodeBatch.output_tensor(i) -- the streams never leave the device).
+    dtype=torch.float16 / torch.float32 selects RGB_PLANAR_F16 / _F32: float [3, H, W] tensors written by the decoder's output stage itself.
+    mean / std (per channel, 0..1 units; both or neither) then make them (u / 255 - mean) / std through affine_from_mean_std; without them
+    a sample is the byte as a float."""
+    if dtype is not None:
+        import torch
+
+        by_dtype = {torch.float16: FMT_RGB_PLANAR_F16, torch.float32: FMT_RGB_PLANAR_F32, torch.uint8: fmt}
+        if dtype not in by_dtype:
+            raise ValueError("decode_to_tensors: dtype is torch.float16, torch.float32 or torch.uint8, not %s" % (dtype,))
+        if dtype != torch.uint8 and fmt not in _RGB_PLANES:
+            raise ValueError("decode_to_tensors: float samples come as three planes (3, H, W) only; leave fmt at its default")
+        fmt = by_dtype[dtype]
+    if (mean is None) != (std is None):
+        raise ValueError("decode_to_tensors: mean and std go together")
+    if mean is not None and fmt not in _SAMPLE_DTYPES:
+        raise ValueError("decode_to_tensors: mean / std apply to float samples; pass dtype=torch.float16 or torch.float32")
+    b = Batch(ctx)
+    if mean is not None:
+        b.set_output_affine(*affine_from_mean_std(mean, std))
+    b = _upload_any(b, files, fmt).decode().sync()
     tensors, results = [], []
     for i in range(len(b)):
         results.append(b.result(i))

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <exception>
 #include <memory>
 #include <new>
@@ -411,6 +412,24 @@ static int run_entropy_stages(DeviceBatch &impl) {
 }
 int jpgpu_batch_run_entropy(jpgpu_batch *b) { JPGPU_GUARD(b, run_entropy_stages(b->impl)); }
 int jpgpu_batch_run_idct(jpgpu_batch *b) { JPGPU_GUARD(b, b->impl.run_idct()); }
+int jpgpu_batch_set_output_affine(jpgpu_batch *b, const float scale[3], const float bias[3]) {
+    if (!b) return JPGPU_ERR_ARGUMENT;
+    if (!scale || !bias) {
+        b->ctx->last_error = "jpgpu_batch_set_output_affine: null argument";
+        return JPGPU_ERR_ARGUMENT;
+    }
+    OutputAffine a;
+    for (int c = 0; c < 3; c++) {
+        if (!std::isfinite(scale[c]) || !std::isfinite(bias[c])) {  // (the constants in force stay)
+            b->ctx->last_error = "jpgpu_batch_set_output_affine: the constants must be finite";
+            return JPGPU_ERR_ARGUMENT;
+        }
+        a.scale[c] = scale[c];
+        a.bias[c] = bias[c];
+    }
+    b->impl.set_output_affine(a);
+    return JPGPU_OK;
+}
 int jpgpu_batch_sync(jpgpu_batch *b) { JPGPU_GUARD(b, b->impl.sync()); }
 int jpgpu_batch_size(const jpgpu_batch *b) { return b ? b->impl.size() : 0; }
 
@@ -511,6 +530,11 @@ static_assert(JPGPU_IDCT_LAYOUT_CLASSES == kNumIdctLayoutClasses, "jpgpu_batch_i
 int jpgpu_batch_idct_work(const jpgpu_batch *b, int32_t *counts, int n) {
     if (!b || !counts || n != JPGPU_IDCT_LAYOUT_CLASSES) return JPGPU_ERR_ARGUMENT;
     b->impl.idct_work(counts);
+    return JPGPU_OK;
+}
+int jpgpu_batch_idct_split_work(const jpgpu_batch *b, int32_t *counts, int n) {
+    if (!b || !counts || n != JPGPU_IDCT_LAYOUT_CLASSES) return JPGPU_ERR_ARGUMENT;
+    b->impl.idct_split_work(counts);
     return JPGPU_OK;
 }
 int jpgpu_batch_totals(const jpgpu_batch *b, uint64_t *compressed_bytes, uint64_t *blocks, uint64_t *pixels, uint64_t *output_bytes) {
@@ -1276,7 +1300,7 @@ int jpgpu_progressive_output_size(jpgpu_progressive *p, int format, size_t *byte
         const BaselineGeometry &g = p->frame.geo();
         size_t n = 0;
         if (fmt_is_sample_bytes(format)) n = (size_t)fh.samples_per_line * fh.lines * fh.num_components;
-        else if (format == JPGPU_FMT_RGB_U8 || format == JPGPU_FMT_RGB_PLANAR_U8) n = (size_t)fh.samples_per_line * fh.lines * 3;
+        else if (format == JPGPU_FMT_RGB_U8 || fmt_is_rgb_planes(format)) n = (size_t)fh.samples_per_line * fh.lines * 3 * fmt_rgb_plane_sample_bytes(format);
         else if (format == JPGPU_FMT_RGBA_U8) n = (size_t)fh.samples_per_line * fh.lines * 4;
         else if (format == JPGPU_FMT_EXTENDED_U16) n = (size_t)fh.samples_per_line * fh.lines * 8;
         else if (format == JPGPU_FMT_PLANAR_U8 || format == JPGPU_FMT_PLANAR_I16) {

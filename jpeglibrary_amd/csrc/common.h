@@ -39,14 +39,18 @@ struct DevScanComponent {
     uint8_t dc_slot, ac_slot; // index into DevScan::huff_pool (LDS slot)
 };
 
-enum OutputFormat : int32_t { kFmtInterleavedU8 = 0, kFmtPlanarU8 = 1, kFmtPlanarI16 = 2, kFmtRgbU8 = 3, kFmtRgbaU8 = 4, kFmtExtendedU16 = 5, kFmtInterleavedU8Scaled = 6, kFmtRgbPlanarU8 = 7 };
-constexpr int kNumOutputFormats = 8;
+enum OutputFormat : int32_t { kFmtInterleavedU8 = 0, kFmtPlanarU8 = 1, kFmtPlanarI16 = 2, kFmtRgbU8 = 3, kFmtRgbaU8 = 4, kFmtExtendedU16 = 5, kFmtInterleavedU8Scaled = 6, kFmtRgbPlanarU8 = 7, kFmtRgbPlanarF16 = 8, kFmtRgbPlanarF32 = 9 };
+constexpr int kNumOutputFormats = 10;
 // the two formats that hold one byte per sample of every component, out[(y*W+x)*C + c]: the same geometry, layout classes, clearing
 // and canvas rules; they differ in how a sample becomes its byte only (K3)
 constexpr bool fmt_is_sample_bytes(int f) { return f == kFmtInterleavedU8 || f == kFmtInterleavedU8Scaled; }
 // the formats that hold the callers' converter's pixels (JpegYCbCrToRgbConverter over the INTERLEAVED_U8 samples): the same refusals, scratch
-// image and conversion rules; RGB_PLANAR_U8 holds RGB_U8's bytes as three tight W x H planes
-constexpr bool fmt_is_rgb(int f) { return f == kFmtRgbU8 || f == kFmtRgbaU8 || f == kFmtRgbPlanarU8; }
+// image and conversion rules; RGB_PLANAR_U8 holds RGB_U8's bytes as three tight W x H planes, RGB_PLANAR_F16 / _F32 the same planes with
+// every byte u of channel c as the float (float)u * scale[c] + bias[c] (OutputAffine below)
+constexpr bool fmt_is_rgb_planes(int f) { return f == kFmtRgbPlanarU8 || f == kFmtRgbPlanarF16 || f == kFmtRgbPlanarF32; }
+constexpr bool fmt_is_rgb(int f) { return f == kFmtRgbU8 || f == kFmtRgbaU8 || fmt_is_rgb_planes(f); }
+// bytes of one sample of the three-plane RGB formats (1 for every other format's byte samples)
+constexpr int fmt_rgb_plane_sample_bytes(int f) { return f == kFmtRgbPlanarF16 ? 2 : (f == kFmtRgbPlanarF32 ? 4 : 1); }
 // the formats K3 assembles from whole pixels of whole MCUs: they take a layout class (idct_layout_class) -- RGB_PLANAR_U8 too, whose planes
 // are pixel-sized like the interleaved image, not MCU-padded like PLANAR_U8's
 constexpr bool fmt_is_interleaved(int f) { return fmt_is_sample_bytes(f) || fmt_is_rgb(f); }
@@ -58,6 +62,13 @@ constexpr int fmt_bytes_per_pixel_rgb(int f) { return f == kFmtRgbaU8 ? 4 : 3; }
 struct YccRgbFactors {
     int32_t cr_r, cr_g, cb_b, cb_g;
 };
+// RGB_PLANAR_F16 / _F32: sample (c, y, x) = (float)u * scale[c] + bias[c] of the byte u RGB_PLANAR_U8 holds there -- one float32 multiply, one
+// float32 add, each rounded to nearest even and never fused; F16 then rounds once more, to nearest even, to binary16.  A property of the
+// output stage (jpgpu_batch_set_output_affine), passed to the launch by value like the factors above; the other formats never read it.
+struct OutputAffine {
+    float scale[3], bias[3];
+};
+constexpr OutputAffine kOutputAffineIdentity = {{1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};
 
 // One scan job.
 struct alignas(16) DevScan {

@@ -187,9 +187,11 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
         if (fh.precision != 8)
             throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "RGB output is defined for 8-bit precision only (the reference converter assumes 8-bit samples).",
                               kDetailUnsupportedFrame);
-        img.out_bytes = (uint64_t)img.width * img.height * (format_ == JPGPU_FMT_RGBA_U8 ? 4 : 3);
-        if (format_ == JPGPU_FMT_RGB_PLANAR_U8)  // three tight planes R, G, B (a 1-component frame too: R = G = B)
-            for (int c = 0; c < 3; c++) img.plane[c] = jpgpu_plane_info{(uint64_t)c * img.width * img.height, img.width, img.height, img.width};
+        // (the three-plane formats: one, two or four bytes per sample)
+        img.out_bytes = (uint64_t)img.width * img.height * (format_ == JPGPU_FMT_RGBA_U8 ? 4 : 3) * fmt_rgb_plane_sample_bytes(format_);
+        if (fmt_is_rgb_planes(format_))  // three tight planes R, G, B (a 1-component frame too: R = G = B); offset in bytes, the rest in samples
+            for (int c = 0; c < 3; c++)
+                img.plane[c] = jpgpu_plane_info{(uint64_t)c * img.width * img.height * fmt_rgb_plane_sample_bytes(format_), img.width, img.height, img.width};
     } else {
         if (fh.num_components > 4)  // jpgpu_plane_info describes four planes; a fifth component would land on plane 0
             throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "The planar output formats describe at most 4 components.", kDetailUnsupportedFrame);

@@ -111,6 +111,7 @@ class DeviceBatch {
     void plan_stats(jpgpu_plan_stats *st) const;  // jpgpu_batch_plan_stats: the entropy stage's work lists and pools
     void progressive_plan(jpgpu_progressive_plan *p) const;  // jpgpu_batch_progressive_plan
     void idct_work(int32_t counts[kNumIdctLayoutClasses]) const;  // jpgpu_batch_idct_work: K3 work entries per layout class
+    void idct_split_work(int32_t counts[kNumIdctLayoutClasses]) const;  // jpgpu_batch_idct_split_work: those of scans handed over as half-line planes
     explicit DeviceBatch(jpgpu_ctx *ctx) : ctx_(ctx) {}
     ~DeviceBatch();
 
@@ -173,6 +174,9 @@ class DeviceBatch {
     int stage_ms(float ms[4]);
     void totals(uint64_t *compressed, uint64_t *blocks, uint64_t *pixels, uint64_t *out_bytes) const;
     int format() const { return format_; }
+    // RGB_PLANAR_F16 / _F32: the constants of the output stage's affine step (common.h: OutputAffine).  Launch state, not part of the plan:
+    // they hold from the next decode() / run_idct() on, whatever was uploaded before or is uploaded after.  No other format reads them.
+    void set_output_affine(const OutputAffine &a) { output_affine_ = a; }
     void note_entropy_only_request() { in_decode_request_ = false; }
     int last_subseq_rounds() const { return last_subseq_rounds_; }
     int progressive_fallbacks() const { return prog_fallbacks_; }
@@ -255,6 +259,7 @@ class DeviceBatch {
 
     jpgpu_ctx *ctx_;
     int format_ = JPGPU_FMT_INTERLEAVED_U8;
+    OutputAffine output_affine_ = kOutputAffineIdentity;
     std::vector<ImagePlan> images_;
     std::vector<ScanJob> jobs_;
     std::vector<int> job_image_;

@@ -258,7 +258,7 @@ int DeviceBatch::run_idct() {
     hipError_t e = launch_idct(ctx_->stream, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const IdctWork *)d_idct_work_.ptr,
                                idct_class_begin_, (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr,
                                extended ? (uint8_t *)d_planes_.ptr : (uint8_t *)d_out_.ptr, extended ? (int)JPGPU_FMT_PLANAR_I16 : format_, kf,
-                               (uint8_t *)d_rgb_scratch_.ptr, split_scans_.empty() || dense_override_ ? nullptr : idct_split_begin_class_);
+                               (uint8_t *)d_rgb_scratch_.ptr, split_scans_.empty() || dense_override_ ? nullptr : idct_split_begin_class_, output_affine_);
     if (e != hipSuccess) return hip_fail(e, "idct_output_kernel");
     // scans ordered behind earlier scans of their image (and the failing MCU of a caller's canvas): one bytewise launch per level
     for (size_t lv = 0; lv + 1 < idct_later_begin_.size(); lv++) {
@@ -268,7 +268,7 @@ int DeviceBatch::run_idct() {
         e = launch_idct(ctx_->stream, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const IdctWork *)d_idct_work_.ptr, cb,
                         (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr,
                         extended ? (uint8_t *)d_planes_.ptr : (uint8_t *)d_out_.ptr, extended ? (int)JPGPU_FMT_PLANAR_I16 : format_, kf,
-                        (uint8_t *)d_rgb_scratch_.ptr);
+                        (uint8_t *)d_rgb_scratch_.ptr, nullptr, output_affine_);
         if (e != hipSuccess) return hip_fail(e, "idct_output_kernel (ordered scans)");
     }
     if (extended) {
@@ -317,7 +317,8 @@ int DeviceBatch::run_idct() {
     }
     for (const RgbConvert &rc : rgb_convert_) {
         e = launch_ycc_to_rgb(ctx_->stream, (const uint8_t *)d_rgb_scratch_.ptr + rc.out_offset, (uint8_t *)d_out_.ptr + rc.out_offset, rc.pixels,
-                              rc.components, format_ == JPGPU_FMT_RGBA_U8 ? 4 : (format_ == JPGPU_FMT_RGB_PLANAR_U8 ? 1 : 3), kf);
+                              rc.components, format_ == JPGPU_FMT_RGBA_U8 ? 4 : (fmt_is_rgb_planes(format_) ? 1 : 3), kf, fmt_rgb_plane_sample_bytes(format_),
+                              output_affine_);
         if (e != hipSuccess) return hip_fail(e, "ycc_to_rgb_kernel");
     }
     return mark_work();
@@ -390,7 +391,7 @@ int DeviceBatch::decode() {
         auto k3 = [&](hipStream_t st, int half) {
             return launch_idct(st, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const IdctWork *)d_idct_work_halves_.ptr,
                                idct_half_begin_[half], (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr,
-                               (uint8_t *)d_out_.ptr, format_, kf, (uint8_t *)d_rgb_scratch_.ptr);
+                               (uint8_t *)d_out_.ptr, format_, kf, (uint8_t *)d_rgb_scratch_.ptr, nullptr, output_affine_);
         };
         if ((e = k2(s1, 0, huff_half_)) != hipSuccess) return hip_fail(e, "huffman_decode_kernel");
         if ((rc = mark(1, s1)) != JPGPU_OK) return rc;  // K1 and K2(A) are done: the second half may start

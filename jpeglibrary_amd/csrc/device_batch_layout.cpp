@@ -512,7 +512,8 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
         else if (format_ == JPGPU_FMT_RGB_U8) row_bytes *= 3;
         else if (format_ == JPGPU_FMT_RGBA_U8) row_bytes *= 4;
         else if (format_ == JPGPU_FMT_PLANAR_I16 || format_ == JPGPU_FMT_EXTENDED_U16) row_bytes *= 2;
-        // (RGB_PLANAR_U8 like PLANAR_U8: one byte per pixel in each plane's row)
+        else if (fmt_is_rgb_planes(format_)) row_bytes *= fmt_rgb_plane_sample_bytes(format_);
+        // (RGB_PLANAR_U8 like PLANAR_U8: one byte per pixel in each plane's row; its float forms two or four)
         for (uint32_t t = mcus_per_wg; t * 4 >= mcus_per_wg * 3 && t > 0; t--)
             if ((t * row_bytes) % 128 == 0) {
                 mcus_per_wg = t;

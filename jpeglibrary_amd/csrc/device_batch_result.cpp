@@ -448,6 +448,10 @@ void DeviceBatch::idct_work(int32_t counts[kNumIdctLayoutClasses]) const {
     for (int c = 0; c < kNumIdctLayoutClasses; c++) counts[c] = idct_class_begin_[c + 1] - idct_class_begin_[c];
 }
 
+void DeviceBatch::idct_split_work(int32_t counts[kNumIdctLayoutClasses]) const {
+    for (int c = 0; c < kNumIdctLayoutClasses; c++) counts[c] = idct_class_begin_[c + 1] - idct_split_begin_class_[c];
+}
+
 void DeviceBatch::totals(uint64_t *compressed, uint64_t *blocks, uint64_t *pixels, uint64_t *out_bytes) const {
     if (compressed) *compressed = compressed_bytes_;
     if (blocks) *blocks = total_blocks_;

@@ -317,6 +317,36 @@ __device__ __forceinline__ void rgb_planes4(uint32_t y0, uint32_t y1, uint32_t y
     b = bytes4(clamp_u8_i32((int32_t)y0 + t0.b), clamp_u8_i32((int32_t)y1 + t1.b), clamp_u8_i32((int32_t)y2 + t2.b), clamp_u8_i32((int32_t)y3 + t3.b));
 }
 
+// RGB_PLANAR_F16 / _F32: the same planes with a wider sample.  A byte u of channel c becomes (float)u * scale[c] + bias[c]: one float32
+// multiply and one float32 add, each rounded to nearest even and never fused (__fmul_rn / __fadd_rn), then for F16 one more rounding to
+// nearest even to binary16 (a float -> _Float16 conversion: subnormals kept, overflow to infinity; never the round-toward-zero packed form).
+constexpr int kConvPlanarF16 = 16, kConvPlanarF32 = 32;
+constexpr bool conv_is_planar(int conv) { return conv == kConvPlanar || conv == kConvPlanarF16 || conv == kConvPlanarF32; }
+constexpr uint32_t conv_plane_sample_bytes(int conv) { return conv == kConvPlanarF16 ? 2 : (conv == kConvPlanarF32 ? 4 : 1); }
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float affine_sample(uint32_t u, float scale, float bias) { return __fadd_rn(__fmul_rn((float)u, scale), bias); }
+// N packed bytes of one plane's row (N = 8 or 16: one or two blocks wide; v_cvt_f32_ubyte0..3 unpack them) -> N samples at dst, which is
+// 16-byte aligned: 16 / 32 bytes as F16 (one or two dwordx4 stores), 32 / 64 as F32 (two or four).  Called plane by plane: at most 16 floats
+// are alive.
+template <int CONV, int N>
+__device__ __forceinline__ void store_affine_row(uint8_t *dst, const uint32_t (&w)[N / 4], float scale, float bias) {
+    float f[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) f[j] = affine_sample((w[j >> 2] >> (8 * (j & 3))) & 0xFFu, scale, bias);
+    if (CONV == kConvPlanarF32) {
+#pragma unroll
+        for (int q = 0; q < N / 4; q++) *reinterpret_cast<float4 *>(dst + q * 16) = float4{f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]};
+    } else {
+#pragma unroll
+        for (int q = 0; q < N / 8; q++) {
+            uint32_t h[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) h[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(float2v{f[8 * q + 2 * j], f[8 * q + 2 * j + 1]}, half2v));
+            *reinterpret_cast<uint4 *>(dst + q * 16) = uint4{h[0], h[1], h[2], h[3]};
+        }
+    }
+}
+
 // Stand-alone conversion of an interleaved u8 image (C = 3: Y,Cb,Cr; C = 1: Y with Cb = Cr = 128 like
 // apps/JpegDecode/DecodeAction.cs:57-65) for the layouts the writer kernel has no fused path for.
 // bpp = 3 / 4: interleaved R,G,B(,A) pixels; bpp = 1: RGB_PLANAR_U8, three planes of n_pixels bytes each (a wave writes 64 consecutive
@@ -338,6 +368,22 @@ __global__ __launch_bounds__(256) void ycc_to_rgb_kernel(const uint8_t *__restri
         d[1] = (uint8_t)(px >> 8);
         d[2] = (uint8_t)(px >> 16);
         if (bpp == 4) d[3] = 255;
+    }
+}
+
+// The same for RGB_PLANAR_F16 / _F32 (T = _Float16 / float): ycc_to_rgb_kernel's bpp = 1 form, the same conversion, then the affine step of
+// the fused path.  W x H is arbitrary here, so a plane's start is aligned for one sample only: one sample per store (a wave still writes 128 /
+// 256 consecutive bytes of each plane).
+template <typename T>
+__global__ __launch_bounds__(256) void ycc_to_rgb_planes_kernel(const uint8_t *__restrict__ src, T *__restrict__ dst, uint64_t n_pixels, int comps,
+                                                                YccRgbFactors k, OutputAffine aff) {
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n_pixels; i += (uint64_t)gridDim.x * 256) {
+        const uint32_t y = src[i * comps];
+        const uint32_t cb = comps == 3 ? src[i * 3 + 1] : 128u, cr = comps == 3 ? src[i * 3 + 2] : 128u;
+        const uint32_t px = rgb_pixel(y, chroma_terms(cb, cr, k));
+        dst[i] = (T)affine_sample(px & 0xFFu, aff.scale[0], aff.bias[0]);  // (float -> _Float16: round to nearest even)
+        dst[n_pixels + i] = (T)affine_sample((px >> 8) & 0xFFu, aff.scale[1], aff.bias[1]);
+        dst[2 * n_pixels + i] = (T)affine_sample((px >> 16) & 0xFFu, aff.scale[2], aff.bias[2]);
     }
 }
 
@@ -444,7 +490,8 @@ __device__ __forceinline__ void quad_exchange(const uint4 &o0, const uint4 &o1, 
 
 // Output assembly of the INTERLEAVED_U8 format from the LDS sample tile [8 rows][256 blocks][8 B] (phase C).
 // CONV: 0 = the samples as they are (Y,Cb,Cr), 3 / 4 = converted to R,G,B / R,G,B,A bytes (fast layouts only), kConvPlanar = converted and
-// written as three planes of one byte per pixel (RGB_PLANAR_U8; fast layouts, and kLayGray as a layout of one-block MCUs without chroma).
+// written as three planes of one byte per pixel (RGB_PLANAR_U8; fast layouts, and kLayGray as a layout of one-block MCUs without chroma),
+// kConvPlanarF16 / kConvPlanarF32 = those planes with every byte as a float sample (RGB_PLANAR_F16 / _F32, `aff`).
 // The fast layouts take the tile's place from wave-uniform state (k3_index_math.h): pos = its first MCU, mpl / line_recip = the MCUs of a
 // line and their reciprocal, row_recip = that of n_mcu, img_h = the frame's lines, img = the image in the output buffer.  Nothing in their
 // task loop divides.
@@ -453,7 +500,7 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
                                                              uint32_t line_recip, uint32_t row_recip, uint32_t img_h, uint32_t n_mcu,
                                                              uint32_t tid, bool have_block, const DevScanComponent &comp, uint32_t mcu_x,
                                                              uint32_t mcu_y, uint32_t b, uint8_t *img, const YccRgbFactors &kf, bool reached,
-                                                             uint32_t mcu, uint32_t fail_block) {
+                                                             uint32_t mcu, uint32_t fail_block, const OutputAffine &aff) {
     if (LAY == kLayGeneric) {
         const uint32_t W = s.width, H = s.height, C = s.frame_components;
         // any component count / sampling: bytewise stores with WriteBlockSlow's replication
@@ -500,13 +547,14 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
     } else {
     // YCbCr fast paths: one task = one pixel row of one MCU (8*max_h pixels); consecutive lanes take consecutive MCUs of
     // the same row, so a wave writes one contiguous run of the output row per store instruction group.
-    constexpr bool gray = LAY == kLayGray;  // (CONV == kConvPlanar only: the other sinks write a gray block from its own lane)
-    constexpr uint32_t max_h = (LAY == kLayYccH1V1 || (gray && CONV == kConvPlanar)) ? 1 : 2;
+    constexpr bool planar = conv_is_planar(CONV);
+    constexpr bool gray = LAY == kLayGray;  // (the planar sinks only: the other sinks write a gray block from its own lane)
+    constexpr uint32_t max_h = (LAY == kLayYccH1V1 || (gray && planar)) ? 1 : 2;
     constexpr uint32_t max_v = (LAY == kLayYccH2V2) ? 2 : 1;
     constexpr uint32_t rows_per_mcu = 8 * max_v;
     constexpr uint32_t vshift = max_v >> 1;
-    constexpr uint32_t kbpm = (gray && CONV == kConvPlanar) ? 1 : max_h * max_v + 2;
-    constexpr uint32_t bpp = CONV == 4 ? 4 : (CONV == kConvPlanar ? 1 : 3);  // bytes from a pixel to the next of its row
+    constexpr uint32_t kbpm = (gray && planar) ? 1 : max_h * max_v + 2;
+    constexpr uint32_t bpp = CONV == 4 ? 4 : (planar ? conv_plane_sample_bytes(CONV) : 3);  // bytes from a pixel to the next of its row
     const uint32_t n_tasks = rows_per_mcu * n_mcu;
     const uint32_t W = mpl * (8 * max_h);  // (whole MCUs: idct_layout_class)
     // wave-uniform: the first pixel line of the tile's first MCU line; a lane adds a 32-bit offset (a tile spans few lines, or short ones)
@@ -514,7 +562,10 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
     uint8_t *line0 = img + (uint64_t)y0 * W * bpp;
     // RGB_PLANAR_U8: the same line in the G and B planes.  A plane is W * H bytes, which can pass 2^32: wave-uniform 64-bit bases like line0,
     // and the lane's 32-bit offset `at` serves all three.  (W is a multiple of the store width and so is every plane: idct_layout_class.)
-    uint8_t *line1 = line0 + (uint64_t)W * img_h, *line2 = line1 + (uint64_t)W * img_h;
+    // RGB_PLANAR_F16 / _F32: a plane is W * H * 2 / 4 bytes and a lane stores 16-byte pieces.  The fast classes have W a whole number of MCUs
+    // (a multiple of 8), so a line is a multiple of 16 bytes in either type, and so is a plane; an image starts on a multiple of 256 in the
+    // batch's output buffer (plan_image): every plane, line and lane start is 16-byte aligned.
+    uint8_t *line1 = line0 + (uint64_t)W * img_h * (planar ? bpp : 1), *line2 = line1 + (uint64_t)W * img_h * (planar ? bpp : 1);
     // Sample bytes of two-block-wide MCUs: the four lanes of a quad exchange 16-byte pieces so that every store instruction writes whole
     // 64-byte blocks (k3_store_quads.h).  Wave-uniform per tile; a tile whose quads are not four MCUs side by side -- a clipped range, tiles
     // that are not line-aligned, a line that is no multiple of four MCUs -- takes the same loop with its own registers at +0 / +16 / +32.
@@ -537,10 +588,19 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
         const uint8_t *crow = sh_px + (row >> vshift) * kPxRowStride + (mb + max_h * max_v) * 8;
         const uint32_t at = k3_mul24(yl, W * bpp) + k3_mul24(gx, 8 * max_h * bpp);  // (W * bpp < 2^18; the sum is far below 2^32)
         uint8_t *dst_px = line0 + at;
-        if (CONV == kConvPlanar) {
+        if (planar) {
             // three stores per task, one per plane: consecutive lanes write consecutive 8 / 16 bytes of one plane row
+            // (float samples: the same bytes, plane by plane through the affine step -- consecutive lanes write consecutive 16 / 32 bytes as
+            // F16 and 32 / 64 as F32 of one plane row, in 16-byte stores)
             if (gray) {
                 const uint2 yv = *reinterpret_cast<const uint2 *>(yrow);  // R = G = B = Y (Cb = Cr = 128 contribute nothing, DecodeAction.cs:57-65)
+                if (CONV != kConvPlanar) {
+                    const uint32_t w[2] = {yv.x, yv.y};
+                    store_affine_row<CONV, 8>(line0 + at, w, aff.scale[0], aff.bias[0]);
+                    store_affine_row<CONV, 8>(line1 + at, w, aff.scale[1], aff.bias[1]);
+                    store_affine_row<CONV, 8>(line2 + at, w, aff.scale[2], aff.bias[2]);
+                    continue;
+                }
                 *reinterpret_cast<uint2 *>(line0 + at) = yv;
                 *reinterpret_cast<uint2 *>(line1 + at) = yv;
                 *reinterpret_cast<uint2 *>(line2 + at) = yv;
@@ -555,6 +615,12 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
                     const ChromaTerms t1 = chroma_terms(byte_of(cv.x, cv.y, 2 * q + 1), byte_of(cv.z, cv.w, 2 * q + 1), kf);
                     rgb_planes4(y4 & 0xFFu, (y4 >> 8) & 0xFFu, (y4 >> 16) & 0xFFu, y4 >> 24, t0, t0, t1, t1, r[q], g[q], bl[q]);
                 }
+                if (CONV != kConvPlanar) {
+                    store_affine_row<CONV, 16>(line0 + at, r, aff.scale[0], aff.bias[0]);
+                    store_affine_row<CONV, 16>(line1 + at, g, aff.scale[1], aff.bias[1]);
+                    store_affine_row<CONV, 16>(line2 + at, bl, aff.scale[2], aff.bias[2]);
+                    continue;
+                }
                 *reinterpret_cast<uint4 *>(line0 + at) = uint4{r[0], r[1], r[2], r[3]};
                 *reinterpret_cast<uint4 *>(line1 + at) = uint4{g[0], g[1], g[2], g[3]};
                 *reinterpret_cast<uint4 *>(line2 + at) = uint4{bl[0], bl[1], bl[2], bl[3]};
@@ -568,6 +634,13 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
                 uint2 r, g, bl;
                 rgb_planes4(byte_of(yv.x, yv.y, 0), byte_of(yv.x, yv.y, 1), byte_of(yv.x, yv.y, 2), byte_of(yv.x, yv.y, 3), t[0], t[1], t[2], t[3], r.x, g.x, bl.x);
                 rgb_planes4(byte_of(yv.x, yv.y, 4), byte_of(yv.x, yv.y, 5), byte_of(yv.x, yv.y, 6), byte_of(yv.x, yv.y, 7), t[4], t[5], t[6], t[7], r.y, g.y, bl.y);
+                if (CONV != kConvPlanar) {
+                    const uint32_t rw[2] = {r.x, r.y}, gw[2] = {g.x, g.y}, bw[2] = {bl.x, bl.y};
+                    store_affine_row<CONV, 8>(line0 + at, rw, aff.scale[0], aff.bias[0]);
+                    store_affine_row<CONV, 8>(line1 + at, gw, aff.scale[1], aff.bias[1]);
+                    store_affine_row<CONV, 8>(line2 + at, bw, aff.scale[2], aff.bias[2]);
+                    continue;
+                }
                 *reinterpret_cast<uint2 *>(line0 + at) = r;
                 *reinterpret_cast<uint2 *>(line1 + at) = g;
                 *reinterpret_cast<uint2 *>(line2 + at) = bl;
@@ -665,8 +738,9 @@ typedef const __attribute__((address_space(1))) void jpgpu_gbl_void;
 template <int FMT, int LAY, bool PRE, bool SPLIT = false>
 __device__ __forceinline__ void idct_output_body(
     const int16_t *__restrict__ coefs, const DevScan *__restrict__ scans, const IdctWork *__restrict__ work,
-    const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf) {
-    constexpr int CONV = FMT == kFmtRgbU8 ? 3 : (FMT == kFmtRgbaU8 ? 4 : (FMT == kFmtRgbPlanarU8 ? kConvPlanar : 0));  // fused YCbCr -> RGB(A), fast layouts and gray only
+    const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf,
+    OutputAffine aff = kOutputAffineIdentity) {
+    constexpr int CONV = FMT == kFmtRgbU8 ? 3 : (FMT == kFmtRgbaU8 ? 4 : (FMT == kFmtRgbPlanarU8 ? kConvPlanar : (FMT == kFmtRgbPlanarF16 ? kConvPlanarF16 : (FMT == kFmtRgbPlanarF32 ? kConvPlanarF32 : 0))));  // fused YCbCr -> RGB(A), fast layouts and gray only
     constexpr bool kSampleBytes = fmt_is_sample_bytes(FMT);  // INTERLEAVED_U8 / _SCALED: one path, two sample-to-byte steps
     __shared__ __attribute__((aligned(16))) uint8_t sh_all[kIdctThreads * 128 + kIdctThreads * 64 + kMaxScanComponents * 128 + (SPLIT && !PRE ? 64 : 0)];
     uint8_t *sh = sh_all;
@@ -1035,7 +1109,7 @@ __device__ __forceinline__ void idct_output_body(
     }
     }
 
-    if (CONV != 0 && CONV != kConvPlanar && LAY == kLayGray) {
+    if (CONV != 0 && !conv_is_planar(CONV) && LAY == kLayGray) {
         // a single-component image as R = G = B = Y (Cb = Cr = 128 contribute nothing, DecodeAction.cs:57-65)
         if (writes) {
             const uint32_t x0 = (mcu_x * comp.h + s.blk_x[b_out]) * 8, y0 = (mcu_y * comp.v + s.blk_y[b_out]) * 8;
@@ -1079,7 +1153,7 @@ __device__ __forceinline__ void idct_output_body(
     // (tile_mcus clamps at range_end only, so at most the run's LAST tile is short: two reciprocals cover every n_mcu; a tile walk that
     // shortens another tile needs its own)
     interleaved_output_from_tile<LAY, CONV>(sh_px, s, pos, mpl, line_recip, n_mcu == mcus_per_tile ? row_recip_full : row_recip_last, img_h, n_mcu, tid,
-                                            writes, comp, mcu_x, mcu_y, b, img, kf, reached, mcu, fail_block);
+                                            writes, comp, mcu_x, mcu_y, b, img, kf, reached, mcu, fail_block, aff);
     }  // interleaved
     }  // u8 formats
 
@@ -1145,14 +1219,14 @@ hipError_t launch_expand_handoff(hipStream_t stream, const int16_t *coefs, int16
 template <int FMT, int LAY>
 __global__ __launch_bounds__(kIdctThreads, (FMT == kFmtPlanarI16 ? 2 : 3)) void idct_output_kernel(
     const int16_t *__restrict__ coefs, const DevScan *__restrict__ scans, const IdctWork *__restrict__ work,
-    const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf) {
-    idct_output_body<FMT, LAY, false>(coefs, scans, work, status, quant_pool, out, kf);
+    const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf, OutputAffine aff) {
+    idct_output_body<FMT, LAY, false>(coefs, scans, work, status, quant_pool, out, kf, aff);
 }
 template <int FMT, int LAY>
 __global__ __launch_bounds__(kIdctThreads, (FMT == kFmtPlanarI16 ? 2 : 3)) void idct_split_kernel(
     const int16_t *__restrict__ coefs, const DevScan *__restrict__ scans, const IdctWork *__restrict__ work,
-    const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf) {
-    idct_output_body<FMT, LAY, false, true>(coefs, scans, work, status, quant_pool, out, kf);
+    const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf, OutputAffine aff) {
+    idct_output_body<FMT, LAY, false, true>(coefs, scans, work, status, quant_pool, out, kf, aff);
 }
 template <int FMT>
 __global__ __launch_bounds__(kIdctThreads, 2) void flush_output_kernel(
@@ -1204,15 +1278,15 @@ __global__ __launch_bounds__(64) void dispose_pass_kernel(int16_t *__restrict__ 
 template <int FMT, int LAY>
 static void launch_idct_one(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work, int n_work, int n_dense,
                             const DevScanStatus *status, const DevQuantTable *quant_pool, uint8_t *out,
-                            YccRgbFactors kf = YccRgbFactors{0, 0, 0, 0}) {
+                            YccRgbFactors kf = YccRgbFactors{0, 0, 0, 0}, OutputAffine aff = kOutputAffineIdentity) {
     // the first n_dense entries: scans with dense coefficient blocks; the rest: scans handed over as half-line planes
     if (n_dense > 0)
         hipLaunchKernelGGL((idct_output_kernel<FMT, LAY>), dim3(n_dense), dim3(kIdctThreads), 0, stream, coefs, scans, work, status,
-                           quant_pool, out, kf);
+                           quant_pool, out, kf, aff);
     if constexpr (idct_split_supported(FMT, LAY))  // (the planner lists no split scan under another format and class)
       if (n_work > n_dense)
         hipLaunchKernelGGL((idct_split_kernel<FMT, LAY>), dim3(n_work - n_dense), dim3(kIdctThreads), 0, stream, coefs, scans, work + n_dense, status,
-                           quant_pool, out, kf);
+                           quant_pool, out, kf, aff);
 }
 
 // work is sorted by layout class; class_begin[c]..class_begin[c+1] are the workgroups of class c, and from split_begin[c] on (where
@@ -1220,7 +1294,7 @@ static void launch_idct_one(hipStream_t stream, const int16_t *coefs, const DevS
 hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
                        const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status,
                        const DevQuantTable *quant_pool, uint8_t *out, int format, const YccRgbFactors &kf, uint8_t *generic_out,
-                       const int *split_begin) {
+                       const int *split_begin, const OutputAffine &aff) {
     for (int c = 0; c < kNumIdctLayoutClasses; c++) {
         const int n = class_begin[c + 1] - class_begin[c];
         if (n <= 0) continue;
@@ -1261,6 +1335,22 @@ hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *
             case kLayGray: launch_idct_one<kFmtRgbPlanarU8, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
             default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
             }
+        } else if (format == kFmtRgbPlanarF16) {
+            switch (c) {
+            case kLayYccH1V1: launch_idct_one<kFmtRgbPlanarF16, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
+            case kLayYccH2V1: launch_idct_one<kFmtRgbPlanarF16, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
+            case kLayYccH2V2: launch_idct_one<kFmtRgbPlanarF16, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
+            case kLayGray: launch_idct_one<kFmtRgbPlanarF16, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
+            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
+            }
+        } else if (format == kFmtRgbPlanarF32) {
+            switch (c) {
+            case kLayYccH1V1: launch_idct_one<kFmtRgbPlanarF32, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
+            case kLayYccH2V1: launch_idct_one<kFmtRgbPlanarF32, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
+            case kLayYccH2V2: launch_idct_one<kFmtRgbPlanarF32, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
+            case kLayGray: launch_idct_one<kFmtRgbPlanarF32, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
+            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
+            }
         } else if (format == kFmtInterleavedU8Scaled) {
             switch (c) {
             case kLayYccH1V1: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
@@ -1284,11 +1374,21 @@ hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *
     return hipSuccess;
 }
 
-// INTERLEAVED_U8 image (comps = 1 or 3) -> RGB / RGBA (bpp = 3 / 4) or the three planes of RGB_PLANAR_U8 (bpp = 1), for the layouts without a fused path
-hipError_t launch_ycc_to_rgb(hipStream_t stream, const uint8_t *src, uint8_t *dst, uint64_t n_pixels, int comps, int bpp, const YccRgbFactors &kf) {
+// INTERLEAVED_U8 image (comps = 1 or 3) -> RGB / RGBA (bpp = 3 / 4) or the three planes of RGB_PLANAR_U8 (bpp = 1), for the layouts without a fused path;
+// sample_bytes = 2 / 4 (with bpp = 1): the planes of RGB_PLANAR_F16 / _F32
+hipError_t launch_ycc_to_rgb(hipStream_t stream, const uint8_t *src, uint8_t *dst, uint64_t n_pixels, int comps, int bpp, const YccRgbFactors &kf,
+                             int sample_bytes, const OutputAffine &aff) {
     if (n_pixels == 0) return hipSuccess;
     const uint64_t want = (n_pixels + 255) / 256;
     const int grid = (int)(want < 65536 ? want : 65536);
+    if (sample_bytes == 2) {
+        hipLaunchKernelGGL(ycc_to_rgb_planes_kernel<_Float16>, dim3(grid), dim3(256), 0, stream, src, reinterpret_cast<_Float16 *>(dst), n_pixels, comps, kf, aff);
+        return hipGetLastError();
+    }
+    if (sample_bytes == 4) {
+        hipLaunchKernelGGL(ycc_to_rgb_planes_kernel<float>, dim3(grid), dim3(256), 0, stream, src, reinterpret_cast<float *>(dst), n_pixels, comps, kf, aff);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(ycc_to_rgb_kernel, dim3(grid), dim3(256), 0, stream, src, dst, n_pixels, comps, bpp, kf);
     return hipGetLastError();
 }
@@ -1303,7 +1403,9 @@ hipError_t launch_dispose_pass(hipStream_t stream, int16_t *coefs, const Dispose
 // Layout class of a scan for the formats K3 assembles from whole pixels (fmt_is_interleaved; 0 = generic bytewise path).
 // RGB_PLANAR_U8 stores 8 (kLayGray, kLayYccH1V1) or 16 bytes (kLayYccH2V1 / H2V2) per lane and plane, at plane c's base out_off + c * W * H plus
 // y * W + 8 or 16 * (MCU column): with W and out_off multiples of 8 / 16, as the conditions below ask, every plane base and every row start
-// is aligned for that store.
+// is aligned for that store.  RGB_PLANAR_F16 / _F32 store 16-byte pieces at out_off + c * W * H * sizeof(T) + (y * W + 8 or 16 * (MCU column)) * sizeof(T):
+// W a multiple of 8 makes every term but out_off a multiple of 16 in both types, and out_off is a multiple of 256 (DeviceBatch::plan_image; 0 for a
+// single job).
 int idct_layout_class(const DevScan &s) {
     const uint32_t W = s.width;
     if (s.frame_components == 1 && s.scan_components == 1 && s.comp[0].h == 1 && s.comp[0].v == 1 && (W % 8) == 0 && (s.out_off % 8) == 0)

@@ -80,22 +80,29 @@ constexpr bool idct_split_supported(int format, int layout_class) {
     if (format == kFmtRgbU8) return layout_class == 1 || layout_class == 4;
     if (format == kFmtRgbaU8) return layout_class != 3;
     if (format == kFmtRgbPlanarU8) return true;  // all four fast classes compile at the kernel's launch bounds without spill or scratch (tests/test_planar_rgb_isa_cpu.py)
+    // RGB_PLANAR_F16 / _F32, by the compiler's resource report for gfx950: every class fits in both forms without a spilled vector register and
+    // without scratch -- dense: 4:4:4, 4:2:2, 4:2:0 162 VGPRs, gray 160; split: 4:4:4 163, 4:2:2 164, 4:2:0 163, gray 163 (of the 168 three waves
+    // per SIMD allow).  The split forms have no scalar register left for the six constants: ten scalars (gray: five) wait in lanes of one vector
+    // register, moved once per tile outside the task loop (tests/test_float_sink_isa_cpu.py).
+    if (format == kFmtRgbPlanarF16 || format == kFmtRgbPlanarF32) return true;
     if (format == kFmtInterleavedU8Scaled) return layout_class != 4;
     return true;
 }
 // work is sorted by layout class; class_begin[c]..class_begin[c+1] are the workgroups of class c.
 // RGB / RGBA formats: classes with a fused conversion write `out`; the generic class writes INTERLEAVED_U8 samples into
-// `generic_out` (same offsets), to be converted by launch_ycc_to_rgb (bpp = 3 / 4, or 1: the three planes of RGB_PLANAR_U8).
+// `generic_out` (same offsets), to be converted by launch_ycc_to_rgb (bpp = 3 / 4, or 1: the three planes of RGB_PLANAR_U8 / _F16 / _F32).
+// aff: the affine step of RGB_PLANAR_F16 / _F32 (no other format reads it).
 hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
                        const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status,
                        const DevQuantTable *quant_pool, uint8_t *out, int format, const YccRgbFactors &kf, uint8_t *generic_out,
-                       const int *split_begin = nullptr);
+                       const int *split_begin = nullptr, const OutputAffine &aff = kOutputAffineIdentity);
 // a scan K2 handed over as half-line planes (common.h: kScanSplitHandoff) -> dense int16[blocks][64] at the same offsets of `dense`
 hipError_t launch_expand_handoff(hipStream_t stream, const int16_t *coefs, int16_t *dense, const DevScan *scans, const uint32_t *scan_ids, int n_scans,
                                  uint32_t max_blocks);
 // the reference's Dispose() taken literally (frames whose component slots do not map one to one onto their components)
 hipError_t launch_dispose_pass(hipStream_t stream, int16_t *coefs, const DisposeJob *jobs, int n_jobs, uint32_t max_blocks, const DevQuantTable *quant_pool);
-hipError_t launch_ycc_to_rgb(hipStream_t stream, const uint8_t *src, uint8_t *dst, uint64_t n_pixels, int comps, int bpp, const YccRgbFactors &kf);
+hipError_t launch_ycc_to_rgb(hipStream_t stream, const uint8_t *src, uint8_t *dst, uint64_t n_pixels, int comps, int bpp, const YccRgbFactors &kf,
+                             int sample_bytes = 1, const OutputAffine &aff = kOutputAffineIdentity);
 
 // Waves per workgroup of the POOLED form of the K2S final pass (k2s_subseq.hip: runs of scans that stage the same tables; one workgroup per CU, every wave takes the
 // next 64 lanes from a counter): 10 waves + 4 tables fill a CU's LDS.  Runs shorter than kSubFinalPoolMinChunks waves, and runs
