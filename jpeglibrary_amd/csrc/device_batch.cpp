@@ -1,6 +1,8 @@
-// jpeglibrary_amd/csrc/device_batch.cpp -- a batch of scan jobs: the host-side plans (header-only / full marker walks), the upload
-// paths and the staging ring.  (Round 6 split the file: device_batch_layout.cpp = layout_and_upload and the planning stages it calls, which every
-// upload path here ends in; device_batch_launch.cpp = the launches of a decode, device_batch_result.cpp = results, the partial-flush replay, downloads.)
+// jpeglibrary_amd/csrc/device_batch.cpp -- a batch of scan jobs: its buffers and errors, an image's output geometry, the ordering of an upload
+// behind unsynchronised work, and the uploads of single scan jobs, progressive frames and scans, and coefficient frames.  (The file is split by role:
+// device_batch_ingest.cpp = the uploads of whole files (jpgpu_batch_upload*): host-side plans, staging, the ingest's stages; device_batch_layout.cpp =
+// layout_and_upload and the planning stages it calls, which every upload path ends in; device_batch_launch.cpp = the launches of a decode,
+// device_batch_result.cpp = results, the partial-flush replay, downloads.)
 //
 // HBM layout (all offsets 256-byte aligned unless noted):
 //   input   : the files' bytes back to back (256-byte slots, 256 bytes of slack before the first and after the last)
@@ -10,17 +12,10 @@
 #include "device_batch.h"
 
 #include <hip/hip_runtime.h>
-#include <sched.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <thread>
 
-#include "host_pool.h"
 #include "kernels.h"
 
 namespace jpgpu {
@@ -65,106 +60,6 @@ int DeviceBatch::fail(int status, const std::string &msg) {
 int DeviceBatch::hip_fail(hipError_t e, const char *what) {
     return fail(e == hipErrorOutOfMemory ? JPGPU_ERR_OUT_OF_MEMORY : JPGPU_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
-
-// Planner: what JpegScanDecoder.Create / ProcessScan become while the batch is being laid out.
-namespace {
-
-class PlanHandler final : public ScanHandler {
-  public:
-    explicit PlanHandler(std::vector<ScanJob> *jobs, bool first_scan_only = false, const std::vector<int> *forced = nullptr)
-        : jobs_(jobs), first_scan_only_(first_scan_only), forced_(forced) {}
-    // Second walk of a file whose sequential scans are already planned (`ends` = where each one's data stops): nothing is
-    // recorded, and scan number `swallow` leaves the reader ONE byte into its terminating marker.  That is where the
-    // reference's reader stands when exactly one whole byte was left in the bit reader behind the last block: the marker
-    // has been pulled into the bit reader, TryPeekMarker() only shows it once the buffer is empty, so the two bytes are
-    // not given back (ScanDecoder/JpegHuffmanBaselineScanDecoder.cs:167-176, JpegBitReader.cs:152-155).
-    PlanHandler(const std::vector<size_t> *ends, int swallow) : jobs_(nullptr), replay_ends_(ends), swallow_(swallow) {}
-    const std::vector<size_t> &sequential_ends() const { return ends_; }
-    void on_frame(HostDecoder &dec, int sof) override {
-        sof_ = sof;
-        baseline_ = false;
-        flush_progressive();  // a second SOF replaces the scan decoder: the old one is disposed first (JpegDecoder.cs:568)
-        if (sof == kSOF0 || sof == kSOF1) {
-            geo_ = BaselineGeometry::latch(dec, dec.frame_header());  // DRI latched at SOF time
-            baseline_ = true;
-        } else if (sof == kSOF2) {
-            prog_.begin(dec, dec.frame_header());
-        }
-    }
-    void on_scan(HostDecoder &dec, MarkerReader &reader, const ScanHeader &scan) override {
-        const uint8_t *entropy = reader.remaining_bytes();
-        const size_t len = (size_t)reader.remaining_byte_count();
-        if (prog_.active()) {
-            prog_.add_scan(dec, scan, entropy, len);  // the reference leaves the outer reader where it is
-            return;
-        }
-        if (!baseline_)
-            throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "Only Huffman DCT frames (SOF0, SOF1, SOF2) run on this path.", kDetailUnsupportedFrame);
-        if (scan.num_components == 0) {
-            // A scan header that names no component: ProcessScan walks the MCUs without reading a bit (:99-136).  With a
-            // restart interval the first restart check finds the bit buffer full and no marker (:139-154); without one
-            // the reader is left where it is and the outer walk skips the entropy data as fill.
-            const uint64_t mcus = (uint64_t)geo_.mcus_per_line * (uint64_t)geo_.mcus_per_column;
-            if (geo_.restart_interval != 0 && mcus >= geo_.restart_interval && len != 0 &&
-                !(len >= 2 && entropy[0] == 0xFF && entropy[1] != 0x00 && entropy[1] != 0xFF))
-                throw DecodeError(JPGPU_ERR_INVALID_OPERATION, "Expect restart marker.", kDetailExpectRestart);
-            if (first_scan_only_)
-                throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "A scan without components is not supported by the optimizer path.", kDetailUnsupportedFrame);
-            if (geo_.restart_interval != 0 && mcus >= geo_.restart_interval)
-                throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "A scan without components in front of restart markers is not supported.", kDetailUnsupportedFrame);
-            reader.try_advance((int)find_scan_end(entropy, len));
-            return;
-        }
-        if (replay_ends_) {
-            const int k = replayed_++;
-            if (k > swallow_ || k >= (int)replay_ends_->size())
-                throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "A scan behind a scan that left one byte unread is not supported.", kDetailUnsupportedFrame);
-            reader.try_advance((int)(*replay_ends_)[k] + (k == swallow_ ? 1 : 0));
-            return;
-        }
-        jobs_->push_back(make_scan_job(dec, geo_, scan, entropy, len, first_scan_only_));
-        if (!first_scan_only_) {
-            // (a scan KNOWN to leave one whole byte unread -- the device said so in the batch this plan is made for -- hands the
-            // reader back one byte into its terminating marker, the way the reference's does: DeviceBatch::redo_swallowed)
-            const bool forced = forced_ != nullptr && std::find(forced_->begin(), forced_->end(), (int)ends_.size()) != forced_->end();
-            ends_.push_back(find_scan_end(entropy, len));
-            jobs_->back().forced_swallow = forced && ends_.back() < len;
-            reader.try_advance((int)ends_.back() + (jobs_->back().forced_swallow ? 1 : 0));
-            return;
-        }
-        // leave the reader just before the next non-RST marker, like ProcessScan does (:167-176); the optimizer path only
-        // wants the scan resolved (what follows it is its own marker walk's business): nothing is left to read
-        reader.try_advance(first_scan_only_ ? (int)len : (int)find_scan_end(entropy, len));
-    }
-    void on_dispose(HostDecoder &) override { flush_progressive(); }
-    const BaselineGeometry &geo() const { return prog_geo_valid_ ? prog_geo_ : geo_; }
-    int sof() const { return sof_; }
-
-  private:
-    // Dispose() of the progressive scan decoder: the frame's IDCT pass, then its entropy scans in file order
-    void flush_progressive() {
-        if (!prog_.active()) return;
-        if (jobs_) {  // (also without a single recorded scan: Dispose() still flushes the allocator's blocks)
-            jobs_->push_back(prog_.make_frame_job());
-            for (ScanJob &j : prog_.scans()) jobs_->push_back(std::move(j));
-            prog_geo_ = prog_.geo();
-            prog_geo_valid_ = true;
-        }
-        prog_.reset();
-    }
-    std::vector<ScanJob> *jobs_;
-    std::vector<size_t> ends_;
-    const std::vector<size_t> *replay_ends_ = nullptr;
-    int swallow_ = -1, replayed_ = 0;
-    bool first_scan_only_ = false;
-    const std::vector<int> *forced_ = nullptr;  // sequential scans (by ordinal) known to leave one byte unread: DeviceBatch::redo_swallowed
-    BaselineGeometry geo_, prog_geo_;
-    bool prog_geo_valid_ = false;
-    ProgressiveFrame prog_;
-    bool baseline_ = false;
-    int sof_ = 0;
-};
-}  // namespace
 
 void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &geo) const {
     const FrameHeader &fh = geo.frame;
@@ -224,303 +119,6 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
                                                         " bytes) is larger than the device's memory.", kDetailUnsupportedFrame);
 }
 
-// ---------------------------------------------------------------------------------------------------------------- ingest
-//
-// jpgpu_batch_upload = SetInput + Identify + Decode's marker loop for n files (ref: JpegDecoder.cs:75-162, 509-617), without
-// the host ever walking entropy-coded bytes in the common case:
-//   1. header-only plan, one file per crew thread: Identify's walk up to the first SOS header, then Decode's walk up to the
-//      same point; the file is planned as "this one sequential scan, its data closed by EOI" (FastPlanHandler);
-//   2. the files go to HBM through the context's pinned staging ring: the crew copies the caller's bytes into 32 MiB slots,
-//      every full slot leaves as one DMA on the upload stream while the next ones are being filled;
-//   3. the device reads the bytes behind each SOS header once (first_marker_kernel) and reports the first marker that is
-//      not RSTn: where that is EOI, Identify and Decode would have seen nothing else either (neither looks behind EOI) and
-//      the plan stands -- including Identify's "last DRI in the file" (every DRI lay in front of the SOS);
-//   4. every other file (several scans, progressive, tables or garbage behind the scan, truncated data, a Decode-walk
-//      failure that a later Identify failure would pre-empt) takes the full walk of both loops, also on the crew.
-
-namespace {
-struct NeedFullWalk {};  // the header-only planner met something that is not "headers, one sequential scan"
-
-class FastPlanHandler final : public ScanHandler {
-  public:
-    explicit FastPlanHandler(std::vector<ScanJob> *jobs) : jobs_(jobs) {}
-    void on_frame(HostDecoder &dec, int sof) override {
-        if (sof != kSOF0 && sof != kSOF1) throw NeedFullWalk{};
-        geo_ = BaselineGeometry::latch(dec, dec.frame_header());  // DRI latched at SOF time
-    }
-    void on_scan(HostDecoder &dec, MarkerReader &reader, const ScanHeader &scan) override {
-        if (scan.num_components == 0) throw NeedFullWalk{};
-        const uint8_t *entropy = reader.remaining_bytes();
-        const size_t len = (size_t)reader.remaining_byte_count();
-        jobs_->push_back(make_scan_job(dec, geo_, scan, entropy, len, false));
-        reader.try_advance((int)len);  // the plan: nothing but this scan's data and an EOI follow (checked on the device)
-    }
-    void on_dispose(HostDecoder &) override {}
-
-  private:
-    std::vector<ScanJob> *jobs_;
-    BaselineGeometry geo_;
-};
-}  // namespace
-
-struct DeviceBatch::FilePlan {
-    ImagePlan img;
-    std::vector<ScanJob> jobs;
-    std::vector<size_t> seq_ends;  // where each sequential scan's data stops (offset from the scan's first entropy byte)
-    bool speculative = false;      // header-only plan, waiting for the device's verdict
-    bool need_full = false;
-    size_t scan_data_pos = 0;      // offset of the first entropy byte in the file (speculative plans)
-};
-
-// Identify + Decode's marker loop over the whole file (both walk the entropy bytes): the general path.
-void DeviceBatch::plan_file_full(const uint8_t *file, size_t len, int index, FilePlan &fp) const {
-    fp.jobs.clear();
-    fp.seq_ends.clear();
-    fp.speculative = false;
-    fp.img = ImagePlan();
-    ImagePlan &img = fp.img;
-    img.file_len = len;
-    bool decoding = false;  // Identify() is over, Decode()'s marker loop is running
-    HostDecoder dec;
-    PlanHandler handler(&fp.jobs, entropy_only_, forced_swallow_.empty() ? nullptr : &forced_swallow_);
-    try {
-        if (len > 0x7FFFFFF0u) throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "JPEG streams of 2 GiB or more are not supported.");
-        dec.set_input(file, len);
-        if (entropy_only_) {
-            // optimizer path: JpegOptimizer.Scan() runs no Identify(); the restart interval is the one in force at the
-            // scan (OptimizeBatch::plan_file found it) unless a DRI segment in front of the frame header says otherwise
-            if ((size_t)index < preset_dri_.size()) dec.set_restart_interval(preset_dri_[index]);
-        } else {
-            dec.identify(false);  // every reference caller runs Identify before Decode; it latches the LAST DRI (F4)
-        }
-        img.sof = (uint8_t)dec.start_of_frame();
-        decoding = true;
-        try {
-            dec.decode(handler, true);
-        } catch (...) {
-            fp.seq_ends = handler.sequential_ends();
-            throw;
-        }
-        decoding = false;
-        if (entropy_only_) img.sof = (uint8_t)dec.start_of_frame();
-        if (fp.jobs.empty()) {
-            // no scan: Decode() succeeds without writing anything; keep the frame geometry for the caller
-            if (img.sof == kSOF0 || img.sof == kSOF1 || img.sof == kSOF2) plan_image_geometry(img, BaselineGeometry::latch(dec, dec.frame_header()));
-        } else {
-            plan_image_geometry(img, fp.jobs[0].geo);
-            img.blocks_per_mcu = (uint32_t)fp.jobs[0].blocks_per_mcu;
-        }
-        fp.seq_ends = handler.sequential_ends();
-    } catch (const DecodeError &e) {
-        // the scans of a progressive frame recorded before the walk failed ran in the reference too (each ProcessScan
-        // decodes its scan on the spot): they are kept so that their own failures come first
-        if (decoding && e.status != JPGPU_ERR_NOT_SUPPORTED) {
-            try {
-                handler.on_dispose(dec);
-            } catch (const DecodeError &) {
-            }
-        }
-        const bool keep = decoding && !fp.jobs.empty() && e.status != JPGPU_ERR_NOT_SUPPORTED;
-        if (keep) {
-            // scans handed to the scan decoder before the walk failed: they run, the failure is reported behind them
-            img.late_status = e.status;
-            img.late_detail = e.detail;
-            img.late_error = e.what();
-            try {
-                plan_image_geometry(img, fp.jobs[0].geo);
-                img.blocks_per_mcu = (uint32_t)fp.jobs[0].blocks_per_mcu;
-            } catch (const DecodeError &e2) {
-                fp.jobs.clear();
-                img.status = e2.status;
-                img.detail = e2.detail;
-                img.error = e2.what();
-            }
-        } else {
-            fp.jobs.clear();
-            img.status = e.status;
-            img.detail = e.detail;
-            img.error = e.what();
-        }
-    }
-    if (!entropy_only_ && img.status == JPGPU_OK) plan_swallowed_terminator(fp, file, len, false);
-}
-
-// Headers only: both marker loops up to the first SOS header, the scan planned as the file's only one.
-void DeviceBatch::plan_file_headers(const uint8_t *file, size_t len, FilePlan &fp) const {
-    fp.jobs.clear();
-    fp.seq_ends.clear();
-    fp.speculative = fp.need_full = false;
-    fp.img = ImagePlan();
-    ImagePlan &img = fp.img;
-    img.file_len = len;
-    if (entropy_only_ || len > 0x7FFFFFF0u || !forced_swallow_.empty()) {
-        fp.need_full = true;  // optimizer walks have rules of their own; oversize files are refused by the full path; a re-plan walks the file
-        return;
-    }
-    HostDecoder dec;
-    try {
-        dec.set_input(file, len);
-        if (!dec.identify_until_scan(false, &fp.scan_data_pos)) {
-            fp.need_full = true;  // no scan in the file: the walk just done WAS the whole Identify; let the general path plan it
-            return;
-        }
-        if (!dec.has_frame_header()) {
-            fp.need_full = true;  // SOS in front of any SOF: Identify's verdict depends on what follows the scan
-            return;
-        }
-    } catch (const DecodeError &e) {
-        // Identify fails in front of the first scan: that is what the caller sees, whatever follows
-        img.status = e.status;
-        img.detail = e.detail;
-        img.error = e.what();
-        return;
-    }
-    img.sof = (uint8_t)dec.start_of_frame();
-    try {
-        FastPlanHandler handler(&fp.jobs);
-        dec.decode(handler, true);
-        if (fp.jobs.size() != 1) throw NeedFullWalk{};
-        plan_image_geometry(img, fp.jobs[0].geo);
-        img.blocks_per_mcu = (uint32_t)fp.jobs[0].blocks_per_mcu;
-        fp.speculative = true;
-    } catch (const NeedFullWalk &) {
-        fp.need_full = true;
-    } catch (const DecodeError &) {
-        // Decode's loop fails before the scan is planned -- but Identify walks the WHOLE file first, and a failure of
-        // its own behind the scan would be the one the caller sees: only the full walk can tell
-        fp.need_full = true;
-    }
-    if (fp.need_full) fp.jobs.clear();
-}
-
-// What Decode() ends in when the LAST sequential scan of the file leaves its reader one byte into the terminating marker.
-// identify_is_clean: the header-only path already knows that Identify() succeeds (and what it latched lies in front of
-// the first SOS): its walk over the entropy data is not repeated.
-void DeviceBatch::plan_swallowed_terminator(FilePlan &fp, const uint8_t *file, size_t len, bool identify_is_clean) const {
-    ImagePlan &img = fp.img;
-    img.swallow_status = JPGPU_OK;
-    img.swallow_detail = 0;
-    img.swallow_error.clear();
-    img.swallow_job = -1;
-    const std::vector<size_t> &ends = fp.seq_ends;
-    if (ends.empty() || fp.jobs.empty()) return;
-    int last = -1, n_seq = 0;
-    for (size_t j = 0; j < fp.jobs.size(); j++)
-        if (fp.jobs[j].kind == kScanSequential) {
-            last = (int)j;
-            n_seq++;
-        }
-    if (last < 0 || n_seq != (int)ends.size() || ends.back() >= fp.jobs[last].entropy_len) return;  // no marker behind it
-    img.swallow_job = last;  // index into fp.jobs; upload_files turns it into a batch job index
-    if (identify_is_clean && n_seq == 1 && (size_t)(fp.jobs[last].entropy - file) + ends.back() + 2 == len) {
-        // The EOI closes the file (every clean file): the replayed walk would step over the scan to one byte into the
-        // marker, find a single byte left and fail in TryReadMarker (JpegDecoder.cs:533-537).  Written down directly: a
-        // thousand exceptions thrown from a crew of threads serialise on the unwinder's lock.
-        img.swallow_status = JPGPU_ERR_INVALID_DATA;
-        img.swallow_detail = kDetailBadHeader;
-        img.swallow_error = "Failed to decode JPEG data at offset " + std::to_string(len - 1) + ". No marker found.";
-        return;
-    }
-    try {
-        HostDecoder dec;
-        dec.set_input(file, len);
-        if (identify_is_clean) {
-            size_t pos;
-            (void)dec.identify_until_scan(false, &pos);
-        } else {
-            dec.identify(false);
-        }
-        PlanHandler replay(&ends, n_seq - 1);
-        dec.decode(replay, true);
-    } catch (const DecodeError &e) {
-        img.swallow_status = e.status;
-        img.swallow_detail = e.detail;
-        img.swallow_error = e.what();
-    }
-}
-
-// Crew size when the caller did not choose one: the CPUs this process may really use -- the affinity mask and the cgroup
-// CPU quota (v2 cpu.max, v1 cpu.cfs_quota_us) both bound it (a container often reports the machine's 256 threads and is
-// granted 16) -- capped at 16.
-int granted_host_cpus() {
-    unsigned cpus = std::max(1u, std::thread::hardware_concurrency());
-    cpu_set_t set;
-    CPU_ZERO(&set);
-    if (sched_getaffinity(0, sizeof set, &set) == 0 && CPU_COUNT(&set) > 0) cpus = std::min(cpus, (unsigned)CPU_COUNT(&set));
-    bool have_quota = false;
-    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {  // cgroup v2: "<quota> <period>" or "max <period>"
-        char q[32] = {0};
-        long period = 0;
-        if (fscanf(f, "%31s %ld", q, &period) == 2 && period > 0) {
-            have_quota = true;
-            if (strcmp(q, "max") != 0) {
-                const long quota = atol(q);
-                if (quota > 0) cpus = std::min(cpus, (unsigned)std::max(1L, (quota + period - 1) / period));
-            }
-        }
-        fclose(f);
-    }
-    if (!have_quota) {  // cgroup v1: cpu.cfs_quota_us (-1 = unlimited) / cpu.cfs_period_us
-        long quota = -1, period = 0;
-        if (FILE *f = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) {
-            if (fscanf(f, "%ld", &quota) != 1) quota = -1;
-            fclose(f);
-        }
-        if (FILE *f = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) {
-            if (fscanf(f, "%ld", &period) != 1) period = 0;
-            fclose(f);
-        }
-        if (quota > 0 && period > 0) cpus = std::min(cpus, (unsigned)std::max(1L, (quota + period - 1) / period));
-    }
-    return (int)cpus;
-}
-int default_host_threads() {
-    if (const char *ev = getenv("JPGPU_HOST_THREADS")) return std::max(1, atoi(ev));
-    return std::min(16, granted_host_cpus());  // a handful of threads already keep the host link busy (profiles/r02_ingest_sweep.jsonl)
-}
-
-// One input file as the caller handed it over: a list of segments (one for jpgpu_batch_upload), and the contiguous bytes the
-// host parser reads -- the file itself, or what was gathered of a multi-segment file (its head for the header-only plan, all
-// of it for the full marker walks).
-struct DeviceBatch::FileSegs {
-    const jpgpu_segment *seg = nullptr;
-    int n = 0;
-    size_t len = 0;
-    const uint8_t *base = nullptr;
-    size_t base_len = 0;
-    std::vector<uint8_t> gathered;
-    // jpgpu_batch_upload_device: the file lies in the caller's device memory (no segments) and, once staged, at `slot` of the
-    // input buffer; `base` is its head as the device delivered it, or the whole file fetched back from its slot; the host sees
-    // nothing else of it but the two bytes at its ingest verdict (verdict_at: offset in the file)
-    const uint8_t *dev = nullptr;
-    bool device = false;
-    uint64_t slot = 0;
-    size_t verdict_at = 0;
-    uint32_t verdict = 0;
-    static constexpr size_t kHeadBytes = 64u << 10;
-    bool whole() const { return base_len == len; }
-    void gather(size_t want) {
-        want = std::min(want, len);
-        gathered.resize(want);
-        size_t pos = 0;
-        for (int k = 0; k < n && pos < want; k++) {
-            const size_t m = std::min(seg[k].len, want - pos);
-            if (m) memcpy(gathered.data() + pos, seg[k].data, m);
-            pos += m;
-        }
-        base = gathered.data();
-        base_len = want;
-    }
-    uint8_t at(size_t off) const {
-        if (device) return off == verdict_at ? (uint8_t)verdict : off == verdict_at + 1 ? (uint8_t)(verdict >> 8) : 0;
-        for (int k = 0; k < n; k++) {
-            if (off < seg[k].len) return seg[k].data[off];
-            off -= seg[k].len;
-        }
-        return 0;
-    }
-};
-
 int DeviceBatch::mark_work() {
     if (!done_ev_) {
         hipError_t e = hipEventCreateWithFlags(&done_ev_, hipEventDisableTiming);
@@ -539,677 +137,6 @@ int DeviceBatch::order_upload_behind_work() {
     if (!work_in_flight_ || !done_ev_) return JPGPU_OK;
     hipError_t e = hipStreamWaitEvent(ctx_->upload_stream, done_ev_, 0);
     if (e != hipSuccess) return hip_fail(e, "hipStreamWaitEvent(upload behind decode)");
-    return JPGPU_OK;
-}
-
-int DeviceBatch::upload_files(const uint8_t *const *jpeg, const size_t *len, int n, int format) {
-    if (n < 0 || (n > 0 && (!jpeg || !len))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload: null argument");
-    std::vector<jpgpu_segment> segs((size_t)n);
-    std::vector<int> per((size_t)n, 1);
-    for (int i = 0; i < n; i++) segs[(size_t)i] = {jpeg[i], len[i]};
-    return upload_segments(segs.data(), per.data(), n, format, 0);
-}
-
-int DeviceBatch::upload_segments(const jpgpu_segment *segments, const int *segments_per_file, int n, int format, unsigned flags) {
-    if (n < 0 || (n > 0 && (!segments || !segments_per_file))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload: null argument");
-    if (format < 0 || format >= kNumOutputFormats) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload: unknown format");
-    if (flags & ~(JPGPU_UPLOAD_PINNED | JPGPU_UPLOAD_PINNED_ARENA)) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_segments: unknown flag");
-    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
-    int rc = begin_ingest(n, format);
-    if (rc != JPGPU_OK) return rc;
-    std::vector<FileSegs> files((size_t)n);
-    {
-        const jpgpu_segment *sp = segments;
-        for (int i = 0; i < n; i++) {
-            FileSegs &f = files[(size_t)i];
-            if (segments_per_file[i] < 0) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_segments: negative segment count");
-            f.seg = sp;
-            f.n = segments_per_file[i];
-            sp += f.n;
-            for (int k = 0; k < f.n; k++) {
-                if (f.seg[k].len && !f.seg[k].data) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload: null segment");
-                f.len += f.seg[k].len;
-            }
-            if (f.n == 1) {
-                f.base = f.seg[0].data;
-                f.base_len = f.len;
-            }
-        }
-    }
-    return ingest_files(files, flags, t_begin);
-}
-
-// What every upload of whole files starts with: the batch forgets its images and jobs, the upload stream waits for the batch's
-// unsynchronised device work.
-int DeviceBatch::begin_ingest(int n, int format) {
-    ingest_ = IngestStats();
-    device_ingest_ = jpgpu_device_ingest_stats();
-    hipError_t e = hipSetDevice(ctx_->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    int rc = order_upload_behind_work();
-    if (rc != JPGPU_OK) return rc;
-    format_ = format;
-    images_.assign((size_t)n, ImagePlan());
-    jobs_.clear();
-    job_image_.clear();
-    job_entropy_off_.clear();
-    return JPGPU_OK;
-}
-
-// jpgpu_batch_upload for whole files that lie in device memory of the context's device (include/jpgpu.h, 1b).
-int DeviceBatch::upload_device(const void *const *device_jpeg, const size_t *len, int n, int format) {
-    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
-    auto refuse = [&](const std::string &why) {
-        images_.clear();
-        jobs_.clear();
-        job_image_.clear();
-        job_entropy_off_.clear();
-        whole_files_ = replay_possible_ = false;
-        device_ingest_ = jpgpu_device_ingest_stats();
-        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_device: " + why);
-    };
-    if (n < 0 || (n > 0 && (!device_jpeg || !len))) return refuse("null argument");
-    if (format < 0 || format >= kNumOutputFormats) return refuse("unknown format");
-    hipError_t e = hipSetDevice(ctx_->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    std::vector<FileSegs> files((size_t)n);
-    for (int i = 0; i < n; i++) {
-        FileSegs &f = files[(size_t)i];
-        f.device = true;
-        f.len = len[i];
-        if (f.len == 0) continue;  // the empty file: its pointer is not looked at
-        f.dev = (const uint8_t *)device_jpeg[i];
-        const std::string which = "file " + std::to_string(i);
-        if (!f.dev) return refuse(which + ": null pointer");
-        const int where = check_device_range(ctx_->device, f.dev, f.len);
-        if (where == 1) return refuse(which + " is not in device memory of the context's device");
-        if (where == 2) return refuse(which + ": " + std::to_string(f.len) + " bytes do not lie inside one device allocation");
-    }
-    const int rc = begin_ingest(n, format);
-    if (rc != JPGPU_OK) return rc;
-    return ingest_files(files, 0, t_begin);
-}
-
-int check_device_range(int device, const void *p, size_t bytes) {
-    hipPointerAttribute_t attr;
-    memset(&attr, 0, sizeof attr);
-    hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess) (void)hipGetLastError();  // (host memory the runtime has never seen: an error of this query, not of the stream)
-    if (e != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != device) return 1;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p);
-    if (e != hipSuccess) (void)hipGetLastError();
-    const uintptr_t lo = (uintptr_t)base, at = (uintptr_t)p;
-    if (e != hipSuccess || at < lo || at - lo > size || bytes > size - (at - lo)) return 2;
-    return 0;
-}
-
-// The ingest proper, for files in host memory (segments) and in device memory alike.  The two sources differ in how a file's
-// head is obtained (host: it is there, or gathered from the segments; device: the files are staged FIRST, the device says how
-// long each head is and delivers them packed), how a whole file is obtained (host: gathered from the segments by the crew
-// thread that needs it; device: the files that need it are fetched back from their slots together, one synchronisation) and
-// how the two bytes at the verdict are read (FileSegs::at).  Everything else is one body.
-int DeviceBatch::ingest_files(std::vector<FileSegs> &files, unsigned flags, std::chrono::steady_clock::time_point t_begin) {
-    const int n = (int)files.size();
-    const bool device = n > 0 && files[0].device;
-    const bool pinned = (flags & (JPGPU_UPLOAD_PINNED | JPGPU_UPLOAD_PINNED_ARENA)) != 0;
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t0) { return (float)std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
-    hipError_t e = hipSuccess;
-    int rc = JPGPU_OK;
-    constexpr size_t kMaxFile = 0x7FFFFFF0u;
-    uint64_t total_bytes = 0;
-    for (const FileSegs &f : files) total_bytes += f.len;
-    std::vector<FilePlan> plans((size_t)n);
-
-    const int want = ctx_->host_threads > 0 ? ctx_->host_threads : default_host_threads();
-    // no more threads than there is work for: one per 8 files or per 2 MiB, whichever asks for more
-    const int useful = (int)std::max<uint64_t>((uint64_t)(n + 7) / 8, total_bytes >> 21);
-    WorkCrew crew(std::max(1, std::min(want, useful)));
-    ingest_.threads = crew.threads();
-
-    // ---- 1. header-only plans (a multi-segment file: over its first 64 KiB, gathered; should its first scan start behind
-    //         them, or the plan not be "headers + one sequential scan", the whole file is gathered for the full walks)
-    clk::time_point t0 = clk::now();
-    float device_stage_ms = 0;
-    if (device) {
-        // (a device source: step 2 comes first -- the heads are read from the batch's own copy of the files)
-        rc = stage_device_files(files);
-        if (rc != JPGPU_OK) return rc;
-        device_stage_ms = ms_since(t0);
-        t0 = clk::now();
-    }
-    std::atomic<int> n_linearised{0};
-    std::vector<int> fetch;            // device files whose head did not do: fetched whole, together, and planned again
-    std::vector<uint8_t> want_whole((size_t)(device ? n : 0), 0);
-    crew.run((size_t)n, [&](size_t i, int) {
-        FileSegs &f = files[i];
-        FilePlan &fp = plans[i];
-        if (f.len > kMaxFile) {
-            fp.img.file_len = f.len;
-            fp.need_full = true;  // refused by the full path before it reads a byte
-            return;
-        }
-        if (f.n > 1) f.gather(FileSegs::kHeadBytes);
-        plan_file_headers(f.base, f.base_len, fp);
-        if (!f.whole()) {
-            if (fp.speculative) {
-                fp.jobs[0].entropy_len = f.len - fp.scan_data_pos;
-            } else if (f.device) {
-                want_whole[i] = 1;
-            } else {
-                f.gather(f.len);
-                n_linearised.fetch_add(1, std::memory_order_relaxed);
-                plan_file_headers(f.base, f.base_len, fp);
-            }
-        }
-        fp.img.file_len = f.len;
-    });
-    for (size_t i = 0; i < want_whole.size(); i++)
-        if (want_whole[i]) fetch.push_back((int)i);
-    if (!fetch.empty()) {
-        rc = fetch_device_files(files, fetch);
-        if (rc != JPGPU_OK) return rc;
-        crew.run(fetch.size(), [&](size_t k, int) {
-            FileSegs &f = files[(size_t)fetch[k]];
-            FilePlan &fp = plans[(size_t)fetch[k]];
-            plan_file_headers(f.base, f.base_len, fp);
-            fp.img.file_len = f.len;
-        });
-    }
-    ingest_.parse_ms = ms_since(t0);
-
-    // ---- 2. the files -> HBM (every file gets its slot, whatever became of its plan: the layout does not wait for plans)
-    t0 = clk::now();
-    // One page-locked arena (JPGPU_UPLOAD_PINNED_ARENA): the device copy keeps the arena's own layout -- file i lies where it
-    // lies in the arena, relative to the lowest address -- so the whole span travels as a few large DMAs instead of one per
-    // file (1 MiB copies reach ~36 GB/s on this link, 32 MiB ones 56).  Needs every file contiguous in memory and a span
-    // that is mostly payload; otherwise the files go one DMA per segment.
-    arena_span_ = {nullptr, 0};
-    if ((flags & JPGPU_UPLOAD_PINNED_ARENA) && n > 0) {
-        const uint8_t *lo = nullptr, *hi = nullptr;
-        bool contiguous = true;
-        for (int i = 0; i < n && contiguous; i++) {
-            const FileSegs &f = files[(size_t)i];
-            if (f.len == 0) continue;
-            if (f.len > kMaxFile) contiguous = false;
-            const uint8_t *expect = nullptr;
-            for (int k = 0; k < f.n; k++) {
-                if (!f.seg[k].len) continue;
-                if (expect && f.seg[k].data != expect) contiguous = false;
-                if (!lo || f.seg[k].data < lo) lo = f.seg[k].data;
-                if (!hi || f.seg[k].data + f.seg[k].len > hi) hi = f.seg[k].data + f.seg[k].len;
-                expect = f.seg[k].data + f.seg[k].len;
-            }
-        }
-        if (contiguous && lo && (uint64_t)(hi - lo) <= 2 * total_bytes + (1u << 20)) arena_span_ = {lo, (size_t)(hi - lo)};
-    }
-    uint64_t in_off = 256;
-    if (device) {
-        for (int i = 0; i < n; i++) plans[i].img.file_offset = files[(size_t)i].slot;  // (stage_device_files has laid them out)
-    } else if (arena_span_.first) {
-        for (int i = 0; i < n; i++) {
-            const FileSegs &f = files[(size_t)i];
-            const uint8_t *first = nullptr;
-            for (int k = 0; k < f.n && !first; k++)
-                if (f.seg[k].len) first = f.seg[k].data;
-            plans[i].img.file_offset = 256 + (first ? (uint64_t)(first - arena_span_.first) : 0u);
-        }
-        in_off = align_up(256 + arena_span_.second, 256);
-    } else {
-        for (int i = 0; i < n; i++) {
-            plans[i].img.file_offset = in_off;
-            if (files[(size_t)i].len <= kMaxFile) in_off = align_up(in_off + files[(size_t)i].len, 256);
-        }
-    }
-    if (!device) {
-        input_bytes_ = in_off + 256;
-        rc = stage_files(crew, files, plans, pinned);
-        if (rc != JPGPU_OK) return rc;
-    }
-
-    // ---- 3. the device's verdict on the header-only plans
-    std::vector<int> spec;
-    for (int i = 0; i < n; i++)
-        if (plans[i].speculative) spec.push_back(i);
-    if (!spec.empty()) {
-        std::vector<uint32_t> first, bytes;
-        rc = verify_plans(plans, spec, first, device ? &bytes : nullptr);
-        if (rc != JPGPU_OK) return rc;
-        for (size_t k = 0; k < spec.size(); k++) {
-            FilePlan &fp = plans[spec[k]];
-            FileSegs &f = files[(size_t)spec[k]];
-            const size_t dlen = f.len - fp.scan_data_pos;
-            const uint32_t pos = first[k];
-            if (device) {
-                f.verdict_at = fp.scan_data_pos + pos;
-                f.verdict = bytes[k];
-            }
-            // classify16 only calls FF xx a marker when xx exists: pos + 1 < dlen
-            if (pos != 0xFFFFFFFFu && (size_t)pos + 1 < dlen && f.at(fp.scan_data_pos + pos) == 0xFF && f.at(fp.scan_data_pos + pos + 1) == kEOI) {
-                fp.seq_ends.assign(1, (size_t)pos);
-            } else {
-                fp.speculative = false;
-                fp.need_full = true;
-                fp.jobs.clear();
-            }
-        }
-    } else {
-        e = hipStreamSynchronize(ctx_->upload_stream);  // the caller's buffers may be released after upload returns
-        if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(upload)");
-    }
-    work_in_flight_ = false;  // the upload stream waited for this batch's earlier device work, and has been drained
-    ingest_.copy_ms = ms_since(t0) + device_stage_ms;
-
-    // ---- 4. the rest: "one byte into the terminator" verdicts of the confirmed plans, full walks of everything else
-    t0 = clk::now();
-    if (device) {
-        // a device file the host has only the head of: like a multi-segment file it keeps its header-only plan when the EOI
-        // closes the file, and takes the general path otherwise; the files that do are fetched together
-        fetch.clear();
-        for (int i = 0; i < n; i++) {
-            FilePlan &fp = plans[i];
-            const FileSegs &f = files[(size_t)i];
-            if (f.whole() || f.len > kMaxFile) continue;
-            if (fp.speculative && fp.scan_data_pos + fp.seq_ends[0] + 2 != f.len) {
-                fp.speculative = false;
-                fp.need_full = true;
-            }
-            if (fp.need_full) fetch.push_back(i);
-        }
-        rc = fetch_device_files(files, fetch);
-        if (rc != JPGPU_OK) return rc;
-    }
-    crew.run((size_t)n, [&](size_t i, int) {
-        FilePlan &fp = plans[i];
-        FileSegs &f = files[i];
-        const uint64_t off = fp.img.file_offset;
-        // a multi-segment file planned from its head: the direct verdict needs nothing but offsets when the EOI closes the
-        // file; anything else replays the walk over the whole file, i.e. takes the general path
-        if (fp.speculative && !f.whole() && fp.scan_data_pos + fp.seq_ends[0] + 2 != f.len) {
-            fp.speculative = false;
-            fp.need_full = true;
-        }
-        if (fp.speculative) {
-            plan_swallowed_terminator(fp, f.base, f.len, true);
-        } else if (fp.need_full) {
-            if (!f.whole() && f.len <= kMaxFile) {
-                f.gather(f.len);
-                n_linearised.fetch_add(1, std::memory_order_relaxed);
-            }
-            plan_file_full(f.base, f.len, (int)i, fp);
-        }
-        fp.img.file_offset = off;
-    });
-    ingest_.full_walk_ms = ms_since(t0);
-    ingest_.n_linearised = n_linearised.load();
-
-    // ---- 5. merge into the batch's job list (file order)
-    t0 = clk::now();
-    std::vector<const uint8_t *> file_ptr((size_t)n);
-    std::vector<size_t> file_len((size_t)n);
-    for (int i = 0; i < n; i++) {
-        FilePlan &fp = plans[i];
-        const FileSegs &f = files[(size_t)i];
-        file_ptr[(size_t)i] = f.base;
-        file_len[(size_t)i] = f.len;
-        const size_t first_job = jobs_.size();
-        if (fp.speculative) ingest_.n_header_only++;
-        else if (fp.need_full) ingest_.n_full_walk++;
-        images_[i] = std::move(fp.img);
-        ImagePlan &img = images_[i];
-        img.file_len = f.len;
-        img.jobs.clear();
-        if (img.status != JPGPU_OK) continue;
-        for (size_t j = 0; j < fp.jobs.size(); j++) {
-            img.jobs.push_back((int)(first_job + j));
-            job_image_.push_back(i);
-            job_entropy_off_.push_back(fp.jobs[j].entropy ? (uint64_t)(fp.jobs[j].entropy - f.base) : 0u);
-            jobs_.push_back(std::move(fp.jobs[j]));
-        }
-        if (img.swallow_job >= 0) img.swallow_job += (int)first_job;
-    }
-    plans.clear();
-    files_resident_ = true;
-    rc = layout_and_upload(file_ptr, file_len);
-    files_resident_ = false;
-    replay_possible_ = rc == JPGPU_OK && !entropy_only_;
-    whole_files_ = rc == JPGPU_OK;  // (redo_swallowed: the files are in d_input_ as they came)
-    ingest_.layout_ms = ms_since(t0);
-    ingest_.total_ms = ms_since(t_begin);
-    return rc;
-}
-
-// Step 2 of the ingest: caller memory -> HBM.
-//  - pageable input: through the pinned staging ring.  The input buffer is cut into pieces that never cross a 32 MiB slot;
-//    the crew copies pieces in buffer order, whoever completes a slot sends it off (one DMA per slot) and records the event
-//    that frees the slot for the chunk n_slots later;
-//  - page-locked input (JPGPU_UPLOAD_PINNED): one DMA per segment from where the caller's bytes lie; the slack between the
-//    files is zeroed by one fill of the whole input buffer in front of the copies (~0.3 ms per GB, on the device).
-int DeviceBatch::stage_files(WorkCrew &crew, const std::vector<FileSegs> &files, const std::vector<FilePlan> &plans, bool pinned) {
-    hipError_t e = d_input_.reserve((size_t)input_bytes_);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(input)");
-    constexpr size_t kMaxFile = 0x7FFFFFF0u;
-    hipStream_t up = ctx_->upload_stream;
-    uint8_t *d_in = (uint8_t *)d_input_.ptr;
-    if (pinned && arena_span_.first) {
-        // the slack in front of the span and behind it is read by the kernels' wide loads: defined (zero); what lies between
-        // the files inside the span are the arena's own bytes (nothing a result depends on: every read is bounded by a length)
-        e = hipMemsetAsync(d_in, 0, 256, up);
-        const uint64_t tail = 256 + arena_span_.second;
-        if (e == hipSuccess) e = hipMemsetAsync(d_in + tail, 0, (size_t)(input_bytes_ - tail), up);
-        if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(input slack)");
-        constexpr size_t kChunk = 32u << 20;
-        for (size_t off = 0; off < arena_span_.second; off += kChunk) {
-            const size_t m = std::min(kChunk, arena_span_.second - off);
-            e = hipMemcpyAsync(d_in + 256 + off, arena_span_.first + off, m, hipMemcpyHostToDevice, up);
-            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(pinned arena)");
-            ingest_.n_pinned_dma++;
-        }
-        return JPGPU_OK;
-    }
-    if (pinned) {
-        // segments scattered in page-locked memory: the device pulls them itself (gather_pinned_kernel, 32 KiB pieces) -- one
-        // launch instead of one hipMemcpyAsync per segment (JPGPU_PINNED_MEMCPY=1: the copy engine, per segment, as before)
-        e = hipMemsetAsync(d_in, 0, (size_t)input_bytes_, up);
-        if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(input)");
-        const bool by_memcpy = getenv("JPGPU_PINNED_MEMCPY") != nullptr;
-        constexpr uint32_t kPiece = 32u << 10;
-        std::vector<GatherPiece> gp;
-        for (size_t i = 0; i < plans.size(); i++) {
-            const FileSegs &f = files[i];
-            if (f.len > kMaxFile || f.len == 0) continue;
-            uint64_t off = plans[i].img.file_offset;
-            for (int k = 0; k < f.n; k++) {
-                if (!f.seg[k].len) continue;
-                if (by_memcpy) {
-                    e = hipMemcpyAsync(d_in + off, f.seg[k].data, f.seg[k].len, hipMemcpyHostToDevice, up);
-                    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(pinned segment)");
-                } else {
-                    for (size_t at = 0; at < f.seg[k].len; at += kPiece)
-                        gp.push_back({(uint64_t)(uintptr_t)(f.seg[k].data + at), off + at, (uint32_t)std::min<size_t>(kPiece, f.seg[k].len - at), 0u});
-                }
-                off += f.seg[k].len;
-                ingest_.n_pinned_dma++;
-            }
-        }
-        if (!gp.empty()) {
-            e = d_gather_.reserve(gp.size() * sizeof(GatherPiece));
-            if (e != hipSuccess) return hip_fail(e, "hipMalloc(gather list)");
-            e = hipMemcpyAsync(d_gather_.ptr, gp.data(), gp.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, up);
-            if (e == hipSuccess) e = hipStreamSynchronize(up);  // `gp` is a local (pageable) vector
-            if (e == hipSuccess) e = launch_gather_pinned(up, (const GatherPiece *)d_gather_.ptr, (int)gp.size(), d_in);
-            if (e != hipSuccess) return hip_fail(e, "gather_pinned_kernel");
-        }
-        return JPGPU_OK;
-    }
-    struct Piece {
-        const uint8_t *src;  // nullptr: zero fill (slack in front of the first file, behind the last, between files)
-        uint64_t dst;
-        uint32_t n;
-    };
-    StagingRing &ring = ctx_->staging;
-    const uint64_t kSlot = ring.slot_bytes;
-    const size_t n_slots = (size_t)ring.n_slots;
-    constexpr uint32_t kPieceMax = 2u << 20;
-    std::vector<Piece> pieces;
-    auto add = [&](const uint8_t *src, uint64_t dst, uint64_t n) {
-        while (n) {
-            const uint64_t room = kSlot - dst % kSlot;
-            const uint32_t m = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, room), kPieceMax);
-            pieces.push_back({src, dst, m});
-            if (src) src += m;
-            dst += m;
-            n -= m;
-        }
-    };
-    uint64_t pos = 0;
-    for (size_t i = 0; i < plans.size(); i++) {
-        const FileSegs &f = files[i];
-        uint64_t off = plans[i].img.file_offset;
-        if (f.len > kMaxFile || f.len == 0) continue;
-        if (off > pos) add(nullptr, pos, off - pos);
-        for (int k = 0; k < f.n; k++) {
-            if (!f.seg[k].len) continue;
-            add(f.seg[k].data, off, f.seg[k].len);
-            off += f.seg[k].len;
-        }
-        pos = off;
-    }
-    if (input_bytes_ > pos) add(nullptr, pos, input_bytes_ - pos);
-
-    const size_t n_chunks = (size_t)((input_bytes_ + kSlot - 1) / kSlot);
-    std::vector<std::atomic<int>> remaining(n_chunks);
-    std::vector<std::atomic<int>> state(n_chunks);  // 0 = being filled, 1 = DMA issued (event recorded), 2 = slot known drained
-    for (size_t c = 0; c < n_chunks; c++) {
-        remaining[c].store(0, std::memory_order_relaxed);
-        state[c].store(0, std::memory_order_relaxed);
-    }
-    for (const Piece &p : pieces) remaining[p.dst / kSlot].fetch_add(1, std::memory_order_relaxed);
-    for (size_t c = 0; c < std::min<size_t>(n_chunks, n_slots); c++) {
-        if (!ring.slot[c]) {
-            e = hipHostMalloc((void **)&ring.slot[c], kSlot, hipHostMallocDefault);
-            if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(staging)");
-        }
-        if (!ring.drained[c]) {
-            e = hipEventCreateWithFlags(&ring.drained[c], hipEventDisableTiming | hipEventBlockingSync);
-            if (e != hipSuccess) return hip_fail(e, "hipEventCreate(staging)");
-        }
-    }
-    std::atomic<int> hip_error{(int)hipSuccess};
-    const int device = ctx_->device;
-    const uint64_t total = input_bytes_;
-    crew.run(pieces.size(), [&](size_t k, int) {
-        const Piece &p = pieces[k];
-        const size_t c = (size_t)(p.dst / kSlot);
-        const int slot = (int)(c % n_slots);
-        if (hip_error.load(std::memory_order_relaxed) != (int)hipSuccess) return;
-        (void)hipSetDevice(device);
-        if (c >= n_slots) {
-            // the slot still holds chunk c - n_slots until that chunk's DMA has read it
-            std::atomic<int> &prev = state[c - n_slots];
-            while (prev.load(std::memory_order_acquire) == 0) {
-                if (hip_error.load(std::memory_order_relaxed) != (int)hipSuccess) return;
-                std::this_thread::yield();
-            }
-            if (prev.load(std::memory_order_acquire) == 1) {
-                const hipError_t es = hipEventSynchronize(ring.drained[slot]);
-                if (es != hipSuccess) {
-                    hip_error.store((int)es);
-                    return;
-                }
-                prev.store(2, std::memory_order_release);
-            }
-        }
-        uint8_t *dst = ring.slot[slot] + (p.dst - (uint64_t)c * kSlot);
-        if (p.src) memcpy(dst, p.src, p.n);
-        else memset(dst, 0, p.n);
-        if (remaining[c].fetch_sub(1, std::memory_order_acq_rel) == 1) {
-            const uint64_t base = (uint64_t)c * kSlot;
-            const size_t bytes = (size_t)std::min<uint64_t>(kSlot, total - base);
-            hipError_t ec = hipMemcpyAsync(d_in + base, ring.slot[slot], bytes, hipMemcpyHostToDevice, up);
-            if (ec == hipSuccess) ec = hipEventRecord(ring.drained[slot], up);
-            if (ec != hipSuccess) hip_error.store((int)ec);
-            state[c].store(1, std::memory_order_release);
-        }
-    });
-    if (hip_error.load() != (int)hipSuccess) {
-        (void)hipStreamSynchronize(up);
-        return hip_fail((hipError_t)hip_error.load(), "staged H2D");
-    }
-    return JPGPU_OK;
-}
-
-// Step 3 of the ingest: first marker that is not RSTn behind every planned SOS header (first_marker_kernel); synchronises
-// the upload stream, so the caller's buffers are free once this returns.
-// bytes (a device source): the two bytes at each reported position too, low byte first (verdict_bytes_kernel behind the verdict;
-// the same D2H carries them).
-int DeviceBatch::verify_plans(const std::vector<FilePlan> &plans, const std::vector<int> &spec, std::vector<uint32_t> &first,
-                              std::vector<uint32_t> *bytes) {
-    const size_t n = spec.size();
-    std::vector<uint32_t> host(3 * n);  // {offset lo, length} pairs, then offset hi
-    uint32_t max_len = 0;
-    for (size_t k = 0; k < n; k++) {
-        const FilePlan &fp = plans[spec[k]];
-        const uint64_t off = fp.img.file_offset + fp.scan_data_pos;
-        const uint32_t dlen = (uint32_t)(fp.img.file_len - fp.scan_data_pos);
-        host[2 * k] = (uint32_t)off;
-        host[2 * k + 1] = dlen;
-        host[2 * n + k] = (uint32_t)(off >> 32);
-        max_len = std::max(max_len, dlen);
-    }
-    const size_t n_out = bytes ? 2 * n : n;
-    hipError_t e = d_verify_.reserve((3 * n + n_out) * sizeof(uint32_t) + 256);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(verify)");
-    StagingRing &ring = ctx_->staging;
-    int rc = reserve_verdict(n_out);
-    if (rc != JPGPU_OK) return rc;
-    hipStream_t up = ctx_->upload_stream;
-    uint32_t *d = (uint32_t *)d_verify_.ptr;
-    e = hipMemcpyAsync(d, host.data(), 3 * n * sizeof(uint32_t), hipMemcpyHostToDevice, up);
-    if (e == hipSuccess) e = hipMemsetAsync(d + 3 * n, 0xFF, n * sizeof(uint32_t), up);
-    if (e == hipSuccess) e = launch_first_marker(up, (const uint8_t *)d_input_.ptr, d, d + 2 * n, (int)n, max_len, d + 3 * n);
-    if (e == hipSuccess && bytes) e = launch_verdict_bytes(up, (const uint8_t *)d_input_.ptr, d, d + 2 * n, d + 3 * n, (int)n, d + 4 * n);
-    if (e == hipSuccess) e = hipMemcpyAsync(ring.verdict, d + 3 * n, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, up);
-    if (e == hipSuccess) e = hipStreamSynchronize(up);
-    if (e != hipSuccess) return hip_fail(e, "ingest verification");
-    first.assign(ring.verdict, ring.verdict + n);
-    if (bytes) bytes->assign(ring.verdict + n, ring.verdict + 2 * n);
-    return JPGPU_OK;
-}
-
-// the context's page-locked words for small per-file results of the device (the ingest verdicts, the head lengths)
-int DeviceBatch::reserve_verdict(size_t n) {
-    StagingRing &ring = ctx_->staging;
-    if (ring.verdict_cap >= n) return JPGPU_OK;
-    if (ring.verdict) (void)hipHostFree(ring.verdict);
-    ring.verdict = nullptr;
-    ring.verdict_cap = 0;
-    const size_t cap = std::max<size_t>(n, 4096);
-    const hipError_t e = hipHostMalloc((void **)&ring.verdict, cap * sizeof(uint32_t), hipHostMallocDefault);
-    if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(verdict)");
-    ring.verdict_cap = cap;
-    return JPGPU_OK;
-}
-
-// Step 2 of the ingest for a device source, and how its heads are obtained: the caller's device memory -> the input buffer
-// (gather_device_kernel: the slots of upload_segments' layout, every byte of slack written as zero), then the head the host
-// parser needs of every file: head_walk_kernel says how long it is, head_scan_kernel where it goes, head_pack_kernel packs them.
-// Two small H2D (the pieces, the files), four launches, one D2H of the lengths, offsets and total and a synchronisation -- from
-// there on no kernel reads the caller's memory any more --, then one D2H of the packed heads and a second synchronisation (the host
-// has to know the total before it can ask for the bytes), whatever the number of files.
-int DeviceBatch::stage_device_files(std::vector<FileSegs> &files) {
-    constexpr size_t kMaxFile = 0x7FFFFFF0u;
-    const size_t n = files.size();
-    uint64_t in_off = 256;
-    for (FileSegs &f : files) {
-        f.slot = in_off;
-        if (f.len <= kMaxFile) in_off = align_up(in_off + f.len, 256);
-    }
-    input_bytes_ = in_off + 256;
-    hipError_t e = d_input_.reserve((size_t)input_bytes_);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(input)");
-    std::vector<GatherPiece> gp;
-    std::vector<DeviceFile> df(n);
-    gp.push_back({0u, 0u, 0u, 256u});  // the slack in front of the first file ...
-    for (size_t i = 0; i < n; i++) {
-        const FileSegs &f = files[i];
-        df[i] = {0u, 0u, 0u};
-        if (f.len == 0 || f.len > kMaxFile) continue;
-        df[i] = {f.slot, (uint32_t)f.len, 0u};
-        for (size_t at = 0; at < f.len; at += kGatherPieceBytes) {
-            const uint32_t m = (uint32_t)std::min<size_t>(kGatherPieceBytes, f.len - at);
-            const uint32_t pad = at + m == f.len ? (uint32_t)(align_up(f.len, 256) - f.len) : 0u;  // (the last piece: up to the slot's end)
-            gp.push_back({(uint64_t)(uintptr_t)(f.dev + at), f.slot + at, m, pad});
-        }
-        device_ingest_.files_gathered++;
-        device_ingest_.bytes_gathered += f.len;
-    }
-    gp.push_back({0u, in_off, 0u, 256u});  // ... and behind the last
-    // one device buffer: the pieces, the files, then what comes back in one copy: head_off[n + 1] (64-bit; [n] = the total), head_len[n]
-    const size_t files_at = align_up(gp.size() * sizeof(GatherPiece), 256), off_at = align_up(files_at + n * sizeof(DeviceFile), 256);
-    const size_t len_at = off_at + (n + 1) * sizeof(uint64_t), back_words = 2 * (n + 1) + n;
-    e = d_gather_.reserve(len_at + n * sizeof(uint32_t) + 256);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(gather list)");
-    int rc = reserve_verdict(back_words);
-    if (rc != JPGPU_OK) return rc;
-    StagingRing &ring = ctx_->staging;
-    hipStream_t up = ctx_->upload_stream;
-    uint8_t *d_in = (uint8_t *)d_input_.ptr, *d_list = (uint8_t *)d_gather_.ptr;
-    const DeviceFile *d_files = (const DeviceFile *)(d_list + files_at);
-    uint64_t *d_head_off = (uint64_t *)(d_list + off_at);
-    uint32_t *d_head_len = (uint32_t *)(d_list + len_at);
-    e = hipMemcpyAsync(d_list, gp.data(), gp.size() * sizeof(GatherPiece), hipMemcpyHostToDevice, up);
-    if (e == hipSuccess && n) e = hipMemcpyAsync(d_list + files_at, df.data(), n * sizeof(DeviceFile), hipMemcpyHostToDevice, up);
-    for (hipEvent_t &ev : gather_ev_)
-        if (e == hipSuccess && !ev) e = hipEventCreate(&ev);
-    if (e == hipSuccess) e = hipEventRecord(gather_ev_[0], up);
-    if (e == hipSuccess) e = launch_gather_device(up, (const GatherPiece *)d_list, (int)gp.size(), d_in);
-    if (e == hipSuccess) e = hipEventRecord(gather_ev_[1], up);
-    if (e == hipSuccess) e = launch_head_walk(up, d_in, d_files, (int)n, d_head_len);
-    if (e == hipSuccess) e = launch_head_scan(up, d_head_len, (int)n, d_head_off);
-    if (e == hipSuccess && n) e = hipMemcpyAsync(ring.verdict, d_head_off, back_words * sizeof(uint32_t), hipMemcpyDeviceToHost, up);
-    if (e == hipSuccess) e = hipStreamSynchronize(up);  // (`gp` and `df` are local, pageable vectors; the caller's memory is free from here)
-    if (e == hipSuccess) e = hipEventElapsedTime(&device_ingest_.gather_ms, gather_ev_[0], gather_ev_[1]);
-    if (e != hipSuccess) return hip_fail(e, "gather of device files");
-    if (n == 0) return JPGPU_OK;
-    std::vector<uint64_t> head_off(n + 1);
-    memcpy(head_off.data(), ring.verdict, (n + 1) * sizeof(uint64_t));
-    const std::vector<uint32_t> head_len(ring.verdict + 2 * (n + 1), ring.verdict + back_words);
-    const uint64_t total = head_off[n];
-    for (size_t i = 0; i < n; i++)
-        if (head_len[i] & kHeadGaveUp) device_ingest_.walker_giveups++;
-    device_ingest_.head_bytes = total;
-    if (total == 0) return JPGPU_OK;
-    if (ring.heads_cap < total) {
-        if (ring.heads) (void)hipHostFree(ring.heads);
-        ring.heads = nullptr;
-        ring.heads_cap = 0;
-        const size_t cap = std::max<size_t>((size_t)total, 4u << 20);
-        e = hipHostMalloc((void **)&ring.heads, cap, hipHostMallocDefault);
-        if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(heads)");
-        ring.heads_cap = cap;
-    }
-    e = d_heads_.reserve((size_t)total + 256);
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(heads)");
-    e = launch_head_pack(up, d_in, d_files, (int)n, d_head_len, d_head_off, (uint8_t *)d_heads_.ptr);
-    if (e == hipSuccess) e = hipMemcpyAsync(ring.heads, d_heads_.ptr, (size_t)total, hipMemcpyDeviceToHost, up);
-    if (e == hipSuccess) e = hipStreamSynchronize(up);
-    if (e != hipSuccess) return hip_fail(e, "heads of device files");
-    for (size_t i = 0; i < n; i++) {
-        if (files[i].len > kMaxFile) continue;
-        files[i].base = ring.heads + head_off[i];
-        // (a hint: what the host reads of it is bounded by the file here too)
-        files[i].base_len = std::min<size_t>(head_len[i] & ~kHeadGaveUp, std::min<size_t>(files[i].len, kDeviceHeadMax));
-    }
-    return JPGPU_OK;
-}
-
-// How a whole device file is obtained: from its slot in the input buffer, one D2H per listed file, issued together, one
-// synchronisation.  The ingest calls it at most twice: behind the header-only plans (heads that did not do) and in front of step 4
-// (plans the device did not confirm, or whose EOI does not close the file).
-int DeviceBatch::fetch_device_files(std::vector<FileSegs> &files, const std::vector<int> &which) {
-    if (which.empty()) return JPGPU_OK;
-    hipStream_t up = ctx_->upload_stream;
-    for (int i : which) {
-        FileSegs &f = files[(size_t)i];
-        f.gathered.resize(f.len);
-        const hipError_t e = hipMemcpyAsync(f.gathered.data(), (const uint8_t *)d_input_.ptr + f.slot, f.len, hipMemcpyDeviceToHost, up);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(up);
-            return hip_fail(e, "hipMemcpyAsync(device file to the host)");
-        }
-        device_ingest_.files_downloaded++;
-        device_ingest_.bytes_downloaded += f.len;
-    }
-    const hipError_t e = hipStreamSynchronize(up);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(device files to the host)");
-    for (int i : which) {
-        FileSegs &f = files[(size_t)i];
-        f.base = f.gathered.data();
-        f.base_len = f.len;
-    }
     return JPGPU_OK;
 }
 
@@ -1326,9 +253,7 @@ int DeviceBatch::rerun_failed_progressive_scan(bool first_scan) {
     jobs_[1].last_interval = h_status_[1].first_error >> 8;  // the lowest failing restart interval: the reference never got behind it
     std::vector<const uint8_t *> fp(1, nullptr);
     std::vector<size_t> fl(1, images_[0].file_len);
-    files_resident_ = true;  // (the scan's bytes are in HBM already)
-    int rc = layout_and_upload(fp, fl);
-    files_resident_ = false;
+    int rc = layout_and_upload(fp, fl, true);  // (the scan's bytes are in HBM already)
     if (rc != JPGPU_OK) return rc;
     if (first_scan || prog_snapshot_blocks_ == 0 || prog_clear_.empty()) {
         keep_progressive_store_ = false;  // run_progressive() clears the store like JpegBlockAllocator.Allocate

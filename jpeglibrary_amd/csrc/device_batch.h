@@ -1,4 +1,5 @@
-// jpeglibrary_amd/csrc/device_batch.h -- device-resident batch of scan jobs: HBM layout, uploads, kernel launches.
+// jpeglibrary_amd/csrc/device_batch.h -- device-resident batch of scan jobs: HBM layout, uploads, kernel launches.  (DeviceBatch is implemented in
+// device_batch.cpp, device_batch_ingest.cpp, device_batch_layout.cpp, device_batch_launch.cpp and device_batch_result.cpp, by role.)
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -104,6 +105,8 @@ struct ImagePlan {
 };
 
 class WorkCrew;
+struct FilePlan;  // device_batch_ingest.cpp
+struct FileSegs;  // ingest_host.h
 
 class DeviceBatch {
   public:
@@ -196,7 +199,8 @@ class DeviceBatch {
     std::vector<uint8_t> preset_no_subseq_;  // entropy-only mode: files whose DRI = 0 scan stays on the interval kernel
     int fail(int status, const std::string &msg);
     int hip_fail(hipError_t e, const char *what);
-    int layout_and_upload(const std::vector<const uint8_t *> &file_ptr, const std::vector<size_t> &file_len);
+    // files_resident: the files are in d_input_ already (staged by the ingest, or by the upload this one lays out again)
+    int layout_and_upload(const std::vector<const uint8_t *> &file_ptr, const std::vector<size_t> &file_len, bool files_resident = false);
     // its stages, in the order they run (device_batch_layout.cpp); UploadPlan is what one stage hands the next
     struct UploadPlan;
     void reset_upload_state(const UploadPlan &p);
@@ -220,28 +224,36 @@ class DeviceBatch {
     void init_status();
     int upload_plan(const UploadPlan &p, const std::vector<const uint8_t *> &file_ptr, const std::vector<size_t> &file_len);
     void plan_image_geometry(ImagePlan &img, const BaselineGeometry &geo) const;
-    // ingest (jpgpu_batch_upload), see device_batch.cpp
-    struct FilePlan;
+    // ingest (jpgpu_batch_upload*), see device_batch_ingest.cpp
     void plan_file_headers(const uint8_t *file, size_t len, FilePlan &fp) const;
     void plan_file_full(const uint8_t *file, size_t len, int index, FilePlan &fp) const;
     void plan_swallowed_terminator(FilePlan &fp, const uint8_t *file, size_t len, bool identify_is_clean) const;
-    struct FileSegs;
     int begin_ingest(int n, int format);
+    void forget_batch();  // no images, no jobs
     int ingest_files(std::vector<FileSegs> &files, unsigned flags, std::chrono::steady_clock::time_point t_begin);
-    int stage_files(WorkCrew &crew, const std::vector<FileSegs> &files, const std::vector<FilePlan> &plans, bool pinned);
-    int stage_device_files(std::vector<FileSegs> &files);
+    // its stages, in the order they run (a device source stages in front of plan_heads); IngestRun is what one stage hands the next
+    struct IngestRun;
+    int plan_heads(IngestRun &r);
+    void find_arena_span(IngestRun &r) const;
+    int place_files(IngestRun &r);
+    int stage_pageable(IngestRun &r);
+    int stage_pinned_arena(IngestRun &r);
+    int stage_pinned_segments(IngestRun &r);
+    int stage_device_gather(IngestRun &r);
+    int stage_device_heads(IngestRun &r);
+    int confirm_plans(IngestRun &r);
+    int verify_plans(const IngestRun &r, const std::vector<int> &spec, std::vector<uint32_t> &first, std::vector<uint32_t> *bytes);
+    void demote_unclosed_plans(IngestRun &r) const;
+    int finish_plans(IngestRun &r);
+    void merge_plans(IngestRun &r);
     int fetch_device_files(std::vector<FileSegs> &files, const std::vector<int> &which);
-    int reserve_verdict(size_t n);
     // device work of this batch issued since its last sync(): uploads are ordered behind it (an upload right
     // after an un-synced decode must not overwrite what that decode's kernels still read)
     int mark_work();
     int order_upload_behind_work();
-    std::pair<const uint8_t *, size_t> arena_span_ = {nullptr, 0};  // JPGPU_UPLOAD_PINNED_ARENA: the span the device copy mirrors
     hipEvent_t done_ev_ = nullptr;
     bool work_in_flight_ = false;
-    int verify_plans(const std::vector<FilePlan> &plans, const std::vector<int> &spec, std::vector<uint32_t> &first, std::vector<uint32_t> *bytes);
     bool whole_files_ = false;     // the last upload was whole files (upload_files / upload_segments): d_input_ holds them as they came
-    bool files_resident_ = false;  // layout_and_upload: the files are in d_input_ already (staged by upload_files)
     IngestStats ingest_;
     jpgpu_device_ingest_stats device_ingest_ = {};
     hipEvent_t gather_ev_[2] = {};  // around the gather of a device upload (device_ingest_.gather_ms)

@@ -105,6 +105,7 @@ size_t same_tables_run(const std::vector<DevScan> &scans, size_t i, size_t n, Sc
 // work list while it grows.  (What the launches and the results read afterwards is a member of DeviceBatch.)
 struct DeviceBatch::UploadPlan {
     LayoutSwitches sw;
+    bool files_resident = false;  // the files are in d_input_ already: no input layout, no copy of them (upload_plan)
     uint32_t subseq_shift = 10, idct_tiles_per_wg = (uint32_t)kIdctTilesPerWg, huff_intervals_per_wg = 0;  // choose_batch_shapes
     uint64_t out_off = 0, coef_off = 0, planes_off = 0, real_blocks = 0, flag_words = 0;
     uint32_t ends_off = 0, total_chunks = 0;
@@ -122,16 +123,17 @@ struct DeviceBatch::UploadPlan {
     std::vector<uint32_t> sr_set_scan;  // a scan that stages each distinct set of tables among the DRI = 0 scans
 };
 
-int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr, const std::vector<size_t> &file_len) {
+int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr, const std::vector<size_t> &file_len, bool files_resident) {
     UploadPlan p;
+    p.files_resident = files_resident;
     p.sw = read_layout_switches();
     p.scan_level.assign(jobs_.size(), 0);
     reset_upload_state(p);
     hipError_t e = hipSetDevice(ctx_->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     if (const int rc = order_upload_behind_work(); rc != JPGPU_OK) return rc;
-    // ---- input layout (jpgpu_batch_upload has laid the files out and sent them already: files_resident_)
-    if (!files_resident_) {
+    // ---- input layout (jpgpu_batch_upload has laid the files out and sent them already: files_resident)
+    if (!files_resident) {
         uint64_t in_off = 256;
         for (size_t i = 0; i < images_.size(); i++) {
             images_[i].file_offset = in_off;
@@ -913,7 +915,7 @@ int DeviceBatch::upload_plan(const UploadPlan &p, const std::vector<const uint8_
     if ((e = launch_lut_pool(up, (const DevHuffTable *)d_huff_pool_.ptr, (int)huff_pool_.size(), (uint8_t *)d_lut_pool_.ptr)) != hipSuccess) return hip_fail(e, "lut_pool_kernel");
     if ((e = launch_sr_luts(up, (const DevScan *)d_scans_.ptr, (const uint32_t *)d_sr_set_scan_.ptr, (int)p.sr_set_scan.size(), (const uint8_t *)d_lut_pool_.ptr,
                             (uint8_t *)d_sr_luts_.ptr)) != hipSuccess) return hip_fail(e, "sr_lut_build_kernel");
-    if (!files_resident_) {
+    if (!p.files_resident) {
         // single scan jobs / frames handed over by the decoder mirror: small, copied as they are
         // slack before the first file and after the last one is read by the kernels' wide loads: keep it defined
         if ((e = hipMemsetAsync(d_input_.ptr, 0, 256, up)) != hipSuccess) return hip_fail(e, "hipMemsetAsync");

@@ -126,9 +126,7 @@ int DeviceBatch::replay_failed_progressive() {
     std::vector<size_t> fl(images_.size(), 0);
     for (size_t ii = 0; ii < images_.size(); ii++) fl[ii] = images_[ii].file_len;
     in_replay_ = true;
-    files_resident_ = true;
-    int rc = layout_and_upload(fp, fl);
-    files_resident_ = false;
+    int rc = layout_and_upload(fp, fl, true);
     if (rc == JPGPU_OK) rc = decode();
     if (rc == JPGPU_OK) rc = fetch_status();
     in_replay_ = false;
@@ -145,9 +143,7 @@ int DeviceBatch::restore_after_replay() {
     std::vector<const uint8_t *> fp(images_.size(), nullptr);
     std::vector<size_t> fl(images_.size(), 0);
     for (size_t ii = 0; ii < images_.size(); ii++) fl[ii] = images_[ii].file_len;
-    files_resident_ = true;
-    const int rc = layout_and_upload(fp, fl);  // (resets the replay's flags and the images' replay_skip)
-    files_resident_ = false;
+    const int rc = layout_and_upload(fp, fl, true);  // (resets the replay's flags and the images' replay_skip)
     replay_possible_ = rc == JPGPU_OK && !entropy_only_;
     return rc;
 }

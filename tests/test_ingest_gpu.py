@@ -435,6 +435,11 @@ def _variety():
     return files
 
 
+def _paths(st):
+    """which way the files of an upload were planned: (from their headers, by the full walks, gathered whole on the host for either)"""
+    return st["n_header_only"], st["n_full_walk"], st["n_linearised"]
+
+
 def test_files_handed_over_as_segment_lists_decode_like_contiguous_ones():
     """jpgpu_batch_upload_segments (ref: JpegDecoder.SetInput(ReadOnlySequence<byte>), JpegDecoder.cs:56-62; a multi-segment
     sequence: apps/JpegDecode/MemoryPoolBufferWriter.cs:166-174 with DecodeAction.cs:81-98's 16 KiB reads): every file cut
@@ -442,9 +447,12 @@ def test_files_handed_over_as_segment_lists_decode_like_contiguous_ones():
     whole -- same per-image status and the same samples as the contiguous upload, which equals the checker."""
     files = _variety()
     plain = jl.Batch().upload(files, jl.FMT_INTERLEAVED_U8).decode().sync()
-    for cutter in (lambda d: list(range(16384, len(d), 16384)),
-                   lambda d: [1, 2, 3, 4, 20, 21, len(d) // 3, len(d) // 3 + 1, len(d) - 2, len(d) - 1],
-                   lambda d: []):
+    assert _paths(plain.ingest_stats()) == (7, 5, 0), plain.ingest_stats()
+    # (which path each file takes: 7 planned from their headers, 5 walked fully, the two-byte and the empty file fail in front of either;
+    # cut into segments, big_head is gathered whole on the host because its first scan starts behind the 64 KiB head)
+    for cutter, paths in ((lambda d: list(range(16384, len(d), 16384)), (7, 5, 1)),
+                          (lambda d: [1, 2, 3, 4, 20, 21, len(d) // 3, len(d) // 3 + 1, len(d) - 2, len(d) - 1], (7, 5, 1)),
+                          (lambda d: [], (7, 5, 0))):
         segs = [_split(f, cutter(f)) for f in files]
         segs[1] = segs[1][:1] + [b""] + segs[1][1:]  # an empty segment in the middle of a file
         b = jl.Batch().upload_segments(segs, jl.FMT_INTERLEAVED_U8).decode().sync()
@@ -457,6 +465,7 @@ def test_files_handed_over_as_segment_lists_decode_like_contiguous_ones():
             if ref is not None:
                 assert np.array_equal(b.output(i), ref), i
         assert st["n_pinned_dma"] == 0
+        assert _paths(st) == paths, st
         b.close()
     plain.close()
 
@@ -477,6 +486,7 @@ def test_page_locked_input_goes_to_hbm_without_a_staging_copy():
     b = jl.Batch(ctx).upload_segments(views, jl.FMT_INTERLEAVED_U8, pinned=True).decode().sync()
     st = b.ingest_stats()
     assert st["n_pinned_dma"] == sum(1 for f in files if len(f)), st
+    assert _paths(st) == (7, 5, 0), st
     for i, f in enumerate(files):
         kind, ref = _oracle(f)
         r = b.result(i)
@@ -494,6 +504,7 @@ def test_page_locked_input_goes_to_hbm_without_a_staging_copy():
     b.upload_segments(views, jl.FMT_INTERLEAVED_U8, arena=True).decode().sync()
     st = b.ingest_stats()
     assert 1 <= st["n_pinned_dma"] <= 2, st
+    assert _paths(st) == (7, 5, 0), st
     for i, f in enumerate(files):
         kind, ref = _oracle(f)
         assert NAMES.get(b.result(i).status) == kind, i
@@ -507,6 +518,7 @@ def test_page_locked_input_goes_to_hbm_without_a_staging_copy():
     # the same arena as two segments per file
     segs = [[v[:len(v) // 2], v[len(v) // 2:]] if len(v) > 4 else [v] for v in views]
     b.upload_segments(segs, jl.FMT_INTERLEAVED_U8, pinned=True).decode().sync()
+    assert _paths(b.ingest_stats()) == (7, 5, 1), b.ingest_stats()  # (big_head again: its scan starts behind the gathered head)
     for i, f in enumerate(files):
         kind, ref = _oracle(f)
         assert NAMES.get(b.result(i).status) == kind, i
