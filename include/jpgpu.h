@@ -320,6 +320,41 @@ int jpgpu_batch_idct_work(const jpgpu_batch *b, int32_t *counts, int n);
 /* ... and how many of them belong to scans the planner hands over to K3 as half-line planes (the split form of the class's kernel). */
 int jpgpu_batch_idct_split_work(const jpgpu_batch *b, int32_t *counts, int n);
 
+/* Windows: decode a rectangle of each image.  A window is given in pixels of the frame; the batch decodes image i into an output the size
+ * of its window, and the output stage (K3) transforms and stores only the MCUs the window touches.  The entropy stage decodes the whole
+ * scan: jpgpu_batch_result is field for field what it is without windows, and jpgpu_batch_download_coefficients /
+ * jpgpu_batch_coefficients_device return the whole frame's coefficients.
+ *   Pixels.  For every whole-pixel format (INTERLEAVED_U8, INTERLEAVED_U8_SCALED, RGB_U8, RGBA_U8, RGB_PLANAR_U8 / _F16 / _F32) the window's
+ * output equals, sample for sample, the slice [y : y + height, x : x + width] of what the same upload produces without windows -- images
+ * that fail or end early (unreached samples read zero in both), progressive frames and the partial flush of a failing one, multi-scan
+ * frames and an image that is planned again on its own included.  The affine constants of the float formats apply unchanged.
+ *   Geometry.  jpgpu_image_info.width / height stay the frame's; out_bytes and plane[] describe the window: (H, W, C) formats hold
+ * height * width * C bytes with pitch width; RGB_PLANAR_* three tight planes of width x height samples, plane[c] = {c * width * height *
+ * sizeof(T), width, height, width}.  out_offset stays a multiple of 256.
+ *   jpgpu_batch_set_windows gives the windows of the NEXT upload of this batch (jpgpu_batch_upload, _upload_segments, _upload_device),
+ * image i -> windows[i]; {0, 0, 0, 0} = the whole frame.  They are consumed by that upload, accepted or refused: the one after it decodes
+ * whole frames again unless the call is repeated.  n == 0 (windows may be NULL) withdraws pending windows.  JPGPU_ERR_ARGUMENT for a NULL
+ * batch, n < 0, or NULL windows with n > 0.
+ *   An upload with pending windows returns JPGPU_ERR_ARGUMENT, decided before anything is enqueued and leaving the batch empty
+ * (jpgpu_batch_size = 0), when its n differs from the windows' n, or when its format is not a whole-pixel format (PLANAR_U8, PLANAR_I16
+ * and EXTENDED_U16 have MCU-padded component planes or another geometry); jpgpu_batch_upload_frames with pending windows is refused the
+ * same way.
+ *   A window that does not lie inside the frame (x + width > W or y + height > H), or with exactly one of width and height zero, fails
+ * that image alone: JPGPU_ERR_ARGUMENT / JPGPU_DETAIL_NONE, out_bytes = 0; the other images are not affected.  An image whose headers
+ * fail keeps the status it has without windows.
+ *   The fast layout classes of K3 serve a window whose x is a multiple of the MCU width and whose width satisfies the class's rule for a
+ * frame's width (RGB_U8 and RGB_PLANAR_*); y and height are free.  Any other window takes the generic class.
+ *   Not windowed: jpgpu_decoder_*, jpgpu_decode_scan, jpgpu_progressive_*, jpgpu_multi_*. */
+typedef struct jpgpu_rect {
+    uint32_t x, y, width, height; /* pixels of the frame; {0, 0, 0, 0} = the whole frame */
+} jpgpu_rect;
+size_t jpgpu_sizeof_rect(void);
+int jpgpu_batch_set_windows(jpgpu_batch *b, const jpgpu_rect *windows, int n);
+/* The window image i was planned with ({0, 0, W, H} for a whole frame).  Valid after an upload. */
+int jpgpu_batch_image_window(const jpgpu_batch *b, int i, jpgpu_rect *window);
+/* Sum of n_mcus over every K3 work entry the last upload listed (all classes, all levels; read only, for tests and tools). */
+int jpgpu_batch_idct_listed_mcus(const jpgpu_batch *b, uint64_t *mcus);
+
 /* Coefficient hand-off for multi-scan (progressive, SOF2) images -- BASELINE config 5's "coefficient accumulate then single
  * IDCT pass": the caller's progressive entropy decoder accumulates the coefficient store, the GPU runs what
  * JpegHuffmanProgressiveScanDecoder.Dispose (ScanDecoder/JpegHuffmanProgressiveScanDecoder.cs:421-470: dequantise, IDCT,

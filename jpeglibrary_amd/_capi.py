@@ -104,6 +104,11 @@ class DeviceIngestStats(C.Structure):
 DEVICE_HEAD_PAD = 64  # JPGPU_DEVICE_HEAD_PAD
 
 
+class Rect(C.Structure):
+    """jpgpu_rect: a window in pixels of the frame; {0, 0, 0, 0} = the whole frame"""
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
 class PlanStats(C.Structure):
     _fields_ = [("k2_plain_work", C.c_int32), ("k2_pools", C.c_int32), ("k2_pooled_chunks", C.c_int32), ("huffman_waves", C.c_int32),
                 ("k2s_scans", C.c_int32), ("k2s_plain_work", C.c_int32), ("k2s_pools", C.c_int32), ("k2s_table_sets", C.c_int32),
@@ -172,6 +177,10 @@ SYMBOLS = [
     ("jpgpu_batch_upload", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int]),
     ("jpgpu_batch_upload_segments", C.c_int, [_P, C.POINTER(Segment), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_uint]),
     ("jpgpu_batch_upload_device", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_int]),
+    ("jpgpu_sizeof_rect", C.c_size_t, []),
+    ("jpgpu_batch_set_windows", C.c_int, [_P, C.POINTER(Rect), C.c_int]),
+    ("jpgpu_batch_image_window", C.c_int, [_P, C.c_int, C.POINTER(Rect)]),
+    ("jpgpu_batch_idct_listed_mcus", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("jpgpu_sizeof_device_ingest_stats", C.c_size_t, []),
     ("jpgpu_batch_device_ingest_stats", C.c_int, [_P, C.POINTER(DeviceIngestStats)]),
     ("jpgpu_batch_upload_frames", C.c_int, [_P, C.POINTER(Frame), C.c_void_p, C.c_int, C.c_int]),
@@ -320,6 +329,8 @@ def _load():
     if lib.jpgpu_sizeof_device_ingest_stats() != C.sizeof(DeviceIngestStats):
         raise ImportError(f"{LIB_PATH} (jpgpu_device_ingest_stats of {lib.jpgpu_sizeof_device_ingest_stats()} bytes) does not match this "
                           f"binding ({C.sizeof(DeviceIngestStats)} bytes): rebuild it")
+    if lib.jpgpu_sizeof_rect() != C.sizeof(Rect):
+        raise ImportError(f"{LIB_PATH} (jpgpu_rect of {lib.jpgpu_sizeof_rect()} bytes) does not match this binding ({C.sizeof(Rect)} bytes): rebuild it")
     if lib.jpgpu_sizeof_progressive_plan() != C.sizeof(ProgressivePlan):
         raise ImportError(f"{LIB_PATH} (jpgpu_progressive_plan of {lib.jpgpu_sizeof_progressive_plan()} bytes) does not match this "
                           f"binding ({C.sizeof(ProgressivePlan)} bytes): rebuild it")

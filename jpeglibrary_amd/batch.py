@@ -92,6 +92,27 @@ def _all_tensors(files):
     return kinds == {True}
 
 
+def _window_rects(rects, n_files=None):
+    """The checks of Batch.set_windows / decode_batch(windows=...), before any library call: [(x, y, w, h)] of four non-negative integers
+    below 2^32 each, one per file ((0, 0, 0, 0) = the whole frame); n_files: the count they must match.  None -> None."""
+    import numbers
+
+    if rects is None:
+        return None
+    out = []
+    for i, r in enumerate(rects):
+        try:
+            vals = tuple(r)
+        except TypeError:
+            raise ValueError("window %d: (x, y, w, h) is expected, not %s" % (i, type(r).__name__)) from None
+        if len(vals) != 4 or not all(isinstance(v, numbers.Integral) and not isinstance(v, bool) and 0 <= v < 2 ** 32 for v in vals):
+            raise ValueError("window %d: (x, y, w, h) are four non-negative integers below 2^32, not %r" % (i, r))
+        out.append(tuple(int(v) for v in vals))
+    if n_files is not None and len(out) != n_files:
+        raise ValueError("%d windows for %d files: one per file ((0, 0, 0, 0) = the whole frame)" % (len(out), n_files))
+    return out
+
+
 def _upload_any(batch, files, fmt):
     """decode_batch / decode_to_tensors: upload() for bytes-like files, upload_tensors() for a list of torch tensors"""
     files = list(files)
@@ -186,6 +207,24 @@ class Batch:
         self.format = fmt
         return self
 
+    def set_windows(self, rects):
+        """The windows of the NEXT upload(), upload_segments() or upload_tensors(): an iterable of (x, y, w, h) in pixels of the frame, one per
+        file ((0, 0, 0, 0) = the whole frame), or None to withdraw pending ones.  Image i is then decoded into an output of its window's size
+        -- the slice [y : y + h, x : x + w] of the whole decode, sample for sample -- and the output stage transforms only the MCUs the window
+        touches.  Whole-pixel formats only.  The windows are consumed by that upload; the one after it decodes whole frames again.
+        ValueError, before the library is called, for a rect that is not four non-negative integers below 2^32."""
+        rects = _window_rects(rects)
+        n = len(rects) if rects else 0
+        arr = (_capi.Rect * max(1, n))(*[_capi.Rect(*r) for r in (rects or [])])
+        self._check(_lib.jpgpu_batch_set_windows(self._h, arr, n))
+        return self
+
+    def window(self, i):
+        """(x, y, w, h): the window image i was planned with; (0, 0, W, H) for a whole frame"""
+        r = _capi.Rect()
+        raise_for_status(_lib.jpgpu_batch_image_window(self._h, i, C.byref(r)), b"jpgpu_batch_image_window: no such image")
+        return (r.x, r.y, r.width, r.height)
+
     def decode(self):
         self._check(_lib.jpgpu_batch_decode(self._h))
         return self
@@ -247,14 +286,18 @@ class Batch:
     def plan_stats(self):
         """How the last upload() planned the entropy stage (K2's plain list and pools, K2S's final-pass list, pools and table
         sets) and K3: idct_work = work entries per output layout class (generic, YCbCr 1x1, 2x1, 2x2, gray, store of samples),
-        idct_split_work = those of them that belong to scans handed over as half-line planes."""
+        idct_split_work = those of them that belong to scans handed over as half-line planes, idct_listed_mcus = the MCUs all of K3's work
+        entries list (under windows: the MCUs the windows touch)."""
         st = _capi.PlanStats()
         self._check(_lib.jpgpu_batch_plan_stats(self._h, C.byref(st)))
         work = (C.c_int32 * IDCT_LAYOUT_CLASSES)()
         self._check(_lib.jpgpu_batch_idct_work(self._h, work, IDCT_LAYOUT_CLASSES))
         split = (C.c_int32 * IDCT_LAYOUT_CLASSES)()
         self._check(_lib.jpgpu_batch_idct_split_work(self._h, split, IDCT_LAYOUT_CLASSES))
-        return dict({k: getattr(st, k) for k, _ in _capi.PlanStats._fields_}, idct_work=list(work), idct_split_work=list(split))
+        listed = C.c_uint64()
+        self._check(_lib.jpgpu_batch_idct_listed_mcus(self._h, C.byref(listed)))
+        return dict({k: getattr(st, k) for k, _ in _capi.PlanStats._fields_}, idct_work=list(work), idct_split_work=list(split),
+                    idct_listed_mcus=listed.value)
 
     def progressive_fallbacks(self):
         """Times the single-launch progressive path timed out and the step was re-issued level by level."""
@@ -308,12 +351,13 @@ class Batch:
         raise_for_status(info.status, _lib.jpgpu_last_error(self.ctx._h))
         raw = np.empty(info.out_bytes, dtype=np.uint8)
         self._check(_lib.jpgpu_batch_download_output(self._h, i, raw.ctypes.data, raw.size))
+        _, _, w, h = self.window(i)  # (the whole frame's W, H without a window)
         if self.format in (FMT_INTERLEAVED_U8, FMT_INTERLEAVED_U8_SCALED):
-            return raw.reshape(info.height, info.width, info.num_components)
+            return raw.reshape(h, w, info.num_components)
         if self.format in (FMT_RGB_U8, FMT_RGBA_U8):
-            return raw.reshape(info.height, info.width, 4 if self.format == FMT_RGBA_U8 else 3)
+            return raw.reshape(h, w, 4 if self.format == FMT_RGBA_U8 else 3)
         if self.format in _RGB_PLANES:  # three tight planes R, G, B
-            return raw.view(_SAMPLE_DTYPES.get(self.format, np.uint8)).reshape(3, info.height, info.width)
+            return raw.view(_SAMPLE_DTYPES.get(self.format, np.uint8)).reshape(3, h, w)
         if self.format == FMT_EXTENDED_U16:  # the reference tests' JpegExtendingOutputWriter buffer: ushort x 4 per pixel
             return raw.view(np.uint16).reshape(info.height, info.width, 4)
         dt = np.int16 if self.format == FMT_PLANAR_I16 else np.uint8
@@ -324,13 +368,15 @@ class Batch:
             planes.append(raw[p.offset:p.offset + nbytes].view(dt).reshape(p.height, p.pitch)[:, :p.width])
         return planes
 
-    def _tensor_shape(self, info):
+    def _tensor_shape(self, info, hw=None):
+        """hw: the (h, w) of the image's window (Batch.window); the frame's without one"""
+        h, w = hw if hw is not None else (info.height, info.width)
         if self.format in (FMT_INTERLEAVED_U8, FMT_INTERLEAVED_U8_SCALED):
-            return (info.height, info.width, info.num_components)
+            return (h, w, info.num_components)
         if self.format in (FMT_RGB_U8, FMT_RGBA_U8):
-            return (info.height, info.width, 4 if self.format == FMT_RGBA_U8 else 3)
+            return (h, w, 4 if self.format == FMT_RGBA_U8 else 3)
         if self.format in _RGB_PLANES:
-            return (3, info.height, info.width)
+            return (3, h, w)
         raise ValueError("output_tensor: format %d is not one dense uint8 array per image (MCU-padded planes, or uint16 pixels); use output()" % self.format)
 
     def output_tensor(self, i):
@@ -344,7 +390,8 @@ class Batch:
 
         info = self.image_info(i)
         raise_for_status(info.status, _lib.jpgpu_last_error(self.ctx._h))
-        shape = self._tensor_shape(info)
+        win = self.window(i)
+        shape = self._tensor_shape(info, (win[3], win[2]))
         if not getattr(self, "_owned", True):
             raise ValueError("output_tensor: a borrowed batch (a MultiDecoder shard) is recycled by its owner; use output()")
         self.sync()
@@ -389,9 +436,15 @@ class Batch:
             pass
 
 
-def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None):
-    """One-call helper: returns (outputs, results).  files: bytes-like objects, or 1-D uint8 torch tensors on the context's device."""
-    b = _upload_any(Batch(ctx), files, fmt).decode().sync()
+def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None):
+    """One-call helper: returns (outputs, results).  files: bytes-like objects, or 1-D uint8 torch tensors on the context's device.
+    windows: one (x, y, w, h) per file (Batch.set_windows): outputs[i] is that rectangle of image i."""
+    files = list(files)
+    windows = _window_rects(windows, len(files))
+    b = Batch(ctx)
+    if windows is not None:
+        b.set_windows(windows)
+    b = _upload_any(b, files, fmt).decode().sync()
     outs, results = [], []
     for i in range(len(b)):
         r = b.result(i)
@@ -401,14 +454,17 @@ def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None):
     return outs, results
 
 
-def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None):
+def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None):
     """One-call helper for torch consumers: returns (tensors, results), tensors[i] = Batch.output_tensor(i) -- uint8[3, H, W] on the
     context's device by default -- or None for an image that failed.  Nothing is downloaded.  The batch is not closed: its output
     buffer is the tensors' memory and is freed with the last of them.  files: bytes-like objects, or 1-D uint8 torch tensors on the
     context's device (Batch.upload_tensors: e.g. EncodeBatch.output_tensor(i) -- the streams never leave the device).
     dtype=torch.float16 / torch.float32 selects RGB_PLANAR_F16 / _F32: float [3, H, W] tensors written by the decoder's output stage itself.
     mean / std (per channel, 0..1 units; both or neither) then make them (u / 255 - mean) / std through affine_from_mean_std; without them
-    a sample is the byte as a float."""
+    a sample is the byte as a float.
+    windows: one (x, y, w, h) per file (Batch.set_windows): tensors[i] is [3, h, w], that rectangle of image i, decoded without the rest."""
+    files = list(files)
+    windows = _window_rects(windows, len(files))
     if dtype is not None:
         import torch
 
@@ -425,6 +481,8 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     b = Batch(ctx)
     if mean is not None:
         b.set_output_affine(*affine_from_mean_std(mean, std))
+    if windows is not None:
+        b.set_windows(windows)
     b = _upload_any(b, files, fmt).decode().sync()
     tensors, results = [], []
     for i in range(len(b)):

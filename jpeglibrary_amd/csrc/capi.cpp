@@ -395,6 +395,15 @@ int jpgpu_batch_upload_segments(jpgpu_batch *b, const jpgpu_segment *segments, c
 int jpgpu_batch_upload_device(jpgpu_batch *b, const void *const *device_jpeg, const size_t *len, int n, int format) {
     JPGPU_GUARD(b, b->impl.upload_device(device_jpeg, len, n, format));
 }
+size_t jpgpu_sizeof_rect(void) { return sizeof(jpgpu_rect); }
+static_assert(sizeof(jpgpu_rect) == 16, "jpgpu_rect: four uint32_t");
+int jpgpu_batch_set_windows(jpgpu_batch *b, const jpgpu_rect *windows, int n) { JPGPU_GUARD(b, b->impl.set_windows(windows, n)); }
+int jpgpu_batch_image_window(const jpgpu_batch *b, int i, jpgpu_rect *window) { return b ? b->impl.image_window(i, window) : JPGPU_ERR_ARGUMENT; }
+int jpgpu_batch_idct_listed_mcus(const jpgpu_batch *b, uint64_t *mcus) {
+    if (!b || !mcus) return JPGPU_ERR_ARGUMENT;
+    *mcus = b->impl.idct_listed_mcus();
+    return JPGPU_OK;
+}
 size_t jpgpu_sizeof_device_ingest_stats(void) { return sizeof(jpgpu_device_ingest_stats); }
 int jpgpu_batch_device_ingest_stats(const jpgpu_batch *b, jpgpu_device_ingest_stats *stats) {
     if (!b || !stats) return JPGPU_ERR_ARGUMENT;

@@ -124,6 +124,13 @@ struct alignas(16) DevScan {
     uint32_t first_scan;       // sequential scans: the image's first scan job (K3: a scan behind a failed one was never started)
     uint32_t sr_set;           // DRI = 0 scans: index of the scan's set of round-kernel lookups (built once per upload: sr_lut_build_kernel)
     uint32_t pad2;
+    // The image's window (jpgpu_batch_set_windows), in pixels of the frame; {0, 0, width, height} for a whole frame.  Only K3's window
+    // instantiations read it: they store sample (x, y) of the frame at (x - win_x, y - win_y) of an image of pitch win_w, where
+    // x - win_x < win_w and y - win_y < win_h (unsigned).  cov_*: the MCUs those instantiations walk, as a raster of cov_cols x cov_rows
+    // MCUs of its own whose MCU (cx, cy) is MCU (cov_x + cx, cov_y + cy) of the scan (IdctWork counts in that raster).  It is the MCUs
+    // the window touches, or the whole scan where MCUs and pixels do not correspond that simply (plan_idct_work).
+    uint16_t win_x, win_y, win_w, win_h;
+    uint16_t cov_x, cov_y, cov_cols, cov_rows;
 };
 constexpr uint32_t kNoDep = 0xFFFFFFFFu;
 // Sequential scans: DevScanStatus::pad[1] = kFailBlockBase - (index, in scan order, of the block the reference threw in), 0 = the

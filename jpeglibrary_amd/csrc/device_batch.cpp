@@ -111,6 +111,8 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
             img.out_bytes = (uint64_t)img.width * img.height * 4 * sizeof(uint16_t);
         }
     }
+    img.windowed = false;  // (a window is applied behind the plans, DeviceBatch::apply_window)
+    img.win = jpgpu_rect{0, 0, img.width, img.height};
     // A frame header is two 16-bit sizes and a component count: a corrupted one can ask for hundreds of gigabytes (the
     // reference's caller would fail allocating the writer's buffer).  Such an image fails BY ITSELF instead of taking the
     // batch's allocation, and every other image, with it (tools/stress_parity.py STRESS_HEADER=1, seed 460).
@@ -301,6 +303,13 @@ int DeviceBatch::upload_progressive_dispose(const ProgressiveFrame &frame, int f
 int DeviceBatch::upload_frames(const jpgpu_frame *frames, const uint16_t *qt, int n, int format) {
     whole_files_ = false;
     device_ingest_ = jpgpu_device_ingest_stats();
+    if (windows_pending_) {  // (windows are for uploads of whole files: consumed and refused, the batch left empty)
+        pending_windows_.clear();
+        windows_pending_ = replay_possible_ = false;
+        forget_batch();
+        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_frames: windows are pending (jpgpu_batch_set_windows), and frames take none");
+    }
+    windows_.clear();
     if (n < 0 || (n > 0 && (!frames || !qt))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_frames: null argument");
     if (format < 0 || format >= kNumOutputFormats) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_frames: unknown format");
     format_ = format;

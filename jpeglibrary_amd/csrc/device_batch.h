@@ -102,6 +102,10 @@ struct ImagePlan {
     std::vector<int> jobs;     // indices into DeviceBatch::jobs_
     uint64_t file_offset = 0;  // position of the file inside the device input buffer
     size_t file_len = 0;
+    // the window the image is decoded through (jpgpu_batch_set_windows): out_bytes and plane[] describe it, width / height stay the frame's.
+    // windowed = false: the whole frame (win = {0, 0, width, height}), planned and decoded exactly as without windows
+    bool windowed = false;
+    jpgpu_rect win = {0, 0, 0, 0};
 };
 
 class WorkCrew;
@@ -131,6 +135,10 @@ class DeviceBatch {
     // on the device; the host sees their heads, and whole only the files that need the full marker walks.
     int upload_device(const void *const *device_jpeg, const size_t *len, int n, int format);
     const jpgpu_device_ingest_stats &device_ingest_stats() const { return device_ingest_; }
+    // The windows of the NEXT upload of whole files (jpgpu_batch_set_windows): consumed by it, accepted or refused.
+    int set_windows(const jpgpu_rect *windows, int n);
+    int image_window(int i, jpgpu_rect *window) const;
+    uint64_t idct_listed_mcus() const { return idct_listed_mcus_; }
     // One progressive frame collected by the JpegDecoder mirror: its entropy scans + the Dispose() pass.
     int upload_progressive_frame(const ProgressiveFrame &frame, const uint8_t *file, size_t file_len, int sof, int format);
     // The per-scan boundary (jpgpu_progressive_*): ONE entropy scan of the frame (index into frame.scans()) accumulating into
@@ -229,6 +237,8 @@ class DeviceBatch {
     void plan_file_full(const uint8_t *file, size_t len, int index, FilePlan &fp) const;
     void plan_swallowed_terminator(FilePlan &fp, const uint8_t *file, size_t len, bool identify_is_clean) const;
     int begin_ingest(int n, int format);
+    int take_windows(int n, int format, const char *what);  // pending windows -> this upload's, or the whole call's refusal
+    void apply_window(size_t i);                            // image i of merge_plans: its window's verdict and geometry
     void forget_batch();  // no images, no jobs
     int ingest_files(std::vector<FileSegs> &files, unsigned flags, std::chrono::steady_clock::time_point t_begin);
     // its stages, in the order they run (a device source stages in front of plan_heads); IngestRun is what one stage hands the next
@@ -306,6 +316,13 @@ class DeviceBatch {
     uint32_t split_max_blocks_ = 0;
     uint64_t coef_store_blocks_ = 0;  // the coefficient buffer's blocks: total_blocks_ + the padding of split scans
     int idct_split_begin_class_[kNumIdctLayoutClasses] = {};  // d_idct_work_: where the split scans' entries of each class begin
+    // The work of windowed images is listed apart (launch_idct_window): d_idct_work_ behind the whole-frame classes, class by class; and every
+    // ordered launch [idct_later_begin_[k], [k + 1]) is of one kind, idct_later_win_[k] saying which.
+    int idct_win_class_begin_[kNumIdctLayoutClasses + 1] = {};
+    std::vector<uint8_t> idct_later_win_;
+    uint64_t idct_listed_mcus_ = 0;
+    bool windows_pending_ = false;
+    std::vector<jpgpu_rect> pending_windows_, windows_;  // set_windows' / the running upload's (empty: whole frames)
     bool dense_valid_ = false, dense_override_ = false;
     DevBuffer d_dense_, d_split_ids_;
     int dense_coefs(const int16_t **ptr);

@@ -380,8 +380,75 @@ int default_host_threads() {
     return std::min(16, granted_host_cpus());  // a handful of threads already keep the host link busy (profiles/r02_ingest_sweep.jsonl)
 }
 
+// jpgpu_batch_set_windows: the windows of the next upload of whole files
+int DeviceBatch::set_windows(const jpgpu_rect *windows, int n) {
+    if (n < 0 || (n > 0 && !windows)) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_set_windows: bad argument");
+    pending_windows_.assign(windows, windows + n);
+    windows_pending_ = n > 0;
+    return JPGPU_OK;
+}
+
+int DeviceBatch::image_window(int i, jpgpu_rect *window) const {
+    const ImagePlan *img = image(i);
+    if (!img || !window) return JPGPU_ERR_ARGUMENT;
+    *window = img->win;
+    return JPGPU_OK;
+}
+
+// What every upload of whole files starts with: the pending windows become this upload's and nobody else's.  The refusals of the whole
+// call, decided before anything is enqueued; they leave the batch empty.
+int DeviceBatch::take_windows(int n, int format, const char *what) {
+    windows_.clear();
+    if (!windows_pending_) return JPGPU_OK;
+    windows_.swap(pending_windows_);
+    windows_pending_ = false;
+    const char *why = nullptr;
+    if ((int)windows_.size() != n) why = ": the upload's n differs from the windows' n (jpgpu_batch_set_windows)";
+    else if (format < 0 || format >= kNumOutputFormats || !fmt_is_interleaved(format))
+        why = ": windows (jpgpu_batch_set_windows) need a whole-pixel format; PLANAR_U8, PLANAR_I16 and EXTENDED_U16 have none";
+    if (!why) return JPGPU_OK;
+    windows_.clear();
+    forget_batch();
+    whole_files_ = replay_possible_ = false;
+    return fail(JPGPU_ERR_ARGUMENT, std::string(what) + why);
+}
+
+// Image i behind its plan: the verdict on its window, and the window's geometry in place of the frame's.  A window that is the whole frame
+// is no window.  An image that failed keeps its status.
+void DeviceBatch::apply_window(size_t i) {
+    ImagePlan &img = images_[i];
+    if (windows_.empty() || img.status != JPGPU_OK) return;
+    const jpgpu_rect w = windows_[i];
+    if (w.x == 0 && w.y == 0 && w.width == 0 && w.height == 0) return;
+    const bool inside = (uint64_t)w.x + w.width <= img.width && (uint64_t)w.y + w.height <= img.height;
+    if (!inside || w.width == 0 || w.height == 0) {  // (outside the frame, or no pixels: this image alone fails)
+        img.status = JPGPU_ERR_ARGUMENT;
+        img.detail = kDetailNone;
+        img.error = "The window {" + std::to_string(w.x) + ", " + std::to_string(w.y) + ", " + std::to_string(w.width) + ", " + std::to_string(w.height) +
+                    "} does not lie inside the " + std::to_string(img.width) + " x " + std::to_string(img.height) + " frame, or is empty.";
+        img.out_bytes = 0;
+        memset(img.plane, 0, sizeof img.plane);
+        return;
+    }
+    if (w.x == 0 && w.y == 0 && w.width == img.width && w.height == img.height) return;
+    img.windowed = true;
+    img.win = w;
+    const uint64_t pixels = (uint64_t)w.width * w.height;
+    if (fmt_is_sample_bytes(format_)) {
+        img.out_bytes = pixels * img.num_components;
+    } else {  // (the RGB formats: take_windows admits nothing else)
+        img.out_bytes = pixels * (format_ == JPGPU_FMT_RGBA_U8 ? 4 : 3) * fmt_rgb_plane_sample_bytes(format_);
+        if (fmt_is_rgb_planes(format_))
+            for (int c = 0; c < 3; c++) img.plane[c] = jpgpu_plane_info{(uint64_t)c * pixels * fmt_rgb_plane_sample_bytes(format_), w.width, w.height, w.width};
+    }
+}
+
 int DeviceBatch::upload_files(const uint8_t *const *jpeg, const size_t *len, int n, int format) {
-    if (n < 0 || (n > 0 && (!jpeg || !len))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload: null argument");
+    if (n < 0 || (n > 0 && (!jpeg || !len))) {
+        pending_windows_.clear();  // (consumed by this upload, refused as it is)
+        windows_pending_ = false;
+        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload: null argument");
+    }
     std::vector<jpgpu_segment> segs((size_t)n);
     std::vector<int> per((size_t)n, 1);
     for (int i = 0; i < n; i++) segs[(size_t)i] = {jpeg[i], len[i]};
@@ -389,6 +456,7 @@ int DeviceBatch::upload_files(const uint8_t *const *jpeg, const size_t *len, int
 }
 
 int DeviceBatch::upload_segments(const jpgpu_segment *segments, const int *segments_per_file, int n, int format, unsigned flags) {
+    if (const int wrc = take_windows(n, format, "jpgpu_batch_upload"); wrc != JPGPU_OK) return wrc;
     if (n < 0 || (n > 0 && (!segments || !segments_per_file))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload: null argument");
     if (format < 0 || format >= kNumOutputFormats) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload: unknown format");
     if (flags & ~(JPGPU_UPLOAD_PINNED | JPGPU_UPLOAD_PINNED_ARENA)) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_segments: unknown flag");
@@ -442,6 +510,10 @@ void DeviceBatch::forget_batch() {
 // jpgpu_batch_upload for whole files that lie in device memory of the context's device (include/jpgpu.h, 1b).
 int DeviceBatch::upload_device(const void *const *device_jpeg, const size_t *len, int n, int format) {
     const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    if (const int wrc = take_windows(n, format, "jpgpu_batch_upload_device"); wrc != JPGPU_OK) {
+        device_ingest_ = jpgpu_device_ingest_stats();
+        return wrc;
+    }
     auto refuse = [&](const std::string &why) {
         forget_batch();
         whole_files_ = replay_possible_ = false;
@@ -1000,6 +1072,7 @@ void DeviceBatch::merge_plans(IngestRun &r) {
         img.file_len = f.len;
         img.file_offset = f.slot;
         img.jobs.clear();
+        apply_window((size_t)i);
         if (img.status != JPGPU_OK) continue;
         for (size_t j = 0; j < fp.jobs.size(); j++) {
             img.jobs.push_back((int)(first_job + j));

@@ -260,11 +260,23 @@ int DeviceBatch::run_idct() {
                                extended ? (uint8_t *)d_planes_.ptr : (uint8_t *)d_out_.ptr, extended ? (int)JPGPU_FMT_PLANAR_I16 : format_, kf,
                                (uint8_t *)d_rgb_scratch_.ptr, split_scans_.empty() || dense_override_ ? nullptr : idct_split_begin_class_, output_affine_);
     if (e != hipSuccess) return hip_fail(e, "idct_output_kernel");
+    // the work of windowed images: the window forms of the same kernels
+    e = launch_idct_window(ctx_->stream, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const IdctWork *)d_idct_work_.ptr, idct_win_class_begin_,
+                           (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr, (uint8_t *)d_out_.ptr, format_, kf,
+                           (uint8_t *)d_rgb_scratch_.ptr, output_affine_);
+    if (e != hipSuccess) return hip_fail(e, "idct_window_kernel");
     // scans ordered behind earlier scans of their image (and the failing MCU of a caller's canvas): one bytewise launch per level
     for (size_t lv = 0; lv + 1 < idct_later_begin_.size(); lv++) {
         int cb[kNumIdctLayoutClasses + 1];
         cb[0] = idct_later_begin_[lv];
         for (int c = 1; c <= kNumIdctLayoutClasses; c++) cb[c] = idct_later_begin_[lv + 1];
+        if (lv < idct_later_win_.size() && idct_later_win_[lv]) {
+            e = launch_idct_window(ctx_->stream, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const IdctWork *)d_idct_work_.ptr, cb,
+                                   (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr, (uint8_t *)d_out_.ptr, format_, kf,
+                                   (uint8_t *)d_rgb_scratch_.ptr, output_affine_);
+            if (e != hipSuccess) return hip_fail(e, "idct_window_kernel (ordered scans)");
+            continue;
+        }
         e = launch_idct(ctx_->stream, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const IdctWork *)d_idct_work_.ptr, cb,
                         (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr,
                         extended ? (uint8_t *)d_planes_.ptr : (uint8_t *)d_out_.ptr, extended ? (int)JPGPU_FMT_PLANAR_I16 : format_, kf,

@@ -117,7 +117,9 @@ struct DeviceBatch::UploadPlan {
     std::vector<IdctWork> idct_work, idct_work_halves;
     std::vector<IdctWork> idct_work_by_class[kNumIdctLayoutClasses];
     std::vector<IdctWork> idct_split_by_class[kNumIdctLayoutClasses];  // scans handed over as half-line planes: the split form of K3
+    std::vector<IdctWork> idct_win_by_class[kNumIdctLayoutClasses];    // scans of windowed images: the window form of K3 (MCUs of the cover)
     std::vector<std::vector<IdctWork>> idct_later_levels;  // scans ordered behind earlier scans of their image: one launch per level
+    std::vector<std::vector<IdctWork>> idct_later_win_levels;  // ... those of windowed images, a launch of their own per level
     std::vector<IdctWork> idct_partial;                     // "the MCU the scan failed in", bytewise (the caller's canvas)
     std::vector<int> scan_level;
     std::vector<uint32_t> sr_set_scan;  // a scan that stages each distinct set of tables among the DRI = 0 scans
@@ -371,6 +373,30 @@ void DeviceBatch::fill_scan(UploadPlan &p, size_t ii, int j, size_t file_len) {
             s.plane_pitch[c] = img.plane[fc].pitch;
         }
     }
+    // the window and the MCUs K3 walks for it (a whole frame: everything; only the window forms of K3 read these).  MCU (mx, my) of a scan
+    // that walks the frame's MCUs holds the pixels [mx * 8 max_h, +8 max_h) x [my * 8 max_v, +8 max_v) and no others: an interleaved
+    // sequential scan (a block lies at (mx * max_h + bx) * 8 and is hs * 8 wide, bx + hs <= max_h), a one-component frame, and the frame
+    // pass of a progressive frame whose sampling factors all divide the maxima (JpegBlockAllocator.Flush places block bx of the MCU at
+    // (mx * h + bx) * hs * 8).  The cover is then the MCUs the window touches; any other scan keeps the whole grid, clipped all the same.
+    s.win_x = (uint16_t)img.win.x;
+    s.win_y = (uint16_t)img.win.y;
+    s.win_w = img.windowed ? (uint16_t)img.win.width : s.width;
+    s.win_h = img.windowed ? (uint16_t)img.win.height : s.height;
+    s.cov_cols = (uint16_t)s.mcus_per_line;
+    s.cov_rows = (uint16_t)s.mcus_per_column;
+    bool mcu_boxes = job.kind != kScanProgressive && g.max_h > 0 && g.max_v > 0 && (job.scan_components > 1 || g.frame.num_components == 1);
+    if (job.kind == kScanFrameOnly)
+        for (int c = 0; c < job.scan_components; c++) mcu_boxes &= job.comp[c].h * job.comp[c].hs == g.max_h && job.comp[c].v * job.comp[c].vs == g.max_v;
+    if (img.windowed && mcu_boxes && img.win.width != 0 && img.win.height != 0) {
+        const uint32_t mw = 8u * (uint32_t)g.max_h, mh = 8u * (uint32_t)g.max_v;
+        const uint32_t c0 = img.win.x / mw, c1 = (img.win.x + img.win.width + mw - 1) / mw, r0 = img.win.y / mh, r1 = (img.win.y + img.win.height + mh - 1) / mh;
+        if (c1 <= s.mcus_per_line && r1 <= s.mcus_per_column) {
+            s.cov_x = (uint16_t)c0;
+            s.cov_y = (uint16_t)r0;
+            s.cov_cols = (uint16_t)(c1 - c0);
+            s.cov_rows = (uint16_t)(r1 - r0);
+        }
+    }
     s.shadow_mask = keep_canvas_ ? kKeepUnreachedMcus : 0;
     for (int c = 0; c < job.scan_components; c++)
         for (int d = c + 1; d < job.scan_components; d++)
@@ -472,7 +498,8 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
     // Half-line planes for the scans K2's interval decoder writes, where the image is this one scan: its region is the
     // image's, and the padding (an even count of whole intervals) goes behind it.  (The scans of a multi-scan image lie back
     // to back in one dense run of the image's blocks, which is what the coefficient readers hand out: they stay dense.)
-    const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_, split_always = p.sw.handoff_set;
+    // (a windowed image's scan is always handed over dense: the split form of K3 would need a window variant of its own)
+    const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed, split_always = p.sw.handoff_set;
     const int k3_class = fmt_is_interleaved(format_) ? idct_layout_class(s) : 0;
     if (split_wanted && job.kind == kScanSequential && s.dri != 0 && img.jobs.size() == 1 && !img.replay_skip && s.total_mcus > 0 &&
         s.blocks_per_mcu != 0 && idct_split_supported(format_, k3_class) &&
@@ -495,7 +522,7 @@ void DeviceBatch::list_rgb_convert(size_t ii) {
     const ImagePlan &img = images_[ii];
     for (const RgbConvert &rc : rgb_convert_)
         if (rc.image == (uint32_t)ii) return;
-    rgb_convert_.push_back({(uint32_t)ii, img.out_offset, (uint64_t)img.width * img.height, img.num_components});
+    rgb_convert_.push_back({(uint32_t)ii, img.out_offset, (uint64_t)img.win.width * img.win.height, img.num_components});  // (the window's pixels)
 }
 
 // K3's work for one scan: tile size and alignment, layout class, scratch conversion, ordering level, work entries, the partial-MCU entry.
@@ -523,7 +550,9 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
             }
     }
     const bool holds_samples = (s.reserved0 & kScanStoreHoldsSamples) != 0;
-    int cls = holds_samples ? kIdctClassStoreHoldsSamples : (fmt_is_interleaved(format_) ? idct_layout_class(s) : 0);
+    // (a windowed image: today's rule with the window's width, and its first column on an MCU boundary -- idct_window_layout_class)
+    int cls = holds_samples ? kIdctClassStoreHoldsSamples
+                            : (fmt_is_interleaved(format_) ? (img.windowed ? idct_window_layout_class(s, format_) : idct_layout_class(s)) : 0);
     // RGB / RGBA of a frame with overlapping scans (below): every scan's samples go to the scratch image in file order and
     // are converted at the end -- a fused conversion of one scan would be overwritten by the scratch image's
     if (!holds_samples && overlapping_scans && rgb_out) cls = 0;
@@ -548,15 +577,24 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
     if (level > 0) {
         s.shadow_mask |= kKeepUnreachedMcus;
         if ((size_t)level > p.idct_later_levels.size()) p.idct_later_levels.resize((size_t)level);
+        if ((size_t)level > p.idct_later_win_levels.size()) p.idct_later_win_levels.resize((size_t)level);
+        if (img.windowed) {  // (any superset of the window's MCUs will do on the later levels: the whole grid, whose numbering is the scan's)
+            s.cov_x = s.cov_y = 0;
+            s.cov_cols = (uint16_t)s.mcus_per_line;
+            s.cov_rows = (uint16_t)s.mcus_per_column;
+        }
         const uint32_t grun = generic_per_wg * p.idct_tiles_per_wg;
+        std::vector<IdctWork> &later = img.windowed ? p.idct_later_win_levels[(size_t)level - 1] : p.idct_later_levels[(size_t)level - 1];
         for (uint32_t first = 0; first < s.total_mcus; first += grun)
-            p.idct_later_levels[(size_t)level - 1].push_back({(uint32_t)j, first, std::min(grun, s.total_mcus - first), generic_per_wg});
+            later.push_back({(uint32_t)j, first, std::min(grun, s.total_mcus - first), generic_per_wg});
         if (rgb_out) list_rgb_convert(ii);  // (bytewise form: samples to the scratch image, then ycc_to_rgb_kernel)
     } else {
         const uint32_t run = mcus_per_wg * p.idct_tiles_per_wg;
-        std::vector<IdctWork> &list = (s.reserved0 & kScanSplitHandoff) ? p.idct_split_by_class[cls] : p.idct_work_by_class[cls];
-        for (uint32_t first = 0; first < s.total_mcus; first += run)
-            list.push_back({(uint32_t)j, first, std::min(run, s.total_mcus - first), mcus_per_wg});
+        std::vector<IdctWork> &list = img.windowed ? p.idct_win_by_class[cls] : (s.reserved0 & kScanSplitHandoff) ? p.idct_split_by_class[cls] : p.idct_work_by_class[cls];
+        // (a windowed image: the MCUs of its cover, counted as a raster of their own; tiles stay full)
+        const uint32_t listed = img.windowed ? (uint32_t)s.cov_cols * s.cov_rows : s.total_mcus;
+        for (uint32_t first = 0; first < listed; first += run)
+            list.push_back({(uint32_t)j, first, std::min(run, listed - first), mcus_per_wg});
         // the caller's canvas under a whole-pixel layout: the MCU a failing scan stops in is written block by block
         if (keep_canvas_ && job.kind == kScanSequential && fmt_is_sample_bytes(format_) &&
             cls >= 1 && cls <= 3)  // (kLayYccH1V1 / H2V1 / H2V2, k3_idct.hip)
@@ -762,7 +800,7 @@ void DeviceBatch::plan_output_clears() {
         // RGB / RGBA = the callers' converter applied to the YCbCr8 buffer (DecodeAction.cs:71-74): an image without any scan
         // leaves that buffer as it was (zero here), and the converter still runs over it
         if (img.jobs.empty() && !img.replay_skip && fmt_is_rgb(format_))
-            rgb_convert_.push_back({(uint32_t)(&img - images_.data()), img.out_offset, (uint64_t)img.width * img.height, img.num_components});
+            rgb_convert_.push_back({(uint32_t)(&img - images_.data()), img.out_offset, (uint64_t)img.win.width * img.win.height, img.num_components});
     }
 }
 
@@ -780,16 +818,31 @@ void DeviceBatch::assemble_idct_lists(UploadPlan &p) {
         idct_work.insert(idct_work.end(), ws.begin(), ws.end());
         idct_class_begin_[c + 1] = (int)idct_work.size();
     }
+    idct_win_class_begin_[0] = (int)idct_work.size();
+    for (int c = 0; c < kNumIdctLayoutClasses; c++) {
+        std::vector<IdctWork> &w = p.idct_win_by_class[c];
+        xcd_interleave(w, p.sw.xcds);
+        idct_work.insert(idct_work.end(), w.begin(), w.end());
+        idct_win_class_begin_[c + 1] = (int)idct_work.size();
+    }
     n_idct_work_ = (int)idct_work.size();
     idct_later_begin_.assign(1, n_idct_work_);
-    for (const std::vector<IdctWork> &w : p.idct_later_levels) {
-        idct_work.insert(idct_work.end(), w.begin(), w.end());
-        idct_later_begin_.push_back((int)idct_work.size());
-    }
+    idct_later_win_.clear();
+    for (size_t lv = 0; lv < std::max(p.idct_later_levels.size(), p.idct_later_win_levels.size()); lv++)
+        for (int win = 0; win < 2; win++) {
+            const std::vector<std::vector<IdctWork>> &levels = win ? p.idct_later_win_levels : p.idct_later_levels;
+            if (lv >= levels.size() || levels[lv].empty()) continue;
+            idct_work.insert(idct_work.end(), levels[lv].begin(), levels[lv].end());
+            idct_later_begin_.push_back((int)idct_work.size());
+            idct_later_win_.push_back((uint8_t)win);
+        }
     if (!p.idct_partial.empty()) {
         idct_work.insert(idct_work.end(), p.idct_partial.begin(), p.idct_partial.end());
         idct_later_begin_.push_back((int)idct_work.size());
+        idct_later_win_.push_back(0);
     }
+    idct_listed_mcus_ = 0;
+    for (const IdctWork &w : idct_work) idct_listed_mcus_ += w.n_mcus;
 }
 
 // ---- two halves for decode()'s overlapped issue order (see decode()): images [0, half_image) and [half_image, n), balanced by
@@ -811,7 +864,8 @@ void DeviceBatch::plan_overlap_halves(UploadPlan &p) {
     while (huff_half_ < n_huff_work_ && h_scans_[p.huff_work[huff_half_].scan].image_index < half_image) huff_half_++;
     // worth it for batches that keep the machine busy for milliseconds: the halves cost four launches and two events
     if (wanted && !entropy_only_ && p.sub_work.empty() && p.prog_work.empty() && total_blocks_ >= (4u << 20) && huff_half_ > 0 &&
-        huff_half_ < n_huff_work_ && rgb_convert_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1) {
+        huff_half_ < n_huff_work_ && rgb_convert_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
+        idct_win_class_begin_[kNumIdctLayoutClasses] == idct_win_class_begin_[0]) {  // (no windowed image: the halves have no list for their work)
         for (int half = 0; half < 2; half++) {
             idct_half_begin_[half][0] = (int)p.idct_work_halves.size();
             for (int c = 0; c < kNumIdctLayoutClasses; c++) {

@@ -252,6 +252,7 @@ int DeviceBatch::redo_swallowed(int i, int job, jpgpu_image_result *res) {
             std::vector<int> forced = forced_swallow_;
             forced.push_back(ordinal);
             sub.set_forced_swallow(forced);
+            if (img.windowed) sub.set_windows(&img.win, 1);  // (the same window: its output replaces the image's)
             const uint8_t *fptr = file.data();
             const size_t flen = file.size();
             int rc = sub.upload_files(&fptr, &flen, 1, format_);
@@ -441,7 +442,8 @@ void DeviceBatch::progressive_plan(jpgpu_progressive_plan *p) const {
 }
 
 void DeviceBatch::idct_work(int32_t counts[kNumIdctLayoutClasses]) const {
-    for (int c = 0; c < kNumIdctLayoutClasses; c++) counts[c] = idct_class_begin_[c + 1] - idct_class_begin_[c];
+    for (int c = 0; c < kNumIdctLayoutClasses; c++)  // (the work of windowed images counts in its class)
+        counts[c] = idct_class_begin_[c + 1] - idct_class_begin_[c] + idct_win_class_begin_[c + 1] - idct_win_class_begin_[c];
 }
 
 void DeviceBatch::idct_split_work(int32_t counts[kNumIdctLayoutClasses]) const {

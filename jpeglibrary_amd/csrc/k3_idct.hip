@@ -495,14 +495,20 @@ __device__ __forceinline__ void quad_exchange(const uint4 &o0, const uint4 &o1, 
 // The fast layouts take the tile's place from wave-uniform state (k3_index_math.h): pos = its first MCU, mpl / line_recip = the MCUs of a
 // line and their reciprocal, row_recip = that of n_mcu, img_h = the frame's lines, img = the image in the output buffer.  Nothing in their
 // task loop divides.
-template <int LAY, int CONV>
+// WIN: the image is a window of the frame (DevScan::win_*).  The generic layout gets the MCU's place in the frame and stores at (x - win_x,
+// y - win_y), clipped to the window by unsigned compares.  The fast layouts get the tile's place in the window's MCU cover instead: pos / mpl /
+// line_recip are the cover's (its first MCU column starts at the window's first pixel column, and the window is whole MCUs wide:
+// idct_window_layout_class, so the pitch mpl * 8 * max_h is the window's), img_h = the window's lines, and win_yoff = the lines of the cover's
+// first MCU row above the window; a row outside the window's lines is dropped.
+template <int LAY, int CONV, bool WIN = false>
 __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_px, const DevScan &s, const K3TilePos &pos, uint32_t mpl,
                                                              uint32_t line_recip, uint32_t row_recip, uint32_t img_h, uint32_t n_mcu,
                                                              uint32_t tid, bool have_block, const DevScanComponent &comp, uint32_t mcu_x,
                                                              uint32_t mcu_y, uint32_t b, uint8_t *img, const YccRgbFactors &kf, bool reached,
-                                                             uint32_t mcu, uint32_t fail_block, const OutputAffine &aff) {
+                                                             uint32_t mcu, uint32_t fail_block, const OutputAffine &aff, uint32_t win_yoff = 0) {
     if (LAY == kLayGeneric) {
-        const uint32_t W = s.width, H = s.height, C = s.frame_components;
+        const uint32_t W = WIN ? s.win_w : s.width, H = WIN ? s.win_h : s.height, C = s.frame_components;
+        const uint32_t wx = WIN ? s.win_x : 0u, wy = WIN ? s.win_y : 0u;
         // any component count / sampling: bytewise stores with WriteBlockSlow's replication
         // (ref: ScanDecoder/JpegHuffmanBaselineScanDecoder.cs:238-268) and the sink's clipping (x < W, y < H)
         if (have_block) {
@@ -524,7 +530,7 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
             if ((overlap_h || overlap_v) && !reached) return;
             for (uint32_t v = 0; v < vs; v++)
                 for (uint32_t i = 0; i < 8; i++) {
-                    const uint32_t y = y0 + 8 * v + i;
+                    const uint32_t y = y0 + 8 * v + i - wy;  // (WIN: above the window wraps to a large value)
                     if (y >= H) continue;
                     const uint8_t *srow = sh_px + ((8 * v + i) >> vshift) * kPxRowStride + tid * 8;
                     for (uint32_t h = 0; h < hs; h++) {
@@ -538,7 +544,7 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
                             if (later != 0xFFFFFFFFu && (uint64_t)mcu * s.blocks_per_mcu + later < fail_block) continue;
                         }
                         for (uint32_t j = 0; j < 8; j++) {
-                            const uint32_t x = x0 + 8 * h + j;
+                            const uint32_t x = x0 + 8 * h + j - wx;
                             if (x < W) img[((size_t)y * W + x) * C + comp.component_index] = srow[(8 * h + j) >> hshift];
                         }
                     }
@@ -560,6 +566,7 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
     // wave-uniform: the first pixel line of the tile's first MCU line; a lane adds a 32-bit offset (a tile spans few lines, or short ones)
     const uint32_t y0 = pos.gy0 * rows_per_mcu;
     uint8_t *line0 = img + (uint64_t)y0 * W * bpp;
+    if (WIN) line0 -= (uint64_t)win_yoff * W * bpp;  // (the cover's first MCU row may begin above the window: such rows are dropped below)
     // RGB_PLANAR_U8: the same line in the G and B planes.  A plane is W * H bytes, which can pass 2^32: wave-uniform 64-bit bases like line0,
     // and the lane's 32-bit offset `at` serves all three.  (W is a multiple of the store width and so is every plane: idct_layout_class.)
     // RGB_PLANAR_F16 / _F32: a plane is W * H * 2 / 4 bytes and a lane stores 16-byte pieces.  The fast classes have W a whole number of MCUs
@@ -582,7 +589,7 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
         asm("" : "+v"(back));  // (kept a 24-bit product: folded into the subtraction it becomes a full 32-bit multiply-add by -mpl)
         const uint32_t gx = x - back;
         const uint32_t yl = wraps * rows_per_mcu + row;  // pixel line below line0
-        if (y0 + yl >= img_h) continue;
+        if (y0 + yl - win_yoff >= img_h) continue;  // (WIN: a line above the window wraps to a large value)
         const uint32_t mb = k3_mul24(m, kbpm);
         const uint8_t *yrow = sh_px + (row & 7) * kPxRowStride + (mb + (row >> 3) * max_h) * 8;
         const uint8_t *crow = sh_px + (row >> vshift) * kPxRowStride + (mb + max_h * max_v) * 8;
@@ -735,7 +742,10 @@ typedef const __attribute__((address_space(1))) void jpgpu_gbl_void;
 // to one onto its components, dispose_pass_kernel below): no dequantisation, no transform -- the block goes to the writer as it lies
 // SPLIT: the scans of this launch were handed over as half-line planes (dma_tile below); a kernel name of its own, because the sixteen
 // dense variants have no register to spare for a branch
-template <int FMT, int LAY, bool PRE, bool SPLIT = false>
+// WIN: the scans of this launch belong to images decoded through a window (DevScan::win_*, cov_*): the work entries count MCUs of the
+// window's cover, a raster of cov_cols x cov_rows MCUs of its own; a tile's coefficients are fetched MCU by MCU from the frame's store, the
+// limits of a failing or short scan are compared in the scan's own numbering, and the stores go to the window.  Always dense.
+template <int FMT, int LAY, bool PRE, bool SPLIT = false, bool WIN = false>
 __device__ __forceinline__ void idct_output_body(
     const int16_t *__restrict__ coefs, const DevScan *__restrict__ scans, const IdctWork *__restrict__ work,
     const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf,
@@ -775,11 +785,14 @@ __device__ __forceinline__ void idct_output_body(
     constexpr bool kPerMcuLayout = fmt_is_interleaved(FMT) && (LAY == kLayYccH1V1 || LAY == kLayYccH2V1 || LAY == kLayYccH2V2);
     uint32_t first_mcu = wk.first_mcu;
     uint32_t range_end = wk.first_mcu + wk.n_mcus;
-    if (first_mcu == kIdctPartialMcu) {
+    // (WIN: the ranges below are in the scan's numbering, which is the cover's only where the cover is the whole scan; elsewhere the lanes'
+    // own `reached` decides, as it does for every scan that keeps nothing)
+    const bool win_whole = !WIN || (s.cov_x == 0 && s.cov_y == 0 && s.cov_cols == s.mcus_per_line);
+    if (!WIN && first_mcu == kIdctPartialMcu) {
         if (fail_block == 0xFFFFFFFFu || fail_block % bpm == 0 || fail_block / bpm >= decoded) return;
         first_mcu = fail_block / bpm;
         range_end = first_mcu + 1;
-    } else if (keep) {
+    } else if (keep && win_whole) {
         const uint32_t reach = kPerMcuLayout ? fail_block / bpm : (fail_block == 0xFFFFFFFFu ? fail_block : (fail_block + bpm - 1) / bpm);
         if (range_end > decoded) range_end = decoded;
         if (range_end > reach) range_end = reach;
@@ -807,6 +820,7 @@ __device__ __forceinline__ void idct_output_body(
     // -- lo plane for pieces 0..3, hi plane for pieces 4..7 of a flagged block; the hi pieces of an unflagged block are zeros, fetched
     // from the scan's zero line or written by the lane (dma_tile).  The flag bytes of a tile are fetched two tiles ahead, behind the
     // transform, and arrive under the wait the DMA has anyway (fetched as the byte that holds the block's bit, kept as one bit per block).
+    static_assert(!(WIN && SPLIT), "a windowed image's scans are handed over dense");
     constexpr bool split = SPLIT && !PRE;
     if (split && (s.reserved0 & kScanSplitHandoff) == 0) return;  // (the host lists split scans apart: never taken)
     const uint32_t sp_dri = split ? s.dri : 1u;
@@ -938,8 +952,39 @@ __device__ __forceinline__ void idct_output_body(
                                                  (jpgpu_lds_void *)(sh + ((uint32_t)k * kIdctThreads + wave * 64) * 16), 16, 0, 0);
     };
 
+    // WIN: the tile's MCUs are consecutive in the cover, not in the store: every 16-byte piece is fetched from its own MCU -- MCU q of the
+    // tile at tp (the tile's first MCU in the cover) is MCU (cov_x + column, cov_y + line) of the frame, found without a division
+    // (k3_index_math.h).  Lanes behind the cover's last MCU fetch that MCU's blocks: never outside the scan's region.
+    // (its 16-bit range hidden from the compiler: a division of such small numbers is done in float, with a fused multiply-add the parity
+    // claim's ISA test would count)
+    uint32_t win_mpl_ = WIN ? __builtin_amdgcn_readfirstlane((uint32_t)s.cov_cols) : 0u;
+    if (WIN) asm("" : "+s"(win_mpl_));
+    const uint32_t win_mpl = win_mpl_;
+    const uint32_t win_recip = WIN ? __builtin_amdgcn_readfirstlane(k3_line_recip(win_mpl)) : 0u;
+    auto dma_tile_win = [&](const K3TilePos &tp, uint32_t tile_first) {
+        uint32_t t_ = tid;
+        asm volatile("" : "+v"(t_));
+        const uint32_t piece_off = ((t_ & 7) ^ ((t_ >> 4) & 7)) * 16;
+        const uint32_t last = (uint32_t)s.cov_cols * s.cov_rows - 1 - tile_first;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const uint32_t blk = (uint32_t)k * 32 + (t_ >> 3);
+            uint32_t q = (blk * sp_rb) >> 16;
+            const uint32_t bb = blk - q * bpm;
+            q = q < last ? q : last;
+            const uint32_t cx = tp.gx0 + q, wr = k3_line_wraps(cx, win_mpl, win_recip);
+            const uint32_t mx = s.cov_x + cx - k3_mul24(wr, win_mpl), my = s.cov_y + tp.gy0 + wr;
+            const uint32_t block = (my * s.mcus_per_line + mx) * bpm + bb;  // (a frame has fewer than 2^32 blocks)
+            if (k < 6 || blk < tile_blocks)  // blocks behind the tile's last MCU are not fetched
+                __builtin_amdgcn_global_load_lds((jpgpu_gbl_void *)(coef_bytes + (uint64_t)block * 128 + piece_off),
+                                                 (jpgpu_lds_void *)(sh + ((uint32_t)k * kIdctThreads + wave * 64) * 16), 16, 0, 0);
+        }
+    };
+
     uint32_t hi_next = 0;  // split scans: the flag bits of the tile behind the one in the staging
-    if (split) {
+    if (WIN) {
+        dma_tile_win(k3_tile_pos(first_mcu, win_mpl), first_mcu);
+    } else if (split) {
         // the first two tiles' flags, into the two sets of words (one look-up site for both: once per workgroup, not worth its code twice)
         const uint32_t n_sets = first_mcu + mcus_per_tile < range_end ? 2u : 1u;
 #pragma nounroll
@@ -959,9 +1004,10 @@ __device__ __forceinline__ void idct_output_body(
     }
     // The place of the tile's first MCU in the image and what the output assembly divides by, wave-uniform (k3_index_math.h): one
     // division each per workgroup, none in the tile loop
-    const uint32_t mpl = __builtin_amdgcn_readfirstlane(s.mcus_per_line);
-    const uint32_t line_recip = __builtin_amdgcn_readfirstlane(k3_line_recip(mpl));
-    const uint32_t img_h = __builtin_amdgcn_readfirstlane((uint32_t)s.height);
+    // (WIN: the place in the window's cover, whose lines are cov_cols MCUs long, and the window's lines)
+    const uint32_t mpl = WIN ? win_mpl : __builtin_amdgcn_readfirstlane(s.mcus_per_line);
+    const uint32_t line_recip = WIN ? win_recip : __builtin_amdgcn_readfirstlane(k3_line_recip(mpl));
+    const uint32_t img_h = __builtin_amdgcn_readfirstlane(WIN ? (uint32_t)s.win_h : (uint32_t)s.height);
     uint8_t *const img = out + s.out_off;  // (read here: the waits of the tile loop keep a load inside it from being moved out)
     K3TilePos pos = k3_tile_pos(first_mcu, mpl);
     pos.gx0 = __builtin_amdgcn_readfirstlane(pos.gx0);
@@ -981,7 +1027,7 @@ __device__ __forceinline__ void idct_output_body(
     const uint32_t next_first = tile_first + mcus_per_tile;
     const bool have_next = next_first < range_end;
 
-    const uint32_t mcu = tile_first + mcu_local;
+    uint32_t mcu = tile_first + mcu_local;  // (WIN: in the cover's numbering until the transform is done)
     const bool have_block = tid < n_blk;
     // a scan component whose frame component a LATER scan component also resolves to: the reference writes its blocks first
     // and the later component's over them (WriteBlock by ComponentIndex, :118-134), so only the later ones reach the output
@@ -1014,7 +1060,11 @@ __device__ __forceinline__ void idct_output_body(
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every lane holds its coefficients: the staging can be refilled
-    if (have_next) dma_tile(next_first, sp_i0 + sp_ipt, hi_next);  // in flight during the whole transform below
+    if (WIN) {
+        K3TilePos pos_next = pos;
+        k3_tile_advance(pos_next, pos_step, mpl);
+        if (have_next) dma_tile_win(pos_next, next_first);
+    } else if (have_next) dma_tile(next_first, sp_i0 + sp_ipt, hi_next);  // in flight during the whole transform below
     hi_next = 0;  // (dead from here to the flag bytes behind the transform)
 
     // phase B2: IDCT entirely in registers
@@ -1024,6 +1074,16 @@ __device__ __forceinline__ void idct_output_body(
     const bool sp_ahead = split && next_first + mcus_per_tile < range_end;
     if (sp_ahead) sp_load_flag(next_first + mcus_per_tile, sp_i0 + 2 * sp_ipt, sp_fb, sp_at);
     sp_i0 += sp_ipt;
+    // WIN: the MCU's place in the frame, and with it its number in the scan, which `decoded` and `fail_block` count in
+    uint32_t win_mx = 0, win_my = 0;
+    if (WIN) {
+        uint32_t ml_win = mcu_local;
+        asm volatile("" : "+v"(ml_win));
+        const uint32_t wr = k3_line_wraps(pos.gx0 + ml_win, mpl, line_recip);
+        win_mx = s.cov_x + pos.gx0 + ml_win - k3_mul24(wr, mpl);
+        win_my = s.cov_y + pos.gy0 + wr;
+        mcu = win_my * s.mcus_per_line + win_mx;
+    }
     // (a frame has fewer than 2^32 blocks: 32-bit arithmetic; computed behind the transform, nothing more alive across it)
     const bool reached = mcu < decoded && mcu * bpm + b < fail_block;
     if ((s.shadow_mask & 0xFu) == 0) {
@@ -1065,7 +1125,7 @@ __device__ __forceinline__ void idct_output_body(
     const uint32_t mcu_wraps = k3_line_wraps(pos.gx0 + ml_late, mpl, line_recip);  // (lines below the tile's first MCU line: no division per lane)
     uint32_t mcu_back = k3_mul24(mcu_wraps, mpl);
     asm("" : "+v"(mcu_back));  // (kept a 24-bit product, as in the task loop)
-    const uint32_t mcu_y = pos.gy0 + mcu_wraps, mcu_x = pos.gx0 + ml_late - mcu_back;
+    const uint32_t mcu_y = WIN ? win_my : pos.gy0 + mcu_wraps, mcu_x = WIN ? win_mx : pos.gx0 + ml_late - mcu_back;
     const uint32_t ci = s.blk_comp[b_late < kMaxBlocksPerMcu ? b_late : 0];  // (again: one byte from the L1-resident descriptor)
     const DevScanComponent comp = s.comp[ci];
     // (the split form indexes the block's place with the late copy: an address derived from `b` would be held across the whole tile loop)
@@ -1112,17 +1172,19 @@ __device__ __forceinline__ void idct_output_body(
     if (CONV != 0 && !conv_is_planar(CONV) && LAY == kLayGray) {
         // a single-component image as R = G = B = Y (Cb = Cr = 128 contribute nothing, DecodeAction.cs:57-65)
         if (writes) {
-            const uint32_t x0 = (mcu_x * comp.h + s.blk_x[b_out]) * 8, y0 = (mcu_y * comp.v + s.blk_y[b_out]) * 8;
+            // (WIN: the block's place in the window -- its column is inside, idct_window_layout_class; a line above the window wraps)
+            const uint32_t x0 = (mcu_x * comp.h + s.blk_x[b_out]) * 8 - (WIN ? s.win_x : 0u), y0 = (mcu_y * comp.v + s.blk_y[b_out]) * 8 - (WIN ? s.win_y : 0u);
 #pragma unroll
             for (int r = 0; r < 8; r++) {
-                if (y0 + r >= s.height) continue;
+                if (y0 + r >= (WIN ? s.win_h : s.height)) continue;
                 uint32_t px[8];
 #pragma unroll
                 for (int j = 0; j < 8; j++) px[j] = byte_of(rows[r].x, rows[r].y, j) * 0x010101u;
-                store_rgb_pixels<8, (CONV == 4 ? 4 : 3)>(out + s.out_off + ((size_t)(y0 + r) * s.width + x0) * (CONV == 4 ? 4 : 3), px);
+                store_rgb_pixels<8, (CONV == 4 ? 4 : 3)>(out + s.out_off + ((size_t)(y0 + r) * (WIN ? s.win_w : s.width) + x0) * (CONV == 4 ? 4 : 3), px);
             }
         }
     } else if (FMT == kFmtPlanarU8 || (kSampleBytes && LAY == kLayGray)) {
+        static_assert(!WIN || !(FMT == kFmtPlanarU8 || (kSampleBytes && LAY == kLayGray)), "no window form: such work takes the generic layout");
         // planar u8 (planes padded to whole MCUs), or a single-component interleaved image (same addressing,
         // pitch = W, clipped at the bottom; the host only picks kLayGray when W is a multiple of 8)
         if (writes) {
@@ -1152,6 +1214,11 @@ __device__ __forceinline__ void idct_output_body(
 
     // (tile_mcus clamps at range_end only, so at most the run's LAST tile is short: two reciprocals cover every n_mcu; a tile walk that
     // shortens another tile needs its own)
+    if constexpr (WIN)
+        interleaved_output_from_tile<LAY, CONV, true>(sh_px, s, pos, mpl, line_recip, n_mcu == mcus_per_tile ? row_recip_full : row_recip_last, img_h, n_mcu, tid,
+                                                      writes, comp, mcu_x, mcu_y, b, img, kf, reached, mcu, fail_block, aff,
+                                                      (uint32_t)s.win_y - (uint32_t)s.cov_y * 8u * s.max_v);
+    else
     interleaved_output_from_tile<LAY, CONV>(sh_px, s, pos, mpl, line_recip, n_mcu == mcus_per_tile ? row_recip_full : row_recip_last, img_h, n_mcu, tid,
                                             writes, comp, mcu_x, mcu_y, b, img, kf, reached, mcu, fail_block, aff);
     }  // interleaved
@@ -1235,6 +1302,22 @@ __global__ __launch_bounds__(kIdctThreads, 2) void flush_output_kernel(
     idct_output_body<FMT, kLayGeneric, true>(coefs, scans, work, status, quant_pool, out, kf);
 }
 
+// The window forms (idct_output_body's WIN): kernels of their own, launched for the work of windowed images only, so that whole-frame work
+// pays nothing for the window.  The generic layout of the two sample-byte formats (which is also where the RGB formats' generic class writes
+// its scratch image), the four fast layouts of RGB_U8 and RGB_PLANAR_U8 / _F16 / _F32, and the flush of a store that holds samples.
+template <int FMT, int LAY>
+__global__ __launch_bounds__(kIdctThreads, 3) void idct_window_kernel(
+    const int16_t *__restrict__ coefs, const DevScan *__restrict__ scans, const IdctWork *__restrict__ work,
+    const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf, OutputAffine aff) {
+    idct_output_body<FMT, LAY, false, false, true>(coefs, scans, work, status, quant_pool, out, kf, aff);
+}
+template <int FMT>
+__global__ __launch_bounds__(kIdctThreads, 2) void flush_window_kernel(
+    const int16_t *__restrict__ coefs, const DevScan *__restrict__ scans, const IdctWork *__restrict__ work,
+    const DevScanStatus *__restrict__ status, const DevQuantTable *__restrict__ quant_pool, uint8_t *__restrict__ out, YccRgbFactors kf) {
+    idct_output_body<FMT, kLayGeneric, true, false, true>(coefs, scans, work, status, quant_pool, out, kf);
+}
+
 // The reference's Dispose() as it is written (ScanDecoder/JpegHuffmanProgressiveScanDecoder.cs:421-470): every component SLOT of
 // the scan decoder, as the last scans left it, dequantises + transforms + level-shifts the blocks of its component IN PLACE.  For
 // files in the usual scan order that is one transform per component and K3 does it on the way to the writer.  When the slots
@@ -1287,6 +1370,53 @@ static void launch_idct_one(hipStream_t stream, const int16_t *coefs, const DevS
       if (n_work > n_dense)
         hipLaunchKernelGGL((idct_split_kernel<FMT, LAY>), dim3(n_work - n_dense), dim3(kIdctThreads), 0, stream, coefs, scans, work + n_dense, status,
                            quant_pool, out, kf, aff);
+}
+
+template <int FMT>
+static void launch_window_fast(hipStream_t stream, int c, const int16_t *coefs, const DevScan *scans, const IdctWork *w, int n, const DevScanStatus *status,
+                               const DevQuantTable *quant_pool, uint8_t *out, const YccRgbFactors &kf, const OutputAffine &aff) {
+    switch (c) {
+    case kLayYccH1V1: hipLaunchKernelGGL((idct_window_kernel<FMT, kLayYccH1V1>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf, aff); break;
+    case kLayYccH2V1: hipLaunchKernelGGL((idct_window_kernel<FMT, kLayYccH2V1>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf, aff); break;
+    case kLayYccH2V2: hipLaunchKernelGGL((idct_window_kernel<FMT, kLayYccH2V2>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf, aff); break;
+    default: hipLaunchKernelGGL((idct_window_kernel<FMT, kLayGray>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf, aff); break;
+    }
+}
+
+// The same lists for the work of windowed images (the planner lists it apart, by the class idct_window_layout_class gives; never split).
+hipError_t launch_idct_window(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
+                              const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status, const DevQuantTable *quant_pool, uint8_t *out,
+                              int format, const YccRgbFactors &kf, uint8_t *generic_out, const OutputAffine &aff) {
+    if (!fmt_is_interleaved(format)) return class_begin[kNumIdctLayoutClasses] > class_begin[0] ? hipErrorInvalidValue : hipSuccess;
+    const bool scaled = format == kFmtInterleavedU8Scaled;
+    uint8_t *const bytes_out = fmt_is_rgb(format) ? generic_out : out;  // where sample bytes go: the image itself, or the RGB formats' scratch image
+    for (int c = 0; c < kNumIdctLayoutClasses; c++) {
+        const int n = class_begin[c + 1] - class_begin[c];
+        if (n <= 0) continue;
+        const IdctWork *w = work + class_begin[c];
+        const bool fast = c >= kLayYccH1V1 && c <= kLayGray;
+        if (c == kIdctClassStoreHoldsSamples) {
+            if (scaled) hipLaunchKernelGGL((flush_window_kernel<kFmtInterleavedU8Scaled>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, bytes_out, kf);
+            else hipLaunchKernelGGL((flush_window_kernel<kFmtInterleavedU8>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, bytes_out, kf);
+        } else if (fast && format == kFmtRgbU8) {
+            launch_window_fast<kFmtRgbU8>(stream, c, coefs, scans, w, n, status, quant_pool, out, kf, aff);
+        } else if (fast && format == kFmtRgbPlanarU8) {
+            launch_window_fast<kFmtRgbPlanarU8>(stream, c, coefs, scans, w, n, status, quant_pool, out, kf, aff);
+        } else if (fast && format == kFmtRgbPlanarF16) {
+            launch_window_fast<kFmtRgbPlanarF16>(stream, c, coefs, scans, w, n, status, quant_pool, out, kf, aff);
+        } else if (fast && format == kFmtRgbPlanarF32) {
+            launch_window_fast<kFmtRgbPlanarF32>(stream, c, coefs, scans, w, n, status, quant_pool, out, kf, aff);
+        } else if (c != kLayGeneric) {
+            return hipErrorInvalidValue;  // (the planner gives no such class to a window: a missing kernel is an error)
+        } else if (scaled) {
+            hipLaunchKernelGGL((idct_window_kernel<kFmtInterleavedU8Scaled, kLayGeneric>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, bytes_out, kf, aff);
+        } else {
+            hipLaunchKernelGGL((idct_window_kernel<kFmtInterleavedU8, kLayGeneric>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, bytes_out, kf, aff);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 // work is sorted by layout class; class_begin[c]..class_begin[c+1] are the workgroups of class c, and from split_begin[c] on (where
@@ -1420,6 +1550,19 @@ int idct_layout_class(const DevScan &s) {
         if (s.max_v == 2) return kLayYccH2V2;
     }
     return kLayGeneric;
+}
+
+// Layout class of a scan of a windowed image: today's rule with the window's width in place of the frame's, and the window's first column on
+// an MCU boundary -- so the cover's first MCU column starts at the window's first pixel, the window is whole MCUs wide, and every store address
+// of the fast classes keeps the alignment it has for a whole frame (a line is win_w samples, an image starts on a multiple of 256).  win_y and
+// win_h are free.  The fast classes have a window form for RGB_U8 and RGB_PLANAR_U8 / _F16 / _F32; every other whole-pixel format takes the
+// generic class under a window (RGBA_U8 through the scratch image and the converter).
+int idct_window_layout_class(const DevScan &s, int format) {
+    if (format != kFmtRgbU8 && !fmt_is_rgb_planes(format)) return kLayGeneric;
+    if (s.max_h == 0 || s.win_x % (8u * s.max_h) != 0) return kLayGeneric;
+    DevScan w = s;
+    w.width = s.win_w;
+    return idct_layout_class(w);
 }
 
 }  // namespace jpgpu

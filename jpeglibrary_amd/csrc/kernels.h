@@ -96,6 +96,12 @@ hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *
                        const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status,
                        const DevQuantTable *quant_pool, uint8_t *out, int format, const YccRgbFactors &kf, uint8_t *generic_out,
                        const int *split_begin = nullptr, const OutputAffine &aff = kOutputAffineIdentity);
+// The work of windowed images (DevScan::win_*, cov_*; IdctWork counts MCUs of the window's cover): the same lists by class, the class given by
+// idct_window_layout_class, never split.  Whole-pixel formats only.
+int idct_window_layout_class(const DevScan &s, int format);
+hipError_t launch_idct_window(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
+                              const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status, const DevQuantTable *quant_pool, uint8_t *out,
+                              int format, const YccRgbFactors &kf, uint8_t *generic_out, const OutputAffine &aff = kOutputAffineIdentity);
 // a scan K2 handed over as half-line planes (common.h: kScanSplitHandoff) -> dense int16[blocks][64] at the same offsets of `dense`
 hipError_t launch_expand_handoff(hipStream_t stream, const int16_t *coefs, int16_t *dense, const DevScan *scans, const uint32_t *scan_ids, int n_scans,
                                  uint32_t max_blocks);
