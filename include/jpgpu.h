@@ -384,6 +384,39 @@ int jpgpu_batch_run_idct(jpgpu_batch *b);    /* coefficient buffer -> output */
  * hold from the next jpgpu_batch_decode / jpgpu_batch_run_idct on, without a new upload, until they are set again.  A NULL pointer or a
  * constant that is not finite: JPGPU_ERR_ARGUMENT, and the constants in force stay.  The other formats never read them. */
 int jpgpu_batch_set_output_affine(jpgpu_batch *b, const float scale[3], const float bias[3]);
+/* The resize stage (K4).  While a resize is set, every jpgpu_batch_decode / jpgpu_batch_run_idct of a JPGPU_FMT_RGB_PLANAR_U8 upload is
+ * followed, on the context's stream behind everything the output stage enqueues, by ONE launch that resamples every image (its window, if it
+ * has one) to out_width x out_height and writes one dense buffer T[N][3][out_height][out_width] of sample_format's samples
+ * (JPGPU_FMT_RGB_PLANAR_U8 / _F16 / _F32: uint8, binary16, float32).  The per-image outputs stay what they are.
+ *
+ * The result is a fixed function of the RGB_PLANAR_U8 bytes: separable antialiased bilinear resampling (a triangle filter, widened by the
+ * scale when shrinking).  For an axis of input length I and output length O, in IEEE double:
+ *     scale = I / O;  sup = max(scale, 1.0)
+ *     for o in 0 .. O-1:
+ *         c  = (o + 0.5) * scale
+ *         lo = max(0, (int)(c - sup + 0.5));  hi = min(I, (int)(c + sup + 0.5))        ((int): truncation toward zero)
+ *         w64[k] = max(0.0, 1.0 - fabs((k + lo - c + 0.5) / sup))   for k in 0 .. hi-lo-1
+ *         w[k]   = (float)(w64[k] / sum(w64))                        (the sum in ascending k)
+ * A horizontal pass, then a vertical pass, each  acc = 0.0f; for k ascending: t = w[k] * x; acc = acc + t  with every multiply and add
+ * rounded to float32 on its own, never fused; x is (float)byte in the first pass and the first pass's float32 result in the second.  With v
+ * the second pass's result the sample is  U8: clamp(rint(v), 0, 255), ties to even;  F32: (v * scale[c]) + bias[c] with the constants of
+ * jpgpu_batch_set_output_affine, two roundings;  F16: that value rounded to nearest even to binary16.  At the image's own size every sample
+ * is bit for bit what RGB_PLANAR_U8 / _F16 / _F32 hold.
+ *
+ * Like the constants, the setting is launch state of the batch: it holds from the next decode / run_idct until it is set again;
+ * (0, 0, any format) withdraws it, and with it what an earlier decode left.  JPGPU_ERR_ARGUMENT, the setting in force kept, for a NULL
+ * batch, a negative size, exactly one zero size, a size above 65535 or another format.  With a resize set, a decode / run_idct of an upload
+ * whose format is not RGB_PLANAR_U8 returns JPGPU_ERR_ARGUMENT before anything is enqueued.  An image whose status is not 0 takes no part:
+ * its slab reads as zeros.  Not resized: jpgpu_decoder_*, jpgpu_decode_scan, jpgpu_progressive_*, jpgpu_multi_*. */
+int jpgpu_batch_set_resize(jpgpu_batch *b, int out_width, int out_height, int sample_format);
+/* The resized buffer in device memory (256-byte aligned; image i at i * 3 * out_height * out_width samples), good until the next upload, decode
+ * or withdrawal, and one image's slab copied to the host (waits for the batch's work).  JPGPU_ERR_INVALID_OPERATION when no decode with a
+ * resize set has run on the upload. */
+int jpgpu_batch_resized_device(const jpgpu_batch *b, void **ptr, uint64_t *bytes);
+int jpgpu_batch_download_resized(jpgpu_batch *b, int i, void *dst, uint64_t bytes);
+/* Device time of the last resize launch, from an event pair of its own (synchronises).  jpgpu_batch_stage_ms does not include it: the launch
+ * lies behind the last stage event. */
+int jpgpu_batch_resize_ms(jpgpu_batch *b, float *ms);
 int jpgpu_batch_sync(jpgpu_batch *b);
 
 int jpgpu_batch_size(const jpgpu_batch *b);

@@ -188,6 +188,10 @@ SYMBOLS = [
     ("jpgpu_batch_run_entropy", C.c_int, [_P]),
     ("jpgpu_batch_run_idct", C.c_int, [_P]),
     ("jpgpu_batch_set_output_affine", C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("jpgpu_batch_set_resize", C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    ("jpgpu_batch_resized_device", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    ("jpgpu_batch_download_resized", C.c_int, [_P, C.c_int, C.c_void_p, C.c_uint64]),
+    ("jpgpu_batch_resize_ms", C.c_int, [_P, C.POINTER(C.c_float)]),
     ("jpgpu_batch_sync", C.c_int, [_P]),
     ("jpgpu_batch_size", C.c_int, [_P]),
     ("jpgpu_batch_image_info", C.c_int, [_P, C.c_int, C.POINTER(ImageInfo)]),

@@ -38,6 +38,27 @@ def affine_from_mean_std(mean, std):
     if not (np.all(np.isfinite(mean)) and np.all(np.isfinite(std))) or np.any(std == 0):
         raise ValueError("mean and std must be finite and std non-zero")
     return (1.0 / (255.0 * std)).astype(np.float32), (-mean / std).astype(np.float32)
+
+
+def _resize_setting(size, dtype):
+    """The checks of Batch.set_resize / decode_resized, before any library call: size = (oh, ow), two integers in 1..65535; dtype = torch.uint8,
+    torch.float16 or torch.float32.  -> (oh, ow, format of the samples, numpy dtype)"""
+    import numbers
+
+    import torch  # (here: the package imports without torch)
+
+    by_dtype = {torch.uint8: (FMT_RGB_PLANAR_U8, np.uint8), torch.float16: (FMT_RGB_PLANAR_F16, np.float16), torch.float32: (FMT_RGB_PLANAR_F32, np.float32)}
+    if dtype not in by_dtype:
+        raise ValueError("resize: dtype is torch.uint8, torch.float16 or torch.float32, not %s" % (dtype,))
+    try:
+        vals = tuple(size)
+    except TypeError:
+        raise ValueError("resize: size is (height, width), not %s" % type(size).__name__) from None
+    if len(vals) != 2 or not all(isinstance(v, numbers.Integral) and not isinstance(v, bool) and 1 <= v <= 65535 for v in vals):
+        raise ValueError("resize: size is (height, width), two integers in 1..65535, not %r" % (size,))
+    return (int(vals[0]), int(vals[1])) + by_dtype[dtype]
+
+
 IDCT_LAYOUT_CLASSES = 6  # JPGPU_IDCT_LAYOUT_CLASSES: generic, YCbCr 1x1 / 2x1 / 2x2, gray, store holding samples
 
 
@@ -126,6 +147,7 @@ class Batch:
         raise_for_status(_lib.jpgpu_batch_create(self.ctx._h, C.byref(self._h)), b"jpgpu_batch_create failed")
         self.format = FMT_INTERLEAVED_U8
         self._keep = None
+        self._resize = self._resized_as = None
 
     def _check(self, rc):
         raise_for_status(rc, _lib.jpgpu_last_error(self.ctx._h))
@@ -227,6 +249,7 @@ class Batch:
 
     def decode(self):
         self._check(_lib.jpgpu_batch_decode(self._h))
+        self._resized_as = getattr(self, "_resize", None)
         return self
 
     def run_entropy(self):
@@ -235,7 +258,69 @@ class Batch:
 
     def run_idct(self):
         self._check(_lib.jpgpu_batch_run_idct(self._h))
+        self._resized_as = getattr(self, "_resize", None)
         return self
+
+    def set_resize(self, size, dtype=None):
+        """The resize stage: from the next decode() / run_idct() on, every image of an RGB_PLANAR_U8 upload (its window, if it has one) is also
+        resampled to size = (oh, ow) -- antialiased bilinear, the fixed function include/jpgpu.h states -- into ONE dense [N, 3, oh, ow] buffer of
+        dtype (torch.uint8, the default, torch.float16 or torch.float32; the float samples take the constants of set_output_affine), in one
+        launch behind the output stage.  The per-image outputs stay what they are.  Launch state like the constants: it holds until set again;
+        None withdraws it, and with it what an earlier decode left.  A decode of an upload of another format is refused while it is set.
+        ValueError, before the library is called, for anything that is not such a size or dtype."""
+        if size is None:
+            self._check(_lib.jpgpu_batch_set_resize(self._h, 0, 0, 0))
+            self._resize = self._resized_as = None
+            return self
+        if dtype is None:
+            import torch
+
+            dtype = torch.uint8
+        oh, ow, fmt, np_dtype = _resize_setting(size, dtype)
+        self._check(_lib.jpgpu_batch_set_resize(self._h, ow, oh, fmt))
+        self._resize = (oh, ow, fmt, np_dtype)
+        return self
+
+    def _resized_span(self):
+        """(device pointer, (N, 3, oh, ow), format, numpy dtype) of the resized buffer; raises when no decode with a resize set has run"""
+        ptr, total = C.c_void_p(), C.c_uint64()
+        self._check(_lib.jpgpu_batch_resized_device(self._h, C.byref(ptr), C.byref(total)))
+        made = getattr(self, "_resized_as", None)
+        if made is None:
+            raise ValueError("resized: the resize was not set through this object (Batch.set_resize)")
+        oh, ow, fmt, np_dtype = made
+        shape = (len(self), 3, oh, ow)
+        if total.value != int(np.prod(shape, dtype=np.int64)) * np.dtype(np_dtype).itemsize:
+            raise ValueError("resized: the buffer holds %d bytes, not %s of %s" % (total.value, shape, np.dtype(np_dtype)))
+        return ptr.value, shape, fmt, np_dtype
+
+    def resized(self):
+        """Downloads the resized images: a numpy array [N, 3, oh, ow] of the dtype that was set (an image that failed reads as zeros)."""
+        _, shape, _, np_dtype = self._resized_span()
+        out = np.empty(shape, dtype=np_dtype)
+        for i in range(shape[0]):
+            self._check(_lib.jpgpu_batch_download_resized(self._h, i, out[i].ctypes.data, out[i].nbytes))
+        return out
+
+    def resized_tensor(self):
+        """The resized images as ONE torch tensor [N, 3, oh, ow] on the context's device that ALIASES the batch's resized buffer -- no copy:
+        data_ptr() is jpgpu_batch_resized_device's pointer.  output_tensor's rules: sync() is called first, the tensor keeps the batch alive,
+        a borrowed batch raises, and the next upload(), decode(), set_resize(None) or close() invalidates it."""
+        import torch  # (here: the package imports without torch)
+
+        if not getattr(self, "_owned", True):
+            raise ValueError("resized_tensor: a borrowed batch (a MultiDecoder shard) is recycled by its owner; use resized()")
+        ptr, shape, fmt, _ = self._resized_span()
+        self.sync()
+        if not ptr or 0 in shape:
+            raise ValueError("resized_tensor: the batch has no resized buffer")
+        return torch.as_tensor(_DeviceView(self, ptr, shape, _typestr(fmt)), device=torch.device("cuda", self.ctx.device))
+
+    def resize_ms(self):
+        """Device time (ms) of the last resize launch, from an event pair of its own; stage_ms() does not include it."""
+        ms = C.c_float()
+        self._check(_lib.jpgpu_batch_resize_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def set_output_affine(self, scale, bias):
         """RGB_PLANAR_F16 / _F32: sample = float32(byte) * scale[c] + bias[c] per channel c (R, G, B); the default is scale 1, bias 0.  The
@@ -421,6 +506,7 @@ class Batch:
         self._h = C.c_void_p(handle)
         self.format = fmt
         self._keep = None
+        self._resize = self._resized_as = None
         self._owned = False
         return self
 
@@ -489,3 +575,34 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
         results.append(b.result(i))
         tensors.append(b.output_tensor(i) if b.image_info(i).status == 0 and results[-1].status == 0 else None)
     return tensors, results
+
+
+def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None):
+    """One-call helper for fixed-size consumers: returns (tensor, results), tensor = Batch.resized_tensor() -- ONE [N, 3, oh, ow] tensor on the
+    context's device, size = (oh, ow), dtype torch.float16 (the default), torch.float32 or torch.uint8 -- every image decoded to RGB and
+    resampled to that size (antialiased bilinear) in one launch behind the output stage; the slab of an image that failed is zero and
+    results[i] says why.  Nothing is downloaded, and the batch is not closed: its buffer is the tensor's memory and is freed with it.
+    files: bytes-like objects, or 1-D uint8 torch tensors on the context's device, as in decode_to_tensors.  mean / std (per channel, 0..1
+    units; both or neither) make the float samples (v / 255 - mean) / std through affine_from_mean_std; they are refused for torch.uint8.
+    windows: one (x, y, w, h) per file (Batch.set_windows): that rectangle of image i is what is resampled -- a RandomResizedCrop's crop."""
+    import torch
+
+    files = list(files)
+    windows = _window_rects(windows, len(files))
+    dtype = torch.float16 if dtype is None else dtype
+    _resize_setting(size, dtype)
+    _all_tensors(files)  # (a list that mixes bytes and tensors raises here, before a batch exists)
+    if (mean is None) != (std is None):
+        raise ValueError("decode_resized: mean and std go together")
+    if mean is not None and dtype == torch.uint8:
+        raise ValueError("decode_resized: mean / std apply to float samples; pass dtype=torch.float16 or torch.float32")
+    consts = affine_from_mean_std(mean, std) if mean is not None else None
+    b = Batch(ctx)
+    if consts is not None:
+        b.set_output_affine(*consts)
+    b.set_resize(size, dtype)
+    if windows is not None:
+        b.set_windows(windows)
+    b = _upload_any(b, files, FMT_RGB_PLANAR_U8).decode().sync()
+    results = [b.result(i) for i in range(len(b))]
+    return b.resized_tensor(), results

@@ -16,6 +16,7 @@
 #include "device_encode.h"
 #include "device_optimize.h"
 #include "host.h"
+#include "resize_tables.h"
 
 using namespace jpgpu;
 
@@ -438,6 +439,21 @@ int jpgpu_batch_set_output_affine(jpgpu_batch *b, const float scale[3], const fl
     }
     b->impl.set_output_affine(a);
     return JPGPU_OK;
+}
+int jpgpu_batch_set_resize(jpgpu_batch *b, int out_width, int out_height, int sample_format) { JPGPU_GUARD(b, b->impl.set_resize(out_width, out_height, sample_format)); }
+int jpgpu_batch_resized_device(const jpgpu_batch *b, void **ptr, uint64_t *bytes) { return b ? b->impl.resized_device(ptr, bytes) : JPGPU_ERR_ARGUMENT; }
+int jpgpu_batch_download_resized(jpgpu_batch *b, int i, void *dst, uint64_t bytes) { JPGPU_GUARD(b, b->impl.download_resized(i, dst, bytes)); }
+int jpgpu_batch_resize_ms(jpgpu_batch *b, float *ms) { JPGPU_GUARD(b, b->impl.resize_ms(ms)); }
+// (tests only, not part of include/jpgpu.h: tests/test_resize_model_cpu.py) the tap table of one axis as the host builds it, no device needed:
+// lo[O], count[O], the weights back to back in `weights` (cap_weights floats).  -> the number of weights, or -1 for a bad argument / too small a buffer
+long long jpgpu_debug_resize_table(int in_len, int out_len, int32_t *lo, int32_t *count, float *weights, size_t cap_weights) {
+    if (in_len <= 0 || out_len <= 0 || !lo || !count || !weights) return -1;
+    const ResizeAxis t = resize_axis(in_len, out_len);
+    if (t.w.size() > cap_weights) return -1;
+    std::copy(t.lo.begin(), t.lo.end(), lo);
+    std::copy(t.count.begin(), t.count.end(), count);
+    std::copy(t.w.begin(), t.w.end(), weights);
+    return (long long)t.w.size();
 }
 int jpgpu_batch_sync(jpgpu_batch *b) { JPGPU_GUARD(b, b->impl.sync()); }
 int jpgpu_batch_size(const jpgpu_batch *b) { return b ? b->impl.size() : 0; }

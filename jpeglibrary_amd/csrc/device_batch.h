@@ -1,5 +1,5 @@
 // jpeglibrary_amd/csrc/device_batch.h -- device-resident batch of scan jobs: HBM layout, uploads, kernel launches.  (DeviceBatch is implemented in
-// device_batch.cpp, device_batch_ingest.cpp, device_batch_layout.cpp, device_batch_launch.cpp and device_batch_result.cpp, by role.)
+// device_batch.cpp, device_batch_ingest.cpp, device_batch_layout.cpp, device_batch_launch.cpp, device_batch_result.cpp and device_batch_resize.cpp, by role.)
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -162,7 +162,7 @@ class DeviceBatch {
     int run_marker_index();
     int run_huffman();
     int run_subseq_sync(const uint32_t **final_state, const uint32_t **first_block);  // K2S rounds + prefix sums only
-    int run_idct();
+    int run_idct(bool with_resize = true);  // with_resize = false: decode()'s, which issues K4 behind its last stage event itself
     int run_progressive();     // entropy scans of progressive frames (K2P), ordinal by ordinal
     int decode();  // marker index + the selected pipeline, with stage events
     int sync();    // waits for THIS batch's device work (an event behind its last launch), not for the whole stream
@@ -188,6 +188,14 @@ class DeviceBatch {
     // RGB_PLANAR_F16 / _F32: the constants of the output stage's affine step (common.h: OutputAffine).  Launch state, not part of the plan:
     // they hold from the next decode() / run_idct() on, whatever was uploaded before or is uploaded after.  No other format reads them.
     void set_output_affine(const OutputAffine &a) { output_affine_ = a; }
+    // The resize stage (K4, device_batch_resize.cpp): launch state like the constants above.  While one is set, every decode() / run_idct() of an
+    // RGB_PLANAR_U8 upload is followed by one launch that resamples every image (its window, if it has one) to out_width x out_height samples
+    // of sample_format into one dense [N][3][out_height][out_width] buffer; an upload of another format is refused before anything is enqueued.
+    // (0, 0, any format) withdraws it.
+    int set_resize(int out_width, int out_height, int sample_format);
+    int resized_device(void **ptr, uint64_t *bytes) const;
+    int download_resized(int i, void *dst, uint64_t bytes);
+    int resize_ms(float *ms);
     void note_entropy_only_request() { in_decode_request_ = false; }
     int last_subseq_rounds() const { return last_subseq_rounds_; }
     int progressive_fallbacks() const { return prog_fallbacks_; }
@@ -282,6 +290,19 @@ class DeviceBatch {
     jpgpu_ctx *ctx_;
     int format_ = JPGPU_FMT_INTERLEAVED_U8;
     OutputAffine output_affine_ = kOutputAffineIdentity;
+    // the resize stage: what is set (width 0 = none), the plan made for this upload at that size (descriptors and tap tables, on the device),
+    // and what the last launch left in d_resized_ (resized_fmt_ < 0: nothing; cleared by an upload and by a withdrawal)
+    struct ResizeSetting {
+        int width = 0, height = 0, format = 0;
+    } resize_;
+    int check_resize_format(const char *who);  // a resize is set and the upload is not RGB_PLANAR_U8: ArgumentException, nothing enqueued
+    int run_resize();                          // behind everything K3 has enqueued on the context's stream
+    int plan_resize();
+    bool resize_plan_valid_ = false;
+    int resize_plan_width_ = 0, resize_plan_height_ = 0, n_resize_images_ = 0;
+    int resized_width_ = 0, resized_height_ = 0, resized_fmt_ = -1, resized_images_ = 0;
+    DevBuffer d_resized_, d_resize_images_, d_resize_tables_;
+    hipEvent_t resize_ev_[2] = {};
     std::vector<ImagePlan> images_;
     std::vector<ScanJob> jobs_;
     std::vector<int> job_image_;

@@ -247,7 +247,12 @@ int DeviceBatch::run_dispose_passes(hipStream_t stream) {
     return e == hipSuccess ? JPGPU_OK : hip_fail(e, "dispose_pass_kernel");
 }
 
-int DeviceBatch::run_idct() {
+int DeviceBatch::run_idct(bool with_resize) {
+    if (with_resize && resize_.width != 0) {  // (decode() has done both already)
+        int rr = check_resize_format("jpgpu_batch_run_idct");
+        if (rr == JPGPU_OK) rr = plan_resize();
+        if (rr != JPGPU_OK) return rr;
+    }
     redo_.clear();  // (K3 writes this plan's samples over what a re-plan copied in: result() / download_output() plan again)
     if (k2s_unchecked_) k2s_idct_behind_ = true;
     const YccRgbFactors kf = ycc_rgb_factors();
@@ -333,6 +338,7 @@ int DeviceBatch::run_idct() {
                               output_affine_);
         if (e != hipSuccess) return hip_fail(e, "ycc_to_rgb_kernel");
     }
+    if (with_resize && resize_.width != 0) return run_resize();  // K4, behind everything above
     return mark_work();
 }
 
@@ -351,6 +357,7 @@ int DeviceBatch::run_idct() {
 // serially on one stream with an event between the stages.  jpgpu_batch_stage_ms reports the stage times from those serial
 // passes and the whole-pipeline time over all passes.
 int DeviceBatch::decode() {
+    if (const int rf = check_resize_format("jpgpu_batch_decode"); rf != JPGPU_OK) return rf;  // (before anything is enqueued)
     hipError_t e = hipSetDevice(ctx_->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     if (replay_layout_active_ && !in_replay_) {  // a decode behind a partial-flush replay: a whole pass again, from the batch's own work lists
@@ -370,6 +377,11 @@ int DeviceBatch::decode() {
         }
     }
     hipEvent_t *ev = &ev_pool_[ev_used_];
+    // (the resize plan of this upload goes to the device in front of the pass, where its wait finds the stream idle)
+    if (resize_.width != 0) {
+        const int rp = plan_resize();
+        if (rp != JPGPU_OK) return rp;
+    }
     redo_.clear();  // (a re-planned image's output is this batch's own plan's again behind this decode; so behind every stage)
     in_decode_request_ = true;
     const bool serial = !overlap_ok_ || (decodes_since_query_ % kSerialEvery) == 0;
@@ -388,7 +400,7 @@ int DeviceBatch::decode() {
         if (staged && (rc = mark(1, s1)) != JPGPU_OK) return rc;
         if ((rc = run_huffman()) != JPGPU_OK) return rc;
         if (staged && (rc = mark(2, s1)) != JPGPU_OK) return rc;
-        if ((rc = run_idct()) != JPGPU_OK) return rc;
+        if ((rc = run_idct(false)) != JPGPU_OK) return rc;
         if ((rc = mark(3, s1)) != JPGPU_OK) return rc;
     } else {
         status_valid_ = false;
@@ -417,6 +429,8 @@ int DeviceBatch::decode() {
     }
     ev_serial_.push_back(staged);
     ev_used_ += 4;
+    // K4 lies behind the last stage event (in the overlapped order: behind the join of both halves), so the stage times are K1..K3's as before
+    if (resize_.width != 0) return run_resize();
     return mark_work();
 }
 

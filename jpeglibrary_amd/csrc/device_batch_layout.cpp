@@ -168,6 +168,8 @@ void DeviceBatch::reset_upload_state(const UploadPlan &p) {
         for (ImagePlan &img : images_) img.replay_skip = false;
     }
     status_valid_ = keep_progressive_store_ = defer_refusal_ = false;
+    resize_plan_valid_ = false;  // (the images' sizes and places are this upload's)
+    resized_fmt_ = -1;
     ev_used_ = 0;
     huff_pool_.clear();
     quant_pool_.clear();

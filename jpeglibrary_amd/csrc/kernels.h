@@ -217,4 +217,20 @@ hipError_t launch_subseq_transcode(hipStream_t stream, int mode, const uint8_t *
                                    const uint64_t *sub_bitoff, const uint64_t *scan_raw_off, uint8_t *raw, int n_slots);
 hipError_t launch_subseq_bit_offsets(hipStream_t stream, const DevScan *scans, const uint32_t *scan_ids, int n_scans, const uint32_t *sub_bits,
                                      uint64_t *bitoff, uint64_t *totals);
+
+// K4 (k4_resample.hip): the RGB_PLANAR_U8 images in `src` (K3's output buffer) resampled to one dense T[n][3][out_height][out_width] of
+// sample_format (RGB_PLANAR_U8 / _F16 / _F32 samples) in `dst`.  One ResizeImage per image that takes part; `tables`: the tap tables of both
+// axes as resize_axis_pack lays them out (resize_tables.h), equal (input, output) lengths sharing one.  src is 256-byte aligned with at
+// least 16 bytes of slack behind the last image.  aff: the affine step of the float samples.
+constexpr int kResizeBandRows = 8;        // output rows one workgroup forms
+constexpr int kResizePieceBytes = 4096;   // bytes of one plane's input row staged in LDS at a time
+struct ResizeImage {
+    uint64_t src_off;          // the image's R plane in src (bytes); G and B follow, w_in * h_in bytes each
+    uint64_t dst_off;          // the image's slab in dst (samples)
+    uint32_t w_in, h_in;
+    uint32_t h_off, h_taps;    // the horizontal table (w_in -> out_width): its first word in `tables`, taps per output
+    uint32_t v_off, v_taps;    // the vertical one (h_in -> out_height)
+};
+hipError_t launch_resample(hipStream_t stream, const uint8_t *src, const ResizeImage *images, int n_images, const uint32_t *tables, void *dst,
+                           int out_width, int out_height, int sample_format, const OutputAffine &aff);
 }  // namespace jpgpu
