@@ -355,6 +355,50 @@ int jpgpu_batch_image_window(const jpgpu_batch *b, int i, jpgpu_rect *window);
 /* Sum of n_mcus over every K3 work entry the last upload listed (all classes, all levels; read only, for tests and tools). */
 int jpgpu_batch_idct_listed_mcus(const jpgpu_batch *b, uint64_t *mcus);
 
+/* ---- Colour: CMYK, YCCK and Adobe-RGB files under the RGB formats (an extension beyond the reference, whose callers refuse such files).
+ *   By default (JPGPU_COLOR_YCC) the RGB formats treat every 1-component frame as grey and every 3-component frame as YCbCr, and refuse
+ * every other frame.  Under JPGPU_COLOR_FILE an image is converted by what its file declares.  The kind of an image of 8-bit precision is
+ * libjpeg's rule over the markers between SOI and the first SOS -- "JFIF seen": an APP0 whose payload (behind the length) is at least 14
+ * bytes and begins "JFIF\0"; "Adobe seen": an APP14 whose payload is at least 12 bytes and begins "Adobe", its transform = payload[11],
+ * the last such segment counting:
+ *     1 component    GRAY
+ *     3 components   JFIF seen: YCBCR.  Else Adobe seen: transform 0 RGB, any other YCBCR.  Else component ids 'R', 'G', 'B': RGB.
+ *                    Otherwise YCBCR.
+ *     4 components   Adobe seen with transform 0: CMYK; with any other transform: YCCK.  No Adobe: CMYK.  JFIF is ignored.
+ *     2 or more than 4 components, or a precision other than 8: refused as without the policy.
+ *   Pixels.  With s0..s3 the INTERLEAVED_U8 ("O2") bytes of the pixel and d(x) = (x + 128 + ((x + 128) >> 8)) >> 8, which is x / 255
+ * rounded to nearest for 0 <= x <= 65025:
+ *     GRAY, YCBCR    the bytes the format holds without the policy
+ *     RGB            (R, G, B) = (s0, s1, s2)
+ *     CMYK           R = d(s0 * s3), G = d(s1 * s3), B = d(s2 * s3)      (Adobe files store inverted inks; Pillow's CMYK -> RGB)
+ *     YCCK           (r, g, b) = RGB_U8's conversion of (s0, s1, s2), the same tables; R = d((255 - r) * s3), likewise G and B
+ * RGBA_U8 adds A = 255; RGB_PLANAR_U8 holds the same bytes as planes; RGB_PLANAR_F16 / _F32 apply their affine step to these bytes (one
+ * float32 multiply, one float32 add, never fused).  Windows and the resize stage see these bytes like any others.
+ *   Only RGB_U8, RGBA_U8 and RGB_PLANAR_U8 / _F16 / _F32 read the policy; every other format decodes and reports as without it.
+ * jpgpu_image_info.out_bytes stays 3 (RGBA_U8: 4) samples per pixel; out_offset of the image BEHIND a 4-component image may lie further on
+ * than out_bytes suggests (the image's samples pass through a scratch slot of 4 bytes per pixel at the same offset): use out_offset.
+ *   jpgpu_batch_set_color_policy is state of the batch: every later upload reads it until it is set again (it is not consumed the way
+ * windows are).  JPGPU_ERR_ARGUMENT for a NULL batch or an unknown value.  jpgpu_batch_upload_frames applies the rule with no marker seen.
+ *   Not covered: jpgpu_decoder_*, jpgpu_decode_scan, jpgpu_progressive_*, jpgpu_multi_* (they decode as JPGPU_COLOR_YCC). */
+typedef enum jpgpu_color_policy {
+    JPGPU_COLOR_YCC = 0, /* 1 component = grey, 3 = YCbCr, anything else refused by the RGB formats */
+    JPGPU_COLOR_FILE = 1 /* what the file declares */
+} jpgpu_color_policy;
+typedef enum jpgpu_color_kind {
+    JPGPU_COLOR_KIND_GRAY = 0,
+    JPGPU_COLOR_KIND_YCBCR = 1,
+    JPGPU_COLOR_KIND_RGB = 2,
+    JPGPU_COLOR_KIND_CMYK = 3,
+    JPGPU_COLOR_KIND_YCCK = 4
+} jpgpu_color_kind;
+int jpgpu_batch_set_color_policy(jpgpu_batch *b, int policy);
+/* The kind image i was planned with: GRAY or YCBCR under JPGPU_COLOR_YCC and under a format that does not read the policy, YCBCR for an
+ * image that failed at upload.  Valid after an upload; JPGPU_ERR_ARGUMENT for a NULL argument or an index out of range. */
+int jpgpu_batch_image_color(const jpgpu_batch *b, int i, int *kind);
+/* The rule above on a file's headers.  Host only, no context needed.  The library's usual header errors (jpgpu_status) for a file without
+ * a frame header or with broken headers; JPGPU_ERR_NOT_SUPPORTED for a frame the rule refuses; JPGPU_ERR_ARGUMENT for a NULL argument. */
+int jpgpu_identify_color(const uint8_t *file, size_t len, int *kind);
+
 /* Coefficient hand-off for multi-scan (progressive, SOF2) images -- BASELINE config 5's "coefficient accumulate then single
  * IDCT pass": the caller's progressive entropy decoder accumulates the coefficient store, the GPU runs what
  * JpegHuffmanProgressiveScanDecoder.Dispose (ScanDecoder/JpegHuffmanProgressiveScanDecoder.cs:421-470: dequantise, IDCT,

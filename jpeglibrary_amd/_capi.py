@@ -129,6 +129,10 @@ class Segment(C.Structure):
     _fields_ = [("data", C.c_void_p), ("len", C.c_size_t)]
 
 
+# jpgpu_color_policy / jpgpu_color_kind, by their Python names
+COLOR_POLICIES = ("ycc", "file")
+COLOR_KINDS = ("gray", "ycbcr", "rgb", "cmyk", "ycck")
+
 UPLOAD_PINNED = 1
 UPLOAD_PINNED_ARENA = 2
 
@@ -181,6 +185,9 @@ SYMBOLS = [
     ("jpgpu_batch_set_windows", C.c_int, [_P, C.POINTER(Rect), C.c_int]),
     ("jpgpu_batch_image_window", C.c_int, [_P, C.c_int, C.POINTER(Rect)]),
     ("jpgpu_batch_idct_listed_mcus", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("jpgpu_batch_set_color_policy", C.c_int, [_P, C.c_int]),
+    ("jpgpu_batch_image_color", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("jpgpu_identify_color", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     ("jpgpu_sizeof_device_ingest_stats", C.c_size_t, []),
     ("jpgpu_batch_device_ingest_stats", C.c_int, [_P, C.POINTER(DeviceIngestStats)]),
     ("jpgpu_batch_upload_frames", C.c_int, [_P, C.POINTER(Frame), C.c_void_p, C.c_int, C.c_int]),

@@ -134,6 +134,24 @@ def _window_rects(rects, n_files=None):
     return out
 
 
+def _color_policy(color, who="color"):
+    """The check of Batch.set_color_policy / decode_batch(color=...), before any library call: "ycc" or "file" -> the jpgpu_color_policy value"""
+    if not isinstance(color, str) or color not in _capi.COLOR_POLICIES:
+        raise ValueError('%s is "ycc" (1 component = grey, 3 = YCbCr) or "file" (what the file declares), not %r' % (who, color))
+    return _capi.COLOR_POLICIES.index(color)
+
+
+def identify_color(data):
+    """What a JPEG file's headers declare its samples to be: "gray", "ycbcr", "rgb", "cmyk" or "ycck" -- libjpeg's rule over the JFIF and Adobe
+    markers and the component ids (include/jpgpu.h, "Colour"), the kind Batch.color(i) reports under the "file" policy.  Host only: no
+    device, no context.  Raises as the decoder does for a file without a frame header, and NotSupported for 2 or more than 4 components or a
+    precision other than 8."""
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    kind = C.c_int()
+    raise_for_status(_lib.jpgpu_identify_color(a.ctypes.data, a.size, C.byref(kind)), b"jpgpu_identify_color: the headers give no colour kind")
+    return _capi.COLOR_KINDS[kind.value]
+
+
 def _upload_any(batch, files, fmt):
     """decode_batch / decode_to_tensors: upload() for bytes-like files, upload_tensors() for a list of torch tensors"""
     files = list(files)
@@ -240,6 +258,21 @@ class Batch:
         arr = (_capi.Rect * max(1, n))(*[_capi.Rect(*r) for r in (rects or [])])
         self._check(_lib.jpgpu_batch_set_windows(self._h, arr, n))
         return self
+
+    def set_color_policy(self, color):
+        """How the RGB formats (RGB_U8, RGBA_U8, RGB_PLANAR_U8 / _F16 / _F32) read a file's colour from the next upload on: "ycc", the default
+        -- 1 component is grey, 3 are YCbCr, anything else fails -- or "file": what the file declares (identify_color), so CMYK and YCCK files
+        come out as RGB the way Pillow converts them and Adobe-RGB files keep their samples.  State of the batch: it holds until set again.
+        ValueError, before the library is called, for any other value."""
+        self._check(_lib.jpgpu_batch_set_color_policy(self._h, _color_policy(color)))
+        return self
+
+    def color(self, i):
+        """"gray", "ycbcr", "rgb", "cmyk" or "ycck": the kind image i was planned with ("gray" / "ycbcr" under the "ycc" policy and under a
+        format that does not read the policy)"""
+        kind = C.c_int()
+        raise_for_status(_lib.jpgpu_batch_image_color(self._h, i, C.byref(kind)), b"jpgpu_batch_image_color: no such image")
+        return _capi.COLOR_KINDS[kind.value]
 
     def window(self, i):
         """(x, y, w, h): the window image i was planned with; (0, 0, W, H) for a whole frame"""
@@ -522,12 +555,15 @@ class Batch:
             pass
 
 
-def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None):
+def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="ycc"):
     """One-call helper: returns (outputs, results).  files: bytes-like objects, or 1-D uint8 torch tensors on the context's device.
-    windows: one (x, y, w, h) per file (Batch.set_windows): outputs[i] is that rectangle of image i."""
+    windows: one (x, y, w, h) per file (Batch.set_windows): outputs[i] is that rectangle of image i.
+    color: "ycc" or "file" (Batch.set_color_policy): under "file" the RGB formats deliver RGB for CMYK, YCCK and Adobe-RGB files."""
     files = list(files)
     windows = _window_rects(windows, len(files))
+    _color_policy(color)
     b = Batch(ctx)
+    b.set_color_policy(color)
     if windows is not None:
         b.set_windows(windows)
     b = _upload_any(b, files, fmt).decode().sync()
@@ -540,7 +576,7 @@ def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None):
     return outs, results
 
 
-def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None):
+def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None, color="ycc"):
     """One-call helper for torch consumers: returns (tensors, results), tensors[i] = Batch.output_tensor(i) -- uint8[3, H, W] on the
     context's device by default -- or None for an image that failed.  Nothing is downloaded.  The batch is not closed: its output
     buffer is the tensors' memory and is freed with the last of them.  files: bytes-like objects, or 1-D uint8 torch tensors on the
@@ -548,9 +584,12 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     dtype=torch.float16 / torch.float32 selects RGB_PLANAR_F16 / _F32: float [3, H, W] tensors written by the decoder's output stage itself.
     mean / std (per channel, 0..1 units; both or neither) then make them (u / 255 - mean) / std through affine_from_mean_std; without them
     a sample is the byte as a float.
-    windows: one (x, y, w, h) per file (Batch.set_windows): tensors[i] is [3, h, w], that rectangle of image i, decoded without the rest."""
+    windows: one (x, y, w, h) per file (Batch.set_windows): tensors[i] is [3, h, w], that rectangle of image i, decoded without the rest.
+    color: "ycc" or "file" (Batch.set_color_policy): under "file" CMYK, YCCK and Adobe-RGB files come out as RGB instead of failing or
+    taking the YCbCr matrix."""
     files = list(files)
     windows = _window_rects(windows, len(files))
+    _color_policy(color)
     if dtype is not None:
         import torch
 
@@ -565,6 +604,7 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     if mean is not None and fmt not in _SAMPLE_DTYPES:
         raise ValueError("decode_to_tensors: mean / std apply to float samples; pass dtype=torch.float16 or torch.float32")
     b = Batch(ctx)
+    b.set_color_policy(color)
     if mean is not None:
         b.set_output_affine(*affine_from_mean_std(mean, std))
     if windows is not None:
@@ -577,18 +617,20 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     return tensors, results
 
 
-def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None):
+def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None, color="ycc"):
     """One-call helper for fixed-size consumers: returns (tensor, results), tensor = Batch.resized_tensor() -- ONE [N, 3, oh, ow] tensor on the
     context's device, size = (oh, ow), dtype torch.float16 (the default), torch.float32 or torch.uint8 -- every image decoded to RGB and
     resampled to that size (antialiased bilinear) in one launch behind the output stage; the slab of an image that failed is zero and
     results[i] says why.  Nothing is downloaded, and the batch is not closed: its buffer is the tensor's memory and is freed with it.
     files: bytes-like objects, or 1-D uint8 torch tensors on the context's device, as in decode_to_tensors.  mean / std (per channel, 0..1
     units; both or neither) make the float samples (v / 255 - mean) / std through affine_from_mean_std; they are refused for torch.uint8.
-    windows: one (x, y, w, h) per file (Batch.set_windows): that rectangle of image i is what is resampled -- a RandomResizedCrop's crop."""
+    windows: one (x, y, w, h) per file (Batch.set_windows): that rectangle of image i is what is resampled -- a RandomResizedCrop's crop.
+    color: "ycc" or "file" (Batch.set_color_policy), as in decode_to_tensors."""
     import torch
 
     files = list(files)
     windows = _window_rects(windows, len(files))
+    _color_policy(color)
     dtype = torch.float16 if dtype is None else dtype
     _resize_setting(size, dtype)
     _all_tensors(files)  # (a list that mixes bytes and tensors raises here, before a batch exists)
@@ -598,6 +640,7 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
         raise ValueError("decode_resized: mean / std apply to float samples; pass dtype=torch.float16 or torch.float32")
     consts = affine_from_mean_std(mean, std) if mean is not None else None
     b = Batch(ctx)
+    b.set_color_policy(color)
     if consts is not None:
         b.set_output_affine(*consts)
     b.set_resize(size, dtype)

@@ -400,6 +400,32 @@ size_t jpgpu_sizeof_rect(void) { return sizeof(jpgpu_rect); }
 static_assert(sizeof(jpgpu_rect) == 16, "jpgpu_rect: four uint32_t");
 int jpgpu_batch_set_windows(jpgpu_batch *b, const jpgpu_rect *windows, int n) { JPGPU_GUARD(b, b->impl.set_windows(windows, n)); }
 int jpgpu_batch_image_window(const jpgpu_batch *b, int i, jpgpu_rect *window) { return b ? b->impl.image_window(i, window) : JPGPU_ERR_ARGUMENT; }
+static_assert((int)JPGPU_COLOR_KIND_GRAY == (int)kColorGray && (int)JPGPU_COLOR_KIND_YCBCR == (int)kColorYcbcr && (int)JPGPU_COLOR_KIND_RGB == (int)kColorRgb &&
+                  (int)JPGPU_COLOR_KIND_CMYK == (int)kColorCmyk && (int)JPGPU_COLOR_KIND_YCCK == (int)kColorYcck, "jpgpu_color_kind mirrors ColorKind");
+int jpgpu_batch_set_color_policy(jpgpu_batch *b, int policy) { JPGPU_GUARD(b, b->impl.set_color_policy(policy)); }
+int jpgpu_batch_image_color(const jpgpu_batch *b, int i, int *kind) { return b ? b->impl.image_color(i, kind) : JPGPU_ERR_ARGUMENT; }
+// Host only: Identify's walk up to the first SOS (or over the whole file, if it has no scan), then the rule of ingest_host.h.
+int jpgpu_identify_color(const uint8_t *file, size_t len, int *kind) {
+    if (!file || !kind) return JPGPU_ERR_ARGUMENT;
+    try {
+        HostDecoder dec;
+        dec.set_input(file, len);
+        size_t pos = 0;
+        (void)dec.identify_until_scan(false, &pos);
+        if (!dec.has_frame_header()) return JPGPU_ERR_INVALID_OPERATION;  // (a scan in front of any frame header) "Frame header was not found."
+        const FrameHeader &fh = dec.frame_header();
+        uint8_t ids[4] = {0, 0, 0, 0};
+        for (size_t c = 0; c < fh.components.size() && c < 4; c++) ids[c] = fh.components[c].identifier;
+        const int k = color_kind_of(fh.precision, fh.num_components, ids, dec.color_markers());
+        if (k < 0) return JPGPU_ERR_NOT_SUPPORTED;
+        *kind = k;
+        return JPGPU_OK;
+    } catch (const DecodeError &e) {
+        return e.status;
+    } catch (const std::exception &) {
+        return JPGPU_ERR_OUT_OF_MEMORY;
+    }
+}
 int jpgpu_batch_idct_listed_mcus(const jpgpu_batch *b, uint64_t *mcus) {
     if (!b || !mcus) return JPGPU_ERR_ARGUMENT;
     *mcus = b->impl.idct_listed_mcus();

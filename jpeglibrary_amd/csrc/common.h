@@ -69,6 +69,11 @@ struct OutputAffine {
     float scale[3], bias[3];
 };
 constexpr OutputAffine kOutputAffineIdentity = {{1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f}};
+// What an image's samples are (jpgpu_color_kind).  Under JPGPU_COLOR_YCC every image is kColorGray or kColorYcbcr; JPGPU_COLOR_FILE adds the
+// three kinds a file can declare (ingest_host.h: color_kind_of), which the RGB formats convert in a launch of their own (k3c_color.hip).
+enum ColorKind : int32_t { kColorGray = 0, kColorYcbcr = 1, kColorRgb = 2, kColorCmyk = 3, kColorYcck = 4 };
+constexpr bool color_kind_by_file(int k) { return k == kColorRgb || k == kColorCmyk || k == kColorYcck; }
+constexpr int color_kind_sample_bytes(int k) { return k == kColorGray ? 1 : (k == kColorCmyk || k == kColorYcck ? 4 : 3); }
 
 // One scan job.
 struct alignas(16) DevScan {

@@ -43,7 +43,7 @@ void DevBuffer::release() {
 
 DeviceBatch::~DeviceBatch() {
     if (ctx_) (void)hipSetDevice(ctx_->device);
-    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
+    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_color_images_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
         b->release();
     for (hipEvent_t &e : ev_pool_)
         if (e) (void)hipEventDestroy(e);
@@ -63,12 +63,31 @@ int DeviceBatch::hip_fail(hipError_t e, const char *what) {
     return fail(e == hipErrorOutOfMemory ? JPGPU_ERR_OUT_OF_MEMORY : JPGPU_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &geo) const {
+uint64_t DeviceBatch::slot_bytes(const ImagePlan &img) {
+    const uint64_t samples = color_kind_by_file(img.color_kind) ? (uint64_t)img.win.width * img.win.height * color_kind_sample_bytes(img.color_kind) : 0u;
+    return std::max(img.out_bytes, samples);
+}
+
+int DeviceBatch::set_color_policy(int policy) {
+    if (policy != JPGPU_COLOR_YCC && policy != JPGPU_COLOR_FILE) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_set_color_policy: unknown policy");
+    color_policy_ = policy;
+    return JPGPU_OK;
+}
+
+int DeviceBatch::image_color(int i, int *kind) const {
+    const ImagePlan *img = image(i);
+    if (!img || !kind) return JPGPU_ERR_ARGUMENT;
+    *kind = img->color_kind;
+    return JPGPU_OK;
+}
+
+void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &geo, const ColorMarkers &markers) const {
     const FrameHeader &fh = geo.frame;
     img.width = fh.samples_per_line;
     img.height = fh.lines;
     img.precision = fh.precision;
     img.num_components = fh.num_components;
+    img.color_kind = fh.num_components == 1 ? kColorGray : kColorYcbcr;
     img.restart_interval = geo.restart_interval;
     img.mcus_per_line = (uint32_t)geo.mcus_per_line;
     img.mcus_per_column = (uint32_t)geo.mcus_per_column;
@@ -79,7 +98,14 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
             throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "INTERLEAVED_U8_SCALED is defined for precisions 1..16 only.", kDetailUnsupportedFrame);
         img.out_bytes = (uint64_t)img.width * img.height * img.num_components;
     } else if (fmt_is_rgb(format_)) {
-        if (fh.num_components != 1 && fh.num_components != 3)  // apps/JpegDecode/DecodeAction.cs:29-33
+        if (color_policy_ == JPGPU_COLOR_FILE) {  // the one decision the policy makes (ingest_host.h); what it refuses is refused below, as ever
+            uint8_t ids[4] = {0, 0, 0, 0};
+            for (size_t c = 0; c < fh.components.size() && c < 4; c++) ids[c] = fh.components[c].identifier;
+            const int kind = color_kind_of(fh.precision, fh.num_components, ids, markers);
+            if (kind >= 0) img.color_kind = (uint8_t)kind;
+        }
+        const bool four = img.color_kind == kColorCmyk || img.color_kind == kColorYcck;
+        if (fh.num_components != 1 && fh.num_components != 3 && !four)  // apps/JpegDecode/DecodeAction.cs:29-33
             throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "This color space is not supported", kDetailUnsupportedFrame);
         if (fh.precision != 8)
             throw DecodeError(JPGPU_ERR_NOT_SUPPORTED, "RGB output is defined for 8-bit precision only (the reference converter assumes 8-bit samples).",

@@ -106,6 +106,9 @@ struct ImagePlan {
     // windowed = false: the whole frame (win = {0, 0, width, height}), planned and decoded exactly as without windows
     bool windowed = false;
     jpgpu_rect win = {0, 0, 0, 0};
+    // what the image's samples are (common.h: ColorKind): kColorGray / kColorYcbcr unless the batch's colour policy is JPGPU_COLOR_FILE, the
+    // format reads it and the file declares otherwise; an image of the other three kinds takes K3's generic class and the K3C launch
+    uint8_t color_kind = kColorYcbcr;
 };
 
 class WorkCrew;
@@ -138,6 +141,9 @@ class DeviceBatch {
     // The windows of the NEXT upload of whole files (jpgpu_batch_set_windows): consumed by it, accepted or refused.
     int set_windows(const jpgpu_rect *windows, int n);
     int image_window(int i, jpgpu_rect *window) const;
+    // The colour policy (jpgpu_batch_set_color_policy): state of the batch, read by every later upload under an RGB format.
+    int set_color_policy(int policy);
+    int image_color(int i, int *kind) const;
     uint64_t idct_listed_mcus() const { return idct_listed_mcus_; }
     // One progressive frame collected by the JpegDecoder mirror: its entropy scans + the Dispose() pass.
     int upload_progressive_frame(const ProgressiveFrame &frame, const uint8_t *file, size_t file_len, int sof, int format);
@@ -239,7 +245,12 @@ class DeviceBatch {
     void plan_overlap_halves(UploadPlan &p);
     void init_status();
     int upload_plan(const UploadPlan &p, const std::vector<const uint8_t *> &file_ptr, const std::vector<size_t> &file_len);
-    void plan_image_geometry(ImagePlan &img, const BaselineGeometry &geo) const;
+    // markers: what the file's headers declare about its colour (none seen: frames, single jobs)
+    void plan_image_geometry(ImagePlan &img, const BaselineGeometry &geo, const ColorMarkers &markers = ColorMarkers()) const;
+    // bytes an image takes in the output buffer AND in the scratch image, which mirrors its offsets: out_bytes, or the 4 bytes per pixel a
+    // CMYK / YCCK image's samples need where that is more (RGB_U8, RGB_PLANAR_U8)
+    static uint64_t slot_bytes(const ImagePlan &img);
+    void plan_color_convert();
     // ingest (jpgpu_batch_upload*), see device_batch_ingest.cpp
     void plan_file_headers(const uint8_t *file, size_t len, FilePlan &fp) const;
     void plan_file_full(const uint8_t *file, size_t len, int index, FilePlan &fp) const;
@@ -282,8 +293,9 @@ class DeviceBatch {
     bool defer_refusal_ = false;           // result(): a frame job's `refuse` is the Dispose() pass's business, not a scan's
     bool keep_canvas_ = false;  // layout of a single scan job over the caller's samples: nothing the scan does not write is touched
     struct OutClear {
-        uint64_t first, second;              // (offset, bytes) in the output buffer
+        uint64_t first, second;              // (offset, bytes) in the output buffer; the scratch image's slot is slot_bytes long
         uint64_t planes_first, planes_bytes; // EXTENDED_U16: the image's int16 planes
+        uint64_t slot_bytes;
     };
     std::vector<OutClear> out_clear_;  // images whose scans leave frame components unwritten
 
@@ -430,6 +442,12 @@ class DeviceBatch {
     };
     std::vector<RgbConvert> rgb_convert_;
     DevBuffer d_rgb_scratch_;
+    // ... and the images of kind RGB, CMYK and YCCK among them, listed apart: one K3C launch converts them all (plan_color_convert)
+    std::vector<RgbConvert> color_convert_;
+    std::vector<ColorImage> color_images_;
+    uint64_t color_max_pixels_ = 0;
+    DevBuffer d_color_images_;
+    int color_policy_ = JPGPU_COLOR_YCC;
     DevBuffer d_chunk_work_, d_chunk_sums_;
     int n_chunk_work_ = 0;
     DevBuffer d_unstuffed_, d_ends_u_;  // K1 output: entropy data as the bit reader sees it + interval ends in it

@@ -206,9 +206,9 @@ void DeviceBatch::plan_file_full(const uint8_t *file, size_t len, int index, Fil
         if (entropy_only_) img.sof = (uint8_t)dec.start_of_frame();
         if (fp.jobs.empty()) {
             // no scan: Decode() succeeds without writing anything; keep the frame geometry for the caller
-            if (img.sof == kSOF0 || img.sof == kSOF1 || img.sof == kSOF2) plan_image_geometry(img, BaselineGeometry::latch(dec, dec.frame_header()));
+            if (img.sof == kSOF0 || img.sof == kSOF1 || img.sof == kSOF2) plan_image_geometry(img, BaselineGeometry::latch(dec, dec.frame_header()), dec.color_markers());
         } else {
-            plan_image_geometry(img, fp.jobs[0].geo);
+            plan_image_geometry(img, fp.jobs[0].geo, dec.color_markers());
             img.blocks_per_mcu = (uint32_t)fp.jobs[0].blocks_per_mcu;
         }
         fp.seq_ends = handler.sequential_ends();
@@ -228,7 +228,7 @@ void DeviceBatch::plan_file_full(const uint8_t *file, size_t len, int index, Fil
             img.late_detail = e.detail;
             img.late_error = e.what();
             try {
-                plan_image_geometry(img, fp.jobs[0].geo);
+                plan_image_geometry(img, fp.jobs[0].geo, dec.color_markers());
                 img.blocks_per_mcu = (uint32_t)fp.jobs[0].blocks_per_mcu;
             } catch (const DecodeError &e2) {
                 fp.jobs.clear();
@@ -281,7 +281,7 @@ void DeviceBatch::plan_file_headers(const uint8_t *file, size_t len, FilePlan &f
         FastPlanHandler handler(&fp.jobs);
         dec.decode(handler, true);
         if (fp.jobs.size() != 1) throw NeedFullWalk{};
-        plan_image_geometry(img, fp.jobs[0].geo);
+        plan_image_geometry(img, fp.jobs[0].geo, dec.color_markers());
         img.blocks_per_mcu = (uint32_t)fp.jobs[0].blocks_per_mcu;
         fp.speculative = true;
     } catch (const NeedFullWalk &) {

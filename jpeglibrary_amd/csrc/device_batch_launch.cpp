@@ -222,8 +222,8 @@ int DeviceBatch::clear_partial_outputs() {
         hipError_t e = hipMemsetAsync((uint8_t *)d_out_.ptr + c.first, 0, c.second, ctx_->stream);
         if (e == hipSuccess && format_ == JPGPU_FMT_EXTENDED_U16 && c.planes_bytes)
             e = hipMemsetAsync((uint8_t *)d_planes_.ptr + c.planes_first, 0, c.planes_bytes, ctx_->stream);
-        if (e == hipSuccess && d_rgb_scratch_.ptr && c.first + c.second <= d_rgb_scratch_.cap)
-            e = hipMemsetAsync((uint8_t *)d_rgb_scratch_.ptr + c.first, 0, c.second, ctx_->stream);
+        if (e == hipSuccess && d_rgb_scratch_.ptr && c.first + c.slot_bytes <= d_rgb_scratch_.cap)
+            e = hipMemsetAsync((uint8_t *)d_rgb_scratch_.ptr + c.first, 0, c.slot_bytes, ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(output)");
     }
     return JPGPU_OK;
@@ -338,6 +338,10 @@ int DeviceBatch::run_idct(bool with_resize) {
                               output_affine_);
         if (e != hipSuccess) return hip_fail(e, "ycc_to_rgb_kernel");
     }
+    // the images of kind RGB, CMYK and YCCK (JPGPU_COLOR_FILE): one launch for all of them
+    e = launch_color_convert(ctx_->stream, (const uint8_t *)d_rgb_scratch_.ptr, (uint8_t *)d_out_.ptr, (const ColorImage *)d_color_images_.ptr,
+                             (int)color_images_.size(), color_max_pixels_, format_, kf, output_affine_);
+    if (e != hipSuccess) return hip_fail(e, "color_convert_kernel");
     if (with_resize && resize_.width != 0) return run_resize();  // K4, behind everything above
     return mark_work();
 }

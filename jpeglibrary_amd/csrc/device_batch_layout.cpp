@@ -151,6 +151,7 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
     plan_subseq_lists(p);
     assemble_progressive_lists(p);
     plan_output_clears();
+    plan_color_convert();
     assemble_idct_lists(p);
     plan_overlap_halves(p);
     init_status();
@@ -181,6 +182,7 @@ void DeviceBatch::reset_upload_state(const UploadPlan &p) {
     prog_pipelined_ = !p.sw.prog_no_pipeline;
     prog_spin_budget_ = p.sw.prog_spin_budget;
     rgb_convert_.clear();
+    color_convert_.clear();
     sub_scan_ids_.clear();
     total_subs_ = max_subs_per_scan_ = 0;
     k2s_budget_ = 0;
@@ -269,7 +271,7 @@ void DeviceBatch::plan_image(UploadPlan &p, size_t ii, const std::vector<size_t>
     img.coef_offset = p.coef_off;
     img.total_blocks = 0;
     if (img.status != JPGPU_OK) return;
-    p.out_off = align_up(p.out_off + img.out_bytes, 256);
+    p.out_off = align_up(p.out_off + slot_bytes(img), 256);  // (the scratch image mirrors these offsets: the slot holds the larger of the two)
     p.planes_off = align_up(p.planes_off + img.planes_bytes, 256);
     if (!img.jobs.empty()) total_pixels_ += (uint64_t)img.width * img.height;
     // sequential scans of this image that write a component an earlier scan of it has written (ordered launches, see plan_idct_work)
@@ -502,7 +504,7 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
     // to back in one dense run of the image's blocks, which is what the coefficient readers hand out: they stay dense.)
     // (a windowed image's scan is always handed over dense: the split form of K3 would need a window variant of its own)
     const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed, split_always = p.sw.handoff_set;
-    const int k3_class = fmt_is_interleaved(format_) ? idct_layout_class(s) : 0;
+    const int k3_class = fmt_is_interleaved(format_) && !color_kind_by_file(img.color_kind) ? idct_layout_class(s) : 0;
     if (split_wanted && job.kind == kScanSequential && s.dri != 0 && img.jobs.size() == 1 && !img.replay_skip && s.total_mcus > 0 &&
         s.blocks_per_mcu != 0 && idct_split_supported(format_, k3_class) &&
         // The planes pay where few blocks reach into coefficients 32..63; all that is known of that in front of the decode is
@@ -519,12 +521,14 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
     }
 }
 
-// no fused conversion for a scan of image ii: its samples go to the scratch image, then ycc_to_rgb_kernel (once per image)
+// no fused conversion for a scan of image ii: its samples go to the scratch image, then ycc_to_rgb_kernel (once per image) -- or, for an image
+// of kind RGB, CMYK or YCCK, the batch's one K3C launch (plan_color_convert)
 void DeviceBatch::list_rgb_convert(size_t ii) {
     const ImagePlan &img = images_[ii];
-    for (const RgbConvert &rc : rgb_convert_)
+    std::vector<RgbConvert> &list = color_kind_by_file(img.color_kind) ? color_convert_ : rgb_convert_;
+    for (const RgbConvert &rc : list)
         if (rc.image == (uint32_t)ii) return;
-    rgb_convert_.push_back({(uint32_t)ii, img.out_offset, (uint64_t)img.win.width * img.win.height, img.num_components});  // (the window's pixels)
+    list.push_back({(uint32_t)ii, img.out_offset, (uint64_t)img.win.width * img.win.height, img.num_components});  // (the window's pixels)
 }
 
 // K3's work for one scan: tile size and alignment, layout class, scratch conversion, ordering level, work entries, the partial-MCU entry.
@@ -558,6 +562,8 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
     // RGB / RGBA of a frame with overlapping scans (below): every scan's samples go to the scratch image in file order and
     // are converted at the end -- a fused conversion of one scan would be overwritten by the scratch image's
     if (!holds_samples && overlapping_scans && rgb_out) cls = 0;
+    // ... and so do the samples of an image whose kind is RGB, CMYK or YCCK (JPGPU_COLOR_FILE): the fused classes convert YCbCr and grey
+    if (!holds_samples && color_kind_by_file(img.color_kind)) cls = 0;
     if ((cls == 0 || holds_samples) && rgb_out) list_rgb_convert(ii);
     // A baseline frame whose LATER scans write a component this one writes too (a corrupted selector: one component
     // scanned twice, another never): in the reference the later WriteBlock wins -- where the later scan GOT to; a later
@@ -798,11 +804,20 @@ void DeviceBatch::plan_output_clears() {
             for (int c = 0; c < s.scan_components; c++) all &= !((s.comp[c].h > 1 && s.comp[c].hs > 1) || (s.comp[c].v > 1 && s.comp[c].vs > 1));
         }
         for (int c = 0; c < img.num_components; c++) all &= ((covered[c >> 6] >> (c & 63)) & 1ull) != 0;
-        if (!all && !img.replay_skip) out_clear_.push_back({img.out_offset, img.out_bytes, img.planes_offset, img.planes_bytes});
+        if (!all && !img.replay_skip) out_clear_.push_back({img.out_offset, img.out_bytes, img.planes_offset, img.planes_bytes, slot_bytes(img)});
         // RGB / RGBA = the callers' converter applied to the YCbCr8 buffer (DecodeAction.cs:71-74): an image without any scan
         // leaves that buffer as it was (zero here), and the converter still runs over it
-        if (img.jobs.empty() && !img.replay_skip && fmt_is_rgb(format_))
-            rgb_convert_.push_back({(uint32_t)(&img - images_.data()), img.out_offset, (uint64_t)img.win.width * img.win.height, img.num_components});
+        if (img.jobs.empty() && !img.replay_skip && fmt_is_rgb(format_)) list_rgb_convert((size_t)(&img - images_.data()));
+    }
+}
+
+// The descriptors of the K3C launch: one per image of kind RGB, CMYK or YCCK whose samples go through the scratch image.
+void DeviceBatch::plan_color_convert() {
+    color_images_.clear();
+    color_max_pixels_ = 0;
+    for (const RgbConvert &rc : color_convert_) {
+        color_images_.push_back({rc.out_offset, rc.out_offset, rc.pixels, (uint32_t)images_[rc.image].color_kind, 0u});
+        color_max_pixels_ = std::max(color_max_pixels_, rc.pixels);
     }
 }
 
@@ -866,7 +881,7 @@ void DeviceBatch::plan_overlap_halves(UploadPlan &p) {
     while (huff_half_ < n_huff_work_ && h_scans_[p.huff_work[huff_half_].scan].image_index < half_image) huff_half_++;
     // worth it for batches that keep the machine busy for milliseconds: the halves cost four launches and two events
     if (wanted && !entropy_only_ && p.sub_work.empty() && p.prog_work.empty() && total_blocks_ >= (4u << 20) && huff_half_ > 0 &&
-        huff_half_ < n_huff_work_ && rgb_convert_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
+        huff_half_ < n_huff_work_ && rgb_convert_.empty() && color_convert_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
         idct_win_class_begin_[kNumIdctLayoutClasses] == idct_win_class_begin_[0]) {  // (no windowed image: the halves have no list for their work)
         for (int half = 0; half < 2; half++) {
             idct_half_begin_[half][0] = (int)p.idct_work_halves.size();
@@ -943,7 +958,8 @@ int DeviceBatch::upload_plan(const UploadPlan &p, const std::vector<const uint8_
         // + one tile of slack (IDCT DMA reads whole tiles) + the split scans' flag words
         {&d_coefs_, nullptr, 0, entropy_only_ ? 256 : (size_t)coef_store_blocks_ * 128 + (size_t)kIdctBlocksPerWg * 128 + (size_t)p.flag_words * 8 + 256},
         {&d_out_, nullptr, 0, entropy_only_ ? 256 : (size_t)out_bytes_ + 256},
-        {&d_rgb_scratch_, nullptr, 0, rgb_convert_.empty() ? 0 : (size_t)out_bytes_ + 256},
+        {&d_rgb_scratch_, nullptr, 0, rgb_convert_.empty() && color_convert_.empty() ? 0 : (size_t)out_bytes_ + 256},
+        {&d_color_images_, color_images_.data(), color_images_.size() * sizeof(ColorImage), 0},
         {&d_planes_, nullptr, 0, format_ == JPGPU_FMT_EXTENDED_U16 && !entropy_only_ ? (size_t)planes_bytes_ + 256 : 0},
         {&d_input_, nullptr, 0, (size_t)input_bytes_},
     };

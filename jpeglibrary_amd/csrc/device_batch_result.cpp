@@ -252,6 +252,7 @@ int DeviceBatch::redo_swallowed(int i, int job, jpgpu_image_result *res) {
             std::vector<int> forced = forced_swallow_;
             forced.push_back(ordinal);
             sub.set_forced_swallow(forced);
+            (void)sub.set_color_policy(color_policy_);
             if (img.windowed) sub.set_windows(&img.win, 1);  // (the same window: its output replaces the image's)
             const uint8_t *fptr = file.data();
             const size_t flen = file.size();

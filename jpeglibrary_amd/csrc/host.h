@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "common.h"
+#include "ingest_host.h"
 
 namespace jpgpu {
 
@@ -167,6 +168,8 @@ class HostDecoder {
     void clear_quantization_tables() { quant_.clear(); }                                // ClearQuantizationTable :784-787
     const uint8_t *input() const { return input_; }
     size_t input_len() const { return input_len_; }
+    // what the last Identify walk (identify, identify_until_scan) saw of APP0 "JFIF" and APP14 "Adobe" in front of the first SOS
+    const ColorMarkers &color_markers() const { return color_; }
 
     // ref: InitDecodeComponents (ScanDecoder/JpegHuffmanScanDecoder.cs:17-72)
     int resolve_scan(const FrameHeader &fh, const ScanHeader &sh, ResolvedScanComponent out[kMaxScanComponents], bool optimizer_rules = false) const;
@@ -174,7 +177,7 @@ class HostDecoder {
   private:
     bool process_marker_for_identification(int marker, MarkerReader &r, bool load_qt);  // :114-162
     bool process_marker_for_decode(int marker, MarkerReader &r, ScanHandler &h);        // :558-617
-    void process_other_marker(MarkerReader &r);                                         // :251-263
+    void process_other_marker(MarkerReader &r, int marker = -1);                        // :251-263 (marker: an Identify walk's, for color_)
     void process_frame_header(MarkerReader &r, bool metadata_only, bool override_allowed);  // :265-289
     ScanHeader process_scan_header(MarkerReader &r, bool metadata_only);                // :291-307
     void process_dri(MarkerReader &r);                                                  // :635-650
@@ -189,6 +192,8 @@ class HostDecoder {
     std::vector<HuffTable> huff_;
     std::vector<QuantTable> quant_;
     bool scan_decoder_created_ = false;
+    ColorMarkers color_;
+    bool color_open_ = false;  // an Identify walk is in front of its first SOS: process_other_marker records into color_
 };
 
 // Geometry of a baseline scan decoder instance, latched at SOF time

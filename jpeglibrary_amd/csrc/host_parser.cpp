@@ -356,9 +356,10 @@ void HostDecoder::set_quantization_table(const QuantTable &t) {
     quant_.push_back(t);
 }
 
-void HostDecoder::process_other_marker(MarkerReader &r) {
+void HostDecoder::process_other_marker(MarkerReader &r, int marker) {
     uint16_t length;
     if (!r.try_read_length(&length)) throw_invalid_data_at(r.consumed_byte_count(), "Unexpected end of input data when reading segment length.", kDetailBadHeader);
+    if (color_open_ && (int)length <= r.remaining_byte_count()) note_color_marker(color_, marker, r.remaining_bytes(), length);
     if (!r.try_advance(length)) throw_invalid_data_at(r.consumed_byte_count(), "Unexpected end of input data reached.", kDetailBadHeader);
 }
 
@@ -449,6 +450,7 @@ bool HostDecoder::process_marker_for_identification(int marker, MarkerReader &r,
         start_of_frame_ = marker;
         process_frame_header(r, false, false);
     } else if (marker == kSOS) {
+        color_open_ = false;  // (what a file declares about its colour lies in front of its first scan)
         process_scan_header(r, true);
     } else if (marker == kDRI) {
         process_dri(r);
@@ -458,7 +460,7 @@ bool HostDecoder::process_marker_for_identification(int marker, MarkerReader &r,
     } else if (marker == kEOI) {
         return false;
     } else {
-        process_other_marker(r);
+        process_other_marker(r, marker);
     }
     return true;
 }
@@ -467,6 +469,8 @@ int HostDecoder::identify(bool load_quantization_tables) {
     if (!input_ || input_len_ == 0) throw_invalid_operation("Input buffer is not specified.");
     MarkerReader r(input_, input_len_);
     frame_.reset();
+    color_ = ColorMarkers();
+    color_open_ = true;
     bool to_continue = true;
     while (to_continue && !r.is_empty()) {
         int marker;
@@ -481,6 +485,8 @@ bool HostDecoder::identify_until_scan(bool load_quantization_tables, size_t *sca
     if (!input_ || input_len_ == 0) throw_invalid_operation("Input buffer is not specified.");
     MarkerReader r(input_, input_len_);
     frame_.reset();
+    color_ = ColorMarkers();
+    color_open_ = true;
     bool to_continue = true;
     while (to_continue && !r.is_empty()) {
         int marker;
@@ -571,6 +577,7 @@ void HostDecoder::decode(ScanHandler &handler, bool have_output_writer) {
     if (!have_output_writer) throw_invalid_operation("The output buffer is not specified.");
     MarkerReader r(input_, input_len_);
     scan_decoder_created_ = false;
+    color_open_ = false;  // (an Identify walk that met no scan left it open)
     if (!r.try_read_start_of_image()) throw_invalid_data_at(r.consumed_byte_count(), "Marker StartOfImage not found.", kDetailBadHeader);
     try {
         bool to_continue = true;

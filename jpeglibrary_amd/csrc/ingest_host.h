@@ -13,6 +13,32 @@
 
 namespace jpgpu {
 
+// What a file declares about its colour space, in the markers between SOI and the first SOS (HostDecoder records it on every Identify walk),
+// and libjpeg's rule over it (jdapimin.c, default_decompress_parms) -- the one decision JPGPU_COLOR_FILE makes (include/jpgpu.h, "Colour").
+struct ColorMarkers {
+    bool saw_jfif = false;     // an APP0 of at least 14 payload bytes that begins "JFIF\0"
+    int adobe_transform = -1;  // payload[11] of the last APP14 of at least 12 payload bytes that begins "Adobe"; -1: none
+};
+inline void note_color_marker(ColorMarkers &m, int marker, const uint8_t *payload, size_t len) {
+    if (marker == 0xE0 && len >= 14 && memcmp(payload, "JFIF\0", 5) == 0) m.saw_jfif = true;
+    if (marker == 0xEE && len >= 12 && memcmp(payload, "Adobe", 5) == 0) m.adobe_transform = payload[11];
+}
+// -> a jpgpu_color_kind, or -1 for what the RGB formats refuse as before: 2 or more than 4 components, a precision other than 8.
+// ids: the frame's component identifiers (num_components of them).
+inline int color_kind_of(int precision, int num_components, const uint8_t *ids, const ColorMarkers &m) {
+    if (precision != 8) return -1;
+    const bool adobe = m.adobe_transform >= 0;
+    switch (num_components) {
+    case 1: return JPGPU_COLOR_KIND_GRAY;
+    case 3:
+        if (m.saw_jfif) return JPGPU_COLOR_KIND_YCBCR;
+        if (adobe) return m.adobe_transform == 0 ? JPGPU_COLOR_KIND_RGB : JPGPU_COLOR_KIND_YCBCR;
+        return ids && ids[0] == 0x52 && ids[1] == 0x47 && ids[2] == 0x42 ? JPGPU_COLOR_KIND_RGB : JPGPU_COLOR_KIND_YCBCR;
+    case 4: return adobe && m.adobe_transform != 0 ? JPGPU_COLOR_KIND_YCCK : JPGPU_COLOR_KIND_CMYK;  // (JFIF says nothing about four components)
+    default: return -1;
+    }
+}
+
 // One input file as the caller handed it over: a list of segments (one for jpgpu_batch_upload), and the contiguous bytes the
 // host parser reads -- the file itself, or what was gathered of a multi-segment file (its head for the header-only plan, all
 // of it for the full marker walks).

@@ -1,0 +1,159 @@
+// jpeglibrary_amd/csrc/k3c_color.hip -- K3C: the colour step of the files JPGPU_COLOR_FILE treats by what they declare (include/jpgpu.h, "Colour").
+// Images of kind RGB, CMYK and YCCK take K3's generic class, which leaves their INTERLEAVED_U8 samples in the scratch image; this kernel turns
+// those samples into the five RGB forms.  One launch per batch: blockIdx.y = image (its descriptor in HBM, like extend_u16_kernel), blockIdx.x
+// strides over the image's groups of four pixels, one group per lane -- a 4-component group is one 16-byte load, a 3-component group three
+// dwords.  GRAY and YCBCR images never come here: they keep K3's fused classes and ycc_to_rgb_kernel.
+// (A file of its own so that every other kernel object stays byte for byte what it was.  The YCbCr terms below restate chroma_terms / rgb_pixel
+// of k3_idct.hip, and affine_sample its affine step: YCCK is defined through the bytes RGB_U8 would hold.)
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "kernels.h"
+
+namespace jpgpu {
+
+namespace {
+
+typedef float float2v __attribute__((ext_vector_type(2)));
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+
+// byte gather from the 8 bytes {lo (indices 0-3), hi (indices 4-7)}, index 12 = a zero byte: one v_perm_b32
+__device__ __forceinline__ uint32_t pick4(uint32_t lo, uint32_t hi, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
+#define JPGPU_SEL(a, b, c, d) ((uint32_t)(a) | ((uint32_t)(b) << 8) | ((uint32_t)(c) << 16) | ((uint32_t)(d) << 24))
+
+// round-to-nearest of x / 255 for 0 <= x <= 65025 (tests/test_color_cpu.py checks every x)
+__device__ __forceinline__ uint32_t div255(uint32_t x) {
+    const uint32_t t = x + 128u;
+    return (t + (t >> 8)) >> 8;
+}
+__device__ __forceinline__ uint32_t clamp_u8_i32(int32_t v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
+// one pixel's samples s = s0 | s1 << 8 | s2 << 16 | s3 << 24 -> R | G << 8 | B << 16
+__device__ __forceinline__ uint32_t color_pixel(uint32_t kind, uint32_t s, const YccRgbFactors &k) {
+    if (kind == kColorRgb) return s & 0x00FFFFFFu;
+    uint32_t c0 = s & 0xFFu, c1 = (s >> 8) & 0xFFu, c2 = (s >> 16) & 0xFFu;
+    const uint32_t s3 = s >> 24;
+    if (kind == kColorYcck) {  // RGB_U8's conversion of (s0, s1, s2), inverted
+        const int32_t cb = (int32_t)c1 - 128, cr = (int32_t)c2 - 128, y = (int32_t)c0;
+        c0 = 255u - clamp_u8_i32(y + ((k.cr_r * cr + 32768) >> 16));
+        c1 = 255u - clamp_u8_i32(y + ((k.cb_g * cb + 32768 + k.cr_g * cr) >> 16));
+        c2 = 255u - clamp_u8_i32(y + ((k.cb_b * cb + 32768) >> 16));
+    }
+    return div255(c0 * s3) | (div255(c1 * s3) << 8) | (div255(c2 * s3) << 16);
+}
+
+__device__ __forceinline__ float affine_sample(uint32_t u, float scale, float bias) { return __fadd_rn(__fmul_rn((float)u, scale), bias); }
+
+// Four bytes of one plane (w = u0 | u1 << 8 | ...) -> four samples at dst.  A plane starts at c * pixels samples, which is a multiple of
+// nothing: the destination is aligned for one sample only, and the stores say so.
+template <int FMT>
+__device__ __forceinline__ void store_plane4(uint8_t *dst, uint32_t w, float scale, float bias) {
+    if constexpr (FMT == kFmtRgbPlanarU8) {
+        __builtin_memcpy(dst, &w, 4);
+    } else {
+        float f[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) f[j] = affine_sample((w >> (8 * j)) & 0xFFu, scale, bias);
+        if constexpr (FMT == kFmtRgbPlanarF32) {
+            __builtin_memcpy(__builtin_assume_aligned(dst, 4), f, 16);
+        } else {
+            const half2v h[2] = {__builtin_convertvector(float2v{f[0], f[1]}, half2v), __builtin_convertvector(float2v{f[2], f[3]}, half2v)};
+            __builtin_memcpy(__builtin_assume_aligned(dst, 2), h, 8);
+        }
+    }
+}
+
+// one sample of one plane (the last one to three pixels of an image whose pixel count is no multiple of four)
+template <int FMT>
+__device__ __forceinline__ void store_plane1(uint8_t *plane, uint64_t i, uint32_t u, float scale, float bias) {
+    if constexpr (FMT == kFmtRgbPlanarU8) plane[i] = (uint8_t)u;
+    else if constexpr (FMT == kFmtRgbPlanarF32) reinterpret_cast<float *>(plane)[i] = affine_sample(u, scale, bias);
+    else reinterpret_cast<_Float16 *>(plane)[i] = (_Float16)affine_sample(u, scale, bias);
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void color_convert_kernel(const uint8_t *__restrict__ scratch, uint8_t *__restrict__ out,
+                                                            const ColorImage *__restrict__ images, YccRgbFactors kf, OutputAffine aff) {
+    const ColorImage g = images[blockIdx.y];
+    const uint8_t *src = scratch + g.src_off;
+    uint8_t *dst = out + g.dst_off;
+    const uint32_t kind = g.kind;
+    const bool four = kind != kColorRgb;  // bytes per pixel in the scratch image: 4 (CMYK, YCCK) or 3
+    constexpr uint32_t kSampleBytes = (uint32_t)fmt_rgb_plane_sample_bytes(FMT);
+    const uint64_t groups = g.pixels >> 2;
+    for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q <= groups; q += (uint64_t)gridDim.x * 256) {
+        if (q == groups) {
+            // the tail: byte by byte, by the one lane that gets here
+            for (uint64_t i = q * 4; i < g.pixels; i++) {
+                const uint8_t *s = src + i * (four ? 4u : 3u);
+                const uint32_t px = color_pixel(kind, (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | (four ? (uint32_t)s[3] << 24 : 0u), kf);
+                if constexpr (fmt_is_rgb_planes(FMT)) {
+#pragma unroll
+                    for (int c = 0; c < 3; c++)
+                        store_plane1<FMT>(dst + (uint64_t)c * g.pixels * kSampleBytes, i, (px >> (8 * c)) & 0xFFu, aff.scale[c], aff.bias[c]);
+                } else {
+                    uint8_t *d = dst + i * (FMT == kFmtRgbaU8 ? 4u : 3u);
+                    d[0] = (uint8_t)px;
+                    d[1] = (uint8_t)(px >> 8);
+                    d[2] = (uint8_t)(px >> 16);
+                    if constexpr (FMT == kFmtRgbaU8) d[3] = 255;
+                }
+            }
+            break;
+        }
+        uint32_t s[4];
+        if (four) {  // (the scratch slot starts on a multiple of 256: every group is 16-byte aligned)
+            const uint4 v = *reinterpret_cast<const uint4 *>(src + q * 16);
+            s[0] = v.x, s[1] = v.y, s[2] = v.z, s[3] = v.w;
+        } else {
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(src + q * 12);
+            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+            s[0] = w0;  // (color_pixel masks the fourth byte away)
+            s[1] = pick4(w0, w1, JPGPU_SEL(3, 4, 5, 12));
+            s[2] = pick4(w1, w2, JPGPU_SEL(2, 3, 4, 12));
+            s[3] = w2 >> 8;
+        }
+        uint32_t px[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) px[j] = color_pixel(kind, s[j], kf);
+        if constexpr (fmt_is_rgb_planes(FMT)) {
+            const uint32_t lo_rg = pick4(px[0], px[1], JPGPU_SEL(0, 4, 1, 5)), hi_rg = pick4(px[2], px[3], JPGPU_SEL(0, 4, 1, 5));
+            const uint32_t r = pick4(lo_rg, hi_rg, JPGPU_SEL(0, 1, 4, 5)), gr = pick4(lo_rg, hi_rg, JPGPU_SEL(2, 3, 6, 7));
+            const uint32_t b = pick4(pick4(px[0], px[1], JPGPU_SEL(2, 6, 12, 12)), pick4(px[2], px[3], JPGPU_SEL(2, 6, 12, 12)), JPGPU_SEL(0, 1, 4, 5));
+            const uint64_t plane = g.pixels * kSampleBytes, at = q * 4 * kSampleBytes;
+            store_plane4<FMT>(dst + at, r, aff.scale[0], aff.bias[0]);
+            store_plane4<FMT>(dst + plane + at, gr, aff.scale[1], aff.bias[1]);
+            store_plane4<FMT>(dst + 2 * plane + at, b, aff.scale[2], aff.bias[2]);
+        } else if constexpr (FMT == kFmtRgbaU8) {
+            *reinterpret_cast<uint4 *>(dst + q * 16) = uint4{px[0] | 0xFF000000u, px[1] | 0xFF000000u, px[2] | 0xFF000000u, px[3] | 0xFF000000u};
+        } else {  // four pixels -> three dwords
+            uint32_t *d = reinterpret_cast<uint32_t *>(dst + q * 12);
+            d[0] = pick4(px[0], px[1], JPGPU_SEL(0, 1, 2, 4));
+            d[1] = pick4(px[1], px[2], JPGPU_SEL(1, 2, 4, 5));
+            d[2] = pick4(px[2], px[3], JPGPU_SEL(2, 4, 5, 6));
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_color_convert(hipStream_t stream, const uint8_t *scratch, uint8_t *out, const ColorImage *images, int n_images, uint64_t max_pixels,
+                                int format, const YccRgbFactors &kf, const OutputAffine &aff) {
+    if (n_images <= 0) return hipSuccess;
+    if (!fmt_is_rgb(format)) return hipErrorInvalidValue;
+    const uint32_t bx = (uint32_t)std::min<uint64_t>((max_pixels / 4 + 1 + 255) / 256, 4096);
+    for (int base = 0; base < n_images; base += 65535) {  // grid.y limit
+        const dim3 grid(bx, (uint32_t)std::min(n_images - base, 65535));
+        switch (format) {
+        case kFmtRgbU8: hipLaunchKernelGGL(color_convert_kernel<kFmtRgbU8>, grid, dim3(256), 0, stream, scratch, out, images + base, kf, aff); break;
+        case kFmtRgbaU8: hipLaunchKernelGGL(color_convert_kernel<kFmtRgbaU8>, grid, dim3(256), 0, stream, scratch, out, images + base, kf, aff); break;
+        case kFmtRgbPlanarU8: hipLaunchKernelGGL(color_convert_kernel<kFmtRgbPlanarU8>, grid, dim3(256), 0, stream, scratch, out, images + base, kf, aff); break;
+        case kFmtRgbPlanarF16: hipLaunchKernelGGL(color_convert_kernel<kFmtRgbPlanarF16>, grid, dim3(256), 0, stream, scratch, out, images + base, kf, aff); break;
+        default: hipLaunchKernelGGL(color_convert_kernel<kFmtRgbPlanarF32>, grid, dim3(256), 0, stream, scratch, out, images + base, kf, aff); break;
+        }
+    }
+    return hipGetLastError();
+}
+
+}  // namespace jpgpu

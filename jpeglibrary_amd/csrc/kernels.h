@@ -109,6 +109,18 @@ hipError_t launch_expand_handoff(hipStream_t stream, const int16_t *coefs, int16
 hipError_t launch_dispose_pass(hipStream_t stream, int16_t *coefs, const DisposeJob *jobs, int n_jobs, uint32_t max_blocks, const DevQuantTable *quant_pool);
 hipError_t launch_ycc_to_rgb(hipStream_t stream, const uint8_t *src, uint8_t *dst, uint64_t n_pixels, int comps, int bpp, const YccRgbFactors &kf,
                              int sample_bytes = 1, const OutputAffine &aff = kOutputAffineIdentity);
+// K3C (k3c_color.hip): the images of kind RGB, CMYK and YCCK (JPGPU_COLOR_FILE) from the INTERLEAVED_U8 samples K3's generic class left in
+// `scratch` to the batch's RGB format in `out` -- ONE launch for all of them, a descriptor per image.  src_off and dst_off are multiples of
+// 256; the scratch slot holds pixels * (kind == kColorRgb ? 3 : 4) bytes, the output pixels * 3 (RGBA_U8: 4) samples.  max_pixels: the
+// largest `pixels` among the descriptors.  aff: the affine step of RGB_PLANAR_F16 / _F32.
+struct ColorImage {
+    uint64_t src_off, dst_off;  // bytes into `scratch` / `out`
+    uint64_t pixels;            // of the image, or of its window
+    uint32_t kind;              // ColorKind: kColorRgb, kColorCmyk or kColorYcck
+    uint32_t reserved;
+};
+hipError_t launch_color_convert(hipStream_t stream, const uint8_t *scratch, uint8_t *out, const ColorImage *images, int n_images, uint64_t max_pixels,
+                                int format, const YccRgbFactors &kf, const OutputAffine &aff);
 
 // Waves per workgroup of the POOLED form of the K2S final pass (k2s_subseq.hip: runs of scans that stage the same tables; one workgroup per CU, every wave takes the
 // next 64 lanes from a counter): 10 waves + 4 tables fill a CU's LDS.  Runs shorter than kSubFinalPoolMinChunks waves, and runs

@@ -1,6 +1,7 @@
 // tools/ingest_host_check.cpp -- the parts of the ingest that need no device (jpeglibrary_amd/csrc/ingest_host.h), run on the CPU under the
 // host sanitizers: FileSegs::gather and FileSegs::at against a byte-serial model over awkward segment lists, and cut_stage_pieces
-// (a piece never crosses a slot of the staging ring, never exceeds kStagePieceMax, the pieces tile the range in order).
+// (a piece never crosses a slot of the staging ring, never exceeds kStagePieceMax, the pieces tile the range in order), and the colour rule
+// (note_color_marker reads exactly the payload it is given; color_kind_of row by row).
 //
 //     make -C tools ingest_host_check && tools/ingest_host_check
 //
@@ -90,6 +91,31 @@ int main() {
                 check_cut(nullptr, dst, n, slot);
             }
     }
+    // the colour rule: payloads allocated at their exact length, so a read behind one is caught
+    auto marker = [](ColorMarkers &m, int code, const char *tag, size_t len, int at11) {
+        std::vector<uint8_t> p(len);
+        for (size_t i = 0; i < len && i < 5; i++) p[i] = (uint8_t)tag[i];
+        if (len > 11) p[11] = (uint8_t)at11;
+        note_color_marker(m, code, p.data(), len);
+    };
+    ColorMarkers m;
+    marker(m, 0xEE, "Adobe", 11, 0);  // too short: no transform byte
+    marker(m, 0xE0, "JFIF", 13, 0);
+    marker(m, 0xEE, "Adobf", 12, 0);
+    marker(m, 0xE1, "Adobe", 12, 0);
+    note_color_marker(m, 0xEE, nullptr, 0);
+    CHECK(!m.saw_jfif && m.adobe_transform == -1);
+    const uint8_t rgb[4] = {0x52, 0x47, 0x42, 0}, ycc[4] = {1, 2, 3, 4};
+    CHECK(color_kind_of(8, 1, ycc, m) == JPGPU_COLOR_KIND_GRAY && color_kind_of(8, 3, ycc, m) == JPGPU_COLOR_KIND_YCBCR);
+    CHECK(color_kind_of(8, 3, rgb, m) == JPGPU_COLOR_KIND_RGB && color_kind_of(8, 3, nullptr, m) == JPGPU_COLOR_KIND_YCBCR);
+    CHECK(color_kind_of(8, 4, ycc, m) == JPGPU_COLOR_KIND_CMYK);
+    CHECK(color_kind_of(8, 2, ycc, m) == -1 && color_kind_of(8, 5, ycc, m) == -1 && color_kind_of(12, 3, ycc, m) == -1 && color_kind_of(12, 4, ycc, m) == -1);
+    marker(m, 0xEE, "Adobe", 12, 2);
+    CHECK(m.adobe_transform == 2 && color_kind_of(8, 4, ycc, m) == JPGPU_COLOR_KIND_YCCK && color_kind_of(8, 3, rgb, m) == JPGPU_COLOR_KIND_YCBCR);
+    marker(m, 0xEE, "Adobe", 14, 0);  // the last one wins
+    CHECK(m.adobe_transform == 0 && color_kind_of(8, 4, ycc, m) == JPGPU_COLOR_KIND_CMYK && color_kind_of(8, 3, ycc, m) == JPGPU_COLOR_KIND_RGB);
+    marker(m, 0xE0, "JFIF", 14, 0);
+    CHECK(m.saw_jfif && color_kind_of(8, 3, rgb, m) == JPGPU_COLOR_KIND_YCBCR && color_kind_of(8, 4, ycc, m) == JPGPU_COLOR_KIND_CMYK);
     printf("ok\n");
     return 0;
 }
