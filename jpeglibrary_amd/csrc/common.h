@@ -27,9 +27,12 @@ struct alignas(16) DevHuffTable {
 static_assert(sizeof(DevHuffTable) % 16 == 0, "DevHuffTable must be a multiple of 16 bytes");
 
 // Quantization table, zig-zag order like JpegQuantizationTable.Elements (ref: JpegQuantizationTable.cs:47).
+// qf: the same table as K3's transform multiplies by it -- (float)q / 8 in the pair order of k3_quant_order.h, made once where the entry is built.
 struct alignas(16) DevQuantTable {
     uint16_t q[64];
+    float qf[64];
 };
+static_assert(sizeof(DevQuantTable) == 128 + 256, "DevQuantTable has no padding: the pool finds duplicates with memcmp");
 
 struct DevScanComponent {
     uint8_t component_index;  // index into the frame's component list (WriteBlock's componentIndex)

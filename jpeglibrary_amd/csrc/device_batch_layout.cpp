@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "k3_quant_order.h"
 #include "kernels.h"
 
 namespace jpgpu {
@@ -256,6 +257,7 @@ uint16_t DeviceBatch::huff_index(UploadPlan &p, const HuffTable &t) {
 uint16_t DeviceBatch::quant_index(const QuantTable &t) {
     DevQuantTable d;
     memcpy(d.q, t.elements, sizeof d.q);
+    k3_quant_pair_floats(d.q, d.qf);
     for (size_t i = 0; i < quant_pool_.size(); i++)
         if (memcmp(&quant_pool_[i], &d, sizeof d) == 0) return (uint16_t)i;
     quant_pool_.push_back(d);

@@ -15,6 +15,7 @@
 #include "encode_kernels.h"
 #include "kernels_device.h"
 #include "k3_index_math.h"
+#include "k3_quant_order.h"
 #include "k3_store_quads.h"
 
 namespace jpgpu {
@@ -71,25 +72,31 @@ __device__ constexpr uint32_t kRecip16[kMaxBlocksPerMcu + 1] = {0, 65536, 32768,
         y4 = a3 - mb3;                                                  \
     }
 
-// DequantizeBlockAndUnZigZag for one block (ref: ScanDecoder/JpegScanDecoder.cs:50-62).
-// c_lds: this lane's 64 int16 coefficients (zig-zag) in the swizzled LDS staging (8 chunks of 16 B, chunk p at
-// c_lds + ((p ^ swz) * 16)); q_lds: 64 uint16 quantisers (zig-zag) of the block's component.
-__device__ __forceinline__ void block_dequant(const uint8_t *c_lds, uint32_t swz, const uint16_t *q_lds, float (&f)[64]) {
+constexpr bool zig_of_nat_inverts_nat() {
+    for (int k = 0; k < 64; k++)
+        if (kZigOfNat[kNat[k]] != k) return false;
+    return true;
+}
+static_assert(zig_of_nat_inverts_nat(), "k3_quant_order.h's kZigOfNat is the inverse of kNat");
+
+// This lane's 64 int16 coefficients (zig-zag) out of the swizzled LDS staging (8 chunks of 16 B, chunk p at c_lds + ((p ^ swz) * 16)),
+// as they lie: word w holds coefficients 2 * w and 2 * w + 1.  They are held packed across the staging barrier -- 32 registers, not the
+// 64 of a dequantised block -- and dequantised inside the transform (block_idct).
+__device__ __forceinline__ void block_load(const uint8_t *c_lds, uint32_t swz, uint32_t (&cw)[32]) {
 #pragma unroll
     for (int piece = 0; piece < 8; piece++) {
         const uint4 cv = *reinterpret_cast<const uint4 *>(c_lds + ((piece ^ swz) * 16));
-        const uint4 qv = reinterpret_cast<const uint4 *>(q_lds)[piece];
-        const uint32_t cw[4] = {cv.x, cv.y, cv.z, cv.w};
-        const uint32_t qw[4] = {qv.x, qv.y, qv.z, qv.w};
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int k = piece * 8 + j;
-            const uint32_t w = cw[j >> 1], q = qw[j >> 1];
-            const int32_t c = (j & 1) ? ((int32_t)w >> 16) : (int32_t)(int16_t)(w & 0xFFFF);
-            const int32_t qq = (j & 1) ? (int32_t)(q >> 16) : (int32_t)(q & 0xFFFF);
-            f[kNat[k]] = (float)(qq * c);  // ushort * short -> int -> float
-        }
+        cw[piece * 4] = cv.x;
+        cw[piece * 4 + 1] = cv.y;
+        cw[piece * 4 + 2] = cv.z;
+        cw[piece * 4 + 3] = cv.w;
     }
+}
+// coefficient at natural position n of a block held as packed words, as a float (sign-extending word select: v_cvt_f32_i32_sdwa)
+__device__ __forceinline__ float coef_at(const uint32_t (&cw)[32], int n) {
+    const int k = kZigOfNat[n];
+    const uint32_t w = cw[k >> 1];
+    return (float)((k & 1) ? ((int32_t)w >> 16) : (int32_t)(int16_t)(w & 0xFFFFu));
 }
 
 typedef float float2v __attribute__((ext_vector_type(2)));
@@ -133,33 +140,24 @@ __device__ __forceinline__ void idct8(T &y0, T &y1, T &y2, T &y3, T &y4, T &y5, 
     y4 = a3 - mb3;
 }
 
-// TransformIDCT + ShiftDataLevel (ref: FastFloatingPointDCT.cs:54-70, ScanDecoder/JpegScanDecoder.cs:64-73) on a
-// dequantised block held in registers, two lanes of the butterfly per instruction.
+// TransformIDCT + ShiftDataLevel (ref: FastFloatingPointDCT.cs:54-70, ScanDecoder/JpegScanDecoder.cs:64-73), two lanes of the
+// butterfly per instruction, on a block that carries the transform's closing 1/8 (MultiplyInplace(C_0_125)) already: the dequantised
+// coefficients times 2^-3.  A power of two scales every product, sum and rounding of the two passes with it (nothing underflows:
+// DESIGN.md 3, K3), so the results are the reference's, bit for bit, without the 64 multiplications at the end.
+// Pass 1 is the caller's: the 1-D IDCT along each ROW (the reference transposes, runs the column butterfly, transposes back);
+// a[r2][c] holds rows 2*r2 and 2*r2+1 of column c.
 // out[r * 4 + c2] = samples (r, 2*c2) | (r, 2*c2 + 1) << 16 as int16: (short)(Round(v) + levelShift), unclamped.
-__device__ __forceinline__ void block_idct(const float (&f)[64], int32_t level_shift, uint32_t (&out)[32]) {
-#if defined(JPGPU_K3_PRICE)
-    // (pricing build only, tools/trace/ab_k3_price.sh: the transform left out -- wrong samples, the time of everything else)
-#pragma unroll
-    for (int i = 0; i < 32; i++) out[i] = (__builtin_bit_cast(uint32_t, f[2 * i]) >> 16) | (__builtin_bit_cast(uint32_t, f[2 * i + 1]) & 0xFFFF0000u) | (uint32_t)level_shift;
-    return;
-#endif
-    // pass 1: 1-D IDCT along each ROW (the reference transposes, runs the column butterfly, transposes back);
-    // a[r2][c] holds rows 2*r2 and 2*r2+1 of column c
-    float2v a[4][8];
-#pragma unroll
-    for (int r2 = 0; r2 < 4; r2++)
-#pragma unroll
-        for (int c = 0; c < 8; c++) a[r2][c] = float2v{f[(2 * r2) * 8 + c], f[(2 * r2 + 1) * 8 + c]};
-#pragma unroll
-    for (int r2 = 0; r2 < 4; r2++) idct8(a[r2][0], a[r2][1], a[r2][2], a[r2][3], a[r2][4], a[r2][5], a[r2][6], a[r2][7]);
+__device__ __forceinline__ void idct_columns_out(const float2v (&a)[4][8], int32_t level_shift, uint32_t (&out)[32]) {
     // pass 2: along each COLUMN; b[r][c2] holds columns 2*c2 and 2*c2+1 of row r
     float2v b[8][4];
 #pragma unroll
     for (int r2 = 0; r2 < 4; r2++)
 #pragma unroll
         for (int c2 = 0; c2 < 4; c2++) {
-            b[2 * r2][c2] = float2v{a[r2][2 * c2].x, a[r2][2 * c2 + 1].x};
-            b[2 * r2 + 1][c2] = float2v{a[r2][2 * c2].y, a[r2][2 * c2 + 1].y};
+            // b[2 * r2][c2] = {a[r2][2 * c2].x, a[r2][2 * c2 + 1].x}, b[2 * r2 + 1][c2] = the two .y: one two-register move each (the low
+            // halves of both sources, the high halves of both), where hipcc builds the pairs from single v_mov_b32
+            asm("v_pk_mov_b32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,0]" : "=v"(b[2 * r2][c2]) : "v"(a[r2][2 * c2]), "v"(a[r2][2 * c2 + 1]));
+            asm("v_pk_mov_b32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,1]" : "=v"(b[2 * r2 + 1][c2]) : "v"(a[r2][2 * c2]), "v"(a[r2][2 * c2 + 1]));
         }
 #pragma unroll
     for (int c2 = 0; c2 < 4; c2++) idct8(b[0][c2], b[1][c2], b[2][c2], b[3][c2], b[4][c2], b[5][c2], b[6][c2], b[7][c2]);
@@ -168,7 +166,7 @@ __device__ __forceinline__ void block_idct(const float (&f)[64], int32_t level_s
     for (int r = 0; r < 8; r++)
 #pragma unroll
         for (int c2 = 0; c2 < 4; c2++) {
-            const float2v v = b[r][c2] * 0.1250f;                  // MultiplyInplace(C_0_125)
+            const float2v v = b[r][c2];
             // MathF.Round: half to even (v_rndne_f32).  Outside int32 the conversion saturates (v_cvt_i32_f32), where the x64
             // reference gives INT_MIN: a fence, pinned by tests/test_idct_stage_gpu.py
             const int32_t x = (int32_t)__builtin_rintf(v.x);
@@ -180,6 +178,49 @@ __device__ __forceinline__ void block_idct(const float (&f)[64], int32_t level_s
         }
 }
 
+// DequantizeBlockAndUnZigZag (ref: ScanDecoder/JpegScanDecoder.cs:50-62) + the transform above on a block held as packed words
+// (block_load).  q_lds: the component's table as floats that carry the 1/8, in pair order (k3_quant_order.h).  The reference
+// multiplies ushort * short as integers and converts the product; (float)c * qf rounds the same exact product c * q / 8 once
+// (|c| <= 2^15 and q / 8 < 2^13 are exact floats), so the two agree bit for bit.
+// Row pair by row pair, directly in front of its pass-1 butterfly: sixteen conversions, eight packed multiplications whose
+// results are the register pairs the butterfly takes -- a block dequantised as a whole first costs moves and registers.
+__device__ __forceinline__ void block_idct(const uint32_t (&cw)[32], const float *q_lds, int32_t level_shift, uint32_t (&out)[32]) {
+    float2v a[4][8];
+#pragma unroll
+    for (int r2 = 0; r2 < 4; r2++) {
+#pragma unroll
+        for (int c = 0; c < 8; c += 2) {
+            const float4 q = reinterpret_cast<const float4 *>(q_lds)[r2 * 4 + (c >> 1)];
+            a[r2][c] = float2v{coef_at(cw, (2 * r2) * 8 + c), coef_at(cw, (2 * r2 + 1) * 8 + c)} * float2v{q.x, q.y};
+            a[r2][c + 1] = float2v{coef_at(cw, (2 * r2) * 8 + c + 1), coef_at(cw, (2 * r2 + 1) * 8 + c + 1)} * float2v{q.z, q.w};
+        }
+#if !defined(JPGPU_K3_PRICE)
+        idct8(a[r2][0], a[r2][1], a[r2][2], a[r2][3], a[r2][4], a[r2][5], a[r2][6], a[r2][7]);
+#endif
+    }
+#if defined(JPGPU_K3_PRICE)
+    // (pricing build only, tools/trace/ab_k3_price.sh: the butterflies left out -- wrong samples, the time of everything else)
+#pragma unroll
+    for (int i = 0; i < 32; i++)
+        out[i] = (__builtin_bit_cast(uint32_t, a[i >> 3][i & 7].x) >> 16) | (__builtin_bit_cast(uint32_t, a[i >> 3][i & 7].y) & 0xFFFF0000u) | (uint32_t)level_shift;
+    return;
+#endif
+    idct_columns_out(a, level_shift, out);
+}
+
+// The same on a block dequantised the reference's way, f[natural position] = (float)(q * c) (dispose_pass_kernel): the 1/8 is
+// multiplied in here.
+__device__ __forceinline__ void block_idct_dequantised(const float (&f)[64], int32_t level_shift, uint32_t (&out)[32]) {
+    float2v a[4][8];
+#pragma unroll
+    for (int r2 = 0; r2 < 4; r2++) {
+#pragma unroll
+        for (int c = 0; c < 8; c++) a[r2][c] = float2v{f[(2 * r2) * 8 + c], f[(2 * r2 + 1) * 8 + c]} * 0.125f;
+        idct8(a[r2][0], a[r2][1], a[r2][2], a[r2][3], a[r2][4], a[r2][5], a[r2][6], a[r2][7]);
+    }
+    idct_columns_out(a, level_shift, out);
+}
+
 // signed clamp of two int16 samples to [0, 255] (JpegBufferOutputWriter8Bit.ClampTo8Bit): v_pk_max_i16 + v_pk_min_i16
 __device__ __forceinline__ uint32_t clamp2_u8(uint32_t pk) {
     short2v v = __builtin_bit_cast(short2v, pk);
@@ -187,9 +228,16 @@ __device__ __forceinline__ uint32_t clamp2_u8(uint32_t pk) {
     v = __builtin_elementwise_min(v, short2v{255, 255});
     return __builtin_bit_cast(uint32_t, v);
 }
-// four clamped samples (two packed pairs) -> four bytes
+// the same clamp of both halves and the packing into bytes 0 and 1 in one instruction (v_sat_pk_u8_i16: {sat_u8(S.i16[1]), sat_u8(S.i16[0])};
+// no builtin names it; the upper half of the result is not used)
+__device__ __forceinline__ uint32_t sat2_u8(uint32_t pk) {
+    uint32_t r;
+    asm("v_sat_pk_u8_i16 %0, %1" : "=v"(r) : "v"(pk));
+    return r;
+}
+// four clamped samples (two packed pairs) -> four bytes: three instructions
 __device__ __forceinline__ uint32_t pack4_u8(uint32_t pk01, uint32_t pk23) {
-    return __builtin_amdgcn_perm(clamp2_u8(pk23), clamp2_u8(pk01), 0x06040200u);  // bytes 0,2 of pk01 then 0,2 of pk23
+    return __builtin_amdgcn_perm(sat2_u8(pk23), sat2_u8(pk01), 0x05040100u);  // bytes 0,1 of pk01's then 0,1 of pk23's
 }
 // INTERLEAVED_U8_SCALED: the sample-to-byte step of the reference's other two stock writers, chosen by the frame's precision P
 // the way apps/JpegDecode/DecodeAction.cs:41-54 chooses the writer.  Wave-uniform: the terms live in scalar registers, derived from DevScan::precision.
@@ -752,11 +800,11 @@ __device__ __forceinline__ void idct_output_body(
     OutputAffine aff = kOutputAffineIdentity) {
     constexpr int CONV = FMT == kFmtRgbU8 ? 3 : (FMT == kFmtRgbaU8 ? 4 : (FMT == kFmtRgbPlanarU8 ? kConvPlanar : (FMT == kFmtRgbPlanarF16 ? kConvPlanarF16 : (FMT == kFmtRgbPlanarF32 ? kConvPlanarF32 : 0))));  // fused YCbCr -> RGB(A), fast layouts and gray only
     constexpr bool kSampleBytes = fmt_is_sample_bytes(FMT);  // INTERLEAVED_U8 / _SCALED: one path, two sample-to-byte steps
-    __shared__ __attribute__((aligned(16))) uint8_t sh_all[kIdctThreads * 128 + kIdctThreads * 64 + kMaxScanComponents * 128 + (SPLIT && !PRE ? 64 : 0)];
+    __shared__ __attribute__((aligned(16))) uint8_t sh_all[kIdctThreads * 128 + kIdctThreads * 64 + kMaxScanComponents * 256 + (SPLIT && !PRE ? 64 : 0)];
     uint8_t *sh = sh_all;
     uint8_t *sh_px = sh_all + kIdctThreads * 128;
-    uint16_t(*sh_q)[64] = reinterpret_cast<uint16_t(*)[64]>(sh_all + kIdctThreads * 128 + kIdctThreads * 64);
-    uint8_t *sh_flag = sh_all + kIdctThreads * 128 + kIdctThreads * 64 + kMaxScanComponents * 128;  // split scans: two sets of eight flag words
+    float(*sh_q)[64] = reinterpret_cast<float(*)[64]>(sh_all + kIdctThreads * 128 + kIdctThreads * 64);  // DevQuantTable::qf of the scan components
+    uint8_t *sh_flag = sh_all + kIdctThreads * 128 + kIdctThreads * 64 + kMaxScanComponents * 256;  // split scans: two sets of eight flag words
 
     const IdctWork wk = work[blockIdx.x];
     const DevScan &s = scans[wk.scan];
@@ -799,11 +847,11 @@ __device__ __forceinline__ void idct_output_body(
         if (first_mcu >= range_end) return;
     }
 
-    // quantisation tables of the scan components
-    if (tid < (uint32_t)s.scan_components * 32) {
-        const uint32_t c = tid >> 5, i = tid & 31;
-        reinterpret_cast<uint32_t *>(sh_q[c])[i] =
-            reinterpret_cast<const uint32_t *>(quant_pool[s.quant_pool[s.comp[c].quant_slot]].q)[i];
+    // quantisation tables of the scan components: the floats the host made of them (they carry the transform's 1/8, in pair order)
+    static_assert(kMaxScanComponents * 64 <= kIdctThreads, "one lane per table entry");
+    if (tid < (uint32_t)s.scan_components * 64) {
+        const uint32_t c = tid >> 6, i = tid & 63;
+        sh_q[c][i] = quant_pool[s.quant_pool[s.comp[c].quant_slot]].qf[i];
     }
 
     const uint32_t mcu_local = tid / bpm;
@@ -1033,8 +1081,8 @@ __device__ __forceinline__ void idct_output_body(
     // and the later component's over them (WriteBlock by ComponentIndex, :118-134), so only the later ones reach the output
     bool writes = have_block && ((s.shadow_mask >> ci_early) & 1u) == 0;
 
-    // phase B1: dequantise this lane's block out of the staging into registers
-    float f[64];
+    // phase B1: this lane's block out of the staging into registers, as packed words
+    uint32_t cw[32];  // int16 coefficient pairs, zig-zag
     uint32_t px[32];  // int16 sample pairs
     if (PRE) {
         if (have_block) {
@@ -1056,7 +1104,7 @@ __device__ __forceinline__ void idct_output_body(
         uint32_t t_ = tid;
         if (kPerTile) asm volatile("" : "+v"(t_));
         if (split && sp_fast) t_ = sp_own_block(t_);  // (the staging is in slot order)
-        if (have_block) block_dequant(sh + t_ * 128, (t_ >> 1) & 7, sh_q[ci_early], f);
+        if (have_block) block_load(sh + t_ * 128, (t_ >> 1) & 7, cw);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every lane holds its coefficients: the staging can be refilled
@@ -1067,9 +1115,9 @@ __device__ __forceinline__ void idct_output_body(
     } else if (have_next) dma_tile(next_first, sp_i0 + sp_ipt, hi_next);  // in flight during the whole transform below
     hi_next = 0;  // (dead from here to the flag bytes behind the transform)
 
-    // phase B2: IDCT entirely in registers
-    if (!PRE && have_block) block_idct(f, (int32_t)s.level_shift, px);
-    // split scans: the flag bytes of the tile after the next one, fetched behind the transform (f[] is dead) and waited for where the DMA is
+    // phase B2: dequantisation + IDCT entirely in registers
+    if (!PRE && have_block) block_idct(cw, sh_q[ci_early], (int32_t)s.level_shift, px);
+    // split scans: the flag bytes of the tile after the next one, fetched behind the transform (its registers are dead) and waited for where the DMA is
     uint32_t sp_fb = 0, sp_at = 0;
     const bool sp_ahead = split && next_first + mcus_per_tile < range_end;
     if (sp_ahead) sp_load_flag(next_first + mcus_per_tile, sp_i0 + 2 * sp_ipt, sp_fb, sp_at);
@@ -1118,8 +1166,8 @@ __device__ __forceinline__ void idct_output_body(
     }
     bool synced = false;
     // the MCU's place in the image is only needed from here on: computed behind the transform (an empty asm the compiler may not
-    // move across keeps it from being hoisted in front of it), two registers fewer are alive while the 64 + 32 of the
-    // transform are -- what four of the sixteen variants spilled (profiles/r03_kernel_resources.txt)
+    // move across keeps it from being hoisted in front of it), two registers fewer are alive while those of the
+    // transform are -- what four of the sixteen variants spilled when it held 64 + 32 (profiles/r03_kernel_resources.txt)
     uint32_t ml_late = mcu_local, b_late = b;
     asm volatile("" : "+v"(ml_late), "+v"(b_late));
     const uint32_t mcu_wraps = k3_line_wraps(pos.gx0 + ml_late, mpl, line_recip);  // (lines below the tile's first MCU line: no division per lane)
@@ -1352,7 +1400,7 @@ __global__ __launch_bounds__(64) void dispose_pass_kernel(int16_t *__restrict__ 
             const int32_t cv = (k & 1) ? ((int32_t)w[k >> 1] >> 16) : (int32_t)(int16_t)(w[k >> 1] & 0xFFFFu);
             f[kNat[k]] = (float)((int32_t)q[k] * cv);  // ushort * short -> int -> float (DequantizeBlockAndUnZigZag)
         }
-        block_idct(f, (int32_t)j.level_shift, w);
+        block_idct_dequantised(f, (int32_t)j.level_shift, w);
     }
 #pragma unroll
     for (int i = 0; i < 8; i++) reinterpret_cast<uint4 *>(blk)[i] = make_uint4(w[i * 4], w[i * 4 + 1], w[i * 4 + 2], w[i * 4 + 3]);
