@@ -508,7 +508,7 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
     const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed, split_always = p.sw.handoff_set;
     const int k3_class = fmt_is_interleaved(format_) && !color_kind_by_file(img.color_kind) ? idct_layout_class(s) : 0;
     if (split_wanted && job.kind == kScanSequential && s.dri != 0 && img.jobs.size() == 1 && !img.replay_skip && s.total_mcus > 0 &&
-        s.blocks_per_mcu != 0 && idct_split_supported(format_, k3_class) &&
+        s.blocks_per_mcu != 0 && k3_variant(format_, k3_class, kK3Split).exists &&
         // The planes pay where few blocks reach into coefficients 32..63; all that is known of that in front of the decode is
         // how many bytes of entropy data a block has.  Q75 content has 5.4 (3 % of the blocks flagged; the step 4.9 % faster),
         // Q85 8.7, Q90 12.3 (66 % flagged: K2 gains 0.12 ms, K3 loses 0.19: 1.8 % slower) -- RESULTS.md, first section.
@@ -607,7 +607,7 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
             list.push_back({(uint32_t)j, first, std::min(run, listed - first), mcus_per_wg});
         // the caller's canvas under a whole-pixel layout: the MCU a failing scan stops in is written block by block
         if (keep_canvas_ && job.kind == kScanSequential && fmt_is_sample_bytes(format_) &&
-            cls >= 1 && cls <= 3)  // (kLayYccH1V1 / H2V1 / H2V2, k3_idct.hip)
+            (cls == kLayYccH1V1 || cls == kLayYccH2V1 || cls == kLayYccH2V2))
             p.idct_partial.push_back({(uint32_t)j, kIdctPartialMcu, 1, generic_per_wg});
     }
 }

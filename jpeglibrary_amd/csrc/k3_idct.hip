@@ -9,12 +9,14 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <utility>
 
 #include "common.h"
 #include "kernels.h"
 #include "encode_kernels.h"
 #include "kernels_device.h"
 #include "k3_index_math.h"
+#include "k3_pixel.h"
 #include "k3_quant_order.h"
 #include "k3_store_quads.h"
 
@@ -29,48 +31,12 @@ __device__ constexpr uint8_t kNat[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24,
                                          41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                          30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
-// The 8-point butterfly of IDCT8x4_LeftPart/RightPart (ref: FastFloatingPointDCT.cs:79-127), one column.
-// Operation order and parenthesisation are normative.
 // ceil(65536 / n), n = 1 .. kMaxBlocksPerMcu (the split form's block -> MCU arithmetic)
 // The split form divides by multiplying (idct_output_body: sp_rb, sp_rd, sp_rw); the ranges those reciprocals are exact for rest on these:
 // a tile is at most 256 blocks (block and MCU numbers inside it < 256, its lines < 128) of at most 16 per MCU.
 static_assert(kIdctBlocksPerWg == 256, "the split form's reciprocals are exact for tiles of up to 256 blocks");
 static_assert(kMaxBlocksPerMcu == 16, "kRecip16 and the 16-bit reciprocals of the split form cover 1..16 blocks per MCU");
 __device__ constexpr uint32_t kRecip16[kMaxBlocksPerMcu + 1] = {0, 65536, 32768, 21846, 16384, 13108, 10923, 9363, 8192, 7282, 6554, 5958, 5462, 5042, 4682, 4370, 4096};
-
-#define JPGPU_IDCT8(y0, y1, y2, y3, y4, y5, y6, y7)                     \
-    {                                                                   \
-        float mz0 = y1 + y7;                                            \
-        float mz2 = y3 + y7;                                            \
-        float mz1 = y3 + y5;                                            \
-        float mz3 = y1 + y5;                                            \
-        float mz4 = (mz0 + mz1) * 1.175875602f;                         \
-        mz2 = (mz2 * -1.961570560f) + mz4;                              \
-        mz3 = (mz3 * -0.390180644f) + mz4;                              \
-        mz0 = mz0 * -0.899976223f;                                      \
-        mz1 = mz1 * -2.562915447f;                                      \
-        const float mb3 = ((y7 * 0.298631336f) + mz0) + mz2;            \
-        const float mb2 = ((y5 * 2.053119869f) + mz1) + mz3;            \
-        const float mb1 = ((y3 * 3.072711026f) + mz1) + mz2;            \
-        const float mb0 = ((y1 * 1.501321110f) + mz0) + mz3;            \
-        mz4 = (y2 + y6) * 0.541196100f;                                 \
-        mz0 = y0 + y4;                                                  \
-        mz1 = y0 - y4;                                                  \
-        mz2 = mz4 + (y6 * -1.847759065f);                               \
-        mz3 = mz4 + (y2 * 0.765366865f);                                \
-        const float a0 = mz0 + mz3;                                     \
-        const float a3 = mz0 - mz3;                                     \
-        const float a1 = mz1 + mz2;                                     \
-        const float a2 = mz1 - mz2;                                     \
-        y0 = a0 + mb0;                                                  \
-        y7 = a0 - mb0;                                                  \
-        y1 = a1 + mb1;                                                  \
-        y6 = a1 - mb1;                                                  \
-        y2 = a2 + mb2;                                                  \
-        y5 = a2 - mb2;                                                  \
-        y3 = a3 + mb3;                                                  \
-        y4 = a3 - mb3;                                                  \
-    }
 
 constexpr bool zig_of_nat_inverts_nat() {
     for (int k = 0; k < 64; k++)
@@ -81,7 +47,7 @@ static_assert(zig_of_nat_inverts_nat(), "k3_quant_order.h's kZigOfNat is the inv
 
 // This lane's 64 int16 coefficients (zig-zag) out of the swizzled LDS staging (8 chunks of 16 B, chunk p at c_lds + ((p ^ swz) * 16)),
 // as they lie: word w holds coefficients 2 * w and 2 * w + 1.  They are held packed across the staging barrier -- 32 registers, not the
-// 64 of a dequantised block -- and dequantised inside the transform (block_idct).
+// 64 of a dequantised block -- and dequantised inside the transform (block_idct).  (swz = 0: a block as it lies in the store.)
 __device__ __forceinline__ void block_load(const uint8_t *c_lds, uint32_t swz, uint32_t (&cw)[32]) {
 #pragma unroll
     for (int piece = 0; piece < 8; piece++) {
@@ -98,10 +64,6 @@ __device__ __forceinline__ float coef_at(const uint32_t (&cw)[32], int n) {
     const uint32_t w = cw[k >> 1];
     return (float)((k & 1) ? ((int32_t)w >> 16) : (int32_t)(int16_t)(w & 0xFFFFu));
 }
-
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef short short2v __attribute__((ext_vector_type(2)));
-typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
 
 // The 8-point butterfly of IDCT8x4_LeftPart/RightPart (ref: FastFloatingPointDCT.cs:79-127) on T = float or a pair of
 // floats (two independent columns at once: v_pk_add_f32 / v_pk_mul_f32, each component one IEEE operation, never fused).
@@ -286,37 +248,11 @@ __device__ __forceinline__ uint32_t expand2_u8(uint32_t pk, const ScaleTo8 &k) {
     const ushort2v hi = r << __builtin_bit_cast(ushort2v, k.rem2);
     return __builtin_bit_cast(uint32_t, hi) | (__builtin_bit_cast(uint32_t, r) & k.mask2);
 }
-// byte gather from the 8 bytes {lo (indices 0-3), hi (indices 4-7)}: one v_perm_b32
-__device__ __forceinline__ uint32_t pick4(uint32_t lo, uint32_t hi, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
-#define JPGPU_SEL(a, b, c, d) ((uint32_t)(a) | ((uint32_t)(b) << 8) | ((uint32_t)(c) << 16) | ((uint32_t)(d) << 24))
 
 constexpr int kIdctThreads = 256;
 constexpr uint32_t kPxRowStride = kIdctThreads * 8;  // bytes between sample rows in the LDS pixel tile
 
-// Output layout classes of the INTERLEAVED_U8 format (chosen per scan on the host, see idct_layout_class()).
-enum IdctLayout : int { kLayGeneric = 0, kLayYccH1V1 = 1, kLayYccH2V1 = 2, kLayYccH2V2 = 3, kLayGray = 4, kNumIdctLayouts = 5 };
-
-// ---- YCbCr -> RGB(A) (ref: apps/JpegDecode/JpegYCbCrToRgbConverter.cs:134-206).  The reference looks the terms up in
-// tables built by Init (:66-118); with ReferenceBlackWhite = {0,255,128,255,128,255} the tables are exactly
-//   yTable[i] = i, crRTable[i] = (cr_r * (i-128) + half) >> 16, cbBTable[i] = (cb_b * (i-128) + half) >> 16,
-//   crGTable[i] = cr_g * (i-128), cbGTable[i] = cb_g * (i-128) + half,  and the clamp table is a clamp to [0, 255],
-// so the terms are computed instead of fetched (the factors come from the host, derived like Init derives them).
-struct ChromaTerms {
-    int32_t r, g, b;
-};
-__device__ __forceinline__ ChromaTerms chroma_terms(uint32_t cb_sample, uint32_t cr_sample, const YccRgbFactors &k) {
-    const int32_t cb = (int32_t)cb_sample - 128, cr = (int32_t)cr_sample - 128;
-    ChromaTerms t;
-    t.r = (k.cr_r * cr + 32768) >> 16;
-    t.b = (k.cb_b * cb + 32768) >> 16;
-    t.g = (k.cb_g * cb + 32768 + k.cr_g * cr) >> 16;
-    return t;
-}
-__device__ __forceinline__ uint32_t clamp_u8_i32(int32_t v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
-// one pixel: R | G << 8 | B << 16
-__device__ __forceinline__ uint32_t rgb_pixel(uint32_t y, const ChromaTerms &t) {
-    return clamp_u8_i32((int32_t)y + t.r) | (clamp_u8_i32((int32_t)y + t.g) << 8) | (clamp_u8_i32((int32_t)y + t.b) << 16);
-}
+// (YCbCr -> RGB(A): chroma_terms / rgb_pixel, k3_pixel.h)
 __device__ __forceinline__ uint32_t byte_of(uint32_t lo, uint32_t hi, int i) { return ((i < 4 ? lo : hi) >> (8 * (i & 3))) & 0xFFu; }
 // N pixels (R | G << 8 | B << 16 each) -> interleaved bytes at dst (16-byte aligned for N = 16, 8-byte aligned for N = 8)
 template <int N, int BPP>
@@ -366,13 +302,11 @@ __device__ __forceinline__ void rgb_planes4(uint32_t y0, uint32_t y1, uint32_t y
 }
 
 // RGB_PLANAR_F16 / _F32: the same planes with a wider sample.  A byte u of channel c becomes (float)u * scale[c] + bias[c]: one float32
-// multiply and one float32 add, each rounded to nearest even and never fused (__fmul_rn / __fadd_rn), then for F16 one more rounding to
+// multiply and one float32 add, each rounded to nearest even and never fused (affine_sample, k3_pixel.h), then for F16 one more rounding to
 // nearest even to binary16 (a float -> _Float16 conversion: subnormals kept, overflow to infinity; never the round-toward-zero packed form).
 constexpr int kConvPlanarF16 = 16, kConvPlanarF32 = 32;
 constexpr bool conv_is_planar(int conv) { return conv == kConvPlanar || conv == kConvPlanarF16 || conv == kConvPlanarF32; }
 constexpr uint32_t conv_plane_sample_bytes(int conv) { return conv == kConvPlanarF16 ? 2 : (conv == kConvPlanarF32 ? 4 : 1); }
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float affine_sample(uint32_t u, float scale, float bias) { return __fadd_rn(__fmul_rn((float)u, scale), bias); }
 // N packed bytes of one plane's row (N = 8 or 16: one or two blocks wide; v_cvt_f32_ubyte0..3 unpack them) -> N samples at dst, which is
 // 16-byte aligned: 16 / 32 bytes as F16 (one or two dwordx4 stores), 32 / 64 as F32 (two or four).  Called plane by plane: at most 16 floats
 // are alive.
@@ -392,6 +326,25 @@ __device__ __forceinline__ void store_affine_row(uint8_t *dst, const uint32_t (&
             for (int j = 0; j < 4; j++) h[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(float2v{f[8 * q + 2 * j], f[8 * q + 2 * j + 1]}, half2v));
             *reinterpret_cast<uint4 *>(dst + q * 16) = uint4{h[0], h[1], h[2], h[3]};
         }
+    }
+}
+// One task's row of the three planes (N = 8 or 16 bytes of each, as dwords) at p0, p1, p2: as the bytes they are (RGB_PLANAR_U8; p is 8- / 16-byte
+// aligned), or plane by plane through the affine step
+template <int CONV, int N>
+__device__ __forceinline__ void store_plane_rows(uint8_t *p0, uint8_t *p1, uint8_t *p2, const uint32_t (&r)[N / 4], const uint32_t (&g)[N / 4],
+                                                 const uint32_t (&b)[N / 4], const OutputAffine &aff) {
+    if constexpr (CONV != kConvPlanar) {
+        store_affine_row<CONV, N>(p0, r, aff.scale[0], aff.bias[0]);
+        store_affine_row<CONV, N>(p1, g, aff.scale[1], aff.bias[1]);
+        store_affine_row<CONV, N>(p2, b, aff.scale[2], aff.bias[2]);
+    } else if constexpr (N == 16) {
+        *reinterpret_cast<uint4 *>(p0) = uint4{r[0], r[1], r[2], r[3]};
+        *reinterpret_cast<uint4 *>(p1) = uint4{g[0], g[1], g[2], g[3]};
+        *reinterpret_cast<uint4 *>(p2) = uint4{b[0], b[1], b[2], b[3]};
+    } else {
+        *reinterpret_cast<uint2 *>(p0) = uint2{r[0], r[1]};
+        *reinterpret_cast<uint2 *>(p1) = uint2{g[0], g[1]};
+        *reinterpret_cast<uint2 *>(p2) = uint2{b[0], b[1]};
     }
 }
 
@@ -651,9 +604,7 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
                 const uint2 yv = *reinterpret_cast<const uint2 *>(yrow);  // R = G = B = Y (Cb = Cr = 128 contribute nothing, DecodeAction.cs:57-65)
                 if (CONV != kConvPlanar) {
                     const uint32_t w[2] = {yv.x, yv.y};
-                    store_affine_row<CONV, 8>(line0 + at, w, aff.scale[0], aff.bias[0]);
-                    store_affine_row<CONV, 8>(line1 + at, w, aff.scale[1], aff.bias[1]);
-                    store_affine_row<CONV, 8>(line2 + at, w, aff.scale[2], aff.bias[2]);
+                    store_plane_rows<CONV, 8>(line0 + at, line1 + at, line2 + at, w, w, w, aff);
                     continue;
                 }
                 *reinterpret_cast<uint2 *>(line0 + at) = yv;
@@ -670,15 +621,7 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
                     const ChromaTerms t1 = chroma_terms(byte_of(cv.x, cv.y, 2 * q + 1), byte_of(cv.z, cv.w, 2 * q + 1), kf);
                     rgb_planes4(y4 & 0xFFu, (y4 >> 8) & 0xFFu, (y4 >> 16) & 0xFFu, y4 >> 24, t0, t0, t1, t1, r[q], g[q], bl[q]);
                 }
-                if (CONV != kConvPlanar) {
-                    store_affine_row<CONV, 16>(line0 + at, r, aff.scale[0], aff.bias[0]);
-                    store_affine_row<CONV, 16>(line1 + at, g, aff.scale[1], aff.bias[1]);
-                    store_affine_row<CONV, 16>(line2 + at, bl, aff.scale[2], aff.bias[2]);
-                    continue;
-                }
-                *reinterpret_cast<uint4 *>(line0 + at) = uint4{r[0], r[1], r[2], r[3]};
-                *reinterpret_cast<uint4 *>(line1 + at) = uint4{g[0], g[1], g[2], g[3]};
-                *reinterpret_cast<uint4 *>(line2 + at) = uint4{bl[0], bl[1], bl[2], bl[3]};
+                store_plane_rows<CONV, 16>(line0 + at, line1 + at, line2 + at, r, g, bl, aff);
             } else {
                 const uint2 yv = *reinterpret_cast<const uint2 *>(yrow);
                 const uint2 bv = *reinterpret_cast<const uint2 *>(crow);
@@ -686,19 +629,10 @@ __device__ __forceinline__ void interleaved_output_from_tile(const uint8_t *sh_p
                 ChromaTerms t[8];
 #pragma unroll
                 for (int j = 0; j < 8; j++) t[j] = chroma_terms(byte_of(bv.x, bv.y, j), byte_of(rv.x, rv.y, j), kf);
-                uint2 r, g, bl;
-                rgb_planes4(byte_of(yv.x, yv.y, 0), byte_of(yv.x, yv.y, 1), byte_of(yv.x, yv.y, 2), byte_of(yv.x, yv.y, 3), t[0], t[1], t[2], t[3], r.x, g.x, bl.x);
-                rgb_planes4(byte_of(yv.x, yv.y, 4), byte_of(yv.x, yv.y, 5), byte_of(yv.x, yv.y, 6), byte_of(yv.x, yv.y, 7), t[4], t[5], t[6], t[7], r.y, g.y, bl.y);
-                if (CONV != kConvPlanar) {
-                    const uint32_t rw[2] = {r.x, r.y}, gw[2] = {g.x, g.y}, bw[2] = {bl.x, bl.y};
-                    store_affine_row<CONV, 8>(line0 + at, rw, aff.scale[0], aff.bias[0]);
-                    store_affine_row<CONV, 8>(line1 + at, gw, aff.scale[1], aff.bias[1]);
-                    store_affine_row<CONV, 8>(line2 + at, bw, aff.scale[2], aff.bias[2]);
-                    continue;
-                }
-                *reinterpret_cast<uint2 *>(line0 + at) = r;
-                *reinterpret_cast<uint2 *>(line1 + at) = g;
-                *reinterpret_cast<uint2 *>(line2 + at) = bl;
+                uint32_t r[2], g[2], bl[2];
+                rgb_planes4(byte_of(yv.x, yv.y, 0), byte_of(yv.x, yv.y, 1), byte_of(yv.x, yv.y, 2), byte_of(yv.x, yv.y, 3), t[0], t[1], t[2], t[3], r[0], g[0], bl[0]);
+                rgb_planes4(byte_of(yv.x, yv.y, 4), byte_of(yv.x, yv.y, 5), byte_of(yv.x, yv.y, 6), byte_of(yv.x, yv.y, 7), t[4], t[5], t[6], t[7], r[1], g[1], bl[1]);
+                store_plane_rows<CONV, 8>(line0 + at, line1 + at, line2 + at, r, g, bl, aff);
             }
         } else if (max_h == 2 && CONV != 0) {
             const uint4 yv = *reinterpret_cast<const uint4 *>(yrow);  // 16 luma samples (two adjacent blocks)
@@ -1087,7 +1021,7 @@ __device__ __forceinline__ void idct_output_body(
     if (PRE) {
         if (have_block) {
 #pragma unroll
-            for (int piece = 0; piece < 8; piece++) {
+            for (int piece = 0; piece < 8; piece++) {  // (block_load, written out: through it the six flush listings come out in another order)
                 const uint4 cv = *reinterpret_cast<const uint4 *>(sh + tid * 128 + ((piece ^ ((tid >> 1) & 7)) * 16));
                 px[piece * 4] = cv.x;
                 px[piece * 4 + 1] = cv.y;
@@ -1384,14 +1318,7 @@ __global__ __launch_bounds__(64) void dispose_pass_kernel(int16_t *__restrict__ 
     if (n == 0) return;
     int16_t *blk = coefs + (j.coef_off + g) * 64;
     uint32_t w[32];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const uint4 v = reinterpret_cast<const uint4 *>(blk)[i];
-        w[i * 4] = v.x;
-        w[i * 4 + 1] = v.y;
-        w[i * 4 + 2] = v.z;
-        w[i * 4 + 3] = v.w;
-    }
+    block_load(reinterpret_cast<const uint8_t *>(blk), 0, w);  // (from the store itself: no swizzle)
     for (uint32_t t = 0; t < n; t++) {
         const uint16_t *q = quant_pool[j.quant[c][t]].q;
         float f[64];
@@ -1406,150 +1333,86 @@ __global__ __launch_bounds__(64) void dispose_pass_kernel(int16_t *__restrict__ 
     for (int i = 0; i < 8; i++) reinterpret_cast<uint4 *>(blk)[i] = make_uint4(w[i * 4], w[i * 4 + 1], w[i * 4 + 2], w[i * 4 + 3]);
 }
 
-template <int FMT, int LAY>
-static void launch_idct_one(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work, int n_work, int n_dense,
-                            const DevScanStatus *status, const DevQuantTable *quant_pool, uint8_t *out,
-                            YccRgbFactors kf = YccRgbFactors{0, 0, 0, 0}, OutputAffine aff = kOutputAffineIdentity) {
-    // the first n_dense entries: scans with dense coefficient blocks; the rest: scans handed over as half-line planes
-    if (n_dense > 0)
-        hipLaunchKernelGGL((idct_output_kernel<FMT, LAY>), dim3(n_dense), dim3(kIdctThreads), 0, stream, coefs, scans, work, status,
-                           quant_pool, out, kf, aff);
-    if constexpr (idct_split_supported(FMT, LAY))  // (the planner lists no split scan under another format and class)
-      if (n_work > n_dense)
-        hipLaunchKernelGGL((idct_split_kernel<FMT, LAY>), dim3(n_work - n_dense), dim3(kIdctThreads), 0, stream, coefs, scans, work + n_dense, status,
-                           quant_pool, out, kf, aff);
-}
+// What every launch of one call shares.
+struct K3LaunchArgs {
+    hipStream_t stream;
+    const int16_t *coefs;
+    const DevScan *scans;
+    const DevScanStatus *status;
+    const DevQuantTable *quant_pool;
+    uint8_t *out, *generic_out;
+    YccRgbFactors kf;
+    OutputAffine aff;
+};
 
-template <int FMT>
-static void launch_window_fast(hipStream_t stream, int c, const int16_t *coefs, const DevScan *scans, const IdctWork *w, int n, const DevScanStatus *status,
-                               const DevQuantTable *quant_pool, uint8_t *out, const YccRgbFactors &kf, const OutputAffine &aff) {
-    switch (c) {
-    case kLayYccH1V1: hipLaunchKernelGGL((idct_window_kernel<FMT, kLayYccH1V1>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf, aff); break;
-    case kLayYccH2V1: hipLaunchKernelGGL((idct_window_kernel<FMT, kLayYccH2V1>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf, aff); break;
-    case kLayYccH2V2: hipLaunchKernelGGL((idct_window_kernel<FMT, kLayYccH2V2>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf, aff); break;
-    default: hipLaunchKernelGGL((idct_window_kernel<FMT, kLayGray>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf, aff); break;
-    }
-}
-
-// The same lists for the work of windowed images (the planner lists it apart, by the class idct_window_layout_class gives; never split).
-hipError_t launch_idct_window(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
-                              const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status, const DevQuantTable *quant_pool, uint8_t *out,
-                              int format, const YccRgbFactors &kf, uint8_t *generic_out, const OutputAffine &aff) {
-    if (!fmt_is_interleaved(format)) return class_begin[kNumIdctLayoutClasses] > class_begin[0] ? hipErrorInvalidValue : hipSuccess;
-    const bool scaled = format == kFmtInterleavedU8Scaled;
-    uint8_t *const bytes_out = fmt_is_rgb(format) ? generic_out : out;  // where sample bytes go: the image itself, or the RGB formats' scratch image
-    for (int c = 0; c < kNumIdctLayoutClasses; c++) {
-        const int n = class_begin[c + 1] - class_begin[c];
-        if (n <= 0) continue;
-        const IdctWork *w = work + class_begin[c];
-        const bool fast = c >= kLayYccH1V1 && c <= kLayGray;
-        if (c == kIdctClassStoreHoldsSamples) {
-            if (scaled) hipLaunchKernelGGL((flush_window_kernel<kFmtInterleavedU8Scaled>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, bytes_out, kf);
-            else hipLaunchKernelGGL((flush_window_kernel<kFmtInterleavedU8>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, bytes_out, kf);
-        } else if (fast && format == kFmtRgbU8) {
-            launch_window_fast<kFmtRgbU8>(stream, c, coefs, scans, w, n, status, quant_pool, out, kf, aff);
-        } else if (fast && format == kFmtRgbPlanarU8) {
-            launch_window_fast<kFmtRgbPlanarU8>(stream, c, coefs, scans, w, n, status, quant_pool, out, kf, aff);
-        } else if (fast && format == kFmtRgbPlanarF16) {
-            launch_window_fast<kFmtRgbPlanarF16>(stream, c, coefs, scans, w, n, status, quant_pool, out, kf, aff);
-        } else if (fast && format == kFmtRgbPlanarF32) {
-            launch_window_fast<kFmtRgbPlanarF32>(stream, c, coefs, scans, w, n, status, quant_pool, out, kf, aff);
-        } else if (c != kLayGeneric) {
-            return hipErrorInvalidValue;  // (the planner gives no such class to a window: a missing kernel is an error)
-        } else if (scaled) {
-            hipLaunchKernelGGL((idct_window_kernel<kFmtInterleavedU8Scaled, kLayGeneric>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, bytes_out, kf, aff);
-        } else {
-            hipLaunchKernelGGL((idct_window_kernel<kFmtInterleavedU8, kLayGeneric>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, bytes_out, kf, aff);
+// Kernel <FMT, LAY> of FORM, if that is the one the rule names (v) -- instantiated exactly where the rule reaches it from some (format, class):
+// kernels.h, k3_variant_compiled.  The formats whose kernels read neither kf nor aff get the caller's all the same.
+template <int FORM, int FMT, int LAY>
+static bool launch_k3_variant_if(const K3Variant &v, const K3LaunchArgs &a, const IdctWork *w, int n) {
+    if (v.fmt != FMT || v.lay != LAY) return false;
+    uint8_t *const dst = v.to_scratch ? a.generic_out : a.out;
+    if constexpr (k3_variant_compiled(FORM, false, FMT, LAY)) {
+        if (!v.pre) {
+            if constexpr (FORM == kK3Dense)
+                hipLaunchKernelGGL((idct_output_kernel<FMT, LAY>), dim3(n), dim3(kIdctThreads), 0, a.stream, a.coefs, a.scans, w, a.status, a.quant_pool, dst, a.kf, a.aff);
+            else if constexpr (FORM == kK3Split)
+                hipLaunchKernelGGL((idct_split_kernel<FMT, LAY>), dim3(n), dim3(kIdctThreads), 0, a.stream, a.coefs, a.scans, w, a.status, a.quant_pool, dst, a.kf, a.aff);
+            else
+                hipLaunchKernelGGL((idct_window_kernel<FMT, LAY>), dim3(n), dim3(kIdctThreads), 0, a.stream, a.coefs, a.scans, w, a.status, a.quant_pool, dst, a.kf, a.aff);
+            return true;
         }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
     }
-    return hipSuccess;
+    if constexpr (k3_variant_compiled(FORM, true, FMT, LAY)) {
+        static_assert(LAY == kLayGeneric && FORM != kK3Split, "the flush kernels: one per format, dense or window");
+        if (v.pre) {
+            if constexpr (FORM == kK3Dense)
+                hipLaunchKernelGGL((flush_output_kernel<FMT>), dim3(n), dim3(kIdctThreads), 0, a.stream, a.coefs, a.scans, w, a.status, a.quant_pool, dst, a.kf);
+            else
+                hipLaunchKernelGGL((flush_window_kernel<FMT>), dim3(n), dim3(kIdctThreads), 0, a.stream, a.coefs, a.scans, w, a.status, a.quant_pool, dst, a.kf);
+            return true;
+        }
+    }
+    return false;
+}
+// The run-time (format, class) of n > 0 workgroups to the compile-time <FMT, LAY> of the rule's answer, over every format and layout.
+// false: the rule has no kernel for such work (the planner lists none: a missing kernel is an error).
+template <int FORM, int... I>
+static bool launch_k3_variant(int format, int layout_class, const K3LaunchArgs &a, const IdctWork *w, int n, std::integer_sequence<int, I...>) {
+    const K3Variant v = k3_variant(format, layout_class, FORM);
+    return v.exists && (launch_k3_variant_if<FORM, I / kNumIdctLayouts, I % kNumIdctLayouts>(v, a, w, n) || ...);
 }
 
-// work is sorted by layout class; class_begin[c]..class_begin[c+1] are the workgroups of class c, and from split_begin[c] on (where
-// given) those of scans handed over as half-line planes.
-hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
-                       const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status,
-                       const DevQuantTable *quant_pool, uint8_t *out, int format, const YccRgbFactors &kf, uint8_t *generic_out,
-                       const int *split_begin, const OutputAffine &aff) {
+// work is sorted by layout class; class_begin[c]..class_begin[c+1] are the workgroups of class c, in form `form` up to split_begin[c] (where
+// given) and from there on those of scans handed over as half-line planes.
+static hipError_t launch_k3_classes(const K3LaunchArgs &a, const IdctWork *work, const int *class_begin, const int *split_begin, int format, K3Form form) {
+    constexpr auto kVariants = std::make_integer_sequence<int, kNumOutputFormats * kNumIdctLayouts>();
     for (int c = 0; c < kNumIdctLayoutClasses; c++) {
         const int n = class_begin[c + 1] - class_begin[c];
         if (n <= 0) continue;
         const int nd = split_begin ? split_begin[c] - class_begin[c] : n;
         const IdctWork *w = work + class_begin[c];
-        if (c == kIdctClassStoreHoldsSamples) {  // the generic Dispose() pass has run: the store goes to the writer as it is
-            if (format == kFmtPlanarI16) hipLaunchKernelGGL((flush_output_kernel<kFmtPlanarI16>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf);
-            else if (format == kFmtPlanarU8) hipLaunchKernelGGL((flush_output_kernel<kFmtPlanarU8>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf);
-            else if (format == kFmtInterleavedU8Scaled) hipLaunchKernelGGL((flush_output_kernel<kFmtInterleavedU8Scaled>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool, out, kf);
-            else hipLaunchKernelGGL((flush_output_kernel<kFmtInterleavedU8>), dim3(n), dim3(kIdctThreads), 0, stream, coefs, scans, w, status, quant_pool,
-                                    fmt_is_rgb(format) ? generic_out : out, kf);
-        } else if (format == kFmtPlanarI16) {
-            launch_idct_one<kFmtPlanarI16, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, out);
-        } else if (format == kFmtPlanarU8) {
-            launch_idct_one<kFmtPlanarU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, out);
-        } else if (format == kFmtRgbU8) {
-            switch (c) {
-            case kLayYccH1V1: launch_idct_one<kFmtRgbU8, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            case kLayYccH2V1: launch_idct_one<kFmtRgbU8, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            case kLayYccH2V2: launch_idct_one<kFmtRgbU8, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            case kLayGray: launch_idct_one<kFmtRgbU8, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            // no fused path: the samples go to `generic_out` as INTERLEAVED_U8 and are converted by launch_ycc_to_rgb
-            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
-            }
-        } else if (format == kFmtRgbaU8) {
-            switch (c) {
-            case kLayYccH1V1: launch_idct_one<kFmtRgbaU8, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            case kLayYccH2V1: launch_idct_one<kFmtRgbaU8, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            case kLayYccH2V2: launch_idct_one<kFmtRgbaU8, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            case kLayGray: launch_idct_one<kFmtRgbaU8, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
-            }
-        } else if (format == kFmtRgbPlanarU8) {
-            switch (c) {
-            case kLayYccH1V1: launch_idct_one<kFmtRgbPlanarU8, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            case kLayYccH2V1: launch_idct_one<kFmtRgbPlanarU8, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            case kLayYccH2V2: launch_idct_one<kFmtRgbPlanarU8, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            case kLayGray: launch_idct_one<kFmtRgbPlanarU8, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf); break;
-            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
-            }
-        } else if (format == kFmtRgbPlanarF16) {
-            switch (c) {
-            case kLayYccH1V1: launch_idct_one<kFmtRgbPlanarF16, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
-            case kLayYccH2V1: launch_idct_one<kFmtRgbPlanarF16, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
-            case kLayYccH2V2: launch_idct_one<kFmtRgbPlanarF16, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
-            case kLayGray: launch_idct_one<kFmtRgbPlanarF16, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
-            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
-            }
-        } else if (format == kFmtRgbPlanarF32) {
-            switch (c) {
-            case kLayYccH1V1: launch_idct_one<kFmtRgbPlanarF32, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
-            case kLayYccH2V1: launch_idct_one<kFmtRgbPlanarF32, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
-            case kLayYccH2V2: launch_idct_one<kFmtRgbPlanarF32, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
-            case kLayGray: launch_idct_one<kFmtRgbPlanarF32, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out, kf, aff); break;
-            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, generic_out); break;
-            }
-        } else if (format == kFmtInterleavedU8Scaled) {
-            switch (c) {
-            case kLayYccH1V1: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
-            case kLayYccH2V1: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
-            case kLayYccH2V2: launch_idct_one<kFmtInterleavedU8Scaled, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
-            case kLayGray: launch_idct_one<kFmtInterleavedU8Scaled, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
-            default: launch_idct_one<kFmtInterleavedU8Scaled, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
-            }
-        } else {
-            switch (c) {
-            case kLayYccH1V1: launch_idct_one<kFmtInterleavedU8, kLayYccH1V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
-            case kLayYccH2V1: launch_idct_one<kFmtInterleavedU8, kLayYccH2V1>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
-            case kLayYccH2V2: launch_idct_one<kFmtInterleavedU8, kLayYccH2V2>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
-            case kLayGray: launch_idct_one<kFmtInterleavedU8, kLayGray>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
-            default: launch_idct_one<kFmtInterleavedU8, kLayGeneric>(stream, coefs, scans, w, n, nd, status, quant_pool, out); break;
-            }
-        }
+        if (nd > 0 && !(form == kK3Window ? launch_k3_variant<kK3Window>(format, c, a, w, nd, kVariants) : launch_k3_variant<kK3Dense>(format, c, a, w, nd, kVariants)))
+            return hipErrorInvalidValue;
+        if (n > nd && !launch_k3_variant<kK3Split>(format, c, a, w + nd, n - nd, kVariants)) return hipErrorInvalidValue;
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// The work of windowed images (the planner lists it apart, by the class idct_window_layout_class gives; never split).  Work under a format
+// that is not assembled from whole pixels, or of a class without a window kernel: hipErrorInvalidValue.
+hipError_t launch_idct_window(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
+                              const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status, const DevQuantTable *quant_pool, uint8_t *out,
+                              int format, const YccRgbFactors &kf, uint8_t *generic_out, const OutputAffine &aff) {
+    return launch_k3_classes({stream, coefs, scans, status, quant_pool, out, generic_out, kf, aff}, work, class_begin, nullptr, format, kK3Window);
+}
+
+hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
+                       const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status,
+                       const DevQuantTable *quant_pool, uint8_t *out, int format, const YccRgbFactors &kf, uint8_t *generic_out,
+                       const int *split_begin, const OutputAffine &aff) {
+    return launch_k3_classes({stream, coefs, scans, status, quant_pool, out, generic_out, kf, aff}, work, class_begin, split_begin, format, kK3Dense);
 }
 
 // INTERLEAVED_U8 image (comps = 1 or 3) -> RGB / RGBA (bpp = 3 / 4) or the three planes of RGB_PLANAR_U8 (bpp = 1), for the layouts without a fused path;
@@ -1603,14 +1466,14 @@ int idct_layout_class(const DevScan &s) {
 // Layout class of a scan of a windowed image: today's rule with the window's width in place of the frame's, and the window's first column on
 // an MCU boundary -- so the cover's first MCU column starts at the window's first pixel, the window is whole MCUs wide, and every store address
 // of the fast classes keeps the alignment it has for a whole frame (a line is win_w samples, an image starts on a multiple of 256).  win_y and
-// win_h are free.  The fast classes have a window form for RGB_U8 and RGB_PLANAR_U8 / _F16 / _F32; every other whole-pixel format takes the
+// win_h are free.  A format without a window kernel for the fast class (k3_variant: all but RGB_U8 and RGB_PLANAR_U8 / _F16 / _F32) takes the
 // generic class under a window (RGBA_U8 through the scratch image and the converter).
 int idct_window_layout_class(const DevScan &s, int format) {
-    if (format != kFmtRgbU8 && !fmt_is_rgb_planes(format)) return kLayGeneric;
     if (s.max_h == 0 || s.win_x % (8u * s.max_h) != 0) return kLayGeneric;
     DevScan w = s;
     w.width = s.win_w;
-    return idct_layout_class(w);
+    const int cls = idct_layout_class(w);
+    return k3_variant(format, cls, kK3Window).exists ? cls : kLayGeneric;
 }
 
 }  // namespace jpgpu

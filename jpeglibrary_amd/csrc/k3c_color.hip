@@ -3,31 +3,24 @@
 // those samples into the five RGB forms.  One launch per batch: blockIdx.y = image (its descriptor in HBM, like extend_u16_kernel), blockIdx.x
 // strides over the image's groups of four pixels, one group per lane -- a 4-component group is one 16-byte load, a 3-component group three
 // dwords.  GRAY and YCBCR images never come here: they keep K3's fused classes and ycc_to_rgb_kernel.
-// (A file of its own so that every other kernel object stays byte for byte what it was.  The YCbCr terms below restate chroma_terms / rgb_pixel
-// of k3_idct.hip, and affine_sample its affine step: YCCK is defined through the bytes RGB_U8 would hold.)
+// (A file of its own so that every other kernel object stays byte for byte what it was.  YCCK is defined through the bytes RGB_U8 would hold;
+// the byte gathers, the clamp and the affine step are K3's, k3_pixel.h.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "kernels.h"
+#include "k3_pixel.h"
 
 namespace jpgpu {
 
 namespace {
-
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-
-// byte gather from the 8 bytes {lo (indices 0-3), hi (indices 4-7)}, index 12 = a zero byte: one v_perm_b32
-__device__ __forceinline__ uint32_t pick4(uint32_t lo, uint32_t hi, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
-#define JPGPU_SEL(a, b, c, d) ((uint32_t)(a) | ((uint32_t)(b) << 8) | ((uint32_t)(c) << 16) | ((uint32_t)(d) << 24))
 
 // round-to-nearest of x / 255 for 0 <= x <= 65025 (tests/test_color_cpu.py checks every x)
 __device__ __forceinline__ uint32_t div255(uint32_t x) {
     const uint32_t t = x + 128u;
     return (t + (t >> 8)) >> 8;
 }
-__device__ __forceinline__ uint32_t clamp_u8_i32(int32_t v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
 // one pixel's samples s = s0 | s1 << 8 | s2 << 16 | s3 << 24 -> R | G << 8 | B << 16
 __device__ __forceinline__ uint32_t color_pixel(uint32_t kind, uint32_t s, const YccRgbFactors &k) {
@@ -35,6 +28,7 @@ __device__ __forceinline__ uint32_t color_pixel(uint32_t kind, uint32_t s, const
     uint32_t c0 = s & 0xFFu, c1 = (s >> 8) & 0xFFu, c2 = (s >> 16) & 0xFFu;
     const uint32_t s3 = s >> 24;
     if (kind == kColorYcck) {  // RGB_U8's conversion of (s0, s1, s2), inverted
+        // (chroma_terms' arithmetic written out: through the shared helper the five listings come out in another instruction order)
         const int32_t cb = (int32_t)c1 - 128, cr = (int32_t)c2 - 128, y = (int32_t)c0;
         c0 = 255u - clamp_u8_i32(y + ((k.cr_r * cr + 32768) >> 16));
         c1 = 255u - clamp_u8_i32(y + ((k.cb_g * cb + 32768 + k.cr_g * cr) >> 16));
@@ -42,8 +36,6 @@ __device__ __forceinline__ uint32_t color_pixel(uint32_t kind, uint32_t s, const
     }
     return div255(c0 * s3) | (div255(c1 * s3) << 8) | (div255(c2 * s3) << 16);
 }
-
-__device__ __forceinline__ float affine_sample(uint32_t u, float scale, float bias) { return __fadd_rn(__fmul_rn((float)u, scale), bias); }
 
 // Four bytes of one plane (w = u0 | u1 << 8 | ...) -> four samples at dst.  A plane starts at c * pixels samples, which is a multiple of
 // nothing: the destination is aligned for one sample only, and the stores say so.

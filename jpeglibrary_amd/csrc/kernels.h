@@ -66,8 +66,10 @@ hipError_t launch_huffman_pool(hipStream_t stream, const uint8_t *data, const De
                                const uint8_t *lut_pool, uint32_t tab_bytes);
 // lut_pool: kLutPoolBytesPerTable per pool table, filled by launch_lut_pool (K2 and the K2S round kernel copy from it)
 hipError_t launch_lut_pool(hipStream_t stream, const DevHuffTable *huff_pool, int n_tables, uint8_t *lut_pool);
+// Output layout classes of the formats K3 assembles from whole pixels (chosen per scan on the host, see idct_layout_class()): the layouts the
+// kernels are instantiated with, and the class of frames whose generic Dispose() pass has run (any format): flush_output_kernel
+enum IdctLayout : int { kLayGeneric = 0, kLayYccH1V1 = 1, kLayYccH2V1 = 2, kLayYccH2V2 = 3, kLayGray = 4, kNumIdctLayouts = 5, kIdctClassStoreHoldsSamples = 5 };
 constexpr int kNumIdctLayoutClasses = 6;
-constexpr int kIdctClassStoreHoldsSamples = 5;  // frames whose generic Dispose() pass has run (any format): flush_output_kernel
 // Output layout class of a scan for the formats K3 assembles from whole pixels (fmt_is_interleaved; 0 = generic bytewise path, else a specialised kernel).
 int idct_layout_class(const DevScan &s);
 // Has K3 a form that reads half-line planes (idct_split_kernel) for this output format and layout class?  Not where the output assembly
@@ -76,22 +78,66 @@ int idct_layout_class(const DevScan &s);
 // scans stay dense.
 constexpr bool idct_split_supported(int format, int layout_class) {
     if (format == kFmtPlanarI16 || format == kFmtPlanarU8 || format == kFmtExtendedU16) return true;
-    if (layout_class == 0 || layout_class >= kIdctClassStoreHoldsSamples) return false;
-    if (format == kFmtRgbU8) return layout_class == 1 || layout_class == 4;
-    if (format == kFmtRgbaU8) return layout_class != 3;
+    if (layout_class == kLayGeneric || layout_class >= kIdctClassStoreHoldsSamples) return false;
+    if (format == kFmtRgbU8) return layout_class == kLayYccH1V1 || layout_class == kLayGray;
+    if (format == kFmtRgbaU8) return layout_class != kLayYccH2V2;
     if (format == kFmtRgbPlanarU8) return true;  // all four fast classes compile at the kernel's launch bounds without spill or scratch (tests/test_planar_rgb_isa_cpu.py)
     // RGB_PLANAR_F16 / _F32, by the compiler's resource report for gfx950: every class fits in both forms without a spilled vector register and
     // without scratch -- dense: 4:4:4, 4:2:2, 4:2:0 162 VGPRs, gray 160; split: 4:4:4 163, 4:2:2 164, 4:2:0 163, gray 163 (of the 168 three waves
     // per SIMD allow).  The split forms have no scalar register left for the six constants: ten scalars (gray: five) wait in lanes of one vector
     // register, moved once per tile outside the task loop (tests/test_float_sink_isa_cpu.py).
     if (format == kFmtRgbPlanarF16 || format == kFmtRgbPlanarF32) return true;
-    if (format == kFmtInterleavedU8Scaled) return layout_class != 4;
+    if (format == kFmtInterleavedU8Scaled) return layout_class != kLayGray;
     return true;
+}
+// THE rule of K3's kernel variants: which kernel serves work of (output format, layout class) in a form -- dense coefficient blocks, blocks
+// handed over as half-line planes, or the work of a windowed image -- and where it writes.  The planner (device_batch_layout.cpp), the launcher
+// and the set of kernels the launcher instantiates (k3_idct.hip: launch_k3_variant) all ask here, and tests/test_k3_variants_cpu.py holds the
+// whole table: a new sink, class or form is added HERE, and its kernel follows.
+enum K3Form : int { kK3Dense = 0, kK3Split = 1, kK3Window = 2, kNumK3Forms = 3 };
+struct K3Variant {
+    bool exists;      // no kernel: the planner must not list such work, the launcher refuses it
+    bool pre;         // the store already holds samples: flush_output_kernel<fmt> / flush_window_kernel<fmt> (lay is kLayGeneric)
+    int fmt, lay;     // idct_output_kernel / idct_split_kernel / idct_window_kernel<fmt, lay>
+    bool to_scratch;  // INTERLEAVED_U8 samples into the RGB formats' scratch image (`generic_out`), converted behind K3
+};
+constexpr K3Variant k3_variant(int format, int layout_class, int form) {
+    constexpr K3Variant none = {false, false, 0, 0, false};
+    if (format < 0 || format >= kNumOutputFormats || layout_class < 0 || layout_class >= kNumIdctLayoutClasses) return none;
+    if (format == kFmtExtendedU16) format = kFmtPlanarI16;  // (extend_u16_kernel widens PLANAR_I16 planes: run_idct launches under that number)
+    const bool rgb = fmt_is_rgb(format);
+    if (form == kK3Window) {  // whole-pixel formats only; sample bytes from the generic layout, fused conversion for RGB_U8 and the three planar sinks
+        if (!fmt_is_interleaved(format)) return none;
+        const int bytes = format == kFmtInterleavedU8Scaled ? kFmtInterleavedU8Scaled : kFmtInterleavedU8;
+        if (layout_class == kIdctClassStoreHoldsSamples) return {true, true, bytes, kLayGeneric, rgb};
+        if (layout_class == kLayGeneric) return {true, false, bytes, kLayGeneric, rgb};
+        if (format == kFmtRgbU8 || fmt_is_rgb_planes(format)) return {true, false, format, layout_class, false};
+        return none;
+    }
+    if (form != kK3Dense && form != kK3Split) return none;
+    if (layout_class == kIdctClassStoreHoldsSamples) {  // the generic Dispose() pass has run: the store goes to the writer as it is (never split)
+        const bool own = format == kFmtPlanarI16 || format == kFmtPlanarU8 || format == kFmtInterleavedU8Scaled;
+        return form == kK3Dense ? K3Variant{true, true, own ? format : kFmtInterleavedU8, kLayGeneric, rgb} : none;
+    }
+    if (form == kK3Split && !idct_split_supported(format, layout_class)) return none;
+    if (format == kFmtPlanarI16 || format == kFmtPlanarU8) return {true, false, format, kLayGeneric, false};  // planes: no layout class
+    // RGB formats without a fused path: the samples go to the scratch image as INTERLEAVED_U8 and are converted by launch_ycc_to_rgb
+    if (rgb && layout_class == kLayGeneric) return {true, false, kFmtInterleavedU8, kLayGeneric, true};
+    return {true, false, format, layout_class, false};
+}
+// Is kernel <fmt, lay> of a form (pre: its flush kernel) one the rule reaches from some (format, class)?  Exactly those are compiled.
+constexpr bool k3_variant_compiled(int form, bool pre, int fmt, int lay) {
+    for (int f = 0; f < kNumOutputFormats; f++)
+        for (int c = 0; c < kNumIdctLayoutClasses; c++) {
+            const K3Variant v = k3_variant(f, c, form);
+            if (v.exists && v.pre == pre && v.fmt == fmt && v.lay == lay) return true;
+        }
+    return false;
 }
 // work is sorted by layout class; class_begin[c]..class_begin[c+1] are the workgroups of class c.
 // RGB / RGBA formats: classes with a fused conversion write `out`; the generic class writes INTERLEAVED_U8 samples into
 // `generic_out` (same offsets), to be converted by launch_ycc_to_rgb (bpp = 3 / 4, or 1: the three planes of RGB_PLANAR_U8 / _F16 / _F32).
-// aff: the affine step of RGB_PLANAR_F16 / _F32 (no other format reads it).
+// aff: the affine step of RGB_PLANAR_F16 / _F32 (no other format reads it).  Work of a class k3_variant has no kernel for: hipErrorInvalidValue.
 hipError_t launch_idct(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IdctWork *work,
                        const int class_begin[kNumIdctLayoutClasses + 1], const DevScanStatus *status,
                        const DevQuantTable *quant_pool, uint8_t *out, int format, const YccRgbFactors &kf, uint8_t *generic_out,

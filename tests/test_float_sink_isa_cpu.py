@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 
+from test_k3_variants_cpu import k3_compiled_variants, k3_variant_rows
 from test_planar_rgb_isa_cpu import CSRC, KERNELS, _resources, _task_loop
 
 FMT_U8, FMT_F16, FMT_F32 = 7, 8, 9
@@ -66,8 +67,25 @@ def test_the_split_forms_are_the_ones_idct_split_supported_admits(isa):
     for fmt in (FMT_F16, FMT_F32):
         have = {cls for cls in range(0, 6) if any(n.startswith(KERNELS["split"] % (fmt, cls)) for n in names)}
         assert have == set(SPLIT_CLASSES), (fmt, have)
-    src = open(os.path.join(CSRC, "kernels.h")).read()
-    assert re.search(r"if \(format == kFmtRgbPlanarF16 \|\| format == kFmtRgbPlanarF32\) return true;", src)  # (behind the generic class's `return false`)
+    rows = k3_variant_rows()  # the rule itself (kernels.h: k3_variant), printed by a host program
+    for fmt in (FMT_F16, FMT_F32):
+        assert {cls for cls in range(0, 6) if rows[("split", fmt, cls)] != "-"} == set(SPLIT_CLASSES), fmt
+        assert rows[("split", fmt, 0)] == "-" and rows[("split", fmt, 5)] == "-"
+        assert all(rows[("split", fmt, cls)] == "%d,%d" % (fmt, cls) for cls in SPLIT_CLASSES)
+
+
+@pytest.mark.timeout(600)
+def test_the_listing_holds_exactly_the_variants_the_rule_enumerates(isa):
+    """the idct_* and flush_* kernels of the listing against the rule's enumeration: neither a variant the launcher cannot reach nor one it
+    reaches and nobody compiled"""
+    names = set(re.findall(r"\.name:\s+(\S+)", isa))
+    have = set()
+    for n in names:
+        m = re.match(r"_ZN5jpgpu\d+((?:idct|flush)_\w+?_kernel)ILi(\d+)E(?:Li(\d+)E)?EE", n)
+        if m:
+            have.add((m.group(1), tuple(int(v) for v in m.groups()[1:] if v is not None)))
+    want = k3_compiled_variants()
+    assert have == want, (sorted(have - want), sorted(want - have))
 
 
 @pytest.mark.timeout(600)
