@@ -399,6 +399,48 @@ int jpgpu_batch_image_color(const jpgpu_batch *b, int i, int *kind);
  * a frame header or with broken headers; JPGPU_ERR_NOT_SUPPORTED for a frame the rule refuses; JPGPU_ERR_ARGUMENT for a NULL argument. */
 int jpgpu_identify_color(const uint8_t *file, size_t len, int *kind);
 
+/* ---- Orientation: the Exif orientation of a file, or a flip or turn the caller asks for, applied in the output stage (an extension beyond the
+ * reference, whose callers hand the stored samples on).
+ *   By default (JPGPU_ORIENT_STORED) an image comes out as its file stores it.  Under JPGPU_ORIENT_FILE it is turned the way its Exif block
+ * says, as ImageOps.exif_transpose, torchvision's apply_exif_orientation and the browsers do.  The rule.  The block is the FIRST APP1 between
+ * SOI and the first SOS whose payload begins "Exif\0\0"; only that segment is read.  With t the bytes behind those six: t[0:2] is "II"
+ * (little-endian) or "MM" (big-endian), the uint16 at t + 2 is 42, the uint32 at t + 4 is the offset o of IFD0, the uint16 at t + o its entry
+ * count, the 12-byte entries follow from t + o + 2.  The first entry with tag 0x0112 counts: of type 3 (SHORT) and count 1, its value is the
+ * uint16 at entry + 8 in the file's byte order, and a value of 1..8 is the orientation.  No such segment, another magic, a read that would
+ * leave the segment, another type or count, a value of 0 or above 8, no such tag: orientation 1.  A bad block never fails an image.
+ *   The transform.  With H x W the stored frame and (Y, X) a pixel of the output, the source pixel (y, x) is
+ *     1   H x W   (Y, X)                        5   W x H   (X, Y)              transpose
+ *     2   H x W   (Y, W-1-X)        mirror      6   W x H   (H-1-X, Y)          a quarter turn clockwise
+ *     3   H x W   (H-1-Y, W-1-X)    half turn   7   W x H   (H-1-X, W-1-Y)      transverse
+ *     4   H x W   (H-1-Y, X)        flip        8   W x H   (X, W-1-Y)          a quarter turn counter-clockwise
+ * and every sample of the output is, bit for bit, the sample at (y, x) of what the same upload produces under orientation 1 -- for images
+ * that fail or end early, for progressive frames and their partial flush, for every colour kind under JPGPU_COLOR_FILE, and for the float
+ * formats, whose affine step is per sample.
+ *   jpgpu_batch_set_orientation_policy is state of the batch like the colour policy.  jpgpu_batch_set_orientations gives the NEXT upload of
+ * whole files one value per file and is consumed by it like windows: 1..8 is used as given, whatever the file says; 0 leaves the image to the
+ * policy; n == 0 withdraws a pending list.  JPGPU_ERR_ARGUMENT for a value above 8; an upload whose n differs from the list's is refused with
+ * JPGPU_ERR_ARGUMENT and leaves the batch empty, and so is jpgpu_batch_upload_frames while a list is pending.
+ *   Only RGB_U8, RGBA_U8 and RGB_PLANAR_U8 / _F16 / _F32 read orientation; every other format decodes as stored and reports 1, and an upload
+ * under one of them with a list pending is refused like windows under PLANAR_U8.
+ *   Geometry.  jpgpu_image_info.width / height stay the stored frame's; out_bytes and plane[] describe the oriented output, width and height
+ * swapped for 5..8.  Windows (jpgpu_batch_set_windows) are given in pixels of the ORIENTED frame, which is what the caller sees: the windowed
+ * output is that slice of the oriented whole decode, jpgpu_batch_image_window returns the rectangle as given, and a window outside the
+ * oriented frame fails that image alone.  The resize stage reads the oriented image.  out_offset of the image behind an oriented one follows
+ * the rule of the colour kinds (the samples pass through a scratch slot at the same offset): use out_offset.
+ *   Not covered: jpgpu_decoder_*, jpgpu_decode_scan, jpgpu_progressive_*, jpgpu_multi_* (they decode as stored). */
+typedef enum jpgpu_orientation_policy {
+    JPGPU_ORIENT_STORED = 0, /* as the file stores the pixels */
+    JPGPU_ORIENT_FILE = 1    /* as the file's Exif orientation says */
+} jpgpu_orientation_policy;
+int jpgpu_batch_set_orientation_policy(jpgpu_batch *b, int policy);
+int jpgpu_batch_set_orientations(jpgpu_batch *b, const uint8_t *orientations, int n);
+/* The orientation image i was planned with: 1 under a format that does not read it and for an image that failed at upload.  Valid after an
+ * upload; JPGPU_ERR_ARGUMENT for a NULL argument or an index out of range. */
+int jpgpu_batch_image_orientation(const jpgpu_batch *b, int i, int *orientation);
+/* The rule above on a file's headers.  Host only, no context needed.  The library's usual header errors (jpgpu_status) for a file without a
+ * frame header or with broken headers -- never for a broken Exif block; JPGPU_ERR_ARGUMENT for a NULL argument. */
+int jpgpu_identify_orientation(const uint8_t *file, size_t len, int *orientation);
+
 /* Coefficient hand-off for multi-scan (progressive, SOF2) images -- BASELINE config 5's "coefficient accumulate then single
  * IDCT pass": the caller's progressive entropy decoder accumulates the coefficient store, the GPU runs what
  * JpegHuffmanProgressiveScanDecoder.Dispose (ScanDecoder/JpegHuffmanProgressiveScanDecoder.cs:421-470: dequantise, IDCT,

@@ -5,7 +5,7 @@ There is no CPU fallback: creating a context without a GPU raises NoDeviceError.
 """
 from . import _capi  # noqa: F401  (loads libjpgpu.so, fails loudly when absent)
 from . import sharding  # noqa: F401
-from .batch import FMT_EXTENDED_U16, FMT_INTERLEAVED_U8, FMT_INTERLEAVED_U8_SCALED, FMT_PLANAR_I16, FMT_PLANAR_U8, FMT_RGB_PLANAR_F16, FMT_RGB_PLANAR_F32, FMT_RGB_PLANAR_U8, FMT_RGB_U8, FMT_RGBA_U8, Batch, affine_from_mean_std, decode_batch, decode_resized, decode_to_tensors, identify_color
+from .batch import FMT_EXTENDED_U16, FMT_INTERLEAVED_U8, FMT_INTERLEAVED_U8_SCALED, FMT_PLANAR_I16, FMT_PLANAR_U8, FMT_RGB_PLANAR_F16, FMT_RGB_PLANAR_F32, FMT_RGB_PLANAR_U8, FMT_RGB_U8, FMT_RGBA_U8, Batch, affine_from_mean_std, decode_batch, decode_resized, decode_to_tensors, identify_color, identify_orientation
 from .context import Context, default_context, device_count
 from .encoder import EncodeBatch, encode_batch, encode_tensors
 from .optimizer import JpegOptimizer, OptimizeBatch, build_optimal_huffman_table, optimize_batch
@@ -22,7 +22,7 @@ __all__ = [
     "JpegStandardHuffmanEncodingTable", "JpegBufferInputReader", "EncodeBatch", "encode_batch", "encode_tensors", "JpegOptimizer", "OptimizeBatch", "optimize_batch", "build_optimal_huffman_table", "Context", "default_context", "device_count", "JpegDecoder", "JpegBlockOutputWriter",
     "JpegBufferOutputWriter8Bit", "JpegExtendingOutputWriter", "JpegFrameHeader", "JpegFrameComponentSpecificationParameters", "JpegScanHeader",
     "JpegScanComponentSpecificationParameters", "JpegHuffmanDecodingTable", "JpegGpuProgressiveScanDecoder", "FMT_INTERLEAVED_U8", "FMT_PLANAR_U8", "FMT_PLANAR_I16", "FMT_RGB_U8", "FMT_RGBA_U8", "FMT_EXTENDED_U16",
-    "FMT_INTERLEAVED_U8_SCALED", "FMT_RGB_PLANAR_U8", "FMT_RGB_PLANAR_F16", "FMT_RGB_PLANAR_F32", "affine_from_mean_std", "identify_color", "JpegBufferOutputWriterGreaterThan8Bit", "JpegBufferOutputWriterLessThan8Bit",
+    "FMT_INTERLEAVED_U8_SCALED", "FMT_RGB_PLANAR_U8", "FMT_RGB_PLANAR_F16", "FMT_RGB_PLANAR_F32", "affine_from_mean_std", "identify_color", "identify_orientation", "JpegBufferOutputWriterGreaterThan8Bit", "JpegBufferOutputWriterLessThan8Bit",
     "JpegError", "InvalidDataException", "InvalidOperationException", "NotSupportedException", "ArgumentException",
     "DeviceError", "NoDeviceError",
 ]

@@ -152,6 +152,41 @@ def identify_color(data):
     return _capi.COLOR_KINDS[kind.value]
 
 
+def _orientation_policy(orientation, who="orientation"):
+    """The check of Batch.set_orientation_policy / decode_batch(orientation=...), before any library call: "stored" or "file" -> the
+    jpgpu_orientation_policy value"""
+    if not isinstance(orientation, str) or orientation not in _capi.ORIENTATION_POLICIES:
+        raise ValueError('%s is "stored" (as the file stores the pixels) or "file" (as its Exif orientation says), not %r' % (who, orientation))
+    return _capi.ORIENTATION_POLICIES.index(orientation)
+
+
+def _orientation_list(orientations, n_files=None):
+    """The checks of Batch.set_orientations / decode_batch(orientations=...), before any library call: integers 0..8, one per file (0 = what
+    the policy gives); n_files: the count they must match.  None -> None."""
+    import numbers
+
+    if orientations is None:
+        return None
+    out = []
+    for i, o in enumerate(orientations):
+        if not isinstance(o, numbers.Integral) or isinstance(o, bool) or not 0 <= o <= 8:
+            raise ValueError("orientation %d: an integer 1..8 (the Exif values), or 0 for what the policy gives, not %r" % (i, o))
+        out.append(int(o))
+    if n_files is not None and len(out) != n_files:
+        raise ValueError("%d orientations for %d files: one per file (0 = what the policy gives)" % (len(out), n_files))
+    return out
+
+
+def identify_orientation(data):
+    """The Exif orientation a JPEG file declares, 1..8 -- the Orientation tag in IFD0 of the first Exif APP1 in front of the first scan
+    (include/jpgpu.h, "Orientation"), what Batch.orientation(i) reports under the "file" policy; 1 for a file without the tag or with a
+    broken Exif block.  Host only: no device, no context.  Raises as the decoder does for a file without a frame header."""
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+    o = C.c_int()
+    raise_for_status(_lib.jpgpu_identify_orientation(a.ctypes.data, a.size, C.byref(o)), b"jpgpu_identify_orientation: the headers could not be read")
+    return o.value
+
+
 def _upload_any(batch, files, fmt):
     """decode_batch / decode_to_tensors: upload() for bytes-like files, upload_tensors() for a list of torch tensors"""
     files = list(files)
@@ -274,8 +309,33 @@ class Batch:
         raise_for_status(_lib.jpgpu_batch_image_color(self._h, i, C.byref(kind)), b"jpgpu_batch_image_color: no such image")
         return _capi.COLOR_KINDS[kind.value]
 
+    def set_orientation_policy(self, orientation):
+        """How the RGB formats (RGB_U8, RGBA_U8, RGB_PLANAR_U8 / _F16 / _F32) turn an image from the next upload on: "stored", the default -- as
+        the file stores its pixels -- or "file": as its Exif orientation says (identify_orientation), the way ImageOps.exif_transpose does, so
+        a portrait phone photo comes out upright, [3, W, H] for the values 5..8.  State of the batch: it holds until set again.  ValueError,
+        before the library is called, for any other value."""
+        self._check(_lib.jpgpu_batch_set_orientation_policy(self._h, _orientation_policy(orientation)))
+        return self
+
+    def set_orientations(self, orientations):
+        """The orientations of the NEXT upload(), upload_segments() or upload_tensors(): one integer per file, 1..8 (the Exif values: 2 is the
+        horizontal flip of the usual augmentation pair) used as given whatever the file says, or 0 for what the policy gives; None withdraws
+        a pending list.  Consumed by that upload like windows.  RGB formats only.  ValueError, before the library is called, for anything
+        that is not such an integer."""
+        vals = _orientation_list(orientations)
+        n = len(vals) if vals else 0
+        arr = (C.c_uint8 * max(1, n))(*(vals or []))
+        self._check(_lib.jpgpu_batch_set_orientations(self._h, arr, n))
+        return self
+
+    def orientation(self, i):
+        """1..8: the orientation image i was planned with (1 under a format that does not read it)"""
+        o = C.c_int()
+        raise_for_status(_lib.jpgpu_batch_image_orientation(self._h, i, C.byref(o)), b"jpgpu_batch_image_orientation: no such image")
+        return o.value
+
     def window(self, i):
-        """(x, y, w, h): the window image i was planned with; (0, 0, W, H) for a whole frame"""
+        """(x, y, w, h): the window image i was planned with, in pixels of the oriented frame; (0, 0, W, H) of that frame for a whole one"""
         r = _capi.Rect()
         raise_for_status(_lib.jpgpu_batch_image_window(self._h, i, C.byref(r)), b"jpgpu_batch_image_window: no such image")
         return (r.x, r.y, r.width, r.height)
@@ -469,7 +529,7 @@ class Batch:
         raise_for_status(info.status, _lib.jpgpu_last_error(self.ctx._h))
         raw = np.empty(info.out_bytes, dtype=np.uint8)
         self._check(_lib.jpgpu_batch_download_output(self._h, i, raw.ctypes.data, raw.size))
-        _, _, w, h = self.window(i)  # (the whole frame's W, H without a window)
+        _, _, w, h = self.window(i)  # (the whole oriented frame's W, H without a window)
         if self.format in (FMT_INTERLEAVED_U8, FMT_INTERLEAVED_U8_SCALED):
             return raw.reshape(h, w, info.num_components)
         if self.format in (FMT_RGB_U8, FMT_RGBA_U8):
@@ -487,7 +547,7 @@ class Batch:
         return planes
 
     def _tensor_shape(self, info, hw=None):
-        """hw: the (h, w) of the image's window (Batch.window); the frame's without one"""
+        """hw: the (h, w) of the image's window (Batch.window), which is the oriented frame's without one; None: the stored frame's"""
         h, w = hw if hw is not None else (info.height, info.width)
         if self.format in (FMT_INTERLEAVED_U8, FMT_INTERLEAVED_U8_SCALED):
             return (h, w, info.num_components)
@@ -555,15 +615,22 @@ class Batch:
             pass
 
 
-def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="ycc"):
+def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None):
     """One-call helper: returns (outputs, results).  files: bytes-like objects, or 1-D uint8 torch tensors on the context's device.
     windows: one (x, y, w, h) per file (Batch.set_windows): outputs[i] is that rectangle of image i.
-    color: "ycc" or "file" (Batch.set_color_policy): under "file" the RGB formats deliver RGB for CMYK, YCCK and Adobe-RGB files."""
+    color: "ycc" or "file" (Batch.set_color_policy): under "file" the RGB formats deliver RGB for CMYK, YCCK and Adobe-RGB files.
+    orientation: "stored" or "file" (Batch.set_orientation_policy); orientations: one value 0..8 per file (Batch.set_orientations).  Windows
+    are then in pixels of the oriented frame."""
     files = list(files)
     windows = _window_rects(windows, len(files))
     _color_policy(color)
+    _orientation_policy(orientation)
+    orientations = _orientation_list(orientations, len(files))
     b = Batch(ctx)
     b.set_color_policy(color)
+    b.set_orientation_policy(orientation)
+    if orientations is not None:
+        b.set_orientations(orientations)
     if windows is not None:
         b.set_windows(windows)
     b = _upload_any(b, files, fmt).decode().sync()
@@ -576,7 +643,7 @@ def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="y
     return outs, results
 
 
-def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None, color="ycc"):
+def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None):
     """One-call helper for torch consumers: returns (tensors, results), tensors[i] = Batch.output_tensor(i) -- uint8[3, H, W] on the
     context's device by default -- or None for an image that failed.  Nothing is downloaded.  The batch is not closed: its output
     buffer is the tensors' memory and is freed with the last of them.  files: bytes-like objects, or 1-D uint8 torch tensors on the
@@ -586,10 +653,15 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     a sample is the byte as a float.
     windows: one (x, y, w, h) per file (Batch.set_windows): tensors[i] is [3, h, w], that rectangle of image i, decoded without the rest.
     color: "ycc" or "file" (Batch.set_color_policy): under "file" CMYK, YCCK and Adobe-RGB files come out as RGB instead of failing or
-    taking the YCbCr matrix."""
+    taking the YCbCr matrix.
+    orientation: "stored" or "file" (Batch.set_orientation_policy): under "file" an image is turned as its Exif orientation says, so
+    tensors[i] is [3, W, H] for the values 5..8; orientations: one value 0..8 per file (Batch.set_orientations), e.g. 2 for a horizontal flip.
+    Windows are then in pixels of the oriented frame."""
     files = list(files)
     windows = _window_rects(windows, len(files))
     _color_policy(color)
+    _orientation_policy(orientation)
+    orientations = _orientation_list(orientations, len(files))
     if dtype is not None:
         import torch
 
@@ -605,6 +677,9 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
         raise ValueError("decode_to_tensors: mean / std apply to float samples; pass dtype=torch.float16 or torch.float32")
     b = Batch(ctx)
     b.set_color_policy(color)
+    b.set_orientation_policy(orientation)
+    if orientations is not None:
+        b.set_orientations(orientations)
     if mean is not None:
         b.set_output_affine(*affine_from_mean_std(mean, std))
     if windows is not None:
@@ -617,7 +692,7 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     return tensors, results
 
 
-def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None, color="ycc"):
+def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None, color="ycc", orientation="stored", orientations=None):
     """One-call helper for fixed-size consumers: returns (tensor, results), tensor = Batch.resized_tensor() -- ONE [N, 3, oh, ow] tensor on the
     context's device, size = (oh, ow), dtype torch.float16 (the default), torch.float32 or torch.uint8 -- every image decoded to RGB and
     resampled to that size (antialiased bilinear) in one launch behind the output stage; the slab of an image that failed is zero and
@@ -625,12 +700,15 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
     files: bytes-like objects, or 1-D uint8 torch tensors on the context's device, as in decode_to_tensors.  mean / std (per channel, 0..1
     units; both or neither) make the float samples (v / 255 - mean) / std through affine_from_mean_std; they are refused for torch.uint8.
     windows: one (x, y, w, h) per file (Batch.set_windows): that rectangle of image i is what is resampled -- a RandomResizedCrop's crop.
-    color: "ycc" or "file" (Batch.set_color_policy), as in decode_to_tensors."""
+    color: "ycc" or "file" (Batch.set_color_policy), orientation and orientations (Batch.set_orientation_policy / set_orientations), as in
+    decode_to_tensors: the oriented image is what is resampled."""
     import torch
 
     files = list(files)
     windows = _window_rects(windows, len(files))
     _color_policy(color)
+    _orientation_policy(orientation)
+    orientations = _orientation_list(orientations, len(files))
     dtype = torch.float16 if dtype is None else dtype
     _resize_setting(size, dtype)
     _all_tensors(files)  # (a list that mixes bytes and tensors raises here, before a batch exists)
@@ -641,6 +719,9 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
     consts = affine_from_mean_std(mean, std) if mean is not None else None
     b = Batch(ctx)
     b.set_color_policy(color)
+    b.set_orientation_policy(orientation)
+    if orientations is not None:
+        b.set_orientations(orientations)
     if consts is not None:
         b.set_output_affine(*consts)
     b.set_resize(size, dtype)

@@ -426,6 +426,25 @@ int jpgpu_identify_color(const uint8_t *file, size_t len, int *kind) {
         return JPGPU_ERR_OUT_OF_MEMORY;
     }
 }
+int jpgpu_batch_set_orientation_policy(jpgpu_batch *b, int policy) { JPGPU_GUARD(b, b->impl.set_orientation_policy(policy)); }
+int jpgpu_batch_set_orientations(jpgpu_batch *b, const uint8_t *orientations, int n) { JPGPU_GUARD(b, b->impl.set_orientations(orientations, n)); }
+int jpgpu_batch_image_orientation(const jpgpu_batch *b, int i, int *orientation) { return b ? b->impl.image_orientation(i, orientation) : JPGPU_ERR_ARGUMENT; }
+// Host only: Identify's walk up to the first SOS, which records the first Exif APP1 on its way (ingest_host.h: exif_orientation_of).
+int jpgpu_identify_orientation(const uint8_t *file, size_t len, int *orientation) {
+    if (!file || !orientation) return JPGPU_ERR_ARGUMENT;
+    try {
+        HostDecoder dec;
+        dec.set_input(file, len);
+        size_t pos = 0;
+        (void)dec.identify_until_scan(false, &pos);
+        *orientation = dec.exif_orientation();
+        return JPGPU_OK;
+    } catch (const DecodeError &e) {
+        return e.status;
+    } catch (const std::exception &) {
+        return JPGPU_ERR_OUT_OF_MEMORY;
+    }
+}
 int jpgpu_batch_idct_listed_mcus(const jpgpu_batch *b, uint64_t *mcus) {
     if (!b || !mcus) return JPGPU_ERR_ARGUMENT;
     *mcus = b->impl.idct_listed_mcus();

@@ -43,7 +43,7 @@ void DevBuffer::release() {
 
 DeviceBatch::~DeviceBatch() {
     if (ctx_) (void)hipSetDevice(ctx_->device);
-    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_color_images_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
+    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_color_images_, &d_orient_images_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
         b->release();
     for (hipEvent_t &e : ev_pool_)
         if (e) (void)hipEventDestroy(e);
@@ -64,7 +64,8 @@ int DeviceBatch::hip_fail(hipError_t e, const char *what) {
 }
 
 uint64_t DeviceBatch::slot_bytes(const ImagePlan &img) {
-    const uint64_t samples = color_kind_by_file(img.color_kind) ? (uint64_t)img.win.width * img.win.height * color_kind_sample_bytes(img.color_kind) : 0u;
+    const bool through_scratch = color_kind_by_file(img.color_kind) || img.orientation != 1;
+    const uint64_t samples = through_scratch ? (uint64_t)img.win.width * img.win.height * color_kind_sample_bytes(img.color_kind) : 0u;
     return std::max(img.out_bytes, samples);
 }
 
@@ -81,7 +82,29 @@ int DeviceBatch::image_color(int i, int *kind) const {
     return JPGPU_OK;
 }
 
-void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &geo, const ColorMarkers &markers) const {
+int DeviceBatch::set_orientation_policy(int policy) {
+    if (policy != JPGPU_ORIENT_STORED && policy != JPGPU_ORIENT_FILE) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_set_orientation_policy: unknown policy");
+    orient_policy_ = policy;
+    return JPGPU_OK;
+}
+
+int DeviceBatch::set_orientations(const uint8_t *orientations, int n) {
+    if (n < 0 || (n > 0 && !orientations)) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_set_orientations: bad argument");
+    for (int i = 0; i < n; i++)
+        if (orientations[i] > 8) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_set_orientations: an orientation is 1..8, or 0 for what the policy gives");
+    pending_orientations_.assign(orientations, orientations + n);
+    orientations_pending_ = n > 0;
+    return JPGPU_OK;
+}
+
+int DeviceBatch::image_orientation(int i, int *orientation) const {
+    const ImagePlan *img = image(i);
+    if (!img || !orientation) return JPGPU_ERR_ARGUMENT;
+    *orientation = img->orientation;
+    return JPGPU_OK;
+}
+
+void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &geo, const ColorMarkers &markers, int exif_orientation) const {
     const FrameHeader &fh = geo.frame;
     img.width = fh.samples_per_line;
     img.height = fh.lines;
@@ -140,7 +163,9 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
         }
     }
     img.windowed = false;  // (a window is applied behind the plans, DeviceBatch::apply_window)
-    img.win = jpgpu_rect{0, 0, img.width, img.height};
+    img.win = img.win_oriented = jpgpu_rect{0, 0, img.width, img.height};
+    img.exif_orientation = (uint8_t)exif_orientation;  // (what the file says; what the image is planned with is apply_window's decision)
+    img.orientation = 1;
     // A frame header is two 16-bit sizes and a component count: a corrupted one can ask for hundreds of gigabytes (the
     // reference's caller would fail allocating the writer's buffer).  Such an image fails BY ITSELF instead of taking the
     // batch's allocation, and every other image, with it (tools/stress_parity.py STRESS_HEADER=1, seed 460).
@@ -331,13 +356,17 @@ int DeviceBatch::upload_progressive_dispose(const ProgressiveFrame &frame, int f
 int DeviceBatch::upload_frames(const jpgpu_frame *frames, const uint16_t *qt, int n, int format) {
     whole_files_ = false;
     device_ingest_ = jpgpu_device_ingest_stats();
-    if (windows_pending_) {  // (windows are for uploads of whole files: consumed and refused, the batch left empty)
+    if (windows_pending_ || orientations_pending_) {  // (both are for uploads of whole files: consumed and refused, the batch left empty)
+        const bool windows = windows_pending_;
         pending_windows_.clear();
-        windows_pending_ = replay_possible_ = false;
+        pending_orientations_.clear();
+        windows_pending_ = orientations_pending_ = replay_possible_ = false;
         forget_batch();
-        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_frames: windows are pending (jpgpu_batch_set_windows), and frames take none");
+        return fail(JPGPU_ERR_ARGUMENT, windows ? "jpgpu_batch_upload_frames: windows are pending (jpgpu_batch_set_windows), and frames take none"
+                                                : "jpgpu_batch_upload_frames: orientations are pending (jpgpu_batch_set_orientations), and frames take none");
     }
     windows_.clear();
+    orientations_.clear();
     if (n < 0 || (n > 0 && (!frames || !qt))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_frames: null argument");
     if (format < 0 || format >= kNumOutputFormats) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload_frames: unknown format");
     format_ = format;

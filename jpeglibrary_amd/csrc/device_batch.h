@@ -109,6 +109,12 @@ struct ImagePlan {
     // what the image's samples are (common.h: ColorKind): kColorGray / kColorYcbcr unless the batch's colour policy is JPGPU_COLOR_FILE, the
     // format reads it and the file declares otherwise; an image of the other three kinds takes K3's generic class and the K3C launch
     uint8_t color_kind = kColorYcbcr;
+    // how the image is turned on its way out (include/jpgpu.h, "Orientation"): 1 = as stored.  exif_orientation is what the file's Exif block
+    // says, orientation what the image was planned with (apply_window: the caller's list, the policy, the format).  `win` stays in pixels of
+    // the STORED frame, which is what K3 decodes; win_oriented is the same rectangle in the oriented frame, as the caller gave and sees it
+    // (equal to win under orientation 1).  An image whose orientation is not 1 takes K3's generic class and the K3O launch.
+    uint8_t exif_orientation = 1, orientation = 1;
+    jpgpu_rect win_oriented = {0, 0, 0, 0};
 };
 
 class WorkCrew;
@@ -144,6 +150,11 @@ class DeviceBatch {
     // The colour policy (jpgpu_batch_set_color_policy): state of the batch, read by every later upload under an RGB format.
     int set_color_policy(int policy);
     int image_color(int i, int *kind) const;
+    // The orientation policy (jpgpu_batch_set_orientation_policy): state of the batch like the colour policy; and the orientations of the NEXT
+    // upload of whole files (jpgpu_batch_set_orientations): consumed by it like windows.
+    int set_orientation_policy(int policy);
+    int set_orientations(const uint8_t *orientations, int n);
+    int image_orientation(int i, int *orientation) const;
     uint64_t idct_listed_mcus() const { return idct_listed_mcus_; }
     // One progressive frame collected by the JpegDecoder mirror: its entropy scans + the Dispose() pass.
     int upload_progressive_frame(const ProgressiveFrame &frame, const uint8_t *file, size_t file_len, int sof, int format);
@@ -246,11 +257,14 @@ class DeviceBatch {
     void init_status();
     int upload_plan(const UploadPlan &p, const std::vector<const uint8_t *> &file_ptr, const std::vector<size_t> &file_len);
     // markers: what the file's headers declare about its colour (none seen: frames, single jobs)
-    void plan_image_geometry(ImagePlan &img, const BaselineGeometry &geo, const ColorMarkers &markers = ColorMarkers()) const;
+    // exif_orientation: what its Exif block says (1: none seen); recorded here, decided on in apply_window
+    void plan_image_geometry(ImagePlan &img, const BaselineGeometry &geo, const ColorMarkers &markers = ColorMarkers(), int exif_orientation = 1) const;
     // bytes an image takes in the output buffer AND in the scratch image, which mirrors its offsets: out_bytes, or the 4 bytes per pixel a
-    // CMYK / YCCK image's samples need where that is more (RGB_U8, RGB_PLANAR_U8)
+    // CMYK / YCCK image's samples need where that is more (RGB_U8, RGB_PLANAR_U8); an oriented image of any kind passes through the scratch
+    // image too, with 1, 3 or 4 bytes per pixel by the same rule
     static uint64_t slot_bytes(const ImagePlan &img);
     void plan_color_convert();
+    void plan_orient_convert();
     // ingest (jpgpu_batch_upload*), see device_batch_ingest.cpp
     void plan_file_headers(const uint8_t *file, size_t len, FilePlan &fp) const;
     void plan_file_full(const uint8_t *file, size_t len, int index, FilePlan &fp) const;
@@ -448,6 +462,14 @@ class DeviceBatch {
     uint64_t color_max_pixels_ = 0;
     DevBuffer d_color_images_;
     int color_policy_ = JPGPU_COLOR_YCC;
+    // ... and the images whose orientation is not 1, of every kind, in a third list: one K3O launch turns and converts them all (plan_orient_convert)
+    std::vector<RgbConvert> orient_convert_;
+    std::vector<OrientImage> orient_images_;
+    uint32_t orient_max_tiles_ = 0;
+    DevBuffer d_orient_images_;
+    int orient_policy_ = JPGPU_ORIENT_STORED;
+    bool orientations_pending_ = false;
+    std::vector<uint8_t> pending_orientations_, orientations_;  // set_orientations' / the running upload's (empty: every image by the policy)
     DevBuffer d_chunk_work_, d_chunk_sums_;
     int n_chunk_work_ = 0;
     DevBuffer d_unstuffed_, d_ends_u_;  // K1 output: entropy data as the bit reader sees it + interval ends in it

@@ -206,9 +206,9 @@ void DeviceBatch::plan_file_full(const uint8_t *file, size_t len, int index, Fil
         if (entropy_only_) img.sof = (uint8_t)dec.start_of_frame();
         if (fp.jobs.empty()) {
             // no scan: Decode() succeeds without writing anything; keep the frame geometry for the caller
-            if (img.sof == kSOF0 || img.sof == kSOF1 || img.sof == kSOF2) plan_image_geometry(img, BaselineGeometry::latch(dec, dec.frame_header()), dec.color_markers());
+            if (img.sof == kSOF0 || img.sof == kSOF1 || img.sof == kSOF2) plan_image_geometry(img, BaselineGeometry::latch(dec, dec.frame_header()), dec.color_markers(), dec.exif_orientation());
         } else {
-            plan_image_geometry(img, fp.jobs[0].geo, dec.color_markers());
+            plan_image_geometry(img, fp.jobs[0].geo, dec.color_markers(), dec.exif_orientation());
             img.blocks_per_mcu = (uint32_t)fp.jobs[0].blocks_per_mcu;
         }
         fp.seq_ends = handler.sequential_ends();
@@ -228,7 +228,7 @@ void DeviceBatch::plan_file_full(const uint8_t *file, size_t len, int index, Fil
             img.late_detail = e.detail;
             img.late_error = e.what();
             try {
-                plan_image_geometry(img, fp.jobs[0].geo, dec.color_markers());
+                plan_image_geometry(img, fp.jobs[0].geo, dec.color_markers(), dec.exif_orientation());
                 img.blocks_per_mcu = (uint32_t)fp.jobs[0].blocks_per_mcu;
             } catch (const DecodeError &e2) {
                 fp.jobs.clear();
@@ -281,7 +281,7 @@ void DeviceBatch::plan_file_headers(const uint8_t *file, size_t len, FilePlan &f
         FastPlanHandler handler(&fp.jobs);
         dec.decode(handler, true);
         if (fp.jobs.size() != 1) throw NeedFullWalk{};
-        plan_image_geometry(img, fp.jobs[0].geo, dec.color_markers());
+        plan_image_geometry(img, fp.jobs[0].geo, dec.color_markers(), dec.exif_orientation());
         img.blocks_per_mcu = (uint32_t)fp.jobs[0].blocks_per_mcu;
         fp.speculative = true;
     } catch (const NeedFullWalk &) {
@@ -391,7 +391,7 @@ int DeviceBatch::set_windows(const jpgpu_rect *windows, int n) {
 int DeviceBatch::image_window(int i, jpgpu_rect *window) const {
     const ImagePlan *img = image(i);
     if (!img || !window) return JPGPU_ERR_ARGUMENT;
-    *window = img->win;
+    *window = img->win_oriented;  // (as the caller gave it: in pixels of the oriented frame)
     return JPGPU_OK;
 }
 
@@ -399,40 +399,67 @@ int DeviceBatch::image_window(int i, jpgpu_rect *window) const {
 // call, decided before anything is enqueued; they leave the batch empty.
 int DeviceBatch::take_windows(int n, int format, const char *what) {
     windows_.clear();
-    if (!windows_pending_) return JPGPU_OK;
+    orientations_.clear();
+    if (!windows_pending_ && !orientations_pending_) return JPGPU_OK;
+    const bool with_windows = windows_pending_, with_orientations = orientations_pending_;
     windows_.swap(pending_windows_);
-    windows_pending_ = false;
+    orientations_.swap(pending_orientations_);
+    pending_windows_.clear();
+    pending_orientations_.clear();
+    windows_pending_ = orientations_pending_ = false;
     const char *why = nullptr;
-    if ((int)windows_.size() != n) why = ": the upload's n differs from the windows' n (jpgpu_batch_set_windows)";
-    else if (format < 0 || format >= kNumOutputFormats || !fmt_is_interleaved(format))
+    if (with_windows && (int)windows_.size() != n) why = ": the upload's n differs from the windows' n (jpgpu_batch_set_windows)";
+    else if (with_windows && (format < 0 || format >= kNumOutputFormats || !fmt_is_interleaved(format)))
         why = ": windows (jpgpu_batch_set_windows) need a whole-pixel format; PLANAR_U8, PLANAR_I16 and EXTENDED_U16 have none";
+    else if (with_orientations && (int)orientations_.size() != n) why = ": the upload's n differs from the orientations' n (jpgpu_batch_set_orientations)";
+    else if (with_orientations && (format < 0 || format >= kNumOutputFormats || !fmt_is_rgb(format)))
+        why = ": orientations (jpgpu_batch_set_orientations) need an RGB format; the sample and the planar formats decode as stored";
+    if (!with_windows) windows_.clear();
+    if (!with_orientations) orientations_.clear();
     if (!why) return JPGPU_OK;
     windows_.clear();
+    orientations_.clear();
     forget_batch();
     whole_files_ = replay_possible_ = false;
     return fail(JPGPU_ERR_ARGUMENT, std::string(what) + why);
 }
 
-// Image i behind its plan: the verdict on its window, and the window's geometry in place of the frame's.  A window that is the whole frame
-// is no window.  An image that failed keeps its status.
+// Image i behind its plan: its orientation -- the caller's value, else what the policy makes of the file's, and 1 under a format that does
+// not read it -- then the verdict on its window, which is given in pixels of the ORIENTED frame, and the geometry of the output in place of
+// the stored frame's.  A window that is the whole frame is no window.  An image that failed keeps its status; an image of orientation 1
+// without a window leaves here exactly as its plan made it.
 void DeviceBatch::apply_window(size_t i) {
     ImagePlan &img = images_[i];
-    if (windows_.empty() || img.status != JPGPU_OK) return;
-    const jpgpu_rect w = windows_[i];
-    if (w.x == 0 && w.y == 0 && w.width == 0 && w.height == 0) return;
-    const bool inside = (uint64_t)w.x + w.width <= img.width && (uint64_t)w.y + w.height <= img.height;
-    if (!inside || w.width == 0 || w.height == 0) {  // (outside the frame, or no pixels: this image alone fails)
-        img.status = JPGPU_ERR_ARGUMENT;
-        img.detail = kDetailNone;
-        img.error = "The window {" + std::to_string(w.x) + ", " + std::to_string(w.y) + ", " + std::to_string(w.width) + ", " + std::to_string(w.height) +
-                    "} does not lie inside the " + std::to_string(img.width) + " x " + std::to_string(img.height) + " frame, or is empty.";
-        img.out_bytes = 0;
-        memset(img.plane, 0, sizeof img.plane);
-        return;
+    if (img.status != JPGPU_OK) return;
+    int o = 1;
+    if (fmt_is_rgb(format_)) {
+        const int given = orientations_.empty() ? 0 : orientations_[i];
+        o = given != 0 ? given : (orient_policy_ == JPGPU_ORIENT_FILE ? img.exif_orientation : 1);
     }
-    if (w.x == 0 && w.y == 0 && w.width == img.width && w.height == img.height) return;
-    img.windowed = true;
-    img.win = w;
+    img.orientation = (uint8_t)o;
+    const uint32_t ow = orientation_transposes(o) ? img.height : img.width, oh = orientation_transposes(o) ? img.width : img.height;  // the oriented frame
+    jpgpu_rect w = windows_.empty() ? jpgpu_rect{0, 0, 0, 0} : windows_[i];
+    bool whole = w.x == 0 && w.y == 0 && w.width == 0 && w.height == 0;
+    if (!whole) {
+        const bool inside = (uint64_t)w.x + w.width <= ow && (uint64_t)w.y + w.height <= oh;
+        if (!inside || w.width == 0 || w.height == 0) {  // (outside the frame, or no pixels: this image alone fails)
+            img.status = JPGPU_ERR_ARGUMENT;
+            img.detail = kDetailNone;
+            img.error = "The window {" + std::to_string(w.x) + ", " + std::to_string(w.y) + ", " + std::to_string(w.width) + ", " + std::to_string(w.height) +
+                        "} does not lie inside the " + std::to_string(ow) + " x " + std::to_string(oh) + " frame, or is empty.";
+            img.out_bytes = 0;
+            memset(img.plane, 0, sizeof img.plane);
+            return;
+        }
+        whole = w.x == 0 && w.y == 0 && w.width == ow && w.height == oh;
+    }
+    if (whole) w = jpgpu_rect{0, 0, ow, oh};
+    img.win_oriented = w;
+    if (whole && o == 1) return;
+    if (!whole) {
+        img.windowed = true;
+        img.win = orientation_stored_rect(o, w, img.width, img.height);  // what K3 decodes
+    }
     const uint64_t pixels = (uint64_t)w.width * w.height;
     if (fmt_is_sample_bytes(format_)) {
         img.out_bytes = pixels * img.num_components;
@@ -446,7 +473,8 @@ void DeviceBatch::apply_window(size_t i) {
 int DeviceBatch::upload_files(const uint8_t *const *jpeg, const size_t *len, int n, int format) {
     if (n < 0 || (n > 0 && (!jpeg || !len))) {
         pending_windows_.clear();  // (consumed by this upload, refused as it is)
-        windows_pending_ = false;
+        pending_orientations_.clear();
+        windows_pending_ = orientations_pending_ = false;
         return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upload: null argument");
     }
     std::vector<jpgpu_segment> segs((size_t)n);

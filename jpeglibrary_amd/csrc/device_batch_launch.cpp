@@ -342,6 +342,10 @@ int DeviceBatch::run_idct(bool with_resize) {
     e = launch_color_convert(ctx_->stream, (const uint8_t *)d_rgb_scratch_.ptr, (uint8_t *)d_out_.ptr, (const ColorImage *)d_color_images_.ptr,
                              (int)color_images_.size(), color_max_pixels_, format_, kf, output_affine_);
     if (e != hipSuccess) return hip_fail(e, "color_convert_kernel");
+    // the images whose orientation is not 1, of every kind: one launch turns and converts them all
+    e = launch_orient_convert(ctx_->stream, (const uint8_t *)d_rgb_scratch_.ptr, (uint8_t *)d_out_.ptr, (const OrientImage *)d_orient_images_.ptr,
+                              (int)orient_images_.size(), orient_max_tiles_, format_, kf, output_affine_);
+    if (e != hipSuccess) return hip_fail(e, "orient_convert_kernel");
     if (with_resize && resize_.width != 0) return run_resize();  // K4, behind everything above
     return mark_work();
 }

@@ -153,6 +153,7 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
     assemble_progressive_lists(p);
     plan_output_clears();
     plan_color_convert();
+    plan_orient_convert();
     assemble_idct_lists(p);
     plan_overlap_halves(p);
     init_status();
@@ -184,6 +185,7 @@ void DeviceBatch::reset_upload_state(const UploadPlan &p) {
     prog_spin_budget_ = p.sw.prog_spin_budget;
     rgb_convert_.clear();
     color_convert_.clear();
+    orient_convert_.clear();
     sub_scan_ids_.clear();
     total_subs_ = max_subs_per_scan_ = 0;
     k2s_budget_ = 0;
@@ -505,8 +507,9 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
     // image's, and the padding (an even count of whole intervals) goes behind it.  (The scans of a multi-scan image lie back
     // to back in one dense run of the image's blocks, which is what the coefficient readers hand out: they stay dense.)
     // (a windowed image's scan is always handed over dense: the split form of K3 would need a window variant of its own)
-    const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed, split_always = p.sw.handoff_set;
-    const int k3_class = fmt_is_interleaved(format_) && !color_kind_by_file(img.color_kind) ? idct_layout_class(s) : 0;
+    // (... and so is an oriented image's: its samples go through the scratch image, which only the generic class fills)
+    const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed && img.orientation == 1, split_always = p.sw.handoff_set;
+    const int k3_class = fmt_is_interleaved(format_) && !color_kind_by_file(img.color_kind) && img.orientation == 1 ? idct_layout_class(s) : 0;
     if (split_wanted && job.kind == kScanSequential && s.dri != 0 && img.jobs.size() == 1 && !img.replay_skip && s.total_mcus > 0 &&
         s.blocks_per_mcu != 0 && k3_variant(format_, k3_class, kK3Split).exists &&
         // The planes pay where few blocks reach into coefficients 32..63; all that is known of that in front of the decode is
@@ -524,10 +527,11 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
 }
 
 // no fused conversion for a scan of image ii: its samples go to the scratch image, then ycc_to_rgb_kernel (once per image) -- or, for an image
-// of kind RGB, CMYK or YCCK, the batch's one K3C launch (plan_color_convert)
+// of kind RGB, CMYK or YCCK, the batch's one K3C launch (plan_color_convert) -- or, for an image of any kind whose orientation is not 1, the
+// batch's one K3O launch (plan_orient_convert), which converts as well
 void DeviceBatch::list_rgb_convert(size_t ii) {
     const ImagePlan &img = images_[ii];
-    std::vector<RgbConvert> &list = color_kind_by_file(img.color_kind) ? color_convert_ : rgb_convert_;
+    std::vector<RgbConvert> &list = img.orientation != 1 ? orient_convert_ : (color_kind_by_file(img.color_kind) ? color_convert_ : rgb_convert_);
     for (const RgbConvert &rc : list)
         if (rc.image == (uint32_t)ii) return;
     list.push_back({(uint32_t)ii, img.out_offset, (uint64_t)img.win.width * img.win.height, img.num_components});  // (the window's pixels)
@@ -566,6 +570,8 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
     if (!holds_samples && overlapping_scans && rgb_out) cls = 0;
     // ... and so do the samples of an image whose kind is RGB, CMYK or YCCK (JPGPU_COLOR_FILE): the fused classes convert YCbCr and grey
     if (!holds_samples && color_kind_by_file(img.color_kind)) cls = 0;
+    // ... and of an image that is turned on its way out (orientation 2..8): the scratch image is what K3O reads
+    if (!holds_samples && img.orientation != 1) cls = 0;
     if ((cls == 0 || holds_samples) && rgb_out) list_rgb_convert(ii);
     // A baseline frame whose LATER scans write a component this one writes too (a corrupted selector: one component
     // scanned twice, another never): in the reference the later WriteBlock wins -- where the later scan GOT to; a later
@@ -867,6 +873,17 @@ void DeviceBatch::assemble_idct_lists(UploadPlan &p) {
 // ---- two halves for decode()'s overlapped issue order (see decode()): images [0, half_image) and [half_image, n), balanced by
 // blocks; the Huffman work list is in image order already (one index cuts it), the IDCT work gets a second list with
 // the classes of each half interleaved over the XCDs on their own
+// The descriptors of the K3O launch: one per image whose orientation is not 1, with the stored window K3 leaves in the scratch image.
+void DeviceBatch::plan_orient_convert() {
+    orient_images_.clear();
+    orient_max_tiles_ = 0;
+    for (const RgbConvert &rc : orient_convert_) {
+        const ImagePlan &img = images_[rc.image];
+        orient_images_.push_back({rc.out_offset, rc.out_offset, img.win.width, img.win.height, (uint32_t)img.color_kind, (uint32_t)img.orientation});
+        orient_max_tiles_ = std::max(orient_max_tiles_, orient_tiles(img.win.width, img.win.height));
+    }
+}
+
 void DeviceBatch::plan_overlap_halves(UploadPlan &p) {
     overlap_ok_ = false;
     // OFF by default: with the round-2 kernels both stages are HBM-heavy (K2 writes the coefficient buffer at 4.7 TB/s)
@@ -883,7 +900,7 @@ void DeviceBatch::plan_overlap_halves(UploadPlan &p) {
     while (huff_half_ < n_huff_work_ && h_scans_[p.huff_work[huff_half_].scan].image_index < half_image) huff_half_++;
     // worth it for batches that keep the machine busy for milliseconds: the halves cost four launches and two events
     if (wanted && !entropy_only_ && p.sub_work.empty() && p.prog_work.empty() && total_blocks_ >= (4u << 20) && huff_half_ > 0 &&
-        huff_half_ < n_huff_work_ && rgb_convert_.empty() && color_convert_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
+        huff_half_ < n_huff_work_ && rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
         idct_win_class_begin_[kNumIdctLayoutClasses] == idct_win_class_begin_[0]) {  // (no windowed image: the halves have no list for their work)
         for (int half = 0; half < 2; half++) {
             idct_half_begin_[half][0] = (int)p.idct_work_halves.size();
@@ -960,8 +977,9 @@ int DeviceBatch::upload_plan(const UploadPlan &p, const std::vector<const uint8_
         // + one tile of slack (IDCT DMA reads whole tiles) + the split scans' flag words
         {&d_coefs_, nullptr, 0, entropy_only_ ? 256 : (size_t)coef_store_blocks_ * 128 + (size_t)kIdctBlocksPerWg * 128 + (size_t)p.flag_words * 8 + 256},
         {&d_out_, nullptr, 0, entropy_only_ ? 256 : (size_t)out_bytes_ + 256},
-        {&d_rgb_scratch_, nullptr, 0, rgb_convert_.empty() && color_convert_.empty() ? 0 : (size_t)out_bytes_ + 256},
+        {&d_rgb_scratch_, nullptr, 0, rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() ? 0 : (size_t)out_bytes_ + 256},
         {&d_color_images_, color_images_.data(), color_images_.size() * sizeof(ColorImage), 0},
+        {&d_orient_images_, orient_images_.data(), orient_images_.size() * sizeof(OrientImage), 0},
         {&d_planes_, nullptr, 0, format_ == JPGPU_FMT_EXTENDED_U16 && !entropy_only_ ? (size_t)planes_bytes_ + 256 : 0},
         {&d_input_, nullptr, 0, (size_t)input_bytes_},
     };

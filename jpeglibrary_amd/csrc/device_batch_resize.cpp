@@ -61,9 +61,9 @@ int DeviceBatch::plan_resize() {
         ResizeImage d;
         d.src_off = img.out_offset;
         d.dst_off = (uint64_t)i * 3u * (uint64_t)oh * (uint64_t)ow;
-        d.w_in = img.win.width;
-        d.h_in = img.win.height;
-        const auto h = table((int)img.win.width, ow), v = table((int)img.win.height, oh);
+        d.w_in = img.win_oriented.width;  // (the output's size: the window as the caller sees it, turned with the image)
+        d.h_in = img.win_oriented.height;
+        const auto h = table((int)d.w_in, ow), v = table((int)d.h_in, oh);
         d.h_off = h.first;
         d.h_taps = h.second;
         d.v_off = v.first;

@@ -170,6 +170,8 @@ class HostDecoder {
     size_t input_len() const { return input_len_; }
     // what the last Identify walk (identify, identify_until_scan) saw of APP0 "JFIF" and APP14 "Adobe" in front of the first SOS
     const ColorMarkers &color_markers() const { return color_; }
+    // ... and of the first APP1 "Exif" there: the orientation its IFD0 gives (1 where it gives none)
+    int exif_orientation() const { return exif_.orientation; }
 
     // ref: InitDecodeComponents (ScanDecoder/JpegHuffmanScanDecoder.cs:17-72)
     int resolve_scan(const FrameHeader &fh, const ScanHeader &sh, ResolvedScanComponent out[kMaxScanComponents], bool optimizer_rules = false) const;
@@ -193,6 +195,7 @@ class HostDecoder {
     std::vector<QuantTable> quant_;
     bool scan_decoder_created_ = false;
     ColorMarkers color_;
+    ExifMarker exif_;
     bool color_open_ = false;  // an Identify walk is in front of its first SOS: process_other_marker records into color_
 };
 

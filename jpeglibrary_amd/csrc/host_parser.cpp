@@ -359,7 +359,10 @@ void HostDecoder::set_quantization_table(const QuantTable &t) {
 void HostDecoder::process_other_marker(MarkerReader &r, int marker) {
     uint16_t length;
     if (!r.try_read_length(&length)) throw_invalid_data_at(r.consumed_byte_count(), "Unexpected end of input data when reading segment length.", kDetailBadHeader);
-    if (color_open_ && (int)length <= r.remaining_byte_count()) note_color_marker(color_, marker, r.remaining_bytes(), length);
+    if (color_open_ && (int)length <= r.remaining_byte_count()) {
+        note_color_marker(color_, marker, r.remaining_bytes(), length);
+        note_exif_marker(exif_, marker, r.remaining_bytes(), length);
+    }
     if (!r.try_advance(length)) throw_invalid_data_at(r.consumed_byte_count(), "Unexpected end of input data reached.", kDetailBadHeader);
 }
 
@@ -470,6 +473,7 @@ int HostDecoder::identify(bool load_quantization_tables) {
     MarkerReader r(input_, input_len_);
     frame_.reset();
     color_ = ColorMarkers();
+    exif_ = ExifMarker();
     color_open_ = true;
     bool to_continue = true;
     while (to_continue && !r.is_empty()) {
@@ -486,6 +490,7 @@ bool HostDecoder::identify_until_scan(bool load_quantization_tables, size_t *sca
     MarkerReader r(input_, input_len_);
     frame_.reset();
     color_ = ColorMarkers();
+    exif_ = ExifMarker();
     color_open_ = true;
     bool to_continue = true;
     while (to_continue && !r.is_empty()) {

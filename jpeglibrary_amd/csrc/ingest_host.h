@@ -39,6 +39,51 @@ inline int color_kind_of(int precision, int num_components, const uint8_t *ids, 
     }
 }
 
+// What a file declares about the way its pixels are to be turned for display: the Orientation tag (0x0112) in IFD0 of the FIRST APP1 "Exif\0\0"
+// segment in front of the first SOS (HostDecoder records it on every Identify walk, next to the colour markers) -- the one decision
+// JPGPU_ORIENT_FILE makes (include/jpgpu.h, "Orientation").  A block that is short, malformed or without the tag gives 1: it never fails an image.
+struct ExifMarker {
+    bool seen = false;        // the first such APP1 has been read; later ones are not
+    uint8_t orientation = 1;  // 1..8
+};
+// t: the n bytes behind "Exif\0\0" (the TIFF header onwards).  Every read is checked against n.
+inline int exif_orientation_of(const uint8_t *t, size_t n) {
+    if (n < 8) return 1;
+    const bool little = t[0] == 'I' && t[1] == 'I';
+    if (!little && !(t[0] == 'M' && t[1] == 'M')) return 1;
+    const auto u16 = [&](size_t at) { return little ? (uint32_t)t[at] | ((uint32_t)t[at + 1] << 8) : ((uint32_t)t[at] << 8) | (uint32_t)t[at + 1]; };
+    const auto u32 = [&](size_t at) { return little ? u16(at) | (u16(at + 2) << 16) : (u16(at) << 16) | u16(at + 2); };
+    if (u16(2) != 42) return 1;
+    const size_t ifd = u32(4);
+    if (ifd > n || n - ifd < 2) return 1;
+    const uint32_t entries = u16(ifd);
+    for (uint32_t k = 0; k < entries; k++) {
+        const size_t e = ifd + 2 + (size_t)k * 12;
+        if (e > n || n - e < 12) return 1;  // (an entry that leaves the segment)
+        if (u16(e) != 0x0112) continue;
+        if (u16(e + 2) != 3 || u32(e + 4) != 1) return 1;  // SHORT, count 1
+        const uint32_t v = u16(e + 8);
+        return v >= 1 && v <= 8 ? (int)v : 1;
+    }
+    return 1;
+}
+inline void note_exif_marker(ExifMarker &m, int marker, const uint8_t *payload, size_t len) {
+    if (m.seen || marker != 0xE1 || len < 6 || memcmp(payload, "Exif\0\0", 6) != 0) return;
+    m.seen = true;
+    m.orientation = (uint8_t)exif_orientation_of(payload + 6, len - 6);
+}
+// Orientation o (1..8) over a stored frame of `width` x `height`: the size of the oriented frame, and the rectangle of the stored frame that
+// holds the pixels of a rectangle given in the oriented one (include/jpgpu.h: the table's (y, x) over the rectangle's corners).
+constexpr bool orientation_transposes(int o) { return o >= 5; }
+constexpr bool orientation_flips_x(int o) { return o == 2 || o == 3 || o == 7 || o == 8; }  // the stored column runs against the output's
+constexpr bool orientation_flips_y(int o) { return o == 3 || o == 4 || o == 6 || o == 7; }  // the stored row runs against the output's
+inline jpgpu_rect orientation_stored_rect(int o, jpgpu_rect r, uint32_t width, uint32_t height) {
+    jpgpu_rect s = orientation_transposes(o) ? jpgpu_rect{r.y, r.x, r.height, r.width} : r;
+    if (orientation_flips_x(o)) s.x = width - s.x - s.width;
+    if (orientation_flips_y(o)) s.y = height - s.y - s.height;
+    return s;
+}
+
 // One input file as the caller handed it over: a list of segments (one for jpgpu_batch_upload), and the contiguous bytes the
 // host parser reads -- the file itself, or what was gathered of a multi-segment file (its head for the header-only plan, all
 // of it for the full marker walks).

@@ -167,6 +167,21 @@ struct ColorImage {
 };
 hipError_t launch_color_convert(hipStream_t stream, const uint8_t *scratch, uint8_t *out, const ColorImage *images, int n_images, uint64_t max_pixels,
                                 int format, const YccRgbFactors &kf, const OutputAffine &aff);
+// K3O (k3o_orient.hip): the images whose orientation is not 1 (include/jpgpu.h, "Orientation"), of every colour kind, from the INTERLEAVED_U8
+// samples K3's generic class left in `scratch` -- `width` x `height` pixels of the STORED frame (the image's window there), 1, 3 or 4 bytes
+// each by kind, tight -- to the batch's RGB format in `out`, turned: ONE launch for all of them, a descriptor per image, a workgroup per
+// tile of kOrientTile x kOrientTile source pixels.  src_off and dst_off are multiples of 256; `out` and `scratch` are different buffers.
+// max_tiles: the largest orient_tiles(width, height) among the descriptors.
+constexpr uint32_t kOrientTile = 64;
+constexpr uint32_t orient_tiles(uint32_t width, uint32_t height) { return ((width + kOrientTile - 1) / kOrientTile) * ((height + kOrientTile - 1) / kOrientTile); }
+struct OrientImage {
+    uint64_t src_off, dst_off;  // bytes into `scratch` / `out`
+    uint32_t width, height;     // of the stored window
+    uint32_t kind;              // ColorKind
+    uint32_t orientation;       // 2..8
+};
+hipError_t launch_orient_convert(hipStream_t stream, const uint8_t *scratch, uint8_t *out, const OrientImage *images, int n_images, uint32_t max_tiles,
+                                 int format, const YccRgbFactors &kf, const OutputAffine &aff);
 
 // Waves per workgroup of the POOLED form of the K2S final pass (k2s_subseq.hip: runs of scans that stage the same tables; one workgroup per CU, every wave takes the
 // next 64 lanes from a counter): 10 waves + 4 tables fill a CU's LDS.  Runs shorter than kSubFinalPoolMinChunks waves, and runs
