@@ -9,11 +9,13 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
 #include "encode_kernels.h"
 #include "kernels_device.h"
+#include "k2_wave.h"
 
 namespace jpgpu {
 
@@ -68,29 +70,19 @@ __global__ __launch_bounds__(256) void lut_pool_kernel(const DevHuffTable *__res
     }
 }
 
-#ifdef JPGPU_K2_PROFILE
-__device__ unsigned long long k2_prof[8];
-#define K2_TICK() __builtin_readcyclecounter()
-#define K2_PROF_ADD(i, v) do { if (lane == 0) atomicAdd(&k2_prof[i], (unsigned long long)(v)); } while (0)
-extern "C" int jpgpu_debug_k2_profile(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(k2_prof), sizeof(k2_prof)) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[8] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(k2_prof), z, sizeof z) != hipSuccess) return 1; }
-    return 0;
-}
-#else
-#define K2_TICK() 0ull
-#define K2_PROF_ADD(i, v) do { (void)(v); } while (0)
-#endif
+// per-wave cycle counters (tools/trace/k2_phases.py): [0] waves, [1] table staging, [2] stream init, [3] decode, [4] top-up, [5] flush, [6] total
+K2_PROF_DEFINE(k2_prof, jpgpu_debug_k2_profile)
 
 // One wave's 64 restart intervals wave_first .. wave_first + 63 of scan `scan_index` (tables staged, the wave's coefficient staging zero on
 // entry and on exit).
 __device__ __forceinline__ void k2_wave(const uint8_t *__restrict__ udata, const DevScan &s, uint32_t scan_index, uint32_t wave_first,
                                         const uint32_t *__restrict__ ends_u, DevScanStatus *__restrict__ status, int16_t *__restrict__ coefs,
-                                        const uint8_t *tabs, const uint32_t *blk_info, uint8_t *stage, uint8_t *ring, uint32_t lane,
-                                        unsigned long long k2_t0) {
-    struct { uint32_t scan; } wk = {scan_index};
+                                        const K2Group &g, uint32_t lane, unsigned long long k2_t0) {
+    const uint8_t *tabs = g.tabs;
+    const uint32_t *blk_info = g.blk_info;
+    uint8_t *stage = g.stage, *ring = g.ring;
     const unsigned long long k2_t1 = K2_TICK();
-    const DevScanStatus st = status[wk.scan];
+    const DevScanStatus st = status[scan_index];
     const uint32_t n_ends = st.n_ends;
     const uint32_t n_intervals = s.n_intervals;
     const uint32_t total_mcus = s.total_mcus;
@@ -111,26 +103,10 @@ __device__ __forceinline__ void k2_wave(const uint8_t *__restrict__ udata, const
         my_mcus = (interval == n_intervals - 1) ? total_mcus - interval * dri_eff : dri_eff;
         closed_by_marker = !(interval == n_ends - 1 && st.terminator == 0);
     }
-    const int32_t pm1_0 = (int32_t)((u0 & 3u) * 8u) - 1;             // bit position - 1, relative to the aligned origin
-    const int32_t endpos = pm1_0 + 1 + (int32_t)((u1 - u0) * 8u);    // first bit after the interval's data
     K2Feed feed;
     K2Pos pos;
-    {
-        const uint8_t *g = ubase + (u0 & ~3u);  // 4-byte aligned 16-byte loads; buffers are padded
-        uint4 c0, c1, c2, c3;
-        __builtin_memcpy(&c0, g, 16);
-        __builtin_memcpy(&c1, g + 16, 16);
-        __builtin_memcpy(&c2, g + 32, 16);
-        __builtin_memcpy(&c3, g + 48, 16);
-        __builtin_memcpy(&feed.nx, g + 64, 16);
-        k2_ring_write(ring, 0, c0);
-        k2_ring_write(ring, 1, c1);
-        k2_ring_write(ring, 2, c2);
-        k2_ring_write(ring, 3, c3);
-        feed.wr = 4;
-        feed.gp = g + 80;
-        k2_pos_init(pos, ring, pm1_0);
-    }
+    int32_t endpos = 0;  // first bit after the interval's data
+    k2_open_at_bit(ubase, u0, 0u, (u1 - u0) * 8u, ring, feed, pos, &endpos);
     // the wave iterates to the largest MCU count among its lanes (only the image's last interval is shorter)
     uint32_t wave_mcus = 0;
     if (wave_first < n_ends) {
@@ -145,9 +121,9 @@ __device__ __forceinline__ void k2_wave(const uint8_t *__restrict__ udata, const
     uint8_t *my_stage = stage + lane * 128;
     const uint32_t swz16 = ((lane >> 1) & 7u) << 4;  // XOR swizzle of the 16-byte chunks of the lane's staged block
 
-    // flush addressing: lane (blk, chunk) of pass `it` stores 16 bytes of the block staged by lane blk
+    // flush: whole 128-byte lines (k2_flush_dense) or, for a scan handed over as half-line planes (common.h: kScanSplitHandoff;
+    // wave-uniform), lane (blk, chunk) of a pass stores 16 bytes of a 64-byte slot
     const uint64_t coef_off = s.coef_off;
-    // ... or, for a scan handed over as half-line planes (common.h: kScanSplitHandoff; wave-uniform), 16 bytes of a 64-byte slot
     const bool split = (s.reserved0 & kScanSplitHandoff) != 0;
     uint8_t *split_lo = reinterpret_cast<uint8_t *>(coefs + coef_off * 64);
     const uint64_t split_hi_off = split_plane_lines(n_intervals, dri_eff, bpm) * 128;
@@ -164,31 +140,17 @@ __device__ __forceinline__ void k2_wave(const uint8_t *__restrict__ udata, const
             const unsigned long long k2_a = K2_TICK();
             int32_t lim = k2_limit(endpos, feed.wr);
             if (active && err == 0 && mcu < my_mcus) {
-                // ReadBlockBaseline (ref: ScanDecoder/JpegHuffmanBaselineScanDecoder.cs:179-222)
-                int32_t v, vb;
-                uint32_t ia = 0, adv_b = 0;
-                k2_symbol<true>(ring, feed, pos, endpos, lim, hdc, closed_by_marker, 0u, v, vb, ia, adv_b, err);
+                // (the predictor's select and write-back stay HERE, between the two pieces: see k2_decode_dc)
                 const int32_t pred = ci == 0 ? pred0 : (ci == 1 ? pred1 : (ci == 2 ? pred2 : pred3));
-                v += pred;
+                const int32_t v = k2_decode_dc(ring, feed, pos, endpos, lim, hdc, closed_by_marker, pred, err);
                 if (ci == 0) pred0 = v;
                 else if (ci == 1) pred1 = v;
                 else if (ci == 2) pred2 = v;
                 else pred3 = v;
-                *reinterpret_cast<int16_t *>(my_stage + swz16) = (int16_t)v;  // zig-zag index 0
-                uint32_t i2 = err == 0 ? 2u : 128u;  // 2 x zig-zag index of the next coefficient
-                while (i2 < 128u) {
-                    // one step = one symbol or, where the lookup held two, both (round 6): Math.Min(i++, 63) for a coefficient; EOB /
-                    // ZRL store a zero at a position nothing was written to yet; a step of one symbol stores it twice
-                    k2_symbol<false>(ring, feed, pos, endpos, lim, hac, closed_by_marker, i2, v, vb, ia, adv_b, err);
-                    const uint32_t at = ia - 2u < 126u ? ia - 2u : 126u;
-                    *reinterpret_cast<int16_t *>(my_stage + (at ^ swz16)) = (int16_t)v;
-                    i2 = ia + 2u * adv_b;
-                    const uint32_t at_b = i2 - 2u < 126u ? i2 - 2u : 126u;
-                    *reinterpret_cast<int16_t *>(my_stage + (at_b ^ swz16)) = (int16_t)vb;
-                }
+                k2_decode_ac(ring, feed, pos, endpos, lim, hac, closed_by_marker, v, my_stage, swz16, err);
                 // the block the reference throws in: blocks in front of it have reached the writer, this one and the rest have not
                 if (err != 0)
-                    atomicMax(&status[wk.scan].pad[1], fail_block_word(((uint64_t)interval * dri_eff + mcu) * bpm + b));
+                    atomicMax(&status[scan_index].pad[1], fail_block_word(((uint64_t)interval * dri_eff + mcu) * bpm + b));
             }
             // top up the ring HERE: the wait for the prefetched chunk then only covers memory operations issued before this
             // block was decoded (the chunk itself and the previous block's coefficient stores), never fresh ones
@@ -196,27 +158,17 @@ __device__ __forceinline__ void k2_wave(const uint8_t *__restrict__ udata, const
             k2_topup(ring, feed, pos.pm1);
             const unsigned long long k2_c = K2_TICK();
             // flush 64 blocks of this wave to the coefficient buffer as whole 128-byte lines, re-zero the staging
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            k2_wave_sync();
             if (!split) {
-#pragma unroll
-                for (int it = 0; it < 8; it++) {
-                    const uint32_t blk = it * 8 + (lane >> 3);
-                    const uint32_t chunk = lane & 7;
-                    uint4 *src = reinterpret_cast<uint4 *>(stage + blk * 128 + ((chunk ^ ((blk >> 1) & 7)) * 16));
-                    const uint4 v = *src;
-                    const uint4 z = {0, 0, 0, 0};
-                    *src = z;
+                // lane blk staged restart interval wave_first + blk: its block exists where the interval has this MCU
+                k2_flush_dense(stage, lane, [&](uint32_t blk, int16_t *&dst) {
                     const uint32_t owner = wave_first + blk;
-                    if (owner < n_ends) {
-                        const uint32_t owner_mcus = (owner == n_intervals - 1) ? total_mcus - owner * dri_eff : dri_eff;
-                        if (mcu < owner_mcus) {
-                            const uint64_t block_index = coef_off + ((uint64_t)owner * dri_eff + mcu) * bpm + b;
-                            *reinterpret_cast<uint4 *>(coefs + block_index * 64 + chunk * 8) = v;
-                        }
-                    }
-                }
+                    if (owner >= n_ends) return false;
+                    const uint32_t owner_mcus = (owner == n_intervals - 1) ? total_mcus - owner * dri_eff : dri_eff;
+                    if (mcu >= owner_mcus) return false;
+                    dst = coefs + (coef_off + ((uint64_t)owner * dri_eff + mcu) * bpm + b) * 64;
+                    return true;
+                });
             } else {
                 // half-line planes: lanes 8j .. 8j + 7 of a pass hold blocks 2p, 2p + 1 = restart intervals 2p, 2p + 1: one whole line of the
                 // lo plane, and -- when either block has a non-zero coefficient in 32..63 -- the same line of the hi plane
@@ -267,28 +219,26 @@ __device__ __forceinline__ void k2_wave(const uint8_t *__restrict__ udata, const
                 }
                 split_step++;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            k2_wave_sync();
             const unsigned long long k2_d = K2_TICK();
             k2_dec += k2_b - k2_a;
             k2_top += k2_c - k2_b;
             k2_fl += k2_d - k2_c;
         }
     }
-    K2_PROF_ADD(0, 1);
-    K2_PROF_ADD(1, k2_t1 - k2_t0);
-    K2_PROF_ADD(2, k2_t2 - k2_t1);
-    K2_PROF_ADD(3, k2_dec);
-    K2_PROF_ADD(4, k2_top);
-    K2_PROF_ADD(5, k2_fl);
-    K2_PROF_ADD(6, K2_TICK() - k2_t0);
+    K2_PROF_ADD(k2_prof, 0, 1);
+    K2_PROF_ADD(k2_prof, 1, k2_t1 - k2_t0);
+    K2_PROF_ADD(k2_prof, 2, k2_t2 - k2_t1);
+    K2_PROF_ADD(k2_prof, 3, k2_dec);
+    K2_PROF_ADD(k2_prof, 4, k2_top);
+    K2_PROF_ADD(k2_prof, 5, k2_fl);
+    K2_PROF_ADD(k2_prof, 6, K2_TICK() - k2_t0);
 
     if (active) {
         int32_t rem = endpos - (pos.pm1 + 1);
         if (rem < 0) rem = 0;
-        const uint32_t code = restart_check(s, st, &status[wk.scan], interval, n_ends, n_intervals, dri_eff, rem, err);
-        if (code != kNoError) atomicMin(&status[wk.scan].first_error, code);
+        const uint32_t code = restart_check(s, st, &status[scan_index], interval, n_ends, n_intervals, dri_eff, rem, err);
+        if (code != kNoError) atomicMin(&status[scan_index].first_error, code);
     }
 }
 
@@ -303,24 +253,12 @@ __global__ __launch_bounds__(64 * WAVES) void huffman_decode_kernel(const uint8_
                                                                     int16_t *__restrict__ coefs, int n_slots,
                                                                     const uint8_t *__restrict__ lut_pool, uint32_t tab_bytes) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t *tabs = smem;                  // tab_bytes: the batch's largest set of staged tables
-    uint8_t *wave_all = smem + tab_bytes;  // WAVES * kK2WaveBytes
-    uint32_t *blk_info = reinterpret_cast<uint32_t *>(wave_all + WAVES * kK2WaveBytes);  // [kMaxBlocksPerMcu]
     const HuffWork wk = work[blockIdx.x];
     const DevScan &s = scans[wk.scan];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned long long k2_t0 = K2_TICK();
-    // stage this scan's Huffman tables (ref: InitDecodeComponents resolves them per scan, JpegHuffmanScanDecoder.cs:63-64)
-    k2_stage_scan_tables(s, lut_pool, tabs, blk_info, n_slots, 64 * WAVES);
-    uint8_t *stage = wave_all + wave * kK2WaveBytes;
-    uint8_t *ring = stage + 8192 + lane * kK2RingStride;
-    {
-        const uint4 z = {0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 8; i++) reinterpret_cast<uint4 *>(stage)[i * 64 + lane] = z;
-    }
-    __syncthreads();
-    k2_wave(udata, s, wk.scan, wk.first_interval + wave * 64, ends_u, status, coefs, tabs, blk_info, stage, ring, lane, k2_t0);
+    const K2Group g = k2_group_setup(smem, tab_bytes, 64 * WAVES, s, lut_pool, n_slots);
+    k2_wave(udata, s, wk.scan, wk.first_interval + wave * 64, ends_u, status, coefs, g, lane, k2_t0);
 }
 
 // POOL (round 6; the K2S final pass has had it since round 5).  Runs of consecutive scans that stage the same tables in the same slots
@@ -337,48 +275,28 @@ __global__ __launch_bounds__(64 * WAVES) void huffman_pool_kernel(const uint8_t 
                                                                   int16_t *__restrict__ coefs, int n_slots, const uint8_t *__restrict__ lut_pool,
                                                                   uint32_t tab_bytes) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t *tabs = smem;
-    uint8_t *wave_all = smem + tab_bytes;
-    uint32_t *blk_info = reinterpret_cast<uint32_t *>(wave_all + WAVES * kK2WaveBytes);
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63;
     const unsigned long long k2_t0 = K2_TICK();
-    k2_stage_scan_tables(scans[work[0].scan], lut_pool, tabs, blk_info, n_slots, 64 * WAVES);  // (every entry of `work` stages the same)
-    uint8_t *stage = wave_all + wave * kK2WaveBytes;
-    uint8_t *ring = stage + 8192 + lane * kK2RingStride;
-    {
-        const uint4 z = {0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 8; i++) reinterpret_cast<uint4 *>(stage)[i * 64 + lane] = z;
-    }
-    __syncthreads();
-#if !defined(JPGPU_K2_TICKET_AHEAD)
-    for (;;) {
-        uint32_t c = 0;
-        if (lane == 0) c = atomicAdd(counter, 1u) - ticket_base;
-        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-        if (c >= n_chunks) break;
+    const K2Group g = k2_group_setup(smem, tab_bytes, 64 * WAVES, scans[work[0].scan], lut_pool, n_slots);  // (every entry of `work` stages the same)
+    for (uint32_t c; (c = k2_next_ticket(counter, ticket_base, lane)) < n_chunks;) {
         const HuffWork wk = work[c];
-        k2_wave(udata, scans[wk.scan], wk.scan, wk.first_interval, ends_u, status, coefs, tabs, blk_info, stage, ring, lane, c == 0 ? k2_t0 : K2_TICK());
+        k2_wave(udata, scans[wk.scan], wk.scan, wk.first_interval, ends_u, status, coefs, g, lane, c == 0 ? k2_t0 : K2_TICK());
     }
-#else
-    // (measured and NOT adopted, round 6: a wave drawing the ticket of its NEXT chunk before it starts on the one it holds, so that the
-    // counter's round trip lies under the chunk's first loads.  K2 4.93 -> 5.10 ms per 1024 x 4K, the benchmark canvases' Huffman stage
-    // 2.26 -> 2.48, DRI = 0 unchanged (profiles/r06_ticket_ahead_ab.txt): the loads of the chunk then queue behind the atomic in the
-    // wave's in-order counter, and a chunk waits for ITS wave.)
-    uint32_t c = 0;
-    if (lane == 0) c = atomicAdd(counter, 1u) - ticket_base;
-    c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-    while (c < n_chunks) {
-        uint32_t ahead = 0;
-        if (lane == 0) ahead = atomicAdd(counter, 1u) - ticket_base;
-        const HuffWork wk = work[c];
-        k2_wave(udata, scans[wk.scan], wk.scan, wk.first_interval, ends_u, status, coefs, tabs, blk_info, stage, ring, lane, c == 0 ? k2_t0 : K2_TICK());
-        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)ahead);
-    }
-#endif
 }
 
 static size_t k2_lds_bytes(uint32_t tab_bytes, int waves) { return (size_t)tab_bytes + (size_t)waves * kK2WaveBytes + kMaxBlocksPerMcu * sizeof(uint32_t); }
+
+// f(std::integral_constant<int, W>) for W = huffman_waves(tab_bytes): the kernels exist for 7 (eight AC tables) .. 11 waves
+template <class F>
+static hipError_t k2_with_waves(uint32_t tab_bytes, F f) {
+    switch (huffman_waves(tab_bytes)) {
+    case 11: return f(std::integral_constant<int, 11>{});
+    case 10: return f(std::integral_constant<int, 10>{});
+    case 9: return f(std::integral_constant<int, 9>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 7>{});
+    }
+}
 
 template <int WAVES>
 static hipError_t launch_huffman_w(hipStream_t stream, const uint8_t *data, const DevScan *scans, const HuffWork *work, int n_work,
@@ -399,16 +317,9 @@ hipError_t launch_huffman(hipStream_t stream, const uint8_t *data, const DevScan
                           const uint32_t *ends, DevScanStatus *status, const DevHuffTable *huff_pool, int16_t *coefs,
                           int n_slots, const uint8_t *lut_pool, uint32_t tab_bytes) {
     if (n_work <= 0) return hipSuccess;
-#define JPGPU_K2_CASE(W) case W: return launch_huffman_w<W>(stream, data, scans, work, n_work, ends, status, huff_pool, coefs, n_slots, lut_pool, tab_bytes)
-    switch (huffman_waves(tab_bytes)) {
-        JPGPU_K2_CASE(11);
-        JPGPU_K2_CASE(10);
-        JPGPU_K2_CASE(9);
-        JPGPU_K2_CASE(8);
-    default:
-        JPGPU_K2_CASE(7);  // (eight AC tables)
-    }
-#undef JPGPU_K2_CASE
+    return k2_with_waves(tab_bytes, [&](auto w) {
+        return launch_huffman_w<decltype(w)::value>(stream, data, scans, work, n_work, ends, status, huff_pool, coefs, n_slots, lut_pool, tab_bytes);
+    });
 }
 
 template <int WAVES>
@@ -429,16 +340,10 @@ hipError_t launch_huffman_pool(hipStream_t stream, const uint8_t *data, const De
                                uint32_t ticket_base, int groups, const uint32_t *ends, DevScanStatus *status, int16_t *coefs, int n_slots,
                                const uint8_t *lut_pool, uint32_t tab_bytes) {
     if (n_chunks <= 0 || groups <= 0) return hipSuccess;
-#define JPGPU_K2_CASE(W) case W: return launch_huffman_pool_w<W>(stream, data, scans, work, n_chunks, counter, ticket_base, groups, ends, status, coefs, n_slots, lut_pool, tab_bytes)
-    switch (huffman_waves(tab_bytes)) {
-        JPGPU_K2_CASE(11);
-        JPGPU_K2_CASE(10);
-        JPGPU_K2_CASE(9);
-        JPGPU_K2_CASE(8);
-    default:
-        JPGPU_K2_CASE(7);
-    }
-#undef JPGPU_K2_CASE
+    return k2_with_waves(tab_bytes, [&](auto w) {
+        return launch_huffman_pool_w<decltype(w)::value>(stream, data, scans, work, n_chunks, counter, ticket_base, groups, ends, status, coefs, n_slots,
+                                                         lut_pool, tab_bytes);
+    });
 }
 
 // Lookups of every table of the pool (once per upload: the tables of a batch do not change between decodes).

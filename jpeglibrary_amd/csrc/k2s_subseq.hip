@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "encode_kernels.h"
 #include "kernels_device.h"
+#include "k2_wave.h"
 
 namespace jpgpu {
 
@@ -913,19 +914,8 @@ __global__ __launch_bounds__(1024) void subseq_order_kernel(const DevScan *__res
     if (in_range) perm[s.sub_off + wk.first_interval / spl + base[key] + rank_in_key] = lane_index;
 }
 
-#ifdef JPGPU_K2_PROFILE  // per-wave cycle counters of the final pass (tools/trace/k2_phases.py dri0): [0] waves, [1] open + skip, [2] decode, [3] top-up, [4] flush, [5] total, [6] block steps, [7] lane-blocks
-__device__ unsigned long long sf_prof[8];
-#define SF_TICK() __builtin_readcyclecounter()
-#define SF_PROF_ADD(i, v) do { if (lane == 0) atomicAdd(&sf_prof[i], (unsigned long long)(v)); } while (0)
-extern "C" int jpgpu_debug_sf_profile(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(sf_prof), sizeof(sf_prof)) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[8] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(sf_prof), z, sizeof z) != hipSuccess) return 1; }
-    return 0;
-}
-#else
-#define SF_TICK() 0ull
-#define SF_PROF_ADD(i, v) do { (void)(v); } while (0)
-#endif
+// per-wave cycle counters of the final pass (tools/trace/k2_phases.py dri0): [0] waves, [1] open + skip, [2] decode, [3] top-up, [4] flush, [5] total, [6] block steps, [7] lane-blocks
+K2_PROF_DEFINE(sf_prof, jpgpu_debug_sf_profile)
 constexpr int kSubFinalMaxWaves = JPGPU_SF_WAVES > kSubFinalPoolWaves ? JPGPU_SF_WAVES : kSubFinalPoolWaves;  // the launch picks subseq_final_waves(n_slots) / the pool's
 constexpr int kSfWaveBytes = kK2WaveBytes;
 static_assert(kSfWaveBytes == (int)kSfWaveLdsBytes && kSubFinalPoolWaves == 11, "kernels.h: subseq_pool_fits");  // K2's staging + rings
@@ -934,10 +924,12 @@ static_assert(kSfWaveBytes == (int)kSfWaveLdsBytes && kSubFinalPoolWaves == 11, 
 __device__ __forceinline__ void sf_wave(const uint8_t *__restrict__ udata, const DevScan &s, const DevScanStatus &st, const HuffWork wk,
                                         const uint32_t *__restrict__ ends_u, DevScanStatus *__restrict__ status,
                                         const uint32_t *__restrict__ exit_state, const uint32_t *__restrict__ first_block,
-                                        const int4 *__restrict__ dc_entry, int16_t *__restrict__ coefs, const uint8_t *tabs,
-                                        const uint32_t *blk_info, uint8_t *stage, uint8_t *ring, uint32_t lane,
+                                        const int4 *__restrict__ dc_entry, int16_t *__restrict__ coefs, const K2Group &g, uint32_t lane,
                                         const uint32_t *__restrict__ perm, uint32_t spl) {
-    const unsigned long long sf_t0 = SF_TICK();
+    const uint8_t *tabs = g.tabs;
+    const uint32_t *blk_info = g.blk_info;
+    uint8_t *stage = g.stage, *ring = g.ring;
+    const unsigned long long sf_t0 = K2_TICK();
     unsigned long long sf_dec = 0, sf_top = 0, sf_fl = 0;
     const uint32_t ulen = ends_u[s.ends_off];
     const uint32_t total_bits = ulen * 8;
@@ -969,7 +961,8 @@ __device__ __forceinline__ void sf_wave(const uint8_t *__restrict__ udata, const
     // decodes them the way the reference does: from the all-ones padding, i.e. with no data bits at all (its loads still
     // have to stay inside the buffer: it opens the stream at bit 0 and sees it as empty).
     const bool behind_data = start_bit >= total_bits;
-    const int32_t pm1_0 = k2_open_at_bit(udata + s.data_off, behind_data ? 0u : start_bit, total_bits, ring, feed, pos, &endpos);
+    const uint32_t open_bit = behind_data ? 0u : start_bit;
+    const int32_t pm1_0 = k2_open_at_bit(udata + s.data_off, open_bit >> 3, open_bit & 7u, total_bits - open_bit, ring, feed, pos, &endpos);
     if (behind_data) endpos = pm1_0 + 1;
     int32_t lim = k2_limit(endpos, feed.wr);
     uint32_t err = 0;
@@ -1019,79 +1012,58 @@ __device__ __forceinline__ void sf_wave(const uint8_t *__restrict__ udata, const
     k2_topup(ring, feed, pos.pm1);
     uint8_t *my_stage = stage + lane * 128;
     const uint32_t swz16 = ((lane >> 1) & 7u) << 4;
-    const unsigned long long sf_t1 = SF_TICK();
+    const unsigned long long sf_t1 = K2_TICK();
 
     for (uint32_t j = 0; j < wave_count; j++) {
         for (uint32_t b = 0; b < bpm; b++) {
-            const unsigned long long sf_a = SF_TICK();
+            const unsigned long long sf_a = K2_TICK();
             const uint32_t bi = __builtin_amdgcn_readfirstlane(blk_info[b]);  // wave-uniform
             const uint32_t ci = bi & 0xFFu;
             const K2Tab hdc = k2_tab_dc(tabs, bi);
             const K2Tab hac = k2_tab_ac(tabs, bi);
             lim = k2_limit(endpos, feed.wr);
             if (j < count && err == 0) {
-                // ReadBlockBaseline (ref: ScanDecoder/JpegHuffmanBaselineScanDecoder.cs:179-222)
-                int32_t v, vb;
-                uint32_t ia = 0, adv_b = 0;
-                k2_symbol<true>(ring, feed, pos, endpos, lim, hdc, closed_by_marker, 0u, v, vb, ia, adv_b, err);
+                // (the predictor's select and write-back stay HERE, between the two pieces: see k2_decode_dc)
                 const int32_t pred = ci == 0 ? pred0 : (ci == 1 ? pred1 : (ci == 2 ? pred2 : pred3));
-                v += pred;
+                const int32_t v = k2_decode_dc(ring, feed, pos, endpos, lim, hdc, closed_by_marker, pred, err);
                 if (ci == 0) pred0 = v;
                 else if (ci == 1) pred1 = v;
                 else if (ci == 2) pred2 = v;
                 else pred3 = v;
-                *reinterpret_cast<int16_t *>(my_stage + swz16) = (int16_t)v;  // zig-zag index 0
-                uint32_t k2i = err == 0 ? 2u : 128u;
-                while (k2i < 128u) {
-                    // one step = one symbol or the two of a pair entry (see K2): a step of one symbol stores it twice
-                    k2_symbol<false>(ring, feed, pos, endpos, lim, hac, closed_by_marker, k2i, v, vb, ia, adv_b, err);
-                    const uint32_t at = ia - 2u < 126u ? ia - 2u : 126u;
-                    *reinterpret_cast<int16_t *>(my_stage + (at ^ swz16)) = (int16_t)v;
-                    k2i = ia + 2u * adv_b;
-                    const uint32_t at_b = k2i - 2u < 126u ? k2i - 2u : 126u;
-                    *reinterpret_cast<int16_t *>(my_stage + (at_b ^ swz16)) = (int16_t)vb;
-                }
+                k2_decode_ac(ring, feed, pos, endpos, lim, hac, closed_by_marker, v, my_stage, swz16, err);
                 // the block the reference throws in (see K2): in front of it every block has reached the writer
                 if (err != 0)
                     atomicMax(&status[wk.scan].pad[1], fail_block_word(((uint64_t)my_first + j) * bpm + b));
             }
-            const unsigned long long sf_b = SF_TICK();
+            const unsigned long long sf_b = K2_TICK();
             k2_topup(ring, feed, pos.pm1);
-            const unsigned long long sf_c = SF_TICK();
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int it = 0; it < 8; it++) {
-                const uint32_t blk = it * 8 + (lane >> 3);
-                const uint32_t chunk = lane & 7;
-                uint4 *src = reinterpret_cast<uint4 *>(stage + blk * 128 + ((chunk ^ ((blk >> 1) & 7)) * 16));
-                const uint4 v = *src;
-                const uint4 z = {0, 0, 0, 0};
-                *src = z;
+            const unsigned long long sf_c = K2_TICK();
+            k2_wave_sync();
+            const uint64_t first_b = coef_off + b;  // block b of the scan's first MCU
+            k2_flush_dense(stage, lane, [&](uint32_t blk, int16_t *&dst) {
                 // (round 6: the owner's first MCU and count come through the lane crossbar -- ds_bpermute, no storage -- where an LDS table of
                 // 512 bytes per wave held them: the eleventh wave of the pooled workgroup fits)
                 const uint32_t owner_first = (uint32_t)__shfl((int)my_first, (int)blk, 64), owner_count = (uint32_t)__shfl((int)count, (int)blk, 64);
-                if (j < owner_count) *reinterpret_cast<uint4 *>(coefs + (coef_off + ((uint64_t)owner_first + j) * bpm + b) * 64 + chunk * 8) = v;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const unsigned long long sf_d = SF_TICK();
+                if (j >= owner_count) return false;
+                dst = coefs + (first_b + ((uint64_t)owner_first + j) * bpm) * 64;
+                return true;
+            });
+            k2_wave_sync();
+            const unsigned long long sf_d = K2_TICK();
             sf_dec += sf_b - sf_a;
             sf_top += sf_c - sf_b;
             sf_fl += sf_d - sf_c;
         }
     }
-    SF_PROF_ADD(0, 1);
-    SF_PROF_ADD(1, sf_t1 - sf_t0);
-    SF_PROF_ADD(2, sf_dec);
-    SF_PROF_ADD(3, sf_top);
-    SF_PROF_ADD(4, sf_fl);
-    SF_PROF_ADD(5, SF_TICK() - sf_t0);
-    SF_PROF_ADD(6, (unsigned long long)wave_count * bpm);
+    K2_PROF_ADD(sf_prof, 0, 1);
+    K2_PROF_ADD(sf_prof, 1, sf_t1 - sf_t0);
+    K2_PROF_ADD(sf_prof, 2, sf_dec);
+    K2_PROF_ADD(sf_prof, 3, sf_top);
+    K2_PROF_ADD(sf_prof, 4, sf_fl);
+    K2_PROF_ADD(sf_prof, 5, K2_TICK() - sf_t0);
+    K2_PROF_ADD(sf_prof, 6, (unsigned long long)wave_count * bpm);
     const uint32_t sf_lane_blocks = wave_sum(count) * bpm;
-    SF_PROF_ADD(7, sf_lane_blocks);
+    K2_PROF_ADD(sf_prof, 7, sf_lane_blocks);
     if (live && err != 0) {
         // failure on the true path: same detail codes as the interval decoder; "interval" field carries the subsequence
         atomicMin(&status[wk.scan].first_error, (sub << 8) | err);
@@ -1121,52 +1093,20 @@ __global__ __launch_bounds__(64 * kSubFinalMaxWaves) void subseq_final_kernel(co
                                                                            int n_slots, uint32_t n_chunks, uint32_t *__restrict__ counter,
                                                                            const uint32_t *__restrict__ perm, uint32_t spl, uint32_t tab_bytes) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t n_waves = blockDim.x >> 6;
-    uint8_t *tabs = smem;                                                    // tab_bytes: the batch's largest set of staged tables
-    uint8_t *wave_all = smem + tab_bytes;                                    // n_waves * kSfWaveBytes
-    uint32_t *blk_info = reinterpret_cast<uint32_t *>(wave_all + n_waves * kSfWaveBytes);  // [kMaxBlocksPerMcu]
     const HuffWork wk0 = work[POOL ? 0u : blockIdx.x];  // POOL: `work` lists the run's waves (scan, first subsequence), all with one set of tables
     if (!POOL && status[wk0.scan].n_ends == 0) return;
-    k2_stage_scan_tables(scans[wk0.scan], lut_pool, tabs, blk_info, n_slots, blockDim.x);
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    uint8_t *stage = wave_all + wave * kSfWaveBytes;
-    uint8_t *ring = stage + 8192 + lane * kK2RingStride;
-    {
-        const uint4 z = {0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 8; i++) reinterpret_cast<uint4 *>(stage)[i * 64 + lane] = z;
-    }
-    __syncthreads();
+    const K2Group g = k2_group_setup(smem, tab_bytes, blockDim.x, scans[wk0.scan], lut_pool, n_slots);
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (!POOL) {
         const HuffWork wk = {wk0.scan, wk0.first_interval + wave * 64u * spl};
-        sf_wave(udata, scans[wk.scan], status[wk.scan], wk, ends_u, status, exit_state, first_block, dc_entry, coefs, tabs, blk_info, stage, ring, lane, perm, spl);
+        sf_wave(udata, scans[wk.scan], status[wk.scan], wk, ends_u, status, exit_state, first_block, dc_entry, coefs, g, lane, perm, spl);
     } else {
-#if !defined(JPGPU_K2_TICKET_AHEAD)
-        for (;;) {
-            uint32_t c = 0;
-            if (lane == 0) c = atomicAdd(counter, 1u);
-            c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-            if (c >= n_chunks) break;
+        for (uint32_t c; (c = k2_next_ticket(counter, 0u, lane)) < n_chunks;) {  // (the host clears these counters before every launch)
             const HuffWork wk = work[c];
             const DevScanStatus st = status[wk.scan];
             if (st.n_ends == 0) continue;
-            sf_wave(udata, scans[wk.scan], st, wk, ends_u, status, exit_state, first_block, dc_entry, coefs, tabs, blk_info, stage, ring, lane, perm, spl);
+            sf_wave(udata, scans[wk.scan], st, wk, ends_u, status, exit_state, first_block, dc_entry, coefs, g, lane, perm, spl);
         }
-#else
-        // (-DJPGPU_K2_TICKET_AHEAD: measured and not adopted, see huffman_pool_kernel in k2_huffman.hip)
-        uint32_t c = 0;
-        if (lane == 0) c = atomicAdd(counter, 1u);
-        c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
-        while (c < n_chunks) {
-            uint32_t ahead = 0;
-            if (lane == 0) ahead = atomicAdd(counter, 1u);
-            const HuffWork wk = work[c];
-            const DevScanStatus st = status[wk.scan];
-            if (st.n_ends != 0)
-                sf_wave(udata, scans[wk.scan], st, wk, ends_u, status, exit_state, first_block, dc_entry, coefs, tabs, blk_info, stage, ring, lane, perm, spl);
-            c = (uint32_t)__builtin_amdgcn_readfirstlane((int)ahead);
-        }
-#endif
     }
 }
 

@@ -5,6 +5,7 @@ Every image is checked against the oracle (coefficients, interleaved u8 samples,
 test asserts through Batch.plan_stats() that the batch took the branch the test is named for.  The inputs are made at test time
 with fixed seeds by jpegsynth, Pillow (its own optimised tables) and the oracle's optimizer (per-image tables)."""
 import io
+import os
 
 import numpy as np
 import pytest
@@ -310,6 +311,55 @@ def test_k2_file_with_more_table_slots_lowers_the_waves_of_the_batch():
     b.close()
 
 
+def _cmyk(w, h, q=90, blocks=0, seed=0):
+    """Pillow, CMYK noise: ONE interleaved scan of FOUR components at 1 x 1 (the fourth DC predictor) with the standard tables."""
+    from PIL import Image
+
+    rng = np.random.default_rng(seed)
+    buf = io.BytesIO()
+    kw = dict(quality=q)
+    if blocks:
+        kw["restart_marker_blocks"] = blocks
+    Image.fromarray(rng.integers(0, 256, size=(h, w, 4), dtype=np.uint8), "CMYK").save(buf, "JPEG", **kw)
+    data = buf.getvalue()
+    sos = _segments(data)[1]
+    assert data[sos + 4] == 4  # (Ns)
+    return data
+
+
+def _separated(files, seed0):
+    """The files with a scan of another shape between every two: no two of them share a run."""
+    out = []
+    for k, f in enumerate(files):
+        out += [f, _separator(seed0 + k)]
+    return out[:-1]
+
+
+def test_k2_corners_of_the_wave_through_the_plain_and_the_pooled_kernel():
+    """What K2's two kernels share with the K2S final pass (k2_wave.h), at the corners of it, each through huffman_decode_kernel (a scan
+    of one chunk) and through huffman_pool_kernel (two chunks or more): a scan of four interleaved components; a last restart interval
+    shorter than DRI beside full ones; waves with fewer than 64 live lanes (every plain scan here, the last chunk of every pooled one);
+    data that ends in the middle of a block (the fail-block record: the blocks in front of it reach the writer, no others).
+    264 x 16 at 4:4:4 with DRI 2 is 33 intervals, all of them full; 264 x 24 has 50 with one MCU in the last."""
+    four_plain, four_pool = _cmyk(64, 48, blocks=1, seed=1), _cmyk(104, 80, blocks=1, seed=2)
+    few_420, few_422 = _synth(64, 48, "420", 75, 1, seed=3), _synth(64, 48, "422", 75, 1, seed=4)
+    full = _synth(264, 16, "444", 75, 2, seed=5)
+    short_plain, short_pool = _synth(264, 24, "444", 75, 2, seed=6), _synth(104, 88, "444", 75, 2, seed=7)
+    assert [_intervals(f) for f in (four_plain, four_pool, few_420, few_422, full, short_plain, short_pool)] == [48, 130, 12, 24, 33, 50, 72]
+    assert (33 * 3) % 2 == 1 and (13 * 11) % 2 == 1  # (MCUs of the two `short` files: the last interval has one)
+    plain = [four_plain, few_420, few_422, full, short_plain, _cut(short_plain), _cut(four_plain)]
+    pooled = [four_pool, short_pool, _cut(short_pool), _cut(four_pool)]
+    files = _separated(plain + pooled, 1100)
+    refs = _refs(files)
+    kinds = [r.kind for r in refs[::2]]
+    assert kinds[:5] == ["OK"] * 5 and kinds[7:9] == ["OK"] * 2 and "OK" not in kinds[5:7] + kinds[9:], kinds
+    b, st, _ = _decode(files, refs)
+    assert st["huffman_waves"] == FULL_WAVES, st
+    assert st["k2_pools"] == len(pooled) and st["k2_pooled_chunks"] == sum(_chunks(f) for f in pooled) == 3 + 2 + 2 + 3, st
+    assert st["k2_plain_work"] == len(plain) + len(files) // 2, st  # (every plain scan and every separator: one chunk, one workgroup)
+    b.close()
+
+
 # ------------------------------------------------------------------------------------------------ K2S (DRI = 0)
 
 def test_k2s_pool_threshold_and_repeated_table_sets():
@@ -346,6 +396,34 @@ def test_k2s_pools_that_do_not_fit_beside_the_tables():
     b, st, refs = _decode([small, large, extra])
     assert refs[2].kind == "OK"
     assert st["k2s_scans"] == 3 and st["k2s_pools"] == 0, st
+    b.close()
+
+
+def test_k2s_corners_of_the_wave_through_the_plain_and_the_pooled_final_pass():
+    """The corners of test_k2_corners_... for the final pass, each in a run below 40 waves (subseq_final_kernel<false>) and in one above
+    (<true>): four interleaved components; a scan of a few dozen lanes; data that ends in the middle of a block; and a lane that owns
+    MCUs but starts behind the data (tests/golden/stress/dri0_invalid_code_late.jpg: 4:4:4, the standard tables -- alone, and in one
+    run with a large file of that shape).  Two uploads, each under 512 KB of DRI = 0 data: 512-bit subsequences, 40 waves = 160 KB."""
+    from golden_util import read_jpeg
+
+    four_plain, four_pool = _cmyk(96, 96, seed=11), _cmyk(288, 256, seed=12)
+    noise = _synth(96, 96, "420", 90, 0, seed=13)
+    files = [four_plain, noise, four_pool, _cut(four_pool), _cut(noise), _cut(four_plain)]
+    assert len(four_plain) < 80_000 and 200_000 < len(four_pool) and sum(map(len, files)) < 450_000
+    refs = _refs(files)
+    assert [r.kind == "OK" for r in refs] == [True, True, True, False, False, False]
+    b, st, _ = _decode(files, refs)
+    assert st["k2s_scans"] == 6 and st["k2s_pools"] == 1 and st["k2s_plain_work"] >= 4 and st["k2s_subs_per_lane"] == 1, st
+    b.close()
+
+    late = read_jpeg(os.path.join("stress", "dri0_invalid_code_late.jpg"))
+    large = _synth(768, 640, "444", 90, 0, seed=14)
+    assert _huffman_tables(late) == _huffman_tables(large) and 200_000 < len(large) < 450_000
+    files = [large, late, noise, late]
+    refs = _refs(files)
+    assert [r.kind for r in refs] == ["OK", "InvalidDataException", "OK", "InvalidDataException"]
+    b, st, _ = _decode(files, refs)
+    assert st["k2s_scans"] == 4 and st["k2s_pools"] == 1 and st["k2s_plain_work"] >= 2, st
     b.close()
 
 

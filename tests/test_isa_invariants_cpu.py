@@ -64,7 +64,7 @@ def test_no_hot_kernel_spills_or_uses_scratch(isa):
     names = re.findall(r"\.name:\s+(\S+)", isa)
     spills = dict(zip(names, re.findall(r"\.vgpr_spill_count:\s+(\d+)", isa)))
     scratch = dict(zip(names, re.findall(r"\.private_segment_fixed_size:\s+(\d+)", isa)))
-    hot = [n for n in names if any(k in n for k in ("idct_output_kernel", "huffman_decode_kernel", "subseq_round_kernel", "subseq_final_kernel",
+    hot = [n for n in names if any(k in n for k in ("idct_output_kernel", "huffman_decode_kernel", "huffman_pool_kernel", "subseq_round_kernel", "subseq_final_kernel",
                                                     "marker_count_kernel", "marker_write_kernel"))]
     assert len(hot) >= 20
     for n in hot:
