@@ -308,6 +308,8 @@ typedef struct jpgpu_plan_stats {
     int32_t k2s_pools;          /* pooled runs of the K2S final pass */
     int32_t k2s_table_sets;     /* distinct table sets among the K2S scans */
     int32_t k2s_subs_per_lane;  /* subsequences a lane of the K2S final pass takes */
+    int32_t k2s_sub_shift;      /* log2 of the subsequence length in bits the upload used; 0 without K2S scans */
+    int32_t k2s_subs;           /* subsequences over all K2S scans of the upload */
 } jpgpu_plan_stats;
 /* sizeof(jpgpu_plan_stats) as THIS library writes it. */
 size_t jpgpu_sizeof_plan_stats(void);

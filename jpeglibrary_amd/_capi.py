@@ -112,7 +112,7 @@ class Rect(C.Structure):
 class PlanStats(C.Structure):
     _fields_ = [("k2_plain_work", C.c_int32), ("k2_pools", C.c_int32), ("k2_pooled_chunks", C.c_int32), ("huffman_waves", C.c_int32),
                 ("k2s_scans", C.c_int32), ("k2s_plain_work", C.c_int32), ("k2s_pools", C.c_int32), ("k2s_table_sets", C.c_int32),
-                ("k2s_subs_per_lane", C.c_int32)]
+                ("k2s_subs_per_lane", C.c_int32), ("k2s_sub_shift", C.c_int32), ("k2s_subs", C.c_int32)]
 
 
 class ProgressivePlan(C.Structure):

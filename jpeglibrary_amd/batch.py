@@ -463,7 +463,8 @@ class Batch:
 
     def plan_stats(self):
         """How the last upload() planned the entropy stage (K2's plain list and pools, K2S's final-pass list, pools and table
-        sets) and K3: idct_work = work entries per output layout class (generic, YCbCr 1x1, 2x1, 2x2, gray, store of samples),
+        sets, k2s_subs_per_lane = subsequences a lane of the final pass takes, k2s_sub_shift = log2 of the subsequence length in bits,
+        0 without K2S scans, k2s_subs = subsequences over all K2S scans) and K3: idct_work = work entries per output layout class (generic, YCbCr 1x1, 2x1, 2x2, gray, store of samples),
         idct_split_work = those of them that belong to scans handed over as half-line planes, idct_listed_mcus = the MCUs all of K3's work
         entries list (under windows: the MCUs the windows touch)."""
         st = _capi.PlanStats()

@@ -418,6 +418,7 @@ class DeviceBatch {
     DevBuffer d_sub_final_work_;
     std::vector<SubseqPool> sub_pools_;  // pooled runs of the final pass: entries of d_sub_final_work_ behind the first n_sub_final_work_
     uint32_t total_subs_ = 0, max_subs_per_scan_ = 0;
+    int sub_shift_used_ = 0;  // the subsequence shift of the upload's K2S scans (0 without any): plan_stats
     std::vector<uint32_t> sub_scan_ids_;
     int last_subseq_rounds_ = 0;
     // Device-driven K2S rounds (launch_subseq_sync): the host enqueues a budget of rounds and reads the counts when it next

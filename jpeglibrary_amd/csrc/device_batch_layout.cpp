@@ -42,6 +42,9 @@ struct LayoutSwitches {
     int dbg_delay_scan = -1, dbg_delay_ms = 0;  // JPGPU_DEBUG_DELAY_SCAN="k:ms" (test hook, see plan_progressive_scan)
     bool dbg_status = false, prog_no_pipeline = false, no_subseq = false;  // JPGPU_DEBUG_STATUS, JPGPU_PROG_NO_PIPELINE, JPGPU_NO_SUBSEQ
     uint32_t subseq_shift = 0;                  // JPGPU_SUBSEQ_SHIFT, 8..14; 0 = unset
+    // subsequences in the batch from which a lane of the K2S final pass takes two (test hook: 1 = always, so a small batch reaches
+    // the form the planner otherwise keeps for kSubFinalFewSubs and more)
+    uint64_t subseq_two_per_lane_from = kSubFinalFewSubs;  // JPGPU_SUBSEQ_TWO_PER_LANE_FROM
     // a scan with fewer restart intervals than this gets one WAVE per interval (progressive_stream_kernel)
     uint32_t stream_max_intervals = 16;         // JPGPU_PROG_STREAM_MAX_INTERVALS
     // polls (~2-3 us each) a follower scan of the pipelined launch may spend before it gives up: ~0.3 s by default (a fully
@@ -65,6 +68,7 @@ LayoutSwitches read_layout_switches() {
     if (dd && sscanf(dd, "%d:%d", &sw.dbg_delay_scan, &sw.dbg_delay_ms) != 2) sw.dbg_delay_scan = -1;
     sw.dbg_status = set("JPGPU_DEBUG_STATUS");
     if (const char *ev = getenv("JPGPU_SUBSEQ_SHIFT")) sw.subseq_shift = (uint32_t)std::min(14, std::max(8, atoi(ev)));
+    if (const char *ev = getenv("JPGPU_SUBSEQ_TWO_PER_LANE_FROM")) sw.subseq_two_per_lane_from = strtoull(ev, nullptr, 10);
     if (const char *ev = getenv("JPGPU_PROG_STREAM_MAX_INTERVALS")) sw.stream_max_intervals = (uint32_t)atoi(ev);
     sw.prog_no_pipeline = set("JPGPU_PROG_NO_PIPELINE");
     if (const char *ev = getenv("JPGPU_PROG_SPIN_BUDGET")) sw.prog_spin_budget = (uint32_t)strtoul(ev, nullptr, 10);
@@ -188,6 +192,7 @@ void DeviceBatch::reset_upload_state(const UploadPlan &p) {
     orient_convert_.clear();
     sub_scan_ids_.clear();
     total_subs_ = max_subs_per_scan_ = 0;
+    sub_shift_used_ = 0;
     k2s_budget_ = 0;
     sub_same_valid_ = k2s_unchecked_ = k2s_idct_behind_ = false;
     // (A/B switch: the host reads the counts between rounds.  Always so over a CALLER'S CANVAS: the device-driven rounds let the
@@ -492,6 +497,7 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
                             !(entropy_only_ && ii < preset_no_subseq_.size() && preset_no_subseq_[ii]);
     if (use_subseq) {
         s.sub_shift = (uint8_t)p.subseq_shift;
+        sub_shift_used_ = (int)p.subseq_shift;
         s.n_subs = (uint32_t)((((uint64_t)s.data_len * 8) + ((1u << p.subseq_shift) - 1)) >> p.subseq_shift);
         s.sub_off = total_subs_;
         total_subs_ += s.n_subs;
@@ -698,7 +704,7 @@ void DeviceBatch::plan_subseq_lists(UploadPlan &p) {
 #ifdef JPGPU_SF_ONE_SUB  // (A/B build variant)
     sub_final_spl_ = 1;
 #else
-    sub_final_spl_ = (kSubFinalSubsPerLane >= 2 && total_subs_ >= kSubFinalFewSubs) ? 2 : 1;
+    sub_final_spl_ = (kSubFinalSubsPerLane >= 2 && total_subs_ >= p.sw.subseq_two_per_lane_from) ? 2 : 1;
 #endif
     const uint32_t lanes_subs = 64u * (uint32_t)sub_final_spl_;
     std::vector<HuffWork> pooled;

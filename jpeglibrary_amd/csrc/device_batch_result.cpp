@@ -427,6 +427,8 @@ void DeviceBatch::plan_stats(jpgpu_plan_stats *st) const {
     st->k2s_pools = (int32_t)sub_pools_.size();
     st->k2s_table_sets = n_sr_sets_;
     st->k2s_subs_per_lane = sub_final_spl_;
+    st->k2s_sub_shift = sub_shift_used_;
+    st->k2s_subs = (int32_t)total_subs_;
 }
 
 void DeviceBatch::progressive_plan(jpgpu_progressive_plan *p) const {

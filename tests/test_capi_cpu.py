@@ -36,7 +36,7 @@ def test_version_and_strings():
     # the struct every *_result call fills in whole: the binding's mirror must have the library's size
     import ctypes
     assert _capi.lib.jpgpu_sizeof_image_result() == ctypes.sizeof(_capi.ImageResult) == 28
-    assert _capi.lib.jpgpu_sizeof_plan_stats() == ctypes.sizeof(_capi.PlanStats) == 36
+    assert _capi.lib.jpgpu_sizeof_plan_stats() == ctypes.sizeof(_capi.PlanStats) == 44
     assert _capi.lib.jpgpu_sizeof_progressive_plan() == ctypes.sizeof(_capi.ProgressivePlan) == 56
     assert _capi.lib.jpgpu_status_string(1) == b"InvalidDataException"
     assert _capi.lib.jpgpu_detail_string(4) == b"Expect restart marker."

@@ -114,7 +114,7 @@ def test_the_abi_has_the_resize_symbols_and_keeps_its_version():
     assert lib.jpgpu_version() == 101 and "#define JPGPU_VERSION 101" in header
     # no existing struct changed size
     assert C.sizeof(_capi.ImageInfo) == 160 and lib.jpgpu_sizeof_image_result() == C.sizeof(_capi.ImageResult) == 28
-    assert lib.jpgpu_sizeof_plan_stats() == 36 and lib.jpgpu_sizeof_rect() == 16 and lib.jpgpu_sizeof_device_ingest_stats() == 40
+    assert lib.jpgpu_sizeof_plan_stats() == 44 and lib.jpgpu_sizeof_rect() == 16 and lib.jpgpu_sizeof_device_ingest_stats() == 40
     for name in ("set_resize", "resized", "resized_tensor", "resize_ms"):
         assert callable(getattr(jl.Batch, name)), name
     assert callable(jl.decode_resized) and "decode_resized" in jl.__all__
