@@ -443,6 +443,46 @@ int jpgpu_batch_image_orientation(const jpgpu_batch *b, int i, int *orientation)
  * frame header or with broken headers -- never for a broken Exif block; JPGPU_ERR_ARGUMENT for a NULL argument. */
 int jpgpu_identify_orientation(const uint8_t *file, size_t len, int *orientation);
 
+/* ---- Chroma upsampling: libjpeg's "fancy" (triangle) filter in place of the reference's sample replication, applied in the output stage (an
+ * extension beyond the reference; the switch DALI and nvJPEG call fancy_upsampling).
+ *   By default (JPGPU_UPSAMPLE_REPLICATE) a sub-sampled chroma sample is repeated over the pixels it covers, as the reference does, bit for
+ * bit as before.  Under JPGPU_UPSAMPLE_FANCY an image is FILTERED when all of these hold: its colour kind is YCbCr (a three-component frame
+ * under JPGPU_COLOR_YCC, kind YCBCR under JPGPU_COLOR_FILE); its precision is 8; component 0 carries the frame's maximal sampling factors;
+ * components 1 and 2 have equal factors and (hs, vs) = (Hmax / H1, Vmax / V1) is (2, 1), (2, 2) or (1, 2); and, for hs == 2, the chroma plane
+ * is more than two samples wide, cw = ceil(W / 2) > 2 (libjpeg takes its replicating routine for narrower planes).  Every other image --
+ * grey, 4:4:4, 4:1:1 and other ratios, the RGB, CMYK and YCCK kinds, other precisions -- decodes exactly as under REPLICATE.
+ *   The function.  With I the INTERLEAVED_U8 decode of the same file (stored orientation, whole frame), the native chroma samples are
+ * C_c[j][i] = I[j * vs][i * hs][c] for c = 1, 2, i < cw = ceil(W / hs), j < ch = ceil(H / vs); indices clamp to that REAL extent, never to
+ * the MCU padding; luma is I[y][x][0], unchanged.  For pixel (x, y), in integers:
+ *     vertical (vs == 2):    j = y >> 1; jf = j - 1 for even y, j + 1 for odd y, clamped; s[i] = 3 * C[j][i] + C[jf][i]; rb = 1 for even y, 2 for odd
+ *     horizontal (hs == 2):  i = x >> 1; in = i - 1 for even x, i + 1 for odd x, clamped
+ *     h2v1:  (3 * C[y][i] + C[y][in] + (x even ? 1 : 2)) >> 2
+ *     h1v2:  (s[x] + rb) >> 2
+ *     h2v2:  (3 * s[i] + s[in] + (x even ? 8 : 7)) >> 4
+ * which is libjpeg's h2v1 / h2v2 / h1v2 fancy upsampler, its special first and last columns included.  The output sample is what the
+ * format's own path makes of (Y, Cb', Cr'): the RGB_U8 conversion, then the alpha byte, the plane split and the per-sample affine step of the
+ * float forms.  Everything behind it composes on the filtered picture: a window is that slice of the filtered whole decode, bit for bit; an
+ * orientation turns it; the resize stage resamples it; a file that fails gives the filter of its partial picture.
+ *   Only RGB_U8, RGBA_U8 and RGB_PLANAR_U8 / _F16 / _F32 read the policy; every other format decodes as before.  The policy is state of the
+ * batch like the colour policy: every later upload of whole files reads it until it is set again.  Sizes, planes and out_bytes are what
+ * REPLICATE reports; out_offset of the image behind a filtered one follows the rule of the colour kinds: use out_offset.
+ *   Not claimed: equality with libjpeg's RGB.  The IDCT here is the reference's float one and the colour arithmetic the reference's, not
+ * libjpeg's integer IDCT, fixed-point conversion or merged upsampling; YCCK chroma stays replicated.
+ *   Not covered: jpgpu_decoder_*, jpgpu_decode_scan, jpgpu_progressive_*, jpgpu_multi_*, jpgpu_batch_upload_frames (they replicate). */
+typedef enum jpgpu_upsampling_policy {
+    JPGPU_UPSAMPLE_REPLICATE = 0, /* the reference's sample replication */
+    JPGPU_UPSAMPLE_FANCY = 1      /* libjpeg's triangle filter for h2v1, h2v2 and h1v2 YCbCr images */
+} jpgpu_upsampling_policy;
+/* JPGPU_ERR_ARGUMENT for any other value. */
+int jpgpu_batch_set_upsampling_policy(jpgpu_batch *b, int policy);
+/* 1 where image i was planned with the filter, else 0 (an image the rule leaves replicated, a format that does not read the policy, an
+ * image that failed at upload).  Valid after an upload; JPGPU_ERR_ARGUMENT for a NULL argument or an index out of range. */
+int jpgpu_batch_image_upsampling(const jpgpu_batch *b, int i, int *applied);
+/* Measuring aid.  Device time of the last call of the upsampling kernels (K3U) of this upload, from an event pair of its own (synchronises).
+ * The pair is recorded only for an upload made while the environment holds JPGPU_TIME_UPSAMPLE=1, so that no other decode pays for it;
+ * JPGPU_ERR_INVALID_OPERATION otherwise, and when the upload has no filtered image or has not been decoded. */
+int jpgpu_batch_upsampling_ms(jpgpu_batch *b, float *ms);
+
 /* Coefficient hand-off for multi-scan (progressive, SOF2) images -- BASELINE config 5's "coefficient accumulate then single
  * IDCT pass": the caller's progressive entropy decoder accumulates the coefficient store, the GPU runs what
  * JpegHuffmanProgressiveScanDecoder.Dispose (ScanDecoder/JpegHuffmanProgressiveScanDecoder.cs:421-470: dequantise, IDCT,

@@ -134,6 +134,8 @@ COLOR_POLICIES = ("ycc", "file")
 COLOR_KINDS = ("gray", "ycbcr", "rgb", "cmyk", "ycck")
 # jpgpu_orientation_policy, by its Python names
 ORIENTATION_POLICIES = ("stored", "file")
+# jpgpu_upsampling_policy, by its Python names
+UPSAMPLING_POLICIES = ("replicate", "fancy")
 
 UPLOAD_PINNED = 1
 UPLOAD_PINNED_ARENA = 2
@@ -194,6 +196,9 @@ SYMBOLS = [
     ("jpgpu_batch_set_orientations", C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int]),
     ("jpgpu_batch_image_orientation", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("jpgpu_identify_orientation", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
+    ("jpgpu_batch_set_upsampling_policy", C.c_int, [_P, C.c_int]),
+    ("jpgpu_batch_image_upsampling", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("jpgpu_batch_upsampling_ms", C.c_int, [_P, C.POINTER(C.c_float)]),
     ("jpgpu_sizeof_device_ingest_stats", C.c_size_t, []),
     ("jpgpu_batch_device_ingest_stats", C.c_int, [_P, C.POINTER(DeviceIngestStats)]),
     ("jpgpu_batch_upload_frames", C.c_int, [_P, C.POINTER(Frame), C.c_void_p, C.c_int, C.c_int]),

@@ -160,6 +160,14 @@ def _orientation_policy(orientation, who="orientation"):
     return _capi.ORIENTATION_POLICIES.index(orientation)
 
 
+def _upsampling_policy(upsampling, who="upsampling"):
+    """The check of Batch.set_upsampling_policy / decode_batch(upsampling=...), before any library call: "replicate" or "fancy" -> the
+    jpgpu_upsampling_policy value"""
+    if not isinstance(upsampling, str) or upsampling not in _capi.UPSAMPLING_POLICIES:
+        raise ValueError('%s is "replicate" (a chroma sample repeated over its pixels) or "fancy" (libjpeg\'s triangle filter), not %r' % (who, upsampling))
+    return _capi.UPSAMPLING_POLICIES.index(upsampling)
+
+
 def _orientation_list(orientations, n_files=None):
     """The checks of Batch.set_orientations / decode_batch(orientations=...), before any library call: integers 0..8, one per file (0 = what
     the policy gives); n_files: the count they must match.  None -> None."""
@@ -333,6 +341,28 @@ class Batch:
         o = C.c_int()
         raise_for_status(_lib.jpgpu_batch_image_orientation(self._h, i, C.byref(o)), b"jpgpu_batch_image_orientation: no such image")
         return o.value
+
+    def set_upsampling_policy(self, upsampling):
+        """How the RGB formats (RGB_U8, RGBA_U8, RGB_PLANAR_U8 / _F16 / _F32) expand sub-sampled chroma from the next upload on: "replicate",
+        the default -- every chroma sample repeated over the pixels it covers, as the reference does -- or "fancy": libjpeg's triangle filter
+        for 4:2:2, 4:2:0 and 4:4:0 YCbCr images (include/jpgpu.h, "Chroma upsampling"), the chroma Pillow, torchvision and OpenCV deliver.
+        State of the batch: it holds until set again.  ValueError, before the library is called, for any other value."""
+        self._check(_lib.jpgpu_batch_set_upsampling_policy(self._h, _upsampling_policy(upsampling)))
+        return self
+
+    def upsampling(self, i):
+        """1 where image i was planned with the "fancy" filter, else 0 (grey, 4:4:4, other ratios and kinds, planes two samples wide, a format
+        that does not read the policy)"""
+        a = C.c_int()
+        raise_for_status(_lib.jpgpu_batch_image_upsampling(self._h, i, C.byref(a)), b"jpgpu_batch_image_upsampling: no such image")
+        return a.value
+
+    def upsampling_ms(self):
+        """device time of this upload's last K3U call, from an event pair of its own (synchronises); only for an upload made under
+        JPGPU_TIME_UPSAMPLE=1 that has a filtered image and was decoded -- a measuring aid (tools/bench_decode_upsample.py)"""
+        ms = C.c_float()
+        self._check(_lib.jpgpu_batch_upsampling_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def window(self, i):
         """(x, y, w, h): the window image i was planned with, in pixels of the oriented frame; (0, 0, W, H) of that frame for a whole one"""
@@ -616,20 +646,23 @@ class Batch:
             pass
 
 
-def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None):
+def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate"):
     """One-call helper: returns (outputs, results).  files: bytes-like objects, or 1-D uint8 torch tensors on the context's device.
     windows: one (x, y, w, h) per file (Batch.set_windows): outputs[i] is that rectangle of image i.
     color: "ycc" or "file" (Batch.set_color_policy): under "file" the RGB formats deliver RGB for CMYK, YCCK and Adobe-RGB files.
     orientation: "stored" or "file" (Batch.set_orientation_policy); orientations: one value 0..8 per file (Batch.set_orientations).  Windows
-    are then in pixels of the oriented frame."""
+    are then in pixels of the oriented frame.
+    upsampling: "replicate" or "fancy" (Batch.set_upsampling_policy): under "fancy" the RGB formats filter 4:2:2 / 4:2:0 / 4:4:0 chroma as libjpeg does."""
     files = list(files)
     windows = _window_rects(windows, len(files))
     _color_policy(color)
     _orientation_policy(orientation)
+    _upsampling_policy(upsampling)
     orientations = _orientation_list(orientations, len(files))
     b = Batch(ctx)
     b.set_color_policy(color)
     b.set_orientation_policy(orientation)
+    b.set_upsampling_policy(upsampling)
     if orientations is not None:
         b.set_orientations(orientations)
     if windows is not None:
@@ -644,7 +677,7 @@ def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="y
     return outs, results
 
 
-def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None):
+def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate"):
     """One-call helper for torch consumers: returns (tensors, results), tensors[i] = Batch.output_tensor(i) -- uint8[3, H, W] on the
     context's device by default -- or None for an image that failed.  Nothing is downloaded.  The batch is not closed: its output
     buffer is the tensors' memory and is freed with the last of them.  files: bytes-like objects, or 1-D uint8 torch tensors on the
@@ -657,11 +690,14 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     taking the YCbCr matrix.
     orientation: "stored" or "file" (Batch.set_orientation_policy): under "file" an image is turned as its Exif orientation says, so
     tensors[i] is [3, W, H] for the values 5..8; orientations: one value 0..8 per file (Batch.set_orientations), e.g. 2 for a horizontal flip.
-    Windows are then in pixels of the oriented frame."""
+    Windows are then in pixels of the oriented frame.
+    upsampling: "replicate" or "fancy" (Batch.set_upsampling_policy): under "fancy" sub-sampled chroma (4:2:2, 4:2:0, 4:4:0) is expanded with
+    libjpeg's triangle filter, as Pillow, torchvision and OpenCV deliver it, instead of repeated; windows, orientation and dtype compose on it."""
     files = list(files)
     windows = _window_rects(windows, len(files))
     _color_policy(color)
     _orientation_policy(orientation)
+    _upsampling_policy(upsampling)
     orientations = _orientation_list(orientations, len(files))
     if dtype is not None:
         import torch
@@ -679,6 +715,7 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     b = Batch(ctx)
     b.set_color_policy(color)
     b.set_orientation_policy(orientation)
+    b.set_upsampling_policy(upsampling)
     if orientations is not None:
         b.set_orientations(orientations)
     if mean is not None:
@@ -693,7 +730,7 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     return tensors, results
 
 
-def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None, color="ycc", orientation="stored", orientations=None):
+def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate"):
     """One-call helper for fixed-size consumers: returns (tensor, results), tensor = Batch.resized_tensor() -- ONE [N, 3, oh, ow] tensor on the
     context's device, size = (oh, ow), dtype torch.float16 (the default), torch.float32 or torch.uint8 -- every image decoded to RGB and
     resampled to that size (antialiased bilinear) in one launch behind the output stage; the slab of an image that failed is zero and
@@ -702,13 +739,15 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
     units; both or neither) make the float samples (v / 255 - mean) / std through affine_from_mean_std; they are refused for torch.uint8.
     windows: one (x, y, w, h) per file (Batch.set_windows): that rectangle of image i is what is resampled -- a RandomResizedCrop's crop.
     color: "ycc" or "file" (Batch.set_color_policy), orientation and orientations (Batch.set_orientation_policy / set_orientations), as in
-    decode_to_tensors: the oriented image is what is resampled."""
+    decode_to_tensors: the oriented image is what is resampled.  upsampling: "replicate" or "fancy" (Batch.set_upsampling_policy): under "fancy"
+    the image that is resampled has libjpeg's filtered chroma."""
     import torch
 
     files = list(files)
     windows = _window_rects(windows, len(files))
     _color_policy(color)
     _orientation_policy(orientation)
+    _upsampling_policy(upsampling)
     orientations = _orientation_list(orientations, len(files))
     dtype = torch.float16 if dtype is None else dtype
     _resize_setting(size, dtype)
@@ -721,6 +760,7 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
     b = Batch(ctx)
     b.set_color_policy(color)
     b.set_orientation_policy(orientation)
+    b.set_upsampling_policy(upsampling)
     if orientations is not None:
         b.set_orientations(orientations)
     if consts is not None:

@@ -429,6 +429,9 @@ int jpgpu_identify_color(const uint8_t *file, size_t len, int *kind) {
 int jpgpu_batch_set_orientation_policy(jpgpu_batch *b, int policy) { JPGPU_GUARD(b, b->impl.set_orientation_policy(policy)); }
 int jpgpu_batch_set_orientations(jpgpu_batch *b, const uint8_t *orientations, int n) { JPGPU_GUARD(b, b->impl.set_orientations(orientations, n)); }
 int jpgpu_batch_image_orientation(const jpgpu_batch *b, int i, int *orientation) { return b ? b->impl.image_orientation(i, orientation) : JPGPU_ERR_ARGUMENT; }
+int jpgpu_batch_set_upsampling_policy(jpgpu_batch *b, int policy) { JPGPU_GUARD(b, b->impl.set_upsampling_policy(policy)); }
+int jpgpu_batch_image_upsampling(const jpgpu_batch *b, int i, int *applied) { return b ? b->impl.image_upsampling(i, applied) : JPGPU_ERR_ARGUMENT; }
+int jpgpu_batch_upsampling_ms(jpgpu_batch *b, float *ms) { JPGPU_GUARD(b, b->impl.upsampling_ms(ms)); }
 // Host only: Identify's walk up to the first SOS, which records the first Exif APP1 on its way (ingest_host.h: exif_orientation_of).
 int jpgpu_identify_orientation(const uint8_t *file, size_t len, int *orientation) {
     if (!file || !orientation) return JPGPU_ERR_ARGUMENT;

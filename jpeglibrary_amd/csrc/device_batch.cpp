@@ -43,7 +43,7 @@ void DevBuffer::release() {
 
 DeviceBatch::~DeviceBatch() {
     if (ctx_) (void)hipSetDevice(ctx_->device);
-    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_color_images_, &d_orient_images_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
+    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_color_images_, &d_orient_images_, &d_fancy_images_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
         b->release();
     for (hipEvent_t &e : ev_pool_)
         if (e) (void)hipEventDestroy(e);
@@ -51,6 +51,8 @@ DeviceBatch::~DeviceBatch() {
     for (hipEvent_t ev : gather_ev_)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : resize_ev_)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : fancy_ev_)
         if (ev) (void)hipEventDestroy(ev);
     if (h_k1_giveup_) (void)hipHostFree(h_k1_giveup_);
 }
@@ -63,7 +65,29 @@ int DeviceBatch::hip_fail(hipError_t e, const char *what) {
     return fail(e == hipErrorOutOfMemory ? JPGPU_ERR_OUT_OF_MEMORY : JPGPU_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+bool DeviceBatch::fancy_filtered(int policy, int format, const ImagePlan &img) {
+    return policy == JPGPU_UPSAMPLE_FANCY && fmt_is_rgb(format) && img.color_kind == kColorYcbcr && img.num_components == 3 && img.precision == 8 &&
+           k3u_ratio_filtered(img.chroma_hs, img.chroma_vs, img.width);
+}
+
+jpgpu_rect DeviceBatch::fancy_fetch_rect(const ImagePlan &img) {
+    const K3uSpan x = k3u_fetch_span(img.win.x, img.win.x + img.win.width, img.width, img.chroma_hs);
+    const K3uSpan y = k3u_fetch_span(img.win.y, img.win.y + img.win.height, img.height, img.chroma_vs);
+    return jpgpu_rect{x.lo, y.lo, x.hi - x.lo, y.hi - y.lo};
+}
+
+// (16 bytes behind the fetch rectangle stay unused: K3U's 12-byte loads of a line's last pixels end there)
+uint64_t DeviceBatch::fancy_staging_offset(const ImagePlan &img) {
+    const jpgpu_rect f = fancy_fetch_rect(img);
+    return ((uint64_t)f.width * f.height * 3 + 16 + 255) / 256 * 256;
+}
+
 uint64_t DeviceBatch::slot_bytes(const ImagePlan &img) {
+    if (img.fancy) {  // the fetch rectangle's samples, and behind them the staged window of an image that is turned as well
+        const jpgpu_rect f = fancy_fetch_rect(img);
+        const uint64_t samples = img.orientation != 1 ? fancy_staging_offset(img) + (uint64_t)img.win.width * img.win.height * 3 : (uint64_t)f.width * f.height * 3;
+        return std::max(img.out_bytes, samples);
+    }
     const bool through_scratch = color_kind_by_file(img.color_kind) || img.orientation != 1;
     const uint64_t samples = through_scratch ? (uint64_t)img.win.width * img.win.height * color_kind_sample_bytes(img.color_kind) : 0u;
     return std::max(img.out_bytes, samples);
@@ -97,6 +121,27 @@ int DeviceBatch::set_orientations(const uint8_t *orientations, int n) {
     return JPGPU_OK;
 }
 
+int DeviceBatch::set_upsampling_policy(int policy) {
+    if (policy != JPGPU_UPSAMPLE_REPLICATE && policy != JPGPU_UPSAMPLE_FANCY) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_set_upsampling_policy: unknown policy");
+    upsample_policy_ = policy;
+    return JPGPU_OK;
+}
+
+int DeviceBatch::image_upsampling(int i, int *applied) const {
+    const ImagePlan *img = image(i);
+    if (!img || !applied) return JPGPU_ERR_ARGUMENT;
+    *applied = img->status == JPGPU_OK && img->fancy ? 1 : 0;
+    return JPGPU_OK;
+}
+
+int DeviceBatch::upsampling_ms(float *ms) {
+    if (!ms) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upsampling_ms: null argument");
+    if (!fancy_timed_) return fail(JPGPU_ERR_INVALID_OPERATION, "jpgpu_batch_upsampling_ms: no K3U call of this upload was timed (JPGPU_TIME_UPSAMPLE=1 at the upload, a filtered image, a decode)");
+    if (const int rc = sync(); rc != JPGPU_OK) return rc;
+    if (hipEventElapsedTime(ms, fancy_ev_[0], fancy_ev_[1]) != hipSuccess) return fail(JPGPU_ERR_DEVICE, "hipEventElapsedTime failed");
+    return JPGPU_OK;
+}
+
 int DeviceBatch::image_orientation(int i, int *orientation) const {
     const ImagePlan *img = image(i);
     if (!img || !orientation) return JPGPU_ERR_ARGUMENT;
@@ -111,6 +156,16 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
     img.precision = fh.precision;
     img.num_components = fh.num_components;
     img.color_kind = fh.num_components == 1 ? kColorGray : kColorYcbcr;
+    // (what the frame says about its chroma; whether the image is filtered is apply_window's decision)
+    img.chroma_hs = img.chroma_vs = 0;
+    img.fancy = false;
+    if (fh.num_components == 3 && fh.components.size() == 3) {
+        const auto &c0 = fh.components[0], &c1 = fh.components[1], &c2 = fh.components[2];
+        if (c0.h == geo.max_h && c0.v == geo.max_v && c1.h == c2.h && c1.v == c2.v && c1.h > 0 && c1.v > 0 && geo.max_h % c1.h == 0 && geo.max_v % c1.v == 0) {
+            img.chroma_hs = (uint8_t)(geo.max_h / c1.h);
+            img.chroma_vs = (uint8_t)(geo.max_v / c1.v);
+        }
+    }
     img.restart_interval = geo.restart_interval;
     img.mcus_per_line = (uint32_t)geo.mcus_per_line;
     img.mcus_per_column = (uint32_t)geo.mcus_per_column;

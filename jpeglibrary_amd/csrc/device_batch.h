@@ -11,6 +11,7 @@
 #include "../../include/jpgpu.h"
 #include "common.h"
 #include "host.h"
+#include "k3u_taps.h"
 #include "kernels.h"
 
 namespace jpgpu {
@@ -115,6 +116,12 @@ struct ImagePlan {
     // (equal to win under orientation 1).  An image whose orientation is not 1 takes K3's generic class and the K3O launch.
     uint8_t exif_orientation = 1, orientation = 1;
     jpgpu_rect win_oriented = {0, 0, 0, 0};
+    // chroma upsampling (include/jpgpu.h, "Chroma upsampling"): chroma_hs / chroma_vs are what the frame says -- the ratio of components 1 and 2
+    // to component 0 where component 0 carries the maximal factors and the two agree, else 0 --, `fancy` what the image was planned with
+    // (fancy_filtered: the policy, the format, the kind, the ratio, the width).  A filtered image takes K3's generic class over its FETCH
+    // RECTANGLE (fancy_fetch_rect) and the K3U launch; if it is turned as well, K3U leaves its samples in a staging slot for K3O.
+    uint8_t chroma_hs = 0, chroma_vs = 0;
+    bool fancy = false;
 };
 
 class WorkCrew;
@@ -155,6 +162,11 @@ class DeviceBatch {
     int set_orientation_policy(int policy);
     int set_orientations(const uint8_t *orientations, int n);
     int image_orientation(int i, int *orientation) const;
+    // The upsampling policy (jpgpu_batch_set_upsampling_policy): state of the batch like the colour policy, read by every later upload of whole
+    // files under an RGB format.
+    int set_upsampling_policy(int policy);
+    int image_upsampling(int i, int *applied) const;
+    int upsampling_ms(float *ms);  // jpgpu_batch_upsampling_ms
     uint64_t idct_listed_mcus() const { return idct_listed_mcus_; }
     // One progressive frame collected by the JpegDecoder mirror: its entropy scans + the Dispose() pass.
     int upload_progressive_frame(const ProgressiveFrame &frame, const uint8_t *file, size_t file_len, int sof, int format);
@@ -263,8 +275,15 @@ class DeviceBatch {
     // CMYK / YCCK image's samples need where that is more (RGB_U8, RGB_PLANAR_U8); an oriented image of any kind passes through the scratch
     // image too, with 1, 3 or 4 bytes per pixel by the same rule
     static uint64_t slot_bytes(const ImagePlan &img);
+    // The one decision of the upsampling policy: is this image filtered (its kind, precision, ratio and width; k3u_taps.h has the ratio rule)
+    static bool fancy_filtered(int policy, int format, const ImagePlan &img);
+    // What K3 leaves in the scratch image of a filtered image: its stored window widened to every tap (k3u_taps.h: k3u_fetch_span), in pixels
+    // of the stored frame; and where, behind those samples in the image's slot, K3U stages the samples of an image K3O turns afterwards
+    static jpgpu_rect fancy_fetch_rect(const ImagePlan &img);
+    static uint64_t fancy_staging_offset(const ImagePlan &img);
     void plan_color_convert();
     void plan_orient_convert();
+    void plan_fancy_convert();
     // ingest (jpgpu_batch_upload*), see device_batch_ingest.cpp
     void plan_file_headers(const uint8_t *file, size_t len, FilePlan &fp) const;
     void plan_file_full(const uint8_t *file, size_t len, int index, FilePlan &fp) const;
@@ -471,6 +490,17 @@ class DeviceBatch {
     int orient_policy_ = JPGPU_ORIENT_STORED;
     bool orientations_pending_ = false;
     std::vector<uint8_t> pending_orientations_, orientations_;  // set_orientations' / the running upload's (empty: every image by the policy)
+    // ... and the images that are filtered under JPGPU_UPSAMPLE_FANCY, in a fourth list: one K3U call filters and converts them all
+    // (plan_fancy_convert); one that is turned as well is in orient_convert_ too, and K3O reads what K3U staged for it
+    std::vector<RgbConvert> fancy_convert_;
+    std::vector<FancyImage> fancy_images_;
+    uint32_t fancy_max_tiles_ = 0;
+    int n_fancy_staged_ = 0;
+    DevBuffer d_fancy_images_;
+    int upsample_policy_ = JPGPU_UPSAMPLE_REPLICATE;
+    // JPGPU_TIME_UPSAMPLE=1 (read per upload): an event pair around the K3U call, for jpgpu_batch_upsampling_ms; fancy_timed_: one was recorded
+    bool fancy_time_wanted_ = false, fancy_timed_ = false;
+    hipEvent_t fancy_ev_[2] = {};
     DevBuffer d_chunk_work_, d_chunk_sums_;
     int n_chunk_work_ = 0;
     DevBuffer d_unstuffed_, d_ends_u_;  // K1 output: entropy data as the bit reader sees it + interval ends in it

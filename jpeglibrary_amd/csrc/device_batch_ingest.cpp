@@ -426,7 +426,7 @@ int DeviceBatch::take_windows(int n, int format, const char *what) {
 
 // Image i behind its plan: its orientation -- the caller's value, else what the policy makes of the file's, and 1 under a format that does
 // not read it -- then the verdict on its window, which is given in pixels of the ORIENTED frame, and the geometry of the output in place of
-// the stored frame's.  A window that is the whole frame is no window.  An image that failed keeps its status; an image of orientation 1
+// the stored frame's; and whether it is filtered under the upsampling policy.  A window that is the whole frame is no window.  An image that failed keeps its status; an image of orientation 1
 // without a window leaves here exactly as its plan made it.
 void DeviceBatch::apply_window(size_t i) {
     ImagePlan &img = images_[i];
@@ -437,6 +437,7 @@ void DeviceBatch::apply_window(size_t i) {
         o = given != 0 ? given : (orient_policy_ == JPGPU_ORIENT_FILE ? img.exif_orientation : 1);
     }
     img.orientation = (uint8_t)o;
+    img.fancy = fancy_filtered(upsample_policy_, format_, img);  // (the window only decides which of its pixels come out)
     const uint32_t ow = orientation_transposes(o) ? img.height : img.width, oh = orientation_transposes(o) ? img.width : img.height;  // the oriented frame
     jpgpu_rect w = windows_.empty() ? jpgpu_rect{0, 0, 0, 0} : windows_[i];
     bool whole = w.x == 0 && w.y == 0 && w.width == 0 && w.height == 0;

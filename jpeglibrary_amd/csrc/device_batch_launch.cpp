@@ -342,6 +342,20 @@ int DeviceBatch::run_idct(bool with_resize) {
     e = launch_color_convert(ctx_->stream, (const uint8_t *)d_rgb_scratch_.ptr, (uint8_t *)d_out_.ptr, (const ColorImage *)d_color_images_.ptr,
                              (int)color_images_.size(), color_max_pixels_, format_, kf, output_affine_);
     if (e != hipSuccess) return hip_fail(e, "color_convert_kernel");
+    // the images that are filtered (JPGPU_UPSAMPLE_FANCY): one call filters and converts them all, or stages them for the turn below
+    const bool time_fancy = fancy_time_wanted_ && !fancy_images_.empty();
+    if (time_fancy) {
+        for (hipEvent_t &ev : fancy_ev_)
+            if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return hip_fail(e, "hipEventCreate(upsampling)");
+        if ((e = hipEventRecord(fancy_ev_[0], ctx_->stream)) != hipSuccess) return hip_fail(e, "hipEventRecord(upsampling)");
+    }
+    e = launch_fancy_upsample(ctx_->stream, (const uint8_t *)d_rgb_scratch_.ptr, (uint8_t *)d_out_.ptr, (uint8_t *)d_rgb_scratch_.ptr,
+                              (const FancyImage *)d_fancy_images_.ptr, (int)fancy_images_.size(), n_fancy_staged_, fancy_max_tiles_, format_, kf, output_affine_);
+    if (e != hipSuccess) return hip_fail(e, "fancy_upsample_kernel");
+    if (time_fancy) {
+        if ((e = hipEventRecord(fancy_ev_[1], ctx_->stream)) != hipSuccess) return hip_fail(e, "hipEventRecord(upsampling)");
+        fancy_timed_ = true;
+    }
     // the images whose orientation is not 1, of every kind: one launch turns and converts them all
     e = launch_orient_convert(ctx_->stream, (const uint8_t *)d_rgb_scratch_.ptr, (uint8_t *)d_out_.ptr, (const OrientImage *)d_orient_images_.ptr,
                               (int)orient_images_.size(), orient_max_tiles_, format_, kf, output_affine_);

@@ -55,6 +55,7 @@ struct LayoutSwitches {
     bool handoff_set = false, handoff_dense = false;
     bool tile_align = true;                     // JPGPU_TILE_ALIGN=0 turns it off (A/B switch, default on)
     bool overlap = false;                       // JPGPU_OVERLAP: the opt-in two-stream issue order (plan_overlap_halves)
+    bool time_upsample = false;                 // JPGPU_TIME_UPSAMPLE: an event pair around the K3U call (jpgpu_batch_upsampling_ms; measuring aid)
     int xcds = 8;                               // JPGPU_XCD_MAP.  MI355X: 8 XCDs; 0 / 1 = memory order (A/B switch)
     // process: JPGPU_PROG_BY_SCAN, JPGPU_PROG_NO_WAVE_CHAINS, JPGPU_K1_THREE_PASS (A/B switch: count + prefix + write kernels)
     bool prog_by_scan = false, no_wave_chains = false, k1_three_pass = false;
@@ -78,6 +79,7 @@ LayoutSwitches read_layout_switches() {
     sw.no_subseq = set("JPGPU_NO_SUBSEQ");
     if (const char *ev = getenv("JPGPU_OVERLAP")) sw.overlap = atoi(ev) != 0;
     if (const char *ev = getenv("JPGPU_XCD_MAP")) sw.xcds = atoi(ev);
+    if (const char *ev = getenv("JPGPU_TIME_UPSAMPLE")) sw.time_upsample = atoi(ev) != 0;
     sw.prog_by_scan = by_scan, sw.no_wave_chains = no_wave_chains, sw.k1_three_pass = three_pass;
     return sw;
 }
@@ -158,6 +160,7 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
     plan_output_clears();
     plan_color_convert();
     plan_orient_convert();
+    plan_fancy_convert();
     assemble_idct_lists(p);
     plan_overlap_halves(p);
     init_status();
@@ -190,6 +193,9 @@ void DeviceBatch::reset_upload_state(const UploadPlan &p) {
     rgb_convert_.clear();
     color_convert_.clear();
     orient_convert_.clear();
+    fancy_convert_.clear();
+    fancy_timed_ = false;
+    fancy_time_wanted_ = p.sw.time_upsample;
     sub_scan_ids_.clear();
     total_subs_ = max_subs_per_scan_ = 0;
     sub_shift_used_ = 0;
@@ -391,18 +397,20 @@ void DeviceBatch::fill_scan(UploadPlan &p, size_t ii, int j, size_t file_len) {
     // sequential scan (a block lies at (mx * max_h + bx) * 8 and is hs * 8 wide, bx + hs <= max_h), a one-component frame, and the frame
     // pass of a progressive frame whose sampling factors all divide the maxima (JpegBlockAllocator.Flush places block bx of the MCU at
     // (mx * h + bx) * hs * 8).  The cover is then the MCUs the window touches; any other scan keeps the whole grid, clipped all the same.
-    s.win_x = (uint16_t)img.win.x;
-    s.win_y = (uint16_t)img.win.y;
-    s.win_w = img.windowed ? (uint16_t)img.win.width : s.width;
-    s.win_h = img.windowed ? (uint16_t)img.win.height : s.height;
+    // (a filtered image, JPGPU_UPSAMPLE_FANCY: K3 decodes its fetch rectangle, the window widened to every tap of K3U -- the whole frame without one)
+    const jpgpu_rect win = img.fancy ? fancy_fetch_rect(img) : img.win;
+    s.win_x = (uint16_t)win.x;
+    s.win_y = (uint16_t)win.y;
+    s.win_w = img.windowed ? (uint16_t)win.width : s.width;
+    s.win_h = img.windowed ? (uint16_t)win.height : s.height;
     s.cov_cols = (uint16_t)s.mcus_per_line;
     s.cov_rows = (uint16_t)s.mcus_per_column;
     bool mcu_boxes = job.kind != kScanProgressive && g.max_h > 0 && g.max_v > 0 && (job.scan_components > 1 || g.frame.num_components == 1);
     if (job.kind == kScanFrameOnly)
         for (int c = 0; c < job.scan_components; c++) mcu_boxes &= job.comp[c].h * job.comp[c].hs == g.max_h && job.comp[c].v * job.comp[c].vs == g.max_v;
-    if (img.windowed && mcu_boxes && img.win.width != 0 && img.win.height != 0) {
+    if (img.windowed && mcu_boxes && win.width != 0 && win.height != 0) {
         const uint32_t mw = 8u * (uint32_t)g.max_h, mh = 8u * (uint32_t)g.max_v;
-        const uint32_t c0 = img.win.x / mw, c1 = (img.win.x + img.win.width + mw - 1) / mw, r0 = img.win.y / mh, r1 = (img.win.y + img.win.height + mh - 1) / mh;
+        const uint32_t c0 = win.x / mw, c1 = (win.x + win.width + mw - 1) / mw, r0 = win.y / mh, r1 = (win.y + win.height + mh - 1) / mh;
         if (c1 <= s.mcus_per_line && r1 <= s.mcus_per_column) {
             s.cov_x = (uint16_t)c0;
             s.cov_y = (uint16_t)r0;
@@ -513,9 +521,9 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
     // image's, and the padding (an even count of whole intervals) goes behind it.  (The scans of a multi-scan image lie back
     // to back in one dense run of the image's blocks, which is what the coefficient readers hand out: they stay dense.)
     // (a windowed image's scan is always handed over dense: the split form of K3 would need a window variant of its own)
-    // (... and so is an oriented image's: its samples go through the scratch image, which only the generic class fills)
-    const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed && img.orientation == 1, split_always = p.sw.handoff_set;
-    const int k3_class = fmt_is_interleaved(format_) && !color_kind_by_file(img.color_kind) && img.orientation == 1 ? idct_layout_class(s) : 0;
+    // (... and so is an oriented image's and a filtered one's: its samples go through the scratch image, which only the generic class fills)
+    const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed && img.orientation == 1 && !img.fancy, split_always = p.sw.handoff_set;
+    const int k3_class = fmt_is_interleaved(format_) && !color_kind_by_file(img.color_kind) && img.orientation == 1 && !img.fancy ? idct_layout_class(s) : 0;
     if (split_wanted && job.kind == kScanSequential && s.dri != 0 && img.jobs.size() == 1 && !img.replay_skip && s.total_mcus > 0 &&
         s.blocks_per_mcu != 0 && k3_variant(format_, k3_class, kK3Split).exists &&
         // The planes pay where few blocks reach into coefficients 32..63; all that is known of that in front of the decode is
@@ -534,13 +542,18 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
 
 // no fused conversion for a scan of image ii: its samples go to the scratch image, then ycc_to_rgb_kernel (once per image) -- or, for an image
 // of kind RGB, CMYK or YCCK, the batch's one K3C launch (plan_color_convert) -- or, for an image of any kind whose orientation is not 1, the
-// batch's one K3O launch (plan_orient_convert), which converts as well
+// batch's one K3O launch (plan_orient_convert), which converts as well.  An image that is filtered (JPGPU_UPSAMPLE_FANCY) is listed for the
+// batch's one K3U call (plan_fancy_convert) in place of the first two, and for K3O besides if it is turned
 void DeviceBatch::list_rgb_convert(size_t ii) {
     const ImagePlan &img = images_[ii];
-    std::vector<RgbConvert> &list = img.orientation != 1 ? orient_convert_ : (color_kind_by_file(img.color_kind) ? color_convert_ : rgb_convert_);
-    for (const RgbConvert &rc : list)
-        if (rc.image == (uint32_t)ii) return;
-    list.push_back({(uint32_t)ii, img.out_offset, (uint64_t)img.win.width * img.win.height, img.num_components});  // (the window's pixels)
+    auto list_in = [&](std::vector<RgbConvert> &list) {
+        for (const RgbConvert &rc : list)
+            if (rc.image == (uint32_t)ii) return;
+        list.push_back({(uint32_t)ii, img.out_offset, (uint64_t)img.win.width * img.win.height, img.num_components});  // (the window's pixels)
+    };
+    if (img.fancy) list_in(fancy_convert_);
+    if (img.orientation != 1) list_in(orient_convert_);
+    else if (!img.fancy) list_in(color_kind_by_file(img.color_kind) ? color_convert_ : rgb_convert_);
 }
 
 // K3's work for one scan: tile size and alignment, layout class, scratch conversion, ordering level, work entries, the partial-MCU entry.
@@ -578,6 +591,8 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
     if (!holds_samples && color_kind_by_file(img.color_kind)) cls = 0;
     // ... and of an image that is turned on its way out (orientation 2..8): the scratch image is what K3O reads
     if (!holds_samples && img.orientation != 1) cls = 0;
+    // ... and of an image whose chroma is filtered (JPGPU_UPSAMPLE_FANCY): the scratch image is what K3U reads
+    if (!holds_samples && img.fancy) cls = 0;
     if ((cls == 0 || holds_samples) && rgb_out) list_rgb_convert(ii);
     // A baseline frame whose LATER scans write a component this one writes too (a corrupted selector: one component
     // scanned twice, another never): in the reference the later WriteBlock wins -- where the later scan GOT to; a later
@@ -885,8 +900,34 @@ void DeviceBatch::plan_orient_convert() {
     orient_max_tiles_ = 0;
     for (const RgbConvert &rc : orient_convert_) {
         const ImagePlan &img = images_[rc.image];
-        orient_images_.push_back({rc.out_offset, rc.out_offset, img.win.width, img.win.height, (uint32_t)img.color_kind, (uint32_t)img.orientation});
+        // (a filtered image: what K3U staged behind the fetch rectangle, (Y, Cb', Cr') of the stored window)
+        const uint64_t src_off = rc.out_offset + (img.fancy ? fancy_staging_offset(img) : 0u);
+        orient_images_.push_back({src_off, rc.out_offset, img.win.width, img.win.height, (uint32_t)img.color_kind, (uint32_t)img.orientation});
         orient_max_tiles_ = std::max(orient_max_tiles_, orient_tiles(img.win.width, img.win.height));
+    }
+}
+
+// The descriptors of the K3U call: one per filtered image, with the fetch rectangle K3 leaves in the scratch image and the stored window
+// that comes out of it -- to the output, or to the staging slot of an image K3O turns afterwards.
+void DeviceBatch::plan_fancy_convert() {
+    fancy_images_.clear();
+    fancy_max_tiles_ = 0;
+    n_fancy_staged_ = 0;
+    for (const RgbConvert &rc : fancy_convert_) {
+        const ImagePlan &img = images_[rc.image];
+        const jpgpu_rect f = fancy_fetch_rect(img);
+        const bool staged = img.orientation != 1;
+        FancyImage g;
+        g.src_off = rc.out_offset;
+        g.dst_off = rc.out_offset + (staged ? fancy_staging_offset(img) : 0u);
+        g.fetch_x = f.x, g.fetch_y = f.y, g.fetch_w = f.width;
+        g.win_x = img.win.x, g.win_y = img.win.y, g.win_w = img.win.width, g.win_h = img.win.height;
+        g.hs = img.chroma_hs, g.vs = img.chroma_vs;
+        g.cw = k3u_chroma_extent(img.width, g.hs), g.ch = k3u_chroma_extent(img.height, g.vs);
+        g.staged = staged ? 1u : 0u;
+        n_fancy_staged_ += staged ? 1 : 0;
+        fancy_images_.push_back(g);
+        fancy_max_tiles_ = std::max(fancy_max_tiles_, fancy_tiles(img.win.width, img.win.height));
     }
 }
 
@@ -906,7 +947,7 @@ void DeviceBatch::plan_overlap_halves(UploadPlan &p) {
     while (huff_half_ < n_huff_work_ && h_scans_[p.huff_work[huff_half_].scan].image_index < half_image) huff_half_++;
     // worth it for batches that keep the machine busy for milliseconds: the halves cost four launches and two events
     if (wanted && !entropy_only_ && p.sub_work.empty() && p.prog_work.empty() && total_blocks_ >= (4u << 20) && huff_half_ > 0 &&
-        huff_half_ < n_huff_work_ && rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
+        huff_half_ < n_huff_work_ && rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && fancy_convert_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
         idct_win_class_begin_[kNumIdctLayoutClasses] == idct_win_class_begin_[0]) {  // (no windowed image: the halves have no list for their work)
         for (int half = 0; half < 2; half++) {
             idct_half_begin_[half][0] = (int)p.idct_work_halves.size();
@@ -983,9 +1024,10 @@ int DeviceBatch::upload_plan(const UploadPlan &p, const std::vector<const uint8_
         // + one tile of slack (IDCT DMA reads whole tiles) + the split scans' flag words
         {&d_coefs_, nullptr, 0, entropy_only_ ? 256 : (size_t)coef_store_blocks_ * 128 + (size_t)kIdctBlocksPerWg * 128 + (size_t)p.flag_words * 8 + 256},
         {&d_out_, nullptr, 0, entropy_only_ ? 256 : (size_t)out_bytes_ + 256},
-        {&d_rgb_scratch_, nullptr, 0, rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() ? 0 : (size_t)out_bytes_ + 256},
+        {&d_rgb_scratch_, nullptr, 0, rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && fancy_convert_.empty() ? 0 : (size_t)out_bytes_ + 256},
         {&d_color_images_, color_images_.data(), color_images_.size() * sizeof(ColorImage), 0},
         {&d_orient_images_, orient_images_.data(), orient_images_.size() * sizeof(OrientImage), 0},
+        {&d_fancy_images_, fancy_images_.data(), fancy_images_.size() * sizeof(FancyImage), 0},
         {&d_planes_, nullptr, 0, format_ == JPGPU_FMT_EXTENDED_U16 && !entropy_only_ ? (size_t)planes_bytes_ + 256 : 0},
         {&d_input_, nullptr, 0, (size_t)input_bytes_},
     };

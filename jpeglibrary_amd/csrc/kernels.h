@@ -182,6 +182,25 @@ struct OrientImage {
 };
 hipError_t launch_orient_convert(hipStream_t stream, const uint8_t *scratch, uint8_t *out, const OrientImage *images, int n_images, uint32_t max_tiles,
                                  int format, const YccRgbFactors &kf, const OutputAffine &aff);
+// K3U (k3u_upsample.hip): the images that are filtered under JPGPU_UPSAMPLE_FANCY (include/jpgpu.h, "Chroma upsampling"; k3u_taps.h has the
+// arithmetic), from the INTERLEAVED_U8 samples K3's generic class left in `scratch` -- the FETCH RECTANGLE of the stored frame, fetch_w
+// pixels per line of 3 bytes, whose first pixel is (fetch_x, fetch_y) of the frame: the stored window widened so that every tap is there.
+// The window's pixels go to the batch's RGB format at `out` + dst_off (staged == 0), or, for an image K3O turns afterwards, as (Y, Cb', Cr')
+// of 3 bytes per pixel to `staging` + dst_off (staged == 1: the sixth sink; `staging` is the scratch buffer, behind the image's fetch
+// rectangle).  ONE call for all of them, a descriptor per image, a workgroup per tile of kFancyTileW x kFancyTileH pixels of the window.
+// src_off and dst_off are multiples of 256.  max_tiles: the largest fancy_tiles(win_w, win_h) among the descriptors.
+constexpr uint32_t kFancyTileW = 128, kFancyTileH = 16;
+constexpr uint32_t fancy_tiles(uint32_t width, uint32_t height) { return ((width + kFancyTileW - 1) / kFancyTileW) * ((height + kFancyTileH - 1) / kFancyTileH); }
+struct FancyImage {
+    uint64_t src_off, dst_off;             // bytes into `scratch` / into `out` or `staging`
+    uint32_t fetch_x, fetch_y, fetch_w;    // the fetch rectangle's first pixel in the frame, and its pixels per line
+    uint32_t win_x, win_y, win_w, win_h;   // the stored window, in pixels of the frame
+    uint32_t cw, ch;                       // the chroma plane's REAL extent: ceil(W / hs) x ceil(H / vs)
+    uint32_t hs, vs;                       // (2, 1), (2, 2) or (1, 2)
+    uint32_t staged;
+};
+hipError_t launch_fancy_upsample(hipStream_t stream, const uint8_t *scratch, uint8_t *out, uint8_t *staging, const FancyImage *images, int n_images,
+                                 int n_staged, uint32_t max_tiles, int format, const YccRgbFactors &kf, const OutputAffine &aff);
 
 // Waves per workgroup of the POOLED form of the K2S final pass (k2s_subseq.hip: runs of scans that stage the same tables; one workgroup per CU, every wave takes the
 // next 64 lanes from a counter): 10 waves + 4 tables fill a CU's LDS.  Runs shorter than kSubFinalPoolMinChunks waves, and runs
