@@ -483,6 +483,45 @@ int jpgpu_batch_image_upsampling(const jpgpu_batch *b, int i, int *applied);
  * JPGPU_ERR_INVALID_OPERATION otherwise, and when the upload has no filtered image or has not been decoded. */
 int jpgpu_batch_upsampling_ms(jpgpu_batch *b, float *ms);
 
+/* ---- Grey output: ONE plane per image in place of three (an extension beyond the reference; torchvision's ImageReadMode.GRAY, the Y output
+ * format of nvJPEG and rocJPEG, libjpeg's JCS_GRAYSCALE).
+ *   By default (JPGPU_CHANNELS_RGB) every format decodes as before, bit for bit.  Under JPGPU_CHANNELS_LUMA the formats RGB_PLANAR_U8 / _F16 /
+ * _F32 deliver one tight plane of the oriented frame, or of its window: out_bytes = W * H * sizeof(sample), plane[0] = {0, W, H, W},
+ * plane[1] and plane[2] zero.  The float forms use scale[0] and bias[0] of jpgpu_batch_set_output_affine with the arithmetic of the three
+ * planes.  out_offset stays a multiple of 256; use it, as under the colour policy.
+ *   The sample of pixel (x, y):
+ *     kinds GRAY and YCBCR   the byte INTERLEAVED_U8 holds at channel 0 of that pixel: component 0's sample.  No chroma is read, so the
+ *                            upsampling policy has no effect: jpgpu_batch_image_upsampling says 0 for every image.
+ *     kinds RGB, CMYK, YCCK  (these exist only under JPGPU_COLOR_FILE)  (19595 * R + 38470 * G + 7471 * B + 32768) >> 16  with R, G, B the
+ *                            bytes RGB_U8 holds for that pixel under the colour policy: Pillow's convert("L").
+ * Windows, orientation (the plane is turned like the three planes are), the partial picture of a failing file and the per-image refusals are
+ * those of the RGB formats; an image that failed reads as zeros.
+ *   Two roads, chosen per image (jpgpu_batch_luma_work counts them).  The FAST road transforms component 0's blocks alone, straight from the
+ * coefficient store: kind GRAY or YCBCR, precision 8, orientation 1, one sequential scan that holds every frame component once with frame
+ * component 0 first, component 0 carrying the frame's maximal sampling factors (vertically it may also have one block per MCU column
+ * under a taller MCU, as (2, 1) luma beside (1, 2) chroma has: its rows are repeated like the reference repeats them), and no caller's
+ * canvas.  The other components' factors, the width, the height and the window are free.  Everything else -- progressive and multi-scan frames, the kinds RGB, CMYK and YCCK,
+ * orientations 2..8 -- takes the SCRATCH road: the INTERLEAVED_U8 samples of the stored window, then one kernel that forms the sample
+ * and turns the plane.  The bytes do not depend on the road.
+ *   Only RGB_PLANAR_U8 / _F16 / _F32 read the policy; every other format decodes as before.  It is state of the batch like the colour
+ * policy: every later upload of whole files reads it until it is set again.
+ *   The resize stage (jpgpu_batch_set_resize) over a LUMA upload of RGB_PLANAR_U8 resamples the one plane with the same tap tables and the
+ * same function per plane, scale[0] and bias[0]: the buffer is T[n][1][out_height][out_width], and jpgpu_batch_resized_device and
+ * jpgpu_batch_download_resized count one plane per image.
+ *   Not covered: jpgpu_decoder_*, jpgpu_decode_scan, jpgpu_progressive_*, jpgpu_multi_*, jpgpu_batch_upload_frames (three planes, as
+ * before); a fast road for turned images or from the split hand-off; an interleaved [H, W, 1] form; grey by any other formula. */
+typedef enum jpgpu_channels_policy {
+    JPGPU_CHANNELS_RGB = 0, /* three planes, as before */
+    JPGPU_CHANNELS_LUMA = 1 /* one plane: component 0's samples, or L of the file's RGB */
+} jpgpu_channels_policy;
+/* JPGPU_ERR_ARGUMENT for any other value. */
+int jpgpu_batch_set_channels_policy(jpgpu_batch *b, int policy);
+/* 1 where image i was planned with one plane, else 3 (the channels of the RGB formats; the policy unset, a format that does not read it, an
+ * image that failed at upload).  Valid after an upload; JPGPU_ERR_ARGUMENT for a NULL argument or an index out of range. */
+int jpgpu_batch_image_channels(const jpgpu_batch *b, int i, int *channels);
+/* counts[0] = images of this upload planned on the fast road, counts[1] = on the scratch road.  Valid after an upload. */
+int jpgpu_batch_luma_work(const jpgpu_batch *b, int32_t counts[2]);
+
 /* Coefficient hand-off for multi-scan (progressive, SOF2) images -- BASELINE config 5's "coefficient accumulate then single
  * IDCT pass": the caller's progressive entropy decoder accumulates the coefficient store, the GPU runs what
  * JpegHuffmanProgressiveScanDecoder.Dispose (ScanDecoder/JpegHuffmanProgressiveScanDecoder.cs:421-470: dequantise, IDCT,

@@ -136,6 +136,8 @@ COLOR_KINDS = ("gray", "ycbcr", "rgb", "cmyk", "ycck")
 ORIENTATION_POLICIES = ("stored", "file")
 # jpgpu_upsampling_policy, by its Python names
 UPSAMPLING_POLICIES = ("replicate", "fancy")
+# jpgpu_channels_policy, by its Python names
+CHANNELS_POLICIES = ("rgb", "gray")
 
 UPLOAD_PINNED = 1
 UPLOAD_PINNED_ARENA = 2
@@ -199,6 +201,9 @@ SYMBOLS = [
     ("jpgpu_batch_set_upsampling_policy", C.c_int, [_P, C.c_int]),
     ("jpgpu_batch_image_upsampling", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("jpgpu_batch_upsampling_ms", C.c_int, [_P, C.POINTER(C.c_float)]),
+    ("jpgpu_batch_set_channels_policy", C.c_int, [_P, C.c_int]),
+    ("jpgpu_batch_image_channels", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("jpgpu_batch_luma_work", C.c_int, [_P, C.POINTER(C.c_int32)]),
     ("jpgpu_sizeof_device_ingest_stats", C.c_size_t, []),
     ("jpgpu_batch_device_ingest_stats", C.c_int, [_P, C.POINTER(DeviceIngestStats)]),
     ("jpgpu_batch_upload_frames", C.c_int, [_P, C.POINTER(Frame), C.c_void_p, C.c_int, C.c_int]),

@@ -168,6 +168,27 @@ def _upsampling_policy(upsampling, who="upsampling"):
     return _capi.UPSAMPLING_POLICIES.index(upsampling)
 
 
+def _channels_policy(mode, fmt=None, who="mode"):
+    """The check of Batch.set_channels_policy / decode_batch(mode=...), before any library call: "rgb" or "gray" -> the jpgpu_channels_policy
+    value.  fmt: the format "gray" is asked for with; only RGB_PLANAR_U8 / _F16 / _F32 have a one-plane form."""
+    if not isinstance(mode, str) or mode not in _capi.CHANNELS_POLICIES:
+        raise ValueError('%s is "rgb" (three planes) or "gray" (one plane: the luma samples, or L of a CMYK or RGB file), not %r' % (who, mode))
+    if mode == "gray" and fmt is not None and fmt not in _RGB_PLANES:
+        raise ValueError('%s="gray" needs RGB_PLANAR_U8, RGB_PLANAR_F16 or RGB_PLANAR_F32; format %d has no one-plane form' % (who, fmt))
+    return _capi.CHANNELS_POLICIES.index(mode)
+
+
+def _gray_mean_std(mean, std):
+    """mean and std of a one-plane decode: a number or a sequence of one, each -> three equal values for affine_from_mean_std (only
+    scale[0] and bias[0] are read)"""
+    def one(v, name):
+        a = np.asarray(v, dtype=np.float64).reshape(-1)
+        if a.shape != (1,):
+            raise ValueError('%s under mode="gray" is one value (a number or a sequence of one), not %r' % (name, v))
+        return [float(a[0])] * 3
+    return one(mean, "mean"), one(std, "std")
+
+
 def _orientation_list(orientations, n_files=None):
     """The checks of Batch.set_orientations / decode_batch(orientations=...), before any library call: integers 0..8, one per file (0 = what
     the policy gives); n_files: the count they must match.  None -> None."""
@@ -364,6 +385,27 @@ class Batch:
         self._check(_lib.jpgpu_batch_upsampling_ms(self._h, C.byref(ms)))
         return ms.value
 
+    def set_channels_policy(self, mode):
+        """How many planes RGB_PLANAR_U8 / _F16 / _F32 deliver from the next upload on: "rgb", the default -- three, as ever -- or "gray": ONE
+        tight plane [1, H, W] of the oriented frame or its window (include/jpgpu.h, "Grey output") -- component 0's samples for grey and
+        YCbCr files, Pillow's convert("L") of the RGB bytes for the CMYK, YCCK and Adobe-RGB files of color="file".  The float forms take
+        scale[0] and bias[0] of set_output_affine.  Every other format ignores it.  State of the batch: it holds until set again.
+        ValueError, before the library is called, for any other value."""
+        self._check(_lib.jpgpu_batch_set_channels_policy(self._h, _channels_policy(mode)))
+        return self
+
+    def channels(self, i):
+        """1 where image i was planned with one plane ("gray" under an RGB_PLANAR_* format), else 3"""
+        c = C.c_int()
+        raise_for_status(_lib.jpgpu_batch_image_channels(self._h, i, C.byref(c)), b"jpgpu_batch_image_channels: no such image")
+        return c.value
+
+    def luma_work(self):
+        """(images on the fast road, images on the scratch road) of this upload under "gray": which kernel forms each one's plane"""
+        counts = (C.c_int32 * 2)()
+        self._check(_lib.jpgpu_batch_luma_work(self._h, counts))
+        return (counts[0], counts[1])
+
     def window(self, i):
         """(x, y, w, h): the window image i was planned with, in pixels of the oriented frame; (0, 0, W, H) of that frame for a whole one"""
         r = _capi.Rect()
@@ -405,14 +447,16 @@ class Batch:
         return self
 
     def _resized_span(self):
-        """(device pointer, (N, 3, oh, ow), format, numpy dtype) of the resized buffer; raises when no decode with a resize set has run"""
+        """(device pointer, (N, 3, oh, ow), format, numpy dtype) of the resized buffer -- (N, 1, oh, ow) for an upload made under "gray" --;
+        raises when no decode with a resize set has run"""
         ptr, total = C.c_void_p(), C.c_uint64()
         self._check(_lib.jpgpu_batch_resized_device(self._h, C.byref(ptr), C.byref(total)))
         made = getattr(self, "_resized_as", None)
         if made is None:
             raise ValueError("resized: the resize was not set through this object (Batch.set_resize)")
         oh, ow, fmt, np_dtype = made
-        shape = (len(self), 3, oh, ow)
+        one_plane = len(self) * oh * ow * np.dtype(np_dtype).itemsize  # (the library sizes the slabs by the upload's plane count)
+        shape = (len(self), 1 if total.value == one_plane and one_plane != 0 else 3, oh, ow)
         if total.value != int(np.prod(shape, dtype=np.int64)) * np.dtype(np_dtype).itemsize:
             raise ValueError("resized: the buffer holds %d bytes, not %s of %s" % (total.value, shape, np.dtype(np_dtype)))
         return ptr.value, shape, fmt, np_dtype
@@ -565,8 +609,8 @@ class Batch:
             return raw.reshape(h, w, info.num_components)
         if self.format in (FMT_RGB_U8, FMT_RGBA_U8):
             return raw.reshape(h, w, 4 if self.format == FMT_RGBA_U8 else 3)
-        if self.format in _RGB_PLANES:  # three tight planes R, G, B
-            return raw.view(_SAMPLE_DTYPES.get(self.format, np.uint8)).reshape(3, h, w)
+        if self.format in _RGB_PLANES:  # three tight planes R, G, B, or the one plane of "gray" (Batch.set_channels_policy)
+            return raw.view(_SAMPLE_DTYPES.get(self.format, np.uint8)).reshape(self._planes(info), h, w)
         if self.format == FMT_EXTENDED_U16:  # the reference tests' JpegExtendingOutputWriter buffer: ushort x 4 per pixel
             return raw.view(np.uint16).reshape(info.height, info.width, 4)
         dt = np.int16 if self.format == FMT_PLANAR_I16 else np.uint8
@@ -577,6 +621,11 @@ class Batch:
             planes.append(raw[p.offset:p.offset + nbytes].view(dt).reshape(p.height, p.pitch)[:, :p.width])
         return planes
 
+    @staticmethod
+    def _planes(info):
+        """planes of an RGB_PLANAR_* image: 1 where it was planned under "gray" (plane[1] and plane[2] are zero), else 3"""
+        return 1 if info.plane[0].width != 0 and info.plane[1].width == 0 and info.plane[1].pitch == 0 else 3
+
     def _tensor_shape(self, info, hw=None):
         """hw: the (h, w) of the image's window (Batch.window), which is the oriented frame's without one; None: the stored frame's"""
         h, w = hw if hw is not None else (info.height, info.width)
@@ -585,7 +634,7 @@ class Batch:
         if self.format in (FMT_RGB_U8, FMT_RGBA_U8):
             return (h, w, 4 if self.format == FMT_RGBA_U8 else 3)
         if self.format in _RGB_PLANES:
-            return (3, h, w)
+            return (self._planes(info), h, w)
         raise ValueError("output_tensor: format %d is not one dense uint8 array per image (MCU-padded planes, or uint16 pixels); use output()" % self.format)
 
     def output_tensor(self, i):
@@ -646,23 +695,26 @@ class Batch:
             pass
 
 
-def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate"):
+def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb"):
     """One-call helper: returns (outputs, results).  files: bytes-like objects, or 1-D uint8 torch tensors on the context's device.
     windows: one (x, y, w, h) per file (Batch.set_windows): outputs[i] is that rectangle of image i.
     color: "ycc" or "file" (Batch.set_color_policy): under "file" the RGB formats deliver RGB for CMYK, YCCK and Adobe-RGB files.
     orientation: "stored" or "file" (Batch.set_orientation_policy); orientations: one value 0..8 per file (Batch.set_orientations).  Windows
     are then in pixels of the oriented frame.
-    upsampling: "replicate" or "fancy" (Batch.set_upsampling_policy): under "fancy" the RGB formats filter 4:2:2 / 4:2:0 / 4:4:0 chroma as libjpeg does."""
+    upsampling: "replicate" or "fancy" (Batch.set_upsampling_policy): under "fancy" the RGB formats filter 4:2:2 / 4:2:0 / 4:4:0 chroma as libjpeg does.
+    mode: "rgb" or "gray" (Batch.set_channels_policy): under "gray" RGB_PLANAR_U8 / _F16 / _F32 give one plane, [1, H, W]; ValueError for another fmt."""
     files = list(files)
     windows = _window_rects(windows, len(files))
     _color_policy(color)
     _orientation_policy(orientation)
     _upsampling_policy(upsampling)
+    _channels_policy(mode, fmt)
     orientations = _orientation_list(orientations, len(files))
     b = Batch(ctx)
     b.set_color_policy(color)
     b.set_orientation_policy(orientation)
     b.set_upsampling_policy(upsampling)
+    b.set_channels_policy(mode)
     if orientations is not None:
         b.set_orientations(orientations)
     if windows is not None:
@@ -677,7 +729,7 @@ def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="y
     return outs, results
 
 
-def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate"):
+def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb"):
     """One-call helper for torch consumers: returns (tensors, results), tensors[i] = Batch.output_tensor(i) -- uint8[3, H, W] on the
     context's device by default -- or None for an image that failed.  Nothing is downloaded.  The batch is not closed: its output
     buffer is the tensors' memory and is freed with the last of them.  files: bytes-like objects, or 1-D uint8 torch tensors on the
@@ -692,7 +744,11 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     tensors[i] is [3, W, H] for the values 5..8; orientations: one value 0..8 per file (Batch.set_orientations), e.g. 2 for a horizontal flip.
     Windows are then in pixels of the oriented frame.
     upsampling: "replicate" or "fancy" (Batch.set_upsampling_policy): under "fancy" sub-sampled chroma (4:2:2, 4:2:0, 4:4:0) is expanded with
-    libjpeg's triangle filter, as Pillow, torchvision and OpenCV deliver it, instead of repeated; windows, orientation and dtype compose on it."""
+    libjpeg's triangle filter, as Pillow, torchvision and OpenCV deliver it, instead of repeated; windows, orientation and dtype compose on it.
+    mode: "rgb" or "gray" (Batch.set_channels_policy): under "gray" tensors[i] is [1, H, W] -- the luma samples of a grey or YCbCr file, decoded
+    without touching its chroma, or Pillow's convert("L") of a CMYK, YCCK or Adobe-RGB file under color="file".  mean and std are then a number or
+    a sequence of one; every other argument composes, and upsampling="fancy" changes nothing (no chroma is read).  ValueError for a fmt that is
+    not RGB_PLANAR_*."""
     files = list(files)
     windows = _window_rects(windows, len(files))
     _color_policy(color)
@@ -712,14 +768,19 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
         raise ValueError("decode_to_tensors: mean and std go together")
     if mean is not None and fmt not in _SAMPLE_DTYPES:
         raise ValueError("decode_to_tensors: mean / std apply to float samples; pass dtype=torch.float16 or torch.float32")
+    _channels_policy(mode, fmt)
+    if mean is not None and mode == "gray":
+        mean, std = _gray_mean_std(mean, std)
+    consts = affine_from_mean_std(mean, std) if mean is not None else None
     b = Batch(ctx)
     b.set_color_policy(color)
     b.set_orientation_policy(orientation)
     b.set_upsampling_policy(upsampling)
+    b.set_channels_policy(mode)
     if orientations is not None:
         b.set_orientations(orientations)
-    if mean is not None:
-        b.set_output_affine(*affine_from_mean_std(mean, std))
+    if consts is not None:
+        b.set_output_affine(*consts)
     if windows is not None:
         b.set_windows(windows)
     b = _upload_any(b, files, fmt).decode().sync()
@@ -730,7 +791,7 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     return tensors, results
 
 
-def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate"):
+def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb"):
     """One-call helper for fixed-size consumers: returns (tensor, results), tensor = Batch.resized_tensor() -- ONE [N, 3, oh, ow] tensor on the
     context's device, size = (oh, ow), dtype torch.float16 (the default), torch.float32 or torch.uint8 -- every image decoded to RGB and
     resampled to that size (antialiased bilinear) in one launch behind the output stage; the slab of an image that failed is zero and
@@ -740,7 +801,8 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
     windows: one (x, y, w, h) per file (Batch.set_windows): that rectangle of image i is what is resampled -- a RandomResizedCrop's crop.
     color: "ycc" or "file" (Batch.set_color_policy), orientation and orientations (Batch.set_orientation_policy / set_orientations), as in
     decode_to_tensors: the oriented image is what is resampled.  upsampling: "replicate" or "fancy" (Batch.set_upsampling_policy): under "fancy"
-    the image that is resampled has libjpeg's filtered chroma."""
+    the image that is resampled has libjpeg's filtered chroma.  mode: "rgb" or "gray" (Batch.set_channels_policy): under "gray" the tensor is
+    [N, 1, oh, ow], the grey plane of decode_to_tensors(mode="gray") resampled by the same function; mean and std are a number or a sequence of one."""
     import torch
 
     files = list(files)
@@ -756,11 +818,15 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
         raise ValueError("decode_resized: mean and std go together")
     if mean is not None and dtype == torch.uint8:
         raise ValueError("decode_resized: mean / std apply to float samples; pass dtype=torch.float16 or torch.float32")
+    _channels_policy(mode)
+    if mean is not None and mode == "gray":
+        mean, std = _gray_mean_std(mean, std)
     consts = affine_from_mean_std(mean, std) if mean is not None else None
     b = Batch(ctx)
     b.set_color_policy(color)
     b.set_orientation_policy(orientation)
     b.set_upsampling_policy(upsampling)
+    b.set_channels_policy(mode)
     if orientations is not None:
         b.set_orientations(orientations)
     if consts is not None:

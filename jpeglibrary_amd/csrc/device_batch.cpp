@@ -43,7 +43,7 @@ void DevBuffer::release() {
 
 DeviceBatch::~DeviceBatch() {
     if (ctx_) (void)hipSetDevice(ctx_->device);
-    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_color_images_, &d_orient_images_, &d_fancy_images_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
+    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_color_images_, &d_orient_images_, &d_fancy_images_, &d_luma_images_, &d_luma_work_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
         b->release();
     for (hipEvent_t &e : ev_pool_)
         if (e) (void)hipEventDestroy(e);
@@ -66,7 +66,7 @@ int DeviceBatch::hip_fail(hipError_t e, const char *what) {
 }
 
 bool DeviceBatch::fancy_filtered(int policy, int format, const ImagePlan &img) {
-    return policy == JPGPU_UPSAMPLE_FANCY && fmt_is_rgb(format) && img.color_kind == kColorYcbcr && img.num_components == 3 && img.precision == 8 &&
+    return policy == JPGPU_UPSAMPLE_FANCY && img.luma == kLumaNone && fmt_is_rgb(format) && img.color_kind == kColorYcbcr && img.num_components == 3 && img.precision == 8 &&
            k3u_ratio_filtered(img.chroma_hs, img.chroma_vs, img.width);
 }
 
@@ -88,7 +88,7 @@ uint64_t DeviceBatch::slot_bytes(const ImagePlan &img) {
         const uint64_t samples = img.orientation != 1 ? fancy_staging_offset(img) + (uint64_t)img.win.width * img.win.height * 3 : (uint64_t)f.width * f.height * 3;
         return std::max(img.out_bytes, samples);
     }
-    const bool through_scratch = color_kind_by_file(img.color_kind) || img.orientation != 1;
+    const bool through_scratch = color_kind_by_file(img.color_kind) || img.orientation != 1 || img.luma == kLumaScratch;
     const uint64_t samples = through_scratch ? (uint64_t)img.win.width * img.win.height * color_kind_sample_bytes(img.color_kind) : 0u;
     return std::max(img.out_bytes, samples);
 }
@@ -134,6 +134,49 @@ int DeviceBatch::image_upsampling(int i, int *applied) const {
     return JPGPU_OK;
 }
 
+int DeviceBatch::set_channels_policy(int policy) {
+    if (policy != JPGPU_CHANNELS_RGB && policy != JPGPU_CHANNELS_LUMA) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_set_channels_policy: unknown policy");
+    channels_policy_ = policy;
+    return JPGPU_OK;
+}
+
+int DeviceBatch::image_channels(int i, int *channels) const {
+    const ImagePlan *img = image(i);
+    if (!img || !channels) return JPGPU_ERR_ARGUMENT;
+    *channels = img->status == JPGPU_OK && img->luma != kLumaNone ? 1 : 3;
+    return JPGPU_OK;
+}
+
+int DeviceBatch::luma_work(int32_t counts[2]) const {
+    if (!counts) return JPGPU_ERR_ARGUMENT;
+    counts[0] = counts[1] = 0;
+    for (const ImagePlan &img : images_)
+        if (img.status == JPGPU_OK && img.luma != kLumaNone) counts[img.luma == kLumaFast ? 0 : 1]++;
+    return JPGPU_OK;
+}
+
+bool DeviceBatch::luma_fast(const ImagePlan &img, const std::vector<ScanJob> &jobs, bool keep_canvas) {
+    if (img.color_kind != kColorGray && img.color_kind != kColorYcbcr) return false;
+    if (img.precision != 8 || img.orientation != 1 || keep_canvas || jobs.size() != 1) return false;
+    const ScanJob &job = jobs[0];
+    if (job.kind != kScanSequential || job.disabled || job.scan_components != img.num_components) return false;
+    if (job.blocks_per_mcu < 1 || job.blocks_per_mcu > kMaxBlocksPerMcu || job.geo.mcus_per_line <= 0 || job.geo.mcus_per_column <= 0) return false;
+    // frame component 0 first, at the frame's maxima, and named once (a scan that names it again writes over its blocks: K3's business).
+    // (Vertically also ONE block per MCU column under a taller MCU -- (2, 1) luma beside (1, 2) chroma --: K3Y repeats its sample rows as the
+    // reference's replication does.  Several blocks that are replicated as well overlap in the reference; those stay K3's.)
+    const ResolvedScanComponent &c0 = job.comp[0];
+    if (c0.component_index != 0 || c0.hs != 1 || c0.h < 1 || c0.h > 4 || c0.v < 1 || c0.v > 4) return false;
+    if (!(c0.vs == 1 || (c0.v == 1 && c0.vs >= 2 && c0.vs <= 4))) return false;
+    for (int c = 1; c < job.scan_components; c++)
+        if (job.comp[c].component_index == 0) return false;
+    // its blocks are the MCU's first, in raster order: slot by * h + bx (what K3Y's index arithmetic assumes)
+    const int n0 = c0.h * c0.v;
+    if (n0 > job.blocks_per_mcu) return false;
+    for (int k = 0; k < n0; k++)
+        if (job.blk_comp[k] != 0 || job.blk_x[k] != k % c0.h || job.blk_y[k] != k / c0.h) return false;
+    return true;
+}
+
 int DeviceBatch::upsampling_ms(float *ms) {
     if (!ms) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upsampling_ms: null argument");
     if (!fancy_timed_) return fail(JPGPU_ERR_INVALID_OPERATION, "jpgpu_batch_upsampling_ms: no K3U call of this upload was timed (JPGPU_TIME_UPSAMPLE=1 at the upload, a filtered image, a decode)");
@@ -159,6 +202,7 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
     // (what the frame says about its chroma; whether the image is filtered is apply_window's decision)
     img.chroma_hs = img.chroma_vs = 0;
     img.fancy = false;
+    img.luma = kLumaNone;
     if (fh.num_components == 3 && fh.components.size() == 3) {
         const auto &c0 = fh.components[0], &c1 = fh.components[1], &c2 = fh.components[2];
         if (c0.h == geo.max_h && c0.v == geo.max_v && c1.h == c2.h && c1.v == c2.v && c1.h > 0 && c1.v > 0 && geo.max_h % c1.h == 0 && geo.max_v % c1.v == 0) {
@@ -410,6 +454,7 @@ int DeviceBatch::upload_progressive_dispose(const ProgressiveFrame &frame, int f
 
 int DeviceBatch::upload_frames(const jpgpu_frame *frames, const uint16_t *qt, int n, int format) {
     whole_files_ = false;
+    luma_upload_ = false;  // (frames decode to three planes whatever the channels policy)
     device_ingest_ = jpgpu_device_ingest_stats();
     if (windows_pending_ || orientations_pending_) {  // (both are for uploads of whole files: consumed and refused, the batch left empty)
         const bool windows = windows_pending_;

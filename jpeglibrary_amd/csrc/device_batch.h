@@ -77,6 +77,8 @@ struct IngestStats {
     int n_linearised = 0;   // multi-segment files gathered as a whole on the host
 };
 
+enum LumaRoad : uint8_t { kLumaNone = 0, kLumaFast = 1, kLumaScratch = 2 };
+
 struct ImagePlan {
     int status = JPGPU_OK;
     int detail = 0;
@@ -122,6 +124,10 @@ struct ImagePlan {
     // RECTANGLE (fancy_fetch_rect) and the K3U launch; if it is turned as well, K3U leaves its samples in a staging slot for K3O.
     uint8_t chroma_hs = 0, chroma_vs = 0;
     bool fancy = false;
+    // grey output (include/jpgpu.h, "Grey output"): kLumaNone = three planes, as ever; under JPGPU_CHANNELS_LUMA and an RGB_PLANAR_* format the
+    // image has ONE plane and takes the fast road (kLumaFast: DeviceBatch::luma_fast holds; K3Y's luma_idct_kernel reads its scan's store, and
+    // no K3 list names it) or the scratch road (kLumaScratch: planned like an oriented image, K3's generic class, then K3Y's luma_plane_kernel)
+    uint8_t luma = kLumaNone;
 };
 
 class WorkCrew;
@@ -167,6 +173,11 @@ class DeviceBatch {
     int set_upsampling_policy(int policy);
     int image_upsampling(int i, int *applied) const;
     int upsampling_ms(float *ms);  // jpgpu_batch_upsampling_ms
+    // The channels policy (jpgpu_batch_set_channels_policy): state of the batch like the colour policy, read by every later upload of whole
+    // files under RGB_PLANAR_U8 / _F16 / _F32.
+    int set_channels_policy(int policy);
+    int image_channels(int i, int *channels) const;
+    int luma_work(int32_t counts[2]) const;  // jpgpu_batch_luma_work
     uint64_t idct_listed_mcus() const { return idct_listed_mcus_; }
     // One progressive frame collected by the JpegDecoder mirror: its entropy scans + the Dispose() pass.
     int upload_progressive_frame(const ProgressiveFrame &frame, const uint8_t *file, size_t file_len, int sof, int format);
@@ -284,13 +295,19 @@ class DeviceBatch {
     void plan_color_convert();
     void plan_orient_convert();
     void plan_fancy_convert();
+    // The one decision between the two roads of a grey image: can K3Y transform component 0's blocks straight from the scan's store (its kind,
+    // precision and orientation; ONE sequential scan that names every frame component once, component 0 first and at the frame's maximal
+    // factors, its blocks the MCU's first in raster order; no caller's canvas).  jobs: the scan jobs of the image's file plan.
+    static bool luma_fast(const ImagePlan &img, const std::vector<ScanJob> &jobs, bool keep_canvas);
+    void plan_luma_work(size_t ii, int j);
+    void plan_luma_convert();
     // ingest (jpgpu_batch_upload*), see device_batch_ingest.cpp
     void plan_file_headers(const uint8_t *file, size_t len, FilePlan &fp) const;
     void plan_file_full(const uint8_t *file, size_t len, int index, FilePlan &fp) const;
     void plan_swallowed_terminator(FilePlan &fp, const uint8_t *file, size_t len, bool identify_is_clean) const;
     int begin_ingest(int n, int format);
     int take_windows(int n, int format, const char *what);  // pending windows -> this upload's, or the whole call's refusal
-    void apply_window(size_t i);                            // image i of merge_plans: its window's verdict and geometry
+    void apply_window(size_t i, const std::vector<ScanJob> &jobs);                            // image i of merge_plans: its window's verdict and geometry
     void forget_batch();  // no images, no jobs
     int ingest_files(std::vector<FileSegs> &files, unsigned flags, std::chrono::steady_clock::time_point t_begin);
     // its stages, in the order they run (a device source stages in front of plan_heads); IngestRun is what one stage hands the next
@@ -345,7 +362,7 @@ class DeviceBatch {
     int plan_resize();
     bool resize_plan_valid_ = false;
     int resize_plan_width_ = 0, resize_plan_height_ = 0, n_resize_images_ = 0;
-    int resized_width_ = 0, resized_height_ = 0, resized_fmt_ = -1, resized_images_ = 0;
+    int resized_width_ = 0, resized_height_ = 0, resized_fmt_ = -1, resized_images_ = 0, resized_planes_ = 3;
     DevBuffer d_resized_, d_resize_images_, d_resize_tables_;
     hipEvent_t resize_ev_[2] = {};
     std::vector<ImagePlan> images_;
@@ -501,6 +518,19 @@ class DeviceBatch {
     // JPGPU_TIME_UPSAMPLE=1 (read per upload): an event pair around the K3U call, for jpgpu_batch_upsampling_ms; fancy_timed_: one was recorded
     bool fancy_time_wanted_ = false, fancy_timed_ = false;
     hipEvent_t fancy_ev_[2] = {};
+    // ... and the images that have ONE plane under JPGPU_CHANNELS_LUMA: those on the scratch road, of every kind and orientation, in a fifth
+    // list of their own and in none of the four above -- one K3Y launch forms and turns them all (plan_luma_convert) --, those on the fast
+    // road in K3Y's own work list and in no K3 list (plan_luma_work)
+    std::vector<RgbConvert> luma_convert_;
+    std::vector<LumaImage> luma_images_;
+    std::vector<LumaWork> luma_work_;
+    uint32_t luma_max_tiles_ = 0;
+    int n_luma_fast_ = 0;
+    bool luma_work_windowed_ = false;
+    DevBuffer d_luma_images_, d_luma_work_;
+    int channels_policy_ = JPGPU_CHANNELS_RGB;
+    bool luma_upload_ = false;  // the last upload of whole files was made under JPGPU_CHANNELS_LUMA and an RGB_PLANAR_* format: one plane per image
+    bool one_plane_upload() const { return luma_upload_ && whole_files_; }  // (what the resize stage sizes its slabs by)
     DevBuffer d_chunk_work_, d_chunk_sums_;
     int n_chunk_work_ = 0;
     DevBuffer d_unstuffed_, d_ends_u_;  // K1 output: entropy data as the bit reader sees it + interval ends in it

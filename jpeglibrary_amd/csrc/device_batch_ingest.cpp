@@ -398,6 +398,7 @@ int DeviceBatch::image_window(int i, jpgpu_rect *window) const {
 // What every upload of whole files starts with: the pending windows become this upload's and nobody else's.  The refusals of the whole
 // call, decided before anything is enqueued; they leave the batch empty.
 int DeviceBatch::take_windows(int n, int format, const char *what) {
+    luma_upload_ = channels_policy_ == JPGPU_CHANNELS_LUMA && fmt_is_rgb_planes(format);  // (this upload's images have one plane each)
     windows_.clear();
     orientations_.clear();
     if (!windows_pending_ && !orientations_pending_) return JPGPU_OK;
@@ -428,7 +429,8 @@ int DeviceBatch::take_windows(int n, int format, const char *what) {
 // not read it -- then the verdict on its window, which is given in pixels of the ORIENTED frame, and the geometry of the output in place of
 // the stored frame's; and whether it is filtered under the upsampling policy.  A window that is the whole frame is no window.  An image that failed keeps its status; an image of orientation 1
 // without a window leaves here exactly as its plan made it.
-void DeviceBatch::apply_window(size_t i) {
+// Under JPGPU_CHANNELS_LUMA and an RGB_PLANAR_* format the image has one plane, and `jobs` (the scan jobs of its file plan) decide its road.
+void DeviceBatch::apply_window(size_t i, const std::vector<ScanJob> &jobs) {
     ImagePlan &img = images_[i];
     if (img.status != JPGPU_OK) return;
     int o = 1;
@@ -437,7 +439,9 @@ void DeviceBatch::apply_window(size_t i) {
         o = given != 0 ? given : (orient_policy_ == JPGPU_ORIENT_FILE ? img.exif_orientation : 1);
     }
     img.orientation = (uint8_t)o;
-    img.fancy = fancy_filtered(upsample_policy_, format_, img);  // (the window only decides which of its pixels come out)
+    const bool one_plane = channels_policy_ == JPGPU_CHANNELS_LUMA && fmt_is_rgb_planes(format_);
+    img.luma = !one_plane ? kLumaNone : (luma_fast(img, jobs, keep_canvas_) ? kLumaFast : kLumaScratch);
+    img.fancy = fancy_filtered(upsample_policy_, format_, img);  // (the window only decides which of its pixels come out; never a grey image)
     const uint32_t ow = orientation_transposes(o) ? img.height : img.width, oh = orientation_transposes(o) ? img.width : img.height;  // the oriented frame
     jpgpu_rect w = windows_.empty() ? jpgpu_rect{0, 0, 0, 0} : windows_[i];
     bool whole = w.x == 0 && w.y == 0 && w.width == 0 && w.height == 0;
@@ -456,7 +460,7 @@ void DeviceBatch::apply_window(size_t i) {
     }
     if (whole) w = jpgpu_rect{0, 0, ow, oh};
     img.win_oriented = w;
-    if (whole && o == 1) return;
+    if (whole && o == 1 && !one_plane) return;
     if (!whole) {
         img.windowed = true;
         img.win = orientation_stored_rect(o, w, img.width, img.height);  // what K3 decodes
@@ -464,6 +468,10 @@ void DeviceBatch::apply_window(size_t i) {
     const uint64_t pixels = (uint64_t)w.width * w.height;
     if (fmt_is_sample_bytes(format_)) {
         img.out_bytes = pixels * img.num_components;
+    } else if (one_plane) {  // ONE tight plane of the oriented frame or of its window
+        img.out_bytes = pixels * fmt_rgb_plane_sample_bytes(format_);
+        memset(img.plane, 0, sizeof img.plane);
+        img.plane[0] = jpgpu_plane_info{0, w.width, w.height, w.width};
     } else {  // (the RGB formats: take_windows admits nothing else)
         img.out_bytes = pixels * (format_ == JPGPU_FMT_RGBA_U8 ? 4 : 3) * fmt_rgb_plane_sample_bytes(format_);
         if (fmt_is_rgb_planes(format_))
@@ -1101,7 +1109,7 @@ void DeviceBatch::merge_plans(IngestRun &r) {
         img.file_len = f.len;
         img.file_offset = f.slot;
         img.jobs.clear();
-        apply_window((size_t)i);
+        apply_window((size_t)i, fp.jobs);
         if (img.status != JPGPU_OK) continue;
         for (size_t j = 0; j < fp.jobs.size(); j++) {
             img.jobs.push_back((int)(first_job + j));

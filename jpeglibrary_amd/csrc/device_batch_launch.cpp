@@ -270,6 +270,11 @@ int DeviceBatch::run_idct(bool with_resize) {
                            (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr, (uint8_t *)d_out_.ptr, format_, kf,
                            (uint8_t *)d_rgb_scratch_.ptr, output_affine_);
     if (e != hipSuccess) return hip_fail(e, "idct_window_kernel");
+    // the grey images on the fast road (JPGPU_CHANNELS_LUMA): component 0's blocks alone, one launch for all of their scans
+    e = launch_luma_idct(ctx_->stream, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const LumaWork *)d_luma_work_.ptr, (int)luma_work_.size(),
+                         luma_work_windowed_, (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr, (uint8_t *)d_out_.ptr, format_,
+                         output_affine_);
+    if (e != hipSuccess) return hip_fail(e, "luma_idct_kernel");
     // scans ordered behind earlier scans of their image (and the failing MCU of a caller's canvas): one bytewise launch per level
     for (size_t lv = 0; lv + 1 < idct_later_begin_.size(); lv++) {
         int cb[kNumIdctLayoutClasses + 1];
@@ -360,6 +365,10 @@ int DeviceBatch::run_idct(bool with_resize) {
     e = launch_orient_convert(ctx_->stream, (const uint8_t *)d_rgb_scratch_.ptr, (uint8_t *)d_out_.ptr, (const OrientImage *)d_orient_images_.ptr,
                               (int)orient_images_.size(), orient_max_tiles_, format_, kf, output_affine_);
     if (e != hipSuccess) return hip_fail(e, "orient_convert_kernel");
+    // the grey images on the scratch road, of every kind and orientation: one launch forms their samples and turns them
+    e = launch_luma_plane(ctx_->stream, (const uint8_t *)d_rgb_scratch_.ptr, (uint8_t *)d_out_.ptr, (const LumaImage *)d_luma_images_.ptr,
+                          (int)luma_images_.size(), luma_max_tiles_, format_, kf, output_affine_);
+    if (e != hipSuccess) return hip_fail(e, "luma_plane_kernel");
     if (with_resize && resize_.width != 0) return run_resize();  // K4, behind everything above
     return mark_work();
 }

@@ -161,6 +161,7 @@ int DeviceBatch::layout_and_upload(const std::vector<const uint8_t *> &file_ptr,
     plan_color_convert();
     plan_orient_convert();
     plan_fancy_convert();
+    plan_luma_convert();
     assemble_idct_lists(p);
     plan_overlap_halves(p);
     init_status();
@@ -194,6 +195,10 @@ void DeviceBatch::reset_upload_state(const UploadPlan &p) {
     color_convert_.clear();
     orient_convert_.clear();
     fancy_convert_.clear();
+    luma_convert_.clear();
+    luma_work_.clear();
+    n_luma_fast_ = 0;
+    luma_work_windowed_ = false;
     fancy_timed_ = false;
     fancy_time_wanted_ = p.sw.time_upsample;
     sub_scan_ids_.clear();
@@ -522,8 +527,9 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
     // to back in one dense run of the image's blocks, which is what the coefficient readers hand out: they stay dense.)
     // (a windowed image's scan is always handed over dense: the split form of K3 would need a window variant of its own)
     // (... and so is an oriented image's and a filtered one's: its samples go through the scratch image, which only the generic class fills)
-    const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed && img.orientation == 1 && !img.fancy, split_always = p.sw.handoff_set;
-    const int k3_class = fmt_is_interleaved(format_) && !color_kind_by_file(img.color_kind) && img.orientation == 1 && !img.fancy ? idct_layout_class(s) : 0;
+    // (... and a grey image's, on either road: K3Y reads component 0's blocks at their places in the dense store, the scratch road is the generic class)
+    const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed && img.orientation == 1 && !img.fancy && img.luma == kLumaNone, split_always = p.sw.handoff_set;
+    const int k3_class = fmt_is_interleaved(format_) && !color_kind_by_file(img.color_kind) && img.orientation == 1 && !img.fancy && img.luma == kLumaNone ? idct_layout_class(s) : 0;
     if (split_wanted && job.kind == kScanSequential && s.dri != 0 && img.jobs.size() == 1 && !img.replay_skip && s.total_mcus > 0 &&
         s.blocks_per_mcu != 0 && k3_variant(format_, k3_class, kK3Split).exists &&
         // The planes pay where few blocks reach into coefficients 32..63; all that is known of that in front of the decode is
@@ -551,6 +557,10 @@ void DeviceBatch::list_rgb_convert(size_t ii) {
             if (rc.image == (uint32_t)ii) return;
         list.push_back({(uint32_t)ii, img.out_offset, (uint64_t)img.win.width * img.win.height, img.num_components});  // (the window's pixels)
     };
+    if (img.luma != kLumaNone) {  // (one list, whatever its kind and orientation, and none of the four others)
+        list_in(luma_convert_);
+        return;
+    }
     if (img.fancy) list_in(fancy_convert_);
     if (img.orientation != 1) list_in(orient_convert_);
     else if (!img.fancy) list_in(color_kind_by_file(img.color_kind) ? color_convert_ : rgb_convert_);
@@ -561,6 +571,10 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
     const ImagePlan &img = images_[ii];
     const ScanJob &job = jobs_[j];
     DevScan &s = h_scans_[j];
+    if (img.luma == kLumaFast) {  // (no entry in any K3 list, nor in a conversion list: K3Y's own work)
+        plan_luma_work(ii, j);
+        return;
+    }
     const bool rgb_out = fmt_is_rgb(format_);
     const uint32_t generic_per_wg = (uint32_t)kIdctBlocksPerWg / s.blocks_per_mcu;
     uint32_t mcus_per_wg = generic_per_wg;
@@ -593,6 +607,8 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
     if (!holds_samples && img.orientation != 1) cls = 0;
     // ... and of an image whose chroma is filtered (JPGPU_UPSAMPLE_FANCY): the scratch image is what K3U reads
     if (!holds_samples && img.fancy) cls = 0;
+    // ... and of a grey image on the scratch road: the scratch image is what K3Y's luma_plane_kernel reads
+    if (!holds_samples && img.luma == kLumaScratch) cls = 0;
     if ((cls == 0 || holds_samples) && rgb_out) list_rgb_convert(ii);
     // A baseline frame whose LATER scans write a component this one writes too (a corrupted selector: one component
     // scanned twice, another never): in the reference the later WriteBlock wins -- where the later scan GOT to; a later
@@ -931,6 +947,32 @@ void DeviceBatch::plan_fancy_convert() {
     }
 }
 
+// K3Y's work for the one scan of an image on the fast road: the luma blocks of the window's MCU cover, row by row, in units of
+// kLumaUnitBlocks neighbouring blocks, kLumaUnitsPerWg consecutive units per workgroup.
+void DeviceBatch::plan_luma_work(size_t ii, int j) {
+    const ImagePlan &img = images_[ii];
+    const DevScan &s = h_scans_[j];
+    n_luma_fast_++;
+    luma_work_windowed_ |= img.windowed;
+    const uint32_t cols = (uint32_t)s.cov_cols * s.comp[0].h, rows = (uint32_t)s.cov_rows * s.comp[0].v;
+    const uint32_t chunks = (cols + kLumaUnitBlocks - 1) / kLumaUnitBlocks;
+    const uint64_t units = (uint64_t)chunks * rows;
+    for (uint64_t u = 0; u < units; u += kLumaUnitsPerWg)
+        luma_work_.push_back({(uint32_t)j, (uint32_t)(u / chunks), (uint32_t)(u % chunks), (uint32_t)std::min<uint64_t>(kLumaUnitsPerWg, units - u)});
+}
+
+// The descriptors of K3Y's scratch-road launch: one per grey image that is not on the fast road, with the stored window K3 leaves in the
+// scratch image.
+void DeviceBatch::plan_luma_convert() {
+    luma_images_.clear();
+    luma_max_tiles_ = 0;
+    for (const RgbConvert &rc : luma_convert_) {
+        const ImagePlan &img = images_[rc.image];
+        luma_images_.push_back({rc.out_offset, rc.out_offset, img.win.width, img.win.height, (uint32_t)img.color_kind, (uint32_t)img.orientation});
+        luma_max_tiles_ = std::max(luma_max_tiles_, orient_tiles(img.win.width, img.win.height));
+    }
+}
+
 void DeviceBatch::plan_overlap_halves(UploadPlan &p) {
     overlap_ok_ = false;
     // OFF by default: with the round-2 kernels both stages are HBM-heavy (K2 writes the coefficient buffer at 4.7 TB/s)
@@ -947,7 +989,7 @@ void DeviceBatch::plan_overlap_halves(UploadPlan &p) {
     while (huff_half_ < n_huff_work_ && h_scans_[p.huff_work[huff_half_].scan].image_index < half_image) huff_half_++;
     // worth it for batches that keep the machine busy for milliseconds: the halves cost four launches and two events
     if (wanted && !entropy_only_ && p.sub_work.empty() && p.prog_work.empty() && total_blocks_ >= (4u << 20) && huff_half_ > 0 &&
-        huff_half_ < n_huff_work_ && rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && fancy_convert_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
+        huff_half_ < n_huff_work_ && rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && fancy_convert_.empty() && luma_convert_.empty() && luma_work_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
         idct_win_class_begin_[kNumIdctLayoutClasses] == idct_win_class_begin_[0]) {  // (no windowed image: the halves have no list for their work)
         for (int half = 0; half < 2; half++) {
             idct_half_begin_[half][0] = (int)p.idct_work_halves.size();
@@ -1024,10 +1066,12 @@ int DeviceBatch::upload_plan(const UploadPlan &p, const std::vector<const uint8_
         // + one tile of slack (IDCT DMA reads whole tiles) + the split scans' flag words
         {&d_coefs_, nullptr, 0, entropy_only_ ? 256 : (size_t)coef_store_blocks_ * 128 + (size_t)kIdctBlocksPerWg * 128 + (size_t)p.flag_words * 8 + 256},
         {&d_out_, nullptr, 0, entropy_only_ ? 256 : (size_t)out_bytes_ + 256},
-        {&d_rgb_scratch_, nullptr, 0, rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && fancy_convert_.empty() ? 0 : (size_t)out_bytes_ + 256},
+        {&d_rgb_scratch_, nullptr, 0, rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && fancy_convert_.empty() && luma_convert_.empty() ? 0 : (size_t)out_bytes_ + 256},
         {&d_color_images_, color_images_.data(), color_images_.size() * sizeof(ColorImage), 0},
         {&d_orient_images_, orient_images_.data(), orient_images_.size() * sizeof(OrientImage), 0},
         {&d_fancy_images_, fancy_images_.data(), fancy_images_.size() * sizeof(FancyImage), 0},
+        {&d_luma_images_, luma_images_.data(), luma_images_.size() * sizeof(LumaImage), 0},
+        {&d_luma_work_, luma_work_.data(), luma_work_.size() * sizeof(LumaWork), 0},
         {&d_planes_, nullptr, 0, format_ == JPGPU_FMT_EXTENDED_U16 && !entropy_only_ ? (size_t)planes_bytes_ + 256 : 0},
         {&d_input_, nullptr, 0, (size_t)input_bytes_},
     };

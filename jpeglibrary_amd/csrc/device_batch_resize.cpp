@@ -57,10 +57,11 @@ int DeviceBatch::plan_resize() {
     for (size_t i = 0; i < images_.size(); i++) {
         const ImagePlan &img = images_[i];
         if (img.status != JPGPU_OK || img.jobs.empty() || img.out_bytes == 0 || img.win.width == 0 || img.win.height == 0) continue;
-        if ((uint64_t)img.win.width * img.win.height * 3 != img.out_bytes || img.out_offset + img.out_bytes > out_bytes_) continue;  // (not three tight planes: no entry)
+        const uint64_t planes = one_plane_upload() ? 1u : 3u;  // (a JPGPU_CHANNELS_LUMA upload: ONE tight plane per image, and K4's one-plane form)
+        if ((uint64_t)img.win.width * img.win.height * planes != img.out_bytes || img.out_offset + img.out_bytes > out_bytes_) continue;  // (not `planes` tight planes: no entry)
         ResizeImage d;
         d.src_off = img.out_offset;
-        d.dst_off = (uint64_t)i * 3u * (uint64_t)oh * (uint64_t)ow;
+        d.dst_off = (uint64_t)i * planes * (uint64_t)oh * (uint64_t)ow;
         d.w_in = img.win_oriented.width;  // (the output's size: the window as the caller sees it, turned with the image)
         d.h_in = img.win_oriented.height;
         const auto h = table((int)d.w_in, ow), v = table((int)d.h_in, oh);
@@ -91,7 +92,8 @@ int DeviceBatch::run_resize() {
     if (const int rc = check_resize_format("jpgpu_batch_run_idct"); rc != JPGPU_OK) return rc;
     if (const int rc = plan_resize(); rc != JPGPU_OK) return rc;
     const int ow = resize_.width, oh = resize_.height;
-    const uint64_t bytes = (uint64_t)images_.size() * 3u * (uint64_t)oh * (uint64_t)ow * (uint64_t)fmt_rgb_plane_sample_bytes(resize_.format);
+    const uint64_t planes = one_plane_upload() ? 1u : 3u;
+    const uint64_t bytes = (uint64_t)images_.size() * planes * (uint64_t)oh * (uint64_t)ow * (uint64_t)fmt_rgb_plane_sample_bytes(resize_.format);
     resized_fmt_ = -1;
     hipError_t e = d_resized_.reserve((size_t)bytes);
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(resized images)");
@@ -100,14 +102,15 @@ int DeviceBatch::run_resize() {
     // an image without an entry reads as zeros
     if (bytes != 0 && (e = hipMemsetAsync(d_resized_.ptr, 0, (size_t)bytes, ctx_->stream)) != hipSuccess) return hip_fail(e, "hipMemsetAsync(resized images)");
     if ((e = hipEventRecord(resize_ev_[0], ctx_->stream)) != hipSuccess) return hip_fail(e, "hipEventRecord(resize)");
-    e = launch_resample(ctx_->stream, (const uint8_t *)d_out_.ptr, (const ResizeImage *)d_resize_images_.ptr, n_resize_images_,
-                        (const uint32_t *)d_resize_tables_.ptr, d_resized_.ptr, ow, oh, resize_.format, output_affine_);
+    e = (one_plane_upload() ? launch_resample_luma : launch_resample)(ctx_->stream, (const uint8_t *)d_out_.ptr, (const ResizeImage *)d_resize_images_.ptr, n_resize_images_,
+                                                                (const uint32_t *)d_resize_tables_.ptr, d_resized_.ptr, ow, oh, resize_.format, output_affine_);
     if (e != hipSuccess) return hip_fail(e, "resample_kernel");
     if ((e = hipEventRecord(resize_ev_[1], ctx_->stream)) != hipSuccess) return hip_fail(e, "hipEventRecord(resize)");
     resized_width_ = ow;
     resized_height_ = oh;
     resized_fmt_ = resize_.format;
     resized_images_ = (int)images_.size();
+    resized_planes_ = (int)planes;
     return mark_work();
 }
 
@@ -121,14 +124,14 @@ int DeviceBatch::resized_device(void **ptr, uint64_t *bytes) const {
         return JPGPU_ERR_INVALID_OPERATION;
     }
     *ptr = d_resized_.ptr;
-    *bytes = (uint64_t)resized_images_ * 3u * (uint64_t)resized_height_ * (uint64_t)resized_width_ * (uint64_t)fmt_rgb_plane_sample_bytes(resized_fmt_);
+    *bytes = (uint64_t)resized_images_ * (uint64_t)resized_planes_ * (uint64_t)resized_height_ * (uint64_t)resized_width_ * (uint64_t)fmt_rgb_plane_sample_bytes(resized_fmt_);
     return JPGPU_OK;
 }
 
 int DeviceBatch::download_resized(int i, void *dst, uint64_t bytes) {
     if (resized_fmt_ < 0) return fail(JPGPU_ERR_INVALID_OPERATION, "jpgpu_batch_download_resized: no decode with a resize set has run on this upload");
     if (!dst || i < 0 || i >= resized_images_) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_download_resized: bad argument");
-    const uint64_t slab = 3u * (uint64_t)resized_height_ * (uint64_t)resized_width_ * (uint64_t)fmt_rgb_plane_sample_bytes(resized_fmt_);
+    const uint64_t slab = (uint64_t)resized_planes_ * (uint64_t)resized_height_ * (uint64_t)resized_width_ * (uint64_t)fmt_rgb_plane_sample_bytes(resized_fmt_);
     if (bytes < slab) return fail(JPGPU_ERR_ARGUMENT, "Destination buffer is too small.");
     if (const int rc = sync(); rc != JPGPU_OK) return rc;
     if (resized_fmt_ < 0) return fail(JPGPU_ERR_INVALID_OPERATION, "jpgpu_batch_download_resized: the decode was issued again without its resize");

@@ -201,6 +201,34 @@ struct FancyImage {
 };
 hipError_t launch_fancy_upsample(hipStream_t stream, const uint8_t *scratch, uint8_t *out, uint8_t *staging, const FancyImage *images, int n_images,
                                  int n_staged, uint32_t max_tiles, int format, const YccRgbFactors &kf, const OutputAffine &aff);
+// K3Y (k3y_luma.hip): the images decoded to ONE plane under JPGPU_CHANNELS_LUMA (include/jpgpu.h, "Grey output"), on their two roads.
+// The fast road, luma_idct_kernel: component 0's blocks of a scan, straight from the dense coefficient store to the plane at `out` +
+// DevScan::out_off, pitch win_w samples.  The luma blocks of the window's MCU cover form a grid of cov_cols * h x cov_rows * v blocks (h, v:
+// component 0's factors: the frame's maxima, or v = 1 under a taller MCU, whose sample rows are repeated vs times); a UNIT is kLumaUnitBlocks neighbouring blocks of one row of that grid, one wave's work; a
+// workgroup takes `n_units` (1..kLumaUnitsPerWg) consecutive units, the first being chunk `chunk` of block row `row`, the next ones following
+// in raster order.  ONE launch for all listed scans.  Component 0 is the scan's first component and its blocks are slots 0 .. h * v - 1 of
+// the MCU in raster order (DeviceBatch::luma_fast checks both).  windowed: a listed scan's win_* / cov_* differ from the whole frame's.
+constexpr uint32_t kLumaUnitBlocks = 64, kLumaUnitsPerWg = 4;
+struct LumaWork {
+    uint32_t scan;
+    uint32_t row, chunk;  // the first unit: block row of the cover's luma grid, chunk of kLumaUnitBlocks blocks in it
+    uint32_t n_units;
+};
+hipError_t launch_luma_idct(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const LumaWork *work, int n_work, bool windowed,
+                            const DevScanStatus *status, const DevQuantTable *quant_pool, uint8_t *out, int format, const OutputAffine &aff);
+// The scratch road, luma_plane_kernel: from the INTERLEAVED_U8 samples K3's generic class left in `scratch` -- `width` x `height` pixels of
+// the STORED frame (the image's window there), 1, 3 or 4 bytes each by kind, tight -- to the one plane in `out`, turned by `orientation`
+// (1..8) like K3O turns: ONE launch for all of them, a descriptor per image, a workgroup per tile of kOrientTile x kOrientTile source pixels.
+// The sample is byte 0 for the kinds GRAY and YCBCR, L = (19595 R + 38470 G + 7471 B + 32768) >> 16 of K3C's pixel for RGB, CMYK and YCCK.
+// src_off and dst_off are multiples of 256; max_tiles: the largest orient_tiles(width, height) among the descriptors.
+struct LumaImage {
+    uint64_t src_off, dst_off;  // bytes into `scratch` / `out`
+    uint32_t width, height;     // of the stored window
+    uint32_t kind;              // ColorKind
+    uint32_t orientation;       // 1..8
+};
+hipError_t launch_luma_plane(hipStream_t stream, const uint8_t *scratch, uint8_t *out, const LumaImage *images, int n_images, uint32_t max_tiles,
+                             int format, const YccRgbFactors &kf, const OutputAffine &aff);
 
 // Waves per workgroup of the POOLED form of the K2S final pass (k2s_subseq.hip: runs of scans that stage the same tables; one workgroup per CU, every wave takes the
 // next 64 lanes from a counter): 10 waves + 4 tables fill a CU's LDS.  Runs shorter than kSubFinalPoolMinChunks waves, and runs
@@ -325,4 +353,8 @@ struct ResizeImage {
 };
 hipError_t launch_resample(hipStream_t stream, const uint8_t *src, const ResizeImage *images, int n_images, const uint32_t *tables, void *dst,
                            int out_width, int out_height, int sample_format, const OutputAffine &aff);
+// K4 on one plane (k4y_resample_luma.hip): the grey planes of a JPGPU_CHANNELS_LUMA upload of RGB_PLANAR_U8, ONE tight plane per image at
+// src_off, to one dense T[n][1][out_height][out_width].  The same descriptors, tables and function per plane; aff.scale[0] and aff.bias[0].
+hipError_t launch_resample_luma(hipStream_t stream, const uint8_t *src, const ResizeImage *images, int n_images, const uint32_t *tables, void *dst,
+                                int out_width, int out_height, int sample_format, const OutputAffine &aff);
 }  // namespace jpgpu
