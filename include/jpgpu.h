@@ -522,6 +522,51 @@ int jpgpu_batch_image_channels(const jpgpu_batch *b, int i, int *channels);
 /* counts[0] = images of this upload planned on the fast road, counts[1] = on the scratch road.  Valid after an upload. */
 int jpgpu_batch_luma_work(const jpgpu_batch *b, int32_t counts[2]);
 
+/* ---- Arithmetic: the transform and the colour constants of libjpeg in place of the reference's (an extension beyond the reference; what
+ * Pillow, torchvision and OpenCV deliver, all on libjpeg-turbo's jpeg_idct_islow).
+ *   By default (JPGPU_ARITHMETIC_REFERENCE) every format decodes as before, bit for bit.  Under JPGPU_ARITHMETIC_LIBJPEG the five RGB formats
+ * (RGB_U8, RGBA_U8, RGB_PLANAR_U8 / _F16 / _F32) change in two places; every other format ignores the policy.
+ *   1. THE TRANSFORM, per image (jpgpu_batch_image_arithmetic says which one an image took).  For every 8 x 8 block, with coef[k] its int16
+ * coefficients and q[k] the uint16 quantisers of its component:
+ *       d[k] = (int32)coef[k] * (int32)q[k]                                     (int16 x uint16: no overflow)
+ *     then libjpeg's jidctint.c, CONST_BITS = 13, PASS1_BITS = 2, on the eight values d0..d7 of each COLUMN first, then of each ROW of the
+ *     workspace the columns left:
+ *       z1 = (d2 + d6) * 4433      e2 = z1 - d6 * 15137       e3 = z1 + d2 * 6270       e0 = (d0 + d4) << 13       e1 = (d0 - d4) << 13
+ *       t10 = e0 + e3    t13 = e0 - e3    t11 = e1 + e2    t12 = e1 - e2
+ *       t0 = d7   t1 = d5   t2 = d3   t3 = d1       z1 = t0 + t3   z2 = t1 + t2   z3 = t0 + t2   z4 = t1 + t3     z5 = (z3 + z4) * 9633
+ *       t0 *= 2446   t1 *= 16819   t2 *= 25172   t3 *= 12299     z1 *= -7373   z2 *= -20995   z3 = z3 * -16069 + z5   z4 = z4 * -3196 + z5
+ *       t0 += z1 + z3    t1 += z2 + z4    t2 += z2 + z3    t3 += z1 + z4
+ *       out0, out7 = t10 +- t3     out1, out6 = t11 +- t2     out2, out5 = t12 +- t1     out3, out4 = t13 +- t0
+ *     each out descaled: (x + 1024) >> 11 behind the columns, (x + 131072) >> 18 behind the rows.  The sample is clamp(v + 128, 0, 255).
+ *     Every sum, product and left shift is 32-bit two's complement and WRAPS; the two descales are arithmetic right shifts of the wrapped
+ *     value.  The clamp is what libjpeg's SIMD code does (it saturates); its C code reads a table that wraps at +-512 around the centre.
+ *     Equality with libjpeg is claimed where every dequantised coefficient and workspace value fits int16 and every pass sum fits int32 --
+ *     every file an encoder made --; outside that range the function above is what is pinned.
+ *     An image takes it if its frame precision is 8, it has 1, 3 or 4 components as its colour kind has, every scan of it has at most 16
+ *     blocks per MCU and components that are replicated by 1, 2 or 4 in each direction, no two of its sequential scans write the same
+ *     component and no scan names a component twice, no sequential component has several blocks per MCU line or column that are replicated as
+ *     well, and its progressive frame, if it is one, is not the kind whose Dispose() the reference runs slot by slot.  Every other image
+ *     keeps the reference's float transform.  So does the second issue of a progressive file that failed, whose pixels are not defined.
+ *   2. THE COLOUR CONSTANTS, per upload: every YCbCr -> RGB step of the decode (YCCK's inner one too) takes libjpeg's
+ *     R = Y + (91881 * Cr + 32768 >> 16), B = Y + (116130 * Cb + 32768 >> 16), G = Y + (-22554 * Cb - 46802 * Cr + 32768 >> 16)
+ *     in place of the reference's, which differ in one constant (-22553).  The CMYK product and the grey formula of JPGPU_CHANNELS_LUMA stay.
+ *   Chroma upsampling stays its own policy: JPGPU_ARITHMETIC_LIBJPEG alone keeps replication; with JPGPU_UPSAMPLE_FANCY the pixels are
+ * libjpeg's default output.  Windows, the colour policy, orientation, grey output, the float samples and the resize stage compose: an image
+ * that takes the transform goes through the scratch image like a filtered one, and everything behind it reads its samples.
+ *   State of the batch like the colour policy: every later upload of whole files reads it until it is set again.
+ *   Not covered: jpgpu_decoder_*, jpgpu_decode_scan, jpgpu_progressive_*, jpgpu_multi_*, jpgpu_batch_upload_frames (the reference's arithmetic,
+ * as before); libjpeg's other transforms (ifast, float, the scaled ones); 12-bit frames. */
+typedef enum jpgpu_arithmetic_policy {
+    JPGPU_ARITHMETIC_REFERENCE = 0, /* the reference's float transform and constants, as before */
+    JPGPU_ARITHMETIC_LIBJPEG = 1    /* jpeg_idct_islow and libjpeg's colour constants */
+} jpgpu_arithmetic_policy;
+/* JPGPU_ERR_ARGUMENT for any other value. */
+int jpgpu_batch_set_arithmetic_policy(jpgpu_batch *b, int policy);
+/* JPGPU_ARITHMETIC_LIBJPEG where image i was planned with the integer transform, else JPGPU_ARITHMETIC_REFERENCE (the policy unset, a format
+ * that does not read it, an image outside the rule above, an image that failed at upload).  Valid after an upload; JPGPU_ERR_ARGUMENT for a
+ * NULL argument or an index out of range. */
+int jpgpu_batch_image_arithmetic(const jpgpu_batch *b, int i, int *arithmetic);
+
 /* Coefficient hand-off for multi-scan (progressive, SOF2) images -- BASELINE config 5's "coefficient accumulate then single
  * IDCT pass": the caller's progressive entropy decoder accumulates the coefficient store, the GPU runs what
  * JpegHuffmanProgressiveScanDecoder.Dispose (ScanDecoder/JpegHuffmanProgressiveScanDecoder.cs:421-470: dequantise, IDCT,

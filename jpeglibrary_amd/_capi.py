@@ -138,6 +138,8 @@ ORIENTATION_POLICIES = ("stored", "file")
 UPSAMPLING_POLICIES = ("replicate", "fancy")
 # jpgpu_channels_policy, by its Python names
 CHANNELS_POLICIES = ("rgb", "gray")
+# jpgpu_arithmetic_policy, by its Python names
+ARITHMETIC_POLICIES = ("reference", "libjpeg")
 
 UPLOAD_PINNED = 1
 UPLOAD_PINNED_ARENA = 2
@@ -204,6 +206,8 @@ SYMBOLS = [
     ("jpgpu_batch_set_channels_policy", C.c_int, [_P, C.c_int]),
     ("jpgpu_batch_image_channels", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("jpgpu_batch_luma_work", C.c_int, [_P, C.POINTER(C.c_int32)]),
+    ("jpgpu_batch_set_arithmetic_policy", C.c_int, [_P, C.c_int]),
+    ("jpgpu_batch_image_arithmetic", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("jpgpu_sizeof_device_ingest_stats", C.c_size_t, []),
     ("jpgpu_batch_device_ingest_stats", C.c_int, [_P, C.POINTER(DeviceIngestStats)]),
     ("jpgpu_batch_upload_frames", C.c_int, [_P, C.POINTER(Frame), C.c_void_p, C.c_int, C.c_int]),

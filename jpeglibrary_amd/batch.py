@@ -168,6 +168,14 @@ def _upsampling_policy(upsampling, who="upsampling"):
     return _capi.UPSAMPLING_POLICIES.index(upsampling)
 
 
+def _arithmetic_policy(arithmetic, who="arithmetic"):
+    """The check of Batch.set_arithmetic_policy / decode_batch(arithmetic=...), before any library call: "reference" or "libjpeg" -> the
+    jpgpu_arithmetic_policy value"""
+    if not isinstance(arithmetic, str) or arithmetic not in _capi.ARITHMETIC_POLICIES:
+        raise ValueError('%s is "reference" (the reference\'s float transform and constants) or "libjpeg" (its integer transform and colour constants), not %r' % (who, arithmetic))
+    return _capi.ARITHMETIC_POLICIES.index(arithmetic)
+
+
 def _channels_policy(mode, fmt=None, who="mode"):
     """The check of Batch.set_channels_policy / decode_batch(mode=...), before any library call: "rgb" or "gray" -> the jpgpu_channels_policy
     value.  fmt: the format "gray" is asked for with; only RGB_PLANAR_U8 / _F16 / _F32 have a one-plane form."""
@@ -384,6 +392,22 @@ class Batch:
         ms = C.c_float()
         self._check(_lib.jpgpu_batch_upsampling_ms(self._h, C.byref(ms)))
         return ms.value
+
+    def set_arithmetic_policy(self, arithmetic):
+        """Which arithmetic the RGB formats decode with from the next upload on: "reference", the default -- the reference's float transform and
+        colour constants, as ever -- or "libjpeg": jpeg_idct_islow, libjpeg's integer transform, and its colour constants (include/jpgpu.h,
+        "Arithmetic"), bit for bit what Pillow, torchvision and OpenCV compute; with set_upsampling_policy("fancy") the pixels are theirs.
+        Every other format ignores it.  State of the batch: it holds until set again.  ValueError, before the library is called, for any
+        other value."""
+        self._check(_lib.jpgpu_batch_set_arithmetic_policy(self._h, _arithmetic_policy(arithmetic)))
+        return self
+
+    def arithmetic(self, i):
+        """1 where image i was planned with libjpeg's integer transform, else 0 (the policy unset, a format that does not read it, a 12-bit
+        frame or another image outside the rule of include/jpgpu.h)"""
+        a = C.c_int()
+        raise_for_status(_lib.jpgpu_batch_image_arithmetic(self._h, i, C.byref(a)), b"jpgpu_batch_image_arithmetic: no such image")
+        return a.value
 
     def set_channels_policy(self, mode):
         """How many planes RGB_PLANAR_U8 / _F16 / _F32 deliver from the next upload on: "rgb", the default -- three, as ever -- or "gray": ONE
@@ -695,25 +719,28 @@ class Batch:
             pass
 
 
-def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb"):
+def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb", arithmetic="reference"):
     """One-call helper: returns (outputs, results).  files: bytes-like objects, or 1-D uint8 torch tensors on the context's device.
     windows: one (x, y, w, h) per file (Batch.set_windows): outputs[i] is that rectangle of image i.
     color: "ycc" or "file" (Batch.set_color_policy): under "file" the RGB formats deliver RGB for CMYK, YCCK and Adobe-RGB files.
     orientation: "stored" or "file" (Batch.set_orientation_policy); orientations: one value 0..8 per file (Batch.set_orientations).  Windows
     are then in pixels of the oriented frame.
     upsampling: "replicate" or "fancy" (Batch.set_upsampling_policy): under "fancy" the RGB formats filter 4:2:2 / 4:2:0 / 4:4:0 chroma as libjpeg does.
-    mode: "rgb" or "gray" (Batch.set_channels_policy): under "gray" RGB_PLANAR_U8 / _F16 / _F32 give one plane, [1, H, W]; ValueError for another fmt."""
+    mode: "rgb" or "gray" (Batch.set_channels_policy): under "gray" RGB_PLANAR_U8 / _F16 / _F32 give one plane, [1, H, W]; ValueError for another fmt.
+    arithmetic: "reference" or "libjpeg" (Batch.set_arithmetic_policy): under "libjpeg" the RGB formats decode with libjpeg's integer transform and constants."""
     files = list(files)
     windows = _window_rects(windows, len(files))
     _color_policy(color)
     _orientation_policy(orientation)
     _upsampling_policy(upsampling)
+    _arithmetic_policy(arithmetic)
     _channels_policy(mode, fmt)
     orientations = _orientation_list(orientations, len(files))
     b = Batch(ctx)
     b.set_color_policy(color)
     b.set_orientation_policy(orientation)
     b.set_upsampling_policy(upsampling)
+    b.set_arithmetic_policy(arithmetic)
     b.set_channels_policy(mode)
     if orientations is not None:
         b.set_orientations(orientations)
@@ -729,7 +756,7 @@ def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="y
     return outs, results
 
 
-def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb"):
+def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb", arithmetic="reference"):
     """One-call helper for torch consumers: returns (tensors, results), tensors[i] = Batch.output_tensor(i) -- uint8[3, H, W] on the
     context's device by default -- or None for an image that failed.  Nothing is downloaded.  The batch is not closed: its output
     buffer is the tensors' memory and is freed with the last of them.  files: bytes-like objects, or 1-D uint8 torch tensors on the
@@ -748,12 +775,16 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     mode: "rgb" or "gray" (Batch.set_channels_policy): under "gray" tensors[i] is [1, H, W] -- the luma samples of a grey or YCbCr file, decoded
     without touching its chroma, or Pillow's convert("L") of a CMYK, YCCK or Adobe-RGB file under color="file".  mean and std are then a number or
     a sequence of one; every other argument composes, and upsampling="fancy" changes nothing (no chroma is read).  ValueError for a fmt that is
-    not RGB_PLANAR_*."""
+    not RGB_PLANAR_*.
+    arithmetic: "reference" or "libjpeg" (Batch.set_arithmetic_policy): under "libjpeg" the samples come from libjpeg's integer transform
+    (jpeg_idct_islow) and its colour constants; with upsampling="fancy" tensors[i] holds exactly the pixels Pillow and torchvision decode.
+    Everything else composes on it."""
     files = list(files)
     windows = _window_rects(windows, len(files))
     _color_policy(color)
     _orientation_policy(orientation)
     _upsampling_policy(upsampling)
+    _arithmetic_policy(arithmetic)
     orientations = _orientation_list(orientations, len(files))
     if dtype is not None:
         import torch
@@ -776,6 +807,7 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     b.set_color_policy(color)
     b.set_orientation_policy(orientation)
     b.set_upsampling_policy(upsampling)
+    b.set_arithmetic_policy(arithmetic)
     b.set_channels_policy(mode)
     if orientations is not None:
         b.set_orientations(orientations)
@@ -791,7 +823,7 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     return tensors, results
 
 
-def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb"):
+def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb", arithmetic="reference"):
     """One-call helper for fixed-size consumers: returns (tensor, results), tensor = Batch.resized_tensor() -- ONE [N, 3, oh, ow] tensor on the
     context's device, size = (oh, ow), dtype torch.float16 (the default), torch.float32 or torch.uint8 -- every image decoded to RGB and
     resampled to that size (antialiased bilinear) in one launch behind the output stage; the slab of an image that failed is zero and
@@ -802,7 +834,8 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
     color: "ycc" or "file" (Batch.set_color_policy), orientation and orientations (Batch.set_orientation_policy / set_orientations), as in
     decode_to_tensors: the oriented image is what is resampled.  upsampling: "replicate" or "fancy" (Batch.set_upsampling_policy): under "fancy"
     the image that is resampled has libjpeg's filtered chroma.  mode: "rgb" or "gray" (Batch.set_channels_policy): under "gray" the tensor is
-    [N, 1, oh, ow], the grey plane of decode_to_tensors(mode="gray") resampled by the same function; mean and std are a number or a sequence of one."""
+    [N, 1, oh, ow], the grey plane of decode_to_tensors(mode="gray") resampled by the same function; mean and std are a number or a sequence of one.
+    arithmetic: "reference" or "libjpeg" (Batch.set_arithmetic_policy): under "libjpeg" the image that is resampled is libjpeg's decode."""
     import torch
 
     files = list(files)
@@ -810,6 +843,7 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
     _color_policy(color)
     _orientation_policy(orientation)
     _upsampling_policy(upsampling)
+    _arithmetic_policy(arithmetic)
     orientations = _orientation_list(orientations, len(files))
     dtype = torch.float16 if dtype is None else dtype
     _resize_setting(size, dtype)
@@ -826,6 +860,7 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
     b.set_color_policy(color)
     b.set_orientation_policy(orientation)
     b.set_upsampling_policy(upsampling)
+    b.set_arithmetic_policy(arithmetic)
     b.set_channels_policy(mode)
     if orientations is not None:
         b.set_orientations(orientations)

@@ -43,7 +43,7 @@ void DevBuffer::release() {
 
 DeviceBatch::~DeviceBatch() {
     if (ctx_) (void)hipSetDevice(ctx_->device);
-    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_color_images_, &d_orient_images_, &d_fancy_images_, &d_luma_images_, &d_luma_work_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
+    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_color_images_, &d_orient_images_, &d_fancy_images_, &d_luma_images_, &d_luma_work_, &d_islow_work_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
         b->release();
     for (hipEvent_t &e : ev_pool_)
         if (e) (void)hipEventDestroy(e);
@@ -88,7 +88,7 @@ uint64_t DeviceBatch::slot_bytes(const ImagePlan &img) {
         const uint64_t samples = img.orientation != 1 ? fancy_staging_offset(img) + (uint64_t)img.win.width * img.win.height * 3 : (uint64_t)f.width * f.height * 3;
         return std::max(img.out_bytes, samples);
     }
-    const bool through_scratch = color_kind_by_file(img.color_kind) || img.orientation != 1 || img.luma == kLumaScratch;
+    const bool through_scratch = color_kind_by_file(img.color_kind) || img.orientation != 1 || img.luma == kLumaScratch || img.islow;
     const uint64_t samples = through_scratch ? (uint64_t)img.win.width * img.win.height * color_kind_sample_bytes(img.color_kind) : 0u;
     return std::max(img.out_bytes, samples);
 }
@@ -177,6 +177,56 @@ bool DeviceBatch::luma_fast(const ImagePlan &img, const std::vector<ScanJob> &jo
     return true;
 }
 
+int DeviceBatch::set_arithmetic_policy(int policy) {
+    if (policy != JPGPU_ARITHMETIC_REFERENCE && policy != JPGPU_ARITHMETIC_LIBJPEG) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_set_arithmetic_policy: unknown policy");
+    arithmetic_policy_ = policy;
+    return JPGPU_OK;
+}
+
+int DeviceBatch::image_arithmetic(int i, int *arithmetic) const {
+    const ImagePlan *img = image(i);
+    if (!img || !arithmetic) return JPGPU_ERR_ARGUMENT;
+    *arithmetic = img->status == JPGPU_OK && img->islow ? JPGPU_ARITHMETIC_LIBJPEG : JPGPU_ARITHMETIC_REFERENCE;
+    return JPGPU_OK;
+}
+
+// libjpeg's jdcolor.c: FIX(1.40200), -FIX(0.71414), FIX(1.77200), -FIX(0.34414) -- the last one is where the reference's differ (-22553)
+YccRgbFactors DeviceBatch::color_factors() const {
+    if (islow_upload_ && whole_files_) return YccRgbFactors{91881, -46802, 116130, -22554};
+    return ycc_rgb_factors();
+}
+
+bool DeviceBatch::islow_taken(int policy, int format, const ImagePlan &img, const std::vector<ScanJob> &jobs, bool keep_canvas) {
+    if (policy != JPGPU_ARITHMETIC_LIBJPEG || !fmt_is_rgb(format) || img.precision != 8 || keep_canvas || jobs.empty()) return false;
+    // (K3J stores color_kind_sample_bytes() bytes per pixel of the scratch slot, one per frame component)
+    if (img.num_components < 1 || img.num_components > kMaxScanComponents || img.num_components != color_kind_sample_bytes(img.color_kind)) return false;
+    auto pow2 = [](int r) { return r == 1 || r == 2 || r == 4; };
+    uint32_t written = 0;  // frame components some sequential scan has written
+    for (const ScanJob &job : jobs) {
+        if (job.kind == kScanProgressive) continue;  // (an entropy scan of a progressive frame: no transform of its own)
+        if (job.kind == kScanFrameOnly && job.dispose_generic) return false;  // the literal Dispose(): the store holds samples when the output stage runs
+        if (job.blocks_per_mcu < 1 || job.blocks_per_mcu > kMaxBlocksPerMcu || job.geo.mcus_per_line <= 0 || job.geo.mcus_per_column <= 0) return false;
+        if (job.scan_components < 1 || job.scan_components > kMaxScanComponents) return false;
+        uint32_t mask = 0;
+        for (int c = 0; c < job.scan_components; c++) {
+            const ResolvedScanComponent &sc = job.comp[c];
+            if (sc.component_index < 0 || sc.component_index >= img.num_components) return false;
+            if ((mask >> sc.component_index) & 1u) return false;  // named twice: the later block wins, K3's business
+            mask |= 1u << sc.component_index;
+            if (!pow2(sc.hs) || !pow2(sc.vs)) return false;
+            // several blocks per MCU line or column that are replicated as well overlap in a sequential scan (k3_idct.hip)
+            if (job.kind == kScanSequential && ((sc.h > 1 && sc.hs > 1) || (sc.v > 1 && sc.vs > 1))) return false;
+        }
+        for (int k = 0; k < job.blocks_per_mcu; k++)
+            if (job.blk_comp[k] >= job.scan_components) return false;
+        if (job.kind == kScanSequential) {
+            if (mask & written) return false;  // scans ordered behind each other: K3's levels
+            written |= mask;
+        }
+    }
+    return true;
+}
+
 int DeviceBatch::upsampling_ms(float *ms) {
     if (!ms) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upsampling_ms: null argument");
     if (!fancy_timed_) return fail(JPGPU_ERR_INVALID_OPERATION, "jpgpu_batch_upsampling_ms: no K3U call of this upload was timed (JPGPU_TIME_UPSAMPLE=1 at the upload, a filtered image, a decode)");
@@ -203,6 +253,7 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
     img.chroma_hs = img.chroma_vs = 0;
     img.fancy = false;
     img.luma = kLumaNone;
+    img.islow = false;
     if (fh.num_components == 3 && fh.components.size() == 3) {
         const auto &c0 = fh.components[0], &c1 = fh.components[1], &c2 = fh.components[2];
         if (c0.h == geo.max_h && c0.v == geo.max_v && c1.h == c2.h && c1.v == c2.v && c1.h > 0 && c1.v > 0 && geo.max_h % c1.h == 0 && geo.max_v % c1.v == 0) {
@@ -455,6 +506,7 @@ int DeviceBatch::upload_progressive_dispose(const ProgressiveFrame &frame, int f
 int DeviceBatch::upload_frames(const jpgpu_frame *frames, const uint16_t *qt, int n, int format) {
     whole_files_ = false;
     luma_upload_ = false;  // (frames decode to three planes whatever the channels policy)
+    islow_upload_ = false;  // (... and with the reference's arithmetic whatever the arithmetic policy)
     device_ingest_ = jpgpu_device_ingest_stats();
     if (windows_pending_ || orientations_pending_) {  // (both are for uploads of whole files: consumed and refused, the batch left empty)
         const bool windows = windows_pending_;

@@ -128,6 +128,9 @@ struct ImagePlan {
     // image has ONE plane and takes the fast road (kLumaFast: DeviceBatch::luma_fast holds; K3Y's luma_idct_kernel reads its scan's store, and
     // no K3 list names it) or the scratch road (kLumaScratch: planned like an oriented image, K3's generic class, then K3Y's luma_plane_kernel)
     uint8_t luma = kLumaNone;
+    // arithmetic (include/jpgpu.h, "Arithmetic"): the image takes libjpeg's integer transform (DeviceBatch::islow_taken holds): planned like a
+    // filtered image -- scratch road, dense hand-off --, its scans in K3J's work list and in none of K3's; never on K3Y's fast road
+    bool islow = false;
 };
 
 class WorkCrew;
@@ -178,6 +181,10 @@ class DeviceBatch {
     int set_channels_policy(int policy);
     int image_channels(int i, int *channels) const;
     int luma_work(int32_t counts[2]) const;  // jpgpu_batch_luma_work
+    // The arithmetic policy (jpgpu_batch_set_arithmetic_policy): state of the batch like the colour policy, read by every later upload of whole
+    // files under an RGB format.
+    int set_arithmetic_policy(int policy);
+    int image_arithmetic(int i, int *arithmetic) const;
     uint64_t idct_listed_mcus() const { return idct_listed_mcus_; }
     // One progressive frame collected by the JpegDecoder mirror: its entropy scans + the Dispose() pass.
     int upload_progressive_frame(const ProgressiveFrame &frame, const uint8_t *file, size_t file_len, int sof, int format);
@@ -300,6 +307,11 @@ class DeviceBatch {
     // factors, its blocks the MCU's first in raster order; no caller's canvas).  jobs: the scan jobs of the image's file plan.
     static bool luma_fast(const ImagePlan &img, const std::vector<ScanJob> &jobs, bool keep_canvas);
     void plan_luma_work(size_t ii, int j);
+    // The one decision of the arithmetic policy: does this image take libjpeg's integer transform (K3J) -- the policy, the format, its
+    // precision and components, and of every scan job of its file plan: the blocks per MCU, replication by 1, 2 or 4, no component written twice,
+    // no overlapping blocks, no literal Dispose(); no caller's canvas.  include/jpgpu.h states the rule.
+    static bool islow_taken(int policy, int format, const ImagePlan &img, const std::vector<ScanJob> &jobs, bool keep_canvas);
+    void plan_islow_work(size_t ii, int j);
     void plan_luma_convert();
     // ingest (jpgpu_batch_upload*), see device_batch_ingest.cpp
     void plan_file_headers(const uint8_t *file, size_t len, FilePlan &fp) const;
@@ -528,6 +540,13 @@ class DeviceBatch {
     int n_luma_fast_ = 0;
     bool luma_work_windowed_ = false;
     DevBuffer d_luma_images_, d_luma_work_;
+    // ... and the scans of the images that take libjpeg's integer transform under JPGPU_ARITHMETIC_LIBJPEG: K3J's own work list, one launch
+    // behind K3's (plan_islow_work); the images themselves are in the conversion lists like every image of the scratch road
+    std::vector<IslowWork> islow_work_;
+    DevBuffer d_islow_work_;
+    int arithmetic_policy_ = JPGPU_ARITHMETIC_REFERENCE;
+    bool islow_upload_ = false;  // the last upload of whole files was made under JPGPU_ARITHMETIC_LIBJPEG and an RGB format: libjpeg's colour constants
+    YccRgbFactors color_factors() const;  // of this upload's YCbCr -> RGB steps: the reference's, or libjpeg's (islow_upload_)
     int channels_policy_ = JPGPU_CHANNELS_RGB;
     bool luma_upload_ = false;  // the last upload of whole files was made under JPGPU_CHANNELS_LUMA and an RGB_PLANAR_* format: one plane per image
     bool one_plane_upload() const { return luma_upload_ && whole_files_; }  // (what the resize stage sizes its slabs by)

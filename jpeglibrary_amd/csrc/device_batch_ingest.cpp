@@ -399,6 +399,7 @@ int DeviceBatch::image_window(int i, jpgpu_rect *window) const {
 // call, decided before anything is enqueued; they leave the batch empty.
 int DeviceBatch::take_windows(int n, int format, const char *what) {
     luma_upload_ = channels_policy_ == JPGPU_CHANNELS_LUMA && fmt_is_rgb_planes(format);  // (this upload's images have one plane each)
+    islow_upload_ = arithmetic_policy_ == JPGPU_ARITHMETIC_LIBJPEG && fmt_is_rgb(format);  // (this upload's colour steps take libjpeg's constants)
     windows_.clear();
     orientations_.clear();
     if (!windows_pending_ && !orientations_pending_) return JPGPU_OK;
@@ -440,7 +441,9 @@ void DeviceBatch::apply_window(size_t i, const std::vector<ScanJob> &jobs) {
     }
     img.orientation = (uint8_t)o;
     const bool one_plane = channels_policy_ == JPGPU_CHANNELS_LUMA && fmt_is_rgb_planes(format_);
-    img.luma = !one_plane ? kLumaNone : (luma_fast(img, jobs, keep_canvas_) ? kLumaFast : kLumaScratch);
+    // (an image that takes libjpeg's transform is never on K3Y's fast road, which runs K3's: its grey plane comes from the scratch slot K3J fills)
+    img.islow = islow_taken(arithmetic_policy_, format_, img, jobs, keep_canvas_ || entropy_only_);
+    img.luma = !one_plane ? kLumaNone : (!img.islow && luma_fast(img, jobs, keep_canvas_) ? kLumaFast : kLumaScratch);
     img.fancy = fancy_filtered(upsample_policy_, format_, img);  // (the window only decides which of its pixels come out; never a grey image)
     const uint32_t ow = orientation_transposes(o) ? img.height : img.width, oh = orientation_transposes(o) ? img.width : img.height;  // the oriented frame
     jpgpu_rect w = windows_.empty() ? jpgpu_rect{0, 0, 0, 0} : windows_[i];

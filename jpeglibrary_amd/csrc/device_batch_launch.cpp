@@ -255,7 +255,7 @@ int DeviceBatch::run_idct(bool with_resize) {
     }
     redo_.clear();  // (K3 writes this plan's samples over what a re-plan copied in: result() / download_output() plan again)
     if (k2s_unchecked_) k2s_idct_behind_ = true;
-    const YccRgbFactors kf = ycc_rgb_factors();
+    const YccRgbFactors kf = color_factors();
     int rc0 = clear_partial_outputs();
     if (rc0 != JPGPU_OK) return rc0;
     if ((rc0 = run_dispose_passes(ctx_->stream)) != JPGPU_OK) return rc0;
@@ -275,6 +275,10 @@ int DeviceBatch::run_idct(bool with_resize) {
                          luma_work_windowed_, (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr, (uint8_t *)d_out_.ptr, format_,
                          output_affine_);
     if (e != hipSuccess) return hip_fail(e, "luma_idct_kernel");
+    // the images that take libjpeg's integer transform (JPGPU_ARITHMETIC_LIBJPEG): every block of their scans, one launch, into the scratch image
+    e = launch_islow(ctx_->stream, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const IslowWork *)d_islow_work_.ptr, (int)islow_work_.size(),
+                     (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr, (uint8_t *)d_rgb_scratch_.ptr);
+    if (e != hipSuccess) return hip_fail(e, "islow_kernel");
     // scans ordered behind earlier scans of their image (and the failing MCU of a caller's canvas): one bytewise launch per level
     for (size_t lv = 0; lv + 1 < idct_later_begin_.size(); lv++) {
         int cb[kNumIdctLayoutClasses + 1];
@@ -435,7 +439,7 @@ int DeviceBatch::decode() {
         if ((rc = mark(3, s1)) != JPGPU_OK) return rc;
     } else {
         status_valid_ = false;
-        const YccRgbFactors kf = ycc_rgb_factors();
+        const YccRgbFactors kf = color_factors();
         if ((rc = run_marker_index()) != JPGPU_OK) return rc;
         if ((rc = clear_partial_outputs()) != JPGPU_OK) return rc;
         auto k2 = [&](hipStream_t st, int first, int n) {

@@ -197,6 +197,7 @@ void DeviceBatch::reset_upload_state(const UploadPlan &p) {
     fancy_convert_.clear();
     luma_convert_.clear();
     luma_work_.clear();
+    islow_work_.clear();
     n_luma_fast_ = 0;
     luma_work_windowed_ = false;
     fancy_timed_ = false;
@@ -528,8 +529,9 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
     // (a windowed image's scan is always handed over dense: the split form of K3 would need a window variant of its own)
     // (... and so is an oriented image's and a filtered one's: its samples go through the scratch image, which only the generic class fills)
     // (... and a grey image's, on either road: K3Y reads component 0's blocks at their places in the dense store, the scratch road is the generic class)
-    const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed && img.orientation == 1 && !img.fancy && img.luma == kLumaNone, split_always = p.sw.handoff_set;
-    const int k3_class = fmt_is_interleaved(format_) && !color_kind_by_file(img.color_kind) && img.orientation == 1 && !img.fancy && img.luma == kLumaNone ? idct_layout_class(s) : 0;
+    // (... and the scans of an image that takes libjpeg's transform: K3J reads every block at its place in the dense store)
+    const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed && img.orientation == 1 && !img.fancy && img.luma == kLumaNone && !img.islow, split_always = p.sw.handoff_set;
+    const int k3_class = fmt_is_interleaved(format_) && !color_kind_by_file(img.color_kind) && img.orientation == 1 && !img.fancy && img.luma == kLumaNone && !img.islow ? idct_layout_class(s) : 0;
     if (split_wanted && job.kind == kScanSequential && s.dri != 0 && img.jobs.size() == 1 && !img.replay_skip && s.total_mcus > 0 &&
         s.blocks_per_mcu != 0 && k3_variant(format_, k3_class, kK3Split).exists &&
         // The planes pay where few blocks reach into coefficients 32..63; all that is known of that in front of the decode is
@@ -576,6 +578,15 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
         return;
     }
     const bool rgb_out = fmt_is_rgb(format_);
+    // An image that takes libjpeg's transform (JPGPU_ARITHMETIC_LIBJPEG): no entry in any K3 list -- K3J's own work, which leaves the samples in
+    // the scratch image where the generic class would, for the conversion the image is listed for.  (Not where the store holds samples by now:
+    // the second issue of a progressive file that failed runs Dispose() literally, and K3 flushes what it left.)
+    if (img.islow && (s.reserved0 & kScanStoreHoldsSamples) == 0) {
+        list_rgb_convert(ii);
+        p.scan_level[(size_t)j] = 0;
+        plan_islow_work(ii, j);
+        return;
+    }
     const uint32_t generic_per_wg = (uint32_t)kIdctBlocksPerWg / s.blocks_per_mcu;
     uint32_t mcus_per_wg = generic_per_wg;
     if (p.sw.tile_align) {
@@ -961,6 +972,15 @@ void DeviceBatch::plan_luma_work(size_t ii, int j) {
         luma_work_.push_back({(uint32_t)j, (uint32_t)(u / chunks), (uint32_t)(u % chunks), (uint32_t)std::min<uint64_t>(kLumaUnitsPerWg, units - u)});
 }
 
+// K3J's work for one scan of an image that takes libjpeg's transform: every block of the window's MCU cover, MCU row by MCU row, the blocks
+// of kIslowThreads / blocks_per_mcu consecutive MCUs of a row per workgroup.
+void DeviceBatch::plan_islow_work(size_t ii, int j) {
+    const DevScan &s = h_scans_[j];
+    const uint32_t row_blocks = (uint32_t)s.cov_cols * s.blocks_per_mcu, step = islow_blocks_per_wg(s.blocks_per_mcu);
+    for (uint32_t row = 0; row < s.cov_rows; row++)
+        for (uint32_t first = 0; first < row_blocks; first += step) islow_work_.push_back({(uint32_t)j, row, first, 0u});
+}
+
 // The descriptors of K3Y's scratch-road launch: one per grey image that is not on the fast road, with the stored window K3 leaves in the
 // scratch image.
 void DeviceBatch::plan_luma_convert() {
@@ -989,7 +1009,7 @@ void DeviceBatch::plan_overlap_halves(UploadPlan &p) {
     while (huff_half_ < n_huff_work_ && h_scans_[p.huff_work[huff_half_].scan].image_index < half_image) huff_half_++;
     // worth it for batches that keep the machine busy for milliseconds: the halves cost four launches and two events
     if (wanted && !entropy_only_ && p.sub_work.empty() && p.prog_work.empty() && total_blocks_ >= (4u << 20) && huff_half_ > 0 &&
-        huff_half_ < n_huff_work_ && rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && fancy_convert_.empty() && luma_convert_.empty() && luma_work_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
+        huff_half_ < n_huff_work_ && rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && fancy_convert_.empty() && luma_convert_.empty() && luma_work_.empty() && islow_work_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
         idct_win_class_begin_[kNumIdctLayoutClasses] == idct_win_class_begin_[0]) {  // (no windowed image: the halves have no list for their work)
         for (int half = 0; half < 2; half++) {
             idct_half_begin_[half][0] = (int)p.idct_work_halves.size();
@@ -1072,6 +1092,7 @@ int DeviceBatch::upload_plan(const UploadPlan &p, const std::vector<const uint8_
         {&d_fancy_images_, fancy_images_.data(), fancy_images_.size() * sizeof(FancyImage), 0},
         {&d_luma_images_, luma_images_.data(), luma_images_.size() * sizeof(LumaImage), 0},
         {&d_luma_work_, luma_work_.data(), luma_work_.size() * sizeof(LumaWork), 0},
+        {&d_islow_work_, islow_work_.data(), islow_work_.size() * sizeof(IslowWork), 0},
         {&d_planes_, nullptr, 0, format_ == JPGPU_FMT_EXTENDED_U16 && !entropy_only_ ? (size_t)planes_bytes_ + 256 : 0},
         {&d_input_, nullptr, 0, (size_t)input_bytes_},
     };

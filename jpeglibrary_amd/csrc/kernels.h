@@ -229,6 +229,24 @@ struct LumaImage {
 };
 hipError_t launch_luma_plane(hipStream_t stream, const uint8_t *scratch, uint8_t *out, const LumaImage *images, int n_images, uint32_t max_tiles,
                              int format, const YccRgbFactors &kf, const OutputAffine &aff);
+// K3J (k3j_islow.hip): the images that take libjpeg's integer transform under JPGPU_ARITHMETIC_LIBJPEG (include/jpgpu.h, "Arithmetic";
+// k3j_islow.h has the block transform), from the dense coefficient store to the INTERLEAVED_U8 samples of the image's scratch slot, at
+// `scratch` + DevScan::out_off -- exactly where K3's generic class puts them, replication and clip to win_* included -- so that K3C, K3U,
+// K3O, K3Y's luma_plane_kernel and K4 run behind it unchanged.  A lane is one block of ANY component; a workgroup takes the blocks of up to
+// kIslowThreads / blocks_per_mcu consecutive MCUs of MCU row `row` of the window's MCU cover, from block `first` of that row (a multiple of
+// blocks_per_mcu: MCU first / bpm): contiguous in the store, and whole MCUs, so that the workgroup can lay its strip of pixels out in LDS and
+// store it row by row.  ONE launch for all listed scans, of whole frames and of windows (cov_* is the whole grid without one).
+// DeviceBatch::islow_taken says which images: no scan of theirs overlaps another or names a component twice, every replication is by 1, 2 or 4.
+constexpr uint32_t kIslowThreads = 256;
+JPGPU_HD constexpr uint32_t islow_blocks_per_wg(uint32_t blocks_per_mcu) { return kIslowThreads / blocks_per_mcu * blocks_per_mcu; }
+struct IslowWork {
+    uint32_t scan;
+    uint32_t row;    // MCU row of the cover
+    uint32_t first;  // first block of the workgroup in that row of cov_cols * blocks_per_mcu blocks
+    uint32_t pad;
+};
+hipError_t launch_islow(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IslowWork *work, int n_work, const DevScanStatus *status,
+                        const DevQuantTable *quant_pool, uint8_t *scratch);
 
 // Waves per workgroup of the POOLED form of the K2S final pass (k2s_subseq.hip: runs of scans that stage the same tables; one workgroup per CU, every wave takes the
 // next 64 lanes from a counter): 10 waves + 4 tables fill a CU's LDS.  Runs shorter than kSubFinalPoolMinChunks waves, and runs
