@@ -555,7 +555,7 @@ int jpgpu_batch_luma_work(const jpgpu_batch *b, int32_t counts[2]);
  * that takes the transform goes through the scratch image like a filtered one, and everything behind it reads its samples.
  *   State of the batch like the colour policy: every later upload of whole files reads it until it is set again.
  *   Not covered: jpgpu_decoder_*, jpgpu_decode_scan, jpgpu_progressive_*, jpgpu_multi_*, jpgpu_batch_upload_frames (the reference's arithmetic,
- * as before); libjpeg's other transforms (ifast, float, the scaled ones); 12-bit frames. */
+ * as before); libjpeg's other transforms (ifast, float; the scaled ones are "Scaled decode" below); 12-bit frames. */
 typedef enum jpgpu_arithmetic_policy {
     JPGPU_ARITHMETIC_REFERENCE = 0, /* the reference's float transform and constants, as before */
     JPGPU_ARITHMETIC_LIBJPEG = 1    /* jpeg_idct_islow and libjpeg's colour constants */
@@ -566,6 +566,51 @@ int jpgpu_batch_set_arithmetic_policy(jpgpu_batch *b, int policy);
  * that does not read it, an image outside the rule above, an image that failed at upload).  Valid after an upload; JPGPU_ERR_ARGUMENT for a
  * NULL argument or an index out of range. */
 int jpgpu_batch_image_arithmetic(const jpgpu_batch *b, int i, int *arithmetic);
+
+/* ---- Scaled decode: the picture at 1/2, 1/4 or 1/8 size with libjpeg's reduced transforms (an extension beyond the reference; libjpeg's
+ * scale_num / scale_denom, which Pillow reaches through Image.draft(), OpenCV through IMREAD_REDUCED_COLOR_2/4/8).  It is part of the
+ * arithmetic of libjpeg: an image takes a denominator above 1 exactly where it takes the integer transform above
+ * (jpgpu_batch_image_arithmetic says JPGPU_ARITHMETIC_LIBJPEG).  Everything else keeps full size and reports 1: the policy
+ * JPGPU_ARITHMETIC_REFERENCE, a format that does not read the arithmetic policy, 12-bit frames and the odd layouts of the rule above, and
+ * every entry the arithmetic policy does not cover.
+ *   Let m = 8 / denom: 4, 2 or 1.
+ *   OUTPUT SIZE.  W' = ceil(W * m / 8), H' = ceil(H * m / 8).
+ *   PER-COMPONENT TRANSFORM SIZE (jdmaster.c of library version 62).  A component with factors h, v under the frame's maxima hmax, vmax:
+ *       s = m;  while (s < 8 && (hmax * m) % (h * s * 2) == 0 && (vmax * m) % (v * s * 2) == 0) s *= 2;
+ *     Its block yields s x s samples; the replication left is rh = hmax * m / (h * s), rv = vmax * m / (v * s).  4:2:0 at 1/2, 1/4, 1/8:
+ *     luma 4, 2, 1 and chroma 8, 4, 2 with nothing left to replicate; 4:4:4 and grey: s = m; 4:2:2: s = m for all, rh = 2 stays for chroma.
+ *   BLOCK TRANSFORMS (jidctred.c).  d[r][c] = (int32)coef * (int32)q, CONST_BITS = 13, PASS1_BITS = 2, DESCALE(x, n) = (x + 2^(n-1)) >> n
+ *     arithmetic; every sum, product and left shift is 32-bit two's complement and wraps, as above; the sample is clamp(v + 128, 0, 255).
+ *     s = 8: jpeg_idct_islow, as above.
+ *     s = 4 (jpeg_idct_4x4): pass 1 over columns 0..3 and 5..7 (column 4 is never used) on rows 0, 1, 2, 3, 5, 6, 7:
+ *       t0 = d0 << 14     t2 = d2 * 15137 - d6 * 6270     t10 = t0 + t2     t12 = t0 - t2
+ *       a = -d7 * 1730 + d5 * 11893 - d3 * 17799 + d1 * 8697          b = -d7 * 4176 - d5 * 4926 + d3 * 7373 + d1 * 20995
+ *       out0..3 = DESCALE(t10 + b), DESCALE(t12 + a), DESCALE(t12 - a), DESCALE(t10 - b)      by 12 bits;
+ *       pass 2 the same on each of the 4 workspace rows over workspace columns 0, 1, 2, 3, 5, 6, 7, by 19 bits.
+ *     s = 2 (jpeg_idct_2x2): pass 1 over columns 0, 1, 3, 5, 7 on rows 0, 1, 3, 5, 7:
+ *       t10 = d0 << 15     t0 = -d7 * 5906 + d5 * 6967 - d3 * 10426 + d1 * 29692     out0, out1 = DESCALE(t10 + t0), DESCALE(t10 - t0)  by 13 bits;
+ *       pass 2 the same on each of the two workspace rows over workspace columns 0, 1, 3, 5, 7, by 20 bits.
+ *     s = 1: DESCALE(d[0][0], 3).
+ *     (libjpeg's shortcut for a column without AC terms gives the same values.)
+ *   ASSEMBLY.  The block at block position (bx, by) of its component's plane lands at (bx * s * rh, by * s * rv) of the reduced picture,
+ *     every sample repeated rh x rv times, the picture clipped to W' x H'.
+ *   UPSAMPLING.  The reduced picture is an ordinary picture whose chroma ratio is (rh, rv).  Under JPGPU_UPSAMPLE_FANCY the rule of "Chroma
+ *     upsampling" applies to it unchanged where (rh, rv) is (2,1), (2,2) or (1,2) and denom < 8 (libjpeg switches the filter off where the
+ *     smallest s is 1); the chroma extent is ceil(W' / rh), ceil(H' / rv).  Otherwise chroma is replicated.
+ *   Colour, orientation, grey output, the float samples and the resize stage run behind this on the reduced picture as they run behind the
+ *   integer transform.  WINDOWS are in pixels of the reduced (and, if turned, oriented) frame.  jpgpu_batch_image_info's width / height stay
+ *   the frame's; plane[], out_bytes and jpgpu_batch_image_window describe the reduced picture.
+ *   Equality with libjpeg is claimed under the condition stated above: dequantised and workspace values inside int16, pass sums inside int32.
+ *   State of the batch like the arithmetic policy: every later upload of whole files reads it until it is set again. */
+/* denom: 1 (the default), 2, 4 or 8; JPGPU_ERR_ARGUMENT for anything else. */
+int jpgpu_batch_set_scale_policy(jpgpu_batch *b, int denom);
+/* Pillow's draft() rule, per image: with k = min(w / min_w, h / min_h) in integer division over the image's ORIENTED frame w x h, the
+ * denominator is 8 if k >= 8, else 4 if k >= 4, else 2 if k >= 2, else 1 -- the smallest picture that is still at least min_w x min_h.
+ * While set it overrides the scale policy; (0, 0) switches it off.  JPGPU_ERR_ARGUMENT where only one of the two is 0. */
+int jpgpu_batch_set_scale_fit(jpgpu_batch *b, uint32_t min_w, uint32_t min_h);
+/* The denominator image i was planned with: 1, 2, 4 or 8 (1 for an image that failed at upload).  Valid after an upload;
+ * JPGPU_ERR_ARGUMENT for a NULL argument or an index out of range. */
+int jpgpu_batch_image_scale(const jpgpu_batch *b, int i, int *denom);
 
 /* Coefficient hand-off for multi-scan (progressive, SOF2) images -- BASELINE config 5's "coefficient accumulate then single
  * IDCT pass": the caller's progressive entropy decoder accumulates the coefficient store, the GPU runs what

@@ -140,6 +140,8 @@ UPSAMPLING_POLICIES = ("replicate", "fancy")
 CHANNELS_POLICIES = ("rgb", "gray")
 # jpgpu_arithmetic_policy, by its Python names
 ARITHMETIC_POLICIES = ("reference", "libjpeg")
+# the denominators of jpgpu_batch_set_scale_policy
+SCALE_DENOMINATORS = (1, 2, 4, 8)
 
 UPLOAD_PINNED = 1
 UPLOAD_PINNED_ARENA = 2
@@ -208,6 +210,9 @@ SYMBOLS = [
     ("jpgpu_batch_luma_work", C.c_int, [_P, C.POINTER(C.c_int32)]),
     ("jpgpu_batch_set_arithmetic_policy", C.c_int, [_P, C.c_int]),
     ("jpgpu_batch_image_arithmetic", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("jpgpu_batch_set_scale_policy", C.c_int, [_P, C.c_int]),
+    ("jpgpu_batch_set_scale_fit", C.c_int, [_P, C.c_uint32, C.c_uint32]),
+    ("jpgpu_batch_image_scale", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("jpgpu_sizeof_device_ingest_stats", C.c_size_t, []),
     ("jpgpu_batch_device_ingest_stats", C.c_int, [_P, C.POINTER(DeviceIngestStats)]),
     ("jpgpu_batch_upload_frames", C.c_int, [_P, C.POINTER(Frame), C.c_void_p, C.c_int, C.c_int]),

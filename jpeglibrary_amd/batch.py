@@ -176,6 +176,19 @@ def _arithmetic_policy(arithmetic, who="arithmetic"):
     return _capi.ARITHMETIC_POLICIES.index(arithmetic)
 
 
+def _scale_setting(scale, arithmetic="libjpeg", fit=False, windows=None, who="scale"):
+    """The check of Batch.set_scale_policy / decode_to_tensors(scale=...) / decode_resized(scale=...), before any library call: 1, 2, 4 or 8,
+    or "fit" where fit is allowed; anything but 1 needs arithmetic="libjpeg" (the reduced transforms are libjpeg's), and "fit" takes no windows."""
+    is_fit = fit and isinstance(scale, str) and scale == "fit"
+    if not is_fit and (isinstance(scale, bool) or not isinstance(scale, int) or scale not in _capi.SCALE_DENOMINATORS):
+        raise ValueError('%s is 1, 2, 4 or 8%s, not %r' % (who, ' or "fit"' if fit else "", scale))
+    if scale != 1 and arithmetic != "libjpeg":
+        raise ValueError('%s=%r needs arithmetic="libjpeg": the reduced transforms are libjpeg\'s, the reference has none' % (who, scale))
+    if is_fit and windows is not None:
+        raise ValueError('%s="fit" takes no windows: each image picks its own scale, and a window is in pixels of the reduced frame' % who)
+    return scale
+
+
 def _channels_policy(mode, fmt=None, who="mode"):
     """The check of Batch.set_channels_policy / decode_batch(mode=...), before any library call: "rgb" or "gray" -> the jpgpu_channels_policy
     value.  fmt: the format "gray" is asked for with; only RGB_PLANAR_U8 / _F16 / _F32 have a one-plane form."""
@@ -408,6 +421,37 @@ class Batch:
         a = C.c_int()
         raise_for_status(_lib.jpgpu_batch_image_arithmetic(self._h, i, C.byref(a)), b"jpgpu_batch_image_arithmetic: no such image")
         return a.value
+
+    def set_scale_policy(self, denom):
+        """The size the RGB formats decode at from the next upload on: 1, the default, or 2, 4, 8 -- the picture at 1/2, 1/4, 1/8 size through
+        libjpeg's reduced transforms (include/jpgpu.h, "Scaled decode"), ceil(W / denom) x ceil(H / denom) pixels, bit for bit Pillow's
+        draft() decode.  Only images that take libjpeg's transform (set_arithmetic_policy("libjpeg"); arithmetic(i) == 1) take it; every other
+        image keeps full size, and scale(i) says which.  Windows are then in pixels of the reduced frame.  State of the batch: it holds until
+        set again.  ValueError, before the library is called, for any other value."""
+        self._check(_lib.jpgpu_batch_set_scale_policy(self._h, _scale_setting(denom, who="denom")))
+        return self
+
+    def set_scale_fit(self, size):
+        """Pillow's draft() rule from the next upload on: size = (h, w), the least size wanted -- every image takes the largest of 1/8, 1/4,
+        1/2 that leaves its oriented frame at least that large, or full size (k = min(W // w, H // h): 8 if k >= 8, else 4, else 2, else 1).
+        While set it overrides set_scale_policy; None switches it off.  ValueError, before the library is called, for anything else."""
+        if size is None:
+            h = w = 0
+        else:
+            try:
+                h, w = size
+            except (TypeError, ValueError):
+                raise ValueError("set_scale_fit: size is (h, w) or None, not %r" % (size,))
+            if any(isinstance(v, bool) or not isinstance(v, int) or v < 1 or v > 0xFFFFFFFF for v in (h, w)):
+                raise ValueError("set_scale_fit: size is two positive integers (h, w), not %r" % (size,))
+        self._check(_lib.jpgpu_batch_set_scale_fit(self._h, w, h))
+        return self
+
+    def scale(self, i):
+        """The denominator image i was planned with: 1, 2, 4 or 8"""
+        d = C.c_int()
+        raise_for_status(_lib.jpgpu_batch_image_scale(self._h, i, C.byref(d)), b"jpgpu_batch_image_scale: no such image")
+        return d.value
 
     def set_channels_policy(self, mode):
         """How many planes RGB_PLANAR_U8 / _F16 / _F32 deliver from the next upload on: "rgb", the default -- three, as ever -- or "gray": ONE
@@ -756,7 +800,7 @@ def decode_batch(files, fmt=FMT_INTERLEAVED_U8, ctx=None, windows=None, color="y
     return outs, results
 
 
-def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb", arithmetic="reference"):
+def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=None, ctx=None, windows=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb", arithmetic="reference", scale=1):
     """One-call helper for torch consumers: returns (tensors, results), tensors[i] = Batch.output_tensor(i) -- uint8[3, H, W] on the
     context's device by default -- or None for an image that failed.  Nothing is downloaded.  The batch is not closed: its output
     buffer is the tensors' memory and is freed with the last of them.  files: bytes-like objects, or 1-D uint8 torch tensors on the
@@ -778,13 +822,17 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     not RGB_PLANAR_*.
     arithmetic: "reference" or "libjpeg" (Batch.set_arithmetic_policy): under "libjpeg" the samples come from libjpeg's integer transform
     (jpeg_idct_islow) and its colour constants; with upsampling="fancy" tensors[i] holds exactly the pixels Pillow and torchvision decode.
-    Everything else composes on it."""
+    Everything else composes on it.
+    scale: 1, 2, 4 or 8 (Batch.set_scale_policy): with arithmetic="libjpeg", tensors[i] is the picture at 1 / scale size, [3, ceil(H / scale),
+    ceil(W / scale)], through libjpeg's reduced transforms -- Pillow's draft() decode; windows are in pixels of that picture.  ValueError for
+    another value, or for a scale other than 1 without arithmetic="libjpeg"."""
     files = list(files)
     windows = _window_rects(windows, len(files))
     _color_policy(color)
     _orientation_policy(orientation)
     _upsampling_policy(upsampling)
     _arithmetic_policy(arithmetic)
+    _scale_setting(scale, arithmetic)
     orientations = _orientation_list(orientations, len(files))
     if dtype is not None:
         import torch
@@ -808,6 +856,7 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     b.set_orientation_policy(orientation)
     b.set_upsampling_policy(upsampling)
     b.set_arithmetic_policy(arithmetic)
+    b.set_scale_policy(scale)
     b.set_channels_policy(mode)
     if orientations is not None:
         b.set_orientations(orientations)
@@ -823,7 +872,7 @@ def decode_to_tensors(files, fmt=FMT_RGB_PLANAR_U8, dtype=None, mean=None, std=N
     return tensors, results
 
 
-def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb", arithmetic="reference"):
+def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, ctx=None, color="ycc", orientation="stored", orientations=None, upsampling="replicate", mode="rgb", arithmetic="reference", scale=1):
     """One-call helper for fixed-size consumers: returns (tensor, results), tensor = Batch.resized_tensor() -- ONE [N, 3, oh, ow] tensor on the
     context's device, size = (oh, ow), dtype torch.float16 (the default), torch.float32 or torch.uint8 -- every image decoded to RGB and
     resampled to that size (antialiased bilinear) in one launch behind the output stage; the slab of an image that failed is zero and
@@ -835,7 +884,10 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
     decode_to_tensors: the oriented image is what is resampled.  upsampling: "replicate" or "fancy" (Batch.set_upsampling_policy): under "fancy"
     the image that is resampled has libjpeg's filtered chroma.  mode: "rgb" or "gray" (Batch.set_channels_policy): under "gray" the tensor is
     [N, 1, oh, ow], the grey plane of decode_to_tensors(mode="gray") resampled by the same function; mean and std are a number or a sequence of one.
-    arithmetic: "reference" or "libjpeg" (Batch.set_arithmetic_policy): under "libjpeg" the image that is resampled is libjpeg's decode."""
+    arithmetic: "reference" or "libjpeg" (Batch.set_arithmetic_policy): under "libjpeg" the image that is resampled is libjpeg's decode.
+    scale: 1, 2, 4, 8 (Batch.set_scale_policy) or "fit" (Batch.set_scale_fit(size)): with arithmetic="libjpeg" the image that is resampled is
+    decoded at 1 / scale size first -- under "fit" at the smallest of 1/1 .. 1/8, per image, that is still at least `size`, Pillow's draft()
+    rule --, so a large file costs the output stage and the resize a fraction of its pixels.  "fit" together with windows is a ValueError."""
     import torch
 
     files = list(files)
@@ -844,6 +896,7 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
     _orientation_policy(orientation)
     _upsampling_policy(upsampling)
     _arithmetic_policy(arithmetic)
+    _scale_setting(scale, arithmetic, fit=True, windows=windows, who="decode_resized: scale")
     orientations = _orientation_list(orientations, len(files))
     dtype = torch.float16 if dtype is None else dtype
     _resize_setting(size, dtype)
@@ -861,6 +914,10 @@ def decode_resized(files, size, dtype=None, mean=None, std=None, windows=None, c
     b.set_orientation_policy(orientation)
     b.set_upsampling_policy(upsampling)
     b.set_arithmetic_policy(arithmetic)
+    if scale == "fit":
+        b.set_scale_fit(tuple(size))
+    else:
+        b.set_scale_policy(scale)
     b.set_channels_policy(mode)
     if orientations is not None:
         b.set_orientations(orientations)

@@ -437,6 +437,9 @@ int jpgpu_batch_image_channels(const jpgpu_batch *b, int i, int *channels) { ret
 int jpgpu_batch_luma_work(const jpgpu_batch *b, int32_t counts[2]) { return b ? b->impl.luma_work(counts) : JPGPU_ERR_ARGUMENT; }
 int jpgpu_batch_set_arithmetic_policy(jpgpu_batch *b, int policy) { JPGPU_GUARD(b, b->impl.set_arithmetic_policy(policy)); }
 int jpgpu_batch_image_arithmetic(const jpgpu_batch *b, int i, int *arithmetic) { return b ? b->impl.image_arithmetic(i, arithmetic) : JPGPU_ERR_ARGUMENT; }
+int jpgpu_batch_set_scale_policy(jpgpu_batch *b, int denom) { JPGPU_GUARD(b, b->impl.set_scale_policy(denom)); }
+int jpgpu_batch_set_scale_fit(jpgpu_batch *b, uint32_t min_w, uint32_t min_h) { JPGPU_GUARD(b, b->impl.set_scale_fit(min_w, min_h)); }
+int jpgpu_batch_image_scale(const jpgpu_batch *b, int i, int *denom) { return b ? b->impl.image_scale(i, denom) : JPGPU_ERR_ARGUMENT; }
 // Host only: Identify's walk up to the first SOS, which records the first Exif APP1 on its way (ingest_host.h: exif_orientation_of).
 int jpgpu_identify_orientation(const uint8_t *file, size_t len, int *orientation) {
     if (!file || !orientation) return JPGPU_ERR_ARGUMENT;

@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "k3r_reduced.h"
 
 namespace jpgpu {
 
@@ -43,7 +44,7 @@ void DevBuffer::release() {
 
 DeviceBatch::~DeviceBatch() {
     if (ctx_) (void)hipSetDevice(ctx_->device);
-    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_color_images_, &d_orient_images_, &d_fancy_images_, &d_luma_images_, &d_luma_work_, &d_islow_work_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
+    for (DevBuffer *b : {&d_sub_work_, &d_sub_final_work_, &d_sub_scan_ids_, &d_sub_exit_a_, &d_sub_exit_b_, &d_sub_nblk_, &d_sub_first_, &d_sub_entry_, &d_sub_dcsum_, &d_sub_dcentry_, &d_sub_changed_, &d_sub_same_, &d_sub_perm_, &d_k1_desc_, &d_k1_tickets_, &d_k2_tickets_, &d_sr_luts_, &d_sr_set_scan_, &d_k1_order_, &d_prog_snapshot_, &d_dense_, &d_split_ids_, &d_dispose_, &d_verify_, &d_lut_pool_, &d_prog_work_, &d_prog_sync_, &d_planes_, &d_extend_desc_, &d_gather_, &d_heads_, &d_rgb_scratch_, &d_color_images_, &d_orient_images_, &d_fancy_images_, &d_luma_images_, &d_luma_work_, &d_islow_work_, &d_reduced_work_, &d_chunk_work_, &d_chunk_sums_, &d_unstuffed_, &d_ends_u_, &d_input_, &d_scans_, &d_status_, &d_ends_, &d_huff_pool_, &d_quant_pool_, &d_huff_work_, &d_idct_work_, &d_idct_work_halves_, &d_coefs_, &d_out_, &d_resized_, &d_resize_images_, &d_resize_tables_})
         b->release();
     for (hipEvent_t &e : ev_pool_)
         if (e) (void)hipEventDestroy(e);
@@ -67,12 +68,12 @@ int DeviceBatch::hip_fail(hipError_t e, const char *what) {
 
 bool DeviceBatch::fancy_filtered(int policy, int format, const ImagePlan &img) {
     return policy == JPGPU_UPSAMPLE_FANCY && img.luma == kLumaNone && fmt_is_rgb(format) && img.color_kind == kColorYcbcr && img.num_components == 3 && img.precision == 8 &&
-           k3u_ratio_filtered(img.chroma_hs, img.chroma_vs, img.width);
+           k3u_ratio_filtered(img.chroma_hs, img.chroma_vs, img.pic_w) && img.scale < 8;  // (libjpeg: no filter where a block yields one sample)
 }
 
 jpgpu_rect DeviceBatch::fancy_fetch_rect(const ImagePlan &img) {
-    const K3uSpan x = k3u_fetch_span(img.win.x, img.win.x + img.win.width, img.width, img.chroma_hs);
-    const K3uSpan y = k3u_fetch_span(img.win.y, img.win.y + img.win.height, img.height, img.chroma_vs);
+    const K3uSpan x = k3u_fetch_span(img.win.x, img.win.x + img.win.width, img.pic_w, img.chroma_hs);
+    const K3uSpan y = k3u_fetch_span(img.win.y, img.win.y + img.win.height, img.pic_h, img.chroma_vs);
     return jpgpu_rect{x.lo, y.lo, x.hi - x.lo, y.hi - y.lo};
 }
 
@@ -227,6 +228,51 @@ bool DeviceBatch::islow_taken(int policy, int format, const ImagePlan &img, cons
     return true;
 }
 
+int DeviceBatch::set_scale_policy(int denom) {
+    if (denom != 1 && denom != 2 && denom != 4 && denom != 8) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_set_scale_policy: the denominator is 1, 2, 4 or 8");
+    scale_policy_ = denom;
+    return JPGPU_OK;
+}
+
+int DeviceBatch::set_scale_fit(uint32_t min_w, uint32_t min_h) {
+    if ((min_w == 0) != (min_h == 0)) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_set_scale_fit: a least size has two positive sides; (0, 0) switches the rule off");
+    scale_fit_w_ = min_w;
+    scale_fit_h_ = min_h;
+    return JPGPU_OK;
+}
+
+int DeviceBatch::image_scale(int i, int *denom) const {
+    const ImagePlan *img = image(i);
+    if (!img || !denom) return JPGPU_ERR_ARGUMENT;
+    *denom = img->status == JPGPU_OK ? img->scale : 1;
+    return JPGPU_OK;
+}
+
+// Pillow's draft(): the largest of 8, 4, 2 that leaves the oriented frame at least the least size in both directions
+int DeviceBatch::scale_wanted(const ImagePlan &img, int orientation) const {
+    if (scale_fit_w_ == 0) return scale_policy_;
+    const uint32_t ow = orientation_transposes(orientation) ? img.height : img.width, oh = orientation_transposes(orientation) ? img.width : img.height;
+    const uint32_t k = std::min(ow / scale_fit_w_, oh / scale_fit_h_);
+    return k >= 8 ? 8 : (k >= 4 ? 4 : (k >= 2 ? 2 : 1));
+}
+
+// The plan of an image that takes libjpeg's transform, at 1 / denom: the reduced picture's size, and of a three-component image whose
+// chroma ratio the frame states (plan_image_geometry) the ratio jdmaster's per-component transform sizes leave in it (k3r_reduced.h).
+// The whole picture is its window; apply_window sizes the output by it.
+void DeviceBatch::plan_reduced_geometry(ImagePlan &img, const BaselineGeometry &geo, int denom) {
+    const uint32_t m = 8u / (uint32_t)denom;
+    img.scale = (uint8_t)denom;
+    img.pic_w = (uint16_t)(((uint32_t)img.width * m + 7u) / 8u);
+    img.pic_h = (uint16_t)(((uint32_t)img.height * m + 7u) / 8u);
+    if (img.chroma_hs != 0 && img.chroma_vs != 0) {
+        const FrameComponent &c1 = geo.frame.components[1];
+        const uint32_t bs = reduced_block_size(m, c1.h, c1.v, (uint32_t)geo.max_h, (uint32_t)geo.max_v);
+        img.chroma_hs = (uint8_t)reduced_replication(m, bs, c1.h, (uint32_t)geo.max_h);
+        img.chroma_vs = (uint8_t)reduced_replication(m, bs, c1.v, (uint32_t)geo.max_v);
+    }
+    img.win = img.win_oriented = jpgpu_rect{0, 0, img.pic_w, img.pic_h};
+}
+
 int DeviceBatch::upsampling_ms(float *ms) {
     if (!ms) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_batch_upsampling_ms: null argument");
     if (!fancy_timed_) return fail(JPGPU_ERR_INVALID_OPERATION, "jpgpu_batch_upsampling_ms: no K3U call of this upload was timed (JPGPU_TIME_UPSAMPLE=1 at the upload, a filtered image, a decode)");
@@ -254,6 +300,9 @@ void DeviceBatch::plan_image_geometry(ImagePlan &img, const BaselineGeometry &ge
     img.fancy = false;
     img.luma = kLumaNone;
     img.islow = false;
+    img.scale = 1;
+    img.pic_w = img.width;
+    img.pic_h = img.height;
     if (fh.num_components == 3 && fh.components.size() == 3) {
         const auto &c0 = fh.components[0], &c1 = fh.components[1], &c2 = fh.components[2];
         if (c0.h == geo.max_h && c0.v == geo.max_v && c1.h == c2.h && c1.v == c2.v && c1.h > 0 && c1.v > 0 && geo.max_h % c1.h == 0 && geo.max_v % c1.v == 0) {

@@ -131,6 +131,13 @@ struct ImagePlan {
     // arithmetic (include/jpgpu.h, "Arithmetic"): the image takes libjpeg's integer transform (DeviceBatch::islow_taken holds): planned like a
     // filtered image -- scratch road, dense hand-off --, its scans in K3J's work list and in none of K3's; never on K3Y's fast road
     bool islow = false;
+    // scaled decode (include/jpgpu.h, "Scaled decode"): the denominator the image was planned with -- 1, or 2, 4, 8 for an image that takes
+    // libjpeg's transform under a scale policy or the fit rule (apply_window) -- and the picture the output stage works on: the frame itself at
+    // scale 1, else the reduced picture of ceil(width * m / 8) x ceil(height * m / 8) pixels, m = 8 / scale.  win, win_oriented, out_bytes and
+    // plane[] are in pixels of that picture, chroma_hs / chroma_vs the ratio that is LEFT in it (jdmaster's per-component sizes), and the
+    // image's scans are in K3R's work list in place of K3J's.  width / height stay the frame's.
+    uint8_t scale = 1;
+    uint16_t pic_w = 0, pic_h = 0;
 };
 
 class WorkCrew;
@@ -185,6 +192,11 @@ class DeviceBatch {
     // files under an RGB format.
     int set_arithmetic_policy(int policy);
     int image_arithmetic(int i, int *arithmetic) const;
+    // Scaled decode (jpgpu_batch_set_scale_policy / _set_scale_fit / _image_scale): state of the batch like the arithmetic policy.  An image
+    // takes a denominator above 1 exactly where it takes libjpeg's transform (islow_taken).
+    int set_scale_policy(int denom);
+    int set_scale_fit(uint32_t min_w, uint32_t min_h);
+    int image_scale(int i, int *denom) const;
     uint64_t idct_listed_mcus() const { return idct_listed_mcus_; }
     // One progressive frame collected by the JpegDecoder mirror: its entropy scans + the Dispose() pass.
     int upload_progressive_frame(const ProgressiveFrame &frame, const uint8_t *file, size_t file_len, int sof, int format);
@@ -312,6 +324,10 @@ class DeviceBatch {
     // no overlapping blocks, no literal Dispose(); no caller's canvas.  include/jpgpu.h states the rule.
     static bool islow_taken(int policy, int format, const ImagePlan &img, const std::vector<ScanJob> &jobs, bool keep_canvas);
     void plan_islow_work(size_t ii, int j);
+    // The denominator an image that takes libjpeg's transform is decoded with: the fit rule over its oriented frame where one is set, else
+    // the policy.  plan_reduced_geometry then turns the image's plan into the reduced picture's (pic_w / pic_h, the residual chroma ratio).
+    int scale_wanted(const ImagePlan &img, int orientation) const;
+    static void plan_reduced_geometry(ImagePlan &img, const BaselineGeometry &geo, int denom);
     void plan_luma_convert();
     // ingest (jpgpu_batch_upload*), see device_batch_ingest.cpp
     void plan_file_headers(const uint8_t *file, size_t len, FilePlan &fp) const;
@@ -544,6 +560,11 @@ class DeviceBatch {
     // behind K3's (plan_islow_work); the images themselves are in the conversion lists like every image of the scratch road
     std::vector<IslowWork> islow_work_;
     DevBuffer d_islow_work_;
+    // ... and those of the images decoded at a reduced size: K3R's work list, one launch behind K3J's
+    std::vector<ReducedWork> reduced_work_;
+    DevBuffer d_reduced_work_;
+    int scale_policy_ = 1;
+    uint32_t scale_fit_w_ = 0, scale_fit_h_ = 0;  // the fit rule's least size (0, 0: off)
     int arithmetic_policy_ = JPGPU_ARITHMETIC_REFERENCE;
     bool islow_upload_ = false;  // the last upload of whole files was made under JPGPU_ARITHMETIC_LIBJPEG and an RGB format: libjpeg's colour constants
     YccRgbFactors color_factors() const;  // of this upload's YCbCr -> RGB steps: the reference's, or libjpeg's (islow_upload_)

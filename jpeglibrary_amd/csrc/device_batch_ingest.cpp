@@ -444,8 +444,10 @@ void DeviceBatch::apply_window(size_t i, const std::vector<ScanJob> &jobs) {
     // (an image that takes libjpeg's transform is never on K3Y's fast road, which runs K3's: its grey plane comes from the scratch slot K3J fills)
     img.islow = islow_taken(arithmetic_policy_, format_, img, jobs, keep_canvas_ || entropy_only_);
     img.luma = !one_plane ? kLumaNone : (!img.islow && luma_fast(img, jobs, keep_canvas_) ? kLumaFast : kLumaScratch);
+    // (... and it alone is decoded at a reduced size: from here on the picture is the reduced one, include/jpgpu.h "Scaled decode")
+    if (const int denom = img.islow ? scale_wanted(img, o) : 1; denom > 1) plan_reduced_geometry(img, jobs.front().geo, denom);
     img.fancy = fancy_filtered(upsample_policy_, format_, img);  // (the window only decides which of its pixels come out; never a grey image)
-    const uint32_t ow = orientation_transposes(o) ? img.height : img.width, oh = orientation_transposes(o) ? img.width : img.height;  // the oriented frame
+    const uint32_t ow = orientation_transposes(o) ? img.pic_h : img.pic_w, oh = orientation_transposes(o) ? img.pic_w : img.pic_h;  // the oriented frame
     jpgpu_rect w = windows_.empty() ? jpgpu_rect{0, 0, 0, 0} : windows_[i];
     bool whole = w.x == 0 && w.y == 0 && w.width == 0 && w.height == 0;
     if (!whole) {
@@ -463,10 +465,10 @@ void DeviceBatch::apply_window(size_t i, const std::vector<ScanJob> &jobs) {
     }
     if (whole) w = jpgpu_rect{0, 0, ow, oh};
     img.win_oriented = w;
-    if (whole && o == 1 && !one_plane) return;
+    if (whole && o == 1 && !one_plane && img.scale == 1) return;
     if (!whole) {
         img.windowed = true;
-        img.win = orientation_stored_rect(o, w, img.width, img.height);  // what K3 decodes
+        img.win = orientation_stored_rect(o, w, img.pic_w, img.pic_h);  // what K3 decodes
     }
     const uint64_t pixels = (uint64_t)w.width * w.height;
     if (fmt_is_sample_bytes(format_)) {

@@ -279,6 +279,10 @@ int DeviceBatch::run_idct(bool with_resize) {
     e = launch_islow(ctx_->stream, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const IslowWork *)d_islow_work_.ptr, (int)islow_work_.size(),
                      (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr, (uint8_t *)d_rgb_scratch_.ptr);
     if (e != hipSuccess) return hip_fail(e, "islow_kernel");
+    // ... and those of them that are decoded at a reduced size: libjpeg's reduced transforms, the reduced picture into the scratch image
+    e = launch_reduced(ctx_->stream, (const int16_t *)d_coefs_.ptr, (const DevScan *)d_scans_.ptr, (const ReducedWork *)d_reduced_work_.ptr, (int)reduced_work_.size(),
+                       (const DevScanStatus *)d_status_.ptr, (const DevQuantTable *)d_quant_pool_.ptr, (uint8_t *)d_rgb_scratch_.ptr);
+    if (e != hipSuccess) return hip_fail(e, "reduced_kernel");
     // scans ordered behind earlier scans of their image (and the failing MCU of a caller's canvas): one bytewise launch per level
     for (size_t lv = 0; lv + 1 < idct_later_begin_.size(); lv++) {
         int cb[kNumIdctLayoutClasses + 1];

@@ -198,6 +198,7 @@ void DeviceBatch::reset_upload_state(const UploadPlan &p) {
     luma_convert_.clear();
     luma_work_.clear();
     islow_work_.clear();
+    reduced_work_.clear();
     n_luma_fast_ = 0;
     luma_work_windowed_ = false;
     fancy_timed_ = false;
@@ -407,15 +408,18 @@ void DeviceBatch::fill_scan(UploadPlan &p, size_t ii, int j, size_t file_len) {
     const jpgpu_rect win = img.fancy ? fancy_fetch_rect(img) : img.win;
     s.win_x = (uint16_t)win.x;
     s.win_y = (uint16_t)win.y;
-    s.win_w = img.windowed ? (uint16_t)win.width : s.width;
-    s.win_h = img.windowed ? (uint16_t)win.height : s.height;
+    // (an image decoded at a reduced size, include/jpgpu.h "Scaled decode": its window -- the whole reduced picture without one -- and its
+    // cover are in pixels and MCUs of that picture, whose MCU is max_h * 8 / scale x max_v * 8 / scale pixels; only K3R reads them)
+    const bool reduced = img.scale > 1;
+    s.win_w = img.windowed || reduced ? (uint16_t)win.width : s.width;
+    s.win_h = img.windowed || reduced ? (uint16_t)win.height : s.height;
     s.cov_cols = (uint16_t)s.mcus_per_line;
     s.cov_rows = (uint16_t)s.mcus_per_column;
     bool mcu_boxes = job.kind != kScanProgressive && g.max_h > 0 && g.max_v > 0 && (job.scan_components > 1 || g.frame.num_components == 1);
     if (job.kind == kScanFrameOnly)
         for (int c = 0; c < job.scan_components; c++) mcu_boxes &= job.comp[c].h * job.comp[c].hs == g.max_h && job.comp[c].v * job.comp[c].vs == g.max_v;
     if (img.windowed && mcu_boxes && win.width != 0 && win.height != 0) {
-        const uint32_t mw = 8u * (uint32_t)g.max_h, mh = 8u * (uint32_t)g.max_v;
+        const uint32_t mw = 8u / img.scale * (uint32_t)g.max_h, mh = 8u / img.scale * (uint32_t)g.max_v;
         const uint32_t c0 = win.x / mw, c1 = (win.x + win.width + mw - 1) / mw, r0 = win.y / mh, r1 = (win.y + win.height + mh - 1) / mh;
         if (c1 <= s.mcus_per_line && r1 <= s.mcus_per_column) {
             s.cov_x = (uint16_t)c0;
@@ -584,7 +588,14 @@ void DeviceBatch::plan_idct_work(UploadPlan &p, size_t ii, int j, bool overlappi
     if (img.islow && (s.reserved0 & kScanStoreHoldsSamples) == 0) {
         list_rgb_convert(ii);
         p.scan_level[(size_t)j] = 0;
-        plan_islow_work(ii, j);
+        plan_islow_work(ii, j);  // (K3J's list at full size, K3R's at a reduced one)
+        return;
+    }
+    // (... decoded at a reduced size: no K3 form writes a reduced picture, and its slot is too small for the frame.  The second issue of such a
+    // file lists no transform: the slot keeps what K3R left in it at the first issue, and the conversion runs on that.)
+    if (img.scale > 1) {
+        list_rgb_convert(ii);
+        p.scan_level[(size_t)j] = 0;
         return;
     }
     const uint32_t generic_per_wg = (uint32_t)kIdctBlocksPerWg / s.blocks_per_mcu;
@@ -950,7 +961,7 @@ void DeviceBatch::plan_fancy_convert() {
         g.fetch_x = f.x, g.fetch_y = f.y, g.fetch_w = f.width;
         g.win_x = img.win.x, g.win_y = img.win.y, g.win_w = img.win.width, g.win_h = img.win.height;
         g.hs = img.chroma_hs, g.vs = img.chroma_vs;
-        g.cw = k3u_chroma_extent(img.width, g.hs), g.ch = k3u_chroma_extent(img.height, g.vs);
+        g.cw = k3u_chroma_extent(img.pic_w, g.hs), g.ch = k3u_chroma_extent(img.pic_h, g.vs);
         g.staged = staged ? 1u : 0u;
         n_fancy_staged_ += staged ? 1 : 0;
         fancy_images_.push_back(g);
@@ -973,12 +984,16 @@ void DeviceBatch::plan_luma_work(size_t ii, int j) {
 }
 
 // K3J's work for one scan of an image that takes libjpeg's transform: every block of the window's MCU cover, MCU row by MCU row, the blocks
-// of kIslowThreads / blocks_per_mcu consecutive MCUs of a row per workgroup.
+// of kIslowThreads / blocks_per_mcu consecutive MCUs of a row per workgroup.  An image decoded at a reduced size: the same division in K3R's
+// list, each entry with m = 8 / scale.
 void DeviceBatch::plan_islow_work(size_t ii, int j) {
     const DevScan &s = h_scans_[j];
     const uint32_t row_blocks = (uint32_t)s.cov_cols * s.blocks_per_mcu, step = islow_blocks_per_wg(s.blocks_per_mcu);
     for (uint32_t row = 0; row < s.cov_rows; row++)
-        for (uint32_t first = 0; first < row_blocks; first += step) islow_work_.push_back({(uint32_t)j, row, first, 0u});
+        for (uint32_t first = 0; first < row_blocks; first += step) {
+            if (images_[ii].scale > 1) reduced_work_.push_back({(uint32_t)j, row, first, 8u / images_[ii].scale});
+            else islow_work_.push_back({(uint32_t)j, row, first, 0u});
+        }
 }
 
 // The descriptors of K3Y's scratch-road launch: one per grey image that is not on the fast road, with the stored window K3 leaves in the
@@ -1009,7 +1024,7 @@ void DeviceBatch::plan_overlap_halves(UploadPlan &p) {
     while (huff_half_ < n_huff_work_ && h_scans_[p.huff_work[huff_half_].scan].image_index < half_image) huff_half_++;
     // worth it for batches that keep the machine busy for milliseconds: the halves cost four launches and two events
     if (wanted && !entropy_only_ && p.sub_work.empty() && p.prog_work.empty() && total_blocks_ >= (4u << 20) && huff_half_ > 0 &&
-        huff_half_ < n_huff_work_ && rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && fancy_convert_.empty() && luma_convert_.empty() && luma_work_.empty() && islow_work_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
+        huff_half_ < n_huff_work_ && rgb_convert_.empty() && color_convert_.empty() && orient_convert_.empty() && fancy_convert_.empty() && luma_convert_.empty() && luma_work_.empty() && islow_work_.empty() && reduced_work_.empty() && format_ != JPGPU_FMT_EXTENDED_U16 && idct_later_begin_.size() == 1 &&
         idct_win_class_begin_[kNumIdctLayoutClasses] == idct_win_class_begin_[0]) {  // (no windowed image: the halves have no list for their work)
         for (int half = 0; half < 2; half++) {
             idct_half_begin_[half][0] = (int)p.idct_work_halves.size();
@@ -1093,6 +1108,7 @@ int DeviceBatch::upload_plan(const UploadPlan &p, const std::vector<const uint8_
         {&d_luma_images_, luma_images_.data(), luma_images_.size() * sizeof(LumaImage), 0},
         {&d_luma_work_, luma_work_.data(), luma_work_.size() * sizeof(LumaWork), 0},
         {&d_islow_work_, islow_work_.data(), islow_work_.size() * sizeof(IslowWork), 0},
+        {&d_reduced_work_, reduced_work_.data(), reduced_work_.size() * sizeof(ReducedWork), 0},
         {&d_planes_, nullptr, 0, format_ == JPGPU_FMT_EXTENDED_U16 && !entropy_only_ ? (size_t)planes_bytes_ + 256 : 0},
         {&d_input_, nullptr, 0, (size_t)input_bytes_},
     };

@@ -256,6 +256,7 @@ int DeviceBatch::redo_swallowed(int i, int job, jpgpu_image_result *res) {
             (void)sub.set_upsampling_policy(upsample_policy_);
             (void)sub.set_channels_policy(channels_policy_);  // (the image decides on its road again, from its new plan)
             (void)sub.set_arithmetic_policy(arithmetic_policy_);  // (... and on its transform)
+            (void)sub.set_scale_policy(img.scale);  // (... at the size it was planned with, whatever decided it)
             if (img.orientation != 1) (void)sub.set_orientations(&img.orientation, 1);  // (as it was planned, whatever decided it)
             if (img.windowed) sub.set_windows(&img.win_oriented, 1);  // (the same window: its output replaces the image's)
             const uint8_t *fptr = file.data();

@@ -247,6 +247,19 @@ struct IslowWork {
 };
 hipError_t launch_islow(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const IslowWork *work, int n_work, const DevScanStatus *status,
                         const DevQuantTable *quant_pool, uint8_t *scratch);
+// K3R (k3r_reduced.hip): the images of K3J's kind that are decoded at 1/2, 1/4 or 1/8 size (include/jpgpu.h, "Scaled decode"; k3r_reduced.h
+// has the block transforms and the per-component rule).  K3J's work division and scratch slot; `m` = 8 / denom is all the kernel needs beyond
+// the scan: a component's transform size and residual replication follow from it and the sampling factors.  The DevScan of such an image
+// carries win_* in pixels and cov_* in MCUs of the REDUCED picture (an MCU is m * max_h x m * max_v pixels of it); no other kernel reads them
+// for it.  ONE launch for all listed scans, behind K3J's.
+struct ReducedWork {
+    uint32_t scan;
+    uint32_t row;    // MCU row of the cover
+    uint32_t first;  // first block of the workgroup in that row of cov_cols * blocks_per_mcu blocks
+    uint32_t m;      // 4, 2 or 1
+};
+hipError_t launch_reduced(hipStream_t stream, const int16_t *coefs, const DevScan *scans, const ReducedWork *work, int n_work, const DevScanStatus *status,
+                          const DevQuantTable *quant_pool, uint8_t *scratch);
 
 // Waves per workgroup of the POOLED form of the K2S final pass (k2s_subseq.hip: runs of scans that stage the same tables; one workgroup per CU, every wave takes the
 // next 64 lanes from a counter): 10 waves + 4 tables fill a CU's LDS.  Runs shorter than kSubFinalPoolMinChunks waves, and runs
