@@ -1052,6 +1052,53 @@ int jpgpu_encoder_upload_device(jpgpu_encoder *e, const void *const *device_pixe
                                 const int32_t *pixel_layouts, int n);
 int jpgpu_encoder_upload_described_device(jpgpu_encoder *e, const void *const *device_pixels, const jpgpu_encode_description *desc,
                                           const int32_t *pixel_layouts, int n);
+/* ---- (4d) Arithmetic: the file libjpeg writes in place of the reference's (an extension beyond the reference; what Pillow's
+ * Image.save(f, "JPEG", quality=q, subsampling=s), torchvision.io.encode_jpeg and OpenCV write, all on libjpeg-turbo's jpeg_fdct_islow).
+ *   By default (JPGPU_ARITHMETIC_REFERENCE) every stream is what it was, byte for byte.  Under JPGPU_ARITHMETIC_LIBJPEG the stream of an
+ * image of jpgpu_encoder_upload / jpgpu_encoder_upload_device is, from SOI to EOI, the file libjpeg's baseline compressor writes for the
+ * same pixels, quality and sampling with its default settings (Annex K Huffman tables, no optimisation, no smoothing).  Per image:
+ *   1. TABLES.  s = quality < 50 ? 5000 / quality : 200 - 2 * quality; element = clamp((std * s + 50) / 100, 1, 255) over the Annex K
+ *     luminance (table 0) and chrominance (table 1) tables, integer division.  jpgpu_encoder_set_quantization_table replaces one.
+ *   2. COLOUR, input_rgb 1 and 2 (2: the alpha byte stepped over):
+ *       Y = (19595 R + 38470 G + 7471 B + 32768) >> 16          Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *       Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *     input_rgb == 0 with three components takes the samples as they are (Pillow's mode "YCbCr").
+ *   3. GEOMETRY AND EDGES.  Three components: luma (H, V) = (luma_h, luma_v), one of 1 x 1, 2 x 1, 2 x 2; chroma 1 x 1; an interleaved scan
+ *     of ceil(W / 8H) x ceil(Ht / 8V) MCUs.  A component with factors (h, v) has wb = ceil(ceil(W h / H) / 8) by hb = ceil(ceil(Ht v / V) / 8)
+ *     blocks of its own.  The last pixel column of the full-size plane is repeated out to wb * 8 * (H / h) columns, the last pixel row out
+ *     to a multiple of V rows and no further; then the plane is downsampled -- H / h = V / v = 2: (a + b + c + d + bias) >> 2 with bias 1, 2,
+ *     1, 2, ... along the output row; H / h = 2 alone: (a + b + bias) >> 1 with bias 0, 1, 0, 1, ...; else a copy -- and the last DOWNSAMPLED
+ *     row is repeated out to hb * 8 rows.  One component: a non-interleaved scan of ceil(W / 8) x ceil(Ht / 8) MCUs of one block, whatever
+ *     luma_h and luma_v say (they must be one of the three shapes); SOF0 carries 1 x 1, as Pillow writes it.
+ *   4. DUMMY BLOCKS.  A block of an MCU at bx >= wb or by >= hb of its component is not transformed: its AC values are zero, its DC is the
+ *     quantised DC of the block emitted just before it in the same MCU (the first block of a component in an MCU always lies inside).
+ *   5. THE TRANSFORM, jfdctint.c with CONST_BITS = 13, PASS1_BITS = 2, on sample - 128, the eight values d0..d7 of each ROW first, then
+ *     of each COLUMN of what the rows left, DESCALE(x, n) = (x + (1 << (n - 1))) >> n an arithmetic shift:
+ *       t0 = d0 + d7   t1 = d1 + d6   t2 = d2 + d5   t3 = d3 + d4       t7 = d0 - d7   t6 = d1 - d6   t5 = d2 - d5   t4 = d3 - d4
+ *       t10 = t0 + t3   t13 = t0 - t3   t11 = t1 + t2   t12 = t1 - t2
+ *       rows: o0 = (t10 + t11) << 2, o4 = (t10 - t11) << 2, n = 11     columns: o0 = DESCALE(t10 + t11, 2), o4 = DESCALE(t10 - t11, 2), n = 15
+ *       z1 = (t12 + t13) * 4433      o2 = DESCALE(z1 + t13 * 6270, n)      o6 = DESCALE(z1 - t12 * 15137, n)
+ *       z1 = t4 + t7   z2 = t5 + t6   z3 = t4 + t6   z4 = t5 + t7   z5 = (z3 + z4) * 9633
+ *       t4 *= 2446   t5 *= 16819   t6 *= 25172   t7 *= 12299   z1 *= -7373   z2 *= -20995   z3 = z3 * -16069 + z5   z4 = z4 * -3196 + z5
+ *       o7 = DESCALE(t4 + z1 + z3, n)   o5 = DESCALE(t5 + z2 + z4, n)   o3 = DESCALE(t6 + z2 + z3, n)   o1 = DESCALE(t7 + z1 + z4, n)
+ *     All in 32-bit integers, which 8-bit samples never leave.  The result is 8 times the DCT.
+ *   6. QUANTISATION.  d = Q << 3, m = (|c| + (d >> 1)) / d, integer division; the value is -m where c < 0 (halves round away from zero).
+ *   7. ENTROPY CODING AND HEADER.  The Annex K tables; restart_interval as in jpgpu_encode_params.  The header: SOI; APP0 "JFIF\0", version
+ *     1.01, units 0, density 1 x 1, no thumbnail; DQT table 0 and DQT table 1, a segment each (one component: table 0 alone); SOF0, precision
+ *     8, component identifiers 1, 2, 3, factors (H, V), (1, 1), (1, 1), tables 0, 1, 1; DHT DC0, AC0, DC1, AC1, a segment each (one
+ *     component: the first two); DRI only with a restart interval, directly in front of SOS; SOS with selectors 0x00, 0x11, 0x11 and 00 3F 00.
+ *   The blocks jpgpu_encoder_download_coefficients returns are the ones of steps 1 to 6, dummy blocks included.
+ *   Refused, the encoder staying as it was: optimize_coding != 0 and luma factors other than the three shapes (JPGPU_ERR_ARGUMENT, for the
+ * whole upload); jpgpu_encoder_upload_described and _upload_described_device (JPGPU_ERR_INVALID_OPERATION): a description is the
+ * reference's encoder state.
+ *   State of the encoder: every later jpgpu_encoder_upload / _upload_device reads it until it is set again; an upload keeps the arithmetic it
+ * was planned with.  Not covered: libjpeg's optimised tables, progressive output, smoothing, other sampling (4:4:0, 4:1:1), other segments
+ * (density, ICC, EXIF); the JpegEncoder mirror and the optimizer.
+ * JPGPU_ERR_ARGUMENT for any other value of `policy` (a jpgpu_arithmetic_policy). */
+int jpgpu_encoder_set_arithmetic_policy(jpgpu_encoder *e, int policy);
+/* JPGPU_ARITHMETIC_LIBJPEG where image i of the last upload was planned with the integer transform, else JPGPU_ARITHMETIC_REFERENCE.  Valid
+ * after an upload; JPGPU_ERR_ARGUMENT for a NULL argument or an index out of range. */
+int jpgpu_encoder_image_arithmetic(const jpgpu_encoder *e, int i, int *arithmetic);
 /* status of image i as known so far (after the upload: JPGPU_OK or the refusal; after the encode also "No symbol is recorded.") */
 int jpgpu_encoder_image_status(const jpgpu_encoder *e, int i);
 /* Host only, no context, no device: the status an encode of `desc` would report, with its message in message[message_cap]

@@ -303,6 +303,8 @@ SYMBOLS = [
     ("jpgpu_encoder_upload_device", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(EncodeParams), C.POINTER(C.c_int32), C.c_int]),
     ("jpgpu_encoder_upload_described_device", C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(EncodeDescription), C.POINTER(C.c_int32), C.c_int]),
     ("jpgpu_encoder_image_status", C.c_int, [_P, C.c_int]),
+    ("jpgpu_encoder_set_arithmetic_policy", C.c_int, [_P, C.c_int]),
+    ("jpgpu_encoder_image_arithmetic", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     ("jpgpu_encode_description_header", C.c_int, [C.POINTER(EncodeDescription), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p,
                                                   C.c_size_t]),
     ("jpgpu_optimizer_create", C.c_int, [_P, C.POINTER(_P)]),

@@ -1497,6 +1497,10 @@ int jpgpu_encoder_upload(jpgpu_encoder *enc, const uint8_t *const *pixels, const
 int jpgpu_encoder_set_quantization_table(jpgpu_encoder *enc, int i, int identifier, const uint16_t *zigzag64) {
     JPGPU_GUARD(enc, enc->impl.set_quantization_table(i, identifier, zigzag64));
 }
+int jpgpu_encoder_set_arithmetic_policy(jpgpu_encoder *enc, int policy) { JPGPU_GUARD(enc, enc->impl.set_arithmetic_policy(policy)); }
+int jpgpu_encoder_image_arithmetic(const jpgpu_encoder *enc, int i, int *arithmetic) {
+    return enc ? enc->impl.image_arithmetic(i, arithmetic) : JPGPU_ERR_ARGUMENT;
+}
 int jpgpu_encoder_encode(jpgpu_encoder *enc) { JPGPU_GUARD(enc, enc->impl.encode()); }
 int jpgpu_encoder_stage_ms(jpgpu_encoder *enc, float ms[5]) { JPGPU_GUARD(enc, enc->impl.stage_ms(ms)); }
 int jpgpu_encoder_emit_passes(const jpgpu_encoder *enc, int *one_pass, int *fell_back) {

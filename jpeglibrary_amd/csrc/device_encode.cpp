@@ -178,6 +178,58 @@ void assemble_header(const std::vector<uint8_t> &pre, const std::vector<uint8_t>
     h.insert(h.end(), post.begin(), post.end());
 }
 
+// ------------------------------------------------------------------------------------------------ libjpeg's header
+
+namespace {
+template <typename Body>
+void put_segment(std::vector<uint8_t> &h, int marker, const Body &body) {
+    put_marker(h, marker);
+    put_length(h, (uint16_t)body.size());
+    h.insert(h.end(), body.begin(), body.end());
+}
+}  // namespace
+
+// jcmarker.c: write_file_header (SOI, APP0), write_frame_header (a DQT segment per table in use, SOF0), write_scan_header (a DHT
+// segment per table in use: DC then AC of each component's pair; DRI; SOS)
+void write_libjpeg_header(const DevEncImage &im, int restart_interval, std::vector<uint8_t> *header) {
+    std::vector<uint8_t> &h = *header;
+    h.clear();
+    const int nc = (int)im.components;
+    put_marker(h, 0xD8);
+    put_segment(h, 0xE0, std::vector<uint8_t>{'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});  // version 1.01, no units, density 1 x 1, no thumbnail
+    for (int t = 0; t < (nc == 3 ? 2 : 1); t++) {
+        std::vector<uint8_t> body(1, (uint8_t)t);
+        for (int i = 0; i < 64; i++) body.push_back((uint8_t)im.quant[t][i]);
+        put_segment(h, 0xDB, body);
+    }
+    std::vector<uint8_t> sof = {8, (uint8_t)(im.height >> 8), (uint8_t)im.height, (uint8_t)(im.width >> 8), (uint8_t)im.width, (uint8_t)nc};
+    for (int c = 0; c < nc; c++) {
+        sof.push_back((uint8_t)(c + 1));
+        sof.push_back(c == 0 ? (uint8_t)((im.luma_h << 4) | im.luma_v) : (uint8_t)0x11);
+        sof.push_back(c == 0 ? 0 : 1);
+    }
+    put_segment(h, 0xC0, sof);
+    for (int t = 0; t < (nc == 3 ? 4 : 2); t++) {  // DC0, AC0, DC1, AC1
+        std::vector<uint8_t> body(1, (uint8_t)(((t & 1) << 4) | (t >> 1)));
+        body.insert(body.end(), kStd[t].lengths, kStd[t].lengths + 16);
+        body.insert(body.end(), kStd[t].values, kStd[t].values + kStd[t].count);
+        put_segment(h, 0xC4, body);
+    }
+    if (restart_interval) put_segment(h, 0xDD, std::vector<uint8_t>{(uint8_t)(restart_interval >> 8), (uint8_t)restart_interval});
+    std::vector<uint8_t> sos(1, (uint8_t)nc);
+    for (int c = 0; c < nc; c++) {
+        sos.push_back((uint8_t)(c + 1));
+        sos.push_back(c == 0 ? 0x00 : 0x11);
+    }
+    sos.insert(sos.end(), {0, 63, 0});
+    put_segment(h, 0xDA, sos);
+}
+
+size_t libjpeg_header_quant_at(const DevEncImage &im, int identifier) {
+    if (identifier != 0 && im.components != 3) return 0;
+    return 2 + 18 + (size_t)identifier * 69 + 5;  // SOI, APP0, the DQT segments in front (marker, length, identifier, 64 elements each)
+}
+
 // ------------------------------------------------------------------------------------------------ stuffing stage layout
 
 StuffPlan plan_stuffing_layout(DevEncImage *images, const uint64_t *raw_bits, int n, bool place_raw) {
@@ -489,7 +541,35 @@ int EncodeBatch::upload_described_device(const void *const *device_pixels, const
     return upload_descriptions(reinterpret_cast<const uint8_t *const *>(device_pixels), desc, n, true, pixel_layouts);
 }
 
+int EncodeBatch::set_arithmetic_policy(int policy) {
+    if (policy != JPGPU_ARITHMETIC_REFERENCE && policy != JPGPU_ARITHMETIC_LIBJPEG)
+        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_set_arithmetic_policy: the policy is JPGPU_ARITHMETIC_REFERENCE (0) or JPGPU_ARITHMETIC_LIBJPEG (1)");
+    arithmetic_policy_ = policy;
+    return JPGPU_OK;
+}
+int EncodeBatch::image_arithmetic(int i, int *arithmetic) const {
+    if (i < 0 || i >= (int)images_.size() || !arithmetic) return JPGPU_ERR_ARGUMENT;
+    *arithmetic = (int)images_[(size_t)i].arithmetic;
+    return JPGPU_OK;
+}
+
+// What the libjpeg policy refuses of an upload, before anything of the encoder's state is touched
+int EncodeBatch::check_libjpeg_params(const jpgpu_encode_params *params, int n) {
+    for (int i = 0; i < n; i++) {
+        const jpgpu_encode_params &p = params[i];
+        if (p.optimize_coding != 0)
+            return fail(JPGPU_ERR_ARGUMENT, "optimize_coding under JPGPU_ARITHMETIC_LIBJPEG: libjpeg's optimal tables are not this encoder's, the bytes would be neither's.");
+        if (!((p.luma_h == 2 && p.luma_v == 2) || (p.luma_h == 2 && p.luma_v == 1) || (p.luma_h == 1 && p.luma_v == 1)))
+            return fail(JPGPU_ERR_ARGUMENT, "JPGPU_ARITHMETIC_LIBJPEG takes luma sampling factors 1 x 1, 2 x 1 and 2 x 2.");
+    }
+    return JPGPU_OK;
+}
+
 int EncodeBatch::upload_params(const uint8_t *const *pixels, const jpgpu_encode_params *params, int n, bool device, const int32_t *pixel_layouts) {
+    if (arithmetic_policy_ == JPGPU_ARITHMETIC_LIBJPEG) {
+        const int rc = check_libjpeg_params(params, n);
+        if (rc != JPGPU_OK) return rc;
+    }
     std::vector<EncPlan> plans((size_t)n);
     for (int i = 0; i < n; i++) {
         plans[(size_t)i].legacy = true;
@@ -500,6 +580,8 @@ int EncodeBatch::upload_params(const uint8_t *const *pixels, const jpgpu_encode_
 }
 
 int EncodeBatch::upload_descriptions(const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n, bool device, const int32_t *pixel_layouts) {
+    if (arithmetic_policy_ == JPGPU_ARITHMETIC_LIBJPEG)
+        return fail(JPGPU_ERR_INVALID_OPERATION, "A described image is the reference's encoder state: JPGPU_ARITHMETIC_LIBJPEG covers jpgpu_encoder_upload and jpgpu_encoder_upload_device.");
     std::vector<EncPlan> plans((size_t)n);
     for (int i = 0; i < n; i++) {
         std::string error;
@@ -699,8 +781,12 @@ int EncodeBatch::plan_encode_action_image(UploadPlan &up, int i, const EncPlan &
     if (rc != JPGPU_OK) return rc;
     im.in_components = p.input_rgb == 2 ? 4u : (uint32_t)p.components;  // (2: Rgba32 pixels, the alpha byte stepped over)
     im.components = (uint32_t)p.components;
-    im.luma_h = (uint32_t)p.luma_h;
-    im.luma_v = (uint32_t)p.luma_v;
+    // (the policy is read for jpgpu_encode_params alone: a described EncodeAction arrangement is refused under it before it gets here)
+    const bool libjpeg = arithmetic_policy_ == JPGPU_ARITHMETIC_LIBJPEG && !pl.legacy_has_quant;
+    im.arithmetic = libjpeg ? JPGPU_ARITHMETIC_LIBJPEG : JPGPU_ARITHMETIC_REFERENCE;
+    // libjpeg: one component is a non-interleaved scan, one block per MCU whatever its factors, and Pillow writes them as 1 x 1
+    im.luma_h = libjpeg && p.components == 1 ? 1u : (uint32_t)p.luma_h;
+    im.luma_v = libjpeg && p.components == 1 ? 1u : (uint32_t)p.luma_v;
     im.bpm = im.luma_h * im.luma_v + (im.components == 3 ? 2 : 0);
     im.input_rgb = p.input_rgb ? 1 : 0;
     im.restart_interval = (uint32_t)p.restart_interval;
@@ -717,6 +803,11 @@ int EncodeBatch::plan_encode_action_image(UploadPlan &up, int i, const EncPlan &
         scale_by_quality(kStdChr, p.quality, im.quant[1]);
     }
     plan_image_work(up, i, p.optimize_coding != 0);
+    if (libjpeg) {  // (E1J gathers into LDS: no samples in HBM; no tables to build: the header is final)
+        write_libjpeg_header(im, p.restart_interval, &headers_[i]);
+        im.header_len = (uint32_t)headers_[i].size();
+        return JPGPU_OK;
+    }
     if ((up.smp_off >> 8) > 0xFFFFFFFFull) return fail(JPGPU_ERR_OUT_OF_MEMORY, "sample buffer beyond 1 TiB");
     im.smp_off_256 = (uint32_t)(up.smp_off >> 8);
     // (an image fdct_fused_kernel takes has no gathered samples: 4.2 GB less per 256 x 4K)
@@ -815,6 +906,15 @@ int EncodeBatch::set_quantization_table(int i, int identifier, const uint16_t *z
     for (int k = 0; k < 64; k++)
         if (zigzag64[k] == 0 || zigzag64[k] > 255) return fail(JPGPU_ERR_ARGUMENT, "Quantization table elements must be in 1..255 (element precision 0).");
     DevEncImage &im = images_[(size_t)i];
+    if (im.arithmetic == JPGPU_ARITHMETIC_LIBJPEG) {  // write_libjpeg_header's DQT segment of this table, if it wrote one
+        const size_t at = libjpeg_header_quant_at(im, identifier);
+        for (int k = 0; k < 64; k++) {
+            im.quant[identifier][k] = zigzag64[k];
+            if (at) headers_[(size_t)i][at + (size_t)k] = (uint8_t)zigzag64[k];
+        }
+        encoded_ = false;
+        return JPGPU_OK;
+    }
     // the DQT segment write_marker_segments wrote: SOI, FF DB, length, then per table one identifier byte + 64 elements
     const size_t at = 2 + 2 + 2 + (size_t)identifier * 65 + 1;
     for (int k = 0; k < 64; k++) {
@@ -881,12 +981,17 @@ int EncodeBatch::upload_image_descriptors() {
 int EncodeBatch::run_fdct(const EncodeRun &r) {
     size_t max_record = 0;
     uint32_t fused_shapes = 0;
+    uint32_t libjpeg_shapes = 0;  // (launch_fdct_libjpeg: 2 x 2, 2 x 1, 1 x 1)
     bool any_other = false, any_other_planar = false;
     // (a device upload: DevEncImage.px_off is the caller's address itself)
     const uint8_t *pixel_base = pixels_on_device_ ? nullptr : (const uint8_t *)d_pixels_.ptr;
     const bool no_fused = !enc_fused_enabled();
     for (const DevEncImage &im : images_) {
         if (im.layout != 0) continue;  // (enc_general_fdct_kernel)
+        if (im.arithmetic == JPGPU_ARITHMETIC_LIBJPEG) {
+            libjpeg_shapes |= im.luma_h == 1 ? 4u : (im.luma_v == 1 ? 2u : 1u);
+            continue;
+        }
         max_record = std::max(max_record, enc_sample_bytes_per_mcu(im.luma_h, im.luma_v, im.components));
         const int shape = no_fused ? 0 : enc_image_fused_shape(im);
         if (shape != 0) fused_shapes |= 1u << shape;
@@ -895,6 +1000,11 @@ int EncodeBatch::run_fdct(const EncodeRun &r) {
     hipError_t e = launch_fdct_quant(ctx_->stream, pixel_base, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_mcu_.ptr, n_work_mcu_,
                                      (uint8_t *)d_samples_.ptr, (int16_t *)d_coefs_.ptr, max_record, fused_shapes, any_other, any_other_planar);
     if (e != hipSuccess) return hip_fail(e, "fdct_quant_kernel");
+    if (libjpeg_shapes) {
+        e = launch_fdct_libjpeg(ctx_->stream, pixel_base, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_mcu_.ptr, n_work_mcu_, (int16_t *)d_coefs_.ptr,
+                                libjpeg_shapes);
+        if (e != hipSuccess) return hip_fail(e, "e1j_fdct_kernel");
+    }
     if (r.layouts) {
         e = launch_fdct_quant_general(ctx_->stream, pixel_base, (const DevEncImage *)d_images_.ptr, r.layouts, (const EncWork *)d_work_mcu_.ptr, n_work_mcu_,
                                       (int16_t *)d_coefs_.ptr);

@@ -40,6 +40,12 @@ void write_marker_segments(const EncSegmentQuant *quant, int n_quant, const EncS
 void assemble_header(const std::vector<uint8_t> &pre, const std::vector<uint8_t> &dht_body, const std::vector<uint8_t> &post,
                      std::vector<uint8_t> *header);
 
+// SOI .. SOS as libjpeg writes them (include/jpgpu.h 4d): SOI, APP0 "JFIF", one DQT segment per table, SOF0, one DHT segment per standard
+// table, (DRI,) SOS.  `im` holds the geometry and the tables; a one-component image names table 0 and the two luminance Huffman tables only.
+void write_libjpeg_header(const DevEncImage &im, int restart_interval, std::vector<uint8_t> *header);
+// ... and where the 64 elements of quantisation table `identifier` stand in it (0: the header holds no such table)
+size_t libjpeg_header_quant_at(const DevEncImage &im, int identifier);
+
 // The stuffing stage's (E4, launch_stuff) layout, for the encoder's images and the optimizer's DRI = 0 scans (descriptors in the
 // encoder's image form): from raw_bits[k] and the image's header_len, restart_interval and n_units, where its raw bytes lie
 // (raw_off; left alone unless place_raw: the one-pass emit has placed them already), where its finished stream goes (out_off: the
@@ -90,6 +96,9 @@ class EncodeBatch {
     int upload_device(const void *const *device_pixels, const jpgpu_encode_params *params, const int32_t *pixel_layouts, int n);
     int upload_described_device(const void *const *device_pixels, const jpgpu_encode_description *desc, const int32_t *pixel_layouts, int n);
     int set_quantization_table(int i, int identifier, const uint16_t *zigzag64);           // SetQuantizationTable of image i
+    // the arithmetic of the uploads from here on (jpgpu_encoder_set_arithmetic_policy), and what image i of the last one was planned with
+    int set_arithmetic_policy(int policy);
+    int image_arithmetic(int i, int *arithmetic) const;
     int encode();                                                                        // JpegEncoder.Encode() x n
     // device time of the last encode() by stage (HIP events on the context's stream): E1 pixels -> quantised blocks, E2 bit counts
     // and offsets, E3 bit emission, E4 byte stuffing; ms[4] = the four together (the host round trips between them excluded)
@@ -117,6 +126,7 @@ class EncodeBatch {
     struct UploadPlan;
     int layout_plans(UploadPlan &up, const std::vector<EncPlan> &plans);
     int check_device_arguments(const UploadPlan &up, int n);
+    int check_libjpeg_params(const jpgpu_encode_params *params, int n);
     void reset_upload_state(int n);
     int plan_described_image(UploadPlan &up, int i, const EncPlan &pl);
     int plan_encode_action_image(UploadPlan &up, int i, const EncPlan &pl);
@@ -137,6 +147,7 @@ class EncodeBatch {
     int place_headers(const EncodeRun &r);
     int emit_and_stuff(const EncodeRun &r);
     jpgpu_ctx *ctx_;
+    int arithmetic_policy_ = JPGPU_ARITHMETIC_REFERENCE;  // state of the encoder: jpgpu_encoder_upload and _upload_device read it
     std::vector<DevEncImage> images_;
     std::vector<std::vector<uint8_t>> headers_;        // SOI .. SOS as Encode() writes them (optimizeCoding: rebuilt per encode())
     std::vector<std::vector<uint8_t>> headers_pre_;    // optimizeCoding: SOI, DQT, SOF0 ...

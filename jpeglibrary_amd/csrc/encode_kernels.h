@@ -35,7 +35,7 @@ struct alignas(16) DevEncImage {
     uint16_t quant[2][64];  // zig-zag quantisation tables: luma, chroma
     uint64_t plane_stride;  // px_planar: bytes from plane to plane (height x width: the planes are tight)
     uint32_t px_planar;     // 1: in_components planes of height x width bytes (JPGPU_PIXELS_PLANAR); a device upload only
-    uint32_t reserved;
+    uint32_t arithmetic;    // JPGPU_ARITHMETIC_LIBJPEG: stage E1J (e1j_libjpeg.hip) takes the image, stage E1's kernels leave it alone
 };
 static_assert(sizeof(DevEncImage) % 16 == 0, "DevEncImage must be a multiple of 16 bytes");
 
@@ -80,6 +80,10 @@ hipError_t launch_fdct_quant(hipStream_t stream, const uint8_t *pixels, const De
                              uint8_t *samples, int16_t *coefs, size_t max_record_bytes,  // (the largest enc_sample_bytes_per_mcu of the batch)
                              uint32_t fused_shapes, bool any_other /* interleaved */, bool any_other_planar = false);
 int enc_image_fused_shape(const DevEncImage &im);
+// E1J (e1j_libjpeg.hip): the images with DevEncImage.arithmetic == JPGPU_ARITHMETIC_LIBJPEG -- three components with luma 2 x 2 (shapes bit
+// 0), 2 x 1 (bit 1) or 1 x 1 (bit 2), or one component (planned 1 x 1: bit 2) -- from any of the pixel forms, into the same blocks of `coefs`
+hipError_t launch_fdct_libjpeg(hipStream_t stream, const uint8_t *pixels, const DevEncImage *images, const EncWork *work, int n_work,
+                               int16_t *coefs, uint32_t shapes);
 size_t enc_sample_bytes_per_mcu(uint32_t luma_h, uint32_t luma_v, uint32_t components);
 // the described arrangements (DevEncImage.layout != 0): pixels -> quantised blocks in one kernel, one lane per MCU; then the
 // general forms of block_stats / block_bits / emit (launch_*: `layouts` != nullptr runs them beside the EncodeAction forms,

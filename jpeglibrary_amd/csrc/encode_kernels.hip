@@ -86,7 +86,7 @@ __device__ __forceinline__ void block_fdct(float (&f)[64]) {
 // E1a + E1b.
 __host__ __device__ inline int enc_fused_shape(const DevEncImage &im) {
     // (four-byte pixels: R, G, B, A with the alpha ignored -- ConvertRgba32ToYCbCr8, instances 4, 5, 6)
-    if (im.layout != 0 || im.components != 3 || !(im.in_components == 3 || (im.in_components == 4 && im.input_rgb != 0 && im.px_planar == 0))) return 0;
+    if (im.layout != 0 || im.arithmetic != 0 || im.components != 3 || !(im.in_components == 3 || (im.in_components == 4 && im.input_rgb != 0 && im.px_planar == 0))) return 0;
     const int wide = im.px_planar != 0 ? 6 : (im.in_components == 4 ? 3 : 0);
     if (im.luma_h == 2 && im.luma_v == 2) return 1 + wide;
     if (im.luma_h == 2 && im.luma_v == 1) return 2 + wide;
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(8 * kEncMcusPerWg) void enc_gather_kernel(const uin
     extern __shared__ __attribute__((aligned(16))) uint8_t sh_records[];
     const EncWork wk = work[blockIdx.x];
     const DevEncImage &im = images[wk.image];
-    if ((skip_fused && enc_fused_ok(im)) || im.layout != 0) return;  // (uniform: fdct_fused_kernel / enc_general_fdct_kernel takes the image)
+    if ((skip_fused && enc_fused_ok(im)) || im.layout != 0 || im.arithmetic != 0) return;  // (uniform: fdct_fused_kernel / enc_general_fdct_kernel takes the image)
     if ((im.px_planar != 0) != PLANAR) return;                        // (... or this kernel's other form)
     const uint32_t m = threadIdx.x % kEncMcusPerWg, k = threadIdx.x / kEncMcusPerWg;
     const uint32_t mcus_per_line = im.mcus_per_line;
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(kEncMcusPerWg, JPGPU_E1B_WAVES) void fdct_quant_ker
     __shared__ __attribute__((aligned(16))) uint8_t sh_blk[kEncMcusPerWg * 128];
     const EncWork wk = work[blockIdx.x];
     const DevEncImage &im = images[wk.image];
-    if ((skip_fused && enc_fused_ok(im)) || im.layout != 0) return;
+    if ((skip_fused && enc_fused_ok(im)) || im.layout != 0 || im.arithmetic != 0) return;
     const uint32_t lane = threadIdx.x;
     if (lane < 64) {
         sh_q[0][lane] = quant_pair(im.quant[0][lane]);

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .batch import _DeviceView
+from .batch import _DeviceView, _arithmetic_policy
 from .context import Context, default_context
 from .errors import raise_for_status
 
@@ -108,15 +108,41 @@ class EncodeBatch:
         self._n = 0
         self._blocks = []
         self._keep = None
+        self._libjpeg = False
 
     def _check(self, rc):
         raise_for_status(rc, _lib.jpgpu_last_error(self.ctx._h))
 
-    def upload(self, images, luma=(2, 2), quality=75, rgb=False, optimize_coding=False, restart_interval=0):
+    def set_arithmetic_policy(self, arithmetic):
+        """Which arithmetic upload() and upload_tensors() plan with from here on: "reference", the default -- the reference's float transform,
+        zero padding and header, every stream the bytes it always was -- or "libjpeg": jpeg_fdct_islow, libjpeg's colour constants, edge
+        replication, dummy blocks and header (include/jpgpu.h, 4d), byte for byte the file Pillow's Image.save(f, "JPEG", quality=q,
+        subsampling=s) writes for the same pixels.  Under "libjpeg" optimize_coding and luma factors other than (1, 1), (2, 1), (2, 2) raise
+        ArgumentException, the described uploads InvalidOperationException; a grey image is planned (1, 1) whatever luma says.  State of the
+        batch: it holds until set again.  ValueError, before the library is called, for any other value."""
+        policy = _arithmetic_policy(arithmetic)
+        self._check(_lib.jpgpu_encoder_set_arithmetic_policy(self._h, policy))
+        self._libjpeg = policy == 1
+        return self
+
+    def arithmetic(self, i):
+        """1 where image i of the last upload was planned with libjpeg's integer transform, else 0"""
+        a = C.c_int()
+        raise_for_status(_lib.jpgpu_encoder_image_arithmetic(self._h, i, C.byref(a)), b"jpgpu_encoder_image_arithmetic: no such image")
+        return a.value
+
+    def _planned_luma(self, luma, components):
+        # (libjpeg: one component is a non-interleaved scan of single blocks, see jpgpu.h 4d)
+        return (1, 1) if self._libjpeg and components == 1 else (luma[0], luma[1])
+
+    def upload(self, images, luma=(2, 2), quality=75, rgb=False, optimize_coding=False, restart_interval=0, arithmetic=None):
         """images: list of uint8 arrays (H, W, 3) or (H, W) / (H, W, 1); with rgb=True also (H, W, 4) = Rgba32 pixels, the alpha byte
         stepped over like ConvertRgba32ToYCbCr8 does (the reference's EncoderBenchmark).  luma = sampling factors of the first component.
         optimize_coding = EncodeAction's switch: Huffman tables built from each image's own statistics.
-        restart_interval = MCUs between restart markers (0 = none, as the reference's encoder; an extension, see jpgpu.h)."""
+        restart_interval = MCUs between restart markers (0 = none, as the reference's encoder; an extension, see jpgpu.h).
+        arithmetic = "reference" or "libjpeg": set_arithmetic_policy() first (None: the batch's policy as it stands)."""
+        if arithmetic is not None:
+            self.set_arithmetic_policy(arithmetic)
         n = len(images)
         ptrs = (C.c_void_p * n)()
         params = (_capi.EncodeParams * n)()
@@ -135,8 +161,7 @@ class EncodeBatch:
                     raise ValueError("four bytes per pixel are Rgba32 pixels: rgb=True")
                 c, mode = 3, 2
             params[i] = _capi.EncodeParams(w, h, c, luma[0], luma[1], quality, mode, int(optimize_coding), int(restart_interval))
-            mcus = (-(-w // (8 * luma[0]))) * (-(-h // (8 * luma[1])))
-            self._blocks.append(mcus * (luma[0] * luma[1] + (2 if c == 3 else 0)))
+            self._blocks.append(_blocks_of(w, h, self._planned_luma(luma, c), c))
         self._keep = None
         self._check(_lib.jpgpu_encoder_upload(self._h, ptrs, params, n))
         self._n = n
@@ -156,7 +181,7 @@ class EncodeBatch:
         self._n = n
         return self
 
-    def upload_tensors(self, tensors, luma=(2, 2), quality=75, rgb=False, optimize_coding=False, restart_interval=0, layout=None):
+    def upload_tensors(self, tensors, luma=(2, 2), quality=75, rgb=False, optimize_coding=False, restart_interval=0, layout=None, arithmetic=None):
         """upload() for pixels that are on the device already: torch uint8 tensors on the context's device, read where they are --
         no download, no permute, no copy (jpgpu_encoder_upload_device).  layout='chw' (the default: what decode_to_tensors returns) takes
         (3, H, W) or (1, H, W); layout='hwc' takes (H, W, 3), (H, W), (H, W, 1) and, with rgb=True, (H, W, 4) = Rgba32.  The other arguments
@@ -164,6 +189,8 @@ class EncodeBatch:
         not contiguous (call .contiguous(): nothing is copied silently) or is not on the context's device.
         torch's current stream on that device is synchronised first, so whatever produced the tensors has finished; the batch keeps
         references to the tensors until the next upload or close(), and they must not be written before encode() has returned."""
+        if arithmetic is not None:
+            self.set_arithmetic_policy(arithmetic)
         tensors = list(tensors)
         hwc = (layout or "chw") == "hwc"
         pixels, pixel_layout = _tensor_pixels(tensors, layout, self.ctx.device, lambda i, w, h, c: c in (1, 3) or (c == 4 and hwc and rgb))
@@ -174,7 +201,7 @@ class EncodeBatch:
             if c == 4:
                 c, mode = 3, 2
             params[i] = _capi.EncodeParams(w, h, c, luma[0], luma[1], quality, mode, int(optimize_coding), int(restart_interval))
-            self._blocks.append(_blocks_of(w, h, luma, c))
+            self._blocks.append(_blocks_of(w, h, self._planned_luma(luma, c), c))
         return self._device_upload(_lib.jpgpu_encoder_upload_device, tensors, pixels, pixel_layout, params)
 
     def upload_described_tensors(self, tensors, descriptions, layout=None):
@@ -293,18 +320,21 @@ class EncodeBatch:
             pass
 
 
-def encode_batch(images, luma=(2, 2), quality=75, rgb=False, ctx=None, optimize_coding=False, restart_interval=0):
-    """One-call helper: list of JPEG byte strings."""
-    b = EncodeBatch(ctx).upload(images, luma, quality, rgb, optimize_coding, restart_interval).encode()
+def encode_batch(images, luma=(2, 2), quality=75, rgb=False, ctx=None, optimize_coding=False, restart_interval=0, arithmetic="reference"):
+    """One-call helper: list of JPEG byte strings.  arithmetic="libjpeg": the files Pillow writes (EncodeBatch.set_arithmetic_policy)."""
+    _arithmetic_policy(arithmetic)  # (ValueError before a context is made)
+    b = EncodeBatch(ctx).upload(images, luma, quality, rgb, optimize_coding, restart_interval, arithmetic).encode()
     outs = [b.output(i) for i in range(len(b))]
     b.close()
     return outs
 
 
-def encode_tensors(tensors, luma=(2, 2), quality=75, rgb=True, ctx=None, optimize_coding=False, restart_interval=0, layout=None):
+def encode_tensors(tensors, luma=(2, 2), quality=75, rgb=True, ctx=None, optimize_coding=False, restart_interval=0, layout=None, arithmetic="reference"):
     """One-call helper for torch producers: uint8 tensors on the context's device (layout 'chw' by default: decode_to_tensors' output,
-    R,G,B planes) -> list of JPEG byte strings.  The pixels are never downloaded; see EncodeBatch.upload_tensors."""
-    b = EncodeBatch(ctx).upload_tensors(tensors, luma, quality, rgb, optimize_coding, restart_interval, layout).encode()
+    R,G,B planes) -> list of JPEG byte strings.  The pixels are never downloaded; see EncodeBatch.upload_tensors.  arithmetic="libjpeg": the
+    files Pillow writes (EncodeBatch.set_arithmetic_policy)."""
+    _arithmetic_policy(arithmetic)  # (ValueError before a context is made)
+    b = EncodeBatch(ctx).upload_tensors(tensors, luma, quality, rgb, optimize_coding, restart_interval, layout, arithmetic).encode()
     outs = [b.output(i) for i in range(len(b))]
     b.close()
     return outs
