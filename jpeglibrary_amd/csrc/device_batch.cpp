@@ -103,7 +103,7 @@ int DeviceBatch::set_color_policy(int policy) {
 int DeviceBatch::image_color(int i, int *kind) const {
     const ImagePlan *img = image(i);
     if (!img || !kind) return JPGPU_ERR_ARGUMENT;
-    *kind = img->color_kind;
+    *kind = img->status == JPGPU_OK ? img->color_kind : kColorYcbcr;  // (include/jpgpu.h: YCBCR for an image that failed at upload, its window's refusal included)
     return JPGPU_OK;
 }
 
@@ -284,7 +284,7 @@ int DeviceBatch::upsampling_ms(float *ms) {
 int DeviceBatch::image_orientation(int i, int *orientation) const {
     const ImagePlan *img = image(i);
     if (!img || !orientation) return JPGPU_ERR_ARGUMENT;
-    *orientation = img->orientation;
+    *orientation = img->status == JPGPU_OK ? img->orientation : 1;  // (include/jpgpu.h: 1 for an image that failed at upload, its window's refusal included)
     return JPGPU_OK;
 }
 

@@ -16,6 +16,7 @@ from tools import jpegsynth
 import color_model as cm
 import luma_model as lm
 import orient_model as om
+import policy_model as pm
 import resize_model as rm
 from test_color_gpu import _assert_bits
 from test_planar_rgb_gpu import _progressive_file
@@ -252,6 +253,7 @@ def test_cmyk_ycck_and_adobe_rgb_files_give_l_of_their_rgb(fmt):
         assert b.color(i) == cm.kind_file(n)[1]
         _check_plan(b, i, 45, 67, fmt)
         _assert_bits(b.output(i), lm.as_dtype(_kind_plane(n), NP[fmt], *args), n)
+        _assert_bits(b.output(i), pm.expected(files[i], arithmetic="reference", scale=1, upsampling="replicate", color="file", mode="gray", orientation=1, window=None, fmt=fmt, consts=consts, resize=None).output, n + ", the composed model")
     _assert_bits(b.output(3), lm.as_dtype(lm.plane("ycck", _samples([files[3]])[0][1]), NP[fmt], *args), "sub-sampled YCCK")
     # the same files under the default colour policy: 4 components fail as ever, the Adobe-RGB file is YCbCr and gives component 0
     c = _gray(files[:3], fmt, consts)

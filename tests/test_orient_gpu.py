@@ -13,6 +13,7 @@ import jpeglibrary_amd as jl
 from tools import jpegsynth
 import color_model as cm
 import orient_model as om
+import policy_model as pm
 import resize_model as rm
 from test_color_gpu import VARIANTS, V_IDS, _assert_bits
 from test_planar_rgb_gpu import _progressive_file
@@ -153,8 +154,23 @@ def test_colour_kinds_under_orientations_6_and_7(variant):
         for i, kind in enumerate(kinds):
             assert b.result(i).status == 0 and b.color(i) == kind and b.orientation(i) == o
             _assert_bits(b.output(i), om.orient_output(o, ref.output(i), fmt), "%s under %d" % (kind, o))
+            _assert_bits(b.output(i), pm.expected(files[i], arithmetic="reference", scale=1, upsampling="replicate", color="file", mode="rgb", orientation=o, window=None, fmt=fmt, consts=consts, resize=None).output, "%s under %d, the composed model" % (kind, o))
         b.close()
     ref.close()
+
+
+def test_an_image_whose_window_is_refused_reports_orientation_1_and_ycbcr_as_a_failed_image_does():
+    """include/jpgpu.h: jpgpu_batch_image_orientation gives 1 and jpgpu_batch_image_color YCBCR for an image that failed at upload; a window
+    outside the oriented frame fails its image at upload.  (The accessors used to hand out what the plan had reached when the window was refused.)"""
+    g = _file(31, 33, "gray")
+    b = _decode([g, g], jl.FMT_RGB_PLANAR_U8, orientations=[6, 6], windows=[(0, 0, 0, 0), (32, 0, 1, 1)], color="file")  # the oriented frame is 33 x 31: its last column
+    assert b.image_info(1).status == 0 and (b.orientation(1), b.color(1)) == (6, "gray")
+    b.close()
+    b = _decode([g, g], jl.FMT_RGB_PLANAR_U8, orientations=[6, 6], windows=[(0, 0, 0, 0), (33, 0, 1, 1)], color="file")
+    assert b.image_info(0).status == 0 and (b.orientation(0), b.color(0)) == (6, "gray")
+    assert b.image_info(1).status == ERR_ARGUMENT and b.image_info(1).out_bytes == 0 and (b.orientation(1), b.color(1)) == (1, "ycbcr")
+    assert (b.scale(1), b.arithmetic(1), b.upsampling(1), b.channels(1)) == (1, 0, 0, 3)
+    b.close()
 
 
 # ------------------------------------------------------------------------------------------------ 4: one mixed upload

@@ -17,6 +17,7 @@ import color_model as cm
 import islow_model as im
 import luma_model as lm
 import orient_model as om
+import policy_model as pm
 import resize_model as rm
 import scaled_model as sm
 from test_color_gpu import _assert_bits
@@ -286,6 +287,7 @@ def test_a_mixed_batch_keeps_full_size_for_what_does_not_take_the_transform():
         assert b.result(2).status != 0 and b.result(2).status == ref.result(2).status
         assert b.arithmetic(4) == 0 and b.result(4).status == 0 and b.window(4) == (0, 0, 70, 33)
         _assert_bits(b.output(4), ref.output(4), "the odd layout comes out full size, as without a scale")
+        _assert_bits(b.output(4), pm.expected(odd, arithmetic="libjpeg", scale=denom, upsampling="fancy", color="ycc", mode="rgb", orientation=1, window=None, fmt=FMT, consts=None, resize=None).output, "the odd layout against the composed model")
         for i in (0, 3, 5):
             solo = _decode([files[i]], denom, upsampling="fancy")
             _assert_bits(b.output(i), solo.output(0), "image %d against its solo decode" % i)
