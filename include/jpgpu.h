@@ -1130,6 +1130,78 @@ int jpgpu_optimizer_download(jpgpu_optimizer *o, int i, void *dst, size_t cap); 
 /* what Scan() counted for table `table` of file i, in the order the reference creates its table builders (:381-413) */
 int jpgpu_optimizer_statistics(const jpgpu_optimizer *o, int i, int table, uint8_t *table_class, uint8_t *identifier, uint32_t *counts);
 int jpgpu_optimizer_last_ms(const jpgpu_optimizer *o, float *ms);  /* device time of the last run (HIP events) */
+
+/* ---- Lossless transform: an image is turned or flipped in the coefficient domain on its way through the optimizer (an extension beyond the
+ * reference; what jpegtran -rotate / -flip / -transpose -optimize -copy none and exiftran -a do).  No coefficient is requantised.
+ *   Inputs.  The files the optimizer accepts: one sequential Huffman scan.  Progressive and multi-scan files stay JPGPU_ERR_NOT_SUPPORTED; the
+ * fences of DESIGN.md 5 apply as they are.  Refused per image with JPGPU_ERR_NOT_SUPPORTED when it is to be turned: a scan that does not hold
+ * every component of the frame once, in frame order; more than four components; factors outside 1..4; a one-component frame whose factors are
+ * not 1 x 1; a scan component without a Huffman table.
+ *   Orientation of an image: the decoder's vocabulary ("Orientation" above), unchanged.  jpgpu_optimizer_set_orientation_policy is state of
+ * the optimizer (JPGPU_ORIENT_STORED, the default, or JPGPU_ORIENT_FILE with the Exif rule of jpgpu_identify_orientation);
+ * jpgpu_optimizer_set_orientations gives the NEXT upload one value per file and is consumed by it: 1..8 is used as given, 0 leaves the image
+ * to the policy, n == 0 withdraws a pending list.  JPGPU_ERR_ARGUMENT for a value above 8 or an unknown policy; an upload whose n differs from
+ * the list's is refused with JPGPU_ERR_ARGUMENT and leaves the optimizer empty.
+ *   Orientation 1: the image takes the transcode path above; its bytes and its status are what the optimizer gives without any of this.  With
+ * no list pending under JPGPU_ORIENT_STORED, or with a 1 in the list, the file is not looked at for the transform at all.  Otherwise its
+ * headers up to the first SOS are read by Identify()'s marker loop -- the one jpgpu_identify_orientation runs: markers are looked for, not
+ * expected, lengths follow the reference's rule --, and a file that loop cannot walk is not turned: it keeps what the optimizer makes of it.
+ *   Orientations 2..8.  With F the source file, whose MCU is 8 Hmax x 8 Vmax pixels, the output is Optimize(strip) of a file F' that differs
+ * from F in four things.
+ *   1. Blocks.  The decoded picture of F' is the picture of F under the source-pixel table of "Orientation", (Y, X) <- (y, x).  Per block, with
+ *     c[v][u] the de-zig-zagged coefficients and v the vertical frequency: a mirror in x negates every odd u, a mirror in y every odd v, and a
+ *     transposing orientation (5..8) swaps u and v.  Source x is mirrored for 2, 3, 7, 8, source y for 3, 4, 6, 7.  Blocks move inside each
+ *     component's full MCU-padded grid: output block (bx', by') of a component is source block (bx, by) under the same table in units of
+ *     blocks, so padding blocks of the source land on padding positions of the output with whatever they hold (no dummy-block rule of libjpeg's
+ *     is adopted).  Values are never clamped or requantised; -(-32768) stays -32768.
+ *   2. SOF.  For 5..8 width and height are swapped and every component's H and V nibbles are swapped (4:2:2 becomes 4:4:0, 4:1:1 becomes
+ *     1 x 4).  Component ids and table selectors are unchanged.
+ *   3. DQT.  For 5..8 every table is transposed in place in its segment: entry zz(v, u) takes the value of entry zz(u, v), 8- and 16-bit
+ *     entries alike.  Segment order and lengths are unchanged.
+ *   4. DRI.  The value is kept: restart markers follow every DRI MCUs of the NEW MCU order, and DC prediction restarts there.
+ *   Huffman tables.  Optimize(strip) depends only on the segments and the symbol sequence, so the Huffman coding of F' does not matter: the
+ * output's tables are JpegHuffmanEncodingTableBuilder.Build over the statistics of the TURNED blocks, per (class, identifier) in the order the
+ * source declares them; jpgpu_optimizer_set_most_optimal_coding is honoured.  (The marker search of Optimize() runs through the DHT payloads:
+ * the source's are assumed to hold no FF byte, as those of every valid table.)
+ *   Edges.  A mirrored source axis must be a whole number of source MCUs.  Otherwise, under JPGPU_EDGE_REFUSE (the default; jpegtran -perfect)
+ * that image alone reports JPGPU_ERR_NOT_SUPPORTED with a message naming the axis, and its output length is 0; under JPGPU_EDGE_TRIM (jpegtran
+ * -trim) the partial last MCU column or row of the mirrored axis is dropped before the transform -- the width or height becomes the largest
+ * multiple of the MCU size --, and an axis shorter than one MCU is refused as above.  Non-mirrored axes are never trimmed; 5 needs nothing.
+ *   Exif.  Without `strip`, when the applied orientation came from the file under the policy (not from the list) and is not 1, the two bytes of
+ * the tag the identify rule found are rewritten to 1 in the file's byte order.  Nothing else in any APPn changes: thumbnails and the
+ * pixel-dimension tags inside Exif are out of scope and keep what the source says.
+ *   Failing scans.  An image whose scan the optimizer would fail keeps that status; its output is empty and its neighbours are untouched.
+ * The reference's restart rule holds for F' as for any file: where the MCU count of F' is a multiple of DRI, Scan() returns before it builds
+ * its tables and the image reports JPGPU_ERR_INVALID_OPERATION (a trimmed image has fewer MCUs than its source).
+ *   jpgpu_optimizer_image_transform reports, after an upload, what image i was planned with: applied orientation, output size, whether it was
+ * trimmed, the per-component factors of the output.  jpgpu_transform_plan gives the same facts and the refusal from a file alone -- host
+ * only, no context, no device -- as jpgpu_encode_description_header does for the encoder: `orientation` 0 = by `policy`, 1..8 as given; the
+ * return value is JPGPU_OK, the refusal (its text in message[message_cap], may be NULL), or the library's header error.  It reads the headers
+ * up to the first SOS as described under "Orientation 1": a second scan is the upload's to refuse.
+ *   Not covered: cropping, jpegtran's default of leaving an unmirrored strip at the edge, grey-scale conversion, the JpegOptimizer mirror. */
+typedef enum jpgpu_edge_policy {
+    JPGPU_EDGE_REFUSE = 0, /* a mirrored axis that is no whole number of MCUs refuses the image */
+    JPGPU_EDGE_TRIM = 1    /* ... drops its partial last MCU column or row */
+} jpgpu_edge_policy;
+typedef struct jpgpu_transform_info {
+    int32_t orientation;    /* applied: 1..8 */
+    int32_t trimmed;        /* 1: an edge was dropped */
+    uint32_t width, height; /* of the output */
+    uint32_t num_components;
+    uint8_t h[4], v[4];     /* of the output, frame order */
+    uint32_t reserved;
+} jpgpu_transform_info;
+size_t jpgpu_sizeof_transform_info(void);
+int jpgpu_optimizer_set_orientation_policy(jpgpu_optimizer *o, int policy);
+int jpgpu_optimizer_set_orientations(jpgpu_optimizer *o, const uint8_t *orientations, int n);
+int jpgpu_optimizer_set_edge_policy(jpgpu_optimizer *o, int edge);
+int jpgpu_optimizer_image_transform(const jpgpu_optimizer *o, int i, jpgpu_transform_info *info);
+/* the turned images' road in the last run (zeros: nothing was turned), HIP events on the context's stream: ms[0] KX alone, ms[1] the entropy
+ * decode in front of it, ms[2] the dense copy of the scans K2 handed over as half-line planes (tools/bench_transform.py reads them) */
+int jpgpu_optimizer_turn_ms(const jpgpu_optimizer *o, float ms[3]);
+int jpgpu_transform_plan(const uint8_t *file, size_t len, int orientation, int policy, int edge, jpgpu_transform_info *info, char *message,
+                         size_t message_cap);
+
 /* JpegHuffmanEncodingTableBuilder.Build(false) for one table: DHT counts and values, and GetCode() for all 256 symbols */
 /* The order .NET's Array.Sort(T[], Comparison<T>) / List<T>.Sort(Comparison<T>) leaves n elements in when the comparison looks at
  * an int32 key alone (ascending): perm[i] = original index of the element that ends up at position i.  That sort is not stable,

@@ -8,7 +8,7 @@ from . import sharding  # noqa: F401
 from .batch import FMT_EXTENDED_U16, FMT_INTERLEAVED_U8, FMT_INTERLEAVED_U8_SCALED, FMT_PLANAR_I16, FMT_PLANAR_U8, FMT_RGB_PLANAR_F16, FMT_RGB_PLANAR_F32, FMT_RGB_PLANAR_U8, FMT_RGB_U8, FMT_RGBA_U8, Batch, affine_from_mean_std, decode_batch, decode_resized, decode_to_tensors, identify_color, identify_orientation
 from .context import Context, default_context, device_count
 from .encoder import EncodeBatch, encode_batch, encode_tensors
-from .optimizer import JpegOptimizer, OptimizeBatch, build_optimal_huffman_table, optimize_batch
+from .optimizer import JpegOptimizer, OptimizeBatch, TransformPlan, build_optimal_huffman_table, optimize_batch, plan_transform
 from .decoder import (JpegBlockOutputWriter, JpegBufferOutputWriter8Bit, JpegBufferOutputWriterGreaterThan8Bit, JpegBufferOutputWriterLessThan8Bit, JpegDecoder, JpegExtendingOutputWriter, JpegFrameComponentSpecificationParameters,
                       JpegFrameHeader, JpegGpuProgressiveScanDecoder, JpegHuffmanDecodingTable, JpegScanComponentSpecificationParameters, JpegScanHeader)
 from .jpeg_encoder import (JpegBufferInputReader, JpegEncoder, JpegHuffmanCanonicalCode, JpegHuffmanEncodingTable, JpegHuffmanEncodingTableBuilder, JpegQuantizationTable, JpegStandardHuffmanEncodingTable,
@@ -19,7 +19,7 @@ from .errors import (ArgumentException, DeviceError, InvalidDataException, Inval
 
 __all__ = [
     "Batch", "decode_batch", "decode_to_tensors", "decode_resized", "MultiDecoder", "JpegEncoder", "JpegQuantizationTable", "JpegStandardQuantizationTable", "JpegHuffmanEncodingTable", "JpegHuffmanCanonicalCode", "JpegHuffmanEncodingTableBuilder",
-    "JpegStandardHuffmanEncodingTable", "JpegBufferInputReader", "EncodeBatch", "encode_batch", "encode_tensors", "JpegOptimizer", "OptimizeBatch", "optimize_batch", "build_optimal_huffman_table", "Context", "default_context", "device_count", "JpegDecoder", "JpegBlockOutputWriter",
+    "JpegStandardHuffmanEncodingTable", "JpegBufferInputReader", "EncodeBatch", "encode_batch", "encode_tensors", "JpegOptimizer", "OptimizeBatch", "optimize_batch", "build_optimal_huffman_table", "plan_transform", "TransformPlan", "Context", "default_context", "device_count", "JpegDecoder", "JpegBlockOutputWriter",
     "JpegBufferOutputWriter8Bit", "JpegExtendingOutputWriter", "JpegFrameHeader", "JpegFrameComponentSpecificationParameters", "JpegScanHeader",
     "JpegScanComponentSpecificationParameters", "JpegHuffmanDecodingTable", "JpegGpuProgressiveScanDecoder", "FMT_INTERLEAVED_U8", "FMT_PLANAR_U8", "FMT_PLANAR_I16", "FMT_RGB_U8", "FMT_RGBA_U8", "FMT_EXTENDED_U16",
     "FMT_INTERLEAVED_U8_SCALED", "FMT_RGB_PLANAR_U8", "FMT_RGB_PLANAR_F16", "FMT_RGB_PLANAR_F32", "affine_from_mean_std", "identify_color", "identify_orientation", "JpegBufferOutputWriterGreaterThan8Bit", "JpegBufferOutputWriterLessThan8Bit",

@@ -104,6 +104,11 @@ class DeviceIngestStats(C.Structure):
 DEVICE_HEAD_PAD = 64  # JPGPU_DEVICE_HEAD_PAD
 
 
+class TransformInfo(C.Structure):
+    _fields_ = [("orientation", C.c_int32), ("trimmed", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32), ("num_components", C.c_uint32),
+                ("h", C.c_uint8 * 4), ("v", C.c_uint8 * 4), ("reserved", C.c_uint32)]
+
+
 class Rect(C.Structure):
     """jpgpu_rect: a window in pixels of the frame; {0, 0, 0, 0} = the whole frame"""
     _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32)]
@@ -318,6 +323,13 @@ SYMBOLS = [
     ("jpgpu_net_sort_permutation", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     ("jpgpu_build_optimal_huffman_table", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     ("jpgpu_optimizer_set_most_optimal_coding", C.c_int, [_P, C.c_int]),
+    ("jpgpu_sizeof_transform_info", C.c_size_t, []),
+    ("jpgpu_optimizer_set_orientation_policy", C.c_int, [_P, C.c_int]),
+    ("jpgpu_optimizer_set_orientations", C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int]),
+    ("jpgpu_optimizer_set_edge_policy", C.c_int, [_P, C.c_int]),
+    ("jpgpu_optimizer_image_transform", C.c_int, [_P, C.c_int, C.POINTER(TransformInfo)]),
+    ("jpgpu_optimizer_turn_ms", C.c_int, [_P, C.POINTER(C.c_float * 3)]),
+    ("jpgpu_transform_plan", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(TransformInfo), C.c_char_p, C.c_size_t]),
 ]
 
 

@@ -1598,6 +1598,40 @@ int jpgpu_optimizer_last_ms(const jpgpu_optimizer *opt, float *ms) {
     *ms = opt->impl.last_ms();
     return JPGPU_OK;
 }
+// the lossless transform (include/jpgpu.h section (5), "Lossless transform")
+size_t jpgpu_sizeof_transform_info(void) { return sizeof(jpgpu_transform_info); }
+int jpgpu_optimizer_set_orientation_policy(jpgpu_optimizer *opt, int policy) { JPGPU_GUARD(opt, opt->impl.set_orientation_policy(policy)); }
+int jpgpu_optimizer_set_orientations(jpgpu_optimizer *opt, const uint8_t *orientations, int n) {
+    JPGPU_GUARD(opt, opt->impl.set_orientations(orientations, n));
+}
+int jpgpu_optimizer_set_edge_policy(jpgpu_optimizer *opt, int edge) { JPGPU_GUARD(opt, opt->impl.set_edge_policy(edge)); }
+int jpgpu_optimizer_image_transform(const jpgpu_optimizer *opt, int i, jpgpu_transform_info *info) {
+    return opt ? opt->impl.image_transform(i, info) : JPGPU_ERR_ARGUMENT;
+}
+int jpgpu_optimizer_turn_ms(const jpgpu_optimizer *opt, float *ms) {
+    if (!opt || !ms) return JPGPU_ERR_ARGUMENT;
+    opt->impl.last_turn_ms(ms);
+    return JPGPU_OK;
+}
+// Host only: the headers up to the first SOS, the orientation rule, the edge policy
+int jpgpu_transform_plan(const uint8_t *file, size_t len, int orientation, int policy, int edge, jpgpu_transform_info *info, char *message, size_t message_cap) {
+    if (!file || !info || orientation < 0 || orientation > 8 || (policy != JPGPU_ORIENT_STORED && policy != JPGPU_ORIENT_FILE) ||
+        (edge != JPGPU_EDGE_REFUSE && edge != JPGPU_EDGE_TRIM))
+        return JPGPU_ERR_ARGUMENT;
+    try {
+        TransformPlan plan;
+        const int rc = plan_transform(file, len, orientation, policy, edge, &plan);
+        transform_info_of(plan, info);
+        if (message && message_cap) {
+            const size_t n = std::min(plan.message.size(), message_cap - 1);
+            memcpy(message, plan.message.data(), n);
+            message[n] = 0;
+        }
+        return rc != JPGPU_OK ? rc : plan.status;
+    } catch (const std::exception &) {
+        return JPGPU_ERR_OUT_OF_MEMORY;
+    }
+}
 int jpgpu_net_sort_permutation(const int32_t *keys, int n, int32_t *perm) {
     if (n < 0 || (n > 0 && (!keys || !perm))) return JPGPU_ERR_ARGUMENT;
     net_sort_permutation(keys, n, perm);

@@ -345,10 +345,12 @@ void optimal_codes_to_table(const std::vector<OptimalCode> &codes, EncHuffTable 
 OptimizeBatch::~OptimizeBatch() {
     for (DevBuffer *b : {&d_work_, &d_scan_ids_, &d_hist_, &d_enc_, &d_sizes_, &d_offsets_, &d_base_, &d_totals_, &d_out_, &d_sub_work_,
                          &d_sub_scan_ids_, &d_sub_bits_, &d_sub_bitoff_, &d_sub_totals_, &d_scan_raw_off_, &d_raw_, &d_simages_, &d_swork_chunk_,
-                         &d_chunk_ff_, &d_sout_, &d_sout_len_})
+                         &d_chunk_ff_, &d_sout_, &d_sout_len_, &d_turn_images_, &d_turn_work_, &d_tcoefs_, &d_timages_, &d_tlayouts_, &d_twork_blk_,
+                         &d_twork_stat_, &d_thist_, &d_ttables_, &d_tbits_, &d_tbit_off_, &d_traw_bits_, &d_traw_, &d_tmarks_, &d_tchunk_ff_,
+                         &d_twork_chunk_, &d_tout_, &d_tout_len_})
         b->release();
-    if (ev0_) (void)hipEventDestroy(ev0_);
-    if (ev1_) (void)hipEventDestroy(ev1_);
+    for (hipEvent_t ev : {ev0_, ev1_, ev_kx0_, ev_kx1_, ev_td_[0], ev_td_[1], ev_td_[2]})
+        if (ev) (void)hipEventDestroy(ev);
 }
 int OptimizeBatch::fail(int status, const std::string &msg) {
     ctx_->last_error = msg;
@@ -380,7 +382,7 @@ size_t OptimizeBatch::scan_end(const uint8_t *entropy, size_t len) {
 
 // Scan()'s and Optimize()'s marker walks (JpegOptimizer.cs:66-153, :540-648) on the host.  Leaves the pieces of the
 // output in p.pieces; the scan itself is located for the device passes.
-void OptimizeBatch::plan_file(Plan &p, const uint8_t *data, size_t len, bool strip, bool swallow_terminator) {
+void OptimizeBatch::plan_file(Plan &p, const uint8_t *data, size_t len, bool strip, bool swallow_terminator, bool turned) {
     // ---- Scan(): tables, frame, restart interval as of the scan; exactly one scan
     std::vector<QuantTable> quant;  // _quantizationTables: replace by identifier, else append (:319-338)
     bool after_scan = false;  // from here on a failure of the walks is only met once the scan itself went through
@@ -584,7 +586,9 @@ void OptimizeBatch::plan_file(Plan &p, const uint8_t *data, size_t len, bool str
                 const uint64_t mcus = (uint64_t)((frame.samples_per_line + 8 * max_h - 1) / (8 * max_h)) * ((frame.lines + 8 * max_v - 1) / (8 * max_v));
                 const uint64_t intervals = dri_at_scan ? (mcus + dri_at_scan - 1) / dri_at_scan : 1;
                 p.rsts_in_scan = end_rsts_.size();
-                for (size_t k = (size_t)intervals; k < end_rsts_.size(); k++) put_marker(cur, (uint8_t)end_rsts_[k]);
+                // (a turned image: `data` is F' with the SOURCE's scan still behind its header; the scan of F' itself is written
+                // from the turned blocks and holds exactly the markers its intervals need)
+                for (size_t k = (size_t)intervals; !turned && k < end_rsts_.size(); k++) put_marker(cur, (uint8_t)end_rsts_[k]);
             }
             r.try_advance((int)end + (swallow_terminator && end < (size_t)r.remaining_byte_count() ? 1 : 0));
             break;
@@ -620,11 +624,19 @@ void OptimizeBatch::plan_file(Plan &p, const uint8_t *data, size_t len, bool str
 
 int OptimizeBatch::upload(const uint8_t *const *jpeg, const size_t *len, int n, int strip) {
     if (n < 0 || (n > 0 && (!jpeg || !len))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_upload: bad arguments");
-    plans_.assign((size_t)n, Plan());
+    plans_.clear();
     ran_ = false;
+    std::vector<uint8_t> given;  // the orientations of THIS upload (empty: every image by the policy)
+    given.swap(pending_orientations_);
+    const bool with_list = orientations_pending_;
+    orientations_pending_ = false;
+    if (with_list && (int)given.size() != n)
+        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_upload: the upload's n differs from the orientations' n (jpgpu_optimizer_set_orientations)");
+    plans_.assign((size_t)n, Plan());
     for (int i = 0; i < n; i++) {
         try {
             plan_file(plans_[i], jpeg[i], len[i], strip != 0);
+            plan_turned_image(plans_[i], jpeg[i], len[i], strip != 0, with_list ? given[(size_t)i] : 0);
         } catch (const Refuse &e) {
             plans_[i].status = e.status;
             plans_[i].detail = e.detail;
@@ -673,6 +685,7 @@ int OptimizeBatch::upload(const uint8_t *const *jpeg, const size_t *len, int n, 
     work_.clear();
     sub_scan_ids_.clear();
     sub_work_.clear();
+    std::vector<HuffWork> counted_only, sub_counted_only;  // the turned images: Scan()'s pass decides their status, nothing of it is emitted
     for (int i = 0; i < n; i++) {
         Plan &p = plans_[i];
         if (p.status != JPGPU_OK) continue;
@@ -700,14 +713,30 @@ int OptimizeBatch::upload(const uint8_t *const *jpeg, const size_t *len, int n, 
         }
         p.by_subsequence = s.n_subs != 0;  // the batch marks DRI = 0 scans for the self-synchronising subsequence machinery
                                            // (not those with RSTn markers in the data: upload() asks for the interval path)
+        const bool turned = p.transform.orientation != 1;
+        if (!turned) {  // (jpgpu_optimizer_image_transform: the frame as it is)
+            const ScanJob &job = batch_.jobs_[p.job];
+            p.transform.out_width = img->width;
+            p.transform.out_height = img->height;
+            p.transform.ncomp = std::min<int>(4, (int)job.geo.frame.components.size());
+            for (int c = 0; c < p.transform.ncomp; c++) {
+                p.transform.h[c] = job.geo.frame.components[(size_t)c].h;
+                p.transform.v[c] = job.geo.frame.components[(size_t)c].v;
+            }
+        }
         if (p.by_subsequence) {
-            sub_scan_ids_.push_back((uint32_t)p.job);
-            for (uint32_t first = 0; first < s.n_subs; first += 256) sub_work_.push_back({(uint32_t)p.job, first});
+            if (!turned) sub_scan_ids_.push_back((uint32_t)p.job);
+            for (uint32_t first = 0; first < s.n_subs; first += 256) (turned ? sub_counted_only : sub_work_).push_back({(uint32_t)p.job, first});
         } else {
-            scan_ids_.push_back((uint32_t)p.job);
-            for (uint32_t first = 0; first < s.n_intervals; first += 256) work_.push_back({(uint32_t)p.job, first});
+            if (!turned) scan_ids_.push_back((uint32_t)p.job);
+            for (uint32_t first = 0; first < s.n_intervals; first += 256) (turned ? counted_only : work_).push_back({(uint32_t)p.job, first});
         }
     }
+    n_work_emit_ = (int)work_.size();
+    n_sub_work_emit_ = (int)sub_work_.size();
+    work_.insert(work_.end(), counted_only.begin(), counted_only.end());
+    sub_work_.insert(sub_work_.end(), sub_counted_only.begin(), sub_counted_only.end());
+    if ((rc = upload_turned(jpeg, len)) != JPGPU_OK) return rc;
     struct Up {
         DevBuffer *buf;
         const void *src;
@@ -746,7 +775,11 @@ int OptimizeBatch::upload(const uint8_t *const *jpeg, const size_t *len, int n, 
 // what run()'s stages hand one another
 struct OptimizeBatch::Run {
     size_t n_jobs = 0;
-    int n_work = 0, n_scans = 0, n_sub_work = 0, n_sub_scans = 0, n_slots = 0;
+    int n_work = 0, n_scans = 0, n_sub_work = 0, n_sub_scans = 0, n_slots = 0;  // (work: what is measured and emitted ...
+    int n_work_counted = 0, n_sub_work_counted = 0;                             // ... and what is counted: the turned images' too)
+    int n_turned = 0;
+    const int16_t *turn_src = nullptr;  // the dense store of turn_batch_
+    std::vector<uint64_t> traw_bits;    // per turned image
     const uint8_t *udata = nullptr, *input = nullptr;
     const DevScan *scans = nullptr;
     DevScanStatus *status = nullptr;
@@ -761,16 +794,23 @@ struct OptimizeBatch::Run {
 int OptimizeBatch::run() {
     ran_ = false;
     if (!ev0_) {
-        if (hipEventCreate(&ev0_) != hipSuccess || hipEventCreate(&ev1_) != hipSuccess) return fail(JPGPU_ERR_DEVICE, "hipEventCreate");
+        if (hipEventCreate(&ev0_) != hipSuccess || hipEventCreate(&ev1_) != hipSuccess || hipEventCreate(&ev_kx0_) != hipSuccess ||
+            hipEventCreate(&ev_kx1_) != hipSuccess || hipEventCreate(&ev_td_[0]) != hipSuccess || hipEventCreate(&ev_td_[1]) != hipSuccess ||
+            hipEventCreate(&ev_td_[2]) != hipSuccess)
+            return fail(JPGPU_ERR_DEVICE, "hipEventCreate");
     }
     (void)hipEventRecord(ev0_, ctx_->stream);
     int rc = batch_.run_marker_index();
     if (rc != JPGPU_OK) return rc;
     Run r;
     r.n_jobs = batch_.h_scans_.size();
-    r.n_work = (int)work_.size();
+    r.n_work = n_work_emit_;
+    r.n_work_counted = (int)work_.size();
     r.n_scans = (int)scan_ids_.size();
-    r.n_sub_work = (int)sub_work_.size();
+    r.n_sub_work = n_sub_work_emit_;
+    r.n_sub_work_counted = (int)sub_work_.size();
+    r.n_turned = (int)timages_.size();
+    last_turn_ms_ = last_turn_decode_ms_ = last_turn_dense_ms_ = 0;
     r.n_sub_scans = (int)sub_scan_ids_.size();
     r.n_slots = batch_.n_huff_slots_;
     r.udata = (const uint8_t *)batch_.d_unstuffed_.ptr;
@@ -785,10 +825,21 @@ int OptimizeBatch::run() {
     if ((rc = measure_and_place(r)) != JPGPU_OK) return rc;
     if ((rc = emit_intervals(r)) != JPGPU_OK) return rc;
     if (r.n_sub_scans && (rc = emit_subsequences_and_stuff(r)) != JPGPU_OK) return rc;
+    if (r.n_turned) {
+        if ((rc = decode_turned(r)) != JPGPU_OK) return rc;
+        if ((rc = turn_blocks(r)) != JPGPU_OK) return rc;
+        if ((rc = build_turned_tables(r)) != JPGPU_OK) return rc;
+        if ((rc = emit_turned(r)) != JPGPU_OK) return rc;
+    }
     (void)hipEventRecord(ev1_, ctx_->stream);
     hipError_t e = hipStreamSynchronize(ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     (void)hipEventElapsedTime(&last_ms_, ev0_, ev1_);
+    if (r.n_turned) {
+        (void)hipEventElapsedTime(&last_turn_ms_, ev_kx0_, ev_kx1_);
+        (void)hipEventElapsedTime(&last_turn_decode_ms_, ev_td_[0], ev_td_[1]);
+        (void)hipEventElapsedTime(&last_turn_dense_ms_, ev_td_[1], ev_td_[2]);
+    }
     collect_lengths(r);
     ran_ = true;
     return JPGPU_OK;
@@ -798,14 +849,14 @@ int OptimizeBatch::run() {
 int OptimizeBatch::count_symbols(Run &r) {
     hipError_t e = hipMemsetAsync(d_hist_.ptr, 0, r.n_jobs * kMaxHuffSlots * 256 * sizeof(uint32_t), ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(histograms)");
-    e = launch_transcode(ctx_->stream, 0, r.udata, r.input, r.scans, (const HuffWork *)d_work_.ptr, r.n_work, r.ends_u, r.ends_raw, r.status, r.pool,
+    e = launch_transcode(ctx_->stream, 0, r.udata, r.input, r.scans, (const HuffWork *)d_work_.ptr, r.n_work_counted, r.ends_u, r.ends_raw, r.status, r.pool,
                          (uint32_t *)d_hist_.ptr, nullptr, nullptr, nullptr, nullptr, r.n_slots);
     if (e != hipSuccess) return hip_fail(e, "transcode_kernel<count>");
     // scans without restart intervals: the decoder's self-synchronising subsequences, then the same three passes per subsequence
-    if (r.n_sub_scans) {
+    if (r.n_sub_work_counted) {
         const int rc = batch_.run_subseq_sync(&r.exit_state, &r.first_block);
         if (rc != JPGPU_OK) return rc;
-        e = launch_subseq_transcode(ctx_->stream, 0, r.udata, r.scans, (const HuffWork *)d_sub_work_.ptr, r.n_sub_work, r.ends_u, r.status, r.pool, r.exit_state,
+        e = launch_subseq_transcode(ctx_->stream, 0, r.udata, r.scans, (const HuffWork *)d_sub_work_.ptr, r.n_sub_work_counted, r.ends_u, r.status, r.pool, r.exit_state,
                                     r.first_block, (uint32_t *)d_hist_.ptr, nullptr, nullptr, nullptr, nullptr, nullptr, r.n_slots);
         if (e != hipSuccess) return hip_fail(e, "subseq_transcode_kernel<count>");
     }
@@ -954,7 +1005,10 @@ void OptimizeBatch::collect_lengths(const Run &r) {
     int k = 0, ks = 0;
     for (Plan &p : plans_) {
         if (p.status != JPGPU_OK || p.job < 0) continue;
-        if (p.by_subsequence) {
+        if (p.transform.orientation != 1) {  // a turned image: the encoder's stuffing stage has closed its stream with EOI, too
+            p.entropy_off = timages_[(size_t)p.turn].out_off;
+            p.entropy_len = tout_len_[(size_t)p.turn] >= 2 ? tout_len_[(size_t)p.turn] - 2 : 0;
+        } else if (p.by_subsequence) {
             p.entropy_off = r.simages[ks].out_off;
             p.entropy_len = r.sout_len[ks] >= 2 ? r.sout_len[ks] - 2 : 0;  // the stuffing stage closes with EOI: that belongs to the host pieces here
             ks++;
@@ -967,6 +1021,344 @@ void OptimizeBatch::collect_lengths(const Run &r) {
         for (const Piece &pc : p.pieces)
             p.out_len += pc.kind == Piece::kBytes ? pc.bytes.size() : (pc.kind == Piece::kHuffmanTables ? p.dht.size() : p.entropy_len);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ lossless transform
+// (include/jpgpu.h section (5), "Lossless transform")
+
+int OptimizeBatch::set_orientation_policy(int policy) {
+    if (policy != JPGPU_ORIENT_STORED && policy != JPGPU_ORIENT_FILE) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_set_orientation_policy: unknown policy");
+    orient_policy_ = policy;
+    return JPGPU_OK;
+}
+int OptimizeBatch::set_orientations(const uint8_t *orientations, int n) {
+    if (n < 0 || (n > 0 && !orientations)) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_set_orientations: bad argument");
+    for (int i = 0; i < n; i++)
+        if (orientations[i] > 8) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_set_orientations: an orientation is 1..8, or 0 for what the policy gives");
+    pending_orientations_.assign(orientations, orientations + n);
+    orientations_pending_ = n > 0;
+    return JPGPU_OK;
+}
+int OptimizeBatch::set_edge_policy(int edge) {
+    if (edge != JPGPU_EDGE_REFUSE && edge != JPGPU_EDGE_TRIM) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_set_edge_policy: unknown policy");
+    edge_policy_ = edge;
+    return JPGPU_OK;
+}
+int OptimizeBatch::image_transform(int i, jpgpu_transform_info *info) const {
+    if (i < 0 || i >= (int)plans_.size() || !info) return JPGPU_ERR_ARGUMENT;
+    transform_info_of(plans_[(size_t)i].transform, info);
+    return JPGPU_OK;
+}
+
+// The host side of a turned image: its plan, and the pieces of Optimize(strip) over F' -- the source with the SOF, DQT and Exif patches.
+// An image whose orientation is 1 is never touched: with nothing set (no list, the STORED policy) or a 1 in the list the file is not even
+// looked at, and a file whose headers plan_transform cannot walk is not turned -- it keeps whatever the optimizer's own walks make of it.
+void OptimizeBatch::plan_turned_image(Plan &p, const uint8_t *data, size_t len, bool strip, int given) {
+    TransformPlan &tp = p.transform;
+    tp = TransformPlan();
+    if (given == 1 || (given == 0 && orient_policy_ == JPGPU_ORIENT_STORED)) return;
+    if (plan_transform(data, len, given, orient_policy_, edge_policy_, &tp) != JPGPU_OK) {
+        tp = TransformPlan();
+        return;
+    }
+    if (tp.orientation == 1) return;
+    if (tp.status != JPGPU_OK) refuse(tp.status, tp.message, kDetailUnsupportedFrame);
+    std::string f((const char *)data, len);
+    uint8_t *b = (uint8_t *)&f[0];
+    patch_turned_file(b, len, tp);
+    Plan turned;
+    end_key_ = nullptr;
+    plan_file(turned, b, len, strip, false, true);
+    end_key_ = nullptr;  // (the key is the address of a buffer that goes away here)
+    p.pieces = std::move(turned.pieces);
+}
+
+// The turned images of an upload: the files once more, as the decoder takes them, and the plans of KX and of the encoder's entropy stages
+int OptimizeBatch::upload_turned(const uint8_t *const *jpeg, const size_t *len) {
+    turned_.clear();
+    turn_images_.clear();
+    turn_work_.clear();
+    timages_.clear();
+    tlayouts_.clear();
+    twork_blk_.clear();
+    twork_stat_.clear();
+    turn_blocks_total_ = 0;
+    std::vector<const uint8_t *> files;
+    std::vector<size_t> lens;
+    for (size_t i = 0; i < plans_.size(); i++) {
+        Plan &p = plans_[i];
+        p.turn = -1;
+        if (p.status != JPGPU_OK || p.job < 0 || p.transform.orientation == 1) continue;
+        turned_.push_back((int)i);
+        files.push_back(jpeg[i]);
+        lens.push_back(len[i]);
+    }
+    if (turned_.empty()) {  // nothing of an earlier upload's turned images stays on the device
+        turn_batch_.reset();
+        for (DevBuffer *b : {&d_turn_images_, &d_turn_work_, &d_tcoefs_, &d_timages_, &d_tlayouts_, &d_twork_blk_, &d_twork_stat_, &d_thist_, &d_ttables_,
+                             &d_tbits_, &d_tbit_off_, &d_traw_bits_, &d_traw_, &d_tmarks_, &d_tchunk_ff_, &d_twork_chunk_, &d_tout_, &d_tout_len_})
+            b->release();
+        return JPGPU_OK;
+    }
+    if (!turn_batch_) turn_batch_.reset(new DeviceBatch(ctx_));
+    int rc = turn_batch_->upload_files(files.data(), lens.data(), (int)files.size(), JPGPU_FMT_PLANAR_U8);
+    if (rc != JPGPU_OK) return rc;
+    for (size_t k = 0; k < turned_.size(); k++) {
+        Plan &p = plans_[(size_t)turned_[k]];
+        const TransformPlan &tp = p.transform;
+        const ScanJob &job = batch_.jobs_[p.job];  // (the optimizer's view of the scan: its table slots are the builders' order)
+        const ImagePlan *img = turn_batch_->image((int)k);
+        const auto refuse_image = [&](const std::string &msg) {
+            p.status = JPGPU_ERR_NOT_SUPPORTED;
+            p.detail = kDetailUnsupportedFrame;
+            p.error = msg;
+            p.pieces.clear();
+        };
+        if (img->status != JPGPU_OK) {
+            p.status = img->status;
+            p.detail = img->detail;
+            p.error = img->error;
+            p.pieces.clear();
+            continue;
+        }
+        uint32_t bpm = 0;
+        for (int c = 0; c < tp.ncomp; c++) bpm += (uint32_t)tp.h[c] * tp.v[c];
+        bool expressible = img->jobs.size() == 1 && turn_batch_->jobs_[img->jobs[0]].kind == kScanSequential && job.scan_components == tp.ncomp &&
+                           img->mcus_per_line == tp.src_mcus_per_line && img->mcus_per_column == tp.src_mcus_per_column && img->blocks_per_mcu == bpm &&
+                           img->total_blocks == (uint64_t)tp.src_mcus_per_line * tp.src_mcus_per_column * bpm && job.n_huff <= 8;
+        for (int c = 0; expressible && c < tp.ncomp; c++)
+            expressible = job.comp[c].h == tp.h[c] && job.comp[c].v == tp.v[c] && job.dc_slot[c] < 8 && job.ac_slot[c] < 8;
+        if (!expressible) {
+            refuse_image("The arrangement of this scan cannot be turned.");
+            continue;
+        }
+        const bool tr = tp.transposes();
+        DevTurnImage g;
+        memset(&g, 0, sizeof g);
+        DevEncImage im;
+        memset(&im, 0, sizeof im);
+        DevEncLayout L;
+        memset(&L, 0, sizeof L);
+        g.src_off = img->coef_offset;
+        g.dst_off = turn_blocks_total_;
+        g.orientation = (uint32_t)tp.orientation;
+        g.bpm = bpm;
+        g.src_mcus_per_line = tp.src_mcus_per_line;
+        g.kept_mcus_per_line = tp.kept_mcus_per_line;
+        g.kept_mcus_per_column = tp.kept_mcus_per_column;
+        g.dst_mcus_per_line = tr ? tp.kept_mcus_per_column : tp.kept_mcus_per_line;
+        g.dst_mcus_per_column = tr ? tp.kept_mcus_per_line : tp.kept_mcus_per_column;
+        g.total_blocks = g.dst_mcus_per_line * g.dst_mcus_per_column * bpm;
+        L.ncomp = (uint32_t)tp.ncomp;
+        L.max_h = tr ? tp.max_v : tp.max_h;
+        L.max_v = tr ? tp.max_h : tp.max_v;
+        L.own_blocks = 1;  // (statistics are taken; the grids below are the whole MCU grid, so no block is the allocator's dummy)
+        L.table_base = (uint32_t)(8 * timages_.size());
+        L.hist_index = (uint32_t)(8 * 256 * timages_.size());
+        uint32_t b = 0;
+        for (int c = 0; c < tp.ncomp; c++) {
+            const uint32_t h = tr ? tp.v[c] : tp.h[c], v = tr ? tp.h[c] : tp.v[c];
+            g.src_h[c] = tp.h[c];
+            g.src_v[c] = tp.v[c];
+            g.first_blk[c] = (uint8_t)b;
+            L.h[c] = (uint8_t)h;
+            L.v[c] = (uint8_t)v;
+            L.hs[c] = (uint8_t)(L.max_h / h);
+            L.vs[c] = (uint8_t)(L.max_v / v);
+            L.dc_slot[c] = job.dc_slot[c];
+            L.ac_slot[c] = job.ac_slot[c];
+            L.first_blk[c] = (uint8_t)b;
+            L.grid_w[c] = g.dst_mcus_per_line * h;
+            L.grid_h[c] = g.dst_mcus_per_column * v;
+            for (uint32_t y = 0; y < v; y++)
+                for (uint32_t x = 0; x < h; x++) {
+                    g.blk[b] = (uint8_t)((uint32_t)c | x << 2 | y << 4);
+                    L.blk_comp[b] = (uint8_t)c;
+                    L.blk_x[b] = (uint8_t)x;
+                    L.blk_y[b] = (uint8_t)y;
+                    L.blk_info[b] = (uint32_t)c | (x << 2) | (y << 4) | (h << 6) | (v << 9) | ((uint32_t)job.dc_slot[c] << 12) | ((uint32_t)job.ac_slot[c] << 15) |
+                                    ((uint32_t)L.first_blk[c] << 18) | (((uint32_t)L.first_blk[c] + h * v - 1u) << 24);
+                    b++;
+                }
+        }
+        im.coef_off = g.dst_off;
+        im.width = tp.out_width;
+        im.height = tp.out_height;
+        im.components = (uint32_t)tp.ncomp;
+        im.luma_h = L.max_h;
+        im.luma_v = L.max_v;
+        im.mcus_per_line = g.dst_mcus_per_line;
+        im.mcus_per_column = g.dst_mcus_per_column;
+        im.bpm = bpm;
+        im.total_blocks = g.total_blocks;
+        im.restart_interval = (uint32_t)p.dri_at_scan;
+        const uint32_t mcus = im.mcus_per_line * im.mcus_per_column;
+        im.n_units = im.restart_interval ? (mcus + im.restart_interval - 1) / im.restart_interval : im.total_blocks;
+        im.work_first = (uint32_t)twork_blk_.size();
+        im.layout = (uint32_t)tlayouts_.size() + 1;
+        p.turn = (int)timages_.size();
+        for (uint32_t f = 0; f < g.total_blocks; f += kTurnBlocksPerWg) turn_work_.push_back({(uint32_t)p.turn, f});
+        for (uint32_t f = 0; f < im.n_units; f += 256) twork_blk_.push_back({(uint32_t)p.turn, f});
+        for (uint32_t f = 0; f < im.total_blocks; f += 256) twork_stat_.push_back({(uint32_t)p.turn, f});
+        turn_blocks_total_ += g.total_blocks;
+        turn_images_.push_back(g);
+        timages_.push_back(im);
+        tlayouts_.push_back(L);
+    }
+    struct Up {
+        DevBuffer *buf;
+        const void *src;
+        size_t bytes, reserve;
+    };
+    const size_t nt = timages_.size(), nw = twork_blk_.size();
+    const Up ups[] = {
+        {&d_turn_images_, turn_images_.data(), nt * sizeof(DevTurnImage), 0},
+        {&d_turn_work_, turn_work_.data(), turn_work_.size() * sizeof(TurnWork), 0},
+        {&d_tlayouts_, tlayouts_.data(), nt * sizeof(DevEncLayout), 0},
+        {&d_twork_blk_, twork_blk_.data(), nw * sizeof(EncWork), 0},
+        {&d_twork_stat_, twork_stat_.data(), twork_stat_.size() * sizeof(EncWork), 0},
+        {&d_timages_, nullptr, 0, nt * sizeof(DevEncImage) + 256},
+        {&d_tcoefs_, nullptr, 0, (size_t)turn_blocks_total_ * 128 + 256},
+        {&d_thist_, nullptr, 0, nt * 8 * 256 * sizeof(uint32_t) + 256},
+        {&d_ttables_, nullptr, 0, nt * 8 * sizeof(EncHuffTable) + 256},
+        {&d_tbits_, nullptr, 0, (size_t)turn_blocks_total_ * sizeof(uint32_t) + 256},
+        {&d_tbit_off_, nullptr, 0, ((nw * sizeof(uint64_t) + 255) & ~(size_t)255) + nw * sizeof(uint32_t) + 256},
+        {&d_traw_bits_, nullptr, 0, nt * sizeof(uint64_t) + 256},
+        {&d_tout_len_, nullptr, 0, nt * sizeof(uint64_t) + 256},
+    };
+    for (const Up &u : ups) {
+        hipError_t e = u.buf->reserve(std::max(u.bytes, u.reserve) + 16);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
+        if (u.bytes) {
+            e = hipMemcpyAsync(u.buf->ptr, u.src, u.bytes, hipMemcpyHostToDevice, ctx_->stream);
+            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(lossless transform plans)");
+        }
+    }
+    return JPGPU_OK;
+}
+
+// ---- the turned images: K1 + K2 of the decoder fill its coefficient store; KX reads it dense
+int OptimizeBatch::decode_turned(Run &r) {
+    (void)hipEventRecord(ev_td_[0], ctx_->stream);
+    turn_batch_->note_entropy_only_request();
+    int rc = turn_batch_->run_marker_index();
+    if (rc == JPGPU_OK) rc = turn_batch_->run_huffman();
+    (void)hipEventRecord(ev_td_[1], ctx_->stream);
+    // (what a reader of the store owes the batch, as jpgpu_batch_download_coefficients pays it: DRI = 0 scans are decoded in rounds whose
+    // count the host confirms here, issuing the stage again where they did not suffice)
+    if (rc == JPGPU_OK) rc = turn_batch_->sync();
+    if (rc != JPGPU_OK) return rc;
+    r.turn_src = (const int16_t *)turn_batch_->coefs_device(nullptr);  // (expands the scans K2 handed over as half-line planes)
+    (void)hipEventRecord(ev_td_[2], ctx_->stream);
+    if (!r.turn_src) return fail(JPGPU_ERR_DEVICE, "the dense coefficient store of the turned images is not available");
+    return JPGPU_OK;
+}
+
+// ---- KX: every block to its place in the turned grid, sign-flipped and transposed (kx_lossless.hip)
+int OptimizeBatch::turn_blocks(Run &r) {
+    (void)hipEventRecord(ev_kx0_, ctx_->stream);
+    hipError_t e = launch_lossless_turn(ctx_->stream, (const DevTurnImage *)d_turn_images_.ptr, (const TurnWork *)d_turn_work_.ptr, (int)turn_work_.size(), r.turn_src,
+                                        (int16_t *)d_tcoefs_.ptr);
+    (void)hipEventRecord(ev_kx1_, ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "lossless_turn_kernel");
+    return JPGPU_OK;
+}
+
+// ---- statistics of the turned blocks (the encoder's GatherBlockStatistics) and Build per (class, identifier) of the source's DHT
+int OptimizeBatch::build_turned_tables(Run &r) {
+    const size_t n_hist = (size_t)r.n_turned * 8 * 256;
+    hipError_t e = hipMemcpyAsync(d_timages_.ptr, timages_.data(), timages_.size() * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_thist_.ptr, 0, n_hist * sizeof(uint32_t), ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(turned statistics)");
+    e = launch_block_stats(ctx_->stream, (const DevEncImage *)d_timages_.ptr, (const EncWork *)d_twork_stat_.ptr, (int)twork_stat_.size(),
+                           (const int16_t *)d_tcoefs_.ptr, (uint32_t *)d_thist_.ptr, (const DevEncLayout *)d_tlayouts_.ptr, false);
+    if (e != hipSuccess) return hip_fail(e, "block_stats_kernel");
+    std::vector<uint32_t> hist(n_hist);
+    e = hipMemcpyAsync(hist.data(), d_thist_.ptr, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx_->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy(turned statistics)");
+    std::vector<EncHuffTable> enc(8 * (size_t)r.n_turned);
+    memset(enc.data(), 0, enc.size() * sizeof(EncHuffTable));
+    for (Plan &p : plans_) {
+        if (p.turn < 0) continue;
+        const ScanJob &job = batch_.jobs_[p.job];
+        std::vector<uint8_t> body;
+        for (int t = 0; t < job.n_huff; t++) {
+            std::vector<OptimalCode> codes;
+            const uint32_t *freq = &hist[((size_t)p.turn * 8 + t) * 256];
+            if (!build_optimal_table(freq, &codes, most_optimal_)) {  // (as build_tables reports it for the source's own statistics)
+                bool any = false;
+                for (int sym = 0; sym < 256; sym++) any |= freq[sym] != 0;
+                if (!p.build_failed) {
+                    p.build_failed = true;
+                    p.late_status = JPGPU_ERR_INVALID_OPERATION;
+                    p.late_detail = 0;
+                    p.late_error = any ? "Index was outside the bounds of the array." : "No symbol is recorded.";
+                }
+                continue;
+            }
+            body.push_back((uint8_t)(job.huff_copy[t].table_class << 4 | (job.huff_copy[t].identifier & 0xF)));
+            optimal_codes_to_table(codes, &enc[(size_t)p.turn * 8 + t], &body);
+        }
+        p.dht.clear();
+        put_marker(p.dht, 0xC4);
+        put_length(p.dht, (uint16_t)body.size());
+        p.dht.append(body.begin(), body.end());
+    }
+    e = hipMemcpyAsync(d_ttables_.ptr, enc.data(), enc.size() * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);  // (`enc` leaves scope)
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(turned encoding tables)");
+    return JPGPU_OK;
+}
+
+// ---- bits, emit and stuffing through the encoder's general kernels (E2, E3, E4); no header in front of the streams
+int OptimizeBatch::emit_turned(Run &r) {
+    const int n = r.n_turned, n_work = (int)twork_blk_.size();
+    const DevEncImage *images = (const DevEncImage *)d_timages_.ptr;
+    const DevEncLayout *layouts = (const DevEncLayout *)d_tlayouts_.ptr;
+    uint32_t *wg_bits = reinterpret_cast<uint32_t *>((uint8_t *)d_tbit_off_.ptr + (((size_t)n_work * sizeof(uint64_t) + 255) & ~(size_t)255));
+    hipError_t e = launch_block_bits(ctx_->stream, images, (const EncWork *)d_twork_blk_.ptr, n_work, (const EncHuffTable *)d_ttables_.ptr,
+                                     (const int16_t *)d_tcoefs_.ptr, (uint32_t *)d_tbits_.ptr, n, wg_bits, (uint64_t *)d_tbit_off_.ptr, (uint64_t *)d_traw_bits_.ptr,
+                                     layouts, false);
+    if (e != hipSuccess) return hip_fail(e, "block_bits_kernel");
+    r.traw_bits.assign((size_t)n, 0);
+    e = hipMemcpyAsync(r.traw_bits.data(), d_traw_bits_.ptr, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpy(turned bit counts)");
+    uint64_t emit_words = 0;  // E3's LDS buffer, by the encoder's rule (EncodeBatch::plan_stuffing)
+    for (int i = 0; i < n; i++) {
+        const uint64_t wgs = ((uint64_t)timages_[(size_t)i].n_units + 255) / 256;
+        const uint64_t avg_words = r.traw_bits[(size_t)i] / 32 / std::max<uint64_t>(wgs, 1) + 1;
+        if (avg_words <= kEmitLdsWordsMax) emit_words = std::max<uint64_t>(emit_words, 2 * avg_words);
+    }
+    const StuffPlan sp = plan_stuffing_layout(timages_.data(), r.traw_bits.data(), n, true);
+    const size_t raw_bytes = (size_t)sp.raw_bytes;
+    const struct {
+        DevBuffer *buf;
+        size_t bytes;
+    } grow[] = {{&d_traw_, raw_bytes + 256}, {&d_tmarks_, raw_bytes / 8 + 256}, {&d_tout_, (size_t)sp.out_bytes + 256},
+                {&d_tchunk_ff_, (size_t)sp.chunks * sizeof(uint32_t) + 256}, {&d_twork_chunk_, sp.work_chunk.size() * sizeof(EncWork) + 16}};
+    for (const auto &g : grow) {
+        e = g.buf->reserve(g.bytes);
+        if (e != hipSuccess) return hip_fail(e, "hipMalloc(turned streams)");
+    }
+    e = hipMemsetAsync(d_traw_.ptr, 0, raw_bytes + 256, ctx_->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_tmarks_.ptr, 0, raw_bytes / 8 + 256, ctx_->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_timages_.ptr, timages_.data(), (size_t)n * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_twork_chunk_.ptr, sp.work_chunk.data(), sp.work_chunk.size() * sizeof(EncWork), hipMemcpyHostToDevice, ctx_->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(turned stream descriptors)");
+    e = launch_emit(ctx_->stream, images, (const EncWork *)d_twork_blk_.ptr, n_work, (const EncHuffTable *)d_ttables_.ptr, (const int16_t *)d_tcoefs_.ptr,
+                    (const uint32_t *)d_tbits_.ptr, (const uint64_t *)d_tbit_off_.ptr, (const uint64_t *)d_traw_bits_.ptr, (uint8_t *)d_traw_.ptr,
+                    (uint32_t *)d_tmarks_.ptr, (uint32_t)std::min<uint64_t>((emit_words + 1023) & ~1023ull, kEmitLdsWordsMax), layouts, false);
+    if (e != hipSuccess) return hip_fail(e, "emit_kernel");
+    e = launch_stuff(ctx_->stream, images, (const EncWork *)d_twork_chunk_.ptr, (int)sp.work_chunk.size(), (const uint64_t *)d_traw_bits_.ptr,
+                     (const uint8_t *)d_traw_.ptr, (const uint32_t *)d_tmarks_.ptr, (uint32_t *)d_tchunk_ff_.ptr, (uint8_t *)d_tout_.ptr, (uint64_t *)d_tout_len_.ptr);
+    if (e != hipSuccess) return hip_fail(e, "stuff kernels");
+    tout_len_.assign((size_t)n, 0);
+    e = hipMemcpyAsync(tout_len_.data(), d_tout_len_.ptr, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);  // (`sp` leaves scope)
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(turned stream lengths)");
+    return JPGPU_OK;
 }
 
 int OptimizeBatch::result(int i, jpgpu_image_result *res, size_t *out_len) {
@@ -1008,6 +1400,15 @@ int OptimizeBatch::result(int i, jpgpu_image_result *res, size_t *out_len) {
             ctx_->last_error = p.late_error;
         }
     }
+    if (res->status == JPGPU_OK && p.turn >= 0) {
+        // the same restart check on F': a trimmed image has fewer MCUs than its source, and where their count is a multiple of DRI Scan() of
+        // F' returns before it builds its tables, as above
+        const DevEncImage &im = timages_[(size_t)p.turn];
+        if (im.restart_interval != 0 && (im.mcus_per_line * im.mcus_per_column) % im.restart_interval == 0) {
+            res->status = JPGPU_ERR_INVALID_OPERATION;
+            ctx_->last_error = "Operation is not valid due to the current state of the object.";
+        }
+    }
     if (res->status == JPGPU_OK && out_len) *out_len = (size_t)p.out_len;
     return JPGPU_OK;
 }
@@ -1029,7 +1430,7 @@ int OptimizeBatch::download(int i, void *dst, size_t cap) {
             memcpy(o, p.dht.data(), p.dht.size());
             o += p.dht.size();
         } else if (p.entropy_len) {
-            const uint8_t *src = (const uint8_t *)(p.by_subsequence ? d_sout_.ptr : d_out_.ptr) + p.entropy_off;
+            const uint8_t *src = (const uint8_t *)(p.turn >= 0 ? d_tout_.ptr : (p.by_subsequence ? d_sout_.ptr : d_out_.ptr)) + p.entropy_off;
             hipError_t e = hipMemcpy(o, src, (size_t)p.entropy_len, hipMemcpyDeviceToHost);
             if (e != hipSuccess) return hip_fail(e, "hipMemcpy(optimizer output)");
             o += p.entropy_len;

@@ -1,11 +1,14 @@
 // jpeglibrary_amd/csrc/device_optimize.h -- device-resident batch of JpegOptimizer runs (see device_optimize.cpp)
 #pragma once
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/jpgpu.h"
 #include "device_batch.h"
 #include "encode_kernels.h"
+#include "kx_lossless.h"
+#include "transform_plan.h"
 
 namespace jpgpu {
 
@@ -39,6 +42,17 @@ class OptimizeBatch {
     bool statistics(int i, int t, uint8_t *table_class, uint8_t *identifier, uint32_t counts[256]) const;
     float last_ms() const { return last_ms_; }
     void set_most_optimal_coding(bool on) { most_optimal_ = on; }  // JpegOptimizer.MostOptimalCoding
+    // The lossless transform: the policy and the edge policy are state of the optimizer, the list is consumed by the next upload
+    int set_orientation_policy(int policy);
+    int set_orientations(const uint8_t *orientations, int n);
+    int set_edge_policy(int edge);
+    int image_transform(int i, jpgpu_transform_info *info) const;
+    // of the last run (zeros: nothing was turned), HIP events all three: KX alone; the entropy decode in front of it; the dense copy
+    void last_turn_ms(float ms[3]) const {
+        ms[0] = last_turn_ms_;
+        ms[1] = last_turn_decode_ms_;
+        ms[2] = last_turn_dense_ms_;
+    }
 
   private:
     // Optimize()'s output is a fixed sequence of pieces: bytes known on the host, the new DHT segment, the scan's data
@@ -66,6 +80,10 @@ class OptimizeBatch {
         uint64_t entropy_off = 0, entropy_len = 0;
         bool by_subsequence = false;  // DRI = 0 scan: transcoded by subsequence (KTS), bytes in d_sout_
         uint64_t out_len = 0;
+        // the lossless transform: the image's plan (orientation 1: the image takes the road above and nothing below is read), and its
+        // place among the turned images of the upload (-1: not turned, or refused)
+        TransformPlan transform;
+        int turn = -1;
     };
     int fail(int status, const std::string &msg);
     int hip_fail(hipError_t e, const char *what);
@@ -77,7 +95,15 @@ class OptimizeBatch {
     int emit_intervals(Run &r);
     int emit_subsequences_and_stuff(Run &r);
     void collect_lengths(const Run &r);
-    void plan_file(Plan &p, const uint8_t *data, size_t len, bool strip, bool swallow_terminator = false);
+    // ... and of the turned images: entropy decode into the dense store, KX, statistics and tables, the encoder's entropy stages
+    int decode_turned(Run &r);
+    int turn_blocks(Run &r);
+    int build_turned_tables(Run &r);
+    int emit_turned(Run &r);
+    // turned: the file is F' (the source with its SOF / DQT / Exif patches), whose scan holds exactly the restart markers it needs
+    void plan_file(Plan &p, const uint8_t *data, size_t len, bool strip, bool swallow_terminator = false, bool turned = false);
+    void plan_turned_image(Plan &p, const uint8_t *data, size_t len, bool strip, int given);
+    int upload_turned(const uint8_t *const *jpeg, const size_t *len);
     size_t scan_end(const uint8_t *entropy, size_t len);
     const uint8_t *end_key_ = nullptr;
     size_t end_len_ = 0, end_val_ = 0;
@@ -85,6 +111,25 @@ class OptimizeBatch {
 
     jpgpu_ctx *ctx_;
     DeviceBatch batch_;
+    // the lossless transform: the turned files once more, as the decoder takes them (its entropy stage fills the dense store KX reads)
+    // (made by the first upload that turns something, released by the next one that turns nothing)
+    std::unique_ptr<DeviceBatch> turn_batch_;
+    int orient_policy_ = JPGPU_ORIENT_STORED, edge_policy_ = JPGPU_EDGE_REFUSE;
+    std::vector<uint8_t> pending_orientations_;
+    bool orientations_pending_ = false;
+    std::vector<int> turned_;                // images of the upload that are turned, in order
+    std::vector<DevTurnImage> turn_images_;  // ... their KX descriptors,
+    std::vector<TurnWork> turn_work_;
+    std::vector<DevEncImage> timages_;       // ... and what the encoder's general kernels need of them
+    std::vector<DevEncLayout> tlayouts_;
+    std::vector<EncWork> twork_blk_, twork_stat_;
+    uint64_t turn_blocks_total_ = 0;
+    int n_work_emit_ = 0, n_sub_work_emit_ = 0;  // entries of work_ / sub_work_ in front of the turned images' (which are only counted)
+    std::vector<uint64_t> tout_len_;
+    float last_turn_ms_ = 0, last_turn_decode_ms_ = 0, last_turn_dense_ms_ = 0;
+    hipEvent_t ev_kx0_ = nullptr, ev_kx1_ = nullptr, ev_td_[3] = {};
+    DevBuffer d_turn_images_, d_turn_work_, d_tcoefs_, d_timages_, d_tlayouts_, d_twork_blk_, d_twork_stat_, d_thist_, d_ttables_, d_tbits_, d_tbit_off_,
+        d_traw_bits_, d_traw_, d_tmarks_, d_tchunk_ff_, d_twork_chunk_, d_tout_, d_tout_len_;
     std::vector<Plan> plans_;
     std::vector<uint32_t> scan_ids_;   // jobs that are transcoded, one lane per restart interval ...
     std::vector<HuffWork> work_;

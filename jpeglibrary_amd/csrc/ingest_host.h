@@ -45,9 +45,12 @@ inline int color_kind_of(int precision, int num_components, const uint8_t *ids, 
 struct ExifMarker {
     bool seen = false;        // the first such APP1 has been read; later ones are not
     uint8_t orientation = 1;  // 1..8
+    size_t value_at = 0;      // a value that counts: its two bytes behind "Exif\0\0" ...
+    bool little = false;      // ... and their byte order (the optimizer's lossless transform rewrites them)
 };
-// t: the n bytes behind "Exif\0\0" (the TIFF header onwards).  Every read is checked against n.
-inline int exif_orientation_of(const uint8_t *t, size_t n) {
+// t: the n bytes behind "Exif\0\0" (the TIFF header onwards).  Every read is checked against n.  value_at / little (may be null): where the
+// two bytes of a value that counts stand in t, and their byte order (the optimizer's lossless transform rewrites them).
+inline int exif_orientation_of(const uint8_t *t, size_t n, size_t *value_at = nullptr, bool *little_endian = nullptr) {
     if (n < 8) return 1;
     const bool little = t[0] == 'I' && t[1] == 'I';
     if (!little && !(t[0] == 'M' && t[1] == 'M')) return 1;
@@ -63,14 +66,17 @@ inline int exif_orientation_of(const uint8_t *t, size_t n) {
         if (u16(e) != 0x0112) continue;
         if (u16(e + 2) != 3 || u32(e + 4) != 1) return 1;  // SHORT, count 1
         const uint32_t v = u16(e + 8);
-        return v >= 1 && v <= 8 ? (int)v : 1;
+        if (v < 1 || v > 8) return 1;
+        if (value_at) *value_at = e + 8;
+        if (little_endian) *little_endian = little;
+        return (int)v;
     }
     return 1;
 }
 inline void note_exif_marker(ExifMarker &m, int marker, const uint8_t *payload, size_t len) {
     if (m.seen || marker != 0xE1 || len < 6 || memcmp(payload, "Exif\0\0", 6) != 0) return;
     m.seen = true;
-    m.orientation = (uint8_t)exif_orientation_of(payload + 6, len - 6);
+    m.orientation = (uint8_t)exif_orientation_of(payload + 6, len - 6, &m.value_at, &m.little);
 }
 // Orientation o (1..8) over a stored frame of `width` x `height`: the size of the oriented frame, and the rectangle of the stored frame that
 // holds the pixels of a rectangle given in the oriented one (include/jpgpu.h: the table's (y, x) over the rectangle's corners).

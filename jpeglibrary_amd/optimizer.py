@@ -5,6 +5,7 @@
 i.e. the Huffman tables are rebuilt from the file's own symbol statistics and the scan is re-written symbol by symbol
 (no coefficients are reconstructed).  Single-scan baseline files; see include/jpgpu.h section (5).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -14,6 +15,30 @@ from .context import Context, default_context
 from .errors import raise_for_status
 
 _lib = _capi.lib
+
+ORIENT_STORED, ORIENT_FILE = 0, 1
+EDGE_REFUSE, EDGE_TRIM = 0, 1
+_POLICIES = {None: ORIENT_STORED, "stored": ORIENT_STORED, "file": ORIENT_FILE}
+_EDGES = {"refuse": EDGE_REFUSE, "trim": EDGE_TRIM}
+
+# what an image is turned by (include/jpgpu.h, "Lossless transform"): factors = [(h, v)] of the output, frame order
+TransformPlan = collections.namedtuple("TransformPlan", "orientation width height trimmed factors")
+
+
+def _policy(orientation):
+    if orientation not in _POLICIES:
+        raise ValueError("orientation is None, 'stored' or 'file' (a value per file goes into orientations=): %r" % (orientation,))
+    return _POLICIES[orientation]
+
+
+def _edge(edge):
+    if edge not in _EDGES:
+        raise ValueError("edge is 'refuse' or 'trim': %r" % (edge,))
+    return _EDGES[edge]
+
+
+def _plan_of(info):
+    return TransformPlan(info.orientation, info.width, info.height, bool(info.trimmed), [(info.h[c], info.v[c]) for c in range(info.num_components)])
 
 
 class OptimizeBatch:
@@ -31,6 +56,41 @@ class OptimizeBatch:
         """JpegOptimizer.MostOptimalCoding"""
         self._check(_lib.jpgpu_optimizer_set_most_optimal_coding(self._h, 1 if on else 0))
         return self
+
+    def set_orientation_policy(self, orientation):
+        """None / "stored" (the default): images stay as stored; "file": every image is turned the way its Exif block says."""
+        self._check(_lib.jpgpu_optimizer_set_orientation_policy(self._h, _policy(orientation)))
+        return self
+
+    def set_orientations(self, orientations):
+        """One value per file of the NEXT upload: 1..8 as given, 0 = what the policy gives; None or [] withdraws a pending list."""
+        values = [int(o) for o in (orientations or [])]
+        if any(o < 0 or o > 8 for o in values):
+            raise ValueError("an orientation is 1..8, or 0 for what the policy gives")
+        arr = (C.c_uint8 * max(1, len(values)))(*values)
+        self._check(_lib.jpgpu_optimizer_set_orientations(self._h, arr, len(values)))
+        return self
+
+    def set_edge_policy(self, edge):
+        """ "refuse" (the default; jpegtran -perfect) or "trim" (jpegtran -trim) for a mirrored axis that is no whole number of MCUs"""
+        self._check(_lib.jpgpu_optimizer_set_edge_policy(self._h, _edge(edge)))
+        return self
+
+    def transform(self, i) -> TransformPlan:
+        """What image i of the last upload was planned with."""
+        info = _capi.TransformInfo()
+        self._check(_lib.jpgpu_optimizer_image_transform(self._h, i, C.byref(info)))
+        return _plan_of(info)
+
+    def turn_ms(self) -> float:
+        """Device time of the turn kernel (KX) alone in the last run; 0 when nothing was turned."""
+        return self.turn_stage_ms()[0]
+
+    def turn_stage_ms(self):
+        """(KX alone, the entropy decode in front of it, the dense copy of split scans) of the last run, in ms; zeros when nothing was turned."""
+        ms = (C.c_float * 3)()
+        _lib.jpgpu_optimizer_turn_ms(self._h, C.byref(ms))
+        return tuple(ms)
 
     def upload(self, files, strip=True):
         n = len(files)
@@ -137,13 +197,42 @@ class JpegOptimizer:
             self._output.write(data)
 
 
-def optimize_batch(files, strip=True, ctx=None, most_optimal=False):
-    """One-call helper: the optimized bytes of every file (raises on the first failing file)."""
-    b = OptimizeBatch(ctx).set_most_optimal_coding(most_optimal).upload(files, strip).run()
+def optimize_batch(files, strip=True, ctx=None, most_optimal=False, orientation=None, orientations=None, edge="refuse"):
+    """One-call helper: the optimized bytes of every file (raises on the first failing file).  orientation="file" bakes every file's Exif
+    orientation into its coefficients, orientations=[...] turns file i by orientations[i] (1..8; 0 = by the policy); edge="trim" drops the
+    partial MCU column or row of a mirrored axis where the default refuses the image (include/jpgpu.h, "Lossless transform")."""
+    policy, edge_policy = _policy(orientation), _edge(edge)
+    if orientations is not None and len(orientations) != len(files):
+        raise ValueError("orientations holds one value per file")
+    b = OptimizeBatch(ctx)
     try:
+        b.set_most_optimal_coding(most_optimal)
+        if policy != ORIENT_STORED:
+            b.set_orientation_policy(orientation)
+        if edge_policy != EDGE_REFUSE:
+            b.set_edge_policy(edge)
+        if orientations is not None:
+            b.set_orientations(orientations)
+        b.upload(files, strip).run()
         return [b.output(i) for i in range(len(b))]
     finally:
         b.close()
+
+
+def plan_transform(file, orientation=None, orientations=None, edge="refuse") -> TransformPlan:
+    """Host only (no device): what optimize_batch([file], orientation=..., orientations=[...], edge=...) would turn the file by.  Raises
+    NotSupportedException with the refusal's text where the image would be refused."""
+    if orientations is not None and len(orientations) != 1:
+        raise ValueError("orientations holds one value per file")
+    given = int(orientations[0]) if orientations is not None else 0
+    if given < 0 or given > 8:
+        raise ValueError("an orientation is 1..8, or 0 for what the policy gives")
+    buf = np.frombuffer(bytes(file), dtype=np.uint8)
+    info = _capi.TransformInfo()
+    msg = C.create_string_buffer(512)
+    rc = _lib.jpgpu_transform_plan(buf.ctypes.data if buf.size else None, buf.size, given, _policy(orientation), _edge(edge), C.byref(info), msg, 512)
+    raise_for_status(rc, msg.value or b"jpgpu_transform_plan failed")
+    return _plan_of(info)
 
 
 def build_optimal_huffman_table(counts, most_optimal=False):
