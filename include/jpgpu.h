@@ -1178,7 +1178,39 @@ int jpgpu_optimizer_last_ms(const jpgpu_optimizer *o, float *ms);  /* device tim
  * only, no context, no device -- as jpgpu_encode_description_header does for the encoder: `orientation` 0 = by `policy`, 1..8 as given; the
  * return value is JPGPU_OK, the refusal (its text in message[message_cap], may be NULL), or the library's header error.  It reads the headers
  * up to the first SOS as described under "Orientation 1": a second scan is the upload's to refuse.
- *   Not covered: cropping, jpegtran's default of leaving an unmirrored strip at the edge, grey-scale conversion, the JpegOptimizer mirror. */
+ *   Window (what jpegtran -crop does).  jpgpu_optimizer_set_windows gives the NEXT upload one jpgpu_rect per file and is consumed by it, as
+ * the orientations are: n == 0 withdraws a pending list, an upload whose n differs is refused with JPGPU_ERR_ARGUMENT and leaves the optimizer
+ * empty.  {0, 0, 0, 0} means no window: with orientation 1 the file is then not looked at and keeps the transcode path, its bytes and its
+ * status.  Any other window -- the whole frame written out included -- takes the coefficient road, turned or not.
+ *     What the output is.  With F' the turned file as defined above (F itself where the applied orientation is 1), the output is
+ *   Optimize(strip) of a file F'' that differs from F' in two things.  Blocks: with (mw, mh) the MCU size of F' in pixels and the window
+ *   (x, y, w, h) in pixels of the frame of F' -- the turned frame, behind a trim, exactly as the decoder's windows are in pixels of the oriented
+ *   frame --, F'' holds the MCUs of F' from MCU column x / mw and MCU row y / mh on, ceil(w / mw) columns and ceil(h / mh) rows of them; every
+ *   block holds what it held in F', and where the window reaches the edge of F' its padding blocks come along as they are.  SOF: the size
+ *   becomes w x h.  Everything else is that of F': factors and DQT (transposed for 5..8), DRI (kept), the Exif rewrite, the Huffman rule,
+ *   everything behind the scan.  Statistics are taken from the blocks of F'' only.  Decoding F'' gives, sample for sample, the slice
+ *   [y, y + h) x [x, x + w) of the decode of F'.
+ *     Order.  The orientation and the edge policy are resolved on the whole frame first, exactly as without a window: a mirrored axis that is
+ *   no whole number of MCUs still refuses or trims the image, even if the window would leave that edge out.  Then the window is applied.
+ *     Origin.  x must be a multiple of mw and y a multiple of mh.  Under JPGPU_ORIGIN_REFUSE (the default; jpegtran -perfect) a window that
+ *   breaks this refuses that image alone with JPGPU_ERR_NOT_SUPPORTED and a message naming the coordinate and the MCU size; under
+ *   JPGPU_ORIGIN_EXPAND (jpegtran's default) x drops to the multiple below and w grows by the difference, y and h likewise.  w and h are free.
+ *   jpgpu_optimizer_set_origin_policy is state of the optimizer; JPGPU_ERR_ARGUMENT for another value.
+ *     Refusals.  A window that does not lie inside the frame of F', or with exactly one of w, h zero, fails that image alone with
+ *   JPGPU_ERR_ARGUMENT (the decoder's rule and status): its output length is 0 and its neighbours are untouched.  An image with a window is
+ *   refused for the reasons a turned one is (progressive, several scans, more than ten blocks per MCU, ...).  Where the headers cannot be
+ *   walked at all and the file has a window, the image FAILS with the plan's header error -- unlike the turn's rule ("is not turned"): a
+ *   caller who asked for a region never gets the whole picture back silently.
+ *     Restart rule.  It is that of F'': where ITS MCU count is a multiple of DRI the image reports JPGPU_ERR_INVALID_OPERATION, and the MCU
+ *   count of the source does not decide it.
+ *     One decode per source.  Entries of one upload that are the same file (the same pointer and length) are entropy-decoded once for the
+ *   coefficient road; jpgpu_optimizer_turn_sources reports how many files the last upload decoded for it.  Outputs do not depend on it.
+ *     jpgpu_optimizer_image_window reports the window image i was planned with, behind JPGPU_ORIGIN_EXPAND ({0, 0, W', H'} for an image
+ *   without one), and jpgpu_optimizer_image_transform then reports the OUTPUT size w x h.  jpgpu_transform_plan_window is
+ *   jpgpu_transform_plan with the window (`applied` may be NULL); a NULL or all-zero window gives exactly what jpgpu_transform_plan gives.
+ *   Not covered: several windows into one output, jpegtran's rule that a window may rescue a partial mirrored edge (the edge policy is resolved
+ * on the whole frame), jpegtran's default of leaving an unmirrored strip at the edge, grey-scale conversion, Exif pixel-dimension tags and
+ * thumbnails, the JpegOptimizer mirror. */
 typedef enum jpgpu_edge_policy {
     JPGPU_EDGE_REFUSE = 0, /* a mirrored axis that is no whole number of MCUs refuses the image */
     JPGPU_EDGE_TRIM = 1    /* ... drops its partial last MCU column or row */
@@ -1201,6 +1233,17 @@ int jpgpu_optimizer_image_transform(const jpgpu_optimizer *o, int i, jpgpu_trans
 int jpgpu_optimizer_turn_ms(const jpgpu_optimizer *o, float ms[3]);
 int jpgpu_transform_plan(const uint8_t *file, size_t len, int orientation, int policy, int edge, jpgpu_transform_info *info, char *message,
                          size_t message_cap);
+/* ... and the window ("Window" above) */
+typedef enum jpgpu_origin_policy {
+    JPGPU_ORIGIN_REFUSE = 0, /* a window whose x or y is no multiple of the MCU size refuses the image */
+    JPGPU_ORIGIN_EXPAND = 1  /* ... is moved up and left to the MCU boundary, and grows by as much */
+} jpgpu_origin_policy;
+int jpgpu_optimizer_set_origin_policy(jpgpu_optimizer *o, int origin);
+int jpgpu_optimizer_set_windows(jpgpu_optimizer *o, const jpgpu_rect *windows, int n);
+int jpgpu_optimizer_image_window(const jpgpu_optimizer *o, int i, jpgpu_rect *applied);
+int jpgpu_optimizer_turn_sources(const jpgpu_optimizer *o, int *files);
+int jpgpu_transform_plan_window(const uint8_t *file, size_t len, int orientation, int policy, int edge, const jpgpu_rect *window, int origin,
+                                jpgpu_transform_info *info, jpgpu_rect *applied, char *message, size_t message_cap);
 
 /* JpegHuffmanEncodingTableBuilder.Build(false) for one table: DHT counts and values, and GetCode() for all 256 symbols */
 /* The order .NET's Array.Sort(T[], Comparison<T>) / List<T>.Sort(Comparison<T>) leaves n elements in when the comparison looks at

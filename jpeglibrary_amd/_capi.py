@@ -330,6 +330,12 @@ SYMBOLS = [
     ("jpgpu_optimizer_image_transform", C.c_int, [_P, C.c_int, C.POINTER(TransformInfo)]),
     ("jpgpu_optimizer_turn_ms", C.c_int, [_P, C.POINTER(C.c_float * 3)]),
     ("jpgpu_transform_plan", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(TransformInfo), C.c_char_p, C.c_size_t]),
+    ("jpgpu_optimizer_set_origin_policy", C.c_int, [_P, C.c_int]),
+    ("jpgpu_optimizer_set_windows", C.c_int, [_P, C.POINTER(Rect), C.c_int]),
+    ("jpgpu_optimizer_image_window", C.c_int, [_P, C.c_int, C.POINTER(Rect)]),
+    ("jpgpu_optimizer_turn_sources", C.c_int, [_P, C.POINTER(C.c_int)]),
+    ("jpgpu_transform_plan_window", C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(Rect), C.c_int, C.POINTER(TransformInfo),
+                                              C.POINTER(Rect), C.c_char_p, C.c_size_t]),
 ]
 
 

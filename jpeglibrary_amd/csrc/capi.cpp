@@ -1613,15 +1613,31 @@ int jpgpu_optimizer_turn_ms(const jpgpu_optimizer *opt, float *ms) {
     opt->impl.last_turn_ms(ms);
     return JPGPU_OK;
 }
+int jpgpu_optimizer_set_origin_policy(jpgpu_optimizer *opt, int origin) { JPGPU_GUARD(opt, opt->impl.set_origin_policy(origin)); }
+int jpgpu_optimizer_set_windows(jpgpu_optimizer *opt, const jpgpu_rect *windows, int n) { JPGPU_GUARD(opt, opt->impl.set_windows(windows, n)); }
+int jpgpu_optimizer_image_window(const jpgpu_optimizer *opt, int i, jpgpu_rect *applied) {
+    return opt ? opt->impl.image_window(i, applied) : JPGPU_ERR_ARGUMENT;
+}
+int jpgpu_optimizer_turn_sources(const jpgpu_optimizer *opt, int *files) {
+    if (!opt || !files) return JPGPU_ERR_ARGUMENT;
+    *files = opt->impl.turn_sources();
+    return JPGPU_OK;
+}
 // Host only: the headers up to the first SOS, the orientation rule, the edge policy
 int jpgpu_transform_plan(const uint8_t *file, size_t len, int orientation, int policy, int edge, jpgpu_transform_info *info, char *message, size_t message_cap) {
+    return jpgpu_transform_plan_window(file, len, orientation, policy, edge, nullptr, JPGPU_ORIGIN_REFUSE, info, nullptr, message, message_cap);
+}
+// ... and the window with its origin policy (a NULL or all-zero window: exactly the above)
+int jpgpu_transform_plan_window(const uint8_t *file, size_t len, int orientation, int policy, int edge, const jpgpu_rect *window, int origin,
+                                jpgpu_transform_info *info, jpgpu_rect *applied, char *message, size_t message_cap) {
     if (!file || !info || orientation < 0 || orientation > 8 || (policy != JPGPU_ORIENT_STORED && policy != JPGPU_ORIENT_FILE) ||
-        (edge != JPGPU_EDGE_REFUSE && edge != JPGPU_EDGE_TRIM))
+        (edge != JPGPU_EDGE_REFUSE && edge != JPGPU_EDGE_TRIM) || (origin != JPGPU_ORIGIN_REFUSE && origin != JPGPU_ORIGIN_EXPAND))
         return JPGPU_ERR_ARGUMENT;
     try {
         TransformPlan plan;
-        const int rc = plan_transform(file, len, orientation, policy, edge, &plan);
+        const int rc = plan_transform(file, len, orientation, policy, edge, &plan, window, origin);
         transform_info_of(plan, info);
+        if (applied) *applied = plan.has_window ? plan.applied : jpgpu_rect{0, 0, plan.out_width, plan.out_height};
         if (message && message_cap) {
             const size_t n = std::min(plan.message.size(), message_cap - 1);
             memcpy(message, plan.message.data(), n);

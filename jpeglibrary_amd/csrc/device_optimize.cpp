@@ -17,6 +17,8 @@
 
 #include <algorithm>
 #include <cstring>
+#include <map>
+#include <utility>
 
 namespace jpgpu {
 
@@ -630,13 +632,19 @@ int OptimizeBatch::upload(const uint8_t *const *jpeg, const size_t *len, int n, 
     given.swap(pending_orientations_);
     const bool with_list = orientations_pending_;
     orientations_pending_ = false;
+    std::vector<jpgpu_rect> windows;  // ... and its windows (empty: none)
+    windows.swap(pending_windows_);
+    const bool with_windows = windows_pending_;
+    windows_pending_ = false;
     if (with_list && (int)given.size() != n)
         return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_upload: the upload's n differs from the orientations' n (jpgpu_optimizer_set_orientations)");
+    if (with_windows && (int)windows.size() != n)
+        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_upload: the upload's n differs from the windows' n (jpgpu_optimizer_set_windows)");
     plans_.assign((size_t)n, Plan());
     for (int i = 0; i < n; i++) {
         try {
             plan_file(plans_[i], jpeg[i], len[i], strip != 0);
-            plan_turned_image(plans_[i], jpeg[i], len[i], strip != 0, with_list ? given[(size_t)i] : 0);
+            plan_turned_image(plans_[i], jpeg[i], len[i], strip != 0, with_list ? given[(size_t)i] : 0, with_windows ? &windows[(size_t)i] : nullptr);
         } catch (const Refuse &e) {
             plans_[i].status = e.status;
             plans_[i].detail = e.detail;
@@ -685,7 +693,8 @@ int OptimizeBatch::upload(const uint8_t *const *jpeg, const size_t *len, int n, 
     work_.clear();
     sub_scan_ids_.clear();
     sub_work_.clear();
-    std::vector<HuffWork> counted_only, sub_counted_only;  // the turned images: Scan()'s pass decides their status, nothing of it is emitted
+    // the images of the coefficient road: Scan()'s pass decides their status, nothing of it is emitted
+    std::vector<HuffWork> counted_only, sub_counted_only;
     for (int i = 0; i < n; i++) {
         Plan &p = plans_[i];
         if (p.status != JPGPU_OK) continue;
@@ -713,7 +722,7 @@ int OptimizeBatch::upload(const uint8_t *const *jpeg, const size_t *len, int n, 
         }
         p.by_subsequence = s.n_subs != 0;  // the batch marks DRI = 0 scans for the self-synchronising subsequence machinery
                                            // (not those with RSTn markers in the data: upload() asks for the interval path)
-        const bool turned = p.transform.orientation != 1;
+        const bool turned = p.transform.coefficient_road();
         if (!turned) {  // (jpgpu_optimizer_image_transform: the frame as it is)
             const ScanJob &job = batch_.jobs_[p.job];
             p.transform.out_width = img->width;
@@ -1005,7 +1014,7 @@ void OptimizeBatch::collect_lengths(const Run &r) {
     int k = 0, ks = 0;
     for (Plan &p : plans_) {
         if (p.status != JPGPU_OK || p.job < 0) continue;
-        if (p.transform.orientation != 1) {  // a turned image: the encoder's stuffing stage has closed its stream with EOI, too
+        if (p.transform.coefficient_road()) {  // a turned or cut image: the encoder's stuffing stage has closed its stream with EOI, too
             p.entropy_off = timages_[(size_t)p.turn].out_off;
             p.entropy_len = tout_len_[(size_t)p.turn] >= 2 ? tout_len_[(size_t)p.turn] - 2 : 0;
         } else if (p.by_subsequence) {
@@ -1049,20 +1058,41 @@ int OptimizeBatch::image_transform(int i, jpgpu_transform_info *info) const {
     transform_info_of(plans_[(size_t)i].transform, info);
     return JPGPU_OK;
 }
+int OptimizeBatch::set_origin_policy(int origin) {
+    if (origin != JPGPU_ORIGIN_REFUSE && origin != JPGPU_ORIGIN_EXPAND) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_set_origin_policy: unknown policy");
+    origin_policy_ = origin;
+    return JPGPU_OK;
+}
+int OptimizeBatch::set_windows(const jpgpu_rect *windows, int n) {
+    if (n < 0 || (n > 0 && !windows)) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_set_windows: bad argument");
+    pending_windows_.assign(windows, windows + n);
+    windows_pending_ = n > 0;
+    return JPGPU_OK;
+}
+int OptimizeBatch::image_window(int i, jpgpu_rect *applied) const {
+    if (i < 0 || i >= (int)plans_.size() || !applied) return JPGPU_ERR_ARGUMENT;
+    const TransformPlan &tp = plans_[(size_t)i].transform;
+    *applied = tp.has_window ? tp.applied : jpgpu_rect{0, 0, tp.out_width, tp.out_height};
+    return JPGPU_OK;
+}
 
 // The host side of a turned image: its plan, and the pieces of Optimize(strip) over F' -- the source with the SOF, DQT and Exif patches.
 // An image whose orientation is 1 is never touched: with nothing set (no list, the STORED policy) or a 1 in the list the file is not even
 // looked at, and a file whose headers plan_transform cannot walk is not turned -- it keeps whatever the optimizer's own walks make of it.
-void OptimizeBatch::plan_turned_image(Plan &p, const uint8_t *data, size_t len, bool strip, int given) {
+// A window ("Window" of the same section) puts the image on this road whatever its orientation, and there an unwalkable file FAILS with the
+// plan's header error: a caller who asked for a region must not get the whole picture back.  The pieces are then those of F''.
+void OptimizeBatch::plan_turned_image(Plan &p, const uint8_t *data, size_t len, bool strip, int given, const jpgpu_rect *window) {
     TransformPlan &tp = p.transform;
     tp = TransformPlan();
-    if (given == 1 || (given == 0 && orient_policy_ == JPGPU_ORIENT_STORED)) return;
-    if (plan_transform(data, len, given, orient_policy_, edge_policy_, &tp) != JPGPU_OK) {
+    const bool windowed = window && (window->x | window->y | window->width | window->height) != 0;
+    if (!windowed && (given == 1 || (given == 0 && orient_policy_ == JPGPU_ORIENT_STORED))) return;
+    if (const int rc = plan_transform(data, len, given, orient_policy_, edge_policy_, &tp, windowed ? window : nullptr, origin_policy_); rc != JPGPU_OK) {
+        if (windowed) refuse(rc, tp.message, kDetailBadHeader);
         tp = TransformPlan();
         return;
     }
-    if (tp.orientation == 1) return;
-    if (tp.status != JPGPU_OK) refuse(tp.status, tp.message, kDetailUnsupportedFrame);
+    if (!tp.coefficient_road()) return;
+    if (tp.status != JPGPU_OK) refuse(tp.status, tp.message, tp.status == JPGPU_ERR_ARGUMENT ? kDetailNone : kDetailUnsupportedFrame);
     std::string f((const char *)data, len);
     uint8_t *b = (uint8_t *)&f[0];
     patch_turned_file(b, len, tp);
@@ -1083,16 +1113,26 @@ int OptimizeBatch::upload_turned(const uint8_t *const *jpeg, const size_t *len) 
     twork_blk_.clear();
     twork_stat_.clear();
     turn_blocks_total_ = 0;
+    turn_sources_ = 0;
+    // entries that are the same file (the same pointer and length: one canvas cut into tiles) take ONE slot of the second batch and are
+    // entropy-decoded once; their descriptors share its place in the dense store
     std::vector<const uint8_t *> files;
     std::vector<size_t> lens;
+    std::vector<int> slot_of;  // per entry of turned_
+    std::map<std::pair<const uint8_t *, size_t>, int> slots;
     for (size_t i = 0; i < plans_.size(); i++) {
         Plan &p = plans_[i];
         p.turn = -1;
-        if (p.status != JPGPU_OK || p.job < 0 || p.transform.orientation == 1) continue;
+        if (p.status != JPGPU_OK || p.job < 0 || !p.transform.coefficient_road()) continue;
         turned_.push_back((int)i);
-        files.push_back(jpeg[i]);
-        lens.push_back(len[i]);
+        const auto at = slots.emplace(std::make_pair(jpeg[i], len[i]), (int)files.size());
+        if (at.second) {
+            files.push_back(jpeg[i]);
+            lens.push_back(len[i]);
+        }
+        slot_of.push_back(at.first->second);
     }
+    turn_sources_ = (int)files.size();
     if (turned_.empty()) {  // nothing of an earlier upload's turned images stays on the device
         turn_batch_.reset();
         for (DevBuffer *b : {&d_turn_images_, &d_turn_work_, &d_tcoefs_, &d_timages_, &d_tlayouts_, &d_twork_blk_, &d_twork_stat_, &d_thist_, &d_ttables_,
@@ -1107,7 +1147,7 @@ int OptimizeBatch::upload_turned(const uint8_t *const *jpeg, const size_t *len) 
         Plan &p = plans_[(size_t)turned_[k]];
         const TransformPlan &tp = p.transform;
         const ScanJob &job = batch_.jobs_[p.job];  // (the optimizer's view of the scan: its table slots are the builders' order)
-        const ImagePlan *img = turn_batch_->image((int)k);
+        const ImagePlan *img = turn_batch_->image(slot_of[k]);
         const auto refuse_image = [&](const std::string &msg) {
             p.status = JPGPU_ERR_NOT_SUPPORTED;
             p.detail = kDetailUnsupportedFrame;
@@ -1148,6 +1188,16 @@ int OptimizeBatch::upload_turned(const uint8_t *const *jpeg, const size_t *len) 
         g.kept_mcus_per_column = tp.kept_mcus_per_column;
         g.dst_mcus_per_line = tr ? tp.kept_mcus_per_column : tp.kept_mcus_per_line;
         g.dst_mcus_per_column = tr ? tp.kept_mcus_per_line : tp.kept_mcus_per_column;
+        if (tp.has_window) {  // the destination is the window's grid; plan_transform has checked that it lies inside the turned one
+            if ((uint64_t)tp.win_mcu_x + tp.win_mcus_per_line > g.dst_mcus_per_line || (uint64_t)tp.win_mcu_y + tp.win_mcus_per_column > g.dst_mcus_per_column) {
+                refuse_image("The window does not lie inside the MCU grid of the turned image.");
+                continue;
+            }
+            g.origin_mx = tp.win_mcu_x;
+            g.origin_my = tp.win_mcu_y;
+            g.dst_mcus_per_line = tp.win_mcus_per_line;
+            g.dst_mcus_per_column = tp.win_mcus_per_column;
+        }
         g.total_blocks = g.dst_mcus_per_line * g.dst_mcus_per_column * bpm;
         L.ncomp = (uint32_t)tp.ncomp;
         L.max_h = tr ? tp.max_v : tp.max_h;
@@ -1380,8 +1430,9 @@ int OptimizeBatch::result(int i, jpgpu_image_result *res, size_t *out_len) {
         // it builds its tables (:437-442); Optimize() then throws InvalidOperationException (:542-545)
         const DevScan &s = batch_.h_scans_[p.job];
         const DevScanStatus &st = batch_.h_status_[p.job];
-        const bool check_saw_eoi = s.dri != 0 && st.terminator == 0xD9 &&
-                                   (st.n_ends < s.n_intervals || (st.n_ends == s.n_intervals && s.restart_check_at_end != 0));
+        // (a windowed image: the restart rule is that of F'', checked below -- the MCU count of the source does not decide it)
+        const bool count_decides = s.restart_check_at_end != 0 && !p.transform.has_window;
+        const bool check_saw_eoi = s.dri != 0 && st.terminator == 0xD9 && (st.n_ends < s.n_intervals || (st.n_ends == s.n_intervals && count_decides));
         if (check_saw_eoi) {
             res->status = JPGPU_ERR_INVALID_OPERATION;
             ctx_->last_error = "Operation is not valid due to the current state of the object.";

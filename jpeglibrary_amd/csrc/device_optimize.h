@@ -47,6 +47,11 @@ class OptimizeBatch {
     int set_orientations(const uint8_t *orientations, int n);
     int set_edge_policy(int edge);
     int image_transform(int i, jpgpu_transform_info *info) const;
+    // ... and its window ("Window" of the same section): the origin policy is state, the list is consumed by the next upload
+    int set_origin_policy(int origin);
+    int set_windows(const jpgpu_rect *windows, int n);
+    int image_window(int i, jpgpu_rect *applied) const;
+    int turn_sources() const { return turn_sources_; }  // files the coefficient road of the last upload entropy-decoded
     // of the last run (zeros: nothing was turned), HIP events all three: KX alone; the entropy decode in front of it; the dense copy
     void last_turn_ms(float ms[3]) const {
         ms[0] = last_turn_ms_;
@@ -80,8 +85,8 @@ class OptimizeBatch {
         uint64_t entropy_off = 0, entropy_len = 0;
         bool by_subsequence = false;  // DRI = 0 scan: transcoded by subsequence (KTS), bytes in d_sout_
         uint64_t out_len = 0;
-        // the lossless transform: the image's plan (orientation 1: the image takes the road above and nothing below is read), and its
-        // place among the turned images of the upload (-1: not turned, or refused)
+        // the lossless transform: the image's plan (orientation 1 and no window: the image takes the road above and nothing below is read), and
+        // its place among the images of the upload that take the coefficient road (-1: not among them, or refused)
         TransformPlan transform;
         int turn = -1;
     };
@@ -102,7 +107,7 @@ class OptimizeBatch {
     int emit_turned(Run &r);
     // turned: the file is F' (the source with its SOF / DQT / Exif patches), whose scan holds exactly the restart markers it needs
     void plan_file(Plan &p, const uint8_t *data, size_t len, bool strip, bool swallow_terminator = false, bool turned = false);
-    void plan_turned_image(Plan &p, const uint8_t *data, size_t len, bool strip, int given);
+    void plan_turned_image(Plan &p, const uint8_t *data, size_t len, bool strip, int given, const jpgpu_rect *window);
     int upload_turned(const uint8_t *const *jpeg, const size_t *len);
     size_t scan_end(const uint8_t *entropy, size_t len);
     const uint8_t *end_key_ = nullptr;
@@ -117,6 +122,10 @@ class OptimizeBatch {
     int orient_policy_ = JPGPU_ORIENT_STORED, edge_policy_ = JPGPU_EDGE_REFUSE;
     std::vector<uint8_t> pending_orientations_;
     bool orientations_pending_ = false;
+    int origin_policy_ = JPGPU_ORIGIN_REFUSE;
+    std::vector<jpgpu_rect> pending_windows_;
+    bool windows_pending_ = false;
+    int turn_sources_ = 0;
     std::vector<int> turned_;                // images of the upload that are turned, in order
     std::vector<DevTurnImage> turn_images_;  // ... their KX descriptors,
     std::vector<TurnWork> turn_work_;

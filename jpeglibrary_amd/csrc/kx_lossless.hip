@@ -10,7 +10,11 @@
 //   5..8: parked in LDS at a block stride of kLdsBlockStride = 144 bytes (E1's staging stride), and behind ONE barrier every lane gathers the
 //         eight coefficients of its DESTINATION piece from the parked block (the transposition is a fixed permutation of the zig-zag positions)
 //         and stores them as one piece.
-// Every coefficient is read once and written once.  The source blocks of 5..8 lie a grid row apart (a destination row walks a source column):
+//   1:    (a window alone, "Window" of the same section) the straight road of 2..4 with an empty sign mask: no LDS, no barrier.
+// A window is an offset and nothing else: the destination grid is the window's, and source_block() adds the window's first MCU to the
+// destination MCU's place before it maps it to the source -- in the turned grid, so under 5..8 the origin's x runs along the source's y, and
+// under a mirrored axis it counts from the far edge of the KEPT grid.  Blocks outside the window are never loaded.
+// Every coefficient of the destination is read once and written once.  The source blocks of 5..8 lie a grid row apart (a destination row walks a source column):
 // whole 128-byte lines, scattered.  LDS: the park is ds_write_b128 at 16-byte steps inside a block and 144 bytes between blocks -- consecutive
 // slots, no conflict; the gather is eight 2-byte reads per lane whose addresses follow the zig-zag, eight lanes per block at 36 dwords between
 // blocks (4 banks apart modulo 32): some of a group's 32 lanes meet on a bank, which the kernel, bound by its global bytes, does not pay for
@@ -71,7 +75,7 @@ __device__ __forceinline__ uint32_t source_block(const DevTurnImage &g, uint32_t
     const uint32_t h = g.src_h[c], v = g.src_v[c];
     const uint32_t dh = transposes ? v : h, dv = transposes ? h : v;
     const uint32_t my = mcu / g.dst_mcus_per_line, mx = mcu - my * g.dst_mcus_per_line;
-    const uint32_t X = mx * dh + ((info >> 2) & 3u), Y = my * dv + ((info >> 4) & 3u);
+    const uint32_t X = (mx + g.origin_mx) * dh + ((info >> 2) & 3u), Y = (my + g.origin_my) * dv + ((info >> 4) & 3u);
     const uint32_t ty = transposes ? X : Y, tx = transposes ? Y : X;
     const uint32_t by = flip_y ? g.kept_mcus_per_column * v - 1u - ty : ty;
     const uint32_t bx = flip_x ? g.kept_mcus_per_line * h - 1u - tx : tx;

@@ -1,7 +1,8 @@
 // jpeglibrary_amd/csrc/transform_plan.h -- the host side of the optimizer's lossless transform (include/jpgpu.h section (5), "Lossless
 // transform"): a file's headers, the orientation rule and the edge policy -> what the image is turned by, or its refusal.  No device, no HIP:
-// jpgpu_transform_plan, OptimizeBatch::upload and the stand-alone sanitizer harness (tools/fuzz/transform_plan_asan.cpp, linked with
-// host_parser.cpp for the marker reader and the header parsers) share it.
+// jpgpu_transform_plan, jpgpu_transform_plan_window, OptimizeBatch::upload and the stand-alone sanitizer harnesses
+// (tools/fuzz/transform_plan_asan.cpp and, for the window, tools/fuzz/crop_plan_asan.cpp, linked with host_parser.cpp for the marker reader
+// and the header parsers) share it.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -36,16 +37,32 @@ struct TransformPlan {
         size_t at, length;
     };
     std::vector<Segment> dqt;  // the payloads of the DQT segments in front of the scan
+    // the window ("Window" of the same section): in pixels of the frame of F' (turned_width x turned_height, the turned frame behind the trim).
+    // With one, out_width x out_height is the window's size, and win_* is what it keeps of the MCU grid of F'.
+    bool has_window = false;
+    int origin = JPGPU_ORIGIN_REFUSE;
+    jpgpu_rect window = {0, 0, 0, 0}, applied = {0, 0, 0, 0};  // as asked for; as applied (behind JPGPU_ORIGIN_EXPAND)
+    uint32_t turned_width = 0, turned_height = 0;
+    uint32_t win_mcu_x = 0, win_mcu_y = 0, win_mcus_per_line = 0, win_mcus_per_column = 0;
     bool transposes() const { return orientation >= 5; }
+    // the image takes the coefficient road (entropy decode, KX, the encoder's entropy stages): it is turned, or cut, or both
+    bool coefficient_road() const { return orientation != 1 || has_window; }
 };
-// orientation: 0 = by `policy` (a jpgpu_orientation_policy), 1..8 as given.  Returns JPGPU_OK (plan->status may refuse the image), or the
-// library's header error for a file without a usable frame header.
+// orientation: 0 = by `policy` (a jpgpu_orientation_policy), 1..8 as given.  window: NULL or all zero = none (nothing below changes for it);
+// origin: a jpgpu_origin_policy.  Returns JPGPU_OK (plan->status may refuse the image), or the library's header error for a file without a
+// usable frame header.
 // The headers of a file up to its first SOS: Identify()'s marker loop restated over the same reader (HostDecoder::identify_until_scan,
 // host_parser.cpp: MarkerReader finds the markers -- bytes in front of one are stepped over, no leading SOI is asked for -- and reads the
 // lengths with the reference's rule), so the Exif block found here is the one jpgpu_identify_orientation finds, and a file that walk
 // accepts is accepted here.  Beside what Identify() keeps it notes WHERE things stand: the frame header, the DQT segments, the Exif value.
-inline int plan_transform(const uint8_t *file, size_t len, int orientation, int policy, int edge, TransformPlan *tp) {
+inline int plan_transform(const uint8_t *file, size_t len, int orientation, int policy, int edge, TransformPlan *tp, const jpgpu_rect *window = nullptr,
+                          int origin = JPGPU_ORIGIN_REFUSE) {
     *tp = TransformPlan();
+    if (window && (window->x | window->y | window->width | window->height) != 0) {
+        tp->has_window = true;
+        tp->window = *window;
+        tp->origin = origin;
+    }
     const auto header_error = [&](const char *msg) {
         tp->status = JPGPU_ERR_INVALID_DATA;
         tp->message = msg;
@@ -122,7 +139,9 @@ inline int plan_transform(const uint8_t *file, size_t len, int orientation, int 
     tp->from_file = orientation == 0 && tp->orientation != 1;
     tp->kept_width = tp->out_width = tp->src_width;
     tp->kept_height = tp->out_height = tp->src_height;
-    if (tp->orientation == 1) return JPGPU_OK;  // (today's road: nothing below is asked of the file)
+    tp->turned_width = tp->src_width;
+    tp->turned_height = tp->src_height;
+    if (!tp->coefficient_road()) return JPGPU_OK;  // (today's road: nothing below is asked of the file)
     const int o = tp->orientation;
     if (other_sof != 0)
         return refuse_image(other_sof == kSOF2 ? "Progressive JPEG is not supported by the optimizer path." : "This type of JPEG stream is not supported by the optimizer path.");
@@ -163,6 +182,40 @@ inline int plan_transform(const uint8_t *file, size_t len, int orientation, int 
     tp->kept_mcus_per_column = (tp->kept_height + mcu_h - 1) / mcu_h;
     tp->out_width = tp->transposes() ? tp->kept_height : tp->kept_width;
     tp->out_height = tp->transposes() ? tp->kept_width : tp->kept_height;
+    tp->turned_width = tp->out_width;
+    tp->turned_height = tp->out_height;
+    if (!tp->has_window) return JPGPU_OK;
+    // ---- the window, in the frame of F': the orientation and the edge policy are resolved by now, on the whole frame
+    const jpgpu_rect w = tp->window;
+    const std::string rect = "The window {" + std::to_string(w.x) + ", " + std::to_string(w.y) + ", " + std::to_string(w.width) + ", " + std::to_string(w.height) + "} ";
+    const auto bad_window = [&](const std::string &msg) {
+        tp->status = JPGPU_ERR_ARGUMENT;
+        tp->message = msg;
+        return JPGPU_OK;
+    };
+    if (w.width == 0 || w.height == 0) return bad_window(rect + "has a zero side.");
+    if ((uint64_t)w.x + w.width > tp->turned_width || (uint64_t)w.y + w.height > tp->turned_height)
+        return bad_window(rect + "lies outside the " + std::to_string(tp->turned_width) + " x " + std::to_string(tp->turned_height) + " frame.");
+    const uint32_t mw = tp->transposes() ? mcu_h : mcu_w, mh = tp->transposes() ? mcu_w : mcu_h;  // the MCU of F'
+    jpgpu_rect a = w;
+    if (a.x % mw != 0 || a.y % mh != 0) {
+        if (origin != JPGPU_ORIGIN_EXPAND) {
+            const bool in_x = a.x % mw != 0;
+            return refuse_image(std::string("The window's ") + (in_x ? "x" : "y") + " (" + std::to_string(in_x ? a.x : a.y) + ") is not a multiple of the MCU " +
+                                (in_x ? "width" : "height") + " (" + std::to_string(in_x ? mw : mh) + " pixels).");
+        }
+        a.width += a.x % mw;
+        a.x -= a.x % mw;
+        a.height += a.y % mh;
+        a.y -= a.y % mh;
+    }
+    tp->applied = a;
+    tp->win_mcu_x = a.x / mw;
+    tp->win_mcu_y = a.y / mh;
+    tp->win_mcus_per_line = (a.width + mw - 1) / mw;
+    tp->win_mcus_per_column = (a.height + mh - 1) / mh;
+    tp->out_width = a.width;
+    tp->out_height = a.height;
     return JPGPU_OK;
 }
 
@@ -179,8 +232,8 @@ inline void transform_info_of(const TransformPlan &tp, jpgpu_transform_info *inf
     }
 }
 
-// F' in place: `b` holds a copy of the file `tp` was planned from (status JPGPU_OK, orientation 2..8).  The SOF's size and, for 5..8, its
-// factor nibbles; for 5..8 every table of every DQT segment in front of the scan transposed; the Exif value where the file decided.
+// F' (with a window: F'') in place: `b` holds a copy of the file `tp` was planned from (status JPGPU_OK, on the coefficient road).  The SOF's
+// size -- the window's where there is one -- and, for 5..8, its factor nibbles; for 5..8 every table of every DQT segment in front of the scan transposed; the Exif value where the file decided.
 // Every place written is one plan_transform read through the marker reader's own bounds checks: the frame header's 6 + 3 n bytes, the DQT
 // payloads it recorded, the two bytes of the Exif value.
 inline void patch_turned_file(uint8_t *b, size_t len, const TransformPlan &tp) {

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
+from .batch import _window_rects
 from .context import Context, default_context
 from .errors import raise_for_status
 
@@ -19,10 +20,17 @@ _lib = _capi.lib
 ORIENT_STORED, ORIENT_FILE = 0, 1
 EDGE_REFUSE, EDGE_TRIM = 0, 1
 _POLICIES = {None: ORIENT_STORED, "stored": ORIENT_STORED, "file": ORIENT_FILE}
+ORIGIN_REFUSE, ORIGIN_EXPAND = 0, 1
 _EDGES = {"refuse": EDGE_REFUSE, "trim": EDGE_TRIM}
+_ORIGINS = {"refuse": ORIGIN_REFUSE, "expand": ORIGIN_EXPAND}
 
-# what an image is turned by (include/jpgpu.h, "Lossless transform"): factors = [(h, v)] of the output, frame order
-TransformPlan = collections.namedtuple("TransformPlan", "orientation width height trimmed factors")
+# what an image is turned by (include/jpgpu.h, "Lossless transform"): factors = [(h, v)] of the output, frame order; window = (x, y, w, h) as
+# applied, in pixels of the turned frame ((0, 0, width, height) without one: the field defaults so, and width x height is the OUTPUT's size)
+class TransformPlan(collections.namedtuple("TransformPlan", "orientation width height trimmed factors window")):
+    __slots__ = ()
+
+    def __new__(cls, orientation, width, height, trimmed, factors, window=None):
+        return super().__new__(cls, orientation, width, height, trimmed, factors, (0, 0, width, height) if window is None else tuple(window))
 
 
 def _policy(orientation):
@@ -37,8 +45,15 @@ def _edge(edge):
     return _EDGES[edge]
 
 
-def _plan_of(info):
-    return TransformPlan(info.orientation, info.width, info.height, bool(info.trimmed), [(info.h[c], info.v[c]) for c in range(info.num_components)])
+def _origin(origin):
+    if origin not in _ORIGINS:
+        raise ValueError("origin is 'refuse' or 'expand': %r" % (origin,))
+    return _ORIGINS[origin]
+
+
+def _plan_of(info, window=None):
+    return TransformPlan(info.orientation, info.width, info.height, bool(info.trimmed), [(info.h[c], info.v[c]) for c in range(info.num_components)],
+                         None if window is None else (window.x, window.y, window.width, window.height))
 
 
 class OptimizeBatch:
@@ -76,11 +91,40 @@ class OptimizeBatch:
         self._check(_lib.jpgpu_optimizer_set_edge_policy(self._h, _edge(edge)))
         return self
 
+    def set_windows(self, rects):
+        """One (x, y, w, h) per file of the NEXT upload, in pixels of the turned frame ((0, 0, 0, 0) = none); None or [] withdraws a pending
+        list.  The image is cut in the coefficient domain (include/jpgpu.h, "Window"): its output decodes to that slice of the whole picture,
+        sample for sample.  ValueError, before the library is called, for a rect that is not four non-negative integers below 2^32."""
+        rects = _window_rects(rects) or []
+        arr = (_capi.Rect * max(1, len(rects)))(*[_capi.Rect(*r) for r in rects])
+        self._check(_lib.jpgpu_optimizer_set_windows(self._h, arr, len(rects)))
+        return self
+
+    def set_origin_policy(self, origin):
+        """ "refuse" (the default; jpegtran -perfect): a window whose x or y is no multiple of the MCU size refuses the image; "expand"
+        (jpegtran's default): it is moved up and left to the MCU boundary and grows by as much"""
+        self._check(_lib.jpgpu_optimizer_set_origin_policy(self._h, _origin(origin)))
+        return self
+
     def transform(self, i) -> TransformPlan:
-        """What image i of the last upload was planned with."""
+        """What image i of the last upload was planned with (width x height: the output's, the window's where there is one)."""
         info = _capi.TransformInfo()
         self._check(_lib.jpgpu_optimizer_image_transform(self._h, i, C.byref(info)))
-        return _plan_of(info)
+        r = _capi.Rect()
+        self._check(_lib.jpgpu_optimizer_image_window(self._h, i, C.byref(r)))
+        return _plan_of(info, r)
+
+    def window(self, i):
+        """(x, y, w, h): the window image i was planned with, behind the origin policy; (0, 0, W, H) of the turned frame without one"""
+        r = _capi.Rect()
+        self._check(_lib.jpgpu_optimizer_image_window(self._h, i, C.byref(r)))
+        return (r.x, r.y, r.width, r.height)
+
+    def turn_sources(self) -> int:
+        """How many files the coefficient road of the last upload entropy-decoded: entries that are the same file are decoded once."""
+        n = C.c_int()
+        self._check(_lib.jpgpu_optimizer_turn_sources(self._h, C.byref(n)))
+        return n.value
 
     def turn_ms(self) -> float:
         """Device time of the turn kernel (KX) alone in the last run; 0 when nothing was turned."""
@@ -96,9 +140,11 @@ class OptimizeBatch:
         n = len(files)
         ptrs = (C.c_void_p * n)()
         lens = (C.c_size_t * n)()
-        keep = []
+        keep, seen = [], {}  # (entries that are the same object share one buffer: the coefficient road decodes such a file once)
         for i, f in enumerate(files):
-            buf = np.frombuffer(bytes(f), dtype=np.uint8)
+            buf = seen.get(id(f))
+            if buf is None:
+                buf = seen[id(f)] = np.frombuffer(bytes(f), dtype=np.uint8)
             keep.append(buf)
             ptrs[i] = buf.ctypes.data if buf.size else None
             lens[i] = buf.size
@@ -197,13 +243,16 @@ class JpegOptimizer:
             self._output.write(data)
 
 
-def optimize_batch(files, strip=True, ctx=None, most_optimal=False, orientation=None, orientations=None, edge="refuse"):
+def optimize_batch(files, strip=True, ctx=None, most_optimal=False, orientation=None, orientations=None, edge="refuse", windows=None, origin="refuse"):
     """One-call helper: the optimized bytes of every file (raises on the first failing file).  orientation="file" bakes every file's Exif
     orientation into its coefficients, orientations=[...] turns file i by orientations[i] (1..8; 0 = by the policy); edge="trim" drops the
-    partial MCU column or row of a mirrored axis where the default refuses the image (include/jpgpu.h, "Lossless transform")."""
-    policy, edge_policy = _policy(orientation), _edge(edge)
+    partial MCU column or row of a mirrored axis where the default refuses the image (include/jpgpu.h, "Lossless transform").
+    windows=[(x, y, w, h), ...] cuts file i to that window of its turned frame without recompressing ((0, 0, 0, 0) = none); origin="expand"
+    moves an x or y that is no multiple of the MCU size to the boundary below where the default refuses the image ("Window")."""
+    policy, edge_policy, origin_policy = _policy(orientation), _edge(edge), _origin(origin)
     if orientations is not None and len(orientations) != len(files):
         raise ValueError("orientations holds one value per file")
+    windows = _window_rects(windows, len(files))
     b = OptimizeBatch(ctx)
     try:
         b.set_most_optimal_coding(most_optimal)
@@ -211,28 +260,35 @@ def optimize_batch(files, strip=True, ctx=None, most_optimal=False, orientation=
             b.set_orientation_policy(orientation)
         if edge_policy != EDGE_REFUSE:
             b.set_edge_policy(edge)
+        if origin_policy != ORIGIN_REFUSE:
+            b.set_origin_policy(origin)
         if orientations is not None:
             b.set_orientations(orientations)
+        if windows is not None:
+            b.set_windows(windows)
         b.upload(files, strip).run()
         return [b.output(i) for i in range(len(b))]
     finally:
         b.close()
 
 
-def plan_transform(file, orientation=None, orientations=None, edge="refuse") -> TransformPlan:
-    """Host only (no device): what optimize_batch([file], orientation=..., orientations=[...], edge=...) would turn the file by.  Raises
-    NotSupportedException with the refusal's text where the image would be refused."""
+def plan_transform(file, orientation=None, orientations=None, edge="refuse", window=None, origin="refuse") -> TransformPlan:
+    """Host only (no device): what optimize_batch([file], orientation=..., orientations=[...], edge=..., windows=[window], origin=...) would
+    turn and cut the file by.  Raises NotSupportedException with the refusal's text where the image would be refused, ArgumentException for
+    a window outside the turned frame or with one zero side."""
     if orientations is not None and len(orientations) != 1:
         raise ValueError("orientations holds one value per file")
     given = int(orientations[0]) if orientations is not None else 0
     if given < 0 or given > 8:
         raise ValueError("an orientation is 1..8, or 0 for what the policy gives")
+    rect = _capi.Rect(*(_window_rects([window])[0] if window is not None else (0, 0, 0, 0)))
     buf = np.frombuffer(bytes(file), dtype=np.uint8)
-    info = _capi.TransformInfo()
+    info, applied = _capi.TransformInfo(), _capi.Rect()
     msg = C.create_string_buffer(512)
-    rc = _lib.jpgpu_transform_plan(buf.ctypes.data if buf.size else None, buf.size, given, _policy(orientation), _edge(edge), C.byref(info), msg, 512)
-    raise_for_status(rc, msg.value or b"jpgpu_transform_plan failed")
-    return _plan_of(info)
+    rc = _lib.jpgpu_transform_plan_window(buf.ctypes.data if buf.size else None, buf.size, given, _policy(orientation), _edge(edge), C.byref(rect),
+                                          _origin(origin), C.byref(info), C.byref(applied), msg, 512)
+    raise_for_status(rc, msg.value or b"jpgpu_transform_plan_window failed")
+    return _plan_of(info, applied)
 
 
 def build_optimal_huffman_table(counts, most_optimal=False):
