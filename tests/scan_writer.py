@@ -31,6 +31,7 @@ def write_baseline(coefs, width, height, ncomp=1, dri=0, table_shape="flat"):
       stuffed         zero bytes stuffed behind an FF;  rst_markers  RSTn markers written
       block_bits      unstuffed bit position of every block's first bit, counted inside its own interval
       symbols         dri = 0 only: (bit position of the code, code length, magnitude length, block) per symbol
+      block_symbols   per block: (table identifier, [(class, symbol)]) in the order written (`priced_block_bits` prices them)
       header_bytes    length of everything in front of the entropy data"""
     coefs = np.asarray(coefs)
     mcus = ((width + 7) // 8) * ((height + 7) // 8)
@@ -94,8 +95,14 @@ def write_baseline(coefs, width, height, ncomp=1, dri=0, table_shape="flat"):
     entropy = bytes(w.out)
     info = {"tables": freq, "magnitude_bits": magnitude_bits, "intervals": intervals, "entropy_bytes": len(entropy),
             "stuffed": entropy.count(b"\xff\x00"), "rst_markers": rst, "block_bits": block_bits, "symbols": symbols,
-            "header_bytes": len(out)}
+            "header_bytes": len(out), "block_symbols": [(t, [(0, dcat)] + [(1, sym) for sym, _, _ in ac]) for t, dcat, _, ac in parsed]}
     return bytes(out) + entropy + b"\xff\xd9", info
+
+
+def priced_block_bits(info, lengths):
+    """bits of every block -- code words and the magnitude bits behind them -- when info's symbols are coded with `lengths`
+    ({(class, identifier): {symbol: code length}}, as parse_baseline reads them from a file's DHT)"""
+    return [sum(lengths[(cls, t)][sym] + (sym & 15) for cls, sym in syms) for t, syms in info["block_symbols"]]
 
 
 def unstuffed_length(info):
