@@ -66,6 +66,24 @@ struct DevBuffer {
     hipError_t reserve(size_t bytes);
     void release();
 };
+// One line of an upload's reservations: `buf` grows to max(bytes, reserve) and, where there are any, takes `bytes` from `src` on the stream.
+struct DevUpload {
+    DevBuffer *buf;
+    const void *src;
+    size_t bytes, reserve;
+};
+// ... and the list of them, in order; *copying says which of the two calls the error is of
+template <size_t N>
+hipError_t reserve_and_copy(const DevUpload (&ups)[N], hipStream_t stream, bool *copying) {
+    for (const DevUpload &u : ups) {
+        *copying = false;
+        hipError_t e = u.buf->reserve(u.bytes > u.reserve ? u.bytes : u.reserve);
+        if (e != hipSuccess) return e;
+        *copying = true;
+        if (u.bytes && (e = hipMemcpyAsync(u.buf->ptr, u.src, u.bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 // What the last jpgpu_batch_upload did (jpgpu_batch_ingest_stats).
 struct IngestStats {

@@ -1057,12 +1057,7 @@ void DeviceBatch::init_status() {
 int DeviceBatch::upload_plan(const UploadPlan &p, const std::vector<const uint8_t *> &file_ptr, const std::vector<size_t> &file_len) {
     hipStream_t up = ctx_->upload_stream;  // everything an upload does stays off the decode stream
     hipError_t e;
-    struct Up {
-        DevBuffer *buf;
-        const void *src;
-        size_t bytes, reserve;
-    };
-    const Up ups[] = {
+    const DevUpload ups[] = {
         {&d_scans_, h_scans_.data(), h_scans_.size() * sizeof(DevScan), 0},
         {&d_status_, h_status_.data(), h_status_.size() * sizeof(DevScanStatus), 0},
         {&d_huff_pool_, huff_pool_.data(), huff_pool_.size() * sizeof(DevHuffTable), 0},
@@ -1112,10 +1107,8 @@ int DeviceBatch::upload_plan(const UploadPlan &p, const std::vector<const uint8_
         {&d_planes_, nullptr, 0, format_ == JPGPU_FMT_EXTENDED_U16 && !entropy_only_ ? (size_t)planes_bytes_ + 256 : 0},
         {&d_input_, nullptr, 0, (size_t)input_bytes_},
     };
-    for (const Up &u : ups) {
-        if ((e = u.buf->reserve(std::max(u.bytes, u.reserve))) != hipSuccess) return hip_fail(e, "hipMalloc");
-        if (u.bytes && (e = hipMemcpyAsync(u.buf->ptr, u.src, u.bytes, hipMemcpyHostToDevice, up)) != hipSuccess) return hip_fail(e, "hipMemcpyAsync(descriptors)");
-    }
+    bool copying = false;
+    if ((e = reserve_and_copy(ups, up, &copying)) != hipSuccess) return hip_fail(e, copying ? "hipMemcpyAsync(descriptors)" : "hipMalloc");
     // the flag region starts from zero: the zero bytes in front of every scan's words stay so (K2 writes flag words only)
     uint8_t *const flags = (uint8_t *)d_coefs_.ptr + ((size_t)coef_store_blocks_ + (size_t)kIdctBlocksPerWg) * 128;
     if (!split_scans_.empty() && (e = hipMemsetAsync(flags, 0, (size_t)p.flag_words * 8, up)) != hipSuccess) return hip_fail(e, "hipMemsetAsync(hand-off flags)");

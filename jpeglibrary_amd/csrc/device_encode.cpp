@@ -252,6 +252,91 @@ StuffPlan plan_stuffing_layout(DevEncImage *images, const uint64_t *raw_bits, in
 
 // ------------------------------------------------------------------------------------------------ described images
 
+// ---- EntropyTail: E2 -> E3 -> E4
+hipError_t EntropyTail::reserve(uint64_t total_blocks, size_t n_work_blk, size_t n_images) {
+    failed = "hipMalloc";
+    const size_t slack = 256 + 16;  // (the kernels read past the payload)
+    hipError_t e = bits.reserve((size_t)total_blocks * sizeof(uint32_t) + slack);
+    if (e == hipSuccess) e = bit_off.reserve(((n_work_blk * sizeof(uint64_t) + 255) & ~(size_t)255) + n_work_blk * sizeof(uint32_t) + 256 + slack);
+    if (e == hipSuccess) e = raw_bits.reserve(n_images * sizeof(uint64_t) + slack);
+    if (e == hipSuccess) e = out_len.reserve(n_images * sizeof(uint64_t) + slack);
+    return e;
+}
+
+hipError_t EntropyTail::count_bits(hipStream_t stream, const Source &s, int n_images) {
+    failed = "block_bits_kernel";
+    uint32_t *wg_bits = reinterpret_cast<uint32_t *>((uint8_t *)bit_off.ptr + (((size_t)s.n_work_blk * sizeof(uint64_t) + 255) & ~(size_t)255));
+    return launch_block_bits(stream, s.images, s.work_blk, s.n_work_blk, s.tables, s.coefs, (uint32_t *)bits.ptr, n_images, wg_bits, (uint64_t *)bit_off.ptr,
+                             (uint64_t *)raw_bits.ptr, s.layouts, s.any_plain);
+}
+
+// one host round trip: a count per image, the stream synchronised (what fed its async copies may leave scope)
+static hipError_t read_counts(hipStream_t stream, const DevBuffer &from, int n_images, std::vector<uint64_t> *to) {
+    to->assign((size_t)n_images, 0);
+    const hipError_t e = hipMemcpyAsync(to->data(), from.ptr, (size_t)n_images * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
+    return e == hipSuccess ? hipStreamSynchronize(stream) : e;
+}
+hipError_t EntropyTail::read_bit_counts(hipStream_t stream, int n_images) {
+    failed = "hipMemcpy(bit counts)";
+    return read_counts(stream, raw_bits, n_images, &h_raw_bits);
+}
+hipError_t EntropyTail::read_lengths(hipStream_t stream, int n_images) {
+    failed = "hipMemcpy(stream lengths)";
+    return read_counts(stream, out_len, n_images, &h_out_len);
+}
+
+hipError_t EntropyTail::plan(hipStream_t stream, DevEncImage *images, int n_images, bool place_raw) {
+    // E3's LDS buffer: twice the largest average stretch a workgroup (256 blocks or restart intervals) of any image writes,
+    // in steps of 4 KB -- the smaller it is the more workgroups share a CU; a workgroup whose stretch does not fit falls back
+    // to atomics in HBM (launch_emit clamps to 8-32 KB).  Images whose AVERAGE stretch is beyond 32 KB (restart intervals of
+    // several MCUs: every lane then writes a stretch of its own and the atomics do not collide) do not count; a batch of
+    // nothing else asks for no LDS at all.
+    emit_words = 0;
+    for (int i = 0; i < n_images; i++) {
+        const uint64_t wgs = ((uint64_t)images[i].n_units + 255) / 256;
+        const uint64_t avg_words = h_raw_bits[(size_t)i] / 32 / std::max<uint64_t>(wgs, 1) + 1;
+        if (avg_words <= kEmitLdsWordsMax) emit_words = std::max<uint64_t>(emit_words, 2 * avg_words);
+    }
+    stuff = plan_stuffing_layout(images, h_raw_bits.data(), n_images, place_raw);
+    const size_t raw_bytes = (size_t)stuff.raw_bytes;
+    const DevUpload grow[] = {{&raw, nullptr, 0, place_raw ? raw_bytes + 256 : 0},
+                              {&marks, nullptr, 0, place_raw ? raw_bytes / 8 + 256 : 0},
+                              {&out, nullptr, 0, (size_t)stuff.out_bytes + 256},
+                              {&chunk_ff, nullptr, 0, (size_t)stuff.chunks * sizeof(uint32_t) + 256},
+                              {&work_chunk, nullptr, 0, stuff.work_chunk.size() * sizeof(EncWork) + 16}};
+    bool copying = false;
+    failed = "hipMalloc";
+    hipError_t e = reserve_and_copy(grow, stream, &copying);
+    if (e != hipSuccess || !place_raw) return e;
+    // (emit_kernel ORs into zeroed words; the one-pass form has one writer per word and no restart marks)
+    failed = "hipMemsetAsync(raw)";
+    e = hipMemsetAsync(raw.ptr, 0, raw_bytes + 256, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(marks.ptr, 0, raw_bytes / 8 + 256, stream);
+    return e;
+}
+
+hipError_t EntropyTail::upload_chunk_work(hipStream_t stream) {
+    failed = "hipMemcpyAsync(chunk work)";
+    return hipMemcpyAsync(work_chunk.ptr, stuff.work_chunk.data(), stuff.work_chunk.size() * sizeof(EncWork), hipMemcpyHostToDevice, stream);
+}
+
+hipError_t EntropyTail::emit(hipStream_t stream, const Source &s) {
+    failed = "emit_kernel";
+    return launch_emit(stream, s.images, s.work_blk, s.n_work_blk, s.tables, s.coefs, (const uint32_t *)bits.ptr, (const uint64_t *)bit_off.ptr,
+                       (const uint64_t *)raw_bits.ptr, (uint8_t *)raw.ptr, (uint32_t *)marks.ptr,
+                       (uint32_t)std::min<uint64_t>((emit_words + 1023) & ~1023ull, kEmitLdsWordsMax), s.layouts, s.any_plain);
+}
+
+hipError_t EntropyTail::stuff_bytes(hipStream_t stream, const DevEncImage *images) {
+    failed = "stuff kernels";
+    return launch_stuff(stream, images, (const EncWork *)work_chunk.ptr, (int)stuff.work_chunk.size(), (const uint64_t *)raw_bits.ptr, (const uint8_t *)raw.ptr,
+                        (const uint32_t *)marks.ptr, (uint32_t *)chunk_ff.ptr, (uint8_t *)out.ptr, (uint64_t *)out_len.ptr);
+}
+
+void EntropyTail::release() {
+    for (DevBuffer *b : {&bits, &bit_off, &raw_bits, &raw, &marks, &chunk_ff, &work_chunk, &out, &out_len}) b->release();
+}
+
 namespace {
 // JpegHuffmanEncodingTable(JpegHuffmanCanonicalCode[]) (ref: JpegHuffmanEncodingTable.cs:21-37), TryWrite (:50-86), GetCode (:94-100)
 void resolve_given_table(const jpgpu_encode_huffman_table &t, EncPlan::Slot *slot) {
@@ -508,9 +593,10 @@ int resolve_encode_description(const jpgpu_encode_description &d, EncPlan *plan,
 EncodeBatch::~EncodeBatch() {
     for (hipEvent_t ev : ev_)
         if (ev) (void)hipEventDestroy(ev);
-    for (DevBuffer *b : {&d_samples_, &d_pixels_, &d_images_, &d_tables_, &d_work_mcu_, &d_work_blk_, &d_work_stat_, &d_work_chunk_, &d_coefs_, &d_bits_, &d_bit_off_,
-                         &d_raw_bits_, &d_raw_, &d_marks_, &d_chunk_ff_, &d_out_, &d_out_len_, &d_hist_, &d_headers_, &d_chain_, &d_work_order_, &d_layouts_})
+    for (DevBuffer *b : {&d_samples_, &d_pixels_, &d_images_, &d_tables_, &d_work_mcu_, &d_work_blk_, &d_work_stat_, &d_coefs_, &d_hist_, &d_headers_, &d_chain_,
+                         &d_work_order_, &d_layouts_})
         b->release();
+    tail_.release();
 }
 
 int EncodeBatch::fail(int status, const std::string &msg) {
@@ -855,12 +941,7 @@ void EncodeBatch::place_table_slots(UploadPlan &up) {
 
 int EncodeBatch::reserve_and_upload(const UploadPlan &up) {
     const size_t n = images_.size();
-    struct Up {
-        DevBuffer *buf;
-        const void *src;
-        size_t bytes, reserve;
-    };
-    const Up ups[] = {
+    const DevUpload ups[] = {
         {&d_tables_, up.tables.data(), up.tables.size() * sizeof(EncHuffTable), 0},
         {&d_hist_, nullptr, 0, (n * 4 + general_.size() * 8) * 256 * sizeof(uint32_t) + 256},
         {&d_layouts_, layouts_.data(), layouts_.size() * sizeof(DevEncLayout), 256},
@@ -868,25 +949,16 @@ int EncodeBatch::reserve_and_upload(const UploadPlan &up) {
         {&d_work_blk_, up.work_blk.data(), up.work_blk.size() * sizeof(EncWork), 0},
         {&d_work_order_, up.work_order.data(), up.work_order.size() * sizeof(uint32_t), 16},
         {&d_work_stat_, up.work_stat.data(), up.work_stat.size() * sizeof(EncWork), 16},
-        {&d_pixels_, nullptr, 0, (size_t)up.px_off + 256},
         {&d_coefs_, nullptr, 0, (size_t)total_blocks_ * 128 + 256},
         {&d_samples_, nullptr, 0, (size_t)up.smp_off + 256},
-        {&d_bits_, nullptr, 0, (size_t)total_blocks_ * sizeof(uint32_t) + 256},
-        {&d_bit_off_, nullptr, 0, up.work_blk.size() * (sizeof(uint64_t) + sizeof(uint32_t)) + 512},  // per workgroup: base (u64) | bits (u32)
-        {&d_raw_bits_, nullptr, 0, n * sizeof(uint64_t) + 256},
-        {&d_out_len_, nullptr, 0, n * sizeof(uint64_t) + 256},
         {&d_images_, nullptr, 0, n * sizeof(DevEncImage) + 256},
     };
-    hipError_t e;
-    for (const Up &u : ups) {
-        if (up.device && u.buf == &d_pixels_) continue;  // (a device upload copies nothing: E1 reads the caller's memory)
-        e = u.buf->reserve(std::max(u.bytes, u.reserve));
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-        if (u.bytes) {
-            e = hipMemcpyAsync(u.buf->ptr, u.src, u.bytes, hipMemcpyHostToDevice, ctx_->stream);
-            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync");
-        }
-    }
+    bool copying = false;
+    hipError_t e = reserve_and_copy(ups, ctx_->stream, &copying);
+    if (e != hipSuccess) return hip_fail(e, copying ? "hipMemcpyAsync" : "hipMalloc");
+    if ((e = tail_.reserve(total_blocks_, up.work_blk.size(), n)) != hipSuccess) return hip_fail(e, tail_.failed);
+    // (a device upload copies nothing: E1 reads the caller's memory)
+    if (!up.device && (e = d_pixels_.reserve((size_t)up.px_off + 256)) != hipSuccess) return hip_fail(e, "hipMalloc");
     for (size_t i = 0; i < n && !up.device; i++) {
         const DevEncImage &im = images_[i];
         if (im.width == 0) continue;  // (a refused arrangement)
@@ -933,10 +1005,7 @@ struct EncodeBatch::EncodeRun {
     int n = 0;                                // images
     const DevEncLayout *layouts = nullptr;    // described images in the upload: their layouts on the device
     bool any_plain = false;                   // EncodeAction arrangements in the upload
-    std::vector<uint64_t> raw_bits;           // per image, once E2 has counted
     bool fused_emit = false;                  // bits_emit_kernel has counted AND written the raw streams
-    uint64_t emit_words = 0;                  // emit_kernel's LDS buffer, in words
-    StuffPlan stuff;
 };
 
 int EncodeBatch::encode() {
@@ -949,7 +1018,7 @@ int EncodeBatch::encode() {
         if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return hip_fail(e, "hipEventCreate");
     r.layouts = layouts_.empty() ? nullptr : (const DevEncLayout *)d_layouts_.ptr;
     r.any_plain = layouts_.size() < images_.size();
-    r.raw_bits.assign((size_t)r.n, 0);
+    tail_.h_raw_bits.assign((size_t)r.n, 0);
     int rc = upload_image_descriptors();
     if (rc != JPGPU_OK) return rc;
     (void)hipEventRecord(ev_[0], ctx_->stream);
@@ -971,7 +1040,7 @@ int EncodeBatch::upload_image_descriptors() {
     hipError_t e = hipMemcpyAsync(d_images_.ptr, images_.data(), images_.size() * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(images)");
     if (n_work_blk_ == 0) {  // nothing but refused arrangements: no kernel counts anything, the streams are empty
-        e = hipMemsetAsync(d_raw_bits_.ptr, 0, images_.size() * sizeof(uint64_t), ctx_->stream);
+        e = hipMemsetAsync(tail_.raw_bits.ptr, 0, images_.size() * sizeof(uint64_t), ctx_->stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(bit counts)");
     }
     return JPGPU_OK;
@@ -1101,9 +1170,9 @@ int EncodeBatch::try_one_pass_emit(EncodeRun &r) {
     // chunk counts and the next upload's buffers are reserved behind them, and a batch that used to encode must not fail there
     // because this one grabbed the rest.  Beyond that the two kernels run.
     size_t free_b = 0, total_b = 0;
-    hipError_t e = (size_t)slot + 256 <= d_raw_.cap ? hipSuccess : hipMemGetInfo(&free_b, &total_b);
-    if (e == hipSuccess && (size_t)slot + 256 > d_raw_.cap && (size_t)slot + 256 > free_b / 3) e = hipErrorOutOfMemory;
-    if (e == hipSuccess) e = d_raw_.reserve((size_t)slot + 256);
+    hipError_t e = (size_t)slot + 256 <= tail_.raw.cap ? hipSuccess : hipMemGetInfo(&free_b, &total_b);
+    if (e == hipSuccess && (size_t)slot + 256 > tail_.raw.cap && (size_t)slot + 256 > free_b / 3) e = hipErrorOutOfMemory;
+    if (e == hipSuccess) e = tail_.raw.reserve((size_t)slot + 256);
     if (e == hipSuccess) e = d_chain_.reserve(chain_bytes + 256);
     if (e != hipSuccess) {  // no room for the worst-case slots: the two kernels size the raw streams from the counts
         (void)hipGetLastError();
@@ -1115,12 +1184,12 @@ int EncodeBatch::try_one_pass_emit(EncodeRun &r) {
     if (e == hipSuccess) e = hipMemcpyAsync(d_images_.ptr, images_.data(), (size_t)r.n * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(images)");
     e = launch_bits_emit(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_blk_.ptr, n_work_blk_, (const EncHuffTable *)d_tables_.ptr,
-                         (const int16_t *)d_coefs_.ptr, (uint8_t *)d_chain_.ptr + 256, (uint32_t *)d_chain_.ptr, (uint8_t *)d_raw_.ptr, (uint64_t *)d_raw_bits_.ptr,
-                         emit_hint_ ? emit_hint_ : 4096u, (const uint32_t *)d_work_order_.ptr);
+                         (const int16_t *)d_coefs_.ptr, (uint8_t *)d_chain_.ptr + 256, (uint32_t *)d_chain_.ptr, (uint8_t *)tail_.raw.ptr,
+                         (uint64_t *)tail_.raw_bits.ptr, emit_hint_ ? emit_hint_ : 4096u, (const uint32_t *)d_work_order_.ptr);
     if (e != hipSuccess) return hip_fail(e, "bits_emit_kernel");
     (void)hipEventRecord(ev_[2], ctx_->stream);
     uint32_t ctl[2] = {0, 0};
-    e = hipMemcpyAsync(r.raw_bits.data(), d_raw_bits_.ptr, (size_t)r.n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
+    e = hipMemcpyAsync(tail_.h_raw_bits.data(), tail_.raw_bits.ptr, (size_t)r.n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(ctl, d_chain_.ptr, sizeof ctl, hipMemcpyDeviceToHost, ctx_->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy(bit counts)");
@@ -1132,55 +1201,29 @@ int EncodeBatch::try_one_pass_emit(EncodeRun &r) {
     return JPGPU_OK;
 }
 
+EntropyTail::Source EncodeBatch::tail_source(const EncodeRun &r) const {
+    return {(const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_blk_.ptr, n_work_blk_, (const EncHuffTable *)d_tables_.ptr, (const int16_t *)d_coefs_.ptr,
+            r.layouts, r.any_plain};
+}
+
 // E2 as its own kernel (E3 follows the stuffing stage's layout: emit_and_stuff)
-int EncodeBatch::count_bits_two_kernels(EncodeRun &r) {
-    uint32_t *wg_bits = reinterpret_cast<uint32_t *>((uint8_t *)d_bit_off_.ptr + (((size_t)n_work_blk_ * sizeof(uint64_t) + 255) & ~(size_t)255));
-    hipError_t e = launch_block_bits(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_blk_.ptr, n_work_blk_,
-                                     (const EncHuffTable *)d_tables_.ptr, (const int16_t *)d_coefs_.ptr, (uint32_t *)d_bits_.ptr, r.n, wg_bits,
-                                     (uint64_t *)d_bit_off_.ptr, (uint64_t *)d_raw_bits_.ptr, r.layouts, r.any_plain);
-    if (e != hipSuccess) return hip_fail(e, "block_bits_kernel");
+int EncodeBatch::count_bits_two_kernels(const EncodeRun &r) {
+    hipError_t e = tail_.count_bits(ctx_->stream, tail_source(r), r.n);
+    if (e != hipSuccess) return hip_fail(e, tail_.failed);
     (void)hipEventRecord(ev_[2], ctx_->stream);
     // the sizes of the raw and finished streams depend on the data: one host round trip
-    e = hipMemcpyAsync(r.raw_bits.data(), d_raw_bits_.ptr, (size_t)r.n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy(bit counts)");
-    return JPGPU_OK;
+    e = tail_.read_bit_counts(ctx_->stream, r.n);
+    return e == hipSuccess ? JPGPU_OK : hip_fail(e, tail_.failed);
 }
 
 // where the stuffing stage reads and writes, E3's LDS buffer, and the buffers both need
-int EncodeBatch::plan_stuffing(EncodeRun &r) {
-    // E3's LDS buffer: twice the largest average stretch a workgroup (256 blocks or restart intervals) of any image writes,
-    // in steps of 4 KB -- the smaller it is the more workgroups share a CU; a workgroup whose stretch does not fit falls back
-    // to atomics in HBM (launch_emit clamps to 8-32 KB).  Images whose AVERAGE stretch is beyond 32 KB (restart intervals of
-    // several MCUs: every lane then writes a stretch of its own and the atomics do not collide) do not count; a batch of
-    // nothing else asks for no LDS at all.
-    for (int i = 0; i < r.n; i++) {
-        const uint64_t wgs = ((uint64_t)images_[i].n_units + 255) / 256;
-        const uint64_t avg_words = r.raw_bits[i] / 32 / std::max<uint64_t>(wgs, 1) + 1;
-        if (avg_words <= kEmitLdsWordsMax) r.emit_words = std::max<uint64_t>(r.emit_words, 2 * avg_words);
-    }
-    // the next encode() of this upload sizes bits_emit_kernel's LDS buffer like emit_kernel's (no stretch would fit: never again)
-    if (emit_hint_ != 0xFFFFFFFFu) emit_hint_ = r.emit_words == 0 ? 0xFFFFFFFFu : (uint32_t)std::min<uint64_t>((r.emit_words + 1023) & ~1023ull, kEmitLdsWordsMax);
+int EncodeBatch::plan_stuffing(const EncodeRun &r) {
     // (the one-pass form has placed and written the raw streams already)
-    r.stuff = plan_stuffing_layout(images_.data(), r.raw_bits.data(), r.n, !r.fused_emit);
-    const size_t raw_bytes = (size_t)r.stuff.raw_bytes;
-    n_work_chunk_ = (int)r.stuff.work_chunk.size();
-    out_cap_ = r.stuff.out_bytes;
-    const struct {
-        DevBuffer *buf;
-        size_t bytes;
-    } grow[] = {{&d_raw_, r.fused_emit ? 0 : raw_bytes + 256}, {&d_marks_, r.fused_emit ? 0 : raw_bytes / 8 + 256}, {&d_out_, (size_t)r.stuff.out_bytes + 256},
-                {&d_chunk_ff_, (size_t)r.stuff.chunks * sizeof(uint32_t) + 256}, {&d_work_chunk_, r.stuff.work_chunk.size() * sizeof(EncWork) + 16}};
-    hipError_t e;
-    for (const auto &g : grow) {
-        e = g.buf->reserve(g.bytes);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    }
-    if (!r.fused_emit) {  // (emit_kernel ORs into zeroed words; the one-pass form has one writer per word and no restart marks)
-        e = hipMemsetAsync(d_raw_.ptr, 0, raw_bytes + 256, ctx_->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_marks_.ptr, 0, raw_bytes / 8 + 256, ctx_->stream);
-        if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(raw)");
-    }
+    const hipError_t e = tail_.plan(ctx_->stream, images_.data(), r.n, !r.fused_emit);
+    if (e != hipSuccess) return hip_fail(e, tail_.failed);
+    // the next encode() of this upload sizes bits_emit_kernel's LDS buffer like emit_kernel's (no stretch would fit: never again)
+    if (emit_hint_ != 0xFFFFFFFFu)
+        emit_hint_ = tail_.emit_words == 0 ? 0xFFFFFFFFu : (uint32_t)std::min<uint64_t>((tail_.emit_words + 1023) & ~1023ull, kEmitLdsWordsMax);
     return JPGPU_OK;
 }
 
@@ -1193,10 +1236,10 @@ int EncodeBatch::place_headers(const EncodeRun &r) {
     }
     hipError_t e = d_headers_.reserve(header_bytes_.size() + 16);
     if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-    e = hipMemcpyAsync(d_work_chunk_.ptr, r.stuff.work_chunk.data(), r.stuff.work_chunk.size() * sizeof(EncWork), hipMemcpyHostToDevice, ctx_->stream);
+    e = tail_.upload_chunk_work(ctx_->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_images_.ptr, images_.data(), (size_t)r.n * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_headers_.ptr, header_bytes_.data(), header_bytes_.size(), hipMemcpyHostToDevice, ctx_->stream);
-    if (e == hipSuccess) e = launch_place_headers(ctx_->stream, (const DevEncImage *)d_images_.ptr, r.n, (const uint8_t *)d_headers_.ptr, (uint8_t *)d_out_.ptr);
+    if (e == hipSuccess) e = launch_place_headers(ctx_->stream, (const DevEncImage *)d_images_.ptr, r.n, (const uint8_t *)d_headers_.ptr, (uint8_t *)tail_.out.ptr);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(headers)");
     return JPGPU_OK;
 }
@@ -1204,23 +1247,12 @@ int EncodeBatch::place_headers(const EncodeRun &r) {
 // E3 (unless the one pass has written the raw streams), E4, and the streams' lengths
 int EncodeBatch::emit_and_stuff(const EncodeRun &r) {
     hipError_t e;
-    if (!r.fused_emit) {
-        e = launch_emit(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_blk_.ptr, n_work_blk_, (const EncHuffTable *)d_tables_.ptr,
-                        (const int16_t *)d_coefs_.ptr, (const uint32_t *)d_bits_.ptr, (const uint64_t *)d_bit_off_.ptr, (const uint64_t *)d_raw_bits_.ptr,
-                        (uint8_t *)d_raw_.ptr, (uint32_t *)d_marks_.ptr, (uint32_t)std::min<uint64_t>((r.emit_words + 1023) & ~1023ull, kEmitLdsWordsMax), r.layouts,
-                        r.any_plain);
-        if (e != hipSuccess) return hip_fail(e, "emit_kernel");
-    }
+    if (!r.fused_emit && (e = tail_.emit(ctx_->stream, tail_source(r))) != hipSuccess) return hip_fail(e, tail_.failed);
     (void)hipEventRecord(ev_[4], ctx_->stream);
-    e = launch_stuff(ctx_->stream, (const DevEncImage *)d_images_.ptr, (const EncWork *)d_work_chunk_.ptr, n_work_chunk_, (const uint64_t *)d_raw_bits_.ptr,
-                     (const uint8_t *)d_raw_.ptr, (const uint32_t *)d_marks_.ptr, (uint32_t *)d_chunk_ff_.ptr, (uint8_t *)d_out_.ptr, (uint64_t *)d_out_len_.ptr);
-    if (e != hipSuccess) return hip_fail(e, "stuff kernels");
+    if ((e = tail_.stuff_bytes(ctx_->stream, (const DevEncImage *)d_images_.ptr)) != hipSuccess) return hip_fail(e, tail_.failed);
     (void)hipEventRecord(ev_[5], ctx_->stream);
-    out_len_.assign((size_t)r.n, 0);
-    e = hipMemcpyAsync(out_len_.data(), d_out_len_.ptr, (size_t)r.n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy(stream lengths)");
-    return JPGPU_OK;
+    e = tail_.read_lengths(ctx_->stream, r.n);
+    return e == hipSuccess ? JPGPU_OK : hip_fail(e, tail_.failed);
 }
 
 int EncodeBatch::stage_ms(float ms[5]) {
@@ -1240,7 +1272,7 @@ int EncodeBatch::encoded_size(int i, size_t *bytes) const {
         ctx_->last_error = messages_[i];
         return status_[i];
     }
-    *bytes = (size_t)out_len_[i];
+    *bytes = (size_t)tail_.h_out_len[i];
     return JPGPU_OK;
 }
 
@@ -1248,8 +1280,8 @@ int EncodeBatch::download(int i, void *dst, size_t cap) {
     if (i < 0 || i >= (int)images_.size() || !dst) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encode_download: bad argument");
     if (!encoded_) return fail(JPGPU_ERR_INVALID_OPERATION, "Nothing has been encoded yet.");
     if (status_[i] != JPGPU_OK) return fail(status_[i], messages_[i]);
-    if (cap < out_len_[i]) return fail(JPGPU_ERR_ARGUMENT, "Destination buffer is too small.");
-    hipError_t e = hipMemcpy(dst, (const uint8_t *)d_out_.ptr + images_[i].out_off, (size_t)out_len_[i], hipMemcpyDeviceToHost);
+    if (cap < tail_.h_out_len[i]) return fail(JPGPU_ERR_ARGUMENT, "Destination buffer is too small.");
+    hipError_t e = hipMemcpy(dst, (const uint8_t *)tail_.out.ptr + images_[i].out_off, (size_t)tail_.h_out_len[i], hipMemcpyDeviceToHost);
     return e == hipSuccess ? JPGPU_OK : hip_fail(e, "hipMemcpy(encoded stream)");
 }
 

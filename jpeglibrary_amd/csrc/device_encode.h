@@ -6,24 +6,11 @@
 #include "../../include/jpgpu.h"
 #include "device_batch.h"
 #include "encode_kernels.h"
+#include "optimize_walk.h"  // put_marker, put_length
 
 namespace jpgpu {
 
 void rgb_ycc_factors(int32_t out[8]);
-
-// JpegWriter.WriteMarker (ref: JpegWriter.cs:289-303) and WriteLength (:309-321: the length counts its own two bytes), for the
-// encoder's byte vectors and the optimizer's strings alike
-template <typename Bytes>
-void put_marker(Bytes &o, int m) {
-    o.push_back((typename Bytes::value_type)0xFF);
-    o.push_back((typename Bytes::value_type)m);
-}
-template <typename Bytes>
-void put_length(Bytes &o, uint16_t length) {
-    const uint16_t v = (uint16_t)(length + 2);
-    o.push_back((typename Bytes::value_type)(v >> 8));
-    o.push_back((typename Bytes::value_type)v);
-}
 
 // The marker segments Encode() writes around the Huffman tables (ref: JpegEncoder.cs:261-280), from the lists the caller's Set* and
 // AddComponent calls left: SOI, DQT, (DRI,) SOF0 into *pre, SOS into *post.
@@ -56,6 +43,36 @@ struct StuffPlan {
     uint32_t chunks = 0;
 };
 StuffPlan plan_stuffing_layout(DevEncImage *images, const uint64_t *raw_bits, int n, bool place_raw);
+
+// E2 -> E3 -> E4 as kernels of their own (block_bits_kernel, emit_kernel, the stuff kernels) over coefficients that lie on the device: the
+// buffers the three hand one another, and one method per step.  What the kernels read beside them is the caller's (a Source); so are the
+// events and the host round trips between the steps.  A step that fails returns HIP's error and leaves the name of the call in `failed`.
+struct EntropyTail {
+    struct Source {
+        const DevEncImage *images;  // on the device
+        const EncWork *work_blk;    // one entry per 256 units of an image
+        int n_work_blk;
+        const EncHuffTable *tables;
+        const int16_t *coefs;
+        const DevEncLayout *layouts;
+        bool any_plain;
+    };
+    DevBuffer bits, bit_off, raw_bits, raw, marks, chunk_ff, work_chunk, out, out_len;  // (bit_off: per workgroup its base (u64) | its bits (u32))
+    std::vector<uint64_t> h_raw_bits, h_out_len;  // per image: what E2 counted, how long the finished stream is
+    StuffPlan stuff;
+    uint64_t emit_words = 0;  // emit_kernel's LDS buffer, in words
+    const char *failed = "";
+    hipError_t reserve(uint64_t total_blocks, size_t n_work_blk, size_t n_images);  // what does not depend on the data
+    hipError_t count_bits(hipStream_t stream, const Source &s, int n_images);
+    hipError_t read_bit_counts(hipStream_t stream, int n_images);  // -> h_raw_bits, the stream synchronised
+    // E3's LDS words, the stuffing stage's layout (into images[]; place_raw false: the raw streams are placed and written already), room for it
+    hipError_t plan(hipStream_t stream, DevEncImage *images, int n_images, bool place_raw);
+    hipError_t upload_chunk_work(hipStream_t stream);
+    hipError_t emit(hipStream_t stream, const Source &s);
+    hipError_t stuff_bytes(hipStream_t stream, const DevEncImage *images);
+    hipError_t read_lengths(hipStream_t stream, int n_images);  // -> h_out_len, the stream synchronised
+    void release();
+};
 
 // A jpgpu_encode_description resolved on the host (no device needed): the reference's checks, the marker segments, the by-symbol
 // Huffman tables and the block map of the general kernels -- or the jpgpu_encode_params of the EncodeAction arrangement it is.
@@ -111,8 +128,8 @@ class EncodeBatch {
     uint32_t total_blocks(int i) const { return (i >= 0 && i < (int)images_.size()) ? images_[i].total_blocks : 0; }
     void *output_device(int i, size_t *bytes) const {
         if (i < 0 || i >= (int)images_.size() || !encoded_) return nullptr;
-        if (bytes) *bytes = (size_t)out_len_[i];
-        return (uint8_t *)d_out_.ptr + images_[i].out_off;
+        if (bytes) *bytes = (size_t)tail_.h_out_len[i];
+        return (uint8_t *)tail_.out.ptr + images_[i].out_off;
     }
 
   private:
@@ -141,9 +158,10 @@ class EncodeBatch {
     int run_fdct(const EncodeRun &r);
     int build_coding_tables(const EncodeRun &r);
     bool build_image_tables(int i, const EncPlan *described, const uint32_t *counters, bool most_optimal, EncHuffTable *tables);
+    EntropyTail::Source tail_source(const EncodeRun &r) const;
     int try_one_pass_emit(EncodeRun &r);
-    int count_bits_two_kernels(EncodeRun &r);
-    int plan_stuffing(EncodeRun &r);
+    int count_bits_two_kernels(const EncodeRun &r);
+    int plan_stuffing(const EncodeRun &r);
     int place_headers(const EncodeRun &r);
     int emit_and_stuff(const EncodeRun &r);
     jpgpu_ctx *ctx_;
@@ -164,14 +182,13 @@ class EncodeBatch {
     bool upload_described_ = false;                    // the last upload was jpgpu_encoder_upload_described
     bool pixels_on_device_ = false;                    // the last upload was a device upload: DevEncImage.px_off is an address, d_pixels_ is not in use
     DevBuffer d_hist_;
-    std::vector<uint64_t> out_len_;
     bool encoded_ = false;
     hipEvent_t ev_[6] = {};
-    uint64_t total_blocks_ = 0, out_cap_ = 0;
-    int n_work_mcu_ = 0, n_work_blk_ = 0, n_work_stat_ = 0, n_work_chunk_ = 0;
+    uint64_t total_blocks_ = 0;
+    int n_work_mcu_ = 0, n_work_blk_ = 0, n_work_stat_ = 0;
     DevBuffer d_samples_;  // E1a -> E1b: gathered samples, enc_sample_bytes_per_mcu per MCU
-    DevBuffer d_pixels_, d_images_, d_tables_, d_work_mcu_, d_work_blk_, d_work_stat_, d_work_chunk_, d_coefs_, d_bits_, d_bit_off_, d_raw_bits_, d_raw_, d_marks_,
-        d_chunk_ff_, d_out_, d_out_len_, d_headers_;
+    DevBuffer d_pixels_, d_images_, d_tables_, d_work_mcu_, d_work_blk_, d_work_stat_, d_coefs_, d_headers_;
+    EntropyTail tail_;  // E2 .. E4 behind them
     std::vector<uint8_t> header_bytes_;  // every image's SOI..SOS, concatenated (one upload per encode)
     // E2 + E3 as one pass (bits_emit_kernel): restart-free uploads only; the LDS stretch buffer is sized from the previous encode()
     // of this upload (0: not known yet; 0xFFFFFFFF: a stretch did not fit or a wait ran out -- the two-kernel path from then on)

@@ -344,14 +344,19 @@ void optimal_codes_to_table(const std::vector<OptimalCode> &codes, EncHuffTable 
 }
 
 // ------------------------------------------------------------------------------------------------ batch
+void OptimizeBatch::Road::release() {
+    batch.reset();
+    for (DevBuffer *b : {&d_turn_images, &d_turn_work, &d_coefs, &d_images, &d_layouts, &d_work_blk, &d_work_stat, &d_hist, &d_tables}) b->release();
+    tail.release();
+}
+
 OptimizeBatch::~OptimizeBatch() {
     for (DevBuffer *b : {&d_work_, &d_scan_ids_, &d_hist_, &d_enc_, &d_sizes_, &d_offsets_, &d_base_, &d_totals_, &d_out_, &d_sub_work_,
                          &d_sub_scan_ids_, &d_sub_bits_, &d_sub_bitoff_, &d_sub_totals_, &d_scan_raw_off_, &d_raw_, &d_simages_, &d_swork_chunk_,
-                         &d_chunk_ff_, &d_sout_, &d_sout_len_, &d_turn_images_, &d_turn_work_, &d_tcoefs_, &d_timages_, &d_tlayouts_, &d_twork_blk_,
-                         &d_twork_stat_, &d_thist_, &d_ttables_, &d_tbits_, &d_tbit_off_, &d_traw_bits_, &d_traw_, &d_tmarks_, &d_tchunk_ff_,
-                         &d_twork_chunk_, &d_tout_, &d_tout_len_})
+                         &d_chunk_ff_, &d_sout_, &d_sout_len_})
         b->release();
-    for (hipEvent_t ev : {ev0_, ev1_, ev_kx0_, ev_kx1_, ev_td_[0], ev_td_[1], ev_td_[2]})
+    road_.release();
+    for (hipEvent_t ev : {ev0_, ev1_, road_.ev_kx[0], road_.ev_kx[1], road_.ev_td[0], road_.ev_td[1], road_.ev_td[2]})
         if (ev) (void)hipEventDestroy(ev);
 }
 int OptimizeBatch::fail(int status, const std::string &msg) {
@@ -362,368 +367,109 @@ int OptimizeBatch::hip_fail(hipError_t e, const char *what) {
     return fail(JPGPU_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-namespace {
-struct Refuse {
-    int status, detail;
-    std::string msg;
+// what upload()'s stages hand one another
+struct OptimizeBatch::Upload {
+    const uint8_t *const *jpeg;
+    const size_t *len;
+    int n;
+    bool strip;
+    std::vector<uint8_t> given;       // the orientations of THIS upload (empty: every image by the policy)
+    std::vector<jpgpu_rect> windows;  // ... and its windows (empty: none)
+    std::vector<int> turned;          // the images that take the coefficient road, in order
 };
-[[noreturn]] void refuse(int status, const std::string &msg, int detail = 0) { throw Refuse{status, detail, msg}; }
-std::string at_offset(int off, const char *msg) { return "Failed to decode JPEG data at offset " + std::to_string(off) + ". " + msg; }
-}  // namespace
-
-// find_scan_end of the scan the walks of one file keep coming back to (four walks, one search)
-size_t OptimizeBatch::scan_end(const uint8_t *entropy, size_t len) {
-    if (entropy != end_key_ || len != end_len_) {
-        end_key_ = entropy;
-        end_len_ = len;
-        end_rsts_.clear();
-        end_val_ = find_scan_end(entropy, len, &end_rsts_);
-    }
-    return end_val_;
-}
-
-// Scan()'s and Optimize()'s marker walks (JpegOptimizer.cs:66-153, :540-648) on the host.  Leaves the pieces of the
-// output in p.pieces; the scan itself is located for the device passes.
-void OptimizeBatch::plan_file(Plan &p, const uint8_t *data, size_t len, bool strip, bool swallow_terminator, bool turned) {
-    // ---- Scan(): tables, frame, restart interval as of the scan; exactly one scan
-    std::vector<QuantTable> quant;  // _quantizationTables: replace by identifier, else append (:319-338)
-    bool after_scan = false;  // from here on a failure of the walks is only met once the scan itself went through
-    try {
-    bool have_frame = false;
-    FrameHeader frame;
-    int n_scans = 0;
-    uint16_t dri = 0, dri_at_scan = 0;
-    {
-        if (len == 0) refuse(JPGPU_ERR_INVALID_OPERATION, "Input buffer is not specified.");
-        MarkerReader r(data, len);
-        bool eoi = false;
-        while (!eoi && !r.is_empty()) {
-            int marker;
-            if (!r.try_read_marker(&marker)) refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "No marker found."));
-            uint16_t length;
-            const uint8_t *buf;
-            auto segment = [&]() {
-                if (!r.try_read_length(&length))
-                    refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Unexpected end of input data when reading segment length."));
-                if (!r.try_read_bytes(length, &buf))
-                    refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Unexpected end of input data when reading segment content."));
-            };
-            switch (marker) {
-            case 0xD8: break;
-            case 0xC0:
-            case 0xC1: {
-                segment();
-                FrameHeader fh;
-                int consumed = 0;
-                if (!FrameHeader::try_parse(buf, length, false, &fh, &consumed))
-                    refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count() - length + consumed, "Failed to parse frame header."));
-                if (have_frame) refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Multiple frame is not supported."));
-                have_frame = true;
-                frame = fh;
-                break;
-            }
-            // StartOfFrame2 is not among Scan()'s cases (:95-146): a progressive frame header is skipped like an APPn segment and
-            // the first SOS then finds no frame header (the null reference below)
-            case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
-                refuse(JPGPU_ERR_INVALID_DATA,
-                       at_offset(r.consumed_byte_count(), ("This type of JPEG stream is not supported (StartOfFrame" + std::to_string(marker - 0xC0) + ").").c_str()),
-                       kDetailUnsupportedFrame);
-            case 0xC4: {
-                // The decoding tables themselves are the decoder-side parser's business (batch_), but a table that does not parse
-                // ends Scan() HERE (JpegOptimizer.cs ProcessDefineHuffmanTable), in front of whatever a later marker would have
-                // thrown -- e.g. the missing frame header at SOS when a bit flip made the SOF marker a DHT
-                // (tests/golden/stress/optimizer_dht_in_place_of_sof_*.jpg)
-                segment();
-                const uint8_t *tb = buf;
-                size_t rem = length;
-                int off = r.consumed_byte_count() - length;
-                while (rem != 0) {
-                    HuffTable t;
-                    int consumed = 0;
-                    if (!HuffTable::try_parse(tb, rem, &t, &consumed)) refuse(JPGPU_ERR_INVALID_DATA, at_offset(off, "Failed to parse Huffman table."));
-                    tb += consumed;
-                    rem -= (size_t)consumed;
-                    off += consumed;
-                }
-                break;
-            }
-            case 0xDB: {
-                segment();
-                const int base = r.consumed_byte_count() - length;
-                int off = 0;
-                while (off < (int)length) {
-                    QuantTable t;
-                    int consumed = 0;
-                    if (!QuantTable::try_parse(buf + off, (size_t)length - off, &t, &consumed))
-                        refuse(JPGPU_ERR_INVALID_DATA, at_offset(base + off, "Failed to parse quantization table."));
-                    off += consumed;
-                    bool replaced = false;
-                    for (QuantTable &q : quant)
-                        if (q.identifier == t.identifier) {
-                            q = t;
-                            replaced = true;
-                        }
-                    if (!replaced) quant.push_back(t);
-                }
-                break;
-            }
-            case 0xDD:
-                segment();
-                if (length < 2)
-                    refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Unexpected end of input data when reading segment content."));
-                dri = (uint16_t)(buf[0] << 8 | buf[1]);
-                break;
-            case 0xDA: {
-                segment();
-                if (!have_frame) refuse(JPGPU_ERR_INVALID_OPERATION, "Object reference not set to an instance of an object.");
-                if (++n_scans > 1)
-                    refuse(JPGPU_ERR_NOT_SUPPORTED, "Files with more than one scan are not supported by the optimizer path.", kDetailUnsupportedFrame);
-                dri_at_scan = dri;
-                p.dri_at_scan = dri;
-                after_scan = true;
-                const size_t end = scan_end(r.remaining_bytes(), (size_t)r.remaining_byte_count());
-                r.try_advance((int)end + (swallow_terminator && end < (size_t)r.remaining_byte_count() ? 1 : 0));
-                break;
-            }
-            case 0xD0: case 0xD1: case 0xD2: case 0xD3: case 0xD4: case 0xD5: case 0xD6: case 0xD7: break;
-            case 0xD9: eoi = true; break;
-            default:
-                if (!r.try_read_length(&length))
-                    refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Unexpected end of input data when reading segment length."));
-                if (!r.try_advance(length))
-                    refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Unexpected end of input data reached."));
-                break;
-            }
-        }
-        if (n_scans == 0) refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "No image data is read."));
-        if (dri_at_scan != dri)
-            refuse(JPGPU_ERR_NOT_SUPPORTED, "A restart interval that changes after the scan is not supported by the optimizer path.", kDetailUnsupportedFrame);
-    }
-    // ---- Optimize(strip)
-    MarkerReader r(data, len);
-    std::string cur;
-    auto flush = [&]() {
-        if (!cur.empty()) p.pieces.push_back({Piece::kBytes, cur});
-        cur.clear();
-    };
-    auto copy_segment = [&](const uint8_t **bytes, uint16_t *n) {  // CopyMarkerData (:661-675)
-        uint16_t length;
-        const uint8_t *buf;
-        if (!r.try_read_length(&length))
-            refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Unexpected end of input data when reading segment length."));
-        if (!r.try_read_bytes(length, &buf))
-            refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Unexpected end of input data when reading segment content."));
-        put_length(cur, length);
-        cur.append((const char *)buf, length);
-        if (bytes) *bytes = buf;
-        if (n) *n = length;
-    };
-    bool eoi = false, dht_written = false, dqt_written = false;
-    while (!eoi && !r.is_empty()) {
-        int marker;
-        if (!r.try_read_marker(&marker)) refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "No marker found."));
-        switch (marker) {
-        case 0xD8: put_marker(cur, marker); break;
-        case 0xE0:
-        case 0xC0:
-        case 0xC1:
-            put_marker(cur, marker);
-            copy_segment(nullptr, nullptr);
-            break;
-        case 0xC2: {  // ProcessFrameHeader, then "not supported" (:580-582).  Reached on baseline files too: the walk does not
-                      // skip the DQT / DHT payloads, and a quantisation table may hold the bytes FF C2 (low qualities)
-            uint16_t length;
-            const uint8_t *buf;
-            if (!r.try_read_length(&length))
-                refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Unexpected end of input data when reading segment length."));
-            if (!r.try_read_bytes(length, &buf))
-                refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Unexpected end of input data when reading segment content."));
-            FrameHeader fh;
-            int consumed = 0;
-            if (!FrameHeader::try_parse(buf, length, false, &fh, &consumed))
-                refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count() - length + consumed, "Failed to parse frame header."));
-            refuse(JPGPU_ERR_INVALID_DATA, "Progressive JPEG is not supported currently.");
-        }
-        case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
-            refuse(JPGPU_ERR_INVALID_DATA,
-                   at_offset(r.consumed_byte_count(), ("This type of JPEG stream is not supported (StartOfFrame" + std::to_string(marker - 0xC0) + ").").c_str()));
-        case 0xC4:  // the segment's own bytes are not skipped: the marker search runs through them (:596-602)
-            if (!dht_written) {
-                flush();
-                p.pieces.push_back({Piece::kHuffmanTables, std::string()});
-                dht_written = true;
-            }
-            break;
-        case 0xDB:
-            if (!dqt_written) {
-                put_marker(cur, 0xDB);
-                uint16_t total = 0;
-                for (const QuantTable &q : quant) total = (uint16_t)(total + (uint8_t)(q.precision == 0 ? 65 : 129));
-                put_length(cur, total);
-                for (const QuantTable &q : quant) {
-                    cur.push_back((char)(q.precision << 4 | (q.identifier & 0xF)));
-                    for (int k = 0; k < 64; k++) {
-                        if (q.precision != 0) cur.push_back((char)(q.elements[k] >> 8));
-                        cur.push_back((char)q.elements[k]);
-                    }
-                }
-                dqt_written = true;
-            }
-            break;
-        case 0xDA: {
-            put_marker(cur, marker);
-            copy_segment(nullptr, nullptr);
-            flush();
-            p.pieces.push_back({Piece::kEntropy, std::string()});
-            const size_t end = scan_end(r.remaining_bytes(), (size_t)r.remaining_byte_count());
-            {
-                // More RSTn markers than the frame's intervals need: the scan stops behind its last MCU and the walk meets
-                // the others as markers of their own, copied one by one (:603-612).  The first of them depends on where
-                // the bit reader stood (transcode_kernel decides it), the rest are certain.
-                int max_h = 1, max_v = 1;
-                for (const FrameComponent &c : frame.components) {
-                    max_h = std::max(max_h, (int)c.h);
-                    max_v = std::max(max_v, (int)c.v);
-                }
-                const uint64_t mcus = (uint64_t)((frame.samples_per_line + 8 * max_h - 1) / (8 * max_h)) * ((frame.lines + 8 * max_v - 1) / (8 * max_v));
-                const uint64_t intervals = dri_at_scan ? (mcus + dri_at_scan - 1) / dri_at_scan : 1;
-                p.rsts_in_scan = end_rsts_.size();
-                // (a turned image: `data` is F' with the SOURCE's scan still behind its header; the scan of F' itself is written
-                // from the turned blocks and holds exactly the markers its intervals need)
-                for (size_t k = (size_t)intervals; !turned && k < end_rsts_.size(); k++) put_marker(cur, (uint8_t)end_rsts_[k]);
-            }
-            r.try_advance((int)end + (swallow_terminator && end < (size_t)r.remaining_byte_count() ? 1 : 0));
-            break;
-        }
-        case 0xD0: case 0xD1: case 0xD2: case 0xD3: case 0xD4: case 0xD5: case 0xD6: case 0xD7: put_marker(cur, marker); break;
-        case 0xD9:
-            put_marker(cur, 0xD9);
-            eoi = true;
-            break;
-        default:
-            if (strip) {
-                uint16_t length;
-                if (!r.try_read_length(&length))
-                    refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Unexpected end of input data when reading segment length."));
-                if (!r.try_advance(length))
-                    refuse(JPGPU_ERR_INVALID_DATA, at_offset(r.consumed_byte_count(), "Unexpected end of input data when reading segment content."));
-            } else {
-                put_marker(cur, marker);
-                copy_segment(nullptr, nullptr);
-            }
-            break;
-        }
-    }
-    flush();
-    } catch (const Refuse &e) {
-        if (!after_scan || e.status == JPGPU_ERR_NOT_SUPPORTED) throw;
-        p.late_status = e.status;
-        p.late_detail = e.detail;
-        p.late_error = e.msg;
-        p.pieces.clear();
-    }
-}
 
 int OptimizeBatch::upload(const uint8_t *const *jpeg, const size_t *len, int n, int strip) {
     if (n < 0 || (n > 0 && (!jpeg || !len))) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_upload: bad arguments");
     plans_.clear();
     ran_ = false;
-    std::vector<uint8_t> given;  // the orientations of THIS upload (empty: every image by the policy)
-    given.swap(pending_orientations_);
-    const bool with_list = orientations_pending_;
-    orientations_pending_ = false;
-    std::vector<jpgpu_rect> windows;  // ... and its windows (empty: none)
-    windows.swap(pending_windows_);
-    const bool with_windows = windows_pending_;
-    windows_pending_ = false;
-    if (with_list && (int)given.size() != n)
-        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_upload: the upload's n differs from the orientations' n (jpgpu_optimizer_set_orientations)");
-    if (with_windows && (int)windows.size() != n)
-        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_upload: the upload's n differs from the windows' n (jpgpu_optimizer_set_windows)");
-    plans_.assign((size_t)n, Plan());
-    for (int i = 0; i < n; i++) {
-        try {
-            plan_file(plans_[i], jpeg[i], len[i], strip != 0);
-            plan_turned_image(plans_[i], jpeg[i], len[i], strip != 0, with_list ? given[(size_t)i] : 0, with_windows ? &windows[(size_t)i] : nullptr);
-        } catch (const Refuse &e) {
-            plans_[i].status = e.status;
-            plans_[i].detail = e.detail;
-            plans_[i].error = e.msg;
-            plans_[i].pieces.clear();
-        }
-        if (plans_[i].status == JPGPU_OK) {
-            // the same walks with the reader resuming inside the scan's terminating marker: only the verdict is kept (a
-            // walk that still goes through would write a different file: refused)
-            Plan &p = plans_[i];
-            Plan alt;
-            p.swallow_status = JPGPU_ERR_NOT_SUPPORTED;
-            p.swallow_detail = kDetailUnsupportedFrame;
-            p.swallow_error = "A scan that leaves one byte unread in front of its terminating marker is not supported by the optimizer path.";
-            try {
-                plan_file(alt, jpeg[i], len[i], strip != 0, true);
-                if (alt.late_status != JPGPU_OK) {
-                    p.swallow_status = alt.late_status;
-                    p.swallow_detail = alt.late_detail;
-                    p.swallow_error = alt.late_error;
-                }
-            } catch (const Refuse &e) {
-                if (e.status != JPGPU_ERR_NOT_SUPPORTED) {
-                    p.swallow_status = e.status;
-                    p.swallow_detail = e.detail;
-                    p.swallow_error = e.msg;
-                }
-            }
-        }
-    }
-    // the decoder-side parser resolves the scan (tables, geometry, restart interval) and lays the files out in HBM
-    batch_.set_entropy_only(true);
-    {
-        std::vector<int> dri((size_t)n, 0);
-        std::vector<uint8_t> no_subseq((size_t)n, 0);
-        for (int i = 0; i < n; i++) {
-            dri[i] = plans_[i].dri_at_scan;
-            no_subseq[i] = plans_[i].rsts_in_scan != 0;  // RSTn behind the last block: the interval kernel knows what to do
-        }
-        batch_.set_preset_restart_intervals(std::move(dri));
-        batch_.set_preset_no_subseq(std::move(no_subseq));
-    }
-    int rc = batch_.upload_files(jpeg, len, n, JPGPU_FMT_PLANAR_U8);
+    Upload u{jpeg, len, n, strip != 0, {}, {}, {}};
+    int rc = take_pending_lists(u);
     if (rc != JPGPU_OK) return rc;
+    plans_.assign((size_t)n, Plan());
+    plan_on_host(u);
+    if ((rc = hand_files_to_decoder(u)) != JPGPU_OK) return rc;
+    admit_and_sort(u);
+    if ((rc = plan_road(u)) != JPGPU_OK) return rc;
+    return reserve_and_upload();
+}
+
+int OptimizeBatch::take_pending_lists(Upload &u) {
+    u.given.swap(pending_orientations_);
+    u.windows.swap(pending_windows_);
+    if (!u.given.empty() && (int)u.given.size() != u.n)
+        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_upload: the upload's n differs from the orientations' n (jpgpu_optimizer_set_orientations)");
+    if (!u.windows.empty() && (int)u.windows.size() != u.n)
+        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_upload: the upload's n differs from the windows' n (jpgpu_optimizer_set_windows)");
+    return JPGPU_OK;
+}
+
+// the marker walks (optimize_walk.h), the plan of the lossless transform, the swallowed-terminator verdict
+void OptimizeBatch::plan_on_host(const Upload &u) {
+    for (int i = 0; i < u.n; i++) {
+        Plan &p = plans_[(size_t)i];
+        ScanEndCache ends;
+        try {
+            walk_file(p, ends, u.jpeg[i], u.len[i], u.strip);
+            plan_turned_image(p, u.jpeg[i], u.len[i], u.strip, u.given.empty() ? 0 : u.given[(size_t)i], u.windows.empty() ? nullptr : &u.windows[(size_t)i]);
+        } catch (const Refuse &e) {
+            p.refused(e);
+        }
+        if (p.status == JPGPU_OK) walk_swallowed_terminator(p, ends, u.jpeg[i], u.len[i], u.strip);
+    }
+}
+
+// the decoder-side parser resolves the scan (tables, geometry, restart interval) and lays the files out in HBM
+int OptimizeBatch::hand_files_to_decoder(const Upload &u) {
+    batch_.set_entropy_only(true);
+    std::vector<int> dri((size_t)u.n, 0);
+    std::vector<uint8_t> no_subseq((size_t)u.n, 0);
+    for (int i = 0; i < u.n; i++) {
+        dri[i] = plans_[i].dri_at_scan;
+        no_subseq[i] = plans_[i].rsts_in_scan != 0;  // RSTn behind the last block: the interval kernel knows what to do
+    }
+    batch_.set_preset_restart_intervals(std::move(dri));
+    batch_.set_preset_no_subseq(std::move(no_subseq));
+    return batch_.upload_files(u.jpeg, u.len, u.n, JPGPU_FMT_PLANAR_U8);
+}
+
+// what the decoder-side batch made of each file decides whether the image is taken, and which kernels transcode it
+void OptimizeBatch::admit_and_sort(Upload &u) {
     scan_ids_.clear();
     work_.clear();
     sub_scan_ids_.clear();
     sub_work_.clear();
     // the images of the coefficient road: Scan()'s pass decides their status, nothing of it is emitted
     std::vector<HuffWork> counted_only, sub_counted_only;
-    for (int i = 0; i < n; i++) {
+    const auto refuse_image = [](Plan &p, const char *msg) {
+        p.status = JPGPU_ERR_NOT_SUPPORTED;
+        p.detail = kDetailUnsupportedFrame;
+        p.error = msg;
+        p.job = -1;
+    };
+    for (int i = 0; i < u.n; i++) {
         Plan &p = plans_[i];
         if (p.status != JPGPU_OK) continue;
         const ImagePlan *img = batch_.image(i);
         if (img->status != JPGPU_OK) {
-            p.status = img->status;
-            p.detail = img->detail;
-            p.error = img->error;
+            static_cast<Verdict &>(p) = {img->status, img->detail, img->error};
             continue;
         }
         if (img->jobs.size() != 1 || batch_.jobs_[img->jobs[0]].kind != kScanSequential) {
-            p.status = JPGPU_ERR_NOT_SUPPORTED;
-            p.detail = kDetailUnsupportedFrame;
-            p.error = "Only single-scan baseline files are supported by the optimizer path.";
+            refuse_image(p, "Only single-scan baseline files are supported by the optimizer path.");
             continue;
         }
         p.job = img->jobs[0];
         const DevScan &s = batch_.h_scans_[p.job];
         if ((int)s.dri != p.dri_at_scan) {  // a DRI segment in front of the frame header that a later one overrides
-            p.status = JPGPU_ERR_NOT_SUPPORTED;
-            p.detail = kDetailUnsupportedFrame;
-            p.error = "A restart interval that changes between the frame header and the scan is not supported by the optimizer path.";
-            p.job = -1;
+            refuse_image(p, "A restart interval that changes between the frame header and the scan is not supported by the optimizer path.");
             continue;
         }
         p.by_subsequence = s.n_subs != 0;  // the batch marks DRI = 0 scans for the self-synchronising subsequence machinery
                                            // (not those with RSTn markers in the data: upload() asks for the interval path)
         const bool turned = p.transform.coefficient_road();
-        if (!turned) {  // (jpgpu_optimizer_image_transform: the frame as it is)
+        if (turned) {
+            u.turned.push_back(i);
+        } else {  // (jpgpu_optimizer_image_transform: the frame as it is)
             const ScanJob &job = batch_.jobs_[p.job];
             p.transform.out_width = img->width;
             p.transform.out_height = img->height;
@@ -745,14 +491,11 @@ int OptimizeBatch::upload(const uint8_t *const *jpeg, const size_t *len, int n, 
     n_sub_work_emit_ = (int)sub_work_.size();
     work_.insert(work_.end(), counted_only.begin(), counted_only.end());
     sub_work_.insert(sub_work_.end(), sub_counted_only.begin(), sub_counted_only.end());
-    if ((rc = upload_turned(jpeg, len)) != JPGPU_OK) return rc;
-    struct Up {
-        DevBuffer *buf;
-        const void *src;
-        size_t bytes, reserve;
-    };
+}
+
+int OptimizeBatch::reserve_and_upload() {
     const size_t n_jobs = batch_.h_scans_.size();
-    const Up ups[] = {
+    const DevUpload ups[] = {
         {&d_work_, work_.data(), work_.size() * sizeof(HuffWork), 0},
         {&d_scan_ids_, scan_ids_.data(), scan_ids_.size() * sizeof(uint32_t), 0},
         {&d_hist_, nullptr, 0, n_jobs * kMaxHuffSlots * 256 * sizeof(uint32_t) + 256},
@@ -770,15 +513,9 @@ int OptimizeBatch::upload(const uint8_t *const *jpeg, const size_t *len, int n, 
         {&d_simages_, nullptr, 0, sub_scan_ids_.size() * sizeof(DevEncImage) + 256},
         {&d_sout_len_, nullptr, 0, sub_scan_ids_.size() * sizeof(uint64_t) + 256},
     };
-    for (const Up &u : ups) {
-        hipError_t e = u.buf->reserve(std::max(u.bytes, u.reserve));
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-        if (u.bytes) {
-            e = hipMemcpyAsync(u.buf->ptr, u.src, u.bytes, hipMemcpyHostToDevice, ctx_->stream);
-            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(optimizer work)");
-        }
-    }
-    return JPGPU_OK;
+    bool copying = false;
+    const hipError_t e = reserve_and_copy(ups, ctx_->stream, &copying);
+    return e == hipSuccess ? JPGPU_OK : hip_fail(e, copying ? "hipMemcpyAsync(optimizer work)" : "hipMalloc");
 }
 
 // what run()'s stages hand one another
@@ -787,8 +524,7 @@ struct OptimizeBatch::Run {
     int n_work = 0, n_scans = 0, n_sub_work = 0, n_sub_scans = 0, n_slots = 0;  // (work: what is measured and emitted ...
     int n_work_counted = 0, n_sub_work_counted = 0;                             // ... and what is counted: the turned images' too)
     int n_turned = 0;
-    const int16_t *turn_src = nullptr;  // the dense store of turn_batch_
-    std::vector<uint64_t> traw_bits;    // per turned image
+    const int16_t *turn_src = nullptr;  // the dense store of road_.batch
     const uint8_t *udata = nullptr, *input = nullptr;
     const DevScan *scans = nullptr;
     DevScanStatus *status = nullptr;
@@ -802,12 +538,8 @@ struct OptimizeBatch::Run {
 
 int OptimizeBatch::run() {
     ran_ = false;
-    if (!ev0_) {
-        if (hipEventCreate(&ev0_) != hipSuccess || hipEventCreate(&ev1_) != hipSuccess || hipEventCreate(&ev_kx0_) != hipSuccess ||
-            hipEventCreate(&ev_kx1_) != hipSuccess || hipEventCreate(&ev_td_[0]) != hipSuccess || hipEventCreate(&ev_td_[1]) != hipSuccess ||
-            hipEventCreate(&ev_td_[2]) != hipSuccess)
-            return fail(JPGPU_ERR_DEVICE, "hipEventCreate");
-    }
+    for (hipEvent_t *ev : {&ev0_, &ev1_, &road_.ev_kx[0], &road_.ev_kx[1], &road_.ev_td[0], &road_.ev_td[1], &road_.ev_td[2]})
+        if (!*ev && hipEventCreate(ev) != hipSuccess) return fail(JPGPU_ERR_DEVICE, "hipEventCreate");
     (void)hipEventRecord(ev0_, ctx_->stream);
     int rc = batch_.run_marker_index();
     if (rc != JPGPU_OK) return rc;
@@ -818,8 +550,8 @@ int OptimizeBatch::run() {
     r.n_scans = (int)scan_ids_.size();
     r.n_sub_work = n_sub_work_emit_;
     r.n_sub_work_counted = (int)sub_work_.size();
-    r.n_turned = (int)timages_.size();
-    last_turn_ms_ = last_turn_decode_ms_ = last_turn_dense_ms_ = 0;
+    r.n_turned = (int)road_.images.size();
+    road_.ms[0] = road_.ms[1] = road_.ms[2] = 0;
     r.n_sub_scans = (int)sub_scan_ids_.size();
     r.n_slots = batch_.n_huff_slots_;
     r.udata = (const uint8_t *)batch_.d_unstuffed_.ptr;
@@ -845,9 +577,9 @@ int OptimizeBatch::run() {
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     (void)hipEventElapsedTime(&last_ms_, ev0_, ev1_);
     if (r.n_turned) {
-        (void)hipEventElapsedTime(&last_turn_ms_, ev_kx0_, ev_kx1_);
-        (void)hipEventElapsedTime(&last_turn_decode_ms_, ev_td_[0], ev_td_[1]);
-        (void)hipEventElapsedTime(&last_turn_dense_ms_, ev_td_[1], ev_td_[2]);
+        (void)hipEventElapsedTime(&road_.ms[0], road_.ev_kx[0], road_.ev_kx[1]);
+        (void)hipEventElapsedTime(&road_.ms[1], road_.ev_td[0], road_.ev_td[1]);
+        (void)hipEventElapsedTime(&road_.ms[2], road_.ev_td[1], road_.ev_td[2]);
     }
     collect_lengths(r);
     ran_ = true;
@@ -877,46 +609,46 @@ int OptimizeBatch::count_symbols(Run &r) {
     return JPGPU_OK;
 }
 
-// ---- BuildTables (:462): one table per (class, identifier) in builder-creation order == the job's slot order
+// ---- BuildTables (:462) of one image: one table per (class, identifier) in builder-creation order == the job's slot order, and the DHT
+// segment they make
+void OptimizeBatch::build_image_tables(Plan &p, const uint32_t *hist, EncHuffTable *enc) const {
+    const ScanJob &job = batch_.jobs_[p.job];
+    std::vector<uint8_t> body;
+    for (int t = 0; t < job.n_huff; t++) {
+        std::vector<OptimalCode> codes;
+        const uint32_t *freq = hist + (size_t)t * 256;
+        if (!build_optimal_table(freq, &codes, most_optimal_)) {
+            // No symbol counted: a failing scan (reported from the device status below, which comes first), or a component
+            // without blocks -- a sampling factor of zero, which JpegOptimizer never divides by -- whose builders stay empty:
+            // Build() throws "No symbol is recorded." (tests/golden/stress/optimizer_component_without_blocks_421.jpg).
+            // Symbols counted and no table: the reference's byte counters overflowed (build_optimal_table) -- its Build() dies
+            // with IndexOutOfRangeException.
+            bool any = false;
+            for (int sym = 0; sym < 256; sym++) any |= freq[sym] != 0;
+            if (!p.build_failed) {  // behind the scan's own failures (BuildTables runs after ProcessScanBaseline, :462), in front of
+                                    // what the markers behind the scan throw (`late` as the walk left it); first builder wins
+                p.build_failed = true;
+                p.late = {JPGPU_ERR_INVALID_OPERATION, 0, any ? "Index was outside the bounds of the array." : "No symbol is recorded."};
+            }
+            continue;
+        }
+        // JpegHuffmanEncodingTableCollection.Write (:172-190): Tc/Th, then the table's own bytes
+        body.push_back((uint8_t)(job.huff_copy[t].table_class << 4 | (job.huff_copy[t].identifier & 0xF)));
+        optimal_codes_to_table(codes, &enc[t], &body);
+    }
+    p.dht.clear();
+    put_marker(p.dht, 0xC4);
+    put_length(p.dht, (uint16_t)body.size());
+    p.dht.append(body.begin(), body.end());
+}
+
 int OptimizeBatch::build_tables(Run &r) {
     std::vector<EncHuffTable> enc(r.n_jobs * kMaxHuffSlots);
     memset(enc.data(), 0, enc.size() * sizeof(EncHuffTable));
-    for (Plan &p : plans_) {
-        if (p.status != JPGPU_OK || p.job < 0) continue;
-        const ScanJob &job = batch_.jobs_[p.job];
-        std::vector<uint8_t> body;
-        for (int t = 0; t < job.n_huff; t++) {
-            std::vector<OptimalCode> codes;
-            const uint32_t *freq = &h_hist_[((size_t)p.job * kMaxHuffSlots + t) * 256];
-            if (!build_optimal_table(freq, &codes, most_optimal_)) {
-                // No symbol counted: a failing scan (reported from the device status below, which comes first), or a component
-                // without blocks -- a sampling factor of zero, which JpegOptimizer never divides by -- whose builders stay empty:
-                // Build() throws "No symbol is recorded." (tests/golden/stress/optimizer_component_without_blocks_421.jpg).
-                // Symbols counted and no table: the reference's byte counters overflowed (build_optimal_table) -- its Build() dies
-                // with IndexOutOfRangeException.
-                bool any = false;
-                for (int sym = 0; sym < 256; sym++) any |= freq[sym] != 0;
-                if (!p.build_failed) {  // behind the scan's own failures (BuildTables runs after ProcessScanBaseline, :462), in front of
-                                        // what the markers behind the scan throw (late_status as the walk left it); first builder wins
-                    p.build_failed = true;
-                    p.late_status = JPGPU_ERR_INVALID_OPERATION;
-                    p.late_detail = 0;
-                    p.late_error = any ? "Index was outside the bounds of the array." : "No symbol is recorded.";
-                }
-                continue;
-            }
-            // JpegHuffmanEncodingTableCollection.Write (:172-190): Tc/Th, then the table's own bytes
-            body.push_back((uint8_t)(job.huff_copy[t].table_class << 4 | (job.huff_copy[t].identifier & 0xF)));
-            optimal_codes_to_table(codes, &enc[(size_t)p.job * kMaxHuffSlots + t], &body);
-        }
-        p.dht.clear();
-        put_marker(p.dht, 0xC4);
-        put_length(p.dht, (uint16_t)body.size());
-        p.dht.append(body.begin(), body.end());
-    }
-    hipError_t e = hipMemcpyAsync(d_enc_.ptr, enc.data(), enc.size() * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(encoding tables)");
-    return JPGPU_OK;
+    for (Plan &p : plans_)
+        if (p.status == JPGPU_OK && p.job >= 0) build_image_tables(p, &h_hist_[(size_t)p.job * kMaxHuffSlots * 256], &enc[(size_t)p.job * kMaxHuffSlots]);
+    const hipError_t e = hipMemcpyAsync(d_enc_.ptr, enc.data(), enc.size() * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
+    return e == hipSuccess ? JPGPU_OK : hip_fail(e, "hipMemcpyAsync(encoding tables)");
 }
 
 // ---- Optimize(): size of every interval and subsequence, and where the interval scans' bytes go
@@ -980,16 +712,13 @@ int OptimizeBatch::emit_subsequences_and_stuff(Run &r) {
     const StuffPlan sp = plan_stuffing_layout(r.simages.data(), r.sub_total_bits.data(), r.n_sub_scans, true);
     std::vector<uint64_t> scan_raw_off(r.n_jobs, 0);
     for (int k = 0; k < r.n_sub_scans; k++) scan_raw_off[sub_scan_ids_[k]] = r.simages[k].raw_off;
-    const struct {
-        DevBuffer *buf;
-        size_t bytes;
-    } grow[] = {{&d_raw_, (size_t)sp.raw_bytes + 256}, {&d_sout_, (size_t)sp.out_bytes + 256}, {&d_chunk_ff_, (size_t)sp.chunks * sizeof(uint32_t) + 256},
-                {&d_swork_chunk_, sp.work_chunk.size() * sizeof(EncWork) + 16}};
-    hipError_t e;
-    for (const auto &g : grow) {
-        e = g.buf->reserve(g.bytes);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(optimizer raw buffers)");
-    }
+    const DevUpload grow[] = {{&d_raw_, nullptr, 0, (size_t)sp.raw_bytes + 256},
+                              {&d_sout_, nullptr, 0, (size_t)sp.out_bytes + 256},
+                              {&d_chunk_ff_, nullptr, 0, (size_t)sp.chunks * sizeof(uint32_t) + 256},
+                              {&d_swork_chunk_, nullptr, 0, sp.work_chunk.size() * sizeof(EncWork) + 16}};
+    bool copying = false;
+    hipError_t e = reserve_and_copy(grow, ctx_->stream, &copying);
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc(optimizer raw buffers)");
     e = hipMemsetAsync(d_raw_.ptr, 0, (size_t)sp.raw_bytes + 256, ctx_->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_scan_raw_off_.ptr, scan_raw_off.data(), scan_raw_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx_->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_simages_.ptr, r.simages.data(), r.simages.size() * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
@@ -1015,8 +744,8 @@ void OptimizeBatch::collect_lengths(const Run &r) {
     for (Plan &p : plans_) {
         if (p.status != JPGPU_OK || p.job < 0) continue;
         if (p.transform.coefficient_road()) {  // a turned or cut image: the encoder's stuffing stage has closed its stream with EOI, too
-            p.entropy_off = timages_[(size_t)p.turn].out_off;
-            p.entropy_len = tout_len_[(size_t)p.turn] >= 2 ? tout_len_[(size_t)p.turn] - 2 : 0;
+            p.entropy_off = road_.images[(size_t)p.turn].out_off;
+            p.entropy_len = road_.tail.h_out_len[(size_t)p.turn] >= 2 ? road_.tail.h_out_len[(size_t)p.turn] - 2 : 0;
         } else if (p.by_subsequence) {
             p.entropy_off = r.simages[ks].out_off;
             p.entropy_len = r.sout_len[ks] >= 2 ? r.sout_len[ks] - 2 : 0;  // the stuffing stage closes with EOI: that belongs to the host pieces here
@@ -1045,7 +774,6 @@ int OptimizeBatch::set_orientations(const uint8_t *orientations, int n) {
     for (int i = 0; i < n; i++)
         if (orientations[i] > 8) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_set_orientations: an orientation is 1..8, or 0 for what the policy gives");
     pending_orientations_.assign(orientations, orientations + n);
-    orientations_pending_ = n > 0;
     return JPGPU_OK;
 }
 int OptimizeBatch::set_edge_policy(int edge) {
@@ -1066,7 +794,6 @@ int OptimizeBatch::set_origin_policy(int origin) {
 int OptimizeBatch::set_windows(const jpgpu_rect *windows, int n) {
     if (n < 0 || (n > 0 && !windows)) return fail(JPGPU_ERR_ARGUMENT, "jpgpu_optimizer_set_windows: bad argument");
     pending_windows_.assign(windows, windows + n);
-    windows_pending_ = n > 0;
     return JPGPU_OK;
 }
 int OptimizeBatch::image_window(int i, jpgpu_rect *applied) const {
@@ -1096,220 +823,192 @@ void OptimizeBatch::plan_turned_image(Plan &p, const uint8_t *data, size_t len, 
     std::string f((const char *)data, len);
     uint8_t *b = (uint8_t *)&f[0];
     patch_turned_file(b, len, tp);
-    Plan turned;
-    end_key_ = nullptr;
-    plan_file(turned, b, len, strip, false, true);
-    end_key_ = nullptr;  // (the key is the address of a buffer that goes away here)
+    WalkPlan turned;
+    ScanEndCache ends;  // (of `f`, which goes away here)
+    walk_file(turned, ends, b, len, strip, false, true);
     p.pieces = std::move(turned.pieces);
 }
 
 // The turned images of an upload: the files once more, as the decoder takes them, and the plans of KX and of the encoder's entropy stages
-int OptimizeBatch::upload_turned(const uint8_t *const *jpeg, const size_t *len) {
-    turned_.clear();
-    turn_images_.clear();
-    turn_work_.clear();
-    timages_.clear();
-    tlayouts_.clear();
-    twork_blk_.clear();
-    twork_stat_.clear();
-    turn_blocks_total_ = 0;
-    turn_sources_ = 0;
+int OptimizeBatch::plan_road(const Upload &u) {
+    static_cast<RoadPlans &>(road_) = RoadPlans();
+    if (u.turned.empty()) {  // nothing of an earlier upload's turned images stays on the device
+        road_.release();
+        return JPGPU_OK;
+    }
     // entries that are the same file (the same pointer and length: one canvas cut into tiles) take ONE slot of the second batch and are
     // entropy-decoded once; their descriptors share its place in the dense store
     std::vector<const uint8_t *> files;
     std::vector<size_t> lens;
-    std::vector<int> slot_of;  // per entry of turned_
+    std::vector<int> slot_of;  // per entry of u.turned
     std::map<std::pair<const uint8_t *, size_t>, int> slots;
-    for (size_t i = 0; i < plans_.size(); i++) {
-        Plan &p = plans_[i];
-        p.turn = -1;
-        if (p.status != JPGPU_OK || p.job < 0 || !p.transform.coefficient_road()) continue;
-        turned_.push_back((int)i);
-        const auto at = slots.emplace(std::make_pair(jpeg[i], len[i]), (int)files.size());
+    for (const int i : u.turned) {
+        const auto at = slots.emplace(std::make_pair(u.jpeg[i], u.len[i]), (int)files.size());
         if (at.second) {
-            files.push_back(jpeg[i]);
-            lens.push_back(len[i]);
+            files.push_back(u.jpeg[i]);
+            lens.push_back(u.len[i]);
         }
         slot_of.push_back(at.first->second);
     }
-    turn_sources_ = (int)files.size();
-    if (turned_.empty()) {  // nothing of an earlier upload's turned images stays on the device
-        turn_batch_.reset();
-        for (DevBuffer *b : {&d_turn_images_, &d_turn_work_, &d_tcoefs_, &d_timages_, &d_tlayouts_, &d_twork_blk_, &d_twork_stat_, &d_thist_, &d_ttables_,
-                             &d_tbits_, &d_tbit_off_, &d_traw_bits_, &d_traw_, &d_tmarks_, &d_tchunk_ff_, &d_twork_chunk_, &d_tout_, &d_tout_len_})
-            b->release();
-        return JPGPU_OK;
-    }
-    if (!turn_batch_) turn_batch_.reset(new DeviceBatch(ctx_));
-    int rc = turn_batch_->upload_files(files.data(), lens.data(), (int)files.size(), JPGPU_FMT_PLANAR_U8);
+    road_.sources = (int)files.size();
+    if (!road_.batch) road_.batch.reset(new DeviceBatch(ctx_));
+    const int rc = road_.batch->upload_files(files.data(), lens.data(), (int)files.size(), JPGPU_FMT_PLANAR_U8);
     if (rc != JPGPU_OK) return rc;
-    for (size_t k = 0; k < turned_.size(); k++) {
-        Plan &p = plans_[(size_t)turned_[k]];
-        const TransformPlan &tp = p.transform;
-        const ScanJob &job = batch_.jobs_[p.job];  // (the optimizer's view of the scan: its table slots are the builders' order)
-        const ImagePlan *img = turn_batch_->image(slot_of[k]);
-        const auto refuse_image = [&](const std::string &msg) {
+    for (size_t k = 0; k < u.turned.size(); k++) {
+        Plan &p = plans_[(size_t)u.turned[k]];
+        const ImagePlan *img = road_.batch->image(slot_of[k]);
+        if (img->status != JPGPU_OK) {
+            static_cast<Verdict &>(p) = {img->status, img->detail, img->error};
+            p.pieces.clear();
+        } else if (!plan_road_image(p, img)) {
             p.status = JPGPU_ERR_NOT_SUPPORTED;
             p.detail = kDetailUnsupportedFrame;
-            p.error = msg;
             p.pieces.clear();
-        };
-        if (img->status != JPGPU_OK) {
-            p.status = img->status;
-            p.detail = img->detail;
-            p.error = img->error;
-            p.pieces.clear();
-            continue;
-        }
-        uint32_t bpm = 0;
-        for (int c = 0; c < tp.ncomp; c++) bpm += (uint32_t)tp.h[c] * tp.v[c];
-        bool expressible = img->jobs.size() == 1 && turn_batch_->jobs_[img->jobs[0]].kind == kScanSequential && job.scan_components == tp.ncomp &&
-                           img->mcus_per_line == tp.src_mcus_per_line && img->mcus_per_column == tp.src_mcus_per_column && img->blocks_per_mcu == bpm &&
-                           img->total_blocks == (uint64_t)tp.src_mcus_per_line * tp.src_mcus_per_column * bpm && job.n_huff <= 8;
-        for (int c = 0; expressible && c < tp.ncomp; c++)
-            expressible = job.comp[c].h == tp.h[c] && job.comp[c].v == tp.v[c] && job.dc_slot[c] < 8 && job.ac_slot[c] < 8;
-        if (!expressible) {
-            refuse_image("The arrangement of this scan cannot be turned.");
-            continue;
-        }
-        const bool tr = tp.transposes();
-        DevTurnImage g;
-        memset(&g, 0, sizeof g);
-        DevEncImage im;
-        memset(&im, 0, sizeof im);
-        DevEncLayout L;
-        memset(&L, 0, sizeof L);
-        g.src_off = img->coef_offset;
-        g.dst_off = turn_blocks_total_;
-        g.orientation = (uint32_t)tp.orientation;
-        g.bpm = bpm;
-        g.src_mcus_per_line = tp.src_mcus_per_line;
-        g.kept_mcus_per_line = tp.kept_mcus_per_line;
-        g.kept_mcus_per_column = tp.kept_mcus_per_column;
-        g.dst_mcus_per_line = tr ? tp.kept_mcus_per_column : tp.kept_mcus_per_line;
-        g.dst_mcus_per_column = tr ? tp.kept_mcus_per_line : tp.kept_mcus_per_column;
-        if (tp.has_window) {  // the destination is the window's grid; plan_transform has checked that it lies inside the turned one
-            if ((uint64_t)tp.win_mcu_x + tp.win_mcus_per_line > g.dst_mcus_per_line || (uint64_t)tp.win_mcu_y + tp.win_mcus_per_column > g.dst_mcus_per_column) {
-                refuse_image("The window does not lie inside the MCU grid of the turned image.");
-                continue;
-            }
-            g.origin_mx = tp.win_mcu_x;
-            g.origin_my = tp.win_mcu_y;
-            g.dst_mcus_per_line = tp.win_mcus_per_line;
-            g.dst_mcus_per_column = tp.win_mcus_per_column;
-        }
-        g.total_blocks = g.dst_mcus_per_line * g.dst_mcus_per_column * bpm;
-        L.ncomp = (uint32_t)tp.ncomp;
-        L.max_h = tr ? tp.max_v : tp.max_h;
-        L.max_v = tr ? tp.max_h : tp.max_v;
-        L.own_blocks = 1;  // (statistics are taken; the grids below are the whole MCU grid, so no block is the allocator's dummy)
-        L.table_base = (uint32_t)(8 * timages_.size());
-        L.hist_index = (uint32_t)(8 * 256 * timages_.size());
-        uint32_t b = 0;
-        for (int c = 0; c < tp.ncomp; c++) {
-            const uint32_t h = tr ? tp.v[c] : tp.h[c], v = tr ? tp.h[c] : tp.v[c];
-            g.src_h[c] = tp.h[c];
-            g.src_v[c] = tp.v[c];
-            g.first_blk[c] = (uint8_t)b;
-            L.h[c] = (uint8_t)h;
-            L.v[c] = (uint8_t)v;
-            L.hs[c] = (uint8_t)(L.max_h / h);
-            L.vs[c] = (uint8_t)(L.max_v / v);
-            L.dc_slot[c] = job.dc_slot[c];
-            L.ac_slot[c] = job.ac_slot[c];
-            L.first_blk[c] = (uint8_t)b;
-            L.grid_w[c] = g.dst_mcus_per_line * h;
-            L.grid_h[c] = g.dst_mcus_per_column * v;
-            for (uint32_t y = 0; y < v; y++)
-                for (uint32_t x = 0; x < h; x++) {
-                    g.blk[b] = (uint8_t)((uint32_t)c | x << 2 | y << 4);
-                    L.blk_comp[b] = (uint8_t)c;
-                    L.blk_x[b] = (uint8_t)x;
-                    L.blk_y[b] = (uint8_t)y;
-                    L.blk_info[b] = (uint32_t)c | (x << 2) | (y << 4) | (h << 6) | (v << 9) | ((uint32_t)job.dc_slot[c] << 12) | ((uint32_t)job.ac_slot[c] << 15) |
-                                    ((uint32_t)L.first_blk[c] << 18) | (((uint32_t)L.first_blk[c] + h * v - 1u) << 24);
-                    b++;
-                }
-        }
-        im.coef_off = g.dst_off;
-        im.width = tp.out_width;
-        im.height = tp.out_height;
-        im.components = (uint32_t)tp.ncomp;
-        im.luma_h = L.max_h;
-        im.luma_v = L.max_v;
-        im.mcus_per_line = g.dst_mcus_per_line;
-        im.mcus_per_column = g.dst_mcus_per_column;
-        im.bpm = bpm;
-        im.total_blocks = g.total_blocks;
-        im.restart_interval = (uint32_t)p.dri_at_scan;
-        const uint32_t mcus = im.mcus_per_line * im.mcus_per_column;
-        im.n_units = im.restart_interval ? (mcus + im.restart_interval - 1) / im.restart_interval : im.total_blocks;
-        im.work_first = (uint32_t)twork_blk_.size();
-        im.layout = (uint32_t)tlayouts_.size() + 1;
-        p.turn = (int)timages_.size();
-        for (uint32_t f = 0; f < g.total_blocks; f += kTurnBlocksPerWg) turn_work_.push_back({(uint32_t)p.turn, f});
-        for (uint32_t f = 0; f < im.n_units; f += 256) twork_blk_.push_back({(uint32_t)p.turn, f});
-        for (uint32_t f = 0; f < im.total_blocks; f += 256) twork_stat_.push_back({(uint32_t)p.turn, f});
-        turn_blocks_total_ += g.total_blocks;
-        turn_images_.push_back(g);
-        timages_.push_back(im);
-        tlayouts_.push_back(L);
-    }
-    struct Up {
-        DevBuffer *buf;
-        const void *src;
-        size_t bytes, reserve;
-    };
-    const size_t nt = timages_.size(), nw = twork_blk_.size();
-    const Up ups[] = {
-        {&d_turn_images_, turn_images_.data(), nt * sizeof(DevTurnImage), 0},
-        {&d_turn_work_, turn_work_.data(), turn_work_.size() * sizeof(TurnWork), 0},
-        {&d_tlayouts_, tlayouts_.data(), nt * sizeof(DevEncLayout), 0},
-        {&d_twork_blk_, twork_blk_.data(), nw * sizeof(EncWork), 0},
-        {&d_twork_stat_, twork_stat_.data(), twork_stat_.size() * sizeof(EncWork), 0},
-        {&d_timages_, nullptr, 0, nt * sizeof(DevEncImage) + 256},
-        {&d_tcoefs_, nullptr, 0, (size_t)turn_blocks_total_ * 128 + 256},
-        {&d_thist_, nullptr, 0, nt * 8 * 256 * sizeof(uint32_t) + 256},
-        {&d_ttables_, nullptr, 0, nt * 8 * sizeof(EncHuffTable) + 256},
-        {&d_tbits_, nullptr, 0, (size_t)turn_blocks_total_ * sizeof(uint32_t) + 256},
-        {&d_tbit_off_, nullptr, 0, ((nw * sizeof(uint64_t) + 255) & ~(size_t)255) + nw * sizeof(uint32_t) + 256},
-        {&d_traw_bits_, nullptr, 0, nt * sizeof(uint64_t) + 256},
-        {&d_tout_len_, nullptr, 0, nt * sizeof(uint64_t) + 256},
-    };
-    for (const Up &u : ups) {
-        hipError_t e = u.buf->reserve(std::max(u.bytes, u.reserve) + 16);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc");
-        if (u.bytes) {
-            e = hipMemcpyAsync(u.buf->ptr, u.src, u.bytes, hipMemcpyHostToDevice, ctx_->stream);
-            if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(lossless transform plans)");
         }
     }
+    const size_t nt = road_.images.size(), nw = road_.work_blk.size(), slack = 16;
+    const DevUpload ups[] = {
+        {&road_.d_turn_images, road_.turn_images.data(), nt * sizeof(DevTurnImage), nt * sizeof(DevTurnImage) + slack},
+        {&road_.d_turn_work, road_.turn_work.data(), road_.turn_work.size() * sizeof(TurnWork), road_.turn_work.size() * sizeof(TurnWork) + slack},
+        {&road_.d_layouts, road_.layouts.data(), nt * sizeof(DevEncLayout), nt * sizeof(DevEncLayout) + slack},
+        {&road_.d_work_blk, road_.work_blk.data(), nw * sizeof(EncWork), nw * sizeof(EncWork) + slack},
+        {&road_.d_work_stat, road_.work_stat.data(), road_.work_stat.size() * sizeof(EncWork), road_.work_stat.size() * sizeof(EncWork) + slack},
+        {&road_.d_images, nullptr, 0, nt * sizeof(DevEncImage) + 256 + slack},
+        {&road_.d_coefs, nullptr, 0, (size_t)road_.blocks_total * 128 + 256 + slack},
+        {&road_.d_hist, nullptr, 0, nt * 8 * 256 * sizeof(uint32_t) + 256 + slack},
+        {&road_.d_tables, nullptr, 0, nt * 8 * sizeof(EncHuffTable) + 256 + slack},
+    };
+    bool copying = false;
+    hipError_t e = reserve_and_copy(ups, ctx_->stream, &copying);
+    if (e != hipSuccess) return hip_fail(e, copying ? "hipMemcpyAsync(lossless transform plans)" : "hipMalloc");
+    if ((e = road_.tail.reserve(road_.blocks_total, nw, nt)) != hipSuccess) return hip_fail(e, road_.tail.failed);
     return JPGPU_OK;
+}
+
+// One image of the coefficient road: DevTurnImage (KX), DevEncImage and DevEncLayout (the encoder's general kernels) from its TransformPlan
+// and the optimizer's view of its scan, whose table slots are the builders' order.  false: refused, the reason in p.error.
+bool OptimizeBatch::plan_road_image(Plan &p, const ImagePlan *img) {
+    const TransformPlan &tp = p.transform;
+    const ScanJob &job = batch_.jobs_[p.job];
+    uint32_t bpm = 0;
+    for (int c = 0; c < tp.ncomp; c++) bpm += (uint32_t)tp.h[c] * tp.v[c];
+    bool expressible = img->jobs.size() == 1 && road_.batch->jobs_[img->jobs[0]].kind == kScanSequential && job.scan_components == tp.ncomp &&
+                       img->mcus_per_line == tp.src_mcus_per_line && img->mcus_per_column == tp.src_mcus_per_column && img->blocks_per_mcu == bpm &&
+                       img->total_blocks == (uint64_t)tp.src_mcus_per_line * tp.src_mcus_per_column * bpm && job.n_huff <= 8;
+    for (int c = 0; expressible && c < tp.ncomp; c++)
+        expressible = job.comp[c].h == tp.h[c] && job.comp[c].v == tp.v[c] && job.dc_slot[c] < 8 && job.ac_slot[c] < 8;
+    if (!expressible) {
+        p.error = "The arrangement of this scan cannot be turned.";
+        return false;
+    }
+    const bool tr = tp.transposes();
+    DevTurnImage g;
+    memset(&g, 0, sizeof g);
+    DevEncImage im;
+    memset(&im, 0, sizeof im);
+    DevEncLayout L;
+    memset(&L, 0, sizeof L);
+    g.src_off = img->coef_offset;
+    g.dst_off = road_.blocks_total;
+    g.orientation = (uint32_t)tp.orientation;
+    g.bpm = bpm;
+    g.src_mcus_per_line = tp.src_mcus_per_line;
+    g.kept_mcus_per_line = tp.kept_mcus_per_line;
+    g.kept_mcus_per_column = tp.kept_mcus_per_column;
+    g.dst_mcus_per_line = tr ? tp.kept_mcus_per_column : tp.kept_mcus_per_line;
+    g.dst_mcus_per_column = tr ? tp.kept_mcus_per_line : tp.kept_mcus_per_column;
+    if (tp.has_window) {  // the destination is the window's grid; plan_transform has checked that it lies inside the turned one
+        if ((uint64_t)tp.win_mcu_x + tp.win_mcus_per_line > g.dst_mcus_per_line || (uint64_t)tp.win_mcu_y + tp.win_mcus_per_column > g.dst_mcus_per_column) {
+            p.error = "The window does not lie inside the MCU grid of the turned image.";
+            return false;
+        }
+        g.origin_mx = tp.win_mcu_x;
+        g.origin_my = tp.win_mcu_y;
+        g.dst_mcus_per_line = tp.win_mcus_per_line;
+        g.dst_mcus_per_column = tp.win_mcus_per_column;
+    }
+    g.total_blocks = g.dst_mcus_per_line * g.dst_mcus_per_column * bpm;
+    L.ncomp = (uint32_t)tp.ncomp;
+    L.max_h = tr ? tp.max_v : tp.max_h;
+    L.max_v = tr ? tp.max_h : tp.max_v;
+    L.own_blocks = 1;  // (statistics are taken; the grids below are the whole MCU grid, so no block is the allocator's dummy)
+    L.table_base = (uint32_t)(8 * road_.images.size());
+    L.hist_index = (uint32_t)(8 * 256 * road_.images.size());
+    uint32_t b = 0;
+    for (int c = 0; c < tp.ncomp; c++) {
+        const uint32_t h = tr ? tp.v[c] : tp.h[c], v = tr ? tp.h[c] : tp.v[c];
+        g.src_h[c] = tp.h[c];
+        g.src_v[c] = tp.v[c];
+        g.first_blk[c] = (uint8_t)b;
+        L.h[c] = (uint8_t)h;
+        L.v[c] = (uint8_t)v;
+        L.hs[c] = (uint8_t)(L.max_h / h);
+        L.vs[c] = (uint8_t)(L.max_v / v);
+        L.dc_slot[c] = job.dc_slot[c];
+        L.ac_slot[c] = job.ac_slot[c];
+        L.first_blk[c] = (uint8_t)b;
+        L.grid_w[c] = g.dst_mcus_per_line * h;
+        L.grid_h[c] = g.dst_mcus_per_column * v;
+        for (uint32_t y = 0; y < v; y++)
+            for (uint32_t x = 0; x < h; x++) {
+                g.blk[b] = (uint8_t)((uint32_t)c | x << 2 | y << 4);
+                L.blk_comp[b] = (uint8_t)c;
+                L.blk_x[b] = (uint8_t)x;
+                L.blk_y[b] = (uint8_t)y;
+                L.blk_info[b] = (uint32_t)c | (x << 2) | (y << 4) | (h << 6) | (v << 9) | ((uint32_t)job.dc_slot[c] << 12) | ((uint32_t)job.ac_slot[c] << 15) |
+                                ((uint32_t)L.first_blk[c] << 18) | (((uint32_t)L.first_blk[c] + h * v - 1u) << 24);
+                b++;
+            }
+    }
+    im.coef_off = g.dst_off;
+    im.width = tp.out_width;
+    im.height = tp.out_height;
+    im.components = (uint32_t)tp.ncomp;
+    im.luma_h = L.max_h;
+    im.luma_v = L.max_v;
+    im.mcus_per_line = g.dst_mcus_per_line;
+    im.mcus_per_column = g.dst_mcus_per_column;
+    im.bpm = bpm;
+    im.total_blocks = g.total_blocks;
+    im.restart_interval = (uint32_t)p.dri_at_scan;
+    const uint32_t mcus = im.mcus_per_line * im.mcus_per_column;
+    im.n_units = im.restart_interval ? (mcus + im.restart_interval - 1) / im.restart_interval : im.total_blocks;
+    im.work_first = (uint32_t)road_.work_blk.size();
+    im.layout = (uint32_t)road_.layouts.size() + 1;
+    p.turn = (int)road_.images.size();
+    for (uint32_t f = 0; f < g.total_blocks; f += kTurnBlocksPerWg) road_.turn_work.push_back({(uint32_t)p.turn, f});
+    for (uint32_t f = 0; f < im.n_units; f += 256) road_.work_blk.push_back({(uint32_t)p.turn, f});
+    for (uint32_t f = 0; f < im.total_blocks; f += 256) road_.work_stat.push_back({(uint32_t)p.turn, f});
+    road_.blocks_total += g.total_blocks;
+    road_.turn_images.push_back(g);
+    road_.images.push_back(im);
+    road_.layouts.push_back(L);
+    return true;
 }
 
 // ---- the turned images: K1 + K2 of the decoder fill its coefficient store; KX reads it dense
 int OptimizeBatch::decode_turned(Run &r) {
-    (void)hipEventRecord(ev_td_[0], ctx_->stream);
-    turn_batch_->note_entropy_only_request();
-    int rc = turn_batch_->run_marker_index();
-    if (rc == JPGPU_OK) rc = turn_batch_->run_huffman();
-    (void)hipEventRecord(ev_td_[1], ctx_->stream);
+    (void)hipEventRecord(road_.ev_td[0], ctx_->stream);
+    road_.batch->note_entropy_only_request();
+    int rc = road_.batch->run_marker_index();
+    if (rc == JPGPU_OK) rc = road_.batch->run_huffman();
+    (void)hipEventRecord(road_.ev_td[1], ctx_->stream);
     // (what a reader of the store owes the batch, as jpgpu_batch_download_coefficients pays it: DRI = 0 scans are decoded in rounds whose
     // count the host confirms here, issuing the stage again where they did not suffice)
-    if (rc == JPGPU_OK) rc = turn_batch_->sync();
+    if (rc == JPGPU_OK) rc = road_.batch->sync();
     if (rc != JPGPU_OK) return rc;
-    r.turn_src = (const int16_t *)turn_batch_->coefs_device(nullptr);  // (expands the scans K2 handed over as half-line planes)
-    (void)hipEventRecord(ev_td_[2], ctx_->stream);
+    r.turn_src = (const int16_t *)road_.batch->coefs_device(nullptr);  // (expands the scans K2 handed over as half-line planes)
+    (void)hipEventRecord(road_.ev_td[2], ctx_->stream);
     if (!r.turn_src) return fail(JPGPU_ERR_DEVICE, "the dense coefficient store of the turned images is not available");
     return JPGPU_OK;
 }
 
 // ---- KX: every block to its place in the turned grid, sign-flipped and transposed (kx_lossless.hip)
 int OptimizeBatch::turn_blocks(Run &r) {
-    (void)hipEventRecord(ev_kx0_, ctx_->stream);
-    hipError_t e = launch_lossless_turn(ctx_->stream, (const DevTurnImage *)d_turn_images_.ptr, (const TurnWork *)d_turn_work_.ptr, (int)turn_work_.size(), r.turn_src,
-                                        (int16_t *)d_tcoefs_.ptr);
-    (void)hipEventRecord(ev_kx1_, ctx_->stream);
+    (void)hipEventRecord(road_.ev_kx[0], ctx_->stream);
+    hipError_t e = launch_lossless_turn(ctx_->stream, (const DevTurnImage *)road_.d_turn_images.ptr, (const TurnWork *)road_.d_turn_work.ptr, (int)road_.turn_work.size(), r.turn_src,
+                                        (int16_t *)road_.d_coefs.ptr);
+    (void)hipEventRecord(road_.ev_kx[1], ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "lossless_turn_kernel");
     return JPGPU_OK;
 }
@@ -1317,45 +1016,21 @@ int OptimizeBatch::turn_blocks(Run &r) {
 // ---- statistics of the turned blocks (the encoder's GatherBlockStatistics) and Build per (class, identifier) of the source's DHT
 int OptimizeBatch::build_turned_tables(Run &r) {
     const size_t n_hist = (size_t)r.n_turned * 8 * 256;
-    hipError_t e = hipMemcpyAsync(d_timages_.ptr, timages_.data(), timages_.size() * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_thist_.ptr, 0, n_hist * sizeof(uint32_t), ctx_->stream);
+    hipError_t e = hipMemcpyAsync(road_.d_images.ptr, road_.images.data(), road_.images.size() * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(road_.d_hist.ptr, 0, n_hist * sizeof(uint32_t), ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(turned statistics)");
-    e = launch_block_stats(ctx_->stream, (const DevEncImage *)d_timages_.ptr, (const EncWork *)d_twork_stat_.ptr, (int)twork_stat_.size(),
-                           (const int16_t *)d_tcoefs_.ptr, (uint32_t *)d_thist_.ptr, (const DevEncLayout *)d_tlayouts_.ptr, false);
+    e = launch_block_stats(ctx_->stream, (const DevEncImage *)road_.d_images.ptr, (const EncWork *)road_.d_work_stat.ptr, (int)road_.work_stat.size(),
+                           (const int16_t *)road_.d_coefs.ptr, (uint32_t *)road_.d_hist.ptr, (const DevEncLayout *)road_.d_layouts.ptr, false);
     if (e != hipSuccess) return hip_fail(e, "block_stats_kernel");
     std::vector<uint32_t> hist(n_hist);
-    e = hipMemcpyAsync(hist.data(), d_thist_.ptr, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx_->stream);
+    e = hipMemcpyAsync(hist.data(), road_.d_hist.ptr, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx_->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy(turned statistics)");
     std::vector<EncHuffTable> enc(8 * (size_t)r.n_turned);
     memset(enc.data(), 0, enc.size() * sizeof(EncHuffTable));
-    for (Plan &p : plans_) {
-        if (p.turn < 0) continue;
-        const ScanJob &job = batch_.jobs_[p.job];
-        std::vector<uint8_t> body;
-        for (int t = 0; t < job.n_huff; t++) {
-            std::vector<OptimalCode> codes;
-            const uint32_t *freq = &hist[((size_t)p.turn * 8 + t) * 256];
-            if (!build_optimal_table(freq, &codes, most_optimal_)) {  // (as build_tables reports it for the source's own statistics)
-                bool any = false;
-                for (int sym = 0; sym < 256; sym++) any |= freq[sym] != 0;
-                if (!p.build_failed) {
-                    p.build_failed = true;
-                    p.late_status = JPGPU_ERR_INVALID_OPERATION;
-                    p.late_detail = 0;
-                    p.late_error = any ? "Index was outside the bounds of the array." : "No symbol is recorded.";
-                }
-                continue;
-            }
-            body.push_back((uint8_t)(job.huff_copy[t].table_class << 4 | (job.huff_copy[t].identifier & 0xF)));
-            optimal_codes_to_table(codes, &enc[(size_t)p.turn * 8 + t], &body);
-        }
-        p.dht.clear();
-        put_marker(p.dht, 0xC4);
-        put_length(p.dht, (uint16_t)body.size());
-        p.dht.append(body.begin(), body.end());
-    }
-    e = hipMemcpyAsync(d_ttables_.ptr, enc.data(), enc.size() * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
+    for (Plan &p : plans_)  // (as build_tables reports it for the source's own statistics)
+        if (p.turn >= 0) build_image_tables(p, &hist[(size_t)p.turn * 8 * 256], &enc[(size_t)p.turn * 8]);
+    e = hipMemcpyAsync(road_.d_tables.ptr, enc.data(), enc.size() * sizeof(EncHuffTable), hipMemcpyHostToDevice, ctx_->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);  // (`enc` leaves scope)
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(turned encoding tables)");
     return JPGPU_OK;
@@ -1363,52 +1038,20 @@ int OptimizeBatch::build_turned_tables(Run &r) {
 
 // ---- bits, emit and stuffing through the encoder's general kernels (E2, E3, E4); no header in front of the streams
 int OptimizeBatch::emit_turned(Run &r) {
-    const int n = r.n_turned, n_work = (int)twork_blk_.size();
-    const DevEncImage *images = (const DevEncImage *)d_timages_.ptr;
-    const DevEncLayout *layouts = (const DevEncLayout *)d_tlayouts_.ptr;
-    uint32_t *wg_bits = reinterpret_cast<uint32_t *>((uint8_t *)d_tbit_off_.ptr + (((size_t)n_work * sizeof(uint64_t) + 255) & ~(size_t)255));
-    hipError_t e = launch_block_bits(ctx_->stream, images, (const EncWork *)d_twork_blk_.ptr, n_work, (const EncHuffTable *)d_ttables_.ptr,
-                                     (const int16_t *)d_tcoefs_.ptr, (uint32_t *)d_tbits_.ptr, n, wg_bits, (uint64_t *)d_tbit_off_.ptr, (uint64_t *)d_traw_bits_.ptr,
-                                     layouts, false);
-    if (e != hipSuccess) return hip_fail(e, "block_bits_kernel");
-    r.traw_bits.assign((size_t)n, 0);
-    e = hipMemcpyAsync(r.traw_bits.data(), d_traw_bits_.ptr, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpy(turned bit counts)");
-    uint64_t emit_words = 0;  // E3's LDS buffer, by the encoder's rule (EncodeBatch::plan_stuffing)
-    for (int i = 0; i < n; i++) {
-        const uint64_t wgs = ((uint64_t)timages_[(size_t)i].n_units + 255) / 256;
-        const uint64_t avg_words = r.traw_bits[(size_t)i] / 32 / std::max<uint64_t>(wgs, 1) + 1;
-        if (avg_words <= kEmitLdsWordsMax) emit_words = std::max<uint64_t>(emit_words, 2 * avg_words);
-    }
-    const StuffPlan sp = plan_stuffing_layout(timages_.data(), r.traw_bits.data(), n, true);
-    const size_t raw_bytes = (size_t)sp.raw_bytes;
-    const struct {
-        DevBuffer *buf;
-        size_t bytes;
-    } grow[] = {{&d_traw_, raw_bytes + 256}, {&d_tmarks_, raw_bytes / 8 + 256}, {&d_tout_, (size_t)sp.out_bytes + 256},
-                {&d_tchunk_ff_, (size_t)sp.chunks * sizeof(uint32_t) + 256}, {&d_twork_chunk_, sp.work_chunk.size() * sizeof(EncWork) + 16}};
-    for (const auto &g : grow) {
-        e = g.buf->reserve(g.bytes);
-        if (e != hipSuccess) return hip_fail(e, "hipMalloc(turned streams)");
-    }
-    e = hipMemsetAsync(d_traw_.ptr, 0, raw_bytes + 256, ctx_->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_tmarks_.ptr, 0, raw_bytes / 8 + 256, ctx_->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_timages_.ptr, timages_.data(), (size_t)n * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_twork_chunk_.ptr, sp.work_chunk.data(), sp.work_chunk.size() * sizeof(EncWork), hipMemcpyHostToDevice, ctx_->stream);
+    EntropyTail &t = road_.tail;
+    const EntropyTail::Source src = {(const DevEncImage *)road_.d_images.ptr, (const EncWork *)road_.d_work_blk.ptr, (int)road_.work_blk.size(),
+                                     (const EncHuffTable *)road_.d_tables.ptr, (const int16_t *)road_.d_coefs.ptr, (const DevEncLayout *)road_.d_layouts.ptr, false};
+    hipError_t e = t.count_bits(ctx_->stream, src, r.n_turned);
+    if (e == hipSuccess) e = t.read_bit_counts(ctx_->stream, r.n_turned);
+    if (e == hipSuccess) e = t.plan(ctx_->stream, road_.images.data(), r.n_turned, true);
+    if (e != hipSuccess) return hip_fail(e, t.failed);
+    e = hipMemcpyAsync(road_.d_images.ptr, road_.images.data(), (size_t)r.n_turned * sizeof(DevEncImage), hipMemcpyHostToDevice, ctx_->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(turned stream descriptors)");
-    e = launch_emit(ctx_->stream, images, (const EncWork *)d_twork_blk_.ptr, n_work, (const EncHuffTable *)d_ttables_.ptr, (const int16_t *)d_tcoefs_.ptr,
-                    (const uint32_t *)d_tbits_.ptr, (const uint64_t *)d_tbit_off_.ptr, (const uint64_t *)d_traw_bits_.ptr, (uint8_t *)d_traw_.ptr,
-                    (uint32_t *)d_tmarks_.ptr, (uint32_t)std::min<uint64_t>((emit_words + 1023) & ~1023ull, kEmitLdsWordsMax), layouts, false);
-    if (e != hipSuccess) return hip_fail(e, "emit_kernel");
-    e = launch_stuff(ctx_->stream, images, (const EncWork *)d_twork_chunk_.ptr, (int)sp.work_chunk.size(), (const uint64_t *)d_traw_bits_.ptr,
-                     (const uint8_t *)d_traw_.ptr, (const uint32_t *)d_tmarks_.ptr, (uint32_t *)d_tchunk_ff_.ptr, (uint8_t *)d_tout_.ptr, (uint64_t *)d_tout_len_.ptr);
-    if (e != hipSuccess) return hip_fail(e, "stuff kernels");
-    tout_len_.assign((size_t)n, 0);
-    e = hipMemcpyAsync(tout_len_.data(), d_tout_len_.ptr, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx_->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx_->stream);  // (`sp` leaves scope)
-    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(turned stream lengths)");
-    return JPGPU_OK;
+    e = t.upload_chunk_work(ctx_->stream);
+    if (e == hipSuccess) e = t.emit(ctx_->stream, src);
+    if (e == hipSuccess) e = t.stuff_bytes(ctx_->stream, src.images);
+    if (e == hipSuccess) e = t.read_lengths(ctx_->stream, r.n_turned);
+    return e == hipSuccess ? JPGPU_OK : hip_fail(e, t.failed);
 }
 
 int OptimizeBatch::result(int i, jpgpu_image_result *res, size_t *out_len) {
@@ -1416,10 +1059,13 @@ int OptimizeBatch::result(int i, jpgpu_image_result *res, size_t *out_len) {
     memset(res, 0, sizeof *res);
     if (out_len) *out_len = 0;
     const Plan &p = plans_[i];
+    const auto report = [&](const Verdict &v) {
+        res->status = v.status;
+        res->detail = v.detail;
+        ctx_->last_error = v.error;
+    };
     if (p.status != JPGPU_OK) {
-        res->status = p.status;
-        res->detail = p.detail;
-        ctx_->last_error = p.error;
+        report(p);
         return JPGPU_OK;
     }
     if (!ran_) return fail(JPGPU_ERR_INVALID_OPERATION, "jpgpu_optimizer_result: run() has not completed");
@@ -1442,19 +1088,15 @@ int OptimizeBatch::result(int i, jpgpu_image_result *res, size_t *out_len) {
             res->detail = kDetailBadHeader;
             ctx_->last_error = "Failed to decode JPEG data at offset " + std::to_string(batch_.image(i)->file_len) + ". No marker found.";
         } else if (st.terminator != 0 && (st.terminator & 0xF8u) != 0xD0u && (st.pad[2] >> 3) == 1) {
-            res->status = p.swallow_status;
-            res->detail = p.swallow_detail;
-            ctx_->last_error = p.swallow_error;
-        } else if (p.late_status != JPGPU_OK) {
-            res->status = p.late_status;
-            res->detail = p.late_detail;
-            ctx_->last_error = p.late_error;
+            report(p.swallow);
+        } else if (p.late.status != JPGPU_OK) {
+            report(p.late);
         }
     }
     if (res->status == JPGPU_OK && p.turn >= 0) {
         // the same restart check on F': a trimmed image has fewer MCUs than its source, and where their count is a multiple of DRI Scan() of
         // F' returns before it builds its tables, as above
-        const DevEncImage &im = timages_[(size_t)p.turn];
+        const DevEncImage &im = road_.images[(size_t)p.turn];
         if (im.restart_interval != 0 && (im.mcus_per_line * im.mcus_per_column) % im.restart_interval == 0) {
             res->status = JPGPU_ERR_INVALID_OPERATION;
             ctx_->last_error = "Operation is not valid due to the current state of the object.";
@@ -1481,7 +1123,7 @@ int OptimizeBatch::download(int i, void *dst, size_t cap) {
             memcpy(o, p.dht.data(), p.dht.size());
             o += p.dht.size();
         } else if (p.entropy_len) {
-            const uint8_t *src = (const uint8_t *)(p.turn >= 0 ? d_tout_.ptr : (p.by_subsequence ? d_sout_.ptr : d_out_.ptr)) + p.entropy_off;
+            const uint8_t *src = (const uint8_t *)(p.turn >= 0 ? road_.tail.out.ptr : (p.by_subsequence ? d_sout_.ptr : d_out_.ptr)) + p.entropy_off;
             hipError_t e = hipMemcpy(o, src, (size_t)p.entropy_len, hipMemcpyDeviceToHost);
             if (e != hipSuccess) return hip_fail(e, "hipMemcpy(optimizer output)");
             o += p.entropy_len;

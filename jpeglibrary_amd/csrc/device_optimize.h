@@ -6,8 +6,10 @@
 
 #include "../../include/jpgpu.h"
 #include "device_batch.h"
+#include "device_encode.h"
 #include "encode_kernels.h"
 #include "kx_lossless.h"
+#include "optimize_walk.h"
 #include "transform_plan.h"
 
 namespace jpgpu {
@@ -51,35 +53,15 @@ class OptimizeBatch {
     int set_origin_policy(int origin);
     int set_windows(const jpgpu_rect *windows, int n);
     int image_window(int i, jpgpu_rect *applied) const;
-    int turn_sources() const { return turn_sources_; }  // files the coefficient road of the last upload entropy-decoded
+    int turn_sources() const { return road_.sources; }  // files the coefficient road of the last upload entropy-decoded
     // of the last run (zeros: nothing was turned), HIP events all three: KX alone; the entropy decode in front of it; the dense copy
     void last_turn_ms(float ms[3]) const {
-        ms[0] = last_turn_ms_;
-        ms[1] = last_turn_decode_ms_;
-        ms[2] = last_turn_dense_ms_;
+        for (int k = 0; k < 3; k++) ms[k] = road_.ms[k];
     }
 
   private:
-    // Optimize()'s output is a fixed sequence of pieces: bytes known on the host, the new DHT segment, the scan's data
-    struct Piece {
-        enum Kind { kBytes, kHuffmanTables, kEntropy } kind;
-        std::string bytes;
-    };
-    struct Plan {
-        int status = JPGPU_OK, detail = 0;
-        std::string error;
-        // failures of the marker walks BEHIND the scan: the reference meets them only once the scan itself went through
-        // (Scan() throws from ProcessScanBaseline first), so they are reported after the device-side status
-        int late_status = JPGPU_OK, late_detail = 0;
+    struct Plan : WalkPlan {  // (optimize_walk.h: what the host walks leave; below, what the device passes add)
         bool build_failed = false;  // BuildTables threw (it runs at the end of the scan: in front of anything a later marker throws)
-        std::string late_error;
-        // ... and what the walks end in instead when the scan leaves exactly one whole byte unread: the reference's reader
-        // then resumes one byte INTO the terminating marker (DeviceBatch::plan_swallowed_terminator has the mechanism)
-        int swallow_status = JPGPU_OK, swallow_detail = 0;
-        std::string swallow_error;
-        int dri_at_scan = 0;
-        size_t rsts_in_scan = 0;  // RSTn markers between the scan header and the scan's terminating marker
-        std::vector<Piece> pieces;
         int job = -1;  // scan job inside batch_
         std::string dht;  // the rewritten DHT segment (marker, length, tables)
         uint64_t entropy_off = 0, entropy_len = 0;
@@ -90,8 +72,36 @@ class OptimizeBatch {
         TransformPlan transform;
         int turn = -1;
     };
+    // The coefficient road (the lossless transform): the turned files once more, as the decoder takes them (its entropy stage fills the dense store KX
+    // reads), KX, statistics and tables, the encoder's entropy stages.  Made by the first upload that turns something, released by the next that turns nothing.
+    struct RoadPlans {                          // (of one upload)
+        int sources = 0;                        // files `batch` entropy-decodes
+        std::vector<DevTurnImage> turn_images;  // per turned image: its KX descriptor,
+        std::vector<TurnWork> turn_work;
+        std::vector<DevEncImage> images;        // ... and what the encoder's general kernels need of it
+        std::vector<DevEncLayout> layouts;
+        std::vector<EncWork> work_blk, work_stat;
+        uint64_t blocks_total = 0;
+    };
+    struct Road : RoadPlans {
+        std::unique_ptr<DeviceBatch> batch;
+        float ms[3] = {};  // of the last run: KX, the entropy decode in front of it, the dense copy
+        hipEvent_t ev_kx[2] = {}, ev_td[3] = {};
+        DevBuffer d_turn_images, d_turn_work, d_coefs, d_images, d_layouts, d_work_blk, d_work_stat, d_hist, d_tables;
+        EntropyTail tail;
+        void release();  // nothing stays on the device
+    };
     int fail(int status, const std::string &msg);
     int hip_fail(hipError_t e, const char *what);
+    // upload() is the list of these; what they hand one another is an Upload that lives for the call
+    struct Upload;
+    int take_pending_lists(Upload &u);
+    void plan_on_host(const Upload &u);
+    int hand_files_to_decoder(const Upload &u);
+    void admit_and_sort(Upload &u);
+    int plan_road(const Upload &u);
+    bool plan_road_image(Plan &p, const ImagePlan *img);
+    int reserve_and_upload();
     // run() is the list of these; what they hand one another is a Run that lives for the call
     struct Run;
     int count_symbols(Run &r);
@@ -105,40 +115,17 @@ class OptimizeBatch {
     int turn_blocks(Run &r);
     int build_turned_tables(Run &r);
     int emit_turned(Run &r);
-    // turned: the file is F' (the source with its SOF / DQT / Exif patches), whose scan holds exactly the restart markers it needs
-    void plan_file(Plan &p, const uint8_t *data, size_t len, bool strip, bool swallow_terminator = false, bool turned = false);
+    // BuildTables of one image: `hist` and `enc` are the rows of the job's n_huff tables
+    void build_image_tables(Plan &p, const uint32_t *hist, EncHuffTable *enc) const;
     void plan_turned_image(Plan &p, const uint8_t *data, size_t len, bool strip, int given, const jpgpu_rect *window);
-    int upload_turned(const uint8_t *const *jpeg, const size_t *len);
-    size_t scan_end(const uint8_t *entropy, size_t len);
-    const uint8_t *end_key_ = nullptr;
-    size_t end_len_ = 0, end_val_ = 0;
-    std::string end_rsts_;
-
     jpgpu_ctx *ctx_;
     DeviceBatch batch_;
-    // the lossless transform: the turned files once more, as the decoder takes them (its entropy stage fills the dense store KX reads)
-    // (made by the first upload that turns something, released by the next one that turns nothing)
-    std::unique_ptr<DeviceBatch> turn_batch_;
+    Road road_;
     int orient_policy_ = JPGPU_ORIENT_STORED, edge_policy_ = JPGPU_EDGE_REFUSE;
-    std::vector<uint8_t> pending_orientations_;
-    bool orientations_pending_ = false;
+    std::vector<uint8_t> pending_orientations_;  // of the next upload (empty: none)
     int origin_policy_ = JPGPU_ORIGIN_REFUSE;
     std::vector<jpgpu_rect> pending_windows_;
-    bool windows_pending_ = false;
-    int turn_sources_ = 0;
-    std::vector<int> turned_;                // images of the upload that are turned, in order
-    std::vector<DevTurnImage> turn_images_;  // ... their KX descriptors,
-    std::vector<TurnWork> turn_work_;
-    std::vector<DevEncImage> timages_;       // ... and what the encoder's general kernels need of them
-    std::vector<DevEncLayout> tlayouts_;
-    std::vector<EncWork> twork_blk_, twork_stat_;
-    uint64_t turn_blocks_total_ = 0;
     int n_work_emit_ = 0, n_sub_work_emit_ = 0;  // entries of work_ / sub_work_ in front of the turned images' (which are only counted)
-    std::vector<uint64_t> tout_len_;
-    float last_turn_ms_ = 0, last_turn_decode_ms_ = 0, last_turn_dense_ms_ = 0;
-    hipEvent_t ev_kx0_ = nullptr, ev_kx1_ = nullptr, ev_td_[3] = {};
-    DevBuffer d_turn_images_, d_turn_work_, d_tcoefs_, d_timages_, d_tlayouts_, d_twork_blk_, d_twork_stat_, d_thist_, d_ttables_, d_tbits_, d_tbit_off_,
-        d_traw_bits_, d_traw_, d_tmarks_, d_tchunk_ff_, d_twork_chunk_, d_tout_, d_tout_len_;
     std::vector<Plan> plans_;
     std::vector<uint32_t> scan_ids_;   // jobs that are transcoded, one lane per restart interval ...
     std::vector<HuffWork> work_;
