@@ -215,7 +215,9 @@ void jpgpu_batch_destroy(jpgpu_batch *b);
 /* Host side of SetInput+Identify+the marker loop of Decode up to SOS (ref: JpegDecoder.cs:75-162, 509-617):
  * parses every file's headers/tables, builds device descriptors and uploads the compressed bytes to HBM.
  * `format` is a jpgpu_format.  Images whose headers fail to parse get a per-image status and are skipped.
- * Returns JPGPU_OK if the batch is usable (even if some images failed). */
+ * Returns JPGPU_OK if the batch is usable (even if some images failed).  n == 0 (the arrays may be NULL) is an upload like any other: it
+ * replaces what the batch held, jpgpu_batch_size is 0, jpgpu_batch_output_device reports no bytes, jpgpu_batch_decode and the stage calls
+ * return JPGPU_OK without work, and every per-image call is refused for its index. */
 int jpgpu_batch_upload(jpgpu_batch *b, const uint8_t *const *jpeg, const size_t *len, int n, int format);
 /* The same for input that is not one contiguous span per file: file i consists of the next segments_per_file[i] entries of
  * `segments`, in order -- the ReadOnlySequence<byte> of JpegDecoder.SetInput (JpegDecoder.cs:56-62), which the reference reads
@@ -710,7 +712,8 @@ int jpgpu_batch_upload_coefficients(jpgpu_batch *b, int i, const int16_t *src, s
  * ms[0] marker index, ms[1] Huffman, ms[2] IDCT+output, averaged over the calls that ran serially (see jpgpu_batch_decode);
  * ms[3] whole pipeline, averaged over all calls. */
 int jpgpu_batch_stage_ms(jpgpu_batch *b, float ms[4]);
-/* Synchronisation rounds the self-synchronising DRI = 0 decoder needed in the most recent decode (0 = not used).  The rounds
+/* Synchronisation rounds the self-synchronising DRI = 0 decoder needed in the most recent decode (0 = not used: also behind an upload
+ * without DRI = 0 scans that follows one with them, and in front of an upload's first decode).  The rounds
  * are enqueued ahead and checked on the device (jpgpu_batch_decode does not wait for them): valid after jpgpu_batch_sync /
  * _result / _download_*. */
 int jpgpu_batch_subseq_rounds(const jpgpu_batch *b);
@@ -728,10 +731,12 @@ int jpgpu_batch_progressive_replays(const jpgpu_batch *b);
  * that nothing can hang -- and of no consequence for the results.  Valid after jpgpu_batch_sync. */
 int jpgpu_batch_marker_fallbacks(const jpgpu_batch *b);
 /* Times the enqueued rounds did not reach the fixed point (the synchronising call then issued the step again with the host
- * reading the counts between rounds, and the upload's later decodes stay that way).  Valid after jpgpu_batch_sync. */
+ * reading the counts between rounds, and the upload's later decodes stay that way).  Counted for the batch: an upload does not reset it.
+ * Valid after jpgpu_batch_sync. */
 int jpgpu_batch_subseq_fallbacks(const jpgpu_batch *b);
 /* Times the single-launch progressive path gave up waiting inside the kernel (its scans follow each other's progress, which
- * relies on workgroups being dispatched in list order) and the step was re-issued scan level by scan level.  Valid after
+ * relies on workgroups being dispatched in list order) and the step was re-issued scan level by scan level.  Counted per upload: every
+ * upload starts at 0 (jpgpu_batch_progressive_replays, _marker_fallbacks and _subseq_fallbacks count for the batch).  Valid after
  * jpgpu_batch_result. */
 int jpgpu_batch_progressive_fallbacks(const jpgpu_batch *b);
 /* How the last upload planned the scans of its progressive (SOF2) frames, and which launches the last decode / run_entropy

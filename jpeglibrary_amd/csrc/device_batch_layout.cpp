@@ -177,6 +177,9 @@ void DeviceBatch::reset_upload_state(const UploadPlan &p) {
         replay_done_ = replay_possible_ = prog_by_scan_ = replay_layout_active_ = false;
         replay_saved_jobs_.clear();
         for (ImagePlan &img : images_) img.replay_skip = false;
+        // jpgpu_batch_subseq_rounds is the last decode's, 0 = not used: an upload without DRI = 0 scans used to report the rounds of the
+        // last upload that had some.  (The replay keeps the first pass's count: its own decode has the failed progressive frames alone.)
+        last_subseq_rounds_ = 0;
     }
     status_valid_ = keep_progressive_store_ = defer_refusal_ = false;
     resize_plan_valid_ = false;  // (the images' sizes and places are this upload's)
@@ -536,7 +539,9 @@ void DeviceBatch::plan_entropy_work(UploadPlan &p, size_t ii, int j) {
     // (... and the scans of an image that takes libjpeg's transform: K3J reads every block at its place in the dense store)
     const bool split_wanted = !p.sw.handoff_dense && !entropy_only_ && !keep_canvas_ && !img.windowed && img.orientation == 1 && !img.fancy && img.luma == kLumaNone && !img.islow, split_always = p.sw.handoff_set;
     const int k3_class = fmt_is_interleaved(format_) && !color_kind_by_file(img.color_kind) && img.orientation == 1 && !img.fancy && img.luma == kLumaNone && !img.islow ? idct_layout_class(s) : 0;
-    if (split_wanted && job.kind == kScanSequential && s.dri != 0 && img.jobs.size() == 1 && !img.replay_skip && s.total_mcus > 0 &&
+    // (an image the replay of failed progressive frames leaves alone keeps this form: its planes and flag words are the first pass's, at the
+    // first pass's places, and the coefficient readers expand them from the descriptors of whichever plan is in force)
+    if (split_wanted && job.kind == kScanSequential && s.dri != 0 && img.jobs.size() == 1 && s.total_mcus > 0 &&
         s.blocks_per_mcu != 0 && k3_variant(format_, k3_class, kK3Split).exists &&
         // The planes pay where few blocks reach into coefficients 32..63; all that is known of that in front of the decode is
         // how many bytes of entropy data a block has.  Q75 content has 5.4 (3 % of the blocks flagged; the step 4.9 % faster),
@@ -1110,8 +1115,9 @@ int DeviceBatch::upload_plan(const UploadPlan &p, const std::vector<const uint8_
     bool copying = false;
     if ((e = reserve_and_copy(ups, up, &copying)) != hipSuccess) return hip_fail(e, copying ? "hipMemcpyAsync(descriptors)" : "hipMalloc");
     // the flag region starts from zero: the zero bytes in front of every scan's words stay so (K2 writes flag words only)
+    // (not in the replay of failed progressive frames: it decodes no split scan, and the words of the images it leaves alone are K2's)
     uint8_t *const flags = (uint8_t *)d_coefs_.ptr + ((size_t)coef_store_blocks_ + (size_t)kIdctBlocksPerWg) * 128;
-    if (!split_scans_.empty() && (e = hipMemsetAsync(flags, 0, (size_t)p.flag_words * 8, up)) != hipSuccess) return hip_fail(e, "hipMemsetAsync(hand-off flags)");
+    if (!split_scans_.empty() && !in_replay_ && (e = hipMemsetAsync(flags, 0, (size_t)p.flag_words * 8, up)) != hipSuccess) return hip_fail(e, "hipMemsetAsync(hand-off flags)");
     if ((e = hipMemsetAsync(d_k2_tickets_.ptr, 0, kK2MaxPools * sizeof(uint32_t), up)) != hipSuccess) return hip_fail(e, "hipMemsetAsync(K2 tickets)");
     // K1 in one pass: descriptors cleared when (re)allocated only (their tags are never reused), tickets + the give-up word per upload
     const size_t want = (size_t)p.total_chunks * kMarkerDescBytes + 256;

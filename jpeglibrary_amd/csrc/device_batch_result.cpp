@@ -126,7 +126,10 @@ int DeviceBatch::replay_failed_progressive() {
     std::vector<size_t> fl(images_.size(), 0);
     for (size_t ii = 0; ii < images_.size(); ii++) fl[ii] = images_[ii].file_len;
     in_replay_ = true;
+    // (the replay's plan leaves every image at its place: the flag words of the split scans, which it does not clear, lie behind the store)
+    const uint64_t first_pass_blocks = coef_store_blocks_;
     int rc = layout_and_upload(fp, fl, true);
+    if (rc == JPGPU_OK && coef_store_blocks_ != first_pass_blocks) rc = fail(JPGPU_ERR_INVALID_OPERATION, "the replay's coefficient store differs from the first pass's");
     if (rc == JPGPU_OK) rc = decode();
     if (rc == JPGPU_OK) rc = fetch_status();
     in_replay_ = false;

@@ -9,6 +9,7 @@
         steps 1 and 2 alone: the colour kind, whether libjpeg's transform is taken, the denominator, the oriented reduced frame
     window_rect(name, ow, oh)   the window axis' symbolic values as rectangles of an oriented, reduced frame of ow x oh pixels
     rows() / uploads()          the covering array (built once, from a fixed seed) and its rows grouped into uploads
+    row_outcome(k)              expected() of row k, cached: test_policy_matrix_gpu.py and test_batch_reuse_gpu.py share one computation per row
     required_tuples()           the pairs and triples the array has to cover; tuples_of(row) what one row covers
 
 Rules the model takes from the header, not from the planner:
@@ -349,6 +350,16 @@ def row_expected(row):
     fmt, consts, resize = sink(row.sink)
     return expected(f, arithmetic=row.arithmetic, scale=row.scale, upsampling=row.upsampling, color=row.color, mode=row.mode, orientation=row.orientation,
                     window=window_rect(row.window, plan.width, plan.height), fmt=fmt, consts=consts, resize=resize)
+
+
+_OUTCOME = {}
+
+
+def row_outcome(k):
+    """row_expected of row k of rows(), computed once for every suite that walks the array and never changed"""
+    if k not in _OUTCOME:
+        _OUTCOME[k] = row_expected(rows()[k])
+    return _OUTCOME[k]
 
 
 def row_refused(row):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import float_sink_model as fm
 import jpeglibrary_amd as jl
 import orient_model as om
 import policy_model as pm
@@ -17,21 +18,18 @@ from test_color_gpu import _assert_bits
 pytestmark = pytest.mark.gpu
 
 _TORCH = {np.uint8: torch.uint8, np.float16: torch.float16, np.float32: torch.float32}
-_OUTCOME = {}
+_outcome = pm.row_outcome  # the model of row k, computed once (shared with test_batch_reuse_gpu.py) and never changed
 
 
-def _outcome(k):
-    """the model of row k, computed once and never changed"""
-    if k not in _OUTCOME:
-        _OUTCOME[k] = pm.row_expected(pm.rows()[k])
-    return _OUTCOME[k]
-
-
-def _upload(settings, images, files=None, orientation_policy=None):
+def _upload(settings, images, files=None, orientation_policy=None, batch=None):
     """settings: a Row whose upload axes count; images: [(file name, orientation, window rectangle or None)] -> the Batch, uploaded, not decoded.
-    files: the bytes to upload in place of the named files'; orientation_policy: set it and give no list"""
+    files: the bytes to upload in place of the named files'; orientation_policy: set it and give no list; batch: a Batch that has been used
+    (test_batch_reuse_gpu.py) in place of a fresh one -- what this upload does not set is first put back to what a fresh Batch has"""
     fmt, consts, resize = pm.sink(settings.sink)
-    b = jl.Batch().set_arithmetic_policy(settings.arithmetic).set_upsampling_policy(settings.upsampling).set_color_policy(settings.color)
+    b = jl.Batch() if batch is None else batch
+    if batch is not None:
+        b.set_resize(None).set_scale_fit(None).set_output_affine(*fm.DEFAULT).set_orientation_policy("stored").set_orientations(None).set_windows(None)
+    b.set_arithmetic_policy(settings.arithmetic).set_upsampling_policy(settings.upsampling).set_color_policy(settings.color)
     b.set_channels_policy(settings.mode)
     if settings.scale == "fit":
         b.set_scale_fit(pm.FIT)
@@ -84,10 +82,10 @@ def _check_image(b, i, want, what):
     _assert_bits(b.output(i), want.output, what)
 
 
-def _check_upload(settings, ks):
+def _check_uploaded(b, settings, ks):
+    """b: the rows ks uploaded under settings, not decoded -> decoded over 0xA5 and checked against the model; b is left open"""
     wants = [_outcome(k) for k in ks]
     what = ["row %d %r" % (k, tuple(pm.rows()[k])) for k in ks]
-    b = _upload(settings, _row_images(ks))
     after = _poisoned_decode(b)
     end = 0
     for i, want in enumerate(wants):
@@ -111,6 +109,11 @@ def _check_upload(settings, ks):
         assert w.refused or b.output(i).tobytes() == first[i], "the second decode of " + what[i]
     if resized is not None:
         assert b.resized().tobytes() == resized.tobytes(), "the second decode's resized buffer"
+
+
+def _check_upload(settings, ks):
+    b = _upload(settings, _row_images(ks))
+    _check_uploaded(b, settings, ks)
     b.close()
 
 
