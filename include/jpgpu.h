@@ -960,7 +960,8 @@ int jpgpu_encoder_set_quantization_table(jpgpu_encoder *e, int i, int identifier
 int jpgpu_encoder_encode(jpgpu_encoder *e);
 /* Device time (ms, HIP events) of the last jpgpu_encoder_encode by stage: ms[0] pixels -> quantised zig-zag blocks (ReadBlock, FDCT,
  * ZigZagAndQuantizeBlock: JpegEncoder.cs:662-741, 812-826; with optimize_coding also GatherBlockStatistics :552-597), ms[1] code lengths
- * and bit offsets, ms[2] bit emission (EncodeBlock :828-925), ms[3] byte stuffing (JpegWriter.cs:133-232), ms[4] their sum. */
+ * and bit offsets, ms[2] bit emission (EncodeBlock :828-925), ms[3] byte stuffing (JpegWriter.cs:133-232), ms[4] their sum.  Which kernels
+ * of JPGPU_CODING_OPTIMIZED and JPGPU_CODING_PROGRESSIVE count in which entry: (4e), "Stages". */
 int jpgpu_encoder_stage_ms(jpgpu_encoder *e, float ms[5]);
 /* How the entropy stage of this encoder's jpgpu_encoder_encode calls ran: *one_pass = calls that counted and emitted the bits in ONE
  * pass over the blocks (uploads of two or more images without restart intervals: EncodeBlock, JpegEncoder.cs:828-925, run once per
@@ -1097,13 +1098,72 @@ int jpgpu_encoder_upload_described_device(jpgpu_encoder *e, const void *const *d
  * whole upload); jpgpu_encoder_upload_described and _upload_described_device (JPGPU_ERR_INVALID_OPERATION): a description is the
  * reference's encoder state.
  *   State of the encoder: every later jpgpu_encoder_upload / _upload_device reads it until it is set again; an upload keeps the arithmetic it
- * was planned with.  Not covered: libjpeg's optimised tables, progressive output, smoothing, other sampling (4:4:0, 4:1:1), other segments
- * (density, ICC, EXIF); the JpegEncoder mirror and the optimizer.
+ * was planned with.  libjpeg's optimised tables and its progressive output are the coding policy's (4e).  Not covered: smoothing, other sampling
+ * (4:4:0, 4:1:1), other segments (density, ICC, EXIF); the JpegEncoder mirror and the optimizer.
  * JPGPU_ERR_ARGUMENT for any other value of `policy` (a jpgpu_arithmetic_policy). */
 int jpgpu_encoder_set_arithmetic_policy(jpgpu_encoder *e, int policy);
 /* JPGPU_ARITHMETIC_LIBJPEG where image i of the last upload was planned with the integer transform, else JPGPU_ARITHMETIC_REFERENCE.  Valid
  * after an upload; JPGPU_ERR_ARGUMENT for a NULL argument or an index out of range. */
 int jpgpu_encoder_image_arithmetic(const jpgpu_encoder *e, int i, int *arithmetic);
+/* ---- (4e) Coding: libjpeg's optimal Huffman tables and its progressive mode (an extension beyond the reference; what Pillow's
+ * Image.save(..., optimize=True) and Image.save(..., progressive=True) write).  Under JPGPU_ARITHMETIC_LIBJPEG only; steps 1 to 6 of (4d) and
+ * the blocks jpgpu_encoder_download_coefficients returns are the same under all three codings.
+ *   JPGPU_CODING_STANDARD, the default: every stream is what it was.
+ *   JPGPU_CODING_OPTIMIZED: sequential SOF0 as in (4d) 7, with the DHT segments DC0, AC0 (, DC1, AC1) holding tables built from the image's
+ * own symbols by the rule of jpgpu_libjpeg_optimal_table below.  restart_interval is honoured (the statistics see the same predictor resets).
+ *   JPGPU_CODING_PROGRESSIVE: SOF2 with the scan script of jpeg_simple_progression.  The header is (4d)'s up to the frame header, SOF2 in
+ * place of SOF0, nothing behind it.  Then per scan: one DHT segment per table the scan built, SOS, the scan's data; EOI.
+ *     Three components, ten scans (component identifiers 1 = Y, 2 = Cb, 3 = Cr; Ss-Se, Ah, Al):
+ *       1. DC of 1, 2, 3, Al = 1 (selectors 0x00, 0x10, 0x10; DHT DC0 and DC1 in front)      2. 1: 1-5, Al = 2       3. 3: 1-63, Al = 1
+ *       4. 2: 1-63, Al = 1      5. 1: 6-63, Al = 2      6. 1: 1-63, Ah = 2, Al = 1      7. DC of 1, 2, 3, Ah = 1, Al = 0 (selectors 0, no DHT)
+ *       8. 3: 1-63, Ah = 1, Al = 0      9. 2: 1-63, Ah = 1, Al = 0      10. 1: 1-63, Ah = 1, Al = 0
+ *     One component, six scans: DC Al = 1; 1-5 Al = 2; 6-63 Al = 2; 1-63 Ah = 2 Al = 1; DC Ah = 1; 1-63 Ah = 1 Al = 0.
+ *     Luma codes with table 0, chroma with table 1 (an AC scan: selector 0x00 / 0x01); every scan's tables are built from that scan alone.
+ *     BLOCK ORDER.  A DC scan of three components is interleaved: MCU order, dummy blocks included.  An AC scan (and every scan of one
+ *     component) visits the REAL blocks of its component, ceil(w_c / 8) x ceil(h_c / 8) in raster order.
+ *     DC first: v = coef[0] >> Al (arithmetic), the difference to the component's previous v coded as in a sequential scan.  DC refinement:
+ *     the bit (coef[0] >> Al) & 1 per block, no table.
+ *     AC first, k over the band, t = |coef[k]| >> Al: t == 0: r++.  Else: flush the EOB run; ZRL (0xF0) while r > 15; symbol (r << 4) + nbits(t)
+ *     and nbits bits (t, or ~t for a negative coefficient); r = 0.  At the block's end r > 0: EOBRUN++, flushed when it reaches 0x7FFF.
+ *     AC refinement, abs[k] = |coef[k]| >> Al, EOB = the last k with abs == 1, r = BR = 0.  abs == 0: r++.  Else: while r > 15 && k <= EOB: flush,
+ *     ZRL, r -= 16, the block's BR buffered bits, BR = 0.  abs > 1: buffer the bit abs & 1, BR++.  abs == 1: flush, symbol (r << 4) + 1, the sign
+ *     bit (0: negative), the BR buffered bits, BR = r = 0.  At the block's end r > 0 || BR > 0: EOBRUN++, BE += BR, flushed when EOBRUN == 0x7FFF
+ *     or BE > 937.
+ *     A flush writes symbol n << 4 with n = floor(log2(EOBRUN)), the low n bits of EOBRUN, then the BE bits buffered by the run's blocks; the
+ *     scan's end flushes.  Every scan ends padded with one-bits to a byte; FF is stuffed with 00.  The statistics take the same road.
+ *     Files are those of progressive=True with or without optimize=True.
+ *   Stages (jpgpu_encoder_stage_ms keeps five entries).  OPTIMIZED: the statistics kernel counts as stage E1, as under optimize_coding.
+ * PROGRESSIVE: E1 as ever; ms[1] (E2) = block classification, run resolution and the statistics of all scans of all images (one copy to the
+ * host and one table build per batch follow, not timed); ms[2] (E3) = bit counts, offsets and emission; ms[3] (E4) = byte stuffing per scan
+ * and the assembly of header | (DHT, SOS, data) per scan | EOI in device memory (jpgpu_encoder_output_device works as ever).
+ *   Output reservation: a scan's raw bit count is known exactly from its statistics before anything is written (sum of count x code length
+ * plus the counted extra bits).  A scan's part of the file is at most its DHT and SOS segments + 2 x ceil(bits / 8) bytes (every byte
+ * stuffed); the file is at most the frame header + the sum of these over its scans + 2 (EOI), and that is what is reserved for it, plus 64
+ * bytes of slack, rounded up to 256 so that every file starts aligned.
+ *   Refused at the upload with JPGPU_ERR_ARGUMENT, the encoder staying usable: a coding other than JPGPU_CODING_STANDARD while the arithmetic
+ * policy is JPGPU_ARITHMETIC_REFERENCE (the reference's encoder has neither; its optimize_coding stays what it is), and JPGPU_CODING_PROGRESSIVE
+ * with restart_interval != 0.  optimize_coding != 0 under JPGPU_ARITHMETIC_LIBJPEG and the described uploads keep the refusals of (4d).
+ *   State of the encoder like the arithmetic policy: later uploads read it until it is set again, an upload keeps what it was planned with.
+ *   Out of scope: progressive with restart intervals, custom scan scripts, the JpegEncoder mirror and described uploads, JPGPU_ARITHMETIC_REFERENCE,
+ * the optimizer.
+ * JPGPU_ERR_ARGUMENT for any other value of `policy`. */
+typedef enum jpgpu_coding_policy {
+    JPGPU_CODING_STANDARD = 0,   /* the Annex K tables, sequential */
+    JPGPU_CODING_OPTIMIZED = 1,  /* sequential, tables built from the image by libjpeg's rule */
+    JPGPU_CODING_PROGRESSIVE = 2 /* SOF2, jpeg_simple_progression, a table built per scan */
+} jpgpu_coding_policy;
+int jpgpu_encoder_set_coding_policy(jpgpu_encoder *e, int policy);
+/* The jpgpu_coding_policy image i of the last upload was planned with.  JPGPU_ERR_ARGUMENT for a NULL argument or an index out of range. */
+int jpgpu_encoder_image_coding(const jpgpu_encoder *e, int i, int *coding);
+/* Host only, no context, no device: libjpeg's jpeg_gen_optimal_table.  freq[256] are a table's symbol counts.  A pseudo-symbol 256 of count 1
+ * joins them, so that no code is all ones.  Repeat: c1 = the symbol of the least non-zero count, among equals the LARGEST index; c2 the next
+ * least by the same rule; freq[c1] += freq[c2], freq[c2] = 0, one bit more for every symbol on both chains, the chains linked.  Count the code
+ * sizes (up to 32), then limit them to 16: for i = 32 .. 17, while bits[i] > 0: j = i - 2 stepping down to the first bits[j] != 0; bits[i] -= 2,
+ * bits[i - 1]++, bits[j + 1] += 2, bits[j]--.  The pseudo-symbol leaves the longest non-empty length.  bits16[l - 1] = codes of length l;
+ * values[0 .. *n_values) = the symbols by code size, then by value (a histogram of one symbol gives it a 1-bit code).  A histogram of
+ * nothing but zeros gives the empty table: JPGPU_OK, sixteen zero counts, *n_values = 0, values untouched.
+ * JPGPU_ERR_ARGUMENT for a NULL argument. */
+int jpgpu_libjpeg_optimal_table(const uint32_t freq[256], uint8_t bits16[16], uint8_t values[256], int *n_values);
 /* status of image i as known so far (after the upload: JPGPU_OK or the refusal; after the encode also "No symbol is recorded.") */
 int jpgpu_encoder_image_status(const jpgpu_encoder *e, int i);
 /* Host only, no context, no device: the status an encode of `desc` would report, with its message in message[message_cap]

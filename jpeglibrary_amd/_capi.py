@@ -145,6 +145,8 @@ UPSAMPLING_POLICIES = ("replicate", "fancy")
 CHANNELS_POLICIES = ("rgb", "gray")
 # jpgpu_arithmetic_policy, by its Python names
 ARITHMETIC_POLICIES = ("reference", "libjpeg")
+# jpgpu_coding_policy, by its Python names
+CODING_POLICIES = ("standard", "optimized", "progressive")
 # the denominators of jpgpu_batch_set_scale_policy
 SCALE_DENOMINATORS = (1, 2, 4, 8)
 
@@ -310,6 +312,9 @@ SYMBOLS = [
     ("jpgpu_encoder_image_status", C.c_int, [_P, C.c_int]),
     ("jpgpu_encoder_set_arithmetic_policy", C.c_int, [_P, C.c_int]),
     ("jpgpu_encoder_image_arithmetic", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("jpgpu_encoder_set_coding_policy", C.c_int, [_P, C.c_int]),
+    ("jpgpu_encoder_image_coding", C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    ("jpgpu_libjpeg_optimal_table", C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
     ("jpgpu_encode_description_header", C.c_int, [C.POINTER(EncodeDescription), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p,
                                                   C.c_size_t]),
     ("jpgpu_optimizer_create", C.c_int, [_P, C.POINTER(_P)]),

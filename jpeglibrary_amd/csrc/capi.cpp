@@ -16,6 +16,7 @@
 #include "device_encode.h"
 #include "device_optimize.h"
 #include "host.h"
+#include "libjpeg_huffman.h"
 #include "resize_tables.h"
 
 using namespace jpgpu;
@@ -1500,6 +1501,13 @@ int jpgpu_encoder_set_quantization_table(jpgpu_encoder *enc, int i, int identifi
 int jpgpu_encoder_set_arithmetic_policy(jpgpu_encoder *enc, int policy) { JPGPU_GUARD(enc, enc->impl.set_arithmetic_policy(policy)); }
 int jpgpu_encoder_image_arithmetic(const jpgpu_encoder *enc, int i, int *arithmetic) {
     return enc ? enc->impl.image_arithmetic(i, arithmetic) : JPGPU_ERR_ARGUMENT;
+}
+int jpgpu_encoder_set_coding_policy(jpgpu_encoder *enc, int policy) { JPGPU_GUARD(enc, enc->impl.set_coding_policy(policy)); }
+int jpgpu_encoder_image_coding(const jpgpu_encoder *enc, int i, int *coding) { return enc ? enc->impl.image_coding(i, coding) : JPGPU_ERR_ARGUMENT; }
+int jpgpu_libjpeg_optimal_table(const uint32_t freq[256], uint8_t bits16[16], uint8_t values[256], int *n_values) {
+    if (!freq || !bits16 || !values || !n_values) return JPGPU_ERR_ARGUMENT;
+    libjpeg_optimal_table(freq, bits16, values, n_values);
+    return JPGPU_OK;
 }
 int jpgpu_encoder_encode(jpgpu_encoder *enc) { JPGPU_GUARD(enc, enc->impl.encode()); }
 int jpgpu_encoder_stage_ms(jpgpu_encoder *enc, float ms[5]) { JPGPU_GUARD(enc, enc->impl.stage_ms(ms)); }

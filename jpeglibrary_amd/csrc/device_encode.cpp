@@ -4,6 +4,7 @@
 // the per-block arithmetic and the entropy coding run in encode_kernels.hip.
 #include "device_encode.h"
 #include "device_optimize.h"
+#include "libjpeg_huffman.h"
 
 #include <string.h>
 
@@ -191,7 +192,7 @@ void put_segment(std::vector<uint8_t> &h, int marker, const Body &body) {
 
 // jcmarker.c: write_file_header (SOI, APP0), write_frame_header (a DQT segment per table in use, SOF0), write_scan_header (a DHT
 // segment per table in use: DC then AC of each component's pair; DRI; SOS)
-void write_libjpeg_header(const DevEncImage &im, int restart_interval, std::vector<uint8_t> *header) {
+void write_libjpeg_header(const DevEncImage &im, int restart_interval, std::vector<uint8_t> *header, const std::vector<std::vector<uint8_t>> *dht, int frame) {
     std::vector<uint8_t> &h = *header;
     h.clear();
     const int nc = (int)im.components;
@@ -208,8 +209,13 @@ void write_libjpeg_header(const DevEncImage &im, int restart_interval, std::vect
         sof.push_back(c == 0 ? (uint8_t)((im.luma_h << 4) | im.luma_v) : (uint8_t)0x11);
         sof.push_back(c == 0 ? 0 : 1);
     }
-    put_segment(h, 0xC0, sof);
+    put_segment(h, frame, sof);
+    if (frame == 0xC2) return;  // a progressive frame: every scan brings its tables and its SOS
     for (int t = 0; t < (nc == 3 ? 4 : 2); t++) {  // DC0, AC0, DC1, AC1
+        if (dht) {
+            put_segment(h, 0xC4, (*dht)[(size_t)t]);
+            continue;
+        }
         std::vector<uint8_t> body(1, (uint8_t)(((t & 1) << 4) | (t >> 1)));
         body.insert(body.end(), kStd[t].lengths, kStd[t].lengths + 16);
         body.insert(body.end(), kStd[t].values, kStd[t].values + kStd[t].count);
@@ -597,6 +603,7 @@ EncodeBatch::~EncodeBatch() {
                          &d_work_order_, &d_layouts_})
         b->release();
     tail_.release();
+    prog_.release();
 }
 
 int EncodeBatch::fail(int status, const std::string &msg) {
@@ -639,6 +646,28 @@ int EncodeBatch::image_arithmetic(int i, int *arithmetic) const {
     return JPGPU_OK;
 }
 
+int EncodeBatch::set_coding_policy(int policy) {
+    if (policy != JPGPU_CODING_STANDARD && policy != JPGPU_CODING_OPTIMIZED && policy != JPGPU_CODING_PROGRESSIVE)
+        return fail(JPGPU_ERR_ARGUMENT, "jpgpu_encoder_set_coding_policy: the policy is JPGPU_CODING_STANDARD (0), JPGPU_CODING_OPTIMIZED (1) or JPGPU_CODING_PROGRESSIVE (2)");
+    coding_policy_ = policy;
+    return JPGPU_OK;
+}
+int EncodeBatch::image_coding(int i, int *coding) const {
+    if (i < 0 || i >= (int)images_.size() || !coding) return JPGPU_ERR_ARGUMENT;
+    *coding = coding_;
+    return JPGPU_OK;
+}
+
+// What the coding policy refuses of an upload, before anything of the encoder's state is touched
+int EncodeBatch::check_coding_params(const jpgpu_encode_params *params, int n) {
+    if (coding_policy_ == JPGPU_CODING_STANDARD) return JPGPU_OK;
+    if (arithmetic_policy_ != JPGPU_ARITHMETIC_LIBJPEG)
+        return fail(JPGPU_ERR_ARGUMENT, "JPGPU_CODING_OPTIMIZED and JPGPU_CODING_PROGRESSIVE are libjpeg's codings: they need JPGPU_ARITHMETIC_LIBJPEG (the reference's encoder has optimize_coding).");
+    for (int i = 0; i < n && coding_policy_ == JPGPU_CODING_PROGRESSIVE; i++)
+        if (params[i].restart_interval != 0) return fail(JPGPU_ERR_ARGUMENT, "JPGPU_CODING_PROGRESSIVE takes no restart interval.");
+    return JPGPU_OK;
+}
+
 // What the libjpeg policy refuses of an upload, before anything of the encoder's state is touched
 int EncodeBatch::check_libjpeg_params(const jpgpu_encode_params *params, int n) {
     for (int i = 0; i < n; i++) {
@@ -656,18 +685,25 @@ int EncodeBatch::upload_params(const uint8_t *const *pixels, const jpgpu_encode_
         const int rc = check_libjpeg_params(params, n);
         if (rc != JPGPU_OK) return rc;
     }
+    int rc = check_coding_params(params, n);
+    if (rc != JPGPU_OK) return rc;
     std::vector<EncPlan> plans((size_t)n);
     for (int i = 0; i < n; i++) {
         plans[(size_t)i].legacy = true;
         plans[(size_t)i].params = params[i];
     }
     upload_described_ = false;
-    return upload_plans(pixels, plans, device, pixel_layouts);
+    coding_ = coding_policy_;
+    rc = upload_plans(pixels, plans, device, pixel_layouts);
+    if (rc == JPGPU_OK && coding_ == JPGPU_CODING_PROGRESSIVE) rc = plan_progressive();
+    return rc;
 }
 
 int EncodeBatch::upload_descriptions(const uint8_t *const *pixels, const jpgpu_encode_description *desc, int n, bool device, const int32_t *pixel_layouts) {
     if (arithmetic_policy_ == JPGPU_ARITHMETIC_LIBJPEG)
         return fail(JPGPU_ERR_INVALID_OPERATION, "A described image is the reference's encoder state: JPGPU_ARITHMETIC_LIBJPEG covers jpgpu_encoder_upload and jpgpu_encoder_upload_device.");
+    if (coding_policy_ != JPGPU_CODING_STANDARD)
+        return fail(JPGPU_ERR_ARGUMENT, "JPGPU_CODING_OPTIMIZED and JPGPU_CODING_PROGRESSIVE are libjpeg's codings: they need JPGPU_ARITHMETIC_LIBJPEG and jpgpu_encoder_upload.");
     std::vector<EncPlan> plans((size_t)n);
     for (int i = 0; i < n; i++) {
         std::string error;
@@ -675,6 +711,7 @@ int EncodeBatch::upload_descriptions(const uint8_t *const *pixels, const jpgpu_e
         if (rc != JPGPU_OK) return fail(rc, error);
     }
     upload_described_ = true;
+    coding_ = JPGPU_CODING_STANDARD;
     return upload_plans(pixels, plans, device, pixel_layouts);
 }
 
@@ -876,7 +913,8 @@ int EncodeBatch::plan_encode_action_image(UploadPlan &up, int i, const EncPlan &
     im.bpm = im.luma_h * im.luma_v + (im.components == 3 ? 2 : 0);
     im.input_rgb = p.input_rgb ? 1 : 0;
     im.restart_interval = (uint32_t)p.restart_interval;
-    if (p.optimize_coding) {
+    const bool libjpeg_tables = libjpeg && coding_ == JPGPU_CODING_OPTIMIZED;  // built from the image by libjpeg's rule (build_libjpeg_tables)
+    if (p.optimize_coding || libjpeg_tables) {
         most_optimal_[i] = p.optimize_coding == 2;  // JpegEncoder.MostOptimalCoding
         optimized_.push_back(i);
         im.table_base = 4u * (uint32_t)optimized_.size();  // tables 0..3 are the standard ones
@@ -888,10 +926,12 @@ int EncodeBatch::plan_encode_action_image(UploadPlan &up, int i, const EncPlan &
         scale_by_quality(kStdLum, p.quality, im.quant[0]);
         scale_by_quality(kStdChr, p.quality, im.quant[1]);
     }
-    plan_image_work(up, i, p.optimize_coding != 0);
-    if (libjpeg) {  // (E1J gathers into LDS: no samples in HBM; no tables to build: the header is final)
-        write_libjpeg_header(im, p.restart_interval, &headers_[i]);
+    plan_image_work(up, i, p.optimize_coding != 0 || libjpeg_tables);
+    if (libjpeg) {  // (E1J gathers into LDS: no samples in HBM; the standard coding builds no tables: the header is final)
+        write_libjpeg_header(im, p.restart_interval, &headers_[i], nullptr, coding_ == JPGPU_CODING_PROGRESSIVE ? 0xC2 : 0xC0);
         im.header_len = (uint32_t)headers_[i].size();
+        // built tables: the DHT segments are written once the statistics are in; reserve the largest they can be (256 values each)
+        if (libjpeg_tables) im.header_len += 4u * 256u;
         return JPGPU_OK;
     }
     if ((up.smp_off >> 8) > 0xFFFFFFFFull) return fail(JPGPU_ERR_OUT_OF_MEMORY, "sample buffer beyond 1 TiB");
@@ -1025,6 +1065,7 @@ int EncodeBatch::encode() {
     if ((rc = run_fdct(r)) != JPGPU_OK) return rc;
     if ((!optimized_.empty() || any_general_builder_) && (rc = build_coding_tables(r)) != JPGPU_OK) return rc;
     (void)hipEventRecord(ev_[1], ctx_->stream);
+    if (coding_ == JPGPU_CODING_PROGRESSIVE) return encode_progressive();  // (its own entropy coder, ev_[2] .. ev_[5] at its stages)
     if ((rc = try_one_pass_emit(r)) != JPGPU_OK) return rc;
     if (!r.fused_emit && (rc = count_bits_two_kernels(r)) != JPGPU_OK) return rc;  // (ev_[2] is recorded behind whichever kernel counted)
     if ((rc = plan_stuffing(r)) != JPGPU_OK) return rc;
@@ -1108,6 +1149,18 @@ bool EncodeBatch::build_image_tables(int i, const EncPlan *described, const uint
     return built;
 }
 
+// JPGPU_CODING_OPTIMIZED: the tables libjpeg builds from the image's counters (DC0, AC0 and, with three components, DC1, AC1), and the
+// header with their DHT segments
+bool EncodeBatch::build_libjpeg_tables(int i, const uint32_t *counters, EncHuffTable *tables) {
+    const DevEncImage &im = images_[i];
+    std::vector<std::vector<uint8_t>> dht(4);
+    for (int t = 0; t < (im.components == 3 ? 4 : 2); t++)
+        libjpeg_build_table(counters + (size_t)t * 256, (uint8_t)(((t & 1) << 4) | (t >> 1)), &tables[t], &dht[(size_t)t]);
+    write_libjpeg_header(im, (int)im.restart_interval, &headers_[i], &dht);
+    images_[i].header_len = (uint32_t)headers_[i].size();
+    return true;
+}
+
 // optimizeCoding: BuildHuffmanTables (:491-550) -- statistics on the device, JpegHuffmanEncodingTableBuilder.Build on the host
 int EncodeBatch::build_coding_tables(const EncodeRun &r) {
     const size_t n_hist = ((size_t)r.n * 4 + general_.size() * 8) * 256;
@@ -1125,6 +1178,10 @@ int EncodeBatch::build_coding_tables(const EncodeRun &r) {
     for (size_t k = 0; k < optimized_.size(); k++) {
         const int i = optimized_[k];
         status_[i] = JPGPU_OK;
+        if (images_[i].arithmetic == JPGPU_ARITHMETIC_LIBJPEG) {
+            build_libjpeg_tables(i, &hist[(size_t)i * 4 * 256], &built[4 * k]);
+            continue;
+        }
         // "No symbol is recorded." (a single-component image: empty chrominance builders)
         if (!build_image_tables(i, nullptr, &hist[(size_t)i * 4 * 256], most_optimal_[i] != 0, &built[4 * k])) status_[i] = JPGPU_ERR_INVALID_OPERATION;
     }
@@ -1281,7 +1338,7 @@ int EncodeBatch::download(int i, void *dst, size_t cap) {
     if (!encoded_) return fail(JPGPU_ERR_INVALID_OPERATION, "Nothing has been encoded yet.");
     if (status_[i] != JPGPU_OK) return fail(status_[i], messages_[i]);
     if (cap < tail_.h_out_len[i]) return fail(JPGPU_ERR_ARGUMENT, "Destination buffer is too small.");
-    hipError_t e = hipMemcpy(dst, (const uint8_t *)tail_.out.ptr + images_[i].out_off, (size_t)tail_.h_out_len[i], hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(dst, stream_of(i), (size_t)tail_.h_out_len[i], hipMemcpyDeviceToHost);
     return e == hipSuccess ? JPGPU_OK : hip_fail(e, "hipMemcpy(encoded stream)");
 }
 
@@ -1300,7 +1357,7 @@ int EncodeBatch::download_coefficients(int i, int16_t *dst, size_t cap_blocks) {
             const uint32_t bx = (mcu % im.mcus_per_line) * L.h[c] + L.blk_x[b], by = (mcu / im.mcus_per_line) * L.v[c] + L.blk_y[b];
             if ((bx >= L.grid_w[c] || by >= L.grid_h[c]) && blk != L.dummy_blk) memcpy(dst + (size_t)blk * 64, dst + (size_t)L.dummy_blk * 64, 128);
         }
-    } else if (im.table_base != 0) {
+    } else if (im.table_base != 0 && im.arithmetic == JPGPU_ARITHMETIC_REFERENCE) {
         // optimizeCoding: the blocks as BuildHuffmanTables / WritePreparedScanData see them -- luma blocks outside the
         // component's own grid alias the allocator's dummy block (enc_source_block in encode_kernels.hip)
         const uint32_t ny = im.luma_h * im.luma_v, last = (im.mcus_per_line * im.mcus_per_column - 1) * im.bpm + ny - 1;

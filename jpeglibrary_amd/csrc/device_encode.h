@@ -6,6 +6,7 @@
 #include "../../include/jpgpu.h"
 #include "device_batch.h"
 #include "encode_kernels.h"
+#include "encode_progressive.h"
 #include "optimize_walk.h"  // put_marker, put_length
 
 namespace jpgpu {
@@ -29,7 +30,10 @@ void assemble_header(const std::vector<uint8_t> &pre, const std::vector<uint8_t>
 
 // SOI .. SOS as libjpeg writes them (include/jpgpu.h 4d): SOI, APP0 "JFIF", one DQT segment per table, SOF0, one DHT segment per standard
 // table, (DRI,) SOS.  `im` holds the geometry and the tables; a one-component image names table 0 and the two luminance Huffman tables only.
-void write_libjpeg_header(const DevEncImage &im, int restart_interval, std::vector<uint8_t> *header);
+// `dht`: the bodies of the DHT segments (Tc/Th, counts, values) in place of the standard tables; frame 0xC2: a progressive frame's header, which ends
+// behind SOF2 (every scan brings its tables and its SOS).
+void write_libjpeg_header(const DevEncImage &im, int restart_interval, std::vector<uint8_t> *header, const std::vector<std::vector<uint8_t>> *dht = nullptr,
+                          int frame = 0xC0);
 // ... and where the 64 elements of quantisation table `identifier` stand in it (0: the header holds no such table)
 size_t libjpeg_header_quant_at(const DevEncImage &im, int identifier);
 
@@ -116,6 +120,9 @@ class EncodeBatch {
     // the arithmetic of the uploads from here on (jpgpu_encoder_set_arithmetic_policy), and what image i of the last one was planned with
     int set_arithmetic_policy(int policy);
     int image_arithmetic(int i, int *arithmetic) const;
+    // the entropy coding of the uploads from here on (jpgpu_encoder_set_coding_policy), and what image i of the last one was planned with
+    int set_coding_policy(int policy);
+    int image_coding(int i, int *coding) const;
     int encode();                                                                        // JpegEncoder.Encode() x n
     // device time of the last encode() by stage (HIP events on the context's stream): E1 pixels -> quantised blocks, E2 bit counts
     // and offsets, E3 bit emission, E4 byte stuffing; ms[4] = the four together (the host round trips between them excluded)
@@ -129,7 +136,7 @@ class EncodeBatch {
     void *output_device(int i, size_t *bytes) const {
         if (i < 0 || i >= (int)images_.size() || !encoded_) return nullptr;
         if (bytes) *bytes = (size_t)tail_.h_out_len[i];
-        return (uint8_t *)tail_.out.ptr + images_[i].out_off;
+        return stream_of(i);
     }
 
   private:
@@ -144,6 +151,7 @@ class EncodeBatch {
     int layout_plans(UploadPlan &up, const std::vector<EncPlan> &plans);
     int check_device_arguments(const UploadPlan &up, int n);
     int check_libjpeg_params(const jpgpu_encode_params *params, int n);
+    int check_coding_params(const jpgpu_encode_params *params, int n);
     void reset_upload_state(int n);
     int plan_described_image(UploadPlan &up, int i, const EncPlan &pl);
     int plan_encode_action_image(UploadPlan &up, int i, const EncPlan &pl);
@@ -164,7 +172,33 @@ class EncodeBatch {
     int plan_stuffing(const EncodeRun &r);
     int place_headers(const EncodeRun &r);
     int emit_and_stuff(const EncodeRun &r);
+    bool build_libjpeg_tables(int i, const uint32_t *counters, EncHuffTable *tables);
+    // the finished stream of image i in device memory
+    uint8_t *stream_of(int i) const {
+        if (coding_ == JPGPU_CODING_PROGRESSIVE) return (uint8_t *)prog_.out.ptr + prog_.files[(size_t)i].dst_off;
+        return (uint8_t *)tail_.out.ptr + images_[(size_t)i].out_off;
+    }
+    // coding "progressive" (device_encode_progressive.cpp): the scans of every image as units of work, planned at the upload; the entropy
+    // coder of encode() behind E1
+    struct Progressive {
+        std::vector<DevProgScan> scans;
+        std::vector<int> scan_image;          // the image a scan belongs to
+        std::vector<EncWork> work;            // per 256 blocks of a scan
+        std::vector<DevProgFile> files;       // per image
+        std::vector<DevEncImage> streams;     // per scan: the stuffing stage's descriptor (its "header": the scan's DHT segments and SOS)
+        std::vector<uint8_t> headers;         // every image's frame header, every scan's DHT + SOS
+        uint64_t total_blocks = 0;
+        int max_scans = 0;
+        DevBuffer d_scans, d_work, d_info, d_heads, d_bits, d_wg_bits, d_wg_base, d_stats, d_tables, d_files, d_streams, d_headers, out, d_file_len;
+        EntropyTail tail;  // E4 over the scans
+        void release();
+    };
+    Progressive prog_;
+    int plan_progressive();
+    int encode_progressive();
     jpgpu_ctx *ctx_;
+    int coding_policy_ = JPGPU_CODING_STANDARD;  // state of the encoder, read by the uploads like the arithmetic policy
+    int coding_ = JPGPU_CODING_STANDARD;         // ... and what the last upload was planned with
     int arithmetic_policy_ = JPGPU_ARITHMETIC_REFERENCE;  // state of the encoder: jpgpu_encoder_upload and _upload_device read it
     std::vector<DevEncImage> images_;
     std::vector<std::vector<uint8_t>> headers_;        // SOI .. SOS as Encode() writes them (optimizeCoding: rebuilt per encode())

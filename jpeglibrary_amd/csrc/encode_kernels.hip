@@ -1028,7 +1028,7 @@ __device__ __forceinline__ uint32_t enc_bit_count(uint32_t a) { return a ? 32u -
 // luma component can leave its grid (the others are 1 x 1 per MCU), and whenever some block does, the last luma block of
 // the last MCU does: that block's coefficients stand in for all of them.
 __device__ __forceinline__ uint32_t enc_source_block(const DevEncImage &im, uint32_t blk) {
-    if (im.table_base == 0) return blk;
+    if (im.table_base == 0 || im.arithmetic != 0) return blk;  // (libjpeg's built tables: its dummy blocks are blocks of their own)
     const uint32_t ny = im.luma_h * im.luma_v;
     const uint32_t mcu = blk / im.bpm, b = blk - mcu * im.bpm;
     if (b >= ny) return blk;

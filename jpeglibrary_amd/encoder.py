@@ -61,6 +61,22 @@ def description_header(desc):
     return rc, msg.value.decode("utf-8", "replace"), buf.raw[:n.value] if rc == 0 else b""
 
 
+def _coding_policy(coding, who="coding"):
+    """The check of EncodeBatch.set_coding_policy / encode_batch(coding=...), before any library call: the jpgpu_coding_policy value"""
+    if coding not in _capi.CODING_POLICIES:
+        raise ValueError("%s is 'standard', 'optimized' or 'progressive', not %r" % (who, coding))
+    return _capi.CODING_POLICIES.index(coding)
+
+
+def libjpeg_optimal_table(freq):
+    """Host only: libjpeg's jpeg_gen_optimal_table for 256 symbol counts -> (bits[16], values) of the DHT (jpgpu_libjpeg_optimal_table).
+    Counts that are all zero give the empty table, ([0] * 16, [])."""
+    f = np.ascontiguousarray(freq, dtype=np.uint32).reshape(256)
+    bits, values, n = (C.c_uint8 * 16)(), (C.c_uint8 * 256)(), C.c_int(0)
+    raise_for_status(_lib.jpgpu_libjpeg_optimal_table(f.ctypes.data, bits, values, C.byref(n)), b"jpgpu_libjpeg_optimal_table: bad argument")
+    return list(bits), list(values)[:n.value]
+
+
 def _blocks_of(w, h, luma, components):
     return (-(-w // (8 * luma[0]))) * (-(-h // (8 * luma[1]))) * (luma[0] * luma[1] + (2 if components == 3 else 0))
 
@@ -125,6 +141,22 @@ class EncodeBatch:
         self._libjpeg = policy == 1
         return self
 
+    def set_coding_policy(self, coding):
+        """Which entropy coding upload() and upload_tensors() plan with from here on, under arithmetic "libjpeg" only: "standard", the default
+        -- the Annex K tables, every stream what it was --, "optimized" -- byte for byte Pillow's Image.save(..., optimize=True): sequential,
+        Huffman tables built from the image by libjpeg's rule; takes restart_interval -- or "progressive" -- byte for byte Image.save(...,
+        progressive=True): SOF2, libjpeg's simple progression, a table built per scan (include/jpgpu.h, 4e).  An upload under "reference" with
+        another coding than "standard", and "progressive" with a restart interval, raise ArgumentException and leave the batch usable.  State
+        of the batch: it holds until set again.  ValueError, before the library is called, for any other value."""
+        self._check(_lib.jpgpu_encoder_set_coding_policy(self._h, _coding_policy(coding)))
+        return self
+
+    def coding(self, i):
+        """"standard", "optimized" or "progressive": what image i of the last upload was planned with"""
+        a = C.c_int()
+        raise_for_status(_lib.jpgpu_encoder_image_coding(self._h, i, C.byref(a)), b"jpgpu_encoder_image_coding: no such image")
+        return _capi.CODING_POLICIES[a.value]
+
     def arithmetic(self, i):
         """1 where image i of the last upload was planned with libjpeg's integer transform, else 0"""
         a = C.c_int()
@@ -135,14 +167,17 @@ class EncodeBatch:
         # (libjpeg: one component is a non-interleaved scan of single blocks, see jpgpu.h 4d)
         return (1, 1) if self._libjpeg and components == 1 else (luma[0], luma[1])
 
-    def upload(self, images, luma=(2, 2), quality=75, rgb=False, optimize_coding=False, restart_interval=0, arithmetic=None):
+    def upload(self, images, luma=(2, 2), quality=75, rgb=False, optimize_coding=False, restart_interval=0, arithmetic=None, coding=None):
         """images: list of uint8 arrays (H, W, 3) or (H, W) / (H, W, 1); with rgb=True also (H, W, 4) = Rgba32 pixels, the alpha byte
         stepped over like ConvertRgba32ToYCbCr8 does (the reference's EncoderBenchmark).  luma = sampling factors of the first component.
         optimize_coding = EncodeAction's switch: Huffman tables built from each image's own statistics.
         restart_interval = MCUs between restart markers (0 = none, as the reference's encoder; an extension, see jpgpu.h).
-        arithmetic = "reference" or "libjpeg": set_arithmetic_policy() first (None: the batch's policy as it stands)."""
+        arithmetic = "reference" or "libjpeg": set_arithmetic_policy() first (None: the batch's policy as it stands).
+        coding = "standard", "optimized" or "progressive": set_coding_policy() first (None: as it stands)."""
         if arithmetic is not None:
             self.set_arithmetic_policy(arithmetic)
+        if coding is not None:
+            self.set_coding_policy(coding)
         n = len(images)
         ptrs = (C.c_void_p * n)()
         params = (_capi.EncodeParams * n)()
@@ -181,7 +216,8 @@ class EncodeBatch:
         self._n = n
         return self
 
-    def upload_tensors(self, tensors, luma=(2, 2), quality=75, rgb=False, optimize_coding=False, restart_interval=0, layout=None, arithmetic=None):
+    def upload_tensors(self, tensors, luma=(2, 2), quality=75, rgb=False, optimize_coding=False, restart_interval=0, layout=None, arithmetic=None,
+                       coding=None):
         """upload() for pixels that are on the device already: torch uint8 tensors on the context's device, read where they are --
         no download, no permute, no copy (jpgpu_encoder_upload_device).  layout='chw' (the default: what decode_to_tensors returns) takes
         (3, H, W) or (1, H, W); layout='hwc' takes (H, W, 3), (H, W), (H, W, 1) and, with rgb=True, (H, W, 4) = Rgba32.  The other arguments
@@ -191,6 +227,8 @@ class EncodeBatch:
         references to the tensors until the next upload or close(), and they must not be written before encode() has returned."""
         if arithmetic is not None:
             self.set_arithmetic_policy(arithmetic)
+        if coding is not None:
+            self.set_coding_policy(coding)
         tensors = list(tensors)
         hwc = (layout or "chw") == "hwc"
         pixels, pixel_layout = _tensor_pixels(tensors, layout, self.ctx.device, lambda i, w, h, c: c in (1, 3) or (c == 4 and hwc and rgb))
@@ -320,21 +358,26 @@ class EncodeBatch:
             pass
 
 
-def encode_batch(images, luma=(2, 2), quality=75, rgb=False, ctx=None, optimize_coding=False, restart_interval=0, arithmetic="reference"):
-    """One-call helper: list of JPEG byte strings.  arithmetic="libjpeg": the files Pillow writes (EncodeBatch.set_arithmetic_policy)."""
+def encode_batch(images, luma=(2, 2), quality=75, rgb=False, ctx=None, optimize_coding=False, restart_interval=0, arithmetic="reference",
+                 coding="standard"):
+    """One-call helper: list of JPEG byte strings.  arithmetic="libjpeg": the files Pillow writes (EncodeBatch.set_arithmetic_policy);
+    with coding="optimized" / "progressive" those of optimize=True / progressive=True (EncodeBatch.set_coding_policy)."""
     _arithmetic_policy(arithmetic)  # (ValueError before a context is made)
-    b = EncodeBatch(ctx).upload(images, luma, quality, rgb, optimize_coding, restart_interval, arithmetic).encode()
+    _coding_policy(coding)
+    b = EncodeBatch(ctx).upload(images, luma, quality, rgb, optimize_coding, restart_interval, arithmetic, coding).encode()
     outs = [b.output(i) for i in range(len(b))]
     b.close()
     return outs
 
 
-def encode_tensors(tensors, luma=(2, 2), quality=75, rgb=True, ctx=None, optimize_coding=False, restart_interval=0, layout=None, arithmetic="reference"):
+def encode_tensors(tensors, luma=(2, 2), quality=75, rgb=True, ctx=None, optimize_coding=False, restart_interval=0, layout=None, arithmetic="reference",
+                   coding="standard"):
     """One-call helper for torch producers: uint8 tensors on the context's device (layout 'chw' by default: decode_to_tensors' output,
     R,G,B planes) -> list of JPEG byte strings.  The pixels are never downloaded; see EncodeBatch.upload_tensors.  arithmetic="libjpeg": the
-    files Pillow writes (EncodeBatch.set_arithmetic_policy)."""
+    files Pillow writes (EncodeBatch.set_arithmetic_policy), coding as in encode_batch."""
     _arithmetic_policy(arithmetic)  # (ValueError before a context is made)
-    b = EncodeBatch(ctx).upload_tensors(tensors, luma, quality, rgb, optimize_coding, restart_interval, layout, arithmetic).encode()
+    _coding_policy(coding)
+    b = EncodeBatch(ctx).upload_tensors(tensors, luma, quality, rgb, optimize_coding, restart_interval, layout, arithmetic, coding).encode()
     outs = [b.output(i) for i in range(len(b))]
     b.close()
     return outs
